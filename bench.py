@@ -11,7 +11,12 @@ rank, controls resident in HBM when the clock starts (`value`, as the bench cont
 With --gpus N > 1 the driver launches one process per GPU (torchrun env); the seed axis is
 sharded and each step ends with the path's single RCCL all-reduce of [sum cost, sum gradient].
 
-The line also carries, measured in the same run on rank 0:
+A plain run sets up, warms up, times --steps steps and prints the line; no kernel carries HIP
+events in it. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
+
+With --full the line also carries the per-kernel times (HIP events of the warm-up and of the
+roofline kernel in the timed steps), the roofline and HBM figures, and, measured in the same run
+on rank 0:
   host_to_host  the same evaluation through qocx_eval_schroedinger - FRESH controls from host
                 memory every step, costs + gradients + final states back in host memory (PCIe
                 inclusive; SURVEY.md 8d's "controls in, results out");
@@ -22,6 +27,7 @@ The line also carries, measured in the same run on rank 0:
                 model).
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
 """
 
 import argparse
@@ -406,12 +412,40 @@ def lindblad_secondary(engine, reps=5):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, engine, total_cost, total_grad):
+    """What the timed path computed in its last step, as DIR/<name>.npy in float64: the sums one
+    step returns (sum_cost [1], sum_grad [Nc, K]) and the per-seed results of this rank's seeds that
+    the evaluation left on the device (cost [B], grad [B, Nc, K], final_states [B, S, n, 2] as real
+    and imaginary parts). Above DUMP_LIMIT_BYTES the per-seed arrays keep the first seeds only."""
+    os.makedirs(directory, exist_ok=True)
+    cost, grads, final = engine.download_results(want_grad=True, want_final=True)
+    sums = {"sum_cost": np.array([total_cost]), "sum_grad": total_grad}
+    per_seed = {"cost": cost, "grad": grads}
+    if final is not None:
+        per_seed["final_states"] = np.stack([final.real, final.imag], axis=-1)
+    room = DUMP_LIMIT_BYTES - sum(np.asarray(a).size * 8 for a in sums.values())
+    seed_bytes = sum(np.asarray(a)[0].size * 8 for a in per_seed.values())
+    keep = max(1, min(len(cost), room // seed_bytes))
+    arrays = dict(sums, **{k: np.asarray(a)[:keep] for k, a in per_seed.items()})
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seeds-per-gpu", type=int, default=SEEDS_PER_GPU)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: per-kernel times, roofline "
+                         "and HBM figures, host_to_host, reference_order, the secondary / latency / "
+                         "general-path blocks and the CPU baseline (the --no-* options below thin it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference-order", action="store_true",
                     help="skip the extra pass with the Pade order pinned to 13 (profiling runs: the "
@@ -427,6 +461,9 @@ def main():
                     help="TESTS ONLY (tests/test_bench_main.py): a stand-in engine module in the "
                          "place of libqocx, to rehearse the multi-rank control flow without a GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
 
     from qoc_amd import parallel
     standin = args.standin_engine
@@ -466,19 +503,23 @@ def main():
         engine.eval_resident(True)
         return parallel.summed_results_resident(engine, comm)
 
-    # kernel timing (HIP events on the launch streams) is already on during the warm-up, so that
-    # the event pool and the runtime's signal pools exist before the clock starts
-    engine.set_timing(True)
+    # --full: kernel timing (HIP events on the launch streams) is already on during the warm-up, so
+    # that the event pool and the runtime's signal pools exist before the clock starts
+    if full:
+        engine.set_timing(True)
     for _ in range(3):  # set-up: first-touch of the result buffers, event / signal pools
         one_step()
-    engine.reset_timing()
+    if full:
+        engine.reset_timing()
     for _ in range(max(1, args.warmup)):
         one_step()
-    warm_timing = engine.timing()  # every kernel, from the warm-up steps
-    # inside the timed region only the roofline kernel carries events (two events on each of the
-    # ~45 launches of an evaluation cost 2-3 % of it)
-    engine.set_timing(True, only="pade_pq")
-    engine.reset_timing()
+    warm_timing = None
+    if full:
+        warm_timing = engine.timing()  # every kernel, from the warm-up steps
+        # inside the timed region only the roofline kernel carries events (two events on each of
+        # the ~45 launches of an evaluation cost 2-3 % of it)
+        engine.set_timing(True, only="pade_pq")
+        engine.reset_timing()
     comm.barrier()
     engine.synchronize()
     t0 = time.perf_counter()
@@ -491,12 +532,14 @@ def main():
     comm.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = float(comm.allreduce_max(np.array([elapsed]))[0])
-    timing = engine.timing()
+    timing = engine.timing() if full else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, total_cost, total_grad)
 
     # the same evaluation host buffer to host buffer (rank 0 of a single-GPU run): fresh controls
     # from host memory every step, costs + gradients + final states back in host memory
     host_to_host = None
-    if world == 1 and not standin:
+    if full and world == 1 and not standin:
         fresh = [make_controls(5000 + 300 * k, seeds) for k in range(3)]
         for warm in fresh:  # first-touch of the result staging on this route
             engine.evaluate(warm, want_grad=True)
@@ -514,7 +557,7 @@ def main():
     # the order pinned to 13, which is what the reference itself always executes
     orders = engine.pade_orders()
     reference_order = None
-    if world == 1 and not args.no_reference_order and not standin:
+    if full and world == 1 and not args.no_reference_order and not standin:
         engine.set_knob("pade_order", 13)
         one_step()
         engine.synchronize()
@@ -532,7 +575,7 @@ def main():
     secondary = None
     latency = None
     general = None
-    if world == 1 and not args.no_secondary and not standin:
+    if full and world == 1 and not args.no_secondary and not standin:
         engine.set_timing(True)
         secondary = lindblad_secondary(engine)
         latency = None if args.no_latency else latency_secondary(engine)
@@ -546,7 +589,7 @@ def main():
     # Pade chain per propagator step - 2 / 3 / 4 / 5 / 6 products for order 3 / 5 / 7 / 9 / 13, as
     # executed on this workload - at 8 real flops per complex MAC. The LU
     # factorisation fused into the kernel (8/3 n^3 VALU flops) is not counted.
-    launches, total_ms = timing["pade_pq"]
+    launches, total_ms = timing["pade_pq"] if full else (0, 0.0)
     products = {3: 2, 5: 3, 7: 4, 9: 5, 13: 6}
     steps_counted = max(1, sum(orders.values()))
     mean_products = sum(products[o] * c for o, c in orders.items()) / steps_counted
@@ -588,8 +631,10 @@ def main():
                                                 "--pmc pass ({}) over this run's launch time{}".format(
                                                     PMC_SQ_SUMMARY, stale_note))
             roofline["frac_executed_current"] = current
-    kernel_ms = {k: (v[1] / v[0] if v[0] else 0.0) for k, v in warm_timing.items()}
-    kernel_ms["pade_pq"] = total_ms / launches if launches else kernel_ms["pade_pq"]
+    kernel_ms = None
+    if full:
+        kernel_ms = {k: (v[1] / v[0] if v[0] else 0.0) for k, v in warm_timing.items()}
+        kernel_ms["pade_pq"] = total_ms / launches if launches else kernel_ms["pade_pq"]
     # The whole path under the BUILD'S OWN operation count (SURVEY.md 8d's
     # 21.33 n^3 is the count of the reference's formulation - U_j formed and squared, the dense
     # reverse rules of the tape - which this algorithm does not execute): per propagator step
@@ -604,9 +649,9 @@ def main():
     path_tflops = path_flops_per_unit * units_per_step * args.steps / elapsed / 1e12 / world
     # HBM traffic of one evaluation (committed PMC passes x this run's launch counts) over this
     # run's time per evaluation
-    per_eval_launches = {k: (v[0] / max(1, args.warmup)) for k, v in warm_timing.items()}
+    per_eval_launches = {k: (v[0] / max(1, args.warmup)) for k, v in (warm_timing or {}).items()}
     hbm = None
-    eval_bytes, eval_parts = pmc_evaluation_bytes(per_eval_launches) if all(
+    eval_bytes, eval_parts = pmc_evaluation_bytes(per_eval_launches) if full and all(
         k in per_eval_launches for k in EVAL_KERNELS) else (None, None)
     if eval_bytes is not None:
         tbs = eval_bytes / (elapsed / args.steps) / 1e12
@@ -636,7 +681,8 @@ def main():
         "roofline": roofline,
         "kernel_ms_per_launch": kernel_ms,
         "kernel_ms_source": "pade_pq: HIP events inside the timed region; the others: HIP events of "
-                            "the warm-up steps (all launches timed there)",
+                            "the warm-up steps (all launches timed there)" if full else None,
+        "full": full,
         "step_ms": step_ms,
         "flops_per_step_path": path_flops_per_unit,
         "path_tflops_per_gpu": path_tflops,
@@ -659,7 +705,7 @@ def main():
         "general_path": general,
     }
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not standin:
+        if full and world == 1 and not args.no_cpu_baseline and not standin:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     engine.close()

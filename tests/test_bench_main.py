@@ -81,3 +81,42 @@ def test_single_process_default_and_gpus_mismatch(tmp_path):
                            "tests.standin_engine"], env=env2, cwd=ROOT,
                           capture_output=True, text=True, timeout=300)
     assert bad2.returncode != 0 and "WORLD_SIZE=4" in (bad2.stderr + bad2.stdout)
+
+
+def _line(run):
+    assert run.returncode == 0, run.stderr[-2000:]
+    return json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one_full_adds_the_rest(tmp_path):
+    """A plain run: the headline only, --steps timed steps, --dump-outputs the last step's results
+    (the stand-in engine's cost sum(u^2) and gradient 2 u). --full adds the kernel figures."""
+    env = _env(tmp_path)
+    seeds = 2
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+            "--seeds-per-gpu", str(seeds), "--standin-engine", "tests.standin_engine"]
+    out = tmp_path / "out"
+    line = _line(subprocess.run(base + ["--dump-outputs", str(out)], env=env, cwd=ROOT,
+                                capture_output=True, text=True, timeout=300))
+    assert line["steps"] == 3 and len(line["step_ms"]) == 3 and line["full"] is False
+    assert line["ms_per_step"] > 0 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["roofline"] is None and line["kernel_ms_per_launch"] is None and line["hbm"] is None
+    assert "cpu_baseline" not in line
+    sys.path.insert(0, ROOT)
+    import bench
+    u = bench.make_controls(0, seeds)
+    dumped = {name: np.load(str(out / (name + ".npy"))) for name in ("sum_cost", "sum_grad", "cost", "grad")}
+    assert all(a.dtype == np.float64 for a in dumped.values())
+    assert abs(dumped["sum_cost"][0] - line["check"]["sum_cost"]) == 0.0
+    assert np.allclose(dumped["cost"], np.sum(u ** 2, axis=(1, 2)), rtol=1e-14, atol=0)
+    assert np.array_equal(dumped["grad"], 2.0 * u)
+    assert np.allclose(dumped["sum_grad"], 2.0 * u.sum(axis=0), rtol=1e-14, atol=1e-15)
+
+    full = _line(subprocess.run(base + ["--full"], env=env, cwd=ROOT, capture_output=True, text=True,
+                                timeout=300))
+    assert full["full"] is True and full["steps"] == 3
+    assert full["roofline"] is not None and full["kernel_ms_per_launch"]["pade_pq"] > 0
+
+    bad = subprocess.run(base + ["--steps", "0"], env=env, cwd=ROOT, capture_output=True, text=True,
+                         timeout=300)
+    assert bad.returncode != 0 and "--steps" in bad.stderr

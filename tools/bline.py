@@ -1,4 +1,4 @@
-"""print the interesting fields of a bench.py JSON line read from stdin (build tooling)"""
+"""print the interesting fields of a `bench.py --full` JSON line read from stdin (build tooling)"""
 import json
 import sys
 
