@@ -388,6 +388,40 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
                   double corr_2, int32_t apply_clip_grads, double clip_grads);
 int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out);
 
+/* ---- the same driver for the Lindblad problem --------------------------------------------------
+ * Multi-start Lindblad GRAPE (qoc/core/lindbladdiscrete.py:297-352 per seed) with controls, results,
+ * Adam moments and the best so far in HBM, apart from the Schroedinger state of the qocx_opt_* family
+ * (a context may hold both problems). The contract is that of qocx_opt_*; every array is in seed
+ * order. An evaluation is that of qocx_eval_lindblad on the same controls, bit for bit: each seed
+ * takes its sub-division count from the maxima |u_k| of ITS controls, seeds with equal counts run as
+ * one group, and the results go back to seed order on the device.
+ *   qocx_lindblad_upload_controls    controls [B][Nc][K] real into HBM (a problem with K >= 1).
+ *   qocx_eval_lindblad_resident      evaluate the resident controls (cost, gradients if want_grad,
+ *                                    final densities); no wait for the device.
+ *   qocx_lindblad_download_results   cost [B], gradients [B][Nc][K], final densities [B][S][n][n]
+ *                                    complex of the last resident evaluation; any pointer may be NULL.
+ *   qocx_lindblad_download_costs     the B costs alone (what the driver polls).
+ *   qocx_lindblad_opt_begin          zero the Adam moments, allocate the best-so-far buffers.
+ *   qocx_lindblad_opt_clip           clip_control_norms on the resident controls, in place; the
+ *                                    per-seed control maxima of the next evaluation's sub-division
+ *                                    come back with it (B K doubles; none on a fixed grid).
+ *   qocx_lindblad_opt_step           as qocx_opt_step: best controls / final densities of the flagged
+ *                                    seeds, then the SGD (kind 0) / Adam (kind 1) update.
+ *   qocx_lindblad_opt_download_best  best controls [B][Nc][K] and best final densities [B][S][n][n]
+ *                                    complex. */
+int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls);
+int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad);
+int qocx_lindblad_download_results(qocx_ctx* ctx, double* cost_out, double* grad_out,
+                                   double* final_out);
+int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out);
+int qocx_lindblad_opt_begin(qocx_ctx* ctx);
+int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms);
+int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
+                           const uint8_t* update, double learning_rate, double beta_1,
+                           double beta_2, double epsilon, double corr_1, double corr_2,
+                           int32_t apply_clip_grads, double clip_grads);
+int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out);
+
 /* ---- host-side helpers of the multi-start GRAPE driver (no GPU work, no context) --------------
  * The reference's driver loop clips the controls and applies its optimizer plugin to ONE control
  * set per process (qoc/core/common.py:8-30, qoc/standard/optimizers/adam.py:110-165, sgd.py). The

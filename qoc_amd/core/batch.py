@@ -1,0 +1,404 @@
+"""
+batch.py - the multi-start GRAPE loop shared by grape_schroedinger_discrete_batch and
+grape_lindblad_discrete_batch: B independent optimisations of one problem in lock step, one
+batched device evaluation per iteration.
+
+Seed b follows EXACTLY the iteration of the single-seed driver (the reference's
+schroedingerdiscrete.py:293-353 / lindbladdiscrete.py:297-352 per seed): clip -> conditions ->
+evaluate -> best-so-far (strict <) -> optimizer update with its own optimizer state, its own
+termination at error <= min_error (a finished seed is frozen). Two routes: the host loop (any
+evaluator, any step-wise optimizer plugin) and the device-resident one, where controls, gradients,
+Adam moments and the best so far stay in HBM and the host sees B costs per iteration.
+"""
+
+import numpy as np
+
+from qoc_amd.core.common import initialize_controls, strip_controls
+from qoc_amd.models import Dummy
+from qoc_amd.standard.optimizers import SGD, Adam
+
+
+class BatchResult(object):
+    """Per-seed bests of a multi-start driver; `best` is the overall winner as the single-seed
+    result class. With a communicator the arrays hold this rank's seeds and `global_best_error` the
+    minimum over all ranks. Subclasses name the single-seed result and its final-state field."""
+
+    single_result = None
+    final_field = None
+
+    def __init__(self, seed_count):
+        self.best_controls = [None] * seed_count
+        self.best_error = np.repeat(np.finfo(np.float64).max, seed_count)
+        setattr(self, self.final_field, [None] * seed_count)
+        self.best_iteration = np.full(seed_count, -1, dtype=np.int64)
+        self.iterations_run = np.zeros(seed_count, dtype=np.int64)
+        self.global_best_error = None
+
+    @property
+    def best(self):
+        b = int(np.argmin(self.best_error))
+        return self.single_result(
+            best_controls=self.best_controls[b], best_error=float(self.best_error[b]),
+            best_iteration=int(self.best_iteration[b]),
+            **{self.final_field: getattr(self, self.final_field)[b]})
+
+
+def _optimizer_clone(optimizer, flat_controls):
+    """A private copy of a step-wise optimizer plugin, initialised as its run() would."""
+    import copy
+    if not hasattr(optimizer, "update"):
+        raise NotImplementedError(
+            "the multi-start GRAPE drivers step the optimizer one update at a time and need its "
+            "update(grads, params) (Adam, SGD); {} only offers run().".format(optimizer))
+    clone = copy.deepcopy(optimizer)
+    if hasattr(clone, "gradient_moment"):  # Adam.run(), adam.py:83-88 of the reference
+        clone.iteration_count = 0
+        clone.gradient_moment = np.zeros_like(flat_controls)
+        clone.gradient_square_moment = np.zeros_like(flat_controls)
+    return clone
+
+
+# ---- the B optimizer states as [B, P] arrays ------------------------------------------------------
+# The per-seed loop (one plugin object per seed: slap / clip / strip / update = ~60 small NumPy
+# calls per seed and iteration) costs 13 ms of host time per iteration at B = 256, Nc = 1001,
+# K = 2 - as long as the device evaluation it wraps. For the built-in Adam and
+# SGD the same arithmetic runs on [rows, P] blocks: every operation is elementwise and in the
+# reference's order (adam.py:110-165, sgd.py), so seed b still walks exactly its single-seed
+# trajectory, bit for bit. Row blocks keep the temporaries cache resident.
+_ROW_BLOCK = 16
+_POOL = None
+
+
+def _row_blocks(rows):
+    """rows (sorted index array) as a list of slices where they are consecutive, index arrays
+    otherwise, at most _ROW_BLOCK rows each."""
+    out = []
+    for lo in range(0, len(rows), _ROW_BLOCK):
+        r = rows[lo:lo + _ROW_BLOCK]
+        out.append(slice(int(r[0]), int(r[-1]) + 1) if r[-1] - r[0] + 1 == len(r) else r)
+    return out
+
+
+def _for_blocks(work, blocks):
+    """work(block) for every block, on a small thread pool (NumPy releases the GIL inside its
+    loops; the blocks are disjoint rows)."""
+    global _POOL
+    if len(blocks) < 4:
+        for blk in blocks:
+            work(blk)
+        return
+    if _POOL is None:
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        _POOL = ThreadPoolExecutor(max_workers=max(1, min(8, (os.cpu_count() or 2) - 1)))
+    list(_POOL.map(work, blocks))
+
+
+_NATIVE_HOST = None
+
+
+def _native_ok(*arrays):
+    """The [B, P] host routines of libqocx (clip, Adam / SGD on host threads) can take these
+    arrays. Without the library (a CPU box running the host logic against the oracle backend)
+    the NumPy block path below each call site does the same arithmetic."""
+    global _NATIVE_HOST
+    if _NATIVE_HOST is None:
+        from qoc_amd import engine
+        try:
+            engine.load_library()
+            _NATIVE_HOST = True
+        except ImportError:  # the library FILE is absent: a CPU box running the host logic only
+            _NATIVE_HOST = False
+        # (a library that is present but does not load, or lacks a declared symbol, is a broken
+        # build: OSError / AttributeError propagate instead of silently taking the NumPy path)
+    return _NATIVE_HOST and all(a.dtype == np.float64 and a.flags.c_contiguous for a in arrays)
+
+
+class _BatchedSGD(object):
+    def __init__(self, optimizer, params):
+        self.learning_rate = optimizer.learning_rate
+
+    def update(self, grads, params, rows):
+        """params[rows] <- SGD.update(grads[rows], params[rows]), in place."""
+        if _native_ok(grads, params):
+            from qoc_amd import engine
+            engine.host_optimizer_update(0, params, grads, None, None, rows, self.learning_rate)
+            return
+
+        def work(r):
+            params[r] = params[r] - self.learning_rate * grads[r]
+        _for_blocks(work, _row_blocks(rows))
+
+
+class _BatchedAdam(object):
+    def __init__(self, optimizer, params):
+        self.o = optimizer
+        self.m = np.zeros_like(params)
+        self.v = np.zeros_like(params)
+        self.count = np.zeros(params.shape[0], dtype=np.int64)
+
+    def update(self, grads, params, rows):
+        """params[rows] <- Adam.update(grads[rows], params[rows]) with every seed's own moments and
+        step counter, in place: the operations of adam.py:110-165 in their order, element by
+        element (a * x + b * y is formed as (a * x) + (b * y) there and here)."""
+        o = self.o
+        for count in np.unique(self.count[rows]):  # (seeds that stopped earlier keep their own)
+            sel = rows[self.count[rows] == count]
+            if o.apply_learning_rate_decay:
+                learning_rate = (o.initial_learning_rate
+                                 * np.exp(-np.divide(count, o.learning_rate_decay)))
+            else:
+                learning_rate = o.initial_learning_rate
+            step = count + 1
+            corr_1 = 1 - np.power(o.beta_1, step)
+            corr_2 = 1 - np.power(o.beta_2, step)
+            if not o.apply_scale_grads and _native_ok(grads, params, self.m, self.v):
+                # the same operations on host threads of libqocx (qocx_host_optimizer_update)
+                from qoc_amd import engine
+                engine.host_optimizer_update(
+                    1, params, grads, self.m, self.v, sel, learning_rate, o.beta_1, o.beta_2,
+                    o.epsilon, corr_1, corr_2, o.clip_grads if o.apply_clip_grads else None)
+                self.count[sel] = step
+                continue
+
+            def work(r):
+                g = grads[r]
+                if o.apply_scale_grads:
+                    norms = np.array([np.linalg.norm(row) for row in g])
+                    g = (g / norms[:, None]) * o.scale_grads
+                if o.apply_clip_grads:
+                    g = np.clip(g, -o.clip_grads, o.clip_grads)
+                m, v = self.m[r], self.v[r]  # views for a slice, copies for an index array
+                t = np.multiply(g, 1 - o.beta_1)
+                np.multiply(m, o.beta_1, out=m)
+                m += t                                    # gradient_moment
+                np.square(g, out=t)
+                t *= (1 - o.beta_2)
+                np.multiply(v, o.beta_2, out=v)
+                v += t                                    # gradient_square_moment
+                if not isinstance(r, slice):
+                    self.m[r] = m
+                    self.v[r] = v
+                u = np.divide(v, corr_2)                  # square_hat
+                np.sqrt(u, out=u)
+                u += o.epsilon
+                np.divide(m, corr_1, out=t)               # moment_hat
+                np.divide(t, u, out=t)
+                t *= learning_rate
+                if isinstance(r, slice):
+                    p = params[r]
+                    p -= t
+                else:
+                    params[r] = params[r] - t
+            _for_blocks(work, _row_blocks(sel))
+            self.count[sel] = step
+
+
+def batched_stepper(optimizer, params):
+    """The [B, P] form of the built-in step-wise optimizers; None for any other plugin (those keep
+    one deep copy per seed and their own update())."""
+    if type(optimizer) is Adam:
+        return _BatchedAdam(optimizer, params)
+    if type(optimizer) is SGD:
+        return _BatchedSGD(optimizer, params)
+    return None
+
+
+def _cost_format_batch(params, pstate):
+    """_cost_format on all rows of params [B, P] at once: (B x Nc x K) controls, clipped in place
+    (a view of params for real controls, as in the single-seed driver), conditions per seed."""
+    B = params.shape[0]
+    shape = (B,) + tuple(pstate.controls_shape)
+    if pstate.complex_controls:
+        half = params.shape[1] // 2
+        controls = (params[:, :half] + 1j * params[:, half:]).reshape(shape)
+    else:
+        controls = params.reshape(shape)
+        if _native_ok(params) and controls.base is not None:
+            from qoc_amd import engine
+            engine.host_clip_controls(controls, pstate.max_control_norms)
+            if pstate.impose_control_conditions is not None:
+                controls = np.stack([pstate.impose_control_conditions(controls[b])
+                                     for b in range(B)])
+            return controls
+    for i, max_norm in enumerate(pstate.max_control_norms):  # clip_control_norms, all seeds
+        column = controls[:, :, i]
+        moduli = np.abs(column)
+        over = np.less(max_norm, moduli)
+        if over.any():
+            column[over] = (column[over] / moduli[over]) * max_norm
+    if pstate.impose_control_conditions is not None:
+        controls = np.stack([pstate.impose_control_conditions(controls[b]) for b in range(B)])
+    return controls
+
+
+def _strip_batch(complex_controls, arrays):
+    """strip_controls on every row: (B x Nc x K) -> [B, P]."""
+    flat = np.reshape(arrays, (arrays.shape[0], -1))
+    if complex_controls:
+        flat = np.hstack((np.real(flat), np.imag(flat)))
+    return flat
+
+
+def prepare_seeds(initial_controls, complex_controls, control_count, control_eval_count,
+                  evolution_time, max_control_norms, impose_control_conditions, comm):
+    """This rank's block of the seeds, checked as the single-seed drivers check one control array:
+    (comm, pstate for _cost_format_batch, params [B, P] in the optimizer's format)."""
+    from qoc_amd import parallel
+    initial_controls = np.asarray(initial_controls)
+    if initial_controls.ndim != 3:
+        raise ValueError("initial_controls must be (seed_count x control_eval_count x "
+                         "control_count), got shape {}".format(initial_controls.shape))
+    comm = comm if comm is not None else parallel.SingleComm()
+    lo, hi = parallel.shard_bounds(initial_controls.shape[0], comm.rank, comm.world)
+    if max_control_norms is None:  # the default of initialize_controls, also for a rank without seeds
+        max_control_norms = np.ones(control_count)
+    seeds = []
+    for b in range(lo, hi):
+        controls_b, max_control_norms = initialize_controls(
+            complex_controls, control_count, control_eval_count, evolution_time,
+            initial_controls[b], max_control_norms)
+        seeds.append(np.array(controls_b))
+    pstate = Dummy()
+    pstate.complex_controls = complex_controls
+    pstate.controls_shape = (control_eval_count, control_count)
+    pstate.max_control_norms = max_control_norms
+    pstate.impose_control_conditions = impose_control_conditions
+    params = (np.stack([strip_controls(complex_controls, c) for c in seeds]) if seeds
+              else np.zeros((0, control_eval_count * control_count)))
+    return comm, pstate, np.array(params, dtype=np.float64)
+
+
+def resident_route(stepper, optimizer, pstate, evaluator, batch):
+    """The device-resident loop applies: built-in Adam / SGD without scale_grads, no control
+    conditions, and an evaluator that can keep everything on the device."""
+    return (batch > 0 and stepper is not None and pstate.impose_control_conditions is None
+            and not getattr(optimizer, "apply_scale_grads", False)
+            and hasattr(evaluator, "resident_capable") and evaluator.resident_capable())
+
+
+def _log_header(log_iteration_step, comm):
+    if log_iteration_step != 0 and comm.rank == 0:
+        print("iter   |  summed error  |   min error    |  active seeds \n"
+              "===========================================================")
+
+
+def _finish(result, comm):
+    best_local = float(np.min(result.best_error)) if len(result.best_error) else np.inf
+    result.global_best_error = float(-comm.allreduce_max(np.array([-best_local]))[0])
+    return result
+
+
+def run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iteration_step,
+                       min_error, comm, result):
+    """The loop with everything but the decisions on the device: ops.opt_clip -> ops.eval_resident
+    -> B costs to the host -> ops.opt_step. `ops` is the engine's resident driver of one problem
+    (upload_controls, opt_begin, opt_clip, eval_resident, download_costs, opt_step,
+    opt_download_best -> (controls [B, Nc, K], finals in the result's shape))."""
+    B = params.shape[0]
+    is_adam = type(optimizer) is Adam
+    _log_header(log_iteration_step, comm)
+    ops.upload_controls(params.reshape((B,) + tuple(pstate.controls_shape)))
+    ops.opt_begin()
+    active = np.ones(B, dtype=bool)
+    count = 0  # optimizer steps taken so far (every active seed has taken all of them)
+    should_log = log_iteration_step != 0
+    for iteration in range(iteration_count):
+        ops.opt_clip(pstate.max_control_norms)
+        ops.eval_resident(True)
+        errors = ops.download_costs()
+        result.iterations_run[active] = iteration + 1
+        improved = active & (errors < result.best_error)  # strict, as the reference
+        result.best_error[improved] = errors[improved]
+        result.best_iteration[improved] = iteration
+        if should_log and (iteration % log_iteration_step == 0 or iteration == iteration_count - 1):
+            total = comm.allreduce_sum(np.array([float(np.sum(errors[active]))]))[0]
+            low = -comm.allreduce_max(np.array([-float(np.min(errors))]))[0]
+            seeds = comm.allreduce_sum(np.array([float(np.sum(active))]))[0]
+            if comm.rank == 0:
+                print("{:^6d} | {:^1.8e} | {:^1.8e} | {:^6d}".format(iteration, total, low,
+                                                                     int(seeds)))
+        active &= ~(errors <= min_error)
+        if is_adam:
+            o = optimizer
+            if o.apply_learning_rate_decay:
+                learning_rate = (o.initial_learning_rate
+                                 * np.exp(-np.divide(count, o.learning_rate_decay)))
+            else:
+                learning_rate = o.initial_learning_rate
+            step = count + 1
+            ops.opt_step(1, improved, active, learning_rate, o.beta_1, o.beta_2, o.epsilon,
+                         1 - np.power(o.beta_1, step), 1 - np.power(o.beta_2, step),
+                         o.clip_grads if o.apply_clip_grads else None)
+        else:
+            ops.opt_step(0, improved, active, optimizer.learning_rate)
+        count += 1
+        still = comm.allreduce_sum(np.array([float(np.sum(active))]))[0]
+        if still == 0:
+            break
+    best_controls, best_finals = ops.opt_download_best()
+    finals = getattr(result, result.final_field)
+    for b in range(B):
+        if result.best_iteration[b] >= 0:
+            result.best_controls[b] = best_controls[b]
+            finals[b] = best_finals[b]
+    return _finish(result, comm)
+
+
+def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_count,
+                   log_iteration_step, min_error, comm, result):
+    """The loop on the host: evaluator.evaluate_batch once per iteration, the [B, P] stepper of the
+    built-in optimizers or one deep copy of any other step-wise plugin per seed."""
+    B = params.shape[0]
+    shape = tuple(pstate.controls_shape)
+    optimizers = None if stepper is not None else [_optimizer_clone(optimizer, p) for p in params]
+    _log_header(log_iteration_step, comm)
+    active = np.ones(B, dtype=bool)
+    best_controls = best_finals = None
+    should_log = log_iteration_step != 0
+    for iteration in range(iteration_count):
+        # cost-function format of every seed (clipping acts in place on the optimizer's params
+        # for real controls, exactly as in the single-seed driver)
+        controls = _cost_format_batch(params, pstate)
+        if B > 0:
+            errors, grads, finals, _ = evaluator.evaluate_batch(controls, want_grad=True)
+        else:
+            errors, grads, finals = np.zeros(0), np.zeros((0,) + shape), np.zeros(0)
+        errors = np.asarray(errors)
+        result.iterations_run[active] = iteration + 1
+        improved = active & (errors < result.best_error)  # strict, as the reference
+        if improved.any():
+            if best_controls is None:
+                best_controls = np.zeros_like(controls)
+                best_finals = np.zeros_like(finals)
+            best_controls[improved] = controls[improved]
+            best_finals[improved] = finals[improved]
+            result.best_error[improved] = errors[improved]
+            result.best_iteration[improved] = iteration
+        if should_log and (iteration % log_iteration_step == 0 or iteration == iteration_count - 1):
+            local = np.array([float(np.sum(errors[active])) if B else 0.0])
+            total = comm.allreduce_sum(local)[0]
+            low = -comm.allreduce_max(np.array([-float(np.min(errors)) if B else -np.inf]))[0]
+            count = comm.allreduce_sum(np.array([float(np.sum(active))]))[0]
+            if comm.rank == 0:
+                print("{:^6d} | {:^1.8e} | {:^1.8e} | {:^6d}".format(iteration, total, low,
+                                                                     int(count)))
+        # a seed at error <= min_error ends its optimizer loop (terminate = True): frozen from here
+        active &= ~(errors <= min_error)
+        rows = np.nonzero(active)[0]
+        if len(rows):
+            flat_grads = _strip_batch(pstate.complex_controls, np.asarray(grads))
+            if stepper is not None:
+                stepper.update(flat_grads, params, rows)
+            else:
+                for b in rows:
+                    params[b] = optimizers[b].update(flat_grads[b], params[b])
+        still = comm.allreduce_sum(np.array([float(np.sum(active))]))[0]
+        if still == 0:
+            break
+    finals = getattr(result, result.final_field)
+    for b in range(B):
+        if result.best_iteration[b] >= 0:
+            result.best_controls[b] = best_controls[b]
+            finals[b] = best_finals[b]
+    return _finish(result, comm)

@@ -566,6 +566,17 @@ class LindbladEvaluator(object):
             old = np.zeros_like(need) if self._table_bounds is None else self._table_bounds
             self._set_time_dependent_problem(np.maximum(old, need))
 
+    def resident_capable(self):
+        """True when a multi-start driver may keep controls and optimizer states on the device
+        (engine.lindblad_opt_*): a Hamiltonian linear in real controls (time-dependent ones
+        included: their tables cover max_control_norms, which the driver's clip enforces), every
+        cost evaluated on the device, and a backend that has the entry points (the real engine)."""
+        return (self.linearized_hamiltonian is None and self._cost_controls is None
+                and not self.complex_controls and self.control_count > 0
+                and (not self.time_dependent or self._table_bounds is not None)
+                and not self.host_costs and not self.opaque_costs
+                and hasattr(self.backend, "lindblad_opt_step"))
+
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_densities=False):
         """
         controls_batch :: (B x Nc x K) (or None / an int B when control_count == 0).

@@ -1,5 +1,6 @@
 """
-lindbladdiscrete.py - evolve_lindblad_discrete and grape_lindblad_discrete.
+lindbladdiscrete.py - evolve_lindblad_discrete, grape_lindblad_discrete and its multi-start form
+grape_lindblad_discrete_batch.
 
 Same positional/keyword signatures, result objects, side effects (stdout table, save file) and
 optimizer-callback protocol as qoc/core/lindbladdiscrete.py:31-257. The integration of the
@@ -11,6 +12,7 @@ the parity tolerances that follow from replacing an adaptive integrator).
 
 import numpy as np
 
+from qoc_amd.core import batch
 from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
                                  strip_controls)
 from qoc_amd.core.device import LindbladEvaluator
@@ -138,3 +140,72 @@ def _eldj_wrap(controls, pstate, reporter, result):
     pstate.log_and_save(controls, error, final_densities, grads, reporter.iteration)
     reporter.iteration += 1
     return strip_controls(pstate.complex_controls, grads), bool(error <= pstate.min_error)
+
+
+# ---- multi-start GRAPE: B independent optimisations in lock step (core/batch.py) -----------------
+
+class GrapeLindbladBatchResult(batch.BatchResult):
+    """Per-seed bests of grape_lindblad_discrete_batch; `best` is the overall winner as a
+    GrapeLindbladResult. With a communicator the arrays hold this rank's seeds and
+    `global_best_error` the minimum over all ranks."""
+
+    single_result = GrapeLindbladResult
+    final_field = "best_final_densities"
+
+
+class _ResidentOps(object):
+    """engine.lindblad_* (the Lindblad problem's resident buffers) as the resident loop of
+    core/batch.py calls them."""
+
+    def __init__(self, engine):
+        self.upload_controls = engine.lindblad_upload_controls
+        self.opt_begin = engine.lindblad_opt_begin
+        self.opt_clip = engine.lindblad_opt_clip
+        self.eval_resident = engine.eval_lindblad_resident
+        self.download_costs = engine.lindblad_download_costs
+        self.opt_step = engine.lindblad_opt_step
+        self.opt_download_best = engine.lindblad_opt_download_best
+
+
+def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evolution_time,
+                                  initial_densities, system_eval_count, initial_controls,
+                                  complex_controls=False, cost_eval_step=1, hamiltonian=None,
+                                  impose_control_conditions=None,
+                                  interpolation_policy=InterpolationPolicy.LINEAR,
+                                  iteration_count=1000, lindblad_data=None, log_iteration_step=10,
+                                  max_control_norms=None, min_error=0, optimizer=Adam(),
+                                  comm=None):
+    """
+    Multi-start Lindblad GRAPE: B = len(initial_controls) independent optimisations of the same
+    problem, one batched device evaluation per iteration. Seed b follows EXACTLY the iteration of
+    grape_lindblad_discrete (reference lindbladdiscrete.py:297-352 per seed): clip -> conditions ->
+    evaluate -> best-so-far (strict <) -> optimizer update with its own optimizer state, its own
+    termination at error <= min_error (a finished seed is frozen; the batch ends when every seed
+    has finished or after iteration_count iterations).
+
+    Arguments as grape_lindblad_discrete without the save-file ones; initial_controls ::
+    (B x control_eval_count x control_count), each conforming to max_control_norms. comm
+    (qoc_amd.parallel communicator, optional): the seed axis is sharded over its ranks, result
+    arrays are rank local. With real controls, device costs, a Hamiltonian linear in the controls,
+    the built-in Adam / SGD and no control conditions, controls, gradients, optimizer states and the
+    best so far stay in HBM (qocx_lindblad_opt_*); otherwise the host drives
+    LindbladEvaluator.evaluate_batch. Both routes give the same numbers.
+    Returns GrapeLindbladBatchResult.
+    """
+    comm, pstate, params = batch.prepare_seeds(
+        initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
+        max_control_norms, impose_control_conditions, comm)
+    B = params.shape[0]
+    evaluator = LindbladEvaluator(
+        evolution_time, initial_densities, system_eval_count, hamiltonian=hamiltonian,
+        lindblad_data=lindblad_data, control_count=control_count,
+        control_eval_count=control_eval_count, complex_controls=complex_controls, costs=costs,
+        cost_eval_step=cost_eval_step, interpolation_policy=interpolation_policy,
+        need_gradients=True, control_bounds=pstate.max_control_norms)
+    stepper = batch.batched_stepper(optimizer, params)
+    result = GrapeLindbladBatchResult(B)
+    run = (iteration_count, log_iteration_step, min_error, comm, result)
+    if batch.resident_route(stepper, optimizer, pstate, evaluator, B):
+        return batch.run_batch_resident(_ResidentOps(evaluator.backend), optimizer, params, pstate,
+                                        *run)
+    return batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)

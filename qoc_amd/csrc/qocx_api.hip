@@ -289,6 +289,18 @@ struct qocx_ctx {
         int dbg_wave_mode = 0;           // 0 auto, 1 one wave per seed, 2 several whenever built for
         DevBuf<double2> a0_tab, gp_tab, op_tab;
         DevBuf<double> gamma_tab;
+        // multi-start driver on the device (qocx_lindblad_upload_controls / _opt_*): controls and
+        // results in seed order, apart from the evaluation's buffers above (group order)
+        int res_B = 0, opt_batch = 0;
+        bool res_have_results = false, res_have_grads = false;
+        bool umax_valid = false;          // umax_host holds the control maxima of res_controls
+        std::vector<double> umax_host;    // [B][K]
+        DevBuf<double> res_controls, res_cost, res_grads, umax;
+        DevBuf<double2> res_final;        // [B][S] dumps
+        DevBuf<int> order_dev;            // lb.order on the device
+        DevBuf<double> opt_m, opt_v, opt_best_controls, opt_max_norms;
+        DevBuf<double2> opt_best_final;
+        DevBuf<unsigned char> opt_flags;  // [2][B]: improved | update
     } lb;
     // ---- qocx_debug_set_knob: kernel-variant switches for A/B measurements and tests ----
     std::map<std::string, int64_t> knobs;
@@ -615,6 +627,13 @@ int qocx_destroy(qocx_ctx* ctx) {
         lb.scratch.release();
         lb.a0_tab.release();
         lb.gp_tab.release();
+        DevBuf<double>* r1[] = {&lb.res_controls, &lb.res_cost, &lb.res_grads, &lb.umax, &lb.opt_m,
+                                &lb.opt_v, &lb.opt_best_controls, &lb.opt_max_norms};
+        for (auto* b : r1) b->release();
+        lb.res_final.release();
+        lb.opt_best_final.release();
+        lb.order_dev.release();
+        lb.opt_flags.release();
     }
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (auto st : ctx->sweep_streams) (void)hipStreamDestroy(st);
@@ -2413,6 +2432,8 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.grids.clear();
     lb.has_problem = true;
     lb.have_results = false;
+    lb.res_B = lb.opt_batch = 0;  // resident controls and optimizer states belong to the old problem
+    lb.res_have_results = false;
     lb.inj_count = 0;
     return 0;
 }
@@ -2525,43 +2546,39 @@ int qocx_lindblad_stage_times(double evolution_time, int32_t system_eval_count,
     return 0;
 }
 
-int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int32_t want_grad,
-                       double* cost_out, double* grad_out, double* final_out) {
-    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
-    auto& lb = ctx->lb;
-    if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set");
-    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = batch;
-    const size_t md = dump_elems(n);
-    want_grad = (want_grad && K > 0) ? 1 : 0;
-    if (K > 0 && !controls) return fail(QOCX_ERR_ARG, "controls is NULL");
-    const bool trace_host = qocx::diag_getenv("QOCX_TRACE_HOST") != nullptr;
-    auto now_ms = [] {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-    };
-    const double t_enter = now_ms();
-    double t_alloc = 0, t_enq = 0, t_sync = 0;
+extern "C++" {
+namespace {
 
-    // Each seed picks its own sub-division count from ITS controls (|| Liouvillian || * length
-    // <= 0.4 per sub-interval), so a seed's result never depends on its batch neighbours. Seeds
-    // with equal counts are evaluated together: `order` lists the seeds group by group.
-    std::vector<int> ksub_of(B);
-    for (int b = 0; b < B; ++b) {
-        // || Liouvillian ||_2 <= || control-free part ||_2 + sum_k |u_k| 2 ||G_k||_2; with a
-        // time-dependent Hamiltonian / lindblad_data (tables) the control-free part is bounded by
-        // the sum of its parts' bounds over the samples
-        double ctl = 0;
+// ---- qocx_eval_lindblad in three parts, shared with the resident driver (qocx_lindblad_*) ----------
+
+// max_i |controls[b][i][k]| -> umax[b][k], in knot order (a NaN is carried as lindblad_subdivisions
+// expects; control_maxima_kernel of qocx_optim.hip is the same scan on the device)
+void lindblad_control_maxima(const double* controls, int B, int nc, int K, double* umax) {
+    for (int b = 0; b < B; ++b)
         for (int k = 0; k < K; ++k) {
             double um = 0;
             for (int i = 0; i < nc; ++i) {
                 const double a = fabs(controls[((size_t)b * nc + i) * K + k]);
                 if (!(a <= um)) um = a;
             }
-            ctl += um * lb.g_norm[k];
+            umax[(size_t)b * K + k] = um;
         }
+}
+
+// Each seed picks its own sub-division count from ITS controls (|| Liouvillian || * length <= 0.4
+// per sub-interval), so a seed's result never depends on its batch neighbours. umax: [B][K] control
+// maxima of the seeds; NULL with a fixed sub-division only (every seed then takes that one, unchecked).
+int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<int>& ksub_of) {
+    auto& lb = ctx->lb;
+    const int K = lb.K, nsteps = lb.nsteps;
+    ksub_of.assign(B, lb.fixed_ksub);
+    if (!umax) return lb.fixed_ksub > 0 ? 0 : fail(QOCX_ERR_STATE, "no control maxima");
+    for (int b = 0; b < B; ++b) {
+        // || Liouvillian ||_2 <= || control-free part ||_2 + sum_k |u_k| 2 ||G_k||_2; with a
+        // time-dependent Hamiltonian / lindblad_data (tables) the control-free part is bounded by
+        // the sum of its parts' bounds over the samples
+        double ctl = 0;
+        for (int k = 0; k < K; ++k) ctl += umax[(size_t)b * K + k] * lb.g_norm[k];
         const double base = lb.fixed_ksub > 0 ? 2 * lb.h0_norm + 2 * lb.diss_norm : lb.l0_norm;
         const double bound = base + 2 * ctl;
         if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or operators");
@@ -2577,7 +2594,23 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
             ksub_of[b] = lb.fixed_ksub;
         }
     }
+    return 0;
+}
+
+// What an evaluation of these sub-division counts launches: seeds with equal counts are evaluated
+// together (`lb.order` lists the seeds group by group), the grid tables and the evaluation's
+// buffers for them.
+struct LindbladPlan {
     std::map<int, std::vector<int>> groups;
+    size_t stage_budget = 0;  // double2 elements
+    bool two_sided_ok = false, two_sided_tiles = false;
+};
+
+int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of, LindbladPlan& plan) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = (int)ksub_of.size();
+    const size_t md = dump_elems(n);
+    auto& groups = plan.groups;
     for (int b = 0; b < B; ++b) groups[ksub_of[b]].push_back(b);
     if (lb.grids.size() > 64) {  // bounded cache of sub-interval tables
         for (auto& kv : lb.grids) {
@@ -2609,14 +2642,14 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
     // (n > 16: the tile-per-wave kernel of qocx_lindblad4t.hip in its phases, constant tables only)
     const bool two_sided_small = n <= 16 && lb.nops >= 1 && lb.multi_wave && !lb.global_scratch &&
                                  lb.dbg_wave_mode != 1;
-    const bool two_sided_tiles = n > 16 && ctx->knob("lindblad_4t", 1) != 0 && lb.nops <= 4;
-    const bool two_sided_ok = want_grad && lb.unit_ok && lb.inj_count == 0 &&
+    const bool two_sided_tiles = plan.two_sided_tiles = n > 16 && ctx->knob("lindblad_4t", 1) != 0 && lb.nops <= 4;
+    const bool two_sided_ok = plan.two_sided_ok = want_grad && lb.unit_ok && lb.inj_count == 0 &&
                               (two_sided_small || two_sided_tiles) && lb.fixed_ksub == 0 &&
                               (int)ctx->sweep_streams.size() >= 1 &&
                               ctx->knob("lindblad_two_sided", 1) != 0;
     if (two_sided_ok)
         if (lb.lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
-    size_t stage_budget = 0;  // double2 elements
+    size_t& stage_budget = plan.stage_budget;
     if (want_grad) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -2646,24 +2679,18 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
         return QOCX_ERR_HIP;
     if (ctx->keep_step_states)
         if (lb.step_densities.ensure((size_t)B * (nsteps + 1) * S * md)) return QOCX_ERR_HIP;
-    if (K > 0) {
-        // gathered group by group into the pinned staging buffer (a pageable source of 2 MB costs
-        // the copy 10-25 ms of page pinning per call at 256 seeds; from pinned memory it is a DMA)
-        const size_t total = (size_t)B * csz;
-        if (ctx->pin_controls_cap < total) {
-            if (ctx->pin_controls) (void)hipHostFree(ctx->pin_controls);
-            ctx->pin_controls = nullptr;
-            ctx->pin_controls_cap = 0;
-            HIP_TRY(hipHostMalloc((void**)&ctx->pin_controls, total * sizeof(double), hipHostMallocDefault));
-            ctx->pin_controls_cap = total;
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // nothing in flight still reads the staging buffer
-        for (int pos = 0; pos < B; ++pos)
-            memcpy(ctx->pin_controls + (size_t)pos * csz, controls + (size_t)lb.order[pos] * csz,
-                   csz * sizeof(double));
-        HIP_TRY(hipMemcpyAsync(lb.controls.p, ctx->pin_controls, total * sizeof(double),
-                               hipMemcpyHostToDevice, ctx->stream));
-    }
+    return 0;
+}
+
+// The launches group by group, piece by piece: results in lb.cost_out / grads / final_out in group
+// order. The controls are in lb.controls, in group order, on ctx->stream before this.
+int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& plan) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = (int)lb.order.size();
+    const size_t md = dump_elems(n), csz = (size_t)nc * K;
+    const size_t stage_budget = plan.stage_budget;
+    const bool two_sided_ok = plan.two_sided_ok;
+    const bool two_sided_tiles = plan.two_sided_tiles;
     if (lb.inj_count > 0) {
         if (lb.inj_batch != B)
             return fail(QOCX_ERR_STATE, "density cotangents were set for a different batch size");
@@ -2680,9 +2707,8 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
         if (lb.inj_index.upload(index, ctx->stream) || lb.inj_bars.upload(dumps, ctx->stream))
             return QOCX_ERR_HIP;
     }
-    t_alloc = now_ms();
     size_t pos0 = 0, ckpt_off = 0, gsub_off = 0;
-    for (auto& kv : groups) {
+    for (auto& kv : plan.groups) {
         const auto& gr = lb.grids[kv.first];
         const int Bg = (int)kv.second.size(), nsub = gr.nsub;
         const size_t per_seed_stage = (size_t)nsub * S * md * 12;
@@ -2806,6 +2832,61 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
         }
     }
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int32_t want_grad,
+                       double* cost_out, double* grad_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set");
+    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, B = batch;
+    const size_t md = dump_elems(n);
+    want_grad = (want_grad && K > 0) ? 1 : 0;
+    if (K > 0 && !controls) return fail(QOCX_ERR_ARG, "controls is NULL");
+    const bool trace_host = qocx::diag_getenv("QOCX_TRACE_HOST") != nullptr;
+    auto now_ms = [] {
+        timespec ts;
+        clock_gettime(CLOCK_MONOTONIC, &ts);
+        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+    };
+    const double t_enter = now_ms();
+    double t_alloc = 0, t_enq = 0, t_sync = 0;
+
+    std::vector<double> umax(std::max<size_t>(1, (size_t)B * K));
+    lindblad_control_maxima(controls, B, nc, K, umax.data());
+    std::vector<int> ksub_of;
+    LindbladPlan plan;
+    int rc = lindblad_subdivisions(ctx, B, umax.data(), ksub_of);
+    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
+    if (rc) return rc;
+    const size_t csz = (size_t)nc * K;
+    if (K > 0) {
+        // gathered group by group into the pinned staging buffer (a pageable source of 2 MB costs
+        // the copy 10-25 ms of page pinning per call at 256 seeds; from pinned memory it is a DMA)
+        const size_t total = (size_t)B * csz;
+        if (ctx->pin_controls_cap < total) {
+            if (ctx->pin_controls) (void)hipHostFree(ctx->pin_controls);
+            ctx->pin_controls = nullptr;
+            ctx->pin_controls_cap = 0;
+            HIP_TRY(hipHostMalloc((void**)&ctx->pin_controls, total * sizeof(double), hipHostMallocDefault));
+            ctx->pin_controls_cap = total;
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // nothing in flight still reads the staging buffer
+        for (int pos = 0; pos < B; ++pos)
+            memcpy(ctx->pin_controls + (size_t)pos * csz, controls + (size_t)lb.order[pos] * csz,
+                   csz * sizeof(double));
+        HIP_TRY(hipMemcpyAsync(lb.controls.p, ctx->pin_controls, total * sizeof(double),
+                               hipMemcpyHostToDevice, ctx->stream));
+    }
+    t_alloc = now_ms();
+    rc = lindblad_launch_groups(ctx, want_grad, plan);
+    if (rc) return rc;
     t_enq = now_ms();
     std::vector<double2> fin(final_out ? (size_t)B * S * md : 0);
     std::vector<double> cst(B), grd(want_grad && grad_out ? (size_t)B * csz : 0);
@@ -3152,6 +3233,210 @@ int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_ou
                 final_out[2 * (v * n + i)] = fin[v * np + i].x;
                 final_out[2 * (v * n + i) + 1] = fin[v * np + i].y;
             }
+    return 0;
+}
+
+// ---- the Lindblad multi-start driver: resident controls, results and optimizer states ------------
+
+int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
+    if (!ctx || !controls) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.K < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_upload_controls needs a Lindblad problem with controls");
+    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    const size_t csz = (size_t)lb.nc * lb.K;
+    if (csz > 65535u * 256u) return fail(QOCX_ERR_ARG, "control arrays too large for the driver kernels' grids");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (lb.res_controls.ensure((size_t)batch * csz)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(lb.res_controls.p, controls, (size_t)batch * csz * sizeof(double),
+                           hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // controls is the caller's memory
+    // the host has these controls: their maxima cost nothing here and spare eval_resident a round trip
+    lb.umax_host.assign((size_t)batch * lb.K, 0.0);
+    lindblad_control_maxima(controls, batch, lb.nc, lb.K, lb.umax_host.data());
+    lb.umax_valid = true;
+    lb.res_B = batch;
+    lb.res_have_results = false;
+    return 0;
+}
+
+int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "no resident Lindblad controls (qocx_lindblad_upload_controls)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, K = lb.K, S = lb.S;
+    const size_t csz = (size_t)lb.nc * K, md = dump_elems(lb.n);
+    want_grad = want_grad ? 1 : 0;
+    lb.res_have_results = false;
+    // the sub-division decision needs the control maxima on the host, except on a fixed grid
+    if (lb.fixed_ksub == 0 && !lb.umax_valid) {
+        if (lb.umax.ensure((size_t)B * K)) return QOCX_ERR_HIP;
+        lb.umax_host.resize((size_t)B * K);
+        qocx::launch_control_maxima(lb.res_controls.p, B, lb.nc, K, lb.umax.p, ctx->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(lb.umax_host.data(), lb.umax.p, (size_t)B * K * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        lb.umax_valid = true;
+    }
+    std::vector<int> ksub_of;
+    LindbladPlan plan;
+    int rc = lindblad_subdivisions(ctx, B, lb.fixed_ksub == 0 ? lb.umax_host.data() : nullptr, ksub_of);
+    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
+    if (rc) return rc;
+    if (lb.res_cost.ensure(B) || lb.res_grads.ensure((size_t)B * csz) ||
+        lb.res_final.ensure((size_t)B * S * md) || lb.order_dev.upload(lb.order, ctx->stream))
+        return QOCX_ERR_HIP;
+    // seed order -> group order: the device-side form of qocx_eval_lindblad's staging copy
+    qocx::launch_gather_seeds(lb.res_controls.p, lb.controls.p, csz, lb.order_dev.p, B, ctx->stream);
+    rc = lindblad_launch_groups(ctx, want_grad, plan);
+    if (rc) return rc;
+    qocx::launch_scatter_seeds(lb.cost_out.p, lb.res_cost.p, want_grad ? lb.grads.p : nullptr,
+                               lb.res_grads.p, csz, lb.final_out.p, lb.res_final.p, (size_t)S * md,
+                               lb.order_dev.p, B, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    if (ctx->timing) {  // (the events of the launches are read once they have run)
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        time_collect(ctx);
+    }
+    lb.B = B;
+    lb.have_results = true;
+    lb.have_steps = ctx->keep_step_states != 0;
+    lb.res_have_results = true;
+    lb.res_have_grads = want_grad != 0;
+    return 0;
+}
+
+int qocx_lindblad_download_results(qocx_ctx* ctx, double* cost_out, double* grad_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.res_have_results) return fail(QOCX_ERR_STATE, "no resident Lindblad evaluation results");
+    if (grad_out && !lb.res_have_grads) return fail(QOCX_ERR_STATE, "the last evaluation had no gradients");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, S = lb.S, n = lb.n;
+    const size_t csz = (size_t)lb.nc * lb.K, md = dump_elems(n);
+    if (cost_out)
+        HIP_TRY(hipMemcpyAsync(cost_out, lb.res_cost.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (grad_out)
+        HIP_TRY(hipMemcpyAsync(grad_out, lb.res_grads.p, (size_t)B * csz * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double2> fin(final_out ? (size_t)B * S * md : 0);
+    if (final_out)
+        HIP_TRY(hipMemcpyAsync(fin.data(), lb.res_final.p, fin.size() * sizeof(double2), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (final_out)
+        for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
+    return 0;
+}
+
+int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out) {
+    if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    return qocx_lindblad_download_results(ctx, cost_out, nullptr, nullptr);
+}
+
+int qocx_lindblad_opt_begin(qocx_ctx* ctx) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin needs resident Lindblad controls");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t total = (size_t)lb.res_B * lb.nc * lb.K;
+    if (lb.opt_m.ensure(total) || lb.opt_v.ensure(total) || lb.opt_best_controls.ensure(total) ||
+        lb.opt_best_final.ensure((size_t)lb.res_B * lb.S * dump_elems(lb.n)) ||
+        lb.opt_flags.ensure(2 * (size_t)lb.res_B) || lb.opt_max_norms.ensure((size_t)lb.K))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipMemsetAsync(lb.opt_m.p, 0, total * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(lb.opt_v.p, 0, total * sizeof(double), ctx->stream));
+    lb.opt_batch = lb.res_B;
+    return 0;
+}
+
+int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
+    if (!ctx || !max_norms) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (lb.opt_batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    for (int k = 0; k < lb.K; ++k)
+        if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, K = lb.K;
+    HIP_TRY(hipMemcpyAsync(lb.opt_max_norms.p, max_norms, K * sizeof(double), hipMemcpyHostToDevice,
+                           ctx->stream));
+    qocx::launch_clip_controls(lb.res_controls.p, (size_t)B * lb.nc * K, K, lb.opt_max_norms.p, ctx->stream);
+    // the maxima of the clipped controls decide the next evaluation's sub-divisions: they come back
+    // with the synchronisation the clip needs anyway (none on a fixed grid)
+    const bool maxima = lb.fixed_ksub == 0;
+    if (maxima) {
+        if (lb.umax.ensure((size_t)B * K)) return QOCX_ERR_HIP;
+        lb.umax_host.resize((size_t)B * K);
+        qocx::launch_control_maxima(lb.res_controls.p, B, lb.nc, K, lb.umax.p, ctx->stream);
+        HIP_TRY(hipMemcpyAsync(lb.umax_host.data(), lb.umax.p, (size_t)B * K * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
+    lb.umax_valid = maxima;
+    lb.res_have_results = false;
+    return 0;
+}
+
+int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const uint8_t* update,
+                           double learning_rate, double beta_1, double beta_2, double epsilon,
+                           double corr_1, double corr_2, int32_t apply_clip_grads, double clip_grads) {
+    if (!ctx || !improved || !update) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (kind != 0 && kind != 1) return fail(QOCX_ERR_ARG, "kind must be 0 (SGD) or 1 (Adam)");
+    auto& lb = ctx->lb;
+    if (lb.opt_batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    if (!lb.res_have_results || !lb.res_have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B;
+    const size_t per_seed = (size_t)lb.nc * lb.K;
+    HIP_TRY(hipMemcpyAsync(lb.opt_flags.p, improved, B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(lb.opt_flags.p + B, update, B, hipMemcpyHostToDevice, ctx->stream));
+    qocx::launch_keep_best(lb.res_controls.p, lb.opt_best_controls.p, per_seed, lb.res_final.p,
+                           lb.opt_best_final.p, (size_t)lb.S * dump_elems(lb.n), lb.opt_flags.p, B,
+                           ctx->stream);
+    qocx::OptimArgs a;
+    a.kind = kind;
+    a.params = lb.res_controls.p; a.grads = lb.res_grads.p;
+    a.moment = lb.opt_m.p; a.square_moment = lb.opt_v.p;
+    a.update = lb.opt_flags.p + B;
+    a.per_seed = per_seed;
+    a.learning_rate = learning_rate; a.beta_1 = beta_1; a.beta_2 = beta_2;
+    a.one_m_b1 = 1 - beta_1; a.one_m_b2 = 1 - beta_2;
+    a.epsilon = epsilon; a.corr_1 = corr_1; a.corr_2 = corr_2;
+    a.clip = clip_grads; a.apply_clip = apply_clip_grads ? 1 : 0;
+    qocx::launch_optimizer_update(a, B, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the flag arrays are the caller's memory
+    lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
+    lb.umax_valid = false;
+    return 0;
+}
+
+int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (lb.opt_batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, S = lb.S, n = lb.n;
+    const size_t md = dump_elems(n);
+    if (controls_out)
+        HIP_TRY(hipMemcpyAsync(controls_out, lb.opt_best_controls.p, (size_t)B * lb.nc * lb.K * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double2> fin(final_out ? (size_t)B * S * md : 0);
+    if (final_out)
+        HIP_TRY(hipMemcpyAsync(fin.data(), lb.opt_best_final.p, fin.size() * sizeof(double2),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (final_out)
+        for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
     return 0;
 }
 

@@ -398,6 +398,13 @@ void launch_keep_best(const double* controls, double* best_controls, size_t per_
                       const double2* final_states, double2* best_final, size_t final_per_seed,
                       const unsigned char* improved, int batch, hipStream_t st);
 void launch_optimizer_update(const OptimArgs& a, int batch, hipStream_t st);
+// the Lindblad multi-start driver: per-seed control maxima, seed order <-> sub-division group order
+void launch_control_maxima(const double* controls, int batch, int nc, int k, double* umax, hipStream_t st);
+void launch_gather_seeds(const double* src, double* dst, size_t per_seed, const int* order, int batch,
+                         hipStream_t st);
+void launch_scatter_seeds(const double* cost, double* cost_out, const double* grads, double* grads_out,
+                          size_t grad_per_seed, const double2* final_states, double2* final_out,
+                          size_t final_per_seed, const int* order, int batch, hipStream_t st);
 
 void launch_lindblad(const LindbladArgs& a, int batch, hipStream_t st);
 void launch_lindblad_combine(const LindbladArgs& a, int batch, hipStream_t st);

@@ -57,6 +57,64 @@ __global__ void optimizer_update_kernel(OptimArgs a) {
     a.params[e] = a.params[e] - s;
 }
 
+// ---- the Lindblad multi-start driver (qocx_lindblad_*): resident controls and results in seed
+// order, the evaluation's buffers in sub-division group order (device position -> seed: order[]).
+
+// umax[b][k] = max_i |controls[b][i][k]|, scanned in knot order with the host's update rule of
+// qocx_eval_lindblad (`if (!(a <= um)) um = a;`), so a NaN is carried exactly as the host carries it
+__global__ void control_maxima_kernel(const double* controls, int batch, int nc, int k, double* umax) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= batch * k) return;
+    const int b = idx / k, kk = idx % k;
+    const double* u = controls + (size_t)b * nc * k + kk;
+    double um = 0;
+    for (int i = 0; i < nc; ++i) {
+        const double a = fabs(u[(size_t)i * k]);
+        if (!(a <= um)) um = a;
+    }
+    umax[idx] = um;
+}
+
+// dst[pos] = src[order[pos]], per_seed doubles per seed
+__global__ void gather_seeds_kernel(const double* src, double* dst, size_t per_seed, const int* order) {
+    const size_t pos = blockIdx.x;
+    const size_t idx = (size_t)blockIdx.y * blockDim.x + threadIdx.x;
+    if (idx < per_seed) dst[pos * per_seed + idx] = src[(size_t)order[pos] * per_seed + idx];
+}
+
+// the results of position pos go to seed order[pos]: cost, gradients, final-density dumps
+__global__ void scatter_seeds_kernel(const double* cost, double* cost_out, const double* grads,
+                                     double* grads_out, size_t grad_per_seed, const double2* final_states,
+                                     double2* final_out, size_t final_per_seed, const int* order) {
+    const size_t pos = blockIdx.x, b = (size_t)order[pos];
+    const size_t idx = (size_t)blockIdx.y * blockDim.x + threadIdx.x;
+    if (idx == 0) cost_out[b] = cost[pos];
+    if (grads && idx < grad_per_seed) grads_out[b * grad_per_seed + idx] = grads[pos * grad_per_seed + idx];
+    if (idx < final_per_seed) final_out[b * final_per_seed + idx] = final_states[pos * final_per_seed + idx];
+}
+
+void launch_control_maxima(const double* controls, int batch, int nc, int k, double* umax, hipStream_t st) {
+    if (batch <= 0 || k <= 0) return;
+    hipLaunchKernelGGL(control_maxima_kernel, dim3((unsigned)((batch * k + 63) / 64)), dim3(64), 0, st,
+                       controls, batch, nc, k, umax);
+}
+void launch_gather_seeds(const double* src, double* dst, size_t per_seed, const int* order, int batch,
+                         hipStream_t st) {
+    if (batch <= 0 || per_seed == 0) return;
+    hipLaunchKernelGGL(gather_seeds_kernel, dim3(batch, (unsigned)((per_seed + 255) / 256)), dim3(256), 0,
+                       st, src, dst, per_seed, order);
+}
+void launch_scatter_seeds(const double* cost, double* cost_out, const double* grads, double* grads_out,
+                          size_t grad_per_seed, const double2* final_states, double2* final_out,
+                          size_t final_per_seed, const int* order, int batch, hipStream_t st) {
+    size_t widest = final_per_seed > 1 ? final_per_seed : 1;
+    if (grads && grad_per_seed > widest) widest = grad_per_seed;
+    if (batch <= 0) return;
+    hipLaunchKernelGGL(scatter_seeds_kernel, dim3(batch, (unsigned)((widest + 255) / 256)), dim3(256), 0,
+                       st, cost, cost_out, grads, grads_out, grad_per_seed, final_states, final_out,
+                       final_per_seed, order);
+}
+
 void launch_clip_controls(double* controls, size_t total, int k, const double* max_norms, hipStream_t st) {
     if (total == 0 || k <= 0) return;
     hipLaunchKernelGGL(clip_controls_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,

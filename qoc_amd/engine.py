@@ -162,6 +162,17 @@ SIGNATURES = {
         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32,
         ctypes.c_double]),
     "qocx_opt_download_best": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
+    "qocx_lindblad_upload_controls": (ctypes.c_int, [_VP, _I32, _c_double_p]),
+    "qocx_eval_lindblad_resident": (ctypes.c_int, [_VP, _I32]),
+    "qocx_lindblad_download_results": (ctypes.c_int, [_VP, _c_double_p, _c_double_p, _c_double_p]),
+    "qocx_lindblad_download_costs": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_lindblad_opt_begin": (ctypes.c_int, [_VP]),
+    "qocx_lindblad_opt_clip": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_lindblad_opt_step": (ctypes.c_int, [
+        _VP, _I32, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8), ctypes.c_double,
+        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32,
+        ctypes.c_double]),
+    "qocx_lindblad_opt_download_best": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
     "qocx_host_clip_controls": (ctypes.c_int, [_c_double_p, _I64, _I64, _I32, _c_double_p]),
     "qocx_host_optimizer_update": (ctypes.c_int, [
         _I32, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _I64, ctypes.POINTER(_I64), _I64,
@@ -434,6 +445,7 @@ class Engine(object):
         self._lindblad = dict(n=n, S=S, K=K, Nc=int(control_eval_count),
                               N=int(system_eval_count))
         self._lindblad_batch = 0
+        self._lindblad_resident_batch = 0
 
     def evaluate_lindblad(self, controls, want_grad=True, want_final=True):
         """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n]) for controls[B,Nc,K]."""
@@ -580,6 +592,61 @@ class Engine(object):
         controls = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64)
         final = np.empty((B, pr["S"], pr["n"]), dtype=np.complex128)
         self._check(self._lib.qocx_opt_download_best(self._ctx, _dp(controls), _dp(final)))
+        return controls, final
+
+    # -- the same for the Lindblad problem (its own resident buffers, seed order) -----------------
+    def lindblad_upload_controls(self, controls):
+        """controls :: (B, Nc, K) real, kept in HBM for eval_lindblad_resident / lindblad_opt_*."""
+        pr = self._lindblad
+        controls = np.ascontiguousarray(controls, dtype=np.float64).reshape(-1, pr["Nc"], pr["K"])
+        self._check(self._lib.qocx_lindblad_upload_controls(self._ctx, controls.shape[0],
+                                                            _dp(controls)))
+        self._lindblad_resident_batch = controls.shape[0]
+
+    def eval_lindblad_resident(self, want_grad=True):
+        self._check(self._lib.qocx_eval_lindblad_resident(self._ctx, int(bool(want_grad))))
+        self._lindblad_batch = self._lindblad_resident_batch
+
+    def lindblad_download_results(self, want_grad=True, want_final=True):
+        """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n] or None), seed order."""
+        pr, B = self._lindblad, self._lindblad_resident_batch
+        cost = np.empty(B, dtype=np.float64)
+        grads = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64) if want_grad else None
+        final = (np.empty((B, pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
+                 if want_final else None)
+        self._check(self._lib.qocx_lindblad_download_results(
+            self._ctx, _dp(cost), _dp(grads) if want_grad else None,
+            _dp(final) if want_final else None))
+        return cost, grads, final
+
+    def lindblad_download_costs(self):
+        cost = np.empty(self._lindblad_resident_batch, dtype=np.float64)
+        self._check(self._lib.qocx_lindblad_download_costs(self._ctx, _dp(cost)))
+        return cost
+
+    def lindblad_opt_begin(self):
+        self._check(self._lib.qocx_lindblad_opt_begin(self._ctx))
+
+    def lindblad_opt_clip(self, max_norms):
+        max_norms = np.ascontiguousarray(max_norms, dtype=np.float64)
+        self._check(self._lib.qocx_lindblad_opt_clip(self._ctx, _dp(max_norms)))
+
+    def lindblad_opt_step(self, kind, improved, update, learning_rate, beta_1=0.0, beta_2=0.0,
+                          epsilon=0.0, corr_1=1.0, corr_2=1.0, clip_grads=None):
+        improved = np.ascontiguousarray(improved, dtype=np.uint8)
+        update = np.ascontiguousarray(update, dtype=np.uint8)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        self._check(self._lib.qocx_lindblad_opt_step(
+            self._ctx, int(kind), improved.ctypes.data_as(u8), update.ctypes.data_as(u8),
+            float(learning_rate), float(beta_1), float(beta_2), float(epsilon), float(corr_1),
+            float(corr_2), 0 if clip_grads is None else 1,
+            0.0 if clip_grads is None else float(clip_grads)))
+
+    def lindblad_opt_download_best(self):
+        pr, B = self._lindblad, self._lindblad_resident_batch
+        controls = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64)
+        final = np.empty((B, pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
+        self._check(self._lib.qocx_lindblad_opt_download_best(self._ctx, _dp(controls), _dp(final)))
         return controls, final
 
     def reduce_results(self, allreduce=False, want_grad=True):
