@@ -285,34 +285,41 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   faster per step when the sweep has the chip to itself (<= 128 seeds). One
  *                   implementation serves all batch sizes of a context, so results stay bit
  *                   identical across batching.
- *   "sweep3_phases" with the blocked sweep selected: bit 0 forward launches, bit 1 adjoint.
- *   "sweep_loader"  column-chain sweep only. 0 (default): the compute wave issues the LDS-DMA from
- *                   inside its triangular solves; 1: a dedicated fetch wave per seed does.
+ *   "sweep_one"     one state, n <= 32: the dedicated one-state kernel of qocx_sweep1.hip (0: the
+ *                   one-state form of the column-chain sweep).
  *   "pade_order"    0 (default): Pade order 3 / 5 / 7 / 9 / 13 by the 1-norm of the step generator;
  *                   13: always [13/13], as the reference executes it (qocx_pade_orders).
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;
  *   "lu_mfma"       (round 4) ... and takes its Schur updates to the matrix cores (qocx_lu4.h).
+ *   "lu_dpp"        diagonally dominant Pade denominators (every step of the evaluation): the
+ *                   factorisations without pivot search (qocx_lu5.h).
+ *   "k1a_three"     17 <= n <= 32, orders 3 and 5: the three-wave K1a (qocx_pade3.hip); "k1a_share":
+ *                   which generator tiles it takes from LDS; "k1a_four" (default 0): the second
+ *                   halves of its factorisations four to a wave behind it (1) or on a side stream (2).
+ *   "k1a_herm4": four-wave K1a, Hermitian generators, orders 3..9: two thirds of the tiles (0: all tiles).
  *   "latency"       0 (default; the host sets 1 for entry points that evaluate ONE control set):
- *                   four time segments, the inverse-image sweep.
+ *                   two time segments, the inverse-image sweep.
  *   "sweep_inverse" latency mode: sub-steps as two matrix-vector products with P^-1 (qocx_sweepi.hip);
- *   "sweep_inverse_small": the same sweep for every batch at n <= 16.
+ *   "sweep_inverse_small": the same sweep for every batch at n <= 16; "pack8": n <= 8, two steps
+ *                   of a seed as the diagonal blocks of one 16 x 16 tile through K1a and K1b;
+ *   "sweep_umode": latency mode, the propagator U = P^-1 Q in the Q image, one product per sub-step.
  *   "sweep_dense"   8 <= S <= 32 states at 17 <= n <= 32 as MFMA GEMM columns (qocx_sweepd.hip);
- *   "krylov_dense"  (default 0) K3 on the matrix cores for those problems; "lu_inverse": the debug
- *                   factor entry point returns P^-1.
+ *                   "lu_inverse": the debug factor entry point returns P^-1.
  *   "m4_linear"     MagnusPolicy.M4 with time-independent H0, G_k on the M2 kernels (commutators
  *                   hoisted into constant matrices); "magnus_4w": four-wave LDS-resident Magnus
- *                   kernels at 17 <= n <= 32; "magnus_general": the general commutator forms.
+ *                   kernels at 17 <= n <= 32.
+ *   "general_split", "general_skew": n > 64 (qocx_general.hip): the many-state sweep in groups of
+ *                   rows on several workgroups; the Krylov chains of Hermitian generators.
  *   "lindblad_two_sided", "lindblad_side_limit": forward and unit-adjoint Lindblad passes side by side.
- *   "k1a_herm4": four-wave K1a, Hermitian generators, orders 3..9: two thirds of the tiles (0: all tiles).
- *   "lu_stream": n > 32, K1b of a time segment on a stream of its own beside K1a of the next (0: one stream).
- *   "lindblad_q2": their stage loop with 18 of the 72 MFMAs of a right-hand side per wave (0: the quarter-split loops).
+ *   "lindblad_q2": their stage loop with 18 of the 72 MFMAs of a right-hand side per wave (0: the quarter-split loops);
+ *   "lindblad_chain", "lindblad_real_ops": the chained stage loop of several jump operators; real operators
+ *                   as two real products per complex one.
  *   "lindblad_4t": Lindblad at 17 <= n <= 32 on the tile-per-wave kernel where it applies (0: one wave per seed).
  *   "lindblad_hermitian": that kernel's shorter stages for Hermitian problems (Y A_R = (A_L Y)^H; 0: the general stages).
  *   "lindblad_pad_operator": Lindblad with ONE operator at n <= 16 on the four-wave launches of two (the second zero);
  *                   read when the problem is set (0: the three-wave form).
- *   "sweep_onebuf", "k3_split": launch shapes of the sweep / of K3.
  * Diagnostic knobs - libqocx_diag.so only (make diag, -DQOCX_DIAG; the product library answers
  * QOCX_ERR_ARG): "dbg_skip", "sweep3_dbg", "k1a_dbg" switch parts of an evaluation off for timing
  * (results are garbage); "sweep3_stamps", "lindblad_stamps", "k1a_stamps" run kernel builds that

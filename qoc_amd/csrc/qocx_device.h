@@ -134,14 +134,11 @@ struct SweepArgs {
     double2* lam_scale = nullptr;   // [B][S] scalars c_s, written at the end of the forward sweep, read by K3
     int* offs_x = nullptr;  // unit adjoint: [B][nsteps+1] first xs slot of each step, written by the ADJOINT
                           // sweep (it may run before the forward sweep has numbered the sub-steps)
-    int batch = 0;        // seeds of the launch (set by the launcher of the two-seeds-per-workgroup form)
-    int onebuf = 0;       // one state: one operand set in LDS; 1: one seed per workgroup, 2: two
+    int batch = 0;        // seeds of the launch (set by the launchers of the one-state forms)
     int one_state = 0;    // one state, n <= 32: the dedicated kernel of qocx_sweep1.hip (knob "sweep_one")
-    int ring2 = 0;        // sweep1, n > 16: two operand sets in LDS, every fetch a whole step ahead (70 KiB per seed)
     const double2* qt_img = nullptr;  // umode: U^T images (launch_umul) - the adjoint sweep copies them straight instead of gathering
     int umode = 0;        // sweepi: q_img holds the propagator U = P^-1 Q (launch_umul): ONE product per sub-step;
                           // the adjoint leaves lambda' in `xs` and K3 forms x = P^-H lambda' (KrylovArgs::umode)
-    int loader;           // 1: a dedicated fetch wave per seed issues the LDS-DMA
     int dbg;              // sweep3 timing diagnostics (results are garbage): bit 0 no inversion,
                           // bit 1 no solves, bit 2 no LU fetch, bit 3 no Q fetch, bit 4 no Q touch
     unsigned long long* stamps;  // sweep3 diagnostic build: [B][4 roles][8] cycle sums, or nullptr
@@ -171,7 +168,6 @@ struct SweepArgs {
 struct KrylovArgs {
     int umode = 0;                       // `xs` holds lambda' (SweepArgs::umode): x = P^-H lambda' is formed here from pinv_img
     const double2* pinv_img = nullptr;   // [B][nsteps] column-major P^-1 images (the LU buffer in inverse mode)
-    int lds_pad = 0;  // extra dynamic LDS per workgroup (bytes): fewer K3 waves per CU beside the tail sweeps (knob "k3_lds_pad")
     const double* controls;
     const StepInterp* interp;
     const double2* h0_rimg;  // column-major h0
@@ -444,11 +440,10 @@ void launch_sweep3(int nb, const SweepArgs& a, int batch, hipStream_t st);
 // dense-state sweep (qocx_sweepd.hip): the states of a seed as GEMM columns; lu_img holds P^-1
 bool sweepd_supports(int nb, int S);
 void launch_sweepd(const SweepArgs& a, int batch, hipStream_t st);
-void launch_krylovd(const KrylovArgs& a, int nsteps, int batch, hipStream_t st);  // K3 on the matrix cores
 // inverse-image sweep of latency mode (qocx_sweepi.hip): two matrix-vector products per sub-step
 bool sweepi_supports(int nb, int S);
 bool sweep1_supports(int nb, int S);
-void launch_sweep1(int nb, const SweepArgs& a, int batch, int pack, hipStream_t st);
+void launch_sweep1(int nb, const SweepArgs& a, int batch, hipStream_t st);
 void launch_sweepi(int nb, const SweepArgs& a, int batch, hipStream_t st);
 int sweep3_max_states(int nb);
 void launch_krylov(int nb, const KrylovArgs& a, int nsteps, int batch, hipStream_t st);

@@ -1,4 +1,5 @@
-// qocx_general.hip - the Schroedinger path for Hilbert sizes ABOVE 64 (65 <= n <= 256, M2): the same
+// qocx_general.hip - the Schroedinger path for Hilbert sizes ABOVE 64 (65 <= n <= 1024, M2, M4 and M6;
+// also n <= 64 with more states than the sweep's LDS holds): the same
 // algorithm as the wavefront kernels - Pade numerator / denominator per step, the
 // sweep applies P^-1 Q per squaring sub-step, the Krylov-chain adjoint forms the generator cotangent -
 // with every matrix in HBM / L2 instead of registers and LDS, one workgroup of four waves per work item.

@@ -708,38 +708,29 @@ namespace qocx {
 // and every wave has left the previous step". The costs couple the states, so wave 0 evaluates
 // them on all S states between two barriers. W = 1 is the single-state form: no barrier at all.
 //
-// LOADER: one more wave per seed does nothing but fetch: it issues the next step's 34 LDS-DMA
-// pieces back to back, waits for them and meets the compute waves at the step barrier. An LDS-DMA
-// costs its issuing wave 60-100 cycles of issue time each (MI355X_MICROARCH.md, 'LDS-DMA piece'),
-// i.e. 2 000 - 3 400 cycles per step when the compute wave issues them from inside its dependent
-// chains (the form without LOADER, kept for comparison: qocx_debug_set_knob "sweep_loader" 0).
+// (Measured and removed: a dedicated fetch wave per seed with a ring of three operand buffers - no
+// faster, docs/rounds/DESIGN_rounds_1_to_4.md, "The column chain is K2's step time".)
 //
-// ONEBUF (one state, one wave per seed): ONE set of operand buffers instead of two, and TWO seeds
-// per workgroup (two independent waves, no barrier between them). A step's LU image is copied to
-// registers at the top of the step and its Q image is last read by the matvec of the last
-// squaring sub-step (forward) - so the next step's operands can land in the SAME buffers while
-// the solves run. The adjoint reads Q at the END of a sub-step (lambda = Q^H x): there the fetch
-// of a step brings the step's OWN Q image (first solve, waited for with a counted vmcnt in front
-// of the matvec) and the NEXT step's LU image. 35 KiB of LDS per seed instead of 68: two seeds
-// share a CU, which halves the CUs on which the sweep displaces a K1a workgroup (a 221-register
-// sweep wave leaves room for three two-wave K1a workgroups instead of four - whether the CU hosts
-// one sweep wave or two).
-template <int NB, int W, bool LOADER, bool ONEBUF = false, int NA = Geo<NB>::NP>
-__global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sweep_kernel(SweepArgs args) {
+// ONEBUF (one state, one wave per seed): ONE set of operand buffers instead of two. A step's LU
+// image is copied to registers at the top of the step and its Q image is last read by the matvec
+// of the last squaring sub-step (forward) - so the next step's operands can land in the SAME
+// buffers while the solves run. The adjoint reads Q at the END of a sub-step (lambda = Q^H x):
+// there the fetch of a step brings the step's OWN Q image (first solve, waited for with a counted
+// vmcnt in front of the matvec) and the NEXT step's LU image. 35 KiB of LDS per seed instead of 68.
+// (The kernel also takes two seeds per workgroup, one wave each; launch_sweep_onebuf gives it one.)
+template <int NB, int W, bool ONEBUF = false, int NA = Geo<NB>::NP>
+__global__ __launch_bounds__(ONEBUF ? 128 : 64 * W) void sweep_kernel(SweepArgs args) {
     typedef Geo<NB> G;
     static_assert(NA == G::NP || (NB == 4 && NA == 48), "NA < NP: the nine-tile images of 33 <= n <= 48");
-    static_assert(!ONEBUF || (W == 1 && !LOADER && SweepPrefetch<NB>::value), "ONEBUF: one wave per seed");
-    // With a loader wave the operands of TWO steps travel at once (ring of three buffers): the
-    // fetch of step t+2 is issued while step t computes and has until the start of step t+2 to land.
+    static_assert(!ONEBUF || (W == 1 && SweepPrefetch<NB>::value), "ONEBUF: one wave per seed");
     // NB = 4 (33 <= n <= 64): one Q and one LU image are 64 KiB each, so there is room for ONE
     // set of operands only - the step's fetch is issued at its start and waited for (PREFETCH off).
     constexpr bool PREFETCH = SweepPrefetch<NB>::value;
     constexpr bool LDSCOEF = SweepLdsCoef<NB>::value;
     // two states of a seed at a time on a wave (tri_solve2, lds_matvec2) where a wave has several:
     // the register-row solves of the multi-state forms
-    constexpr bool PAIRS = !ONEBUF && !LDSCOEF && !LOADER && W > 1;
-    static_assert(PREFETCH || !LOADER, "the loader variant needs a ring of buffers");
-    constexpr int NBUF = LOADER ? 3 : ((PREFETCH && !ONEBUF) ? 2 : 1);
+    constexpr bool PAIRS = !ONEBUF && !LDSCOEF && W > 1;
+    constexpr int NBUF = (PREFETCH && !ONEBUF) ? 2 : 1;
     typedef SweepLds<NB, NBUF, NA> L;
     constexpr int NP = G::NP, H = G::H, MAT = G::MAT;
     constexpr int LMAT = NA * NP;  // complex per image in LDS (NA of its NP columns)
@@ -754,19 +745,14 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
     double2* lbuf = reinterpret_cast<double2*>(smem + L::L_OFF);
     double2* dbuf = reinterpret_cast<double2*>(smem + L::D_OFF);
     int* pbuf = reinterpret_cast<int*>(smem + L::P_OFF);
-    constexpr bool MULTI = (W > 1) || LOADER;  // more than one wave in the workgroup
+    constexpr bool MULTI = W > 1;  // more than one wave in the workgroup
     const int w = MULTI ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-    // the wave that fetches: the extra one, or compute wave 0 from inside its solves
-    const bool fetcher = LOADER ? (w == W) : (w == 0);
-    const bool computes = !LOADER || (w < W);
-    double2* tmp = reinterpret_cast<double2*>(smem + L::TMP_OFF) + (computes ? w : 0) * L::TMPV * NP;
+    // the wave that fetches, from inside its solves
+    const bool fetcher = (w == 0);
+    double2* tmp = reinterpret_cast<double2*>(smem + L::TMP_OFF) + w * L::TMPV * NP;
     double2* vecs = reinterpret_cast<double2*>(smem + L::VEC_OFF);
     auto block_sync = [&]() {
-        if constexpr (LOADER) {
-            // LDS hand-off only: a __syncthreads() also waits for vmcnt(0), i.e. for the fetch the
-            // loader has just issued - which is what made the first loader variant slower
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        } else if constexpr (MULTI) {
+        if constexpr (MULTI) {
             // (measured: a raw s_barrier without the vmcnt drain changes nothing here - at S > 1
             // the evaluation is bound by K3 and K1b on the compute stream, not by the sweep)
             __syncthreads();
@@ -774,18 +760,7 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
             wave_sync();
         }
     };
-    // the loader's wait at the top of a step: everything but the fetch that is one step ahead
-    auto wait_landed = [&](bool younger_in_flight) {
-        if constexpr (LOADER) {
-            if (younger_in_flight) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (G::MAT / 64) + 2) : "memory");
-                return;
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-    // the loader wave runs the same control flow (every barrier) with empty state loops
-    const int S = args.S, s0 = computes ? w : args.S;
+    const int S = args.S, s0 = w;
     double2* lam = vecs + S * NP;
     const int b = ONEBUF ? (int)(blockDim.x >> 6) * blockIdx.x + pack_wave : blockIdx.x;
     if (ONEBUF && b >= args.batch) return;  // odd batch: the last workgroup has one seed
@@ -917,16 +892,16 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
         pf_fire_l = false;
     };
     auto hook_a = [&](auto KK) __attribute__((always_inline)) {  // first solve: pieces 0 .. NP-2
-        if constexpr (!LOADER && PREFETCH) dma_fire(KK);
+        if constexpr (PREFETCH) dma_fire(KK);
     };
     auto hook_b = [&](auto KK) __attribute__((always_inline)) {  // second solve: the remaining pieces
         constexpr int piece = NP - 1 + decltype(KK)::value;
-        if constexpr (!LOADER && PREFETCH && piece < PIECES)
+        if constexpr (PREFETCH && piece < PIECES)
             dma_fire(std::integral_constant<int, piece>());
     };
     auto finish_prefetch = [&]() {  // pieces that did not fit into the two solves (NP = 16)
         constexpr int DONE = 2 * (NP - 1), REST = PIECES > DONE ? PIECES - DONE : 0;
-        if constexpr (LOADER || !PREFETCH) return;
+        if constexpr (!PREFETCH) return;
         for_each_const(
             [&](auto P) __attribute__((always_inline)) {
                 dma_fire(std::integral_constant<int, DONE + decltype(P)::value>());
@@ -938,10 +913,6 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
         }
         pf_fire_q = false;
         pf_fire_l = false;
-    };
-    auto issue_all_due = [&]() {  // LOADER: the whole step at once, from the wave that only fetches
-        if (pf_due) for_each_const(dma_one, std::make_integer_sequence<int, PIECES>{});
-        pf_due = false;
     };
     auto scalars = [&](int par, bool adjoint) {
         StepScalars sc;
@@ -1033,7 +1004,6 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
     // dependent chains run -------------------------------------------------------------------
     if (do_fwd) {
         if (fetcher) issue_dma(m0 + jb, 0, false);
-        if (LOADER && fetcher && jb + 1 < je) issue_dma(m0 + jb + 1, 1, false);
         int nsub_next = 1 << step_squarings(args.s_arr[m0 + jb]);
         for (int step = jb; step < je; ++step) {
             const int par = (step - jb) % NBUF;
@@ -1044,11 +1014,11 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
                     if (fetcher) issue_dma(m0 + step, 0, false);
                 }
             }
-            if (fetcher) wait_landed(step + 1 < je);
+            if (fetcher) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             block_sync();
             const StepScalars sc = scalars(par, false);
             if constexpr (!LDSCOEF) {
-                if (computes && !(QOCX_DBG_BITS(args.dbg) & 8192))  // (timing experiment: stale rows)
+                if (!(QOCX_DBG_BITS(args.dbg) & 8192))  // (timing experiment: stale rows)
                     lds_to_regs<NB, false>(qbuf + par * LMAT, lbuf + par * LMAT, pbuf + par * PINTS, r,
                                            sc.pm, lane, i);
             } else {
@@ -1056,11 +1026,7 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
             }
             qcur = qbuf + par * LMAT;
             wave_sync();
-            if constexpr (LOADER) {
-                pf_due = fetcher && (step + 2 < je);
-                if (pf_due) set_prefetch(m0 + step + 2, (par + 2) % NBUF, false, m0 + step + 2);
-                issue_all_due();
-            } else if constexpr (PREFETCH) {
+            if constexpr (PREFETCH) {
                 pf_due = fetcher && (step + 1 < je) && !(QOCX_DBG_BITS(args.dbg) & 256);  // (dbg: timing experiment)
                 if (pf_due) set_prefetch(m0 + step + 1, (par + 1) % NBUF, false, m0 + step + 1);
             }
@@ -1239,7 +1205,6 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
         const size_t ml = m0 + je - 1;
         if constexpr (ONEBUF) issue_lu_only(ml, true);
         else if (fetcher) issue_dma(ml, 0, true);
-        if (LOADER && fetcher && je - 2 >= jb) issue_dma(ml - 1, 1, true);
         int nsub_next = 1 << step_squarings(args.s_arr[ml]);
         for (int step = je - 1, it = 0; step >= jb; --step, ++it) {
             const int par = it % NBUF;
@@ -1250,11 +1215,11 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
                     if (fetcher) issue_dma(m0 + step, 0, true);
                 }
             }
-            if (fetcher) wait_landed(step - 1 >= jb);
+            if (fetcher) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             block_sync();
             const StepScalars sc = scalars(par, true);
             if constexpr (!LDSCOEF) {
-                if (computes && !(QOCX_DBG_BITS(args.dbg) & 8192))
+                if (!(QOCX_DBG_BITS(args.dbg) & 8192))
                     lds_to_regs<NB, true>(qbuf + par * LMAT, lbuf + par * LMAT, pbuf + par * PINTS, r,
                                           sc.pm, lane, i);
             } else {
@@ -1263,11 +1228,7 @@ __global__ __launch_bounds__(ONEBUF ? 128 : 64 * (W + (LOADER ? 1 : 0))) void sw
             }
             qcur = qbuf + par * LMAT;
             wave_sync();
-            if constexpr (LOADER) {
-                pf_due = fetcher && (step - 2 >= jb);
-                if (pf_due) set_prefetch(m0 + step - 2, (par + 2) % NBUF, true, m0 + step - 2);
-                issue_all_due();
-            } else if constexpr (ONEBUF) {
+            if constexpr (ONEBUF) {
                 pf_due = (step - 1 >= jb) && !(QOCX_DBG_BITS(args.dbg) & 512);
                 pf_qdue = !(QOCX_DBG_BITS(args.dbg) & 512);
                 set_prefetch(pf_due ? m0 + step - 1 : m0 + step, 0, true, m0 + step);
@@ -1817,59 +1778,44 @@ static void launch_pq_explicit_t(const double2* a_in, int n, const FactorArgs& a
         hipLaunchKernelGGL((pade_pq_explicit_kernel<NB, false>), dim3(count), dim3(64),
                            PqLds<NB>::BYTES, st, a_in, n, a);
 }
-template <int NB, int W, bool LOADER>
-static void launch_sweep_wl(const SweepArgs& a, int batch, hipStream_t st) {
-    if constexpr (NB == 4 && !LOADER) {
-        if (a.n > 0 && a.n <= 48) {  // nine-tile images: 48 of the 64 columns in LDS, 47 stages per solve
-            const int bytes9 = SweepLds<4, 1, 48>::bytes(a.S);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<4, W, false, false, 48>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, bytes9);
-            hipLaunchKernelGGL((sweep_kernel<4, W, false, false, 48>), dim3(batch), dim3(64 * W), bytes9, st, a);
-            return;
-        }
-    }
-    const int bytes = LOADER ? SweepLds<NB, 3>::bytes(a.S) : SweepLds<NB>::bytes(a.S);
-    if (bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<NB, W, LOADER>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipLaunchKernelGGL((sweep_kernel<NB, W, LOADER>), dim3(batch),
-                       dim3(64 * (W + (LOADER ? 1 : 0))), bytes, st, a);
-}
 template <int NB, int W>
 static void launch_sweep_w(const SweepArgs& a, int batch, hipStream_t st) {
-    // (the loader variant's ring of three must fit the CU's LDS beside the state vectors)
-    if constexpr (SweepPrefetch<NB>::value) {
-        if (a.loader && SweepLds<NB, 3>::bytes(a.S) <= 160 * 1024) {
-            launch_sweep_wl<NB, W, true>(a, batch, st);
+    if constexpr (NB == 4) {
+        if (a.n > 0 && a.n <= 48) {  // nine-tile images: 48 of the 64 columns in LDS, 47 stages per solve
+            const int bytes9 = SweepLds<4, 1, 48>::bytes(a.S);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<4, W, false, 48>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, bytes9);
+            hipLaunchKernelGGL((sweep_kernel<4, W, false, 48>), dim3(batch), dim3(64 * W), bytes9, st, a);
             return;
         }
     }
-    launch_sweep_wl<NB, W, false>(a, batch, st);
+    const int bytes = SweepLds<NB>::bytes(a.S);
+    if (bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<NB, W>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    hipLaunchKernelGGL((sweep_kernel<NB, W>), dim3(batch), dim3(64 * W), bytes, st, a);
 }
-// one state, one wave per seed: one operand set in LDS, two seeds per workgroup
+// one state, one wave per seed: one operand set in LDS, one seed per workgroup
 template <int NB>
 static void launch_sweep_onebuf(const SweepArgs& a, int batch, hipStream_t st) {
     if constexpr (SweepPrefetch<NB>::value) {
-        const int bytes = 2 * SweepLds<NB, 1>::bytes_static(1);
+        const int bytes = SweepLds<NB, 1>::bytes_static(1);
         static bool attr_set = false;
         if (bytes > 48 * 1024 && !attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<NB, 1, false, true>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep_kernel<NB, 1, true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             attr_set = true;
         }
         SweepArgs b = a;
         b.batch = batch;
-        const int pack = a.onebuf >= 2 ? 2 : 1;  // seeds (waves) per workgroup
-        hipLaunchKernelGGL((sweep_kernel<NB, 1, false, true>), dim3((batch + pack - 1) / pack),
-                           dim3(64 * pack), bytes / 2 * pack, st, b);
+        hipLaunchKernelGGL((sweep_kernel<NB, 1, true>), dim3(batch), dim3(64), bytes, st, b);
     }
 }
 template <int NB>
 static void launch_sweep_t(const SweepArgs& a, int batch, hipStream_t st) {
-    if (SweepPrefetch<NB>::value && a.onebuf && a.S == 1 && !a.loader &&
-        diag_getenv("QOCX_SWEEP_W") == nullptr) {
+    if (SweepPrefetch<NB>::value && a.S == 1 && diag_getenv("QOCX_SWEEP_W") == nullptr) {
         if (a.one_state && sweep1_supports(NB, a.S)) {  // qocx_sweep1.hip: the same step, bit for bit
-            launch_sweep1(NB, a, batch, a.onebuf, st);
+            launch_sweep1(NB, a, batch, st);
             return;
         }
         launch_sweep_onebuf<NB>(a, batch, st);
@@ -1906,7 +1852,7 @@ static void launch_krylov_t(const KrylovArgs& a, int nsteps, int batch, hipStrea
                            KrylovLds<NB>::BYTES, st, a);
     else if (a.skew)
         hipLaunchKernelGGL((krylov_grad_skew_kernel<NB, false>), dim3(nsteps, batch), dim3(64),
-                           KrylovLds<NB>::BYTES + (a.lds_pad > 0 && a.lds_pad <= 40 * 1024 ? a.lds_pad : 0), st, a);
+                           KrylovLds<NB>::BYTES, st, a);
     else
         hipLaunchKernelGGL((krylov_grad_kernel<NB, false>), dim3(nsteps, batch), dim3(64),
                            KrylovLds<NB>::BYTES, st, a);

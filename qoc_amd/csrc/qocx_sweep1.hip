@@ -448,39 +448,28 @@ __global__ __launch_bounds__(128) void sweep1_kernel(SweepArgs args) {
 
 bool sweep1_supports(int nb, int S) { return nb <= 2 && S == 1; }
 
-// `pack`: seeds (waves) per workgroup, 1 or 2
-void launch_sweep1(int nb, const SweepArgs& a, int batch, int pack, hipStream_t st) {
+void launch_sweep1(int nb, const SweepArgs& a, int batch, hipStream_t st) {
     SweepArgs b = a;
     b.batch = batch;
-    pack = pack >= 2 ? 2 : 1;
     if (nb == 1) {
         constexpr int RING = 4;
-        const int bytes = sweep1::Lds1<1, RING>::SEED_BYTES * pack;
+        const int bytes = sweep1::Lds1<1, RING>::SEED_BYTES;
         static bool attr_set = false;
         if (bytes > 48 * 1024 && !attr_set) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep1::sweep1_kernel<1, RING>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             attr_set = true;
         }
-        hipLaunchKernelGGL((sweep1::sweep1_kernel<1, RING>), dim3((batch + pack - 1) / pack), dim3(64 * pack), bytes, st, b);
-    } else if (a.ring2) {
-        const int bytes = sweep1::Lds1<2, 2>::SEED_BYTES * pack;
-        static bool attr_set = false;
-        if (bytes > 48 * 1024 && !attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep1::sweep1_kernel<2, 2>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((sweep1::sweep1_kernel<2, 2>), dim3((batch + pack - 1) / pack), dim3(64 * pack), bytes, st, b);
+        hipLaunchKernelGGL((sweep1::sweep1_kernel<1, RING>), dim3(batch), dim3(64), bytes, st, b);
     } else {
-        const int bytes = sweep1::Lds1<2, 1>::SEED_BYTES * pack;
+        const int bytes = sweep1::Lds1<2, 1>::SEED_BYTES;
         static bool attr_set = false;
         if (bytes > 48 * 1024 && !attr_set) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sweep1::sweep1_kernel<2, 1>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
             attr_set = true;
         }
-        hipLaunchKernelGGL((sweep1::sweep1_kernel<2, 1>), dim3((batch + pack - 1) / pack), dim3(64 * pack), bytes, st, b);
+        hipLaunchKernelGGL((sweep1::sweep1_kernel<2, 1>), dim3(batch), dim3(64), bytes, st, b);
     }
 }
 

@@ -45,12 +45,12 @@ def total_registers(entry):
     return entry["VGPRs"] + entry.get("AGPRs", 0)
 
 
-def test_headline_kernels_share_a_simd():
+def test_sweep_k1a_and_k3_share_a_simd():
     kernels = resources("qocx_kernels.hip")
     pade2 = resources("qocx_pade2.hip")
-    sweep = find(kernels, "sweep_kernelILi2ELi1ELb0ELb0E")
-    sweep1 = find(kernels, "sweep_kernelILi2ELi1ELb0ELb1E")  # one operand set in LDS (round 3)
-    sweep4 = find(kernels, "sweep_kernelILi2ELi4ELb0ELb0E")
+    sweep = find(kernels, "sweep_kernelILi2ELi1ELb0E")
+    sweep1 = find(kernels, "sweep_kernelILi2ELi1ELb1E")  # one operand set in LDS (round 3)
+    sweep4 = find(kernels, "sweep_kernelILi2ELi4ELb0E")
     k1a = find(pade2, "pade_pq2_kernelILb1ELb0ELb1E")   # Hermitian, product build, step table (the headline's)
     k1a_norm = find(pade2, "pade_pq2_kernelILb1ELb0ELb0E")  # ... deciding order / squarings from the matrix norm
     k3 = find(kernels, "krylov_grad_skew_kernelILi2ELb0ELb0E")  # (the third flag: the copy of latency mode, sweep_umode)
@@ -130,19 +130,35 @@ def test_general_path_kernels_do_not_spill():
         assert entry["VGPRs Spill"] == 0 and total_registers(entry) <= 256
 
 
+# the run-time variant knobs of qocx_debug_set_knob (include/qocx.h), and those whose variants were removed
+VARIANT_KNOBS = (
+    "sweep_impl", "sweep_one", "sweep_dense", "sweep_inverse", "sweep_inverse_small", "sweep_umode", "bidir",
+    "unit_adjoint", "latency", "fuse_lu", "lu_inverse", "lu_mfma", "lu_dpp", "pack8", "m4_linear", "magnus_4w",
+    "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
+    "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
+    "lindblad_hermitian", "lindblad_pad_operator")
+REMOVED_KNOBS = (
+    "k1a_streams", "sweep_tail_ring", "k3_lds_pad", "krylov_dense", "sweep_loader", "magnus_general",
+    "sweep3_phases", "bidir_min_segments", "bidir_adj_first", "k3_split", "k3_split_outer", "step_table",
+    "sweep_nine", "lu_stream", "sweep_onebuf")
+
+
 def test_release_library_has_no_diagnostic_switches():
     """the knobs that return garbage (timing experiments), the stamped kernel
     builds and the QOCX_* environment switches exist in libqocx_diag.so only (-DQOCX_DIAG,
     qoc_amd/csrc/qocx_diag.h); the product library rejects the knobs and does not even contain the
-    variable names."""
+    variable names. Every variant knob is accepted; the knobs of removed variants are unknown."""
+    assert len(VARIANT_KNOBS) == 31 and len(REMOVED_KNOBS) == 15
     from qoc_amd import engine
     lib = engine.load_library()
     assert lib.qocx_build_is_diag() == 0
     for name in (b"dbg_skip", b"sweep3_dbg", b"sweep3_stamps", b"lindblad_stamps", b"k1a_dbg",
                  b"k1a_stamps", b"peak_mode"):
         assert lib.qocx_knob_kind(name) == -2, name
-    for name in (b"pade_order", b"fuse_lu", b"lu_mfma", b"bidir", b"unit_adjoint", b"sweep_impl"):
-        assert lib.qocx_knob_kind(name) == 1, name
+    for name in VARIANT_KNOBS:
+        assert lib.qocx_knob_kind(name.encode()) == 1, name
+    for name in REMOVED_KNOBS:
+        assert lib.qocx_knob_kind(name.encode()) == 0, name
     assert lib.qocx_knob_kind(b"no_such_knob") == 0
     blob = open(engine.LIBRARY_PATH, "rb").read()
     for env in (b"QOCX_PQ1", b"QOCX_SWEEP_W", b"QOCX_SEG_WEIGHTS", b"QOCX_SWEEP_IMPL",

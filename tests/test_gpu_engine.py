@@ -739,7 +739,7 @@ def test_inverse_image_sweep_several_states_small_n(engine):
     assert checked >= 12
 
 
-def test_dense_state_sweep(engine):
+def test_dense_state_sweep_matches_column_chain(engine):
     """8 <= S <= 32 states at 17 <= n <= 32 run on the dense-state sweep (qocx_sweepd.hip: P^-1 from
     K1b's Gauss-Jordan sibling, two MFMA GEMMs per sub-step over all states; knob "sweep_dense"):
     random problems - step costs of every kind, cost_eval_step, squarings, Hermitian or not, time
@@ -749,23 +749,20 @@ def test_dense_state_sweep(engine):
     checked = 0
     for index in range(24):
         out = []
-        # dense sweep + K3 on the matrix cores | dense sweep + vector-unit K3 (the default) | neither
-        for dense, k3 in ((1, 1), (1, 0), (0, 0)):
+        # dense sweep (the default) | column-chain sweep
+        for dense in (1, 0):
             engine.set_knob("sweep_dense", dense)
-            engine.set_knob("krylov_dense", k3)
             rng = np.random.default_rng(5000 + index)
             worst, tag = fuzz_parity.one(engine, rng, index, nmin=17, nmax=32, smin=8, smax=32,
                                          results=out)
             if worst is None:
                 break
-            assert worst < 1.0, (dense, k3, tag)
+            assert worst < 1.0, (dense, tag)
         engine.set_knob("sweep_dense", 1)
-        engine.set_knob("krylov_dense", 0)
-        if len(out) == 3:
+        if len(out) == 2:
             checked += 1
-            for other in out[:2]:
-                for a, b in zip(other, out[2]):
-                    assert np.max(np.abs(a - b)) <= 1e-11 * max(1.0, np.max(np.abs(b))), tag
+            for a, b in zip(out[0], out[1]):
+                assert np.max(np.abs(a - b)) <= 1e-11 * max(1.0, np.max(np.abs(b))), tag
     assert checked >= 18
     case = cases_mod.case_by_name("c3_fullU_short")
     from tests import gpu_helpers as gh

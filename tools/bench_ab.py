@@ -3,7 +3,7 @@ bench_ab.py - BUILD-CONTAINER / GPU-BOX TOOLING: interleaved A/B rounds of the C
 (bench.py's) in ONE process (cdna_hip_programming.md rule 24), switching engine knobs
 (qocx_debug_set_knob) between rounds.
 
-    python tools/bench_ab.py --knob sweep_loader --values 0 1 --rounds 6
+    python tools/bench_ab.py --knob fuse_lu --values 1 0 --rounds 6
 Prints one JSON line per variant: median / min ms per evaluation and per-kernel ms per launch.
 """
 
