@@ -188,6 +188,25 @@ int qocx_download_results(qocx_ctx* ctx, double* cost_out, double* grad_out, dou
 int qocx_upload_generators(qocx_ctx* ctx, int32_t batch, const double* generators);
 int qocx_download_generator_cotangents(qocx_ctx* ctx, double* cotangents_out);
 
+/*
+ * Hamiltonians quadratic in the real controls r (the reference's report names an epsilon^2
+ * AC-Stark term, report.tex:22-32):
+ *     H(r, t) = H0(t) + sum_k r_k G_k(t) + sum_q r_(k_q) r_(l_q) Q_q
+ * with H0 / G_k from qocx_set_schroedinger_problem and constant Q_q. Call after that function
+ * (which clears the terms); count = 0 clears them too. Real-control indices follow the problem's
+ * layout (complex controls: Re u_j -> 2j, Im u_j -> 2j+1).
+ *   pairs     [count][2] int32, 0 <= k_q <= l_q < control_count (repeated pairs add up)
+ *   matrices  [count][n][n] complex, row-major
+ * The engine evaluates H as linear in the K + count effective controls (r_k, r_k r_l) on both
+ * evaluation routes, and folds their cotangents back to the real controls on the device; the
+ * controls, the gradients and the qocx_opt_* state stay in the K real controls. QOCX_ERR_ARG for
+ * indices out of range, magnus_policy M4 / M6, explicit generators, or control_count + count > 64;
+ * QOCX_ERR_CAPACITY when a time-dependent problem's augmented tables (nt x (K + count) padded
+ * matrices, three images below hilbert_size 65) would exceed 4 GiB. Controls must be uploaded
+ * again afterwards.
+ */
+int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs, const double* matrices);
+
 /* Optional: all system-step states of the last evaluation, [B][N][S][n] complex
  * (what save_intermediate_states persists, schroedingerdiscrete.py:395-402). */
 int qocx_set_keep_step_states(qocx_ctx* ctx, int32_t keep); /* before the evaluation */

@@ -11,6 +11,7 @@ import numpy as np
 
 from qoc_amd.core import structure
 from qoc_amd.models.policies import InterpolationPolicy, MagnusPolicy
+from qoc_amd.standard.hamiltonians import QuadraticHamiltonian
 
 def make_backend(device=-1):
     """The HIP engine. There is no CPU fallback: this raises when libqocx.so or the GPU is
@@ -123,10 +124,27 @@ class SchroedingerEvaluator(object):
         # problem with the same cost and the same control gradient), one control array at a time.
         self.linearized_hamiltonian = None
         self._problem_static = None
+        # A QuadraticHamiltonian under M2, on an engine that takes quadratic terms: the linear part
+        # goes in structured form and the r_k r_l Q_kl terms to qocx_set_quadratic_terms - the
+        # engine evaluates it as linear in the effective controls (r_k, r_k r_l), the callable is
+        # never called per evaluation. Elsewhere it is just a callable (the routes below).
+        self.quadratic_terms = None
+        if isinstance(hamiltonian, QuadraticHamiltonian) and backend is None:
+            backend = make_backend()  # (the route depends on what the backend takes)
+        if (isinstance(hamiltonian, QuadraticHamiltonian) and magnus_policy == MagnusPolicy.M2
+                and control_count > 0 and hasattr(backend, "set_quadratic_terms")):
+            hamiltonian.check_real_control_count(
+                control_count * (2 if complex_controls else 1), self.hilbert_size)
+            self.quadratic_terms = (hamiltonian.pairs, hamiltonian.matrices)
+            probed = hamiltonian.linear_hamiltonian
+        else:
+            probed = hamiltonian
         try:
-            h0, g = structure.probe_hamiltonian(hamiltonian, self.hilbert_size, control_count,
+            h0, g = structure.probe_hamiltonian(probed, self.hilbert_size, control_count,
                                                 complex_controls, times)
         except structure.NonLinearHamiltonianError:
+            if self.quadratic_terms is not None:
+                raise
             if magnus_policy != MagnusPolicy.M2:
                 self.linearized_hamiltonian = hamiltonian
                 self._node_times = times
@@ -173,6 +191,8 @@ class SchroedingerEvaluator(object):
     def _set_problem(self, h0, g):
         head, psi0, kw = self._problem_static
         self.backend.set_schroedinger_problem(*head, h0, g, psi0, **kw)
+        if self.quadratic_terms is not None:
+            self.backend.set_quadratic_terms(*self.quadratic_terms)
 
     # -- device round trip: structured controls, or generators sampled from an opaque callable ----
     def _upload(self, controls_batch, device_controls):

@@ -236,6 +236,14 @@ struct qocx_ctx {
     DevBuf<double2> ge_cimg, ge_rimg, ge_timg;
     DevBuf<qocx::StepInterp> interp_id;
     DevBuf<double> veff, gnode;
+    // H quadratic in the real controls (qocx_set_quadratic_terms, QuadArgs): the augmented images
+    // ge_* (G_k then Q_q) and veff / gnode are shared with M4 on a linear system, which needs
+    // magnus_policy M4 - the two never coexist
+    int quad_count = 0;                  // 0: no quadratic terms
+    std::vector<int> quad_pairs;         // [count][2]
+    std::vector<double> quad_norm;       // ||Q_q||_1
+    DevBuf<int> quad_pairs_dev;
+    int hermitian_linear = 0;            // `hermitian` of H0 / G_k alone (qocx_set_quadratic_terms folds in the Q_q)
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;
@@ -635,7 +643,7 @@ int qocx_destroy(qocx_ctx* ctx) {
     ctx->lam_scale.release();
     ctx->offs_x.release();
     ctx->ge_cimg.release(); ctx->ge_rimg.release(); ctx->ge_timg.release();
-    ctx->interp_id.release(); ctx->veff.release(); ctx->gnode.release();
+    ctx->interp_id.release(); ctx->veff.release(); ctx->gnode.release(); ctx->quad_pairs_dev.release();
     ctx->ustep.release(); ctx->g_norm_dev.release(); ctx->lu_redo.release(); ctx->lu_fallbacks.release();
     ctx->opt_m.release(); ctx->opt_v.release(); ctx->opt_best_controls.release();
     ctx->opt_max_norms.release(); ctx->opt_best_final.release(); ctx->opt_flags.release();
@@ -761,7 +769,9 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
                 herm = is_hermitian(p->g + ((size_t)t * K + k) * n * n * 2);
         }
         ctx->hermitian = herm ? 1 : 0;
+        ctx->hermitian_linear = ctx->hermitian;
     }
+    ctx->quad_count = 0;  // a new problem clears the quadratic terms
     // Hamiltonian images + norms for the squaring bound
     std::vector<double2> img((size_t)nt * mat);
     ctx->h0_norm_max = 0;
@@ -923,6 +933,83 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     return 0;
 }
 
+int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs, const double* matrices) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
+    if (count < 0) return fail(QOCX_ERR_ARG, "count must be >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (count == 0) {
+        ctx->quad_count = 0;
+        ctx->hermitian = ctx->hermitian_linear;
+        ctx->have_results = false;
+        ctx->B = 0;  // the norm bound of the uploaded controls no longer applies
+        return 0;
+    }
+    if (!pairs || !matrices) return fail(QOCX_ERR_ARG, "pairs / matrices missing");
+    if (ctx->nodes != 1)
+        return fail(QOCX_ERR_ARG, "quadratic terms need magnus_policy M2 (M4 / M6 take the callable's tangent)");
+    if (ctx->explicit_mode) return fail(QOCX_ERR_ARG, "quadratic terms do not apply to explicit generators");
+    const int n = ctx->n, K = ctx->K, nt = ctx->nt, nb = ctx->nb, np = ctx->np;
+    if (K < 1) return fail(QOCX_ERR_ARG, "quadratic terms need control_count >= 1");
+    if (K + count > 64) return fail(QOCX_ERR_ARG, "control_count + quadratic term count must be <= 64");
+    for (int q = 0; q < count; ++q)
+        if (pairs[2 * q] < 0 || pairs[2 * q] > pairs[2 * q + 1] || pairs[2 * q + 1] >= K)
+            return fail(QOCX_ERR_ARG, "quadratic term pairs must satisfy 0 <= k <= l < control_count");
+    const size_t nn = (size_t)n * n, mat = (size_t)np * np;
+    const int Ke = K + count;
+    // With a time-dependent linear part the K1a / K3 tables are [nt][Ke]: every table entry carries
+    // the Q_q again. Three images (one on the general path) of nt * Ke padded matrices: bounded here.
+    const size_t images = ctx->general_path ? 1 : 3;
+    if ((size_t)nt * Ke * mat * sizeof(double2) * images > ((size_t)4 << 30))
+        return fail(QOCX_ERR_CAPACITY, "the augmented operator tables of the quadratic terms would exceed 4 GiB");
+    std::vector<double> norms(count);
+    bool herm = ctx->hermitian_linear != 0;
+    for (int q = 0; q < count; ++q) {
+        const double* m = matrices + (size_t)q * nn * 2;
+        for (size_t e = 0; e < nn * 2; ++e)
+            if (!std::isfinite(m[e])) return fail(QOCX_ERR_ARG, "non-finite quadratic term matrix");
+        norms[q] = one_norm(m, n);
+        for (int r = 0; r < n && herm; ++r)  // Hermitian bit for bit, as qocx_set_schroedinger_problem
+            for (int c = r; c < n && herm; ++c)
+                herm = m[2 * ((size_t)r * n + c)] == m[2 * ((size_t)c * n + r)] &&
+                       m[2 * ((size_t)r * n + c) + 1] == -m[2 * ((size_t)c * n + r) + 1];
+    }
+    // augmented images [nt][G_0 .. G_K-1, Q_0 .. Q_count-1], built on the device from the G_k images
+    std::vector<double2> qimg((size_t)count * mat);
+    DevBuf<double2> qdev;
+    for (int pass = ctx->general_path ? 2 : 0; pass < 3; ++pass) {
+        for (int q = 0; q < count; ++q) {
+            const double* m = matrices + (size_t)q * nn * 2;
+            if (pass == 0) c_image(m, n, nb, qimg.data() + (size_t)q * mat);
+            else r_image(m, n, np, pass == 2, qimg.data() + (size_t)q * mat);
+        }
+        if (qdev.upload(qimg, ctx->stream)) return QOCX_ERR_HIP;
+        DevBuf<double2>& src = pass == 0 ? ctx->g_cimg : (pass == 1 ? ctx->g_rimg : ctx->g_timg);
+        DevBuf<double2>& dst = pass == 0 ? ctx->ge_cimg : (pass == 1 ? ctx->ge_rimg : ctx->ge_timg);
+        if (dst.ensure((size_t)nt * Ke * mat)) return QOCX_ERR_HIP;
+        const size_t gbytes = (size_t)K * mat * sizeof(double2), qbytes = (size_t)count * mat * sizeof(double2);
+        HIP_TRY(hipMemcpy2DAsync(dst.p, gbytes + qbytes, src.p, gbytes, gbytes, nt, hipMemcpyDeviceToDevice,
+                                 ctx->stream));
+        for (int t = 0; t < nt; ++t)
+            HIP_TRY(hipMemcpyAsync(dst.p + ((size_t)t * Ke + K) * mat, qdev.p, qbytes, hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // qdev is released at the end of this scope
+    }
+    qdev.release();
+    std::vector<qocx::StepInterp> ident(ctx->nsteps);
+    for (int j = 0; j < ctx->nsteps; ++j) ident[j] = qocx::StepInterp{j, j, 1.0, 0.0};
+    std::vector<int> pr(pairs, pairs + 2 * (size_t)count);
+    if (ctx->interp_id.upload(ident, ctx->stream) || ctx->quad_pairs_dev.upload(pr, ctx->stream)) return QOCX_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->quad_pairs = pr;
+    ctx->quad_norm = norms;
+    ctx->quad_count = count;
+    ctx->hermitian = herm ? 1 : 0;
+    ctx->have_results = false;
+    ctx->B = 0;  // controls must be uploaded again: their norm bound now includes the Q_q
+    return 0;
+}
+
 }  // extern "C"
 
 // 1-norm bound of the step generator from the bound b >= ||dt a(t)|| of its node generators
@@ -969,6 +1056,19 @@ namespace qocx {
 size_t general_krylov_scratch(int np, int S);
 void launch_general_magnus(const MagnusArgs& a, bool vjp, int blocks, hipStream_t st);
 }
+// QuadArgs of a chunk of `bc` seeds whose real controls start at `controls`. The chain kernel writes
+// the per-step real-control cotangents into gnode, which scatter_kernel then reads (real, with
+// lam_scale already applied) - the m4lin arrangement.
+static qocx::QuadArgs quad_args(qocx_ctx* ctx, const double* controls, const double2* lam_scale, int bc) {
+    qocx::QuadArgs qa;
+    qa.controls = controls; qa.interp = ctx->interp.p; qa.pairs = ctx->quad_pairs_dev.p;
+    qa.K = ctx->K; qa.count = ctx->quad_count; qa.Ke = ctx->K + ctx->quad_count;
+    qa.nc = ctx->nc; qa.nsteps = ctx->nsteps; qa.S = ctx->S;
+    qa.veff = ctx->veff.p; qa.gstep = ctx->gstep.p; qa.lam_scale = lam_scale; qa.greal = ctx->gnode.p;
+    qa.total = (size_t)bc * ctx->nsteps;
+    return qa;
+}
+
 static int eval_general(qocx_ctx* ctx, int want_grad) {
     const int B = ctx->B, np = ctx->np, S = ctx->S, K = ctx->K, nsteps = ctx->nsteps;
     const size_t mat = (size_t)np * np;
@@ -977,8 +1077,10 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
     const bool m4lin = ctx->m4lin_Ke > 0 && ctx->nodes == 2 && !explicit_gen;
     // M6, and M4 on a time-dependent system: generators and reverse rules by qocx_general.hip's magnus_kernel
     const bool magnus = ctx->nodes > 1 && !m4lin && !explicit_gen;
+    // M2, H quadratic in the real controls: linear in Ke = K + count effective controls (QuadArgs)
+    const bool quad = ctx->quad_count > 0 && ctx->nodes == 1 && !explicit_gen;
     const int nodes = magnus ? ctx->nodes : 1;
-    const int Kk = m4lin ? ctx->m4lin_Ke : K;
+    const int Kk = m4lin ? ctx->m4lin_Ke : (quad ? K + ctx->quad_count : K);
     const size_t per_seed = (size_t)nsteps * (mat * 32 + 4) + ctx->slot_cap * S * np * 32 +
                             (size_t)(nsteps + 1) * 4 + (size_t)nsteps * std::max(Kk, 1) * 40;
     // (persistent workgroups with 7 scratch matrices each: as many as 16 GB hold, two per CU at most)
@@ -1001,6 +1103,7 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
         ctx->xs.ensure(want_grad ? (size_t)chunk * ctx->slot_cap * S * np : 1) ||
         ctx->offs.ensure((size_t)chunk * (nsteps + 1)) || ctx->gstep.ensure(cm * std::max(Kk, 1)) ||
         (m4lin && (ctx->veff.ensure(cm * Kk) || ctx->gnode.ensure(want_grad ? cm * 2 * K : 1))) ||
+        (quad && (ctx->veff.ensure(cm * Kk) || ctx->gnode.ensure(want_grad ? cm * K : 1))) ||
         ctx->cost_out.ensure(B) || ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) ||
         ctx->final_out.ensure((size_t)B * S * np) || ctx->lam_buf.ensure((size_t)chunk * S * np) ||
         ctx->magnus_scratch.ensure((size_t)blocks * 7 * mat))
@@ -1040,6 +1143,13 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
             m4.lam_scale = nullptr;
             m4.total = fa.total;
             qocx::launch_m4lin_controls(m4, cs);
+            fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_rm = ctx->ge_timg.p;
+            fa.K = Kk; fa.nc = nsteps;
+        }
+        qocx::QuadArgs qa;
+        if (quad) {
+            qa = quad_args(ctx, fa.controls, nullptr, bc);
+            qocx::launch_quad_controls(qa, cs);
             fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_rm = ctx->ge_timg.p;
             fa.K = Kk; fa.nc = nsteps;
         }
@@ -1131,6 +1241,10 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
                     qocx::launch_m4lin_chain(m4, cs);
                     sc.gstep = ctx->gnode.p;
                 }
+                if (quad) {  // effective-control cotangents -> real-control cotangents per step
+                    qocx::launch_quad_chain(qa, cs);
+                    sc.gstep = ctx->gnode.p;
+                }
                 qocx::launch_scatter(sc, cs);
                 time_end(ctx, cs);
             }
@@ -1159,6 +1273,7 @@ namespace {
 struct ResidentRoute {
     bool latency;        // one control set at a time (the host's single-evaluation entry points)
     bool m4lin;          // M4 on the M2 kernels (M4LinArgs): Ke controls per step, one node
+    bool quad;           // H quadratic in the real controls (QuadArgs): K + count controls per step
     int Kk;              // controls as K1a / K3 see them
     int nodes;           // nodes of the generator kernels
     bool dense;          // dense-state sweep (qocx_sweepd.hip)
@@ -1185,7 +1300,12 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // over "sweep_impl" = 3 there.
     r.latency = ctx->knob("latency", 0) != 0;
     r.m4lin = ctx->m4lin_Ke > 0 && ctx->nodes == 2 && !explicit_gen && ctx->knob("m4_linear", 1);
-    r.Kk = r.m4lin ? ctx->m4lin_Ke : ctx->K;
+    // The quadratic route makes the m4lin decisions below, each for the same reason: one effective
+    // control row per step read through interp_id (nodes 1), the unit adjoint with the scalar applied
+    // by the chain kernel, no step table (it interpolates the K real controls at the knots and bounds
+    // with ||G_k||_1 alone, blind to the Q_q), no pack8 (kept to the plain structured problem).
+    r.quad = ctx->quad_count > 0 && ctx->nodes == 1 && !explicit_gen;
+    r.Kk = r.m4lin ? ctx->m4lin_Ke : (r.quad ? ctx->K + ctx->quad_count : ctx->K);
     r.nodes = r.m4lin ? 1 : ctx->nodes;
     // 8..32 states of a seed as the columns of MFMA GEMMs, with P^-1 in place of the LU factors
     r.dense = qocx::sweepd_supports(nb, S) && ctx->knob("sweep_dense", 1) != 0;
@@ -1213,7 +1333,7 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // every step and decides its Pade order and squaring count from the bound dt (||H0||_1 + sum |u_k|
     // ||G_k||_1); K1a and K3 then read both instead of interpolating and (K1a) reducing a norm behind
     // a barrier.
-    r.step_table = nb == 2 && !r.one_wave_k1a && !explicit_gen && r.nodes == 1 && !r.m4lin && !r.dense &&
+    r.step_table = nb == 2 && !r.one_wave_k1a && !explicit_gen && r.nodes == 1 && !r.m4lin && !r.quad && !r.dense &&
                    ctx->K > 0 && ctx->g_norm_dev.p != nullptr;
     // every Pade denominator of the evaluation diagonally dominant by the margin of qocx_lu5.h
     // (eps_m(theta) <= 0.40 for every order m at the host's bound theta of the step norm)
@@ -1221,7 +1341,7 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // n <= 8: two consecutive steps of a seed as the diagonal blocks of one 16 x 16 tile through K1a
     // and K1b (pade_pq8_kernel, inv16_dpp_kernel<1, true>); the sweeps and K3 see the usual images
     r.pack8 = nb == 1 && ctx->n <= 8 && r.inverse_sweep && !r.dense && r.all_dominant && !explicit_gen &&
-              r.nodes == 1 && !r.m4lin && ctx->knob("pack8", 1) != 0;
+              r.nodes == 1 && !r.m4lin && !r.quad && ctx->knob("pack8", 1) != 0;
     // One control set at a time, inverse-image sweep: K1b's sibling umul_kernel leaves the propagator
     // itself in the Q image; the sweeps apply ONE matrix per sub-step, the adjoint sweep hands lambda'
     // to K3, which forms x = P^-H lambda' from the P^-1 image (knob "sweep_umode").
@@ -1255,6 +1375,7 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
         ctx->offs.ensure((size_t)chunk * (nsteps + 1)) ||
         ctx->gstep.ensure(cm * r.nodes * std::max(r.Kk, 1) * (r.unit ? 2 : 1)) || ctx->cost_out.ensure(B) ||
         (r.m4lin && (ctx->veff.ensure(cm * r.Kk) || ctx->gnode.ensure(want_grad ? cm * 2 * K : 1))) ||
+        (r.quad && (ctx->veff.ensure(cm * r.Kk) || ctx->gnode.ensure(want_grad ? cm * K : 1))) ||
         (r.unit && ctx->offs_x.ensure((size_t)chunk * (nsteps + 1))) ||
         ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) ||
         ctx->final_out.ensure((size_t)B * S * np) ||
@@ -1312,6 +1433,7 @@ struct ResidentChunk {
                    // sweep, bit 1 no adjoint sweep, bit 2 no K3, bit 3 K1a stores no Q
     qocx::FactorArgs fa;
     qocx::M4LinArgs m4;
+    qocx::QuadArgs qa;
     qocx::LuArgs la;
     qocx::MagnusArgs ma;
     qocx::SweepArgs sa;
@@ -1359,6 +1481,14 @@ struct ResidentChunk {
             m4.total = (size_t)bc * nsteps;
             time_begin(ctx, 0, cs);
             qocx::launch_m4lin_controls(m4, cs);
+            time_end(ctx, cs);
+            fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_cimg = ctx->ge_cimg.p;
+            fa.K = r.Kk; fa.nc = nsteps;
+        }
+        if (r.quad) {
+            qa = quad_args(ctx, fa.controls, r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr, bc);
+            time_begin(ctx, 0, cs);
+            qocx::launch_quad_controls(qa, cs);
             time_end(ctx, cs);
             fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_cimg = ctx->ge_cimg.p;
             fa.K = r.Kk; fa.nc = nsteps;
@@ -1484,8 +1614,8 @@ struct ResidentChunk {
         ka.controls = fa.controls;
         ka.interp = fa.interp;
         ka.h0_rimg = ctx->h0_rimg.p; ka.h0_timg = ctx->h0_timg.p;
-        ka.g_rimg = r.m4lin ? ctx->ge_rimg.p : ctx->g_rimg.p;
-        ka.g_timg = r.m4lin ? ctx->ge_timg.p : ctx->g_timg.p;
+        ka.g_rimg = (r.m4lin || r.quad) ? ctx->ge_rimg.p : ctx->g_rimg.p;
+        ka.g_timg = (r.m4lin || r.quad) ? ctx->ge_timg.p : ctx->g_timg.p;
         ka.K = fa.K; ka.nc = fa.nc; ka.nsteps = nsteps; ka.nt = ctx->nt; ka.S = S;
         ka.umode = r.umode ? 1 : 0;
         ka.pinv_img = fa.lu_img;
@@ -1700,6 +1830,26 @@ int run_two_sided(ResidentChunk& c) {
     return 0;
 }
 
+// sum_q ||Q_q||_1 umax[k_q] umax[l_q]: with umax[k] >= max_t |r_k(t)|, a bound of the quadratic
+// terms' share of ||H(t)||_1 at every time, between knots included
+double quad_bound(const qocx_ctx* ctx, const double* umax) {
+    double b = 0.0;
+    for (int q = 0; q < ctx->quad_count; ++q)
+        b += ctx->quad_norm[q] * fabs(umax[ctx->quad_pairs[2 * q]]) * fabs(umax[ctx->quad_pairs[2 * q + 1]]);
+    return b;
+}
+
+// max over `rows` rows of [rows][K] controls of |r_k|, per k (NaN propagates)
+std::vector<double> quad_control_max(const double* rows_p, size_t rows, int K) {
+    std::vector<double> m(K, 0.0);
+    for (size_t row = 0; row < rows; ++row)
+        for (int k = 0; k < K; ++k) {
+            const double a = fabs(rows_p[row * K + k]);
+            if (!(a <= m[k])) m[k] = a;
+        }
+    return m;
+}
+
 // per-step control cotangents -> the chunk's control gradients
 void scatter_gradients(ResidentChunk& c) {
     qocx_ctx* ctx = c.ctx;
@@ -1713,6 +1863,11 @@ void scatter_gradients(ResidentChunk& c) {
     time_begin(ctx, 3, c.cs);
     if (c.r.m4lin) {  // effective-control cotangents -> node cotangents (applies the scalar)
         qocx::launch_m4lin_chain(c.m4, c.cs);
+        sc.gstep = ctx->gnode.p;
+        sc.lam_scale = nullptr;
+    }
+    if (c.r.quad) {  // effective-control cotangents -> real-control cotangents (applies the scalar)
+        qocx::launch_quad_chain(c.qa, c.cs);
         sc.gstep = ctx->gnode.p;
         sc.lam_scale = nullptr;
     }
@@ -1770,11 +1925,15 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
             }
             sprev = srow;
         }
-        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1)
+        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->quad_count == 0)
             ctx->norm_bound_mid = (bound + smid) * fabs(ctx->dt) * (1.0 + 1e-12);
         else
             ctx->norm_bound_mid = 1e300;
         bound += smax;
+        // Quadratic terms: r_k(t) r_l(t) is not convex between knots (r_k 0 -> a, r_l a -> 0 peaks at
+        // a^2 / 4 mid-interval), so the knot sums above do not bound it. |r_k(t)| <= max over the knots of
+        // |r_k| does hold everywhere (linear interpolation): ||Q_q||_1 max|r_k| max|r_l| bounds every step.
+        if (ctx->quad_count > 0) bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, K).data());
         if (ctx->controls.ensure(total)) return QOCX_ERR_HIP;
         HIP_TRY(hipMemcpyAsync(ctx->controls.p, stage, total * sizeof(double), hipMemcpyHostToDevice,
                                ctx->stream));
@@ -3136,6 +3295,7 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
         bound += max_norms[k] * ctx->g_norm_max[k];
     }
+    bound += quad_bound(ctx, max_norms);  // (quadratic terms: ||Q_q||_1 max_norms_k max_norms_l)
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
     const int sb = pade_scale_count(bound);

@@ -235,6 +235,19 @@ struct M4LinArgs {
     size_t total;              // B * nsteps
 };
 
+// Hamiltonian quadratic in the real controls (qocx_quad.hip): Ke = K + count effective controls
+struct QuadArgs {
+    const double* controls;    // [B][nc][K]
+    const StepInterp* interp;  // [nsteps]
+    const int* pairs;          // [count][2], k <= l
+    int K, Ke, count, nc, nsteps, S;
+    double* veff;              // controls kernel out: [B][nsteps][Ke]
+    const double* gstep;       // chain kernel in: [B][nsteps][Ke] (x 2: complex, unit adjoint)
+    const double2* lam_scale;  // unit adjoint: [B][S] (see ScatterArgs), or nullptr
+    double* greal;             // chain kernel out: [B][nsteps][K], read by scatter_kernel
+    size_t total;              // B * nsteps
+};
+
 struct ScatterArgs {
     const double* gstep;
     const int* row_ptr;   // [nc+1]
@@ -464,6 +477,8 @@ void launch_magnus4w_fwd(const MagnusArgs& a, int batch, hipStream_t st);
 void launch_magnus4w_vjp(const MagnusArgs& a, int batch, hipStream_t st);
 void launch_m4lin_controls(const M4LinArgs& a, hipStream_t st);
 void launch_m4lin_chain(const M4LinArgs& a, hipStream_t st);
+void launch_quad_controls(const QuadArgs& a, hipStream_t st);
+void launch_quad_chain(const QuadArgs& a, hipStream_t st);
 void launch_selftest(double* out, hipStream_t st);
 
 }  // namespace qocx

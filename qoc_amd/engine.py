@@ -119,6 +119,7 @@ SIGNATURES = {
     "qocx_download_results": (ctypes.c_int, [_VP, _c_double_p, _c_double_p, _c_double_p]),
     "qocx_upload_generators": (ctypes.c_int, [_VP, _I32, _c_double_p]),
     "qocx_download_generator_cotangents": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_set_quadratic_terms": (ctypes.c_int, [_VP, _I32, _c_int_p, _c_double_p]),
     "qocx_set_keep_step_states": (ctypes.c_int, [_VP, _I32]),
     "qocx_download_step_states": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_lindblad_problem": (ctypes.c_int, [_VP, ctypes.POINTER(_LindbladProblem)]),
@@ -308,6 +309,18 @@ class Engine(object):
         p.costs = descs
         self._check(self._lib.qocx_set_schroedinger_problem(self._ctx, ctypes.byref(p)))
         self._problem = dict(n=n, S=S, K=K, Nc=int(control_eval_count), N=int(system_eval_count))
+        self.batch = 0
+
+    def set_quadratic_terms(self, pairs, matrices):
+        """+ sum_q r_k r_l Q_q on the current problem (qocx_set_quadratic_terms): pairs :: (count, 2)
+        real-control indices k <= l, matrices :: (count, n, n) complex. An empty `pairs` clears them.
+        Controls must be uploaded again afterwards."""
+        n = self._problem["n"]
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        count = pairs.shape[0]
+        mats = _as_complex(matrices if count else np.zeros((0, n, n)), (count, n, n))
+        self._check(self._lib.qocx_set_quadratic_terms(
+            self._ctx, count, pairs.ctypes.data_as(_c_int_p), _dp(mats)))
         self.batch = 0
 
     # -- evaluation ----------------------------------------------------------------------------
