@@ -207,6 +207,33 @@ int qocx_download_generator_cotangents(qocx_ctx* ctx, double* cotangents_out);
  */
 int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs, const double* matrices);
 
+/*
+ * Hamiltonian ensembles (robust GRAPE): M members of the problem, all driven by the same seed
+ * controls u. Call after qocx_set_schroedinger_problem, whose LAST `fixed` = J control channels
+ * are the perturbation matrices D_j; K_r = control_count - J channels remain for the seeds.
+ * Member m of seed b evaluates the problem on the K-channel controls
+ *     r[j][k] = s_mk u_b[j][k] (k < K_r),   r[j][K_r + i] = delta_mi (every knot)
+ * i.e. H_m(u, t) = H(s_m . u, t) + sum_i delta_mi D_i.
+ *   scales  [M][K_r] (NULL: all 1)   offsets [M][J] (NULL exactly when J = 0)   weights [M] >= 0
+ * QOCX_ERR_ARG unless 1 <= M <= 1024, 0 <= J < control_count, every input is finite and no
+ * quadratic terms are set. A new problem clears the ensemble. Controls must be uploaded afterwards.
+ * With an ensemble set:
+ *   qocx_upload_controls(ctx, B, controls [B][Nc][K_r]) keeps the seed controls on the device and
+ *     expands them into the B x M items (item b * M + m); the squaring bounds are those of the
+ *     expanded array.
+ *   qocx_eval_resident evaluates the items as any batch, then reduces them in member order:
+ *     cost_b = sum_m w_m c_bm, grad_b[j][k] = sum_m w_m s_mk dc_bm / dr[j][k] (k < K_r; the
+ *     gradients of the fixed channels are dropped).
+ *   qocx_download_results (costs [B], gradients [B][Nc][K_r], final states [B][M][S][n]),
+ *   qocx_download_costs, qocx_reduce_results and qocx_opt_* act on the B seeds and their K_r
+ *     channels (qocx_opt_clip takes max_norms [K_r]; the best final states are [B][M][S][n]).
+ *   qocx_download_step_states returns the items, [B][M][N][S][n].
+ * qocx_ensemble_download_members: the unweighted cost of every item of the last evaluation, [B][M].
+ */
+int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
+                      const double* offsets, const double* weights);
+int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out);
+
 /* Optional: all system-step states of the last evaluation, [B][N][S][n] complex
  * (what save_intermediate_states persists, schroedingerdiscrete.py:395-402). */
 int qocx_set_keep_step_states(qocx_ctx* ctx, int32_t keep); /* before the evaluation */

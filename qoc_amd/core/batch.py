@@ -33,14 +33,19 @@ class BatchResult(object):
         self.best_iteration = np.full(seed_count, -1, dtype=np.int64)
         self.iterations_run = np.zeros(seed_count, dtype=np.int64)
         self.global_best_error = None
+        # Hamiltonian ensembles: per seed, the members' unweighted costs at the best controls
+        self.member_errors = [None] * seed_count
 
     @property
     def best(self):
         b = int(np.argmin(self.best_error))
-        return self.single_result(
+        out = self.single_result(
             best_controls=self.best_controls[b], best_error=float(self.best_error[b]),
             best_iteration=int(self.best_iteration[b]),
             **{self.final_field: getattr(self, self.final_field)[b]})
+        if self.member_errors[b] is not None:
+            out.member_errors = self.member_errors[b]
+        return out
 
 
 def _optimizer_clone(optimizer, flat_controls):

@@ -11,7 +11,7 @@ import numpy as np
 
 from qoc_amd.core import structure
 from qoc_amd.models.policies import InterpolationPolicy, MagnusPolicy
-from qoc_amd.standard.hamiltonians import QuadraticHamiltonian
+from qoc_amd.standard.hamiltonians import HamiltonianEnsemble, QuadraticHamiltonian
 
 def make_backend(device=-1):
     """The HIP engine. There is no CPU fallback: this raises when libqocx.so or the GPU is
@@ -129,6 +129,16 @@ class SchroedingerEvaluator(object):
         # engine evaluates it as linear in the effective controls (r_k, r_k r_l), the callable is
         # never called per evaluation. Elsewhere it is just a callable (the routes below).
         self.quadratic_terms = None
+        # A HamiltonianEnsemble: its linear base goes in structured form with the perturbation
+        # matrices D_j appended to the G_k as J extra channels, and the engine expands every seed
+        # into the M members' (K_r + J)-channel controls (qocx_set_ensemble). Evaluations return
+        # the weighted seed costs and gradients, and final states with a member axis.
+        self.ensemble = None
+        if isinstance(hamiltonian, HamiltonianEnsemble):
+            if backend is None:
+                backend = make_backend()
+            hamiltonian = self._ensemble_base(hamiltonian, control_count, complex_controls,
+                                              backend)
         if isinstance(hamiltonian, QuadraticHamiltonian) and backend is None:
             backend = make_backend()  # (the route depends on what the backend takes)
         if (isinstance(hamiltonian, QuadraticHamiltonian) and magnus_policy == MagnusPolicy.M2
@@ -142,7 +152,11 @@ class SchroedingerEvaluator(object):
         try:
             h0, g = structure.probe_hamiltonian(probed, self.hilbert_size, control_count,
                                                 complex_controls, times)
-        except structure.NonLinearHamiltonianError:
+        except structure.NonLinearHamiltonianError as exc:
+            if self.ensemble is not None:
+                raise NotImplementedError(
+                    "a HamiltonianEnsemble needs a base hamiltonian linear in the controls "
+                    "({})".format(exc))
             if self.quadratic_terms is not None:
                 raise
             if magnus_policy != MagnusPolicy.M2:
@@ -172,6 +186,13 @@ class SchroedingerEvaluator(object):
                 self.host_costs.append(cost)
             else:
                 self.opaque_costs.append(cost)
+        if self.ensemble is not None:
+            if self.opaque_costs:
+                raise NotImplementedError(
+                    "a HamiltonianEnsemble takes costs evaluated on the device (with a "
+                    "device_descriptor()) and costs of the controls alone; {} is neither"
+                    "".format(self.opaque_costs[0]))
+            g = self._append_perturbations(g)
         self.backend = backend if backend is not None else make_backend()
         if hasattr(self.backend, "set_knob"):
             self.backend.set_knob(
@@ -179,6 +200,8 @@ class SchroedingerEvaluator(object):
             self.backend.set_knob("latency", 1 if latency_mode else 0)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
+        if self.ensemble is not None:
+            device_k += self.ensemble.perturbation_count
         self._problem_static = (
             (self.hilbert_size, self.state_count, device_k, control_eval_count if device_k else 0,
              system_eval_count, evolution_time),
@@ -193,6 +216,45 @@ class SchroedingerEvaluator(object):
         self.backend.set_schroedinger_problem(*head, h0, g, psi0, **kw)
         if self.quadratic_terms is not None:
             self.backend.set_quadratic_terms(*self.quadratic_terms)
+        if self.ensemble is not None:
+            self.backend.set_ensemble(*self._ensemble_args)
+
+    # -- Hamiltonian ensembles ------------------------------------------------------------------
+    def _ensemble_base(self, ensemble, control_count, complex_controls, backend):
+        """Checks an ensemble against this problem and the backend; returns its base Hamiltonian
+        (probed like any linear one)."""
+        base = ensemble.hamiltonian
+        if control_count == 0:
+            raise NotImplementedError("a HamiltonianEnsemble needs at least one control "
+                                      "(control_count = 0)")
+        if isinstance(base, (QuadraticHamiltonian, HamiltonianEnsemble)):
+            raise NotImplementedError(
+                "a HamiltonianEnsemble needs a base hamiltonian linear in the controls, got {!r}"
+                "".format(base))
+        if not hasattr(backend, "set_ensemble"):
+            raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian ensembles "
+                                      "(no set_ensemble)".format(backend))
+        if ensemble.hilbert_size is not None and ensemble.hilbert_size != self.hilbert_size:
+            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
+                ensemble.hilbert_size, self.hilbert_size))
+        scales = ensemble.real_channel_scales(control_count, complex_controls)
+        self.ensemble = ensemble
+        self._ensemble_args = (scales if ensemble.control_scales is not None else None,
+                               ensemble.offsets, ensemble.weights)
+        return base
+
+    def _append_perturbations(self, g):
+        """G (nt, K_r, n, n) -> [G_1 .. G_K_r, D_1 .. D_J] in every one of the nt tables."""
+        d = self.ensemble.perturbations
+        if d is None:
+            return g
+        g = np.asarray(g, dtype=np.complex128)
+        return np.concatenate([g, np.broadcast_to(d[None], (g.shape[0],) + d.shape)], axis=1)
+
+    def member_errors(self):
+        """The unweighted device cost of every member of every seed of the last evaluation,
+        (B, M)."""
+        return self.backend.ensemble_member_costs()
 
     # -- device round trip: structured controls, or generators sampled from an opaque callable ----
     def _upload(self, controls_batch, device_controls):
@@ -272,7 +334,9 @@ class SchroedingerEvaluator(object):
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
         """
         controls_batch :: (B x Nc x K) (or None / an int B when control_count == 0).
-        Returns (errors[B], grads[B x Nc x K] or None, final_states[B x S x n x 1], step_states).
+        Returns (errors[B], grads[B x Nc x K] or None, final_states[B x S x n x 1], step_states);
+        with an ensemble the final states are [B x M x S x n x 1] and the step states, if asked
+        for, [B x M x N x S x n x 1].
         """
         if self.control_count == 0:
             batch = 1 if controls_batch is None else int(controls_batch)
@@ -392,6 +456,9 @@ class LindbladEvaluator(object):
         if interpolation_policy != InterpolationPolicy.LINEAR:
             raise NotImplementedError("This operation does not yet support the interpolation "
                                       "policy {}.".format(interpolation_policy))
+        if isinstance(hamiltonian, HamiltonianEnsemble):
+            raise NotImplementedError("Hamiltonian ensembles are evaluated on the Schroedinger path "
+                                      "only, not on the Lindblad path")
         self._cost_controls = None
         if frozen_controls is not None:
             if need_gradients:

@@ -20,7 +20,15 @@ from qoc_amd.core.structure import NonLinearHamiltonianError
 from qoc_amd.models import (Dummy, EvolveLindbladDiscreteState, EvolveLindbladResult,
                             GrapeLindbladDiscreteState, GrapeLindbladResult,
                             InterpolationPolicy)
+from qoc_amd.standard.hamiltonians import HamiltonianEnsemble
 from qoc_amd.standard.optimizers import Adam
+
+
+def _reject_ensemble(hamiltonian):
+    """Before any save file is touched: ensembles run on the Schroedinger path only."""
+    if isinstance(hamiltonian, HamiltonianEnsemble):
+        raise NotImplementedError("Hamiltonian ensembles are evaluated on the Schroedinger path "
+                                  "only, not on the Lindblad path")
 
 
 def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_count,
@@ -34,6 +42,7 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
     lindblad_data :: (time) -> (dissipators (L), operators (L x n x n)).
     Returns EvolveLindbladResult{error, final_densities}.
     """
+    _reject_ensemble(hamiltonian)
     if controls is not None:
         controls = np.asarray(controls)
         control_eval_count, control_count = controls.shape[0], controls.shape[1]
@@ -81,6 +90,7 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
     Returns GrapeLindbladResult{best_controls, best_error, best_final_densities,
     best_iteration}.
     """
+    _reject_ensemble(hamiltonian)
     initial_controls, max_control_norms = initialize_controls(
         complex_controls, control_count, control_eval_count, evolution_time, initial_controls,
         max_control_norms)
@@ -192,6 +202,7 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     LindbladEvaluator.evaluate_batch. Both routes give the same numbers.
     Returns GrapeLindbladBatchResult.
     """
+    _reject_ensemble(hamiltonian)
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
         max_control_norms, impose_control_conditions, comm)

@@ -16,7 +16,14 @@ from qoc_amd.core.device import SchroedingerEvaluator
 from qoc_amd.models import (Dummy, EvolveSchroedingerDiscreteState, EvolveSchroedingerResult,
                             GrapeSchroedingerDiscreteState, GrapeSchroedingerResult,
                             InterpolationPolicy, MagnusPolicy)
+from qoc_amd.standard.hamiltonians import HamiltonianEnsemble
 from qoc_amd.standard.optimizers import Adam
+
+
+def _check_ensemble_save(hamiltonian, save_file_path):
+    if isinstance(hamiltonian, HamiltonianEnsemble) and save_file_path is not None:
+        raise NotImplementedError("save files are not written for a HamiltonianEnsemble "
+                                  "(save_file_path must be None)")
 
 
 def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, system_eval_count,
@@ -31,8 +38,12 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
     evolution_time :: float; hamiltonian :: (controls (control_count), time) -> (n x n);
     initial_states :: (state_count x n x 1); system_eval_count :: int >= 2;
     controls :: (control_eval_count x control_count) or None; costs :: iterable(Cost).
-    Returns EvolveSchroedingerResult{error, final_states}.
+    Returns EvolveSchroedingerResult{error, final_states}. With a HamiltonianEnsemble
+    (qoc_amd.standard) the error is the weighted sum over its members, final_states gains a
+    member axis (M x state_count x n x 1) and the result's member_errors holds each member's
+    unweighted device cost.
     """
+    _check_ensemble_save(hamiltonian, save_file_path)
     if controls is not None:
         controls = np.asarray(controls)
         control_eval_count, control_count = controls.shape[0], controls.shape[1]
@@ -53,7 +64,11 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
         controls, want_grad=False, want_step_states=pstate.save_intermediate_states_)
     if pstate.save_intermediate_states_:
         pstate.save_all_intermediate_states(0, step_states)
-    return EvolveSchroedingerResult(error=error, final_states=final_states)
+    member_errors = None
+    if getattr(evaluator, "ensemble", None) is not None:
+        member_errors = evaluator.member_errors()[0]
+    return EvolveSchroedingerResult(error=error, final_states=final_states,
+                                    member_errors=member_errors)
 
 
 def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolution_time,
@@ -69,7 +84,11 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     Optimize time-discrete controls for the evolution of a set of states (GRAPE).
     Arguments as in the reference (schroedingerdiscrete.py:106-212).
     Returns GrapeSchroedingerResult{best_controls, best_error, best_final_states, best_iteration}.
+    With a HamiltonianEnsemble the error is the weighted sum over its members, best_final_states
+    has a member axis, and member_errors holds each member's unweighted device cost at
+    best_controls (one forward evaluation after the loop).
     """
+    _check_ensemble_save(hamiltonian, save_file_path)
     initial_controls, max_control_norms = initialize_controls(
         complex_controls, control_count, control_eval_count, evolution_time, initial_controls,
         max_control_norms)
@@ -92,6 +111,10 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     flat_controls = strip_controls(pstate.complex_controls, pstate.initial_controls)
     pstate.optimizer.run(_esd_wrap, pstate.iteration_count, flat_controls, _esdj_wrap,
                          args=(pstate, reporter, result))
+    if (getattr(pstate.evaluator, "ensemble", None) is not None
+            and result.best_controls is not None):
+        pstate.evaluator.evaluate(result.best_controls, want_grad=False)
+        result.member_errors = pstate.evaluator.member_errors()[0]
     return result
 
 
@@ -180,18 +203,24 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     max_control_norms. comm (qoc_amd.parallel communicator, optional): the seed axis is sharded
     over its ranks, every rank optimises its own block, and the logged error is the all-reduced
     sum (the path's single collective); result arrays are rank local.
+    With a HamiltonianEnsemble (qoc_amd.standard) every seed is evaluated over its M members: the
+    errors are the weighted sums, the final states have a member axis, and member_errors[b] holds
+    seed b's unweighted member costs at its best controls (one forward evaluation of all seeds
+    after the loop).
     Returns GrapeSchroedingerBatchResult.
     """
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
         max_control_norms, impose_control_conditions, comm)
     B = params.shape[0]
+    # (latency mode up to 128 evaluated items: an ensemble evaluates M per seed)
+    items = B * (hamiltonian.member_count if isinstance(hamiltonian, HamiltonianEnsemble) else 1)
     evaluator = SchroedingerEvaluator(
         evolution_time, hamiltonian, initial_states, system_eval_count,
         control_count=control_count, control_eval_count=control_eval_count,
         complex_controls=complex_controls, costs=costs, cost_eval_step=cost_eval_step,
         interpolation_policy=interpolation_policy, magnus_policy=magnus_policy,
-        need_gradients=True, latency_mode=B <= 128)
+        need_gradients=True, latency_mode=items <= 128)
     stepper = batch.batched_stepper(optimizer, params)
     result = GrapeSchroedingerBatchResult(B)
     run = (iteration_count, log_iteration_step, min_error, comm, result)
@@ -199,6 +228,22 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     # so far stay in HBM; per iteration the host sees B costs and sends 2 B flags. The same
     # iteration, the same arithmetic (qocx_optim.hip: IEEE operations in the reference's order).
     if batch.resident_route(stepper, optimizer, pstate, evaluator, B):
-        return batch.run_batch_resident(_ResidentOps(evaluator.backend), optimizer, params, pstate,
-                                        *run)
-    return batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
+        out = batch.run_batch_resident(_ResidentOps(evaluator.backend), optimizer, params, pstate,
+                                       *run)
+    else:
+        out = batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
+    if getattr(evaluator, "ensemble", None) is not None:
+        _ensemble_member_errors(evaluator, out)
+    return out
+
+
+def _ensemble_member_errors(evaluator, result):
+    """result.member_errors[b]: the members' unweighted costs at seed b's best controls, from one
+    forward evaluation of every seed that has best controls."""
+    seeds = [b for b in range(len(result.best_controls)) if result.best_controls[b] is not None]
+    if not seeds:
+        return
+    evaluator.evaluate_batch(np.stack([result.best_controls[b] for b in seeds]), want_grad=False)
+    members = evaluator.member_errors()
+    for i, b in enumerate(seeds):
+        result.member_errors[b] = members[i]

@@ -244,6 +244,17 @@ struct qocx_ctx {
     std::vector<double> quad_norm;       // ||Q_q||_1
     DevBuf<int> quad_pairs_dev;
     int hermitian_linear = 0;            // `hermitian` of H0 / G_k alone (qocx_set_quadratic_terms folds in the Q_q)
+    // Hamiltonian ensemble (qocx_set_ensemble, EnsembleArgs): the last ens_J of the problem's K channels
+    // are fixed perturbation channels; controls, costs and gradients of the seeds live in ens_* and the
+    // evaluation buffers (controls, cost_out, grads, final_out) hold the B x M member items
+    int ens_M = 0;                       // 0: no ensemble
+    int ens_J = 0, ens_Kr = 0;           // fixed channels, seed channels (K = ens_Kr + ens_J)
+    int ens_B = 0;                       // seeds of the last upload (ctx->B = ens_B * ens_M)
+    bool ens_stale = false;              // ens_controls moved (qocx_opt_clip / _step) since the expansion
+    std::vector<double> ens_scales_h, ens_offsets_h;    // [M][Kr], [M][J]
+    std::vector<double> ens_scale_max, ens_offset_max;  // max_m |s_mk|, max_m |delta_mj|
+    DevBuf<double> ens_scales, ens_offsets, ens_weights;
+    DevBuf<double> ens_controls, ens_cost, ens_grads;   // [B][nc][Kr], [B], [B][nc][Kr]
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;
@@ -644,6 +655,8 @@ int qocx_destroy(qocx_ctx* ctx) {
     ctx->offs_x.release();
     ctx->ge_cimg.release(); ctx->ge_rimg.release(); ctx->ge_timg.release();
     ctx->interp_id.release(); ctx->veff.release(); ctx->gnode.release(); ctx->quad_pairs_dev.release();
+    ctx->ens_scales.release(); ctx->ens_offsets.release(); ctx->ens_weights.release();
+    ctx->ens_controls.release(); ctx->ens_cost.release(); ctx->ens_grads.release();
     ctx->ustep.release(); ctx->g_norm_dev.release(); ctx->lu_redo.release(); ctx->lu_fallbacks.release();
     ctx->opt_m.release(); ctx->opt_v.release(); ctx->opt_best_controls.release();
     ctx->opt_max_norms.release(); ctx->opt_best_final.release(); ctx->opt_flags.release();
@@ -772,6 +785,7 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
         ctx->hermitian_linear = ctx->hermitian;
     }
     ctx->quad_count = 0;  // a new problem clears the quadratic terms
+    ctx->ens_M = 0;       // ... and the ensemble
     // Hamiltonian images + norms for the squaring bound
     std::vector<double2> img((size_t)nt * mat);
     ctx->h0_norm_max = 0;
@@ -937,6 +951,8 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
     if (count < 0) return fail(QOCX_ERR_ARG, "count must be >= 0");
+    if (ctx->ens_M > 0 && count > 0)
+        return fail(QOCX_ERR_ARG, "quadratic terms do not combine with an ensemble (qocx_set_ensemble)");
     HIP_TRY(hipSetDevice(ctx->device));
     if (count == 0) {
         ctx->quad_count = 0;
@@ -1007,6 +1023,54 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     ctx->hermitian = herm ? 1 : 0;
     ctx->have_results = false;
     ctx->B = 0;  // controls must be uploaded again: their norm bound now includes the Q_q
+    return 0;
+}
+
+int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
+                      const double* offsets, const double* weights) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
+    if (members < 1 || members > 1024) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
+    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
+    if (fixed >= ctx->K)
+        return fail(QOCX_ERR_ARG, "an ensemble needs fixed < control_count (at least one seed control)");
+    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed perturbation channels need offsets");
+    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 perturbation channels");
+    if (!weights) return fail(QOCX_ERR_ARG, "weights missing");
+    if (ctx->quad_count > 0)
+        return fail(QOCX_ERR_ARG, "an ensemble needs a Hamiltonian linear in the controls (no quadratic terms)");
+    const int M = members, J = fixed, Kr = ctx->K - fixed;
+    std::vector<double> sc((size_t)M * Kr, 1.0), off((size_t)M * J), w(weights, weights + M);
+    if (scales) sc.assign(scales, scales + sc.size());
+    if (J > 0) off.assign(offsets, offsets + off.size());
+    for (double v : sc)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble control scale");
+    for (double v : off)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble offset");
+    for (double v : w)
+        if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "ensemble weights must be finite and >= 0");
+    std::vector<double> smax(Kr, 0.0), omax(J, 0.0);
+    for (int m = 0; m < M; ++m) {
+        for (int k = 0; k < Kr; ++k) smax[k] = std::max(smax[k], fabs(sc[(size_t)m * Kr + k]));
+        for (int j = 0; j < J; ++j) omax[j] = std::max(omax[j], fabs(off[(size_t)m * J + j]));
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->ens_scales.upload(sc, ctx->stream) || ctx->ens_weights.upload(w, ctx->stream) ||
+        (J > 0 && ctx->ens_offsets.upload(off, ctx->stream)))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->ens_scales_h = sc;
+    ctx->ens_offsets_h = off;
+    ctx->ens_scale_max = smax;
+    ctx->ens_offset_max = omax;
+    ctx->ens_M = M;
+    ctx->ens_J = J;
+    ctx->ens_Kr = Kr;
+    ctx->ens_B = 0;
+    ctx->ens_stale = false;
+    ctx->have_results = false;
+    ctx->B = 0;  // controls must be uploaded again (as seed controls)
+    ctx->opt_batch = 0;
     return 0;
 }
 
@@ -1875,6 +1939,75 @@ void scatter_gradients(ResidentChunk& c) {
     time_end(ctx, c.cs);
 }
 
+// ---- Hamiltonian ensembles (qocx_set_ensemble) ----------------------------------------------------
+
+qocx::EnsembleArgs ensemble_args(qocx_ctx* ctx, int seeds) {
+    qocx::EnsembleArgs a;
+    a.seed_controls = ctx->ens_controls.p; a.scales = ctx->ens_scales.p;
+    a.offsets = ctx->ens_J > 0 ? ctx->ens_offsets.p : nullptr; a.weights = ctx->ens_weights.p;
+    a.controls = ctx->controls.p;
+    a.member_cost = ctx->cost_out.p; a.member_grads = ctx->grads.p;
+    a.cost = ctx->ens_cost.p; a.grads = ctx->ens_grads.p;
+    a.B = seeds; a.M = ctx->ens_M; a.nc = ctx->nc; a.K = ctx->K; a.Kr = ctx->ens_Kr; a.J = ctx->ens_J;
+    return a;
+}
+
+// The seeds' controls into the pinned staging buffer, and the bounds qocx_upload_controls takes from
+// a control array: here those of the expanded [B][M][nc][K] array - the same per-row sum in the same
+// order over the member rows (s_mk u_bjk for k < K_r, delta_mj beyond), so they equal bit for bit
+// what an upload of the expanded array gives.
+void ensemble_stage(const qocx_ctx* ctx, int batch, const double* controls, double* stage, double& smax,
+                    double& smid) {
+    const int M = ctx->ens_M, Kr = ctx->ens_Kr, J = ctx->ens_J, nc = ctx->nc;
+    const double* gn = ctx->g_norm_max.data();
+    memcpy(stage, controls, (size_t)batch * nc * Kr * sizeof(double));
+    double sprev = 0.0;
+    for (int b = 0; b < batch; ++b)
+        for (int m = 0; m < M; ++m) {
+            const double* s = ctx->ens_scales_h.data() + (size_t)m * Kr;
+            const double* d = ctx->ens_offsets_h.data() + (size_t)m * J;
+            for (int j = 0; j < nc; ++j) {
+                const double* u = controls + ((size_t)b * nc + j) * Kr;
+                double srow = 0.0;
+                for (int k = 0; k < Kr; ++k) srow += fabs(s[k] * u[k]) * gn[k];
+                for (int k = 0; k < J; ++k) srow += fabs(d[k]) * gn[Kr + k];
+                if (!(srow <= smax)) smax = srow;  // also catches NaN
+                if (j != 0) {
+                    const double mid = 0.5 * (sprev + srow);
+                    if (!(mid <= smid)) smid = mid;
+                }
+                sprev = srow;
+            }
+        }
+}
+
+// expand the seeds' controls into the member items of ctx->controls
+int ensemble_expand(qocx_ctx* ctx, int seeds) {
+    qocx::launch_ensemble_expand(ensemble_args(ctx, seeds), ctx->stream);
+    HIP_TRY(hipGetLastError());
+    ctx->ens_stale = false;
+    return 0;
+}
+
+// the staged seed controls to the device, expanded there
+int ensemble_upload(qocx_ctx* ctx, int batch, const double* stage) {
+    const size_t seeds = (size_t)batch * ctx->nc * ctx->ens_Kr;
+    const size_t items = (size_t)batch * ctx->ens_M * ctx->nc * ctx->K;
+    if ((items + 255) / 256 > 0x7fffffffu) return fail(QOCX_ERR_ARG, "ensemble control arrays too large");
+    if (ctx->ens_controls.ensure(seeds) || ctx->controls.ensure(items)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(ctx->ens_controls.p, stage, seeds * sizeof(double), hipMemcpyHostToDevice,
+                           ctx->stream));
+    return ensemble_expand(ctx, batch);
+}
+
+// The seed-level view: with an ensemble the entry points of the host's optimizer loop (costs,
+// gradients, qocx_opt_*) act on the seeds and their K_r channels, else on the items themselves.
+int seed_count(const qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_B : ctx->B; }
+int seed_channels(const qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_Kr : ctx->K; }
+double* seed_controls(qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_controls.p : ctx->controls.p; }
+double* seed_costs(qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_cost.p : ctx->cost_out.p; }
+double* seed_grads(qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_grads.p : ctx->grads.p; }
+
 }  // namespace
 
 extern "C" {
@@ -1884,7 +2017,11 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set");
     if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t per = (size_t)ctx->nc * ctx->K;
+    const bool ens = ctx->ens_M > 0;
+    if (ens && (int64_t)batch * ctx->ens_M > 0x7fffffff)
+        return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
+    // (with an ensemble the caller's array holds the seeds' K_r channels)
+    const size_t per = (size_t)ctx->nc * (ens ? ctx->ens_Kr : ctx->K);
     double bound = ctx->h0_norm_max;
     if (ctx->K > 0) {
         if (!controls) return fail(QOCX_ERR_ARG, "controls is NULL");
@@ -1908,7 +2045,8 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // per-step bound (launch_step_table) - tighter than sum_k max_t |u_k(t)| ||G_k||_1
         double smax = 0.0, smid = 0.0, sprev = 0.0;
         double* stage = ctx->pin_controls;
-        for (size_t row = 0; row < (size_t)batch * ctx->nc; ++row) {
+        if (ens) ensemble_stage(ctx, batch, controls, stage, smax, smid);
+        for (size_t row = 0; !ens && row < (size_t)batch * ctx->nc; ++row) {
             const double* src = controls + row * K;
             double* dst = stage + row * K;
             double srow = 0.0;
@@ -1934,9 +2072,13 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // a^2 / 4 mid-interval), so the knot sums above do not bound it. |r_k(t)| <= max over the knots of
         // |r_k| does hold everywhere (linear interpolation): ||Q_q||_1 max|r_k| max|r_l| bounds every step.
         if (ctx->quad_count > 0) bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, K).data());
-        if (ctx->controls.ensure(total)) return QOCX_ERR_HIP;
-        HIP_TRY(hipMemcpyAsync(ctx->controls.p, stage, total * sizeof(double), hipMemcpyHostToDevice,
-                               ctx->stream));
+        if (ens) {
+            if (int rc = ensemble_upload(ctx, batch, stage)) return rc;
+        } else {
+            if (ctx->controls.ensure(total)) return QOCX_ERR_HIP;
+            HIP_TRY(hipMemcpyAsync(ctx->controls.p, stage, total * sizeof(double), hipMemcpyHostToDevice,
+                                   ctx->stream));
+        }
     }
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or Hamiltonian");
@@ -1946,7 +2088,8 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         return fail(QOCX_ERR_CAPACITY,
                     "||dt H||_1 bound needs more than 2^10 squaring sub-steps per step; reduce dt");
     ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
-    ctx->B = batch;
+    ctx->B = ens ? batch * ctx->ens_M : batch;
+    ctx->ens_B = ens ? batch : 0;
     ctx->have_results = false;
     ctx->explicit_mode = false;
     return 0;
@@ -2065,8 +2208,8 @@ int qocx_set_keep_step_states(qocx_ctx* ctx, int32_t keep) {
     return 0;
 }
 
-int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
-    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+// The evaluation of the ctx->B items of the uploaded controls (qocx_eval_resident)
+static int eval_items(qocx_ctx* ctx, int32_t want_grad) {
     if (!ctx->has_problem || ctx->B < 1) return fail(QOCX_ERR_STATE, "no problem / controls");
     HIP_TRY(hipSetDevice(ctx->device));
     const int B = ctx->B;
@@ -2103,17 +2246,41 @@ int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
     return 0;
 }
 
+int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (ctx->ens_M == 0) return eval_items(ctx, want_grad);
+    // ensemble: the member items of the seeds' current controls, evaluated as any batch, then
+    // reduced to seed costs and gradients
+    if (!ctx->has_problem || ctx->B < 1) return fail(QOCX_ERR_STATE, "no problem / controls");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int seeds = ctx->ens_B;
+    if (ctx->ens_stale)
+        if (int rc = ensemble_expand(ctx, seeds)) return rc;
+    if (int rc = eval_items(ctx, want_grad)) return rc;
+    if (ctx->ens_cost.ensure((size_t)seeds) ||
+        (ctx->have_grads && ctx->ens_grads.ensure((size_t)seeds * ctx->nc * ctx->ens_Kr)))
+        return QOCX_ERR_HIP;
+    qocx::EnsembleArgs a = ensemble_args(ctx, seeds);
+    if (!ctx->have_grads) a.grads = nullptr;
+    qocx::launch_ensemble_reduce(a, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 int qocx_download_results(qocx_ctx* ctx, double* cost_out, double* grad_out, double* final_out) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = ctx->B, np = ctx->np, S = ctx->S, n = ctx->n;
+    // (costs and gradients of the seeds, final states of every item: [B][M][S][n] with an ensemble)
+    const int B = ctx->B, np = ctx->np, S = ctx->S, n = ctx->n, seeds = seed_count(ctx);
     if (cost_out)
-        HIP_TRY(hipMemcpyAsync(cost_out, ctx->cost_out.p, (size_t)B * sizeof(double),
+        HIP_TRY(hipMemcpyAsync(cost_out, seed_costs(ctx), (size_t)seeds * sizeof(double),
                                hipMemcpyDeviceToHost, ctx->stream));
     if (grad_out) {
         if (!ctx->have_grads) return fail(QOCX_ERR_STATE, "gradients were not computed");
-        HIP_TRY(hipMemcpyAsync(grad_out, ctx->grads.p, (size_t)B * ctx->nc * ctx->K * sizeof(double),
+        HIP_TRY(hipMemcpyAsync(grad_out, seed_grads(ctx),
+                               (size_t)seeds * ctx->nc * seed_channels(ctx) * sizeof(double),
                                hipMemcpyDeviceToHost, ctx->stream));
     }
     std::vector<double2> fin;
@@ -3274,10 +3441,11 @@ int qocx_opt_begin(qocx_ctx* ctx) {
     if (!ctx->has_problem || ctx->B < 1 || ctx->K < 1 || ctx->explicit_mode)
         return fail(QOCX_ERR_STATE, "qocx_opt_begin needs uploaded controls of a structured problem");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t total = (size_t)ctx->B * ctx->nc * ctx->K;
+    // (the seeds' optimizer states; the best final states of every item)
+    const size_t total = (size_t)seed_count(ctx) * ctx->nc * seed_channels(ctx);
     if (ctx->opt_m.ensure(total) || ctx->opt_v.ensure(total) || ctx->opt_best_controls.ensure(total) ||
         ctx->opt_best_final.ensure((size_t)ctx->B * ctx->S * ctx->np) ||
-        ctx->opt_flags.ensure(2 * (size_t)ctx->B) || ctx->opt_max_norms.ensure((size_t)ctx->K))
+        ctx->opt_flags.ensure(2 * (size_t)seed_count(ctx)) || ctx->opt_max_norms.ensure((size_t)ctx->K))
         return QOCX_ERR_HIP;
     HIP_TRY(hipMemsetAsync(ctx->opt_m.p, 0, total * sizeof(double), ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->opt_v.p, 0, total * sizeof(double), ctx->stream));
@@ -3290,11 +3458,15 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     if (ctx->opt_batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
     HIP_TRY(hipSetDevice(ctx->device));
     // after the clip |u_k| <= max_norms[k]: the squaring capacity follows from that bound
+    // (ensemble: |s_mk u_k| <= max_norms[k] max_m |s_mk| on the K_r seed channels, |delta_mj| beyond)
+    const bool ens = ctx->ens_M > 0;
+    const int Ks = seed_channels(ctx);
     double bound = ctx->h0_norm_max;
-    for (int k = 0; k < ctx->K; ++k) {
+    for (int k = 0; k < Ks; ++k) {
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
-        bound += max_norms[k] * ctx->g_norm_max[k];
+        bound += (ens ? max_norms[k] * ctx->ens_scale_max[k] : max_norms[k]) * ctx->g_norm_max[k];
     }
+    for (int j = 0; ens && j < ctx->ens_J; ++j) bound += ctx->ens_offset_max[j] * ctx->g_norm_max[Ks + j];
     bound += quad_bound(ctx, max_norms);  // (quadratic terms: ||Q_q||_1 max_norms_k max_norms_l)
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
@@ -3306,20 +3478,32 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     ctx->norm_bound = std::max(ctx->norm_bound, bound);
     ctx->norm_bound_mid = 1e300;  // (the controls move on the device from here on)
     ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
-    HIP_TRY(hipMemcpyAsync(ctx->opt_max_norms.p, max_norms, ctx->K * sizeof(double),
+    HIP_TRY(hipMemcpyAsync(ctx->opt_max_norms.p, max_norms, Ks * sizeof(double),
                            hipMemcpyHostToDevice, ctx->stream));
-    if (((size_t)ctx->B * ctx->nc * ctx->K + 255) / 256 > 0x7fffffffu || (size_t)ctx->nc * ctx->K > 65535u * 256u)
+    const size_t total = (size_t)seed_count(ctx) * ctx->nc * Ks;
+    if ((total + 255) / 256 > 0x7fffffffu || (size_t)ctx->nc * Ks > 65535u * 256u)
         return fail(QOCX_ERR_ARG, "control arrays too large for the optimizer kernels' grids");
-    qocx::launch_clip_controls(ctx->controls.p, (size_t)ctx->B * ctx->nc * ctx->K, ctx->K,
-                               ctx->opt_max_norms.p, ctx->stream);
+    qocx::launch_clip_controls(seed_controls(ctx), total, Ks, ctx->opt_max_norms.p, ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
     ctx->have_results = false;
+    ctx->ens_stale = ens;  // (the next evaluation expands the clipped seed controls)
     return 0;
 }
 
 int qocx_download_costs(qocx_ctx* ctx, double* cost_out) {
     if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(cost_out, seed_costs(ctx), (size_t)seed_count(ctx) * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
+    if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (ctx->ens_M == 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_set_ensemble)");
     if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(cost_out, ctx->cost_out.p, (size_t)ctx->B * sizeof(double),
@@ -3336,16 +3520,18 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
     if (ctx->opt_batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
     if (!ctx->have_results || !ctx->have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = ctx->B;
-    const size_t per_seed = (size_t)ctx->nc * ctx->K;
+    // (ensemble: a seed's controls and the final states of its M items)
+    const int B = seed_count(ctx);
+    const size_t per_seed = (size_t)ctx->nc * seed_channels(ctx);
+    const size_t items = ctx->ens_M > 0 ? (size_t)ctx->ens_M : 1;
     HIP_TRY(hipMemcpyAsync(ctx->opt_flags.p, improved, B, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->opt_flags.p + B, update, B, hipMemcpyHostToDevice, ctx->stream));
-    qocx::launch_keep_best(ctx->controls.p, ctx->opt_best_controls.p, per_seed, ctx->final_out.p,
-                           ctx->opt_best_final.p, (size_t)ctx->S * ctx->np, ctx->opt_flags.p, B,
+    qocx::launch_keep_best(seed_controls(ctx), ctx->opt_best_controls.p, per_seed, ctx->final_out.p,
+                           ctx->opt_best_final.p, items * ctx->S * ctx->np, ctx->opt_flags.p, B,
                            ctx->stream);
     qocx::OptimArgs a;
     a.kind = kind;
-    a.params = ctx->controls.p; a.grads = ctx->grads.p;
+    a.params = seed_controls(ctx); a.grads = seed_grads(ctx);
     a.moment = ctx->opt_m.p; a.square_moment = ctx->opt_v.p;
     a.update = ctx->opt_flags.p + B;
     a.per_seed = per_seed;
@@ -3357,6 +3543,7 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the flag arrays are the caller's memory
     ctx->have_results = false;  // the resident controls are no longer those of the last evaluation
+    ctx->ens_stale = ctx->ens_M > 0;
     return 0;
 }
 
@@ -3367,8 +3554,8 @@ int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_ou
     const int B = ctx->B, np = ctx->np, S = ctx->S, n = ctx->n;
     if (controls_out)
         HIP_TRY(hipMemcpyAsync(controls_out, ctx->opt_best_controls.p,
-                               (size_t)B * ctx->nc * ctx->K * sizeof(double), hipMemcpyDeviceToHost,
-                               ctx->stream));
+                               (size_t)seed_count(ctx) * ctx->nc * seed_channels(ctx) * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
     std::vector<double2> fin;
     if (final_out) {
         fin.resize((size_t)B * S * np);
@@ -3593,13 +3780,13 @@ int qocx_reduce_results(qocx_ctx* ctx, int32_t allreduce, double* out, int64_t c
     if (!ctx || !out) return fail(QOCX_ERR_ARG, "NULL argument");
     if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     if (allreduce && !ctx->comm) return fail(QOCX_ERR_STATE, "communicator not initialised");
-    const int per_seed = count > 1 ? ctx->nc * ctx->K : 0;  // count == 1: the cost only
+    const int per_seed = count > 1 ? ctx->nc * seed_channels(ctx) : 0;  // count == 1: the cost only
     if (count != 1 + per_seed || (per_seed > 0 && !ctx->have_grads))
         return fail(QOCX_ERR_ARG, "count must be 1, or 1 + control_eval_count * control_count after "
                                   "an evaluation with gradients");
     HIP_TRY(hipSetDevice(ctx->device));
     if (ctx->comm_buf.ensure((size_t)count)) return QOCX_ERR_HIP;
-    qocx::launch_reduce_results(ctx->cost_out.p, ctx->grads.p, ctx->B, per_seed, ctx->comm_buf.p,
+    qocx::launch_reduce_results(seed_costs(ctx), seed_grads(ctx), seed_count(ctx), per_seed, ctx->comm_buf.p,
                                 ctx->stream);
     if (allreduce) {  // ncclFloat64 = 8 ; ncclSum = 0
         int e = ctx->rccl.AllReduce(ctx->comm_buf.p, ctx->comm_buf.p, (size_t)count, 8, 0, ctx->comm,

@@ -248,6 +248,20 @@ struct QuadArgs {
     size_t total;              // B * nsteps
 };
 
+// Hamiltonian ensemble (qocx_ensemble.hip): B seeds x M members, K = Kr + J channels per member
+struct EnsembleArgs {
+    const double* seed_controls;  // expand in: [B][nc][Kr]
+    const double* scales;         // [M][Kr]
+    const double* offsets;        // [M][J] (J > 0)
+    const double* weights;        // [M]
+    double* controls;             // expand out: [B][M][nc][K]
+    const double* member_cost;    // reduce in: [B][M]
+    const double* member_grads;   // reduce in: [B][M][nc][K]
+    double* cost;                 // reduce out: [B]
+    double* grads;                // reduce out: [B][nc][Kr], or nullptr (no gradients)
+    int B, M, nc, K, Kr, J;
+};
+
 struct ScatterArgs {
     const double* gstep;
     const int* row_ptr;   // [nc+1]
@@ -479,6 +493,8 @@ void launch_m4lin_controls(const M4LinArgs& a, hipStream_t st);
 void launch_m4lin_chain(const M4LinArgs& a, hipStream_t st);
 void launch_quad_controls(const QuadArgs& a, hipStream_t st);
 void launch_quad_chain(const QuadArgs& a, hipStream_t st);
+void launch_ensemble_expand(const EnsembleArgs& a, hipStream_t st);
+void launch_ensemble_reduce(const EnsembleArgs& a, hipStream_t st);
 void launch_selftest(double* out, hipStream_t st);
 
 }  // namespace qocx

@@ -120,6 +120,8 @@ SIGNATURES = {
     "qocx_upload_generators": (ctypes.c_int, [_VP, _I32, _c_double_p]),
     "qocx_download_generator_cotangents": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_quadratic_terms": (ctypes.c_int, [_VP, _I32, _c_int_p, _c_double_p]),
+    "qocx_set_ensemble": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p, _c_double_p]),
+    "qocx_ensemble_download_members": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_keep_step_states": (ctypes.c_int, [_VP, _I32]),
     "qocx_download_step_states": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_lindblad_problem": (ctypes.c_int, [_VP, ctypes.POINTER(_LindbladProblem)]),
@@ -240,6 +242,7 @@ class Engine(object):
         self._ctx = _VP()
         self._check(self._lib.qocx_create(int(device), ctypes.byref(self._ctx)))
         self._problem = None
+        self._ensemble = None
         self._keepalive = []
         self.batch = 0
 
@@ -309,6 +312,7 @@ class Engine(object):
         p.costs = descs
         self._check(self._lib.qocx_set_schroedinger_problem(self._ctx, ctypes.byref(p)))
         self._problem = dict(n=n, S=S, K=K, Nc=int(control_eval_count), N=int(system_eval_count))
+        self._ensemble = None
         self.batch = 0
 
     def set_quadratic_terms(self, pairs, matrices):
@@ -323,12 +327,47 @@ class Engine(object):
             self._ctx, count, pairs.ctypes.data_as(_c_int_p), _dp(mats)))
         self.batch = 0
 
+    def set_ensemble(self, scales, offsets, weights):
+        """An ensemble of M members on the current problem (qocx_set_ensemble): the problem's last J
+        control channels are the perturbation matrices D_j. scales :: (M, K - J) or None (all 1),
+        offsets :: (M, J) or None (J = 0), weights :: (M,). From here on the seed-level calls
+        (upload_controls, download_results, download_costs, reduce_results, opt_*) take and return
+        the seeds' K - J channels, and final states carry a member axis: (B, M, S, n)."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        M = weights.shape[0]
+        J = 0 if offsets is None else np.asarray(offsets).size // max(M, 1)
+        kr = self._problem["K"] - J
+        none = ctypes.cast(None, _c_double_p)
+        sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64).reshape(M, kr)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float64).reshape(M, J)
+        self._check(self._lib.qocx_set_ensemble(
+            self._ctx, M, J, none if sc is None else _dp(sc), none if off is None else _dp(off),
+            _dp(weights)))
+        self._ensemble = dict(M=M, J=J, Kr=kr)
+        self.batch = 0
+
+    def ensemble_member_costs(self):
+        """The unweighted cost of every member of every seed of the last evaluation, (B, M)
+        (qocx_ensemble_download_members)."""
+        out = np.empty((self.batch, self._ensemble["M"]), dtype=np.float64)
+        self._check(self._lib.qocx_ensemble_download_members(self._ctx, _dp(out)))
+        return out
+
+    def _seed_channels(self):
+        """Control channels of a seed: the problem's K, or K - J with an ensemble set."""
+        return self._problem["K"] if self._ensemble is None else self._ensemble["Kr"]
+
+    def _final_shape(self, B):
+        pr = self._problem
+        members = () if self._ensemble is None else (self._ensemble["M"],)
+        return (B,) + members + (pr["S"], pr["n"])
+
     # -- evaluation ----------------------------------------------------------------------------
     def upload_controls(self, controls):
         pr = self._problem
         if pr["K"] > 0:
             controls = np.ascontiguousarray(controls, dtype=np.float64)
-            controls = controls.reshape(-1, pr["Nc"], pr["K"])
+            controls = controls.reshape(-1, pr["Nc"], self._seed_channels())
             batch = controls.shape[0]
             self._check(self._lib.qocx_upload_controls(self._ctx, batch, _dp(controls)))
         else:
@@ -357,8 +396,9 @@ class Engine(object):
         pr, B = self._problem, self.batch
         cost = np.empty(B, dtype=np.float64)
         want_grad = want_grad and pr["K"] > 0
-        grads = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64) if want_grad else None
-        final = np.empty((B, pr["S"], pr["n"]), dtype=np.complex128) if want_final else None
+        grads = (np.empty((B, pr["Nc"], self._seed_channels()), dtype=np.float64) if want_grad
+                 else None)
+        final = np.empty(self._final_shape(B), dtype=np.complex128) if want_final else None
         self._check(self._lib.qocx_download_results(
             self._ctx, _dp(cost), _dp(grads) if want_grad else None,
             _dp(final) if want_final else None))
@@ -375,7 +415,8 @@ class Engine(object):
 
     def download_step_states(self):
         pr, B = self._problem, self.batch
-        out = np.empty((B, pr["N"], pr["S"], pr["n"]), dtype=np.complex128)
+        members = () if self._ensemble is None else (self._ensemble["M"],)
+        out = np.empty((B,) + members + (pr["N"], pr["S"], pr["n"]), dtype=np.complex128)
         self._check(self._lib.qocx_download_step_states(self._ctx, _dp(out)))
         return out
 
@@ -602,8 +643,8 @@ class Engine(object):
 
     def opt_download_best(self):
         pr, B = self._problem, self.batch
-        controls = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64)
-        final = np.empty((B, pr["S"], pr["n"]), dtype=np.complex128)
+        controls = np.empty((B, pr["Nc"], self._seed_channels()), dtype=np.float64)
+        final = np.empty(self._final_shape(B), dtype=np.complex128)
         self._check(self._lib.qocx_opt_download_best(self._ctx, _dp(controls), _dp(final)))
         return controls, final
 
@@ -666,7 +707,7 @@ class Engine(object):
         """(sum of the costs, sum of the gradients [Nc x K] or None) over the seeds of the last
         evaluation, summed on the device and - allreduce=True - over the ranks of the communicator
         by one ncclAllReduce on the device buffer (qocx_reduce_results)."""
-        nc, k = self._problem["Nc"], self._problem["K"]
+        nc, k = self._problem["Nc"], self._seed_channels()
         want_grad = want_grad and k > 0
         count = 1 + (nc * k if want_grad else 0)
         out = np.zeros(count)

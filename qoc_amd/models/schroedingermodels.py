@@ -74,10 +74,14 @@ class EvolveSchroedingerDiscreteState(ProgramState):
 
 
 class EvolveSchroedingerResult(object):
-    def __init__(self, error=None, final_states=None):
+    """member_errors: with a HamiltonianEnsemble, the unweighted device cost of each member (M,);
+    None otherwise."""
+
+    def __init__(self, error=None, final_states=None, member_errors=None):
         super().__init__()
         self.error = error
         self.final_states = final_states
+        self.member_errors = member_errors
 
 
 class GrapeSchroedingerDiscreteState(GrapeState):
@@ -183,10 +187,14 @@ class GrapeSchroedingerDiscreteState(GrapeState):
 
 
 class GrapeSchroedingerResult(object):
+    """member_errors: with a HamiltonianEnsemble, the unweighted device cost of each member (M,)
+    at best_controls, from one forward evaluation after the optimisation; None otherwise."""
+
     def __init__(self, best_controls=None, best_error=np.finfo(np.float64).max,
-                 best_final_states=None, best_iteration=None):
+                 best_final_states=None, best_iteration=None, member_errors=None):
         super().__init__()
         self.best_controls = best_controls
         self.best_error = best_error
         self.best_final_states = best_final_states
         self.best_iteration = best_iteration
+        self.member_errors = member_errors

@@ -8,7 +8,7 @@ from .costs import (ControlArea, ControlBandwidthMax, ControlNorm, ControlVariat
                     TargetStateInfidelityTime)
 from .functions import (column_vector_list_to_matrix, commutator, conjugate_transpose, expm,
                         krons, matmuls, matrix_to_column_vector_list, rms_norm)
-from .hamiltonians import QuadraticHamiltonian
+from .hamiltonians import HamiltonianEnsemble, QuadraticHamiltonian
 from .optimizers import LBFGSB, SGD, Adam
 from .utils import CustomJSONEncoder, generate_save_file_path
 
@@ -21,6 +21,6 @@ __all__ = [
     "commutator", "conjugate_transpose", "expm", "krons", "rms_norm", "matmuls",
     "column_vector_list_to_matrix", "matrix_to_column_vector_list",
     "Adam", "LBFGSB", "SGD",
-    "QuadraticHamiltonian",
+    "HamiltonianEnsemble", "QuadraticHamiltonian",
     "generate_save_file_path", "CustomJSONEncoder",
 ]

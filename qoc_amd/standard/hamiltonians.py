@@ -10,6 +10,11 @@ in the real controls r, so under MagnusPolicy.M2 the engine evaluates it on the 
 problem linear in the effective controls (r_k, r_k r_l) - no call of the callable per step or
 per evaluation (qocx_set_quadratic_terms). The Piccolo Hamiltonian of the reference's report
 (report.tex:22-32, an AC-Stark term in epsilon_sb^2) has this form.
+
+HamiltonianEnsemble is NOT a callable: it is M copies of a linear Hamiltonian with scaled controls
+and fixed perturbation terms, all driven by the same controls (robust GRAPE). The Schroedinger
+evaluator sets it up as one structured problem whose extra control channels are the perturbation
+matrices, and the engine expands every seed into its M members on the device (qocx_set_ensemble).
 """
 
 import numbers
@@ -103,3 +108,135 @@ class QuadraticHamiltonian(object):
     def __repr__(self):
         return "QuadraticHamiltonian({!r}, {} quadratic terms)".format(
             self.linear_hamiltonian, len(self.pairs))
+
+
+def _real_array(value, name, ndim):
+    out = np.asarray(value)
+    if np.iscomplexobj(out):
+        raise ValueError("{} must be real".format(name))
+    out = np.array(out, dtype=np.float64)
+    if out.ndim != ndim:
+        raise ValueError("{} must have {} dimensions, got shape {}".format(name, ndim, out.shape))
+    if not np.all(np.isfinite(out)):
+        raise ValueError("{} is not finite".format(name))
+    return out
+
+
+class HamiltonianEnsemble(object):
+    """
+    E = HamiltonianEnsemble(hamiltonian, perturbations=None, offsets=None, control_scales=None,
+                            weights=None)
+
+    M copies of a system, all driven by the same controls (robust GRAPE). Member m is
+
+        H_m(u, t) = hamiltonian(s_m * u, t) + sum_j offsets[m, j] D_j
+
+    hamiltonian :: (controls, time) -> (n x n), real-linear in the controls (time dependence
+        allowed).
+    perturbations :: (J, n, n) complex - the fixed matrices D_j (detuning, crosstalk, ...).
+    offsets :: (M, J) real - delta_mj; given exactly when perturbations are.
+    control_scales :: (M, control_count) real - s_mk (amplitude errors); a complex control's
+        scale multiplies its real and imaginary parts alike. Default: all 1.
+    weights :: (M,) real >= 0 - w_m; default 1 / M.
+
+    M is read from whichever of offsets, control_scales and weights is given; they must agree.
+    Passed as the `hamiltonian` of evolve_schroedinger_discrete, grape_schroedinger_discrete or
+    grape_schroedinger_discrete_batch, the cost is sum_m w_m c_m over the members' device costs
+    (costs of the controls alone are added once), and the gradient is that of this sum. The
+    object is not itself callable: member(m) is member m as a plain callable.
+    """
+
+    def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
+                 weights=None):
+        if not callable(hamiltonian):
+            raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
+        counts = {}
+        if perturbations is not None:
+            perturbations = np.array(perturbations, dtype=np.complex128)
+            if perturbations.ndim != 3 or perturbations.shape[1] != perturbations.shape[2]:
+                raise ValueError("perturbations must be (J, n, n), got shape {}"
+                                 "".format(perturbations.shape))
+            if not np.all(np.isfinite(perturbations)):
+                raise ValueError("perturbations is not finite")
+            if offsets is None:
+                raise ValueError("perturbations need offsets of shape (M, J)")
+        if offsets is not None:
+            if perturbations is None:
+                raise ValueError("offsets need perturbations (the matrices D_j they multiply)")
+            offsets = _real_array(offsets, "offsets", 2)
+            if offsets.shape[1] != perturbations.shape[0]:
+                raise ValueError("offsets must be (M, J) with J = {} perturbations, got shape {}"
+                                 "".format(perturbations.shape[0], offsets.shape))
+            counts["offsets"] = offsets.shape[0]
+        if control_scales is not None:
+            control_scales = _real_array(control_scales, "control_scales", 2)
+            counts["control_scales"] = control_scales.shape[0]
+        if weights is not None:
+            weights = _real_array(weights, "weights", 1)
+            if np.any(weights < 0):
+                raise ValueError("weights must be >= 0")
+            counts["weights"] = weights.shape[0]
+        if not counts:
+            raise ValueError("an ensemble needs offsets, control_scales or weights (M is read "
+                             "from them)")
+        if len(set(counts.values())) > 1:
+            raise ValueError("offsets, control_scales and weights disagree on the member count: {}"
+                             "".format(", ".join("{} {}".format(k, v) for k, v in counts.items())))
+        M = next(iter(counts.values()))
+        if M == 0:
+            raise ValueError("an ensemble needs at least one member (M = 0 in {})"
+                             "".format(", ".join(counts)))
+        self.hamiltonian = hamiltonian
+        self.perturbations = perturbations
+        self.offsets = offsets
+        self.control_scales = control_scales
+        self.weights = weights if weights is not None else np.full(M, 1.0 / M)
+        self.member_count = M
+
+    @property
+    def perturbation_count(self):
+        """J, the number of perturbation matrices."""
+        return 0 if self.perturbations is None else self.perturbations.shape[0]
+
+    @property
+    def hilbert_size(self):
+        """n of the perturbation matrices (None without them)."""
+        return None if self.perturbations is None else self.perturbations.shape[1]
+
+    def real_channel_scales(self, control_count, complex_controls):
+        """s_mk per real control channel, (M, K_r): the scales as given for real controls, each
+        repeated for Re and Im of a complex control (channels 2k and 2k + 1)."""
+        if self.control_scales is None:
+            kr = control_count * (2 if complex_controls else 1)
+            return np.ones((self.member_count, kr))
+        if self.control_scales.shape[1] != control_count:
+            raise ValueError("control_scales must be (M, control_count) = ({}, {}), got shape {}"
+                             "".format(self.member_count, control_count,
+                                       self.control_scales.shape))
+        if complex_controls:
+            return np.repeat(self.control_scales, 2, axis=1)
+        return self.control_scales.copy()
+
+    def member(self, m):
+        """Member m as a plain callable (controls, time) -> (n x n)."""
+        m = int(m)
+        if not 0 <= m < self.member_count:
+            raise IndexError("member {} out of range for {} members".format(m, self.member_count))
+        base = self.hamiltonian
+        scales = None if self.control_scales is None else self.control_scales[m]
+        shift = None
+        if self.perturbations is not None:
+            shift = np.einsum("j,jab->ab", self.offsets[m].astype(np.complex128),
+                              self.perturbations)
+
+        def hamiltonian(controls, time):
+            u = controls
+            if scales is not None and controls is not None:
+                u = np.asarray(controls) * scales
+            out = np.asarray(base(u, time), dtype=np.complex128)
+            return out if shift is None else out + shift
+        return hamiltonian
+
+    def __repr__(self):
+        return "HamiltonianEnsemble({!r}, {} members, {} perturbations)".format(
+            self.hamiltonian, self.member_count, self.perturbation_count)

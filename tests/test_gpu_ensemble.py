@@ -1,0 +1,313 @@
+"""
+GPU tests (-m gpu) of Hamiltonian ensembles on the device (qoc_amd.standard.HamiltonianEnsemble ->
+qocx_set_ensemble): the engine expands B seeds into B x M member items, evaluates them as any
+batch, and reduces them to seed costs and gradients. A member's outputs are those of the plain
+(K_r + J)-channel problem on the host-expanded controls, bit for bit.
+"""
+
+import numpy as np
+import pytest
+
+import qoc_amd
+import qoc_amd.standard.costs as product_costs
+from oracle import qoc_numpy as onp
+from qoc_amd import engine as engine_mod
+from qoc_amd.core import batch as batch_mod
+from qoc_amd.core import device
+from qoc_amd.models import MagnusPolicy
+from qoc_amd.standard import SGD, Adam, HamiltonianEnsemble
+from tests import cases as cases_mod
+from tests import helpers
+from tests.helpers import rel_err
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(autouse=True)
+def real_engine():
+    helpers.set_backend_factory(None)
+    yield
+    helpers.set_backend_factory(None)
+
+
+@pytest.fixture
+def routes(monkeypatch):
+    """Counts the runs of each route of the multi-start loop."""
+    taken = {"resident": 0, "host": 0}
+    resident, host = batch_mod.run_batch_resident, batch_mod.run_batch_host
+
+    def run_resident(*a, **k):
+        taken["resident"] += 1
+        return resident(*a, **k)
+
+    def run_host(*a, **k):
+        taken["host"] += 1
+        return host(*a, **k)
+    monkeypatch.setattr(batch_mod, "run_batch_resident", run_resident)
+    monkeypatch.setattr(batch_mod, "run_batch_host", run_host)
+    return taken
+
+
+# ---- the engine: members against the plain expanded problem ----------------------------------------
+
+def engine_problem(n, magnus, time_dependent, step_costs, S, kr=3, J=2, M=3, B=2, N=21, Nc=8,
+                   seed=0):
+    rng = np.random.default_rng(500 + n + 7 * seed)
+    nodes = {"M2": 1, "M4": 2, "M6": 3}[magnus]
+    nt = (N - 1) * nodes if time_dependent else 1
+    h0 = cases_mod.gue(rng, n)
+    gs = np.stack([cases_mod.gue(rng, n) for _ in range(kr)])
+    d = np.stack([0.5 * cases_mod.gue(rng, n) for _ in range(J)]) if J else np.zeros((0, n, n))
+    wobble = 1 + 0.2 * np.sin(np.linspace(0, 3, nt)) if time_dependent else np.ones(1)
+    h0_t = wobble[:, None, None] * h0[None]
+    g_t = np.concatenate([np.repeat(gs[None], nt, axis=0),
+                          np.repeat(d[None], nt, axis=0)], axis=1)
+    psi0 = np.eye(n, dtype=np.complex128)[:S]
+    target = cases_mod.random_unitary(rng, n)[:, :S]
+    tgt = cases_mod.column_states(target)
+    if step_costs:
+        forbid = cases_mod.column_states(np.eye(n)[:, S:S + 1])[None].repeat(S, axis=0)
+        costs = [product_costs.ForbidStates(forbid, N), product_costs.TargetStateInfidelityTime(N, tgt)]
+    else:
+        costs = [product_costs.TargetStateInfidelity(tgt)]
+    descs = [c.device_descriptor(S, n) for c in costs]
+    scales = 1 + 0.05 * rng.standard_normal((M, kr))
+    offsets = 0.4 * rng.standard_normal((M, J)) if J else None
+    weights = rng.uniform(0.1, 1.0, M)
+    u = 0.6 * rng.standard_normal((B, Nc, kr))
+    return dict(n=n, S=S, K=kr + J, kr=kr, J=J, M=M, B=B, N=N, Nc=Nc, T=0.05 * (N - 1),
+                h0=h0_t, g=g_t, psi0=psi0, descs=descs, magnus=magnus, scales=scales,
+                offsets=offsets, weights=weights, u=u)
+
+
+def expand(p):
+    B, M, Nc, K, kr = p["B"], p["M"], p["Nc"], p["K"], p["kr"]
+    items = np.empty((B, M, Nc, K))
+    items[..., :kr] = p["scales"][None, :, None, :] * p["u"][:, None]
+    if p["J"]:
+        items[..., kr:] = p["offsets"][None, :, None, :]
+    return items.reshape(B * M, Nc, K)
+
+
+def make_engine(p, latency=False):
+    eng = engine_mod.Engine(0)
+    eng.set_schroedinger_problem(p["n"], p["S"], p["K"], p["Nc"], p["N"], p["T"], p["h0"], p["g"],
+                                 p["psi0"], costs=p["descs"], magnus_policy=p["magnus"])
+    if latency:
+        eng.set_knob("latency", 1)
+    return eng
+
+
+CASES = [  # (n, magnus, time-dependent, step costs, S, latency knob)
+    (4, "M2", False, False, 1, False),   # unit adjoint, n <= 8
+    (24, "M4", False, True, 2, False),   # M4 on a linear system, step costs
+    (24, "M2", True, False, 1, True),    # latency mode (single-seed entry points), unit adjoint
+    (40, "M6", True, False, 2, False),   # M6 above n = 32
+    (72, "M2", True, True, 2, False),    # the general path
+]
+
+
+@pytest.mark.parametrize("n, magnus, time_dependent, step_costs, S, latency", CASES)
+def test_members_equal_the_plain_expanded_problem_and_reduce(n, magnus, time_dependent, step_costs,
+                                                             S, latency):
+    p = engine_problem(n, magnus, time_dependent, step_costs, S)
+    ens, plain = make_engine(p, latency), make_engine(p, latency)
+    try:
+        ens.set_ensemble(p["scales"], p["offsets"], p["weights"])
+        ens.upload_controls(p["u"])
+        ens.eval_resident(True)
+        cost, grads, final = ens.download_results()
+        members = ens.ensemble_member_costs()
+        plain.upload_controls(expand(p))
+        plain.eval_resident(True)
+        pcost, pgrads, pfinal = plain.download_results()
+    finally:
+        ens.close()
+        plain.close()
+    B, M, kr = p["B"], p["M"], p["kr"]
+    assert members.shape == (B, M) and final.shape == (B, M, S, n)
+    assert grads.shape == (B, p["Nc"], kr)
+    # 1. every member is the plain item, bit for bit
+    assert np.array_equal(members.reshape(-1), pcost)
+    assert np.array_equal(final.reshape(B * M, S, n), pfinal)
+    # 2. the reduction: weighted sums in member order
+    pgrads = pgrads.reshape(B, M, p["Nc"], p["K"])[..., :kr]
+    for b in range(B):
+        want = 0.0
+        want_g = np.zeros((p["Nc"], kr))
+        for m in range(M):
+            want += p["weights"][m] * members[b, m]
+            want_g += (p["weights"][m] * p["scales"][m]) * pgrads[b, m]
+        assert abs(cost[b] - want) <= 1e-14 * abs(want)
+        assert rel_err(grads[b], want_g) < 1e-14
+
+
+def test_reduce_results_and_resident_driver_act_on_the_seeds():
+    p = engine_problem(24, "M2", False, False, 1, B=3)
+    eng = make_engine(p)
+    try:
+        eng.set_ensemble(p["scales"], p["offsets"], p["weights"])
+        eng.upload_controls(p["u"])
+        eng.eval_resident(True)
+        cost, grads, _ = eng.download_results()
+        total, total_g = eng.reduce_results()
+        assert abs(total - np.sum(cost)) <= 1e-14 * abs(total)
+        assert rel_err(total_g, np.sum(grads, axis=0)) < 1e-14
+        # clip on the device: the next evaluation expands the clipped seed controls
+        eng.opt_begin()
+        eng.opt_clip(np.full(p["kr"], 0.3))
+        eng.eval_resident(True)
+        costs = eng.download_costs()
+        c2, g2, f2 = eng.evaluate(np.clip(p["u"], -0.3, 0.3))
+    finally:
+        eng.close()
+    assert np.max(np.abs(costs - c2)) < 1e-12
+
+
+def test_degenerate_ensemble_is_the_plain_problem():
+    p = engine_problem(24, "M2", False, False, 1, J=0, M=1, B=3)
+    ens, plain = make_engine(p), make_engine(p)
+    try:
+        ens.set_ensemble(None, None, np.ones(1))
+        c1, g1, f1 = ens.evaluate(p["u"])
+        c0, g0, f0 = plain.evaluate(p["u"])
+    finally:
+        ens.close()
+        plain.close()
+    assert np.array_equal(c1, c0)
+    assert np.array_equal(g1, g0)
+    assert np.array_equal(f1[:, 0], f0)
+
+
+# ---- the evaluator against the oracle ------------------------------------------------------------
+
+def transmon_ensemble(n, K=2, M=4, J=2, seed=0, complex_controls=True):
+    rng = np.random.default_rng(900 + n + seed)
+    h0 = cases_mod.gue(rng, n)
+    g_re = [cases_mod.gue(rng, n) for _ in range(K)]
+    g_im = [cases_mod.gue(rng, n) for _ in range(K)]
+
+    def linear(u, t):
+        out = h0 * (1 + 0.25 * np.sin(2.1 * t))
+        for k in range(K):
+            out = out + (u[k].real * g_re[k] + u[k].imag * g_im[k] if complex_controls
+                         else u[k] * g_re[k])
+        return out
+    d = np.stack([0.3 * cases_mod.gue(rng, n) for _ in range(J)])
+    return HamiltonianEnsemble(linear, perturbations=d, offsets=0.5 * rng.standard_normal((M, J)),
+                               control_scales=1 + 0.05 * rng.standard_normal((M, K)),
+                               weights=rng.uniform(0.2, 1.0, M)), rng
+
+
+@pytest.mark.parametrize("n, magnus", [(6, MagnusPolicy.M4), (24, MagnusPolicy.M2)])
+def test_members_and_gradients_against_the_oracle(n, magnus):
+    K, N, Nc, S, T = 2, 21, 8, 2, 1.2
+    e, rng = transmon_ensemble(n, K)
+    psi0 = cases_mod.column_states(np.eye(n)[:, :S])
+    target = cases_mod.column_states(cases_mod.random_unitary(rng, n)[:, :S])
+    ev = device.SchroedingerEvaluator(T, e, psi0, N, control_count=K, control_eval_count=Nc,
+                                      complex_controls=True, magnus_policy=magnus,
+                                      costs=[product_costs.TargetStateInfidelity(target)])
+    u = 0.6 * (rng.standard_normal((2, Nc, K)) + 1j * rng.standard_normal((2, Nc, K)))
+    errors, grads, finals, _ = ev.evaluate_batch(u)
+    members = ev.member_errors()
+    for b in range(2):
+        want_g = 0.0
+        for m in range(e.member_count):
+            problem = onp.SchroedingerProblem(
+                T, e.member(m), psi0, N, control_eval_count=Nc,
+                costs=[onp.TargetStateInfidelity(target)], magnus_policy=magnus.short,
+                complex_controls=True, control_count=K)
+            err, gr, fin = onp.evaluate_with_grad(problem, u[b])
+            assert abs(members[b, m] - err) < 1e-10
+            assert np.max(np.abs(finals[b, m] - fin)) < 1e-10
+            want_g = want_g + e.weights[m] * gr
+        assert abs(errors[b] - np.dot(e.weights, members[b])) < 1e-14
+        assert rel_err(grads[b], want_g) < 1e-8
+    # the single-evaluation entry point (latency mode, its own kernels): the same members
+    result = qoc_amd.evolve_schroedinger_discrete(
+        T, e, psi0, N, controls=u[0], magnus_policy=magnus,
+        costs=[product_costs.TargetStateInfidelity(target)])
+    assert np.max(np.abs(result.member_errors - members[0])) < 1e-12
+    assert np.max(np.abs(result.final_states - finals[0])) < 1e-12
+    assert abs(result.error - errors[0]) < 1e-12
+
+
+# ---- multi-start GRAPE ---------------------------------------------------------------------------
+
+class PluginAdam(Adam):  # not type(...) is Adam: takes the host loop
+    pass
+
+
+class PluginSGD(SGD):
+    pass
+
+
+def test_multistart_runs_resident_and_equals_host_loop_and_single_runs(routes):
+    K, N, Nc, S, T, n = 3, 31, 10, 2, 1.5, 24
+    e, rng = transmon_ensemble(n, K, M=3, J=1, seed=5, complex_controls=False)
+    psi0 = cases_mod.column_states(np.eye(n)[:, :S])
+    target = cases_mod.column_states(cases_mod.random_unitary(rng, n)[:, :S])
+    costs = [product_costs.TargetStateInfidelity(target)]
+    B = 4
+    u0 = np.clip(0.6 * np.random.default_rng(93).standard_normal((B, Nc, K)), -1, 1)
+    args = (K, Nc, costs, T, e, psi0, N)
+    kw = dict(iteration_count=5, log_iteration_step=0, max_control_norms=np.full(K, 1.0))
+    a = qoc_amd.grape_schroedinger_discrete_batch(*args, u0.copy(),
+                                                  optimizer=Adam(learning_rate=5e-2), **kw)
+    assert routes == {"resident": 1, "host": 0}
+    b = qoc_amd.grape_schroedinger_discrete_batch(*args, u0.copy(),
+                                                  optimizer=PluginAdam(learning_rate=5e-2), **kw)
+    assert routes == {"resident": 1, "host": 1}
+    assert np.array_equal(a.best_error, b.best_error)
+    assert np.array_equal(a.best_iteration, b.best_iteration)
+    for s in range(B):
+        assert a.best_final_states[s].shape == (e.member_count, S, n, 1)
+        assert np.array_equal(a.best_controls[s], b.best_controls[s])
+        assert np.array_equal(a.best_final_states[s], b.best_final_states[s])
+        assert np.array_equal(a.member_errors[s], b.member_errors[s])
+    for s in range(B):
+        one = qoc_amd.grape_schroedinger_discrete_batch(*args, u0[s:s + 1].copy(),
+                                                        optimizer=Adam(learning_rate=5e-2), **kw)
+        assert one.best_error[0] == a.best_error[s]
+        assert np.array_equal(one.best_controls[0], a.best_controls[s])
+        assert np.array_equal(one.best_final_states[0], a.best_final_states[s])
+        ref = qoc_amd.grape_schroedinger_discrete(*args, initial_controls=u0[s].copy(),
+                                                  optimizer=Adam(learning_rate=5e-2), **kw)
+        assert ref.best_iteration == a.best_iteration[s]
+        assert abs(ref.best_error - a.best_error[s]) < 1e-12
+        assert rel_err(a.best_controls[s], ref.best_controls) < 1e-10
+        assert np.max(np.abs(ref.member_errors - a.member_errors[s])) < 1e-12
+    assert routes["host"] == 1 and routes["resident"] == 1 + B
+
+
+# ---- rejections through the engine ---------------------------------------------------------------
+
+def test_engine_rejections():
+    n, N = 2, 5
+    rng = np.random.default_rng(3)
+    d = np.stack([cases_mod.gue(rng, n) for _ in range(5)])
+    big = HamiltonianEnsemble(lambda u, t: np.sum(u) * np.diag([1.0, -1.0]) + 0j,
+                              perturbations=d, offsets=np.zeros((2, 5)))
+    psi0 = cases_mod.column_states(np.eye(n)[:, :1])
+    target = cases_mod.column_states(np.eye(n)[:, 1:2])
+    with pytest.raises(engine_mod.QocxError, match="0..64"):  # K_r + J = 65
+        device.SchroedingerEvaluator(1.0, big, psi0, N, control_count=60, control_eval_count=N,
+                                     costs=[product_costs.TargetStateInfidelity(target)])
+    eng = engine_mod.Engine(0)
+    try:
+        eng.set_schroedinger_problem(n, 1, 1, N, N, 1.0, np.diag([1.0, -1.0])[None],
+                                     np.array([[[0, 1], [1, 0]]])[None], np.eye(n)[:1])
+        with pytest.raises(engine_mod.QocxError, match="1 .. 1024"):
+            eng.set_ensemble(None, None, np.ones(1025))
+        with pytest.raises(engine_mod.QocxError, match="fixed < control_count"):
+            eng.set_ensemble(None, np.zeros((2, 1)), np.ones(2))  # no channel is left for the seeds
+        dummy, w = np.zeros(2), np.ones(2)
+        assert eng._lib.qocx_set_ensemble(eng._ctx, 2, 0, None, engine_mod._dp(dummy),
+                                          engine_mod._dp(w)) != 0  # offsets without channels
+        assert b"offsets need fixed >= 1" in eng._lib.qocx_last_error()
+        with pytest.raises(engine_mod.QocxError, match="weights"):
+            eng.set_ensemble(None, None, np.array([1.0, -1.0]))
+        eng.set_ensemble(None, None, np.ones(1024))  # the largest M is taken
+    finally:
+        eng.close()
