@@ -475,6 +475,57 @@ int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
                            int32_t apply_clip_grads, double clip_grads);
 int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out);
 
+/* ---- costs of the controls alone, on the device ------------------------------------------------
+ * The reference's ControlNorm, ControlVariation, ControlArea and ControlBandwidthMax
+ * (qoc/standard/costs/controlnorm.py:48-73, controlvariation.py:47-75, controlarea.py:43-67,
+ * controlbandwidthmax.py:52-77) and their gradients for the control sets resident in HBM, so that the
+ * multi-start drivers above keep pulse-shaping penalties off the host. `path` names the problem of
+ * the context they belong to. K controls; with complex_controls != 0 control k is the real channels
+ * 2k (Re) and 2k + 1 (Im) of the problem, K = channels / 2, and gradients are d/dRe, d/dIm in those
+ * channels. With an ensemble set the channels are the seeds' K_r. */
+#define QOCX_PATH_SCHROEDINGER 0
+#define QOCX_PATH_LINDBLAD 1
+#define QOCX_CONTROL_NORM 0          /* multiplier * sum |u_jk / max_k * w_k|^2                      */
+#define QOCX_CONTROL_VARIATION 1     /* multiplier * sum |order-th forward difference of u_k / max_k|^2 */
+#define QOCX_CONTROL_AREA 2          /* multiplier * sum_k |sum_j u_jk / max_k|                      */
+#define QOCX_CONTROL_BANDWIDTH_MAX 3 /* multiplier * sum_k sum_P |X_f| / (|P_k| max_P |X_f|), X = DFT(u_k) */
+
+typedef struct qocx_control_cost_desc {
+    int32_t kind;            /* QOCX_CONTROL_*                                                      */
+    int32_t order;           /* VARIATION: 1 <= order < Nc                                          */
+    double multiplier;       /* cost_multiplier with the normalisation constant of the cost folded in:
+                                / (Nc K), / (K (Nc - order) 2^order), / (Nc K), / K                  */
+    const double* max_norms; /* [K] max_control_norms, or NULL (none; AREA needs them)              */
+    const double* weights;   /* NORM: [K] control_weights, or NULL                                  */
+    const int32_t* bins;     /* BANDWIDTH_MAX: the DFT bins f with fftfreq(Nc, dt)[f] >= max_bandwidths[k], */
+    const int32_t* bin_ptr;  /*   ascending per control: P_k = bins[bin_ptr[k] .. bin_ptr[k + 1]), [K + 1]  */
+} qocx_control_cost_desc;
+
+/* Set (count > 0) or clear (count = 0) the control costs of a path. Call after the qocx_set_*_problem
+ * of that path (and after qocx_set_ensemble), which clear them. QOCX_ERR_ARG for a problem without
+ * controls, an odd channel count with complex_controls, an unknown kind, `order` out of range, an
+ * empty or out-of-range P_k, AREA without max_norms, or non-finite inputs.
+ * With control costs set, qocx_eval_resident (after the ensemble reduction: once per seed, on the
+ * seed's unscaled controls) and qocx_eval_lindblad_resident add their sum to every seed's cost and
+ * - with gradients - its gradient to the seed's gradient, one addition per entry; what
+ * qocx_download_costs / _results, qocx_reduce_results, qocx_opt_step and the Lindblad twins see are
+ * the totals. qocx_eval_schroedinger and qocx_eval_lindblad (host buffers in and out) do not add them. */
+int qocx_set_control_costs(qocx_ctx* ctx, int32_t path, int32_t complex_controls, int32_t count,
+                           const qocx_control_cost_desc* descs);
+/* The control costs alone: controls [batch][Nc][channels] on the host in, their sum cost_out [batch]
+ * and its gradient grad_out [batch][Nc][channels] (NULL: none) out. A seed's numbers do not depend on
+ * the batch it is part of. */
+int qocx_eval_control_costs(qocx_ctx* ctx, int32_t path, int32_t batch, const double* controls,
+                            double* cost_out, double* grad_out);
+/* Complex controls in the resident drivers. The reference clips a COPY of complex controls
+ * (common.py:8-30 on the array slap_controls builds, :201-223) and its optimizer keeps the unclipped parameters. Begun
+ * with these instead of qocx_opt_begin / qocx_lindblad_opt_begin, the driver keeps the parameters
+ * apart from the evaluated controls: *_opt_clip takes max_norms [K = channels / 2] and writes the
+ * parameters, clipped by modulus hypot(Re, Im), into the evaluation buffer; *_opt_step updates the
+ * parameters; the best so far are the clipped controls that were evaluated. */
+int qocx_opt_begin_complex(qocx_ctx* ctx);
+int qocx_lindblad_opt_begin_complex(qocx_ctx* ctx);
+
 /* ---- host-side helpers of the multi-start GRAPE driver (no GPU work, no context) --------------
  * The reference's driver loop clips the controls and applies its optimizer plugin to ONE control
  * set per process (qoc/core/common.py:8-30, qoc/standard/optimizers/adam.py:110-165, sgd.py). The

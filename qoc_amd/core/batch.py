@@ -276,7 +276,8 @@ def prepare_seeds(initial_controls, complex_controls, control_count, control_eva
 
 def resident_route(stepper, optimizer, pstate, evaluator, batch):
     """The device-resident loop applies: built-in Adam / SGD without scale_grads, no control
-    conditions, and an evaluator that can keep everything on the device."""
+    conditions, and an evaluator that can keep everything on the device (structured Hamiltonian,
+    device costs and built-in costs of the controls; real or complex controls)."""
     return (batch > 0 and stepper is not None and pstate.impose_control_conditions is None
             and not getattr(optimizer, "apply_scale_grads", False)
             and hasattr(evaluator, "resident_capable") and evaluator.resident_capable())
@@ -299,11 +300,28 @@ def run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iter
     """The loop with everything but the decisions on the device: ops.opt_clip -> ops.eval_resident
     -> B costs to the host -> ops.opt_step. `ops` is the engine's resident driver of one problem
     (upload_controls, opt_begin, opt_clip, eval_resident, download_costs, opt_step,
-    opt_download_best -> (controls [B, Nc, K], finals in the result's shape))."""
+    opt_download_best -> (controls [B, Nc, K], finals in the result's shape)); controls go in and
+    come back in the cost-function format (complex arrays for complex controls: ops holds them as
+    two real channels each and keeps the optimizer's parameters unclipped, as _cost_format_batch
+    does on the host). ops.finish(), if there is one, runs when the loop ends, however it ends."""
+    try:
+        return _run_batch_resident(ops, optimizer, params, pstate, iteration_count,
+                                   log_iteration_step, min_error, comm, result)
+    finally:
+        getattr(ops, "finish", lambda: None)()
+
+
+def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iteration_step,
+                        min_error, comm, result):
     B = params.shape[0]
     is_adam = type(optimizer) is Adam
     _log_header(log_iteration_step, comm)
-    ops.upload_controls(params.reshape((B,) + tuple(pstate.controls_shape)))
+    shape = (B,) + tuple(pstate.controls_shape)
+    if pstate.complex_controls:
+        half = params.shape[1] // 2
+        ops.upload_controls((params[:, :half] + 1j * params[:, half:]).reshape(shape))
+    else:
+        ops.upload_controls(params.reshape(shape))
     ops.opt_begin()
     active = np.ones(B, dtype=bool)
     count = 0  # optimizer steps taken so far (every active seed has taken all of them)

@@ -23,6 +23,29 @@ def make_backend(device=-1):
 _FD_STEP = 1e-6
 
 
+def control_cost_descriptors(host_costs, control_count, control_eval_count, complex_controls):
+    """One entry per cost of the controls alone: the dict engine.set_control_costs() takes, or None
+    where only the host can evaluate the cost (a user plugin without control_descriptor(), or a
+    built-in one that declines)."""
+    out = []
+    for cost in host_costs:
+        hook = getattr(cost, "control_descriptor", None)
+        out.append(None if hook is None
+                   else hook(control_count, control_eval_count, complex_controls))
+    return out
+
+
+def controls_stay_resident(backend, descriptors, complex_controls, begin_complex):
+    """The resident drivers can take these costs of the controls (every one has a descriptor and
+    the backend evaluates them) and this kind of controls (complex ones need the backend's complex
+    clip, `begin_complex`)."""
+    if complex_controls and not hasattr(backend, begin_complex):
+        return False
+    if not descriptors:
+        return True
+    return (all(d is not None for d in descriptors) and hasattr(backend, "set_control_costs"))
+
+
 def user_states_bar(cost, controls, states, step):
     """
     d cost / d Re(states) + i d cost / d Im(states) of a user Cost: its states_bar() hook when it
@@ -186,6 +209,9 @@ class SchroedingerEvaluator(object):
                 self.host_costs.append(cost)
             else:
                 self.opaque_costs.append(cost)
+        # the same costs as the resident multi-start driver hands them to the engine
+        self.control_cost_descriptors = control_cost_descriptors(
+            self.host_costs, control_count, control_eval_count, complex_controls)
         if self.ensemble is not None:
             if self.opaque_costs:
                 raise NotImplementedError(
@@ -324,12 +350,14 @@ class SchroedingerEvaluator(object):
 
     def resident_capable(self):
         """True when a multi-start driver may keep controls and optimizer states on the device
-        (engine.opt_*): structured Hamiltonian, real controls, every cost evaluated on the device,
-        and a backend that has the entry points (the real engine)."""
+        (engine.opt_*): structured Hamiltonian, every cost evaluated on the device - the built-in
+        costs of the controls alone included, through their control_descriptor() -, and a backend
+        that has the entry points (the real engine; complex controls need its complex clip)."""
         return (self.opaque_hamiltonian is None and self.linearized_hamiltonian is None
-                and not self.complex_controls
-                and self.control_count > 0 and not self.host_costs and not self.opaque_costs
-                and hasattr(self.backend, "opt_step"))
+                and self.control_count > 0 and not self.opaque_costs
+                and hasattr(self.backend, "opt_step")
+                and controls_stay_resident(self.backend, self.control_cost_descriptors,
+                                           self.complex_controls, "opt_begin_complex"))
 
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
         """
@@ -533,6 +561,8 @@ class LindbladEvaluator(object):
                 self.host_costs.append(cost)
             else:
                 self.opaque_costs.append(cost)
+        self.control_cost_descriptors = control_cost_descriptors(
+            self.host_costs, control_count, control_eval_count, complex_controls)
         self._problem_args = (self.hilbert_size, self.density_count, self.kr, control_eval_count,
                               system_eval_count, evolution_time, h0, g, dissipators, operators,
                               initial_densities)
@@ -655,14 +685,18 @@ class LindbladEvaluator(object):
 
     def resident_capable(self):
         """True when a multi-start driver may keep controls and optimizer states on the device
-        (engine.lindblad_opt_*): a Hamiltonian linear in real controls (time-dependent ones
+        (engine.lindblad_opt_*): a Hamiltonian linear in the controls (time-dependent ones
         included: their tables cover max_control_norms, which the driver's clip enforces), every
-        cost evaluated on the device, and a backend that has the entry points (the real engine)."""
+        cost evaluated on the device - the built-in costs of the controls alone included -, and a
+        backend that has the entry points (the real engine; complex controls need its complex
+        clip)."""
         return (self.linearized_hamiltonian is None and self._cost_controls is None
-                and not self.complex_controls and self.control_count > 0
+                and self.control_count > 0
                 and (not self.time_dependent or self._table_bounds is not None)
-                and not self.host_costs and not self.opaque_costs
-                and hasattr(self.backend, "lindblad_opt_step"))
+                and not self.opaque_costs
+                and hasattr(self.backend, "lindblad_opt_step")
+                and controls_stay_resident(self.backend, self.control_cost_descriptors,
+                                           self.complex_controls, "lindblad_opt_begin_complex"))
 
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_densities=False):
         """

@@ -12,11 +12,12 @@ the parity tolerances that follow from replacing an adaptive integrator).
 
 import numpy as np
 
-from qoc_amd.core import batch
+from qoc_amd.core import batch, structure
 from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
                                  strip_controls)
 from qoc_amd.core.device import LindbladEvaluator
 from qoc_amd.core.structure import NonLinearHamiltonianError
+from qoc_amd.engine import PATH_LINDBLAD
 from qoc_amd.models import (Dummy, EvolveLindbladDiscreteState, EvolveLindbladResult,
                             GrapeLindbladDiscreteState, GrapeLindbladResult,
                             InterpolationPolicy)
@@ -167,14 +168,30 @@ class _ResidentOps(object):
     """engine.lindblad_* (the Lindblad problem's resident buffers) as the resident loop of
     core/batch.py calls them."""
 
-    def __init__(self, engine):
-        self.upload_controls = engine.lindblad_upload_controls
-        self.opt_begin = engine.lindblad_opt_begin
+    def __init__(self, engine, control_costs=(), complex_controls=False):
+        self.engine = engine
+        self.control_costs = list(control_costs)
+        self.complex_controls = complex_controls
+        self.opt_begin = (engine.lindblad_opt_begin_complex if complex_controls
+                          else engine.lindblad_opt_begin)
         self.opt_clip = engine.lindblad_opt_clip
         self.eval_resident = engine.eval_lindblad_resident
         self.download_costs = engine.lindblad_download_costs
         self.opt_step = engine.lindblad_opt_step
-        self.opt_download_best = engine.lindblad_opt_download_best
+
+    def upload_controls(self, controls):
+        if self.control_costs:
+            self.engine.set_control_costs(PATH_LINDBLAD, self.complex_controls, self.control_costs)
+        self.engine.lindblad_upload_controls(
+            structure.to_real_controls(controls, self.complex_controls))
+
+    def opt_download_best(self):
+        controls, finals = self.engine.lindblad_opt_download_best()
+        return structure.from_real_gradients(controls, self.complex_controls), finals
+
+    def finish(self):
+        if self.control_costs:  # evaluate_batch and the single-seed entry points keep them on the host
+            self.engine.set_control_costs(PATH_LINDBLAD, self.complex_controls, [])
 
 
 def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evolution_time,
@@ -196,10 +213,12 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     Arguments as grape_lindblad_discrete without the save-file ones; initial_controls ::
     (B x control_eval_count x control_count), each conforming to max_control_norms. comm
     (qoc_amd.parallel communicator, optional): the seed axis is sharded over its ranks, result
-    arrays are rank local. With real controls, device costs, a Hamiltonian linear in the controls,
-    the built-in Adam / SGD and no control conditions, controls, gradients, optimizer states and the
-    best so far stay in HBM (qocx_lindblad_opt_*); otherwise the host drives
-    LindbladEvaluator.evaluate_batch. Both routes give the same numbers.
+    arrays are rank local. With costs the device evaluates (the built-in density costs and the four
+    built-in costs of the controls), a Hamiltonian linear in the controls, the built-in Adam / SGD
+    and no control conditions, controls, gradients, optimizer states and the best so far stay in HBM
+    (qocx_lindblad_opt_*; real or complex controls); otherwise the host drives
+    LindbladEvaluator.evaluate_batch. Both routes give the same numbers to rounding (bit for bit
+    without costs of the controls and without a clip acting on a complex control).
     Returns GrapeLindbladBatchResult.
     """
     _reject_ensemble(hamiltonian)
@@ -217,6 +236,6 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     result = GrapeLindbladBatchResult(B)
     run = (iteration_count, log_iteration_step, min_error, comm, result)
     if batch.resident_route(stepper, optimizer, pstate, evaluator, B):
-        return batch.run_batch_resident(_ResidentOps(evaluator.backend), optimizer, params, pstate,
-                                        *run)
+        ops = _ResidentOps(evaluator.backend, evaluator.control_cost_descriptors, complex_controls)
+        return batch.run_batch_resident(ops, optimizer, params, pstate, *run)
     return batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)

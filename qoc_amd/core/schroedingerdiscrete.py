@@ -9,10 +9,11 @@ MI355X through qoc_amd.core.device.SchroedingerEvaluator.
 
 import numpy as np
 
-from qoc_amd.core import batch
+from qoc_amd.core import batch, structure
 from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
                                  strip_controls)
 from qoc_amd.core.device import SchroedingerEvaluator
+from qoc_amd.engine import PATH_SCHROEDINGER
 from qoc_amd.models import (Dummy, EvolveSchroedingerDiscreteState, EvolveSchroedingerResult,
                             GrapeSchroedingerDiscreteState, GrapeSchroedingerResult,
                             InterpolationPolicy, MagnusPolicy)
@@ -168,17 +169,38 @@ class GrapeSchroedingerBatchResult(batch.BatchResult):
 
 
 class _ResidentOps(object):
-    """engine.opt_* as the resident loop of core/batch.py calls it (final states [B, S, n, 1])."""
+    """engine.opt_* as the resident loop of core/batch.py calls it (final states [B, S, n, 1]).
+    control_costs: the descriptors of the costs of the controls alone, which the engine then
+    adds to every resident evaluation until finish(); complex_controls: the loop's complex arrays
+    travel as two real channels per control and the engine clips a copy of the parameters."""
 
-    def __init__(self, engine):
+    def __init__(self, engine, control_costs=(), complex_controls=False):
         self.engine = engine
+        self.control_costs = list(control_costs)
+        self.complex_controls = complex_controls
 
     def __getattr__(self, name):
         return getattr(self.engine, name)
 
+    def upload_controls(self, controls):
+        if self.control_costs:
+            self.engine.set_control_costs(PATH_SCHROEDINGER, self.complex_controls,
+                                          self.control_costs)
+        self.engine.upload_controls(structure.to_real_controls(controls, self.complex_controls))
+
+    def opt_begin(self):
+        if self.complex_controls:
+            self.engine.opt_begin_complex()
+        else:
+            self.engine.opt_begin()
+
     def opt_download_best(self):
         controls, finals = self.engine.opt_download_best()
-        return controls, finals[..., None]
+        return structure.from_real_gradients(controls, self.complex_controls), finals[..., None]
+
+    def finish(self):
+        if self.control_costs:  # evaluate_batch and the single-seed entry points keep them on the host
+            self.engine.set_control_costs(PATH_SCHROEDINGER, self.complex_controls, [])
 
 
 def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, evolution_time,
@@ -226,10 +248,11 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     run = (iteration_count, log_iteration_step, min_error, comm, result)
     # Device-resident form: controls, gradients, Adam moments and the best
     # so far stay in HBM; per iteration the host sees B costs and sends 2 B flags. The same
-    # iteration, the same arithmetic (qocx_optim.hip: IEEE operations in the reference's order).
+    # iteration, the same arithmetic (qocx_optim.hip: IEEE operations in the reference's order);
+    # the built-in costs of the controls alone are evaluated there too (qocx_ctrlcost.hip).
     if batch.resident_route(stepper, optimizer, pstate, evaluator, B):
-        out = batch.run_batch_resident(_ResidentOps(evaluator.backend), optimizer, params, pstate,
-                                       *run)
+        ops = _ResidentOps(evaluator.backend, evaluator.control_cost_descriptors, complex_controls)
+        out = batch.run_batch_resident(ops, optimizer, params, pstate, *run)
     else:
         out = batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
     if getattr(evaluator, "ensemble", None) is not None:

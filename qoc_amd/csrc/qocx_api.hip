@@ -168,6 +168,37 @@ struct Rccl {
     const char* (*GetErrorString)(int) = nullptr;
 };
 
+// The costs of the controls alone of one path (qocx_set_control_costs, qocx_ctrlcost.hip)
+struct ControlCosts {
+    int count = 0;        // 0: none set
+    int cplx = 0, K = 0;  // complex controls; controls (channels / 2 when complex)
+    int Kr = 0, nc = 0;   // the channels and knots they were set for
+    int elementwise = 0;  // descriptors of the kernel of NORM / VARIATION / AREA
+    bool variation = false;
+    struct Bandwidth {
+        double multiplier;
+        int pmax;
+        size_t bins, bin_ptr;  // offsets into `ints`
+    };
+    std::vector<Bandwidth> bandwidth;
+    DevBuf<qocx::CtrlCostDev> descs;
+    DevBuf<double> arrays;  // the per-control arrays of the descriptors
+    DevBuf<int> ints;       // bins and bin_ptr of the bandwidth costs
+    DevBuf<double2> twiddle;
+    // per evaluation
+    DevBuf<double> cost, grad, work0, work1, stage;
+    DevBuf<double2> spectrum, ybar;
+    void clear() {
+        count = 0;
+        bandwidth.clear();
+    }
+    void release() {
+        descs.release(); arrays.release(); ints.release(); twiddle.release(); cost.release();
+        grad.release(); work0.release(); work1.release(); stage.release(); spectrum.release();
+        ybar.release();
+    }
+};
+
 }  // namespace
 
 struct ncclUniqueIdBytes {
@@ -211,6 +242,9 @@ struct qocx_ctx {
     DevBuf<double2> opt_best_final;
     DevBuf<unsigned char> opt_flags;  // [2][B]: improved | update
     int opt_batch = 0;
+    bool opt_complex = false;    // qocx_opt_begin_complex: opt_params are the optimizer's parameters,
+    DevBuf<double> opt_params;   // the seed controls the copy clipped by modulus that is evaluated
+    ControlCosts control_costs;  // qocx_set_control_costs(QOCX_PATH_SCHROEDINGER)
     DevBuf<double2> lam_scale;     // unit adjoint: [B][S]
     DevBuf<int> offs_x;            // unit adjoint: [chunk][nsteps + 1]
     int keep_step_states = 0;
@@ -320,6 +354,9 @@ struct qocx_ctx {
         DevBuf<double> opt_m, opt_v, opt_best_controls, opt_max_norms;
         DevBuf<double2> opt_best_final;
         DevBuf<unsigned char> opt_flags;  // [2][B]: improved | update
+        bool opt_complex = false;         // qocx_lindblad_opt_begin_complex
+        DevBuf<double> opt_params;
+        ControlCosts control_costs;       // qocx_set_control_costs(QOCX_PATH_LINDBLAD)
     } lb;
     // ---- qocx_debug_set_knob: kernel-variant switches for A/B measurements and tests ----
     std::map<std::string, int64_t> knobs;
@@ -661,6 +698,8 @@ int qocx_destroy(qocx_ctx* ctx) {
     ctx->opt_m.release(); ctx->opt_v.release(); ctx->opt_best_controls.release();
     ctx->opt_max_norms.release(); ctx->opt_best_final.release(); ctx->opt_flags.release();
     ctx->gen_rm.release(); ctx->genbar_rm.release(); ctx->stamps.release();
+    ctx->opt_params.release(); ctx->control_costs.release();
+    ctx->lb.opt_params.release(); ctx->lb.control_costs.release();
     DevBuf<double2>* b2[] = {&ctx->h0_cimg, &ctx->g_cimg, &ctx->h0_rimg, &ctx->g_rimg, &ctx->h0_timg,
                              &ctx->g_timg, &ctx->psi0, &ctx->cost_vectors, &ctx->final_out,
                              &ctx->step_states, &ctx->q_img, &ctx->qt_img, &ctx->lu_img, &ctx->dinv,
@@ -761,6 +800,7 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     // h0_timg / g_timg hold - the column-major images of the transposes)
     const int nb = (n <= 16) ? 1 : (n <= 32 ? 2 : (n <= 64 ? 4 : (n + 15) / 16)), np = 16 * nb, mat = np * np, nt = p->nt;
     ctx->has_problem = false;
+    ctx->control_costs.clear();
     ctx->n = n; ctx->nb = nb; ctx->np = np; ctx->S = S; ctx->K = K; ctx->nc = nc; ctx->N = N;
     ctx->nsteps = nsteps; ctx->ces = p->cost_eval_step; ctx->nt = nt; ctx->nodes = nodes;
     ctx->T = p->evolution_time;
@@ -2000,6 +2040,47 @@ int ensemble_upload(qocx_ctx* ctx, int batch, const double* stage) {
     return ensemble_expand(ctx, batch);
 }
 
+// ---- costs of the controls alone (qocx_set_control_costs) -----------------------------------------
+
+// cc.cost [B] and, if want_grad, cc.grad [B][nc][Kr] of the control sets `controls` on the device
+int run_control_costs(qocx_ctx* ctx, ControlCosts& cc, int B, int nc, int Kr, const double* controls,
+                      bool want_grad) {
+    if (cc.Kr != Kr || cc.nc != nc)
+        return fail(QOCX_ERR_STATE, "the control costs were set for another control layout "
+                                    "(qocx_set_control_costs after qocx_set_ensemble)");
+    const size_t total = (size_t)B * nc * Kr;
+    if ((size_t)nc * Kr > 0x7fffffffu) return fail(QOCX_ERR_ARG, "control arrays too large for the control-cost kernels");
+    if (cc.cost.ensure((size_t)B) || (want_grad && cc.grad.ensure(total)) ||
+        (cc.variation && (cc.work0.ensure(total) || cc.work1.ensure(total))))
+        return QOCX_ERR_HIP;
+    qocx::CtrlCostArgs a;
+    a.controls = controls; a.cost = cc.cost.p; a.grad = want_grad ? cc.grad.p : nullptr;
+    a.work0 = cc.work0.p; a.work1 = cc.work1.p;
+    a.descs = cc.descs.p; a.count = cc.elementwise;
+    a.B = B; a.nc = nc; a.Kr = Kr; a.cplx = cc.cplx;
+    qocx::launch_control_costs(a, ctx->stream);
+    int pmax = 0;  // (one allocation for all bandwidth costs: none while a kernel is in flight)
+    for (const auto& bw : cc.bandwidth) pmax = std::max(pmax, bw.pmax);
+    if (pmax > 0) {
+        if (cc.spectrum.ensure((size_t)B * Kr * pmax) || (want_grad && cc.ybar.ensure((size_t)B * cc.K * pmax)))
+            return QOCX_ERR_HIP;
+        if ((size_t)B * (1 + cc.cplx) / 8 + 1 > 65535u)
+            return fail(QOCX_ERR_ARG, "batch too large for the bandwidth kernels' grids");
+    }
+    for (const auto& bw : cc.bandwidth) {
+        qocx::BandwidthArgs w;
+        w.controls = controls; w.twiddle = cc.twiddle.p;
+        w.bins = cc.ints.p + bw.bins; w.bin_ptr = cc.ints.p + bw.bin_ptr;
+        w.spectrum = cc.spectrum.p; w.ybar = cc.ybar.p;
+        w.cost = cc.cost.p; w.grad = want_grad ? cc.grad.p : nullptr;
+        w.multiplier = bw.multiplier;
+        w.B = B; w.nc = nc; w.Kr = Kr; w.K = cc.K; w.cplx = cc.cplx; w.pmax = bw.pmax;
+        qocx::launch_bandwidth_cost(w, ctx->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The seed-level view: with an ensemble the entry points of the host's optimizer loop (costs,
 // gradients, qocx_opt_*) act on the seeds and their K_r channels, else on the items themselves.
 int seed_count(const qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_B : ctx->B; }
@@ -2246,8 +2327,8 @@ static int eval_items(qocx_ctx* ctx, int32_t want_grad) {
     return 0;
 }
 
-int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
-    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+// The evaluation of the seeds of the uploaded controls, without the costs of the controls alone
+static int eval_seeds(qocx_ctx* ctx, int32_t want_grad) {
     if (ctx->ens_M == 0) return eval_items(ctx, want_grad);
     // ensemble: the member items of the seeds' current controls, evaluated as any batch, then
     // reduced to seed costs and gradients
@@ -2263,6 +2344,23 @@ int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
     qocx::EnsembleArgs a = ensemble_args(ctx, seeds);
     if (!ctx->have_grads) a.grads = nullptr;
     qocx::launch_ensemble_reduce(a, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (int rc = eval_seeds(ctx, want_grad)) return rc;
+    ControlCosts& cc = ctx->control_costs;
+    if (cc.count == 0) return 0;
+    // the costs of the controls, once per seed on the controls that were evaluated (ensemble: the
+    // seed's own, unscaled), added to the seed's cost and gradient
+    const int seeds = seed_count(ctx);
+    if (int rc = run_control_costs(ctx, cc, seeds, ctx->nc, seed_channels(ctx), seed_controls(ctx), ctx->have_grads))
+        return rc;
+    qocx::launch_add_control_costs(seed_costs(ctx), cc.cost.p, ctx->have_grads ? seed_grads(ctx) : nullptr,
+                                   cc.grad.p, seeds, (size_t)ctx->nc * seed_channels(ctx), ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -2320,7 +2418,7 @@ int qocx_eval_schroedinger(qocx_ctx* ctx, int32_t batch, const double* controls,
                            double* cost_out, double* grad_out, double* final_out) {
     int rc = qocx_upload_controls(ctx, batch, controls);
     if (rc) return rc;
-    rc = qocx_eval_resident(ctx, want_grad);
+    rc = eval_seeds(ctx, want_grad);  // (host buffers in and out: without qocx_set_control_costs' terms)
     if (rc) return rc;
     return qocx_download_results(ctx, cost_out, (want_grad && ctx->K > 0) ? grad_out : nullptr,
                                  final_out);
@@ -2564,6 +2662,7 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
                          qocx::lindblad_lds_size(n, S, Lmw, 3, K) <= 160 * 1024) ? 1 : 0;
     auto& lb = ctx->lb;
     lb.has_problem = false;
+    lb.control_costs.clear();
     lb.n = n; lb.S = S; lb.K = K; lb.nc = nc; lb.N = N; lb.nsteps = N - 1; lb.ces = p->cost_eval_step;
     lb.nops = L; lb.T = p->evolution_time; lb.dt = p->evolution_time / (N - 1);
 
@@ -3450,6 +3549,7 @@ int qocx_opt_begin(qocx_ctx* ctx) {
     HIP_TRY(hipMemsetAsync(ctx->opt_m.p, 0, total * sizeof(double), ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->opt_v.p, 0, total * sizeof(double), ctx->stream));
     ctx->opt_batch = ctx->B;
+    ctx->opt_complex = false;
     return 0;
 }
 
@@ -3461,6 +3561,12 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     // (ensemble: |s_mk u_k| <= max_norms[k] max_m |s_mk| on the K_r seed channels, |delta_mj| beyond)
     const bool ens = ctx->ens_M > 0;
     const int Ks = seed_channels(ctx);
+    // (complex controls: max_norms [Ks / 2] bound the moduli, hence both channels of a control)
+    const int Kn = ctx->opt_complex ? Ks / 2 : Ks;
+    std::vector<double> channel_norms((size_t)Ks);
+    for (int k = 0; k < Ks; ++k) channel_norms[k] = max_norms[ctx->opt_complex ? k / 2 : k];
+    const double* caller_norms = max_norms;
+    max_norms = channel_norms.data();
     double bound = ctx->h0_norm_max;
     for (int k = 0; k < Ks; ++k) {
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
@@ -3478,12 +3584,16 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     ctx->norm_bound = std::max(ctx->norm_bound, bound);
     ctx->norm_bound_mid = 1e300;  // (the controls move on the device from here on)
     ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
-    HIP_TRY(hipMemcpyAsync(ctx->opt_max_norms.p, max_norms, Ks * sizeof(double),
+    HIP_TRY(hipMemcpyAsync(ctx->opt_max_norms.p, caller_norms, Kn * sizeof(double),
                            hipMemcpyHostToDevice, ctx->stream));
     const size_t total = (size_t)seed_count(ctx) * ctx->nc * Ks;
     if ((total + 255) / 256 > 0x7fffffffu || (size_t)ctx->nc * Ks > 65535u * 256u)
         return fail(QOCX_ERR_ARG, "control arrays too large for the optimizer kernels' grids");
-    qocx::launch_clip_controls(seed_controls(ctx), total, Ks, ctx->opt_max_norms.p, ctx->stream);
+    if (ctx->opt_complex)
+        qocx::launch_clip_complex(ctx->opt_params.p, seed_controls(ctx), total / 2, Kn, ctx->opt_max_norms.p,
+                                  ctx->stream);
+    else
+        qocx::launch_clip_controls(seed_controls(ctx), total, Ks, ctx->opt_max_norms.p, ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
     ctx->have_results = false;
@@ -3531,7 +3641,7 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
                            ctx->stream);
     qocx::OptimArgs a;
     a.kind = kind;
-    a.params = seed_controls(ctx); a.grads = seed_grads(ctx);
+    a.params = ctx->opt_complex ? ctx->opt_params.p : seed_controls(ctx); a.grads = seed_grads(ctx);
     a.moment = ctx->opt_m.p; a.square_moment = ctx->opt_v.p;
     a.update = ctx->opt_flags.p + B;
     a.per_seed = per_seed;
@@ -3633,6 +3743,13 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
                                lb.res_grads.p, csz, lb.final_out.p, lb.res_final.p, (size_t)S * md,
                                lb.order_dev.p, B, ctx->stream);
     HIP_TRY(hipGetLastError());
+    if (lb.control_costs.count > 0) {  // the costs of the controls, on the seeds' resident controls
+        ControlCosts& cc = lb.control_costs;
+        if (int rc2 = run_control_costs(ctx, cc, B, lb.nc, K, lb.res_controls.p, want_grad != 0)) return rc2;
+        qocx::launch_add_control_costs(lb.res_cost.p, cc.cost.p, want_grad ? lb.res_grads.p : nullptr, cc.grad.p,
+                                       B, csz, ctx->stream);
+        HIP_TRY(hipGetLastError());
+    }
     if (ctx->timing) {  // (the events of the launches are read once they have run)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         time_collect(ctx);
@@ -3688,6 +3805,7 @@ int qocx_lindblad_opt_begin(qocx_ctx* ctx) {
     HIP_TRY(hipMemsetAsync(lb.opt_m.p, 0, total * sizeof(double), ctx->stream));
     HIP_TRY(hipMemsetAsync(lb.opt_v.p, 0, total * sizeof(double), ctx->stream));
     lb.opt_batch = lb.res_B;
+    lb.opt_complex = false;
     return 0;
 }
 
@@ -3696,13 +3814,18 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     auto& lb = ctx->lb;
     if (lb.opt_batch != lb.res_B || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
-    for (int k = 0; k < lb.K; ++k)
+    const int Kn = lb.opt_complex ? lb.K / 2 : lb.K;  // (complex controls: one modulus bound per control)
+    for (int k = 0; k < Kn; ++k)
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
     HIP_TRY(hipSetDevice(ctx->device));
     const int B = lb.res_B, K = lb.K;
-    HIP_TRY(hipMemcpyAsync(lb.opt_max_norms.p, max_norms, K * sizeof(double), hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(lb.opt_max_norms.p, max_norms, Kn * sizeof(double), hipMemcpyHostToDevice,
                            ctx->stream));
-    qocx::launch_clip_controls(lb.res_controls.p, (size_t)B * lb.nc * K, K, lb.opt_max_norms.p, ctx->stream);
+    if (lb.opt_complex)
+        qocx::launch_clip_complex(lb.opt_params.p, lb.res_controls.p, (size_t)B * lb.nc * Kn, Kn,
+                                  lb.opt_max_norms.p, ctx->stream);
+    else
+        qocx::launch_clip_controls(lb.res_controls.p, (size_t)B * lb.nc * K, K, lb.opt_max_norms.p, ctx->stream);
     // the maxima of the clipped controls decide the next evaluation's sub-divisions: they come back
     // with the synchronisation the clip needs anyway (none on a fixed grid)
     const bool maxima = lb.fixed_ksub == 0;
@@ -3739,7 +3862,7 @@ int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
                            ctx->stream);
     qocx::OptimArgs a;
     a.kind = kind;
-    a.params = lb.res_controls.p; a.grads = lb.res_grads.p;
+    a.params = lb.opt_complex ? lb.opt_params.p : lb.res_controls.p; a.grads = lb.res_grads.p;
     a.moment = lb.opt_m.p; a.square_moment = lb.opt_v.p;
     a.update = lb.opt_flags.p + B;
     a.per_seed = per_seed;
@@ -3773,6 +3896,165 @@ int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double*
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (final_out)
         for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
+    return 0;
+}
+
+// ---- costs of the controls alone; complex controls in the resident drivers -------------------------
+
+static ControlCosts* control_costs_of(qocx_ctx* ctx, int32_t path, int& nc, int& Kr) {
+    if (path == QOCX_PATH_SCHROEDINGER && ctx->has_problem) {
+        nc = ctx->nc;
+        Kr = ctx->ens_M > 0 ? ctx->ens_Kr : ctx->K;
+        return &ctx->control_costs;
+    }
+    if (path == QOCX_PATH_LINDBLAD && ctx->lb.has_problem) {
+        nc = ctx->lb.nc;
+        Kr = ctx->lb.K;
+        return &ctx->lb.control_costs;
+    }
+    return nullptr;
+}
+
+int qocx_set_control_costs(qocx_ctx* ctx, int32_t path, int32_t complex_controls, int32_t count,
+                           const qocx_control_cost_desc* descs) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (path != QOCX_PATH_SCHROEDINGER && path != QOCX_PATH_LINDBLAD) return fail(QOCX_ERR_ARG, "unknown path");
+    int nc = 0, Kr = 0;
+    ControlCosts* ccp = control_costs_of(ctx, path, nc, Kr);
+    if (!ccp) return fail(QOCX_ERR_STATE, "no problem set on this path");
+    ControlCosts& cc = *ccp;
+    cc.clear();
+    if (count <= 0) return 0;
+    if (!descs) return fail(QOCX_ERR_ARG, "descs is NULL");
+    const int cplx = complex_controls ? 1 : 0;
+    if (Kr < 1 || nc < 2) return fail(QOCX_ERR_ARG, "control costs need a problem with controls");
+    if (Kr > 128) return fail(QOCX_ERR_ARG, "control costs take up to 128 control channels");
+    if (cplx && Kr % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
+    const int K = Kr >> cplx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<double> arrays;
+    std::vector<int> ints;
+    std::vector<qocx::CtrlCostDev> dev;
+    std::vector<size_t> offsets;  // of max_norms | weights in `arrays`, per elementwise descriptor
+    bool variation = false;
+    for (int d = 0; d < count; ++d) {
+        const qocx_control_cost_desc& c = descs[d];
+        if (!std::isfinite(c.multiplier)) return fail(QOCX_ERR_ARG, "non-finite cost multiplier");
+        for (int k = 0; k < K; ++k)
+            if ((c.max_norms && !std::isfinite(c.max_norms[k])) || (c.weights && !std::isfinite(c.weights[k])))
+                return fail(QOCX_ERR_ARG, "non-finite max_norms / weights");
+        if (c.kind == QOCX_CONTROL_BANDWIDTH_MAX) {
+            if (!c.bins || !c.bin_ptr || c.bin_ptr[0] != 0) return fail(QOCX_ERR_ARG, "bandwidth cost without bins");
+            ControlCosts::Bandwidth bw;
+            bw.multiplier = c.multiplier;
+            bw.pmax = 0;
+            for (int k = 0; k < K; ++k) {
+                const int np = c.bin_ptr[k + 1] - c.bin_ptr[k];
+                if (np < 1) return fail(QOCX_ERR_ARG, "a control without penalised DFT bins (empty P_k)");
+                for (int i = c.bin_ptr[k]; i < c.bin_ptr[k + 1]; ++i)
+                    if (c.bins[i] < 0 || c.bins[i] >= nc || (i > c.bin_ptr[k] && c.bins[i] <= c.bins[i - 1]))
+                        return fail(QOCX_ERR_ARG, "DFT bins must be ascending and in 0..Nc-1");
+                bw.pmax = std::max(bw.pmax, np);
+            }
+            bw.bins = ints.size();
+            ints.insert(ints.end(), c.bins, c.bins + c.bin_ptr[K]);
+            bw.bin_ptr = ints.size();
+            ints.insert(ints.end(), c.bin_ptr, c.bin_ptr + K + 1);
+            cc.bandwidth.push_back(bw);
+            continue;
+        }
+        if (c.kind != QOCX_CONTROL_NORM && c.kind != QOCX_CONTROL_VARIATION && c.kind != QOCX_CONTROL_AREA) {
+            cc.clear();
+            return fail(QOCX_ERR_ARG, "unknown control cost kind");
+        }
+        if (c.kind == QOCX_CONTROL_VARIATION && (c.order < 1 || c.order >= nc)) {
+            cc.clear();
+            return fail(QOCX_ERR_ARG, "ControlVariation needs 1 <= order < control_eval_count");
+        }
+        if (c.kind == QOCX_CONTROL_AREA && !c.max_norms) {
+            cc.clear();
+            return fail(QOCX_ERR_ARG, "ControlArea needs max_norms");
+        }
+        variation = variation || c.kind == QOCX_CONTROL_VARIATION;
+        qocx::CtrlCostDev e;
+        e.kind = c.kind; e.order = c.order; e.multiplier = c.multiplier;
+        e.max_norms = e.weights = nullptr;
+        offsets.push_back(arrays.size());
+        for (int k = 0; k < K; ++k) arrays.push_back(c.max_norms ? c.max_norms[k] : 1.0);
+        for (int k = 0; k < K; ++k) arrays.push_back(c.weights ? c.weights[k] : 1.0);
+        dev.push_back(e);
+    }
+    if (cc.arrays.upload(arrays, ctx->stream) || cc.ints.upload(ints, ctx->stream)) {
+        cc.clear();
+        return QOCX_ERR_HIP;
+    }
+    for (size_t d = 0; d < dev.size(); ++d) {
+        dev[d].max_norms = cc.arrays.p + offsets[d];
+        dev[d].weights = cc.arrays.p + offsets[d] + K;
+    }
+    if (!cc.bandwidth.empty()) {  // exp(-2 pi i m / Nc), m = 0 .. Nc-1, rounded from extended precision
+        std::vector<double2> tw((size_t)nc);
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        for (int m = 0; m < nc; ++m) {
+            const long double th = two_pi * (long double)m / (long double)nc;
+            tw[m] = make_double2((double)cosl(th), (double)-sinl(th));
+        }
+        if (cc.twiddle.upload(tw, ctx->stream)) {
+            cc.clear();
+            return QOCX_ERR_HIP;
+        }
+    }
+    if (cc.descs.upload(dev, ctx->stream)) {
+        cc.clear();
+        return QOCX_ERR_HIP;
+    }
+    cc.count = count;
+    cc.cplx = cplx; cc.K = K; cc.Kr = Kr; cc.nc = nc;
+    cc.elementwise = (int)dev.size();
+    cc.variation = variation;
+    return 0;
+}
+
+int qocx_eval_control_costs(qocx_ctx* ctx, int32_t path, int32_t batch, const double* controls,
+                            double* cost_out, double* grad_out) {
+    if (!ctx || !controls || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    int nc = 0, Kr = 0;
+    ControlCosts* cc = control_costs_of(ctx, path, nc, Kr);
+    if (!cc || cc->count == 0) return fail(QOCX_ERR_STATE, "no control costs set on this path");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t total = (size_t)batch * nc * Kr;
+    if (cc->stage.ensure(total)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(cc->stage.p, controls, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = run_control_costs(ctx, *cc, batch, nc, Kr, cc->stage.p, grad_out != nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(cost_out, cc->cost.p, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_out)
+        HIP_TRY(hipMemcpyAsync(grad_out, cc->grad.p, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_opt_begin_complex(qocx_ctx* ctx) {
+    if (int rc = qocx_opt_begin(ctx)) return rc;
+    const int Ks = seed_channels(ctx);
+    if (Ks % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
+    const size_t total = (size_t)seed_count(ctx) * ctx->nc * Ks;
+    if (ctx->opt_params.ensure(total)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(ctx->opt_params.p, seed_controls(ctx), total * sizeof(double),
+                           hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->opt_complex = true;
+    return 0;
+}
+
+int qocx_lindblad_opt_begin_complex(qocx_ctx* ctx) {
+    if (int rc = qocx_lindblad_opt_begin(ctx)) return rc;
+    auto& lb = ctx->lb;
+    if (lb.K % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
+    const size_t total = (size_t)lb.res_B * lb.nc * lb.K;
+    if (lb.opt_params.ensure(total)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(lb.opt_params.p, lb.res_controls.p, total * sizeof(double), hipMemcpyDeviceToDevice,
+                           ctx->stream));
+    lb.opt_complex = true;
     return 0;
 }
 

@@ -421,6 +421,45 @@ void launch_keep_best(const double* controls, double* best_controls, size_t per_
                       const double2* final_states, double2* best_final, size_t final_per_seed,
                       const unsigned char* improved, int batch, hipStream_t st);
 void launch_optimizer_update(const OptimArgs& a, int batch, hipStream_t st);
+// complex controls: controls[b][j][2k .. 2k+1] = params clipped by modulus to max_norms[k]; params stay
+void launch_clip_complex(const double* params, double* controls, size_t pairs, int k,
+                         const double* max_norms, hipStream_t st);
+
+// Costs of the controls alone (qocx_ctrlcost.hip; qoc/standard/costs/control*.py)
+struct CtrlCostDev {
+    int kind, order;    // QOCX_CONTROL_*; ControlVariation: order of the difference
+    double multiplier;  // cost_multiplier with the cost's normalisation constant folded in
+    const double* max_norms;  // [K] per control (ones when the cost has none)
+    const double* weights;    // [K] ControlNorm (ones when it has none)
+};
+struct CtrlCostArgs {
+    const double* controls;  // [B][nc][Kr]; a complex control k is the channels 2k, 2k+1
+    double* cost;            // out [B]: the sum of the control costs
+    double* grad;            // out [B][nc][Kr]: its gradient, or nullptr
+    double* work0;           // [B][nc][Kr] each: the difference passes of ControlVariation
+    double* work1;
+    const CtrlCostDev* descs;  // the costs that are not bandwidth costs, in the caller's order
+    int count;
+    int B, nc, Kr, cplx;
+};
+// one ControlBandwidthMax: the bins P_k of control k are bins[bin_ptr[k] .. bin_ptr[k + 1])
+struct BandwidthArgs {
+    const double* controls;  // [B][nc][Kr]
+    const double2* twiddle;  // [nc]: exp(-2 pi i m / nc)
+    const int* bins;
+    const int* bin_ptr;      // [K + 1]
+    double2* spectrum;       // [B][Kr][pmax]: the DFT of every real channel at the bins of its control
+    double2* ybar;           // [B][K][pmax]: the cotangents of the bins
+    double* cost;            // [B], added to
+    double* grad;            // [B][nc][Kr], added to, or nullptr
+    double multiplier;       // cost_multiplier / control_count
+    int B, nc, Kr, K, cplx, pmax;
+};
+void launch_control_costs(const CtrlCostArgs& a, hipStream_t st);
+void launch_bandwidth_cost(const BandwidthArgs& a, hipStream_t st);
+// cost[b] += add_cost[b]; grads[e] += add_grad[e] (grads may be nullptr): one addition per entry
+void launch_add_control_costs(double* cost, const double* add_cost, double* grads, const double* add_grad,
+                              int batch, size_t per_seed, hipStream_t st);
 // the Lindblad multi-start driver: per-seed control maxima, seed order <-> sub-division group order
 void launch_control_maxima(const double* controls, int batch, int nc, int k, double* umax, hipStream_t st);
 void launch_gather_seeds(const double* src, double* dst, size_t per_seed, const int* order, int batch,

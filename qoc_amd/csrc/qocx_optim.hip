@@ -19,6 +19,24 @@ __global__ void clip_controls_kernel(double* controls, size_t total, int k, cons
     if (mx < mod) controls[idx] = (v / mod) * mx;
 }
 
+// complex controls (channels 2k, 2k+1 of a knot): the parameters clipped by modulus into the buffer
+// that is evaluated, as clip_control_norms acts on the complex array slap_controls builds - NumPy
+// divides the complex entry by its real modulus through the reciprocal
+__global__ void clip_complex_kernel(const double* params, double* controls, size_t pairs, int k,
+                                    const double* max_norms) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= pairs) return;
+    double re = params[2 * idx], im = params[2 * idx + 1];
+    const double mod = hypot(re, im), mx = max_norms[idx % k];
+    if (mx < mod) {
+        const double inv = 1.0 / mod;
+        re = (re * inv) * mx;
+        im = (im * inv) * mx;
+    }
+    controls[2 * idx] = re;
+    controls[2 * idx + 1] = im;
+}
+
 // best_controls[b] = controls[b], best_final[b] = final[b] for the seeds flagged in `improved`
 __global__ void keep_best_kernel(const double* controls, double* best_controls, size_t per_seed,
                                  const double2* final_states, double2* best_final, size_t final_per_seed,
@@ -119,6 +137,12 @@ void launch_clip_controls(double* controls, size_t total, int k, const double* m
     if (total == 0 || k <= 0) return;
     hipLaunchKernelGGL(clip_controls_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                        controls, total, k, max_norms);
+}
+void launch_clip_complex(const double* params, double* controls, size_t pairs, int k,
+                         const double* max_norms, hipStream_t st) {
+    if (pairs == 0 || k <= 0) return;
+    hipLaunchKernelGGL(clip_complex_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st,
+                       params, controls, pairs, k, max_norms);
 }
 void launch_keep_best(const double* controls, double* best_controls, size_t per_seed,
                       const double2* final_states, double2* best_final, size_t final_per_seed,

@@ -23,6 +23,13 @@ COST_FORBID_DENSITY = 4
 
 MAGNUS_CODES = {"M2": 2, "M4": 4, "M6": 6}
 
+PATH_SCHROEDINGER = 0
+PATH_LINDBLAD = 1
+CONTROL_NORM = 0
+CONTROL_VARIATION = 1
+CONTROL_AREA = 2
+CONTROL_BANDWIDTH_MAX = 3
+
 ERR_SINGULAR = -4
 
 KERNEL_NAMES = ("pade_pq", "sweep", "krylov_grad", "scatter", "lu", "lindblad", "lindblad_combine")
@@ -72,6 +79,12 @@ class QocxError(RuntimeError):
 class _CostDesc(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("step_cost", ctypes.c_int32),
                 ("scale", ctypes.c_double), ("vectors", _c_double_p), ("counts", _c_int_p)]
+
+
+class _ControlCostDesc(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("order", ctypes.c_int32),
+                ("multiplier", ctypes.c_double), ("max_norms", _c_double_p),
+                ("weights", _c_double_p), ("bins", _c_int_p), ("bin_ptr", _c_int_p)]
 
 
 class _SchroedingerProblem(ctypes.Structure):
@@ -176,6 +189,12 @@ SIGNATURES = {
         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32,
         ctypes.c_double]),
     "qocx_lindblad_opt_download_best": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
+    "qocx_set_control_costs": (ctypes.c_int, [_VP, _I32, _I32, _I32,
+                                              ctypes.POINTER(_ControlCostDesc)]),
+    "qocx_eval_control_costs": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p,
+                                               _c_double_p]),
+    "qocx_opt_begin_complex": (ctypes.c_int, [_VP]),
+    "qocx_lindblad_opt_begin_complex": (ctypes.c_int, [_VP]),
     "qocx_host_clip_controls": (ctypes.c_int, [_c_double_p, _I64, _I64, _I32, _c_double_p]),
     "qocx_host_optimizer_update": (ctypes.c_int, [
         _I32, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _I64, ctypes.POINTER(_I64), _I64,
@@ -621,6 +640,11 @@ class Engine(object):
     def opt_begin(self):
         self._check(self._lib.qocx_opt_begin(self._ctx))
 
+    def opt_begin_complex(self):
+        """opt_begin for complex controls (channels 2k, 2k+1): the optimizer's parameters stay
+        unclipped, opt_clip takes one modulus bound per complex control (qocx_opt_begin_complex)."""
+        self._check(self._lib.qocx_opt_begin_complex(self._ctx))
+
     def opt_clip(self, max_norms):
         max_norms = np.ascontiguousarray(max_norms, dtype=np.float64)
         self._check(self._lib.qocx_opt_clip(self._ctx, _dp(max_norms)))
@@ -681,6 +705,9 @@ class Engine(object):
     def lindblad_opt_begin(self):
         self._check(self._lib.qocx_lindblad_opt_begin(self._ctx))
 
+    def lindblad_opt_begin_complex(self):
+        self._check(self._lib.qocx_lindblad_opt_begin_complex(self._ctx))
+
     def lindblad_opt_clip(self, max_norms):
         max_norms = np.ascontiguousarray(max_norms, dtype=np.float64)
         self._check(self._lib.qocx_lindblad_opt_clip(self._ctx, _dp(max_norms)))
@@ -702,6 +729,58 @@ class Engine(object):
         final = np.empty((B, pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
         self._check(self._lib.qocx_lindblad_opt_download_best(self._ctx, _dp(controls), _dp(final)))
         return controls, final
+
+    # -- costs of the controls alone on the device ------------------------------------------------
+    def _control_channels(self, path):
+        if path == PATH_LINDBLAD:
+            return self._lindblad["Nc"], self._lindblad["K"]
+        return self._problem["Nc"], self._seed_channels()
+
+    def set_control_costs(self, path, complex_controls, descriptors):
+        """The costs of the controls alone of the problem `path` (PATH_SCHROEDINGER / PATH_LINDBLAD),
+        added by eval_resident / eval_lindblad_resident from here on (qocx_set_control_costs); an
+        empty list clears them. descriptors :: dicts {kind (CONTROL_*), multiplier, order (optional),
+        max_norms / weights (per control, optional), bins (one ascending index array per control,
+        bandwidth cost)} as the control_descriptor() of the cost classes returns them."""
+        descriptors = list(descriptors)
+        descs = (_ControlCostDesc * max(1, len(descriptors)))()
+        keep = []
+
+        def doubles(values):
+            if values is None:
+                return ctypes.cast(None, _c_double_p)
+            array = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+            keep.append(array)
+            return _dp(array)
+
+        for i, d in enumerate(descriptors):
+            descs[i].kind = int(d["kind"])
+            descs[i].order = int(d.get("order", 0))
+            descs[i].multiplier = float(d["multiplier"])
+            descs[i].max_norms = doubles(d.get("max_norms"))
+            descs[i].weights = doubles(d.get("weights"))
+            if d.get("bins") is not None:
+                sets = [np.asarray(b, dtype=np.int32).reshape(-1) for b in d["bins"]]
+                ptr = np.ascontiguousarray(np.cumsum([0] + [len(b) for b in sets]), dtype=np.int32)
+                bins = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0),
+                                            dtype=np.int32)
+                keep.extend([ptr, bins])
+                descs[i].bins = bins.ctypes.data_as(_c_int_p)
+                descs[i].bin_ptr = ptr.ctypes.data_as(_c_int_p)
+        self._check(self._lib.qocx_set_control_costs(
+            self._ctx, int(path), int(bool(complex_controls)), len(descriptors), descs))
+
+    def eval_control_costs(self, path, controls, want_grad=True):
+        """(cost [B], gradient [B, Nc, channels] or None) of the control costs alone for controls
+        [B, Nc, channels] real (a complex control: channels 2k, 2k+1) (qocx_eval_control_costs)."""
+        nc, channels = self._control_channels(path)
+        controls = np.ascontiguousarray(controls, dtype=np.float64).reshape(-1, nc, channels)
+        cost = np.empty(controls.shape[0], dtype=np.float64)
+        grads = np.empty(controls.shape, dtype=np.float64) if want_grad else None
+        self._check(self._lib.qocx_eval_control_costs(
+            self._ctx, int(path), controls.shape[0], _dp(controls), _dp(cost),
+            _dp(grads) if want_grad else None))
+        return cost, grads
 
     def reduce_results(self, allreduce=False, want_grad=True):
         """(sum of the costs, sum of the gradients [Nc x K] or None) over the seeds of the last

@@ -2,13 +2,21 @@
 controlcosts.py - the four built-in costs that depend on the controls only.
 
 Values follow qoc/standard/costs/controlnorm.py:48-73, controlvariation.py:47-75,
-controlarea.py:43-67 and controlbandwidthmax.py:52-77. They never touch the GPU:
-O(control_eval_count * control_count) NumPy, with closed-form `controls_bar` in qoc's gradient
-convention (d/dRe + i d/dIm for complex controls) in place of autograd.
+controlarea.py:43-67 and controlbandwidthmax.py:52-77: O(control_eval_count * control_count)
+NumPy, with closed-form `controls_bar` in qoc's gradient convention (d/dRe + i d/dIm for complex
+controls) in place of autograd. The single-seed drivers and evaluate_batch call these on the host.
+
+The device-resident multi-start drivers evaluate the same formulas on the GPU
+(qoc_amd/csrc/qocx_ctrlcost.hip): `control_descriptor(control_count, control_eval_count,
+complex_controls)` returns the dict engine.set_control_costs() takes - or None when the host must
+keep the cost so that its Python behaviour survives (shapes that do not match the problem, the
+NameError of ControlArea without max_control_norms, a bandwidth cost without penalised bins).
 """
 
 import numpy as np
 
+from qoc_amd.engine import (CONTROL_AREA, CONTROL_BANDWIDTH_MAX, CONTROL_NORM,
+                            CONTROL_VARIATION)
 from qoc_amd.models.cost import Cost
 
 
@@ -18,6 +26,17 @@ def _abs2(z):
 
 def _match_dtype(grad, controls):
     return grad if np.iscomplexobj(controls) else np.real(grad)
+
+
+def _per_control(values, control_count):
+    """`values` as a float64 (control_count,) array; None if absent; False if it has another
+    shape or is not real (the host keeps such a cost)."""
+    if values is None:
+        return None
+    array = np.asarray(values)
+    if array.shape != (control_count,) or not np.isrealobj(array) or array.dtype == object:
+        return False
+    return np.array(array, dtype=np.float64)
 
 
 class ControlNorm(Cost):
@@ -47,6 +66,15 @@ class ControlNorm(Cost):
         if self.control_weights is not None:
             factor = factor * self.control_weights
         return (2 * self.cost_multiplier / self.controls_size) * controls * factor ** 2
+
+    def control_descriptor(self, control_count, control_eval_count, complex_controls):
+        max_norms = _per_control(self.max_control_norms, control_count)
+        weights = _per_control(self.control_weights, control_count)
+        if (max_norms is False or weights is False
+                or self.controls_size != control_eval_count * control_count):
+            return None
+        return dict(kind=CONTROL_NORM, multiplier=self.cost_multiplier / self.controls_size,
+                    max_norms=max_norms, weights=weights)
 
 
 class ControlVariation(Cost):
@@ -82,6 +110,16 @@ class ControlVariation(Cost):
             back = grown
         return self._normalised(back)
 
+    def control_descriptor(self, control_count, control_eval_count, complex_controls):
+        max_norms = _per_control(self.max_control_norms, control_count)
+        order = self.order
+        if (max_norms is False or not isinstance(order, (int, np.integer))
+                or not 1 <= order < control_eval_count
+                or self.diffs_size != control_count * (control_eval_count - order)):
+            return None
+        return dict(kind=CONTROL_VARIATION, order=int(order), max_norms=max_norms,
+                    multiplier=self.cost_multiplier / self.cost_normalization_constant)
+
 
 class ControlArea(Cost):
     """Modulus of the discrete integral of each normalised control."""
@@ -112,6 +150,14 @@ class ControlArea(Cost):
         direction = np.where(moduli > 0, sums / np.where(moduli > 0, moduli, 1), 0)
         row = (self.cost_multiplier / self.control_size) * direction / self.max_control_norms
         return _match_dtype(np.tile(row, (controls.shape[0], 1)), controls)
+
+    def control_descriptor(self, control_count, control_eval_count, complex_controls):
+        max_norms = _per_control(self.max_control_norms, control_count)
+        if (max_norms is None or max_norms is False or self.control_count != control_count
+                or self.control_size != control_count * control_eval_count):
+            return None  # (without max_control_norms cost() raises the reference's NameError)
+        return dict(kind=CONTROL_AREA, multiplier=self.cost_multiplier / self.control_size,
+                    max_norms=max_norms)
 
 
 class ControlBandwidthMax(Cost):
@@ -151,3 +197,14 @@ class ControlBandwidthMax(Cost):
             spectrum_bar = weight * spectrum / np.where(magnitudes > 0, magnitudes, 1)
             out[:, i] = np.fft.ifft(spectrum_bar) * count * (self.cost_multiplier / self.control_count)
         return _match_dtype(out, controls)
+
+    def control_descriptor(self, control_count, control_eval_count, complex_controls):
+        bandwidths = _per_control(self.max_bandwidths, control_count)
+        if (bandwidths is None or bandwidths is False or self.control_count != control_count
+                or self.freqs.shape[0] != control_eval_count):
+            return None
+        bins = [np.nonzero(self.freqs >= b)[0].astype(np.int32) for b in bandwidths]
+        if any(len(b) == 0 for b in bins):
+            return None  # (numpy.max of an empty array raises in cost())
+        return dict(kind=CONTROL_BANDWIDTH_MAX, bins=bins,
+                    multiplier=self.cost_multiplier / self.control_count)
