@@ -2,7 +2,10 @@
 fuzz_parity.py - TEST TOOLING (parity checker; lives under tests/ because it drives the oracle): random problem shapes, engine (through the C ABI) against the
 oracle. Complements the fixed fixtures: sizes 1..32 (any range by argument, up to 256), random step counts / control grids / state
 counts / time steps (so that 0..4 squarings occur), all three Magnus policies, Hermitian and
-non-Hermitian generators, all state-cost kinds at once.
+non-Hermitian generators, all state-cost kinds at once. With shapes=True (fuzz_parity.one) each
+seed of a draw gets a pulse family of tests/mixed_pulses.py (quiet, bell, spike, square, ramp,
+loud) and an amplitude of its own instead of one shared Gaussian scale, so that the steps of one
+upload differ in Pade order, squaring count and pivoting regime.
 
     python -m tests.fuzz_parity [count] [seed] [nmin] [nmax] [smin] [smax]
 """
@@ -17,12 +20,13 @@ from oracle import qoc_numpy as onp  # noqa: E402
 from qoc_amd.engine import (Engine, QocxError, COST_FORBID, COST_TARGET_COHERENT,  # noqa: E402
                             COST_TARGET_INCOHERENT)
 from tests.cases import gue  # noqa: E402
+from tests.mixed_pulses import FAMILIES, families  # noqa: E402
 
 NODES = {"M2": (0.5,), "M4": (0.5 - 3 ** 0.5 / 6, 0.5 + 3 ** 0.5 / 6),
          "M6": (0.5 - 15 ** 0.5 / 10, 0.5, 0.5 + 15 ** 0.5 / 10)}
 
 
-def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None):
+def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shapes=False):
     n = int(rng.integers(nmin, nmax + 1))
     N = int(rng.integers(2, 14))
     K = int(rng.integers(1, 4))
@@ -71,9 +75,17 @@ def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None):
         h0s, gs = h0[None], np.stack(g)[None]
     engine.set_schroedinger_problem(n, S, K, Nc, N, T, h0s, gs, init, costs=descs,
                                     cost_eval_step=ces, magnus_policy=policy)
-    controls = float(10 ** rng.uniform(-1, 0.5)) * rng.standard_normal((2, Nc, K))
     tag = "n={} N={} Nc={} K={} S={} ces={} {} herm={} tdep={} dt={:.3g} |H|={:.3g}".format(
         n, N, Nc, K, S, ces, policy, hermitian, time_dep, dt, scale)
+    if shapes:
+        # (peak amplitude three times the Gaussian scale of the default draw: its 3 sigma)
+        picks = [(FAMILIES[int(rng.integers(0, len(FAMILIES)))], 3 * float(10 ** rng.uniform(-1, 0.5)))
+                 for _ in range(2)]
+        controls = np.stack([families(Nc, K, amp, rng, quiet_sigma=0.02 * amp)[name]
+                             for name, amp in picks])
+        tag += " " + " ".join("{}:{:.3g}".format(name, amp) for name, amp in picks)
+    else:
+        controls = float(10 ** rng.uniform(-1, 0.5)) * rng.standard_normal((2, Nc, K))
     try:
         cost, grads, final = engine.evaluate(controls, want_grad=True)
     except QocxError as exc:
