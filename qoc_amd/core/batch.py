@@ -13,6 +13,7 @@ Adam moments and the best so far stay in HBM and the host sees B costs per itera
 
 import numpy as np
 
+from qoc_amd.core import structure
 from qoc_amd.core.common import initialize_controls, strip_controls
 from qoc_amd.models import Dummy
 from qoc_amd.standard.optimizers import SGD, Adam
@@ -293,6 +294,41 @@ def _finish(result, comm):
     best_local = float(np.min(result.best_error)) if len(result.best_error) else np.inf
     result.global_best_error = float(-comm.allreduce_max(np.array([-best_local]))[0])
     return result
+
+
+class ResidentOps(object):
+    """One path's resident driver of the engine as run_batch_resident calls it. `calls` are the
+    engine's bound methods of that path under the loop's names: upload_controls, opt_begin (the
+    complex one for complex controls), opt_clip, eval_resident, download_costs, opt_step,
+    opt_download_best.
+    control_costs: the descriptors of the costs of the controls alone, which the engine then adds
+    to every resident evaluation of `path` until finish(); complex_controls: the loop's complex
+    arrays travel as two real channels per control and the engine clips a copy of the parameters;
+    column_states: the final states come back as columns ([B, S, n, 1], Schroedinger)."""
+
+    def __init__(self, engine, path, control_costs, complex_controls, column_states=False, **calls):
+        self.engine = engine
+        self.path = path
+        self.control_costs = list(control_costs)
+        self.complex_controls = complex_controls
+        self.column_states = column_states
+        self._upload_controls = calls.pop("upload_controls")
+        self._opt_download_best = calls.pop("opt_download_best")
+        self.__dict__.update(calls)  # opt_begin, opt_clip, eval_resident, download_costs, opt_step
+
+    def upload_controls(self, controls):
+        if self.control_costs:
+            self.engine.set_control_costs(self.path, self.complex_controls, self.control_costs)
+        self._upload_controls(structure.to_real_controls(controls, self.complex_controls))
+
+    def opt_download_best(self):
+        controls, finals = self._opt_download_best()
+        return (structure.from_real_gradients(controls, self.complex_controls),
+                finals[..., None] if self.column_states else finals)
+
+    def finish(self):
+        if self.control_costs:  # evaluate_batch and the single-seed entry points keep them on the host
+            self.engine.set_control_costs(self.path, self.complex_controls, [])
 
 
 def run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iteration_step,

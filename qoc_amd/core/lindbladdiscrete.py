@@ -12,7 +12,7 @@ the parity tolerances that follow from replacing an adaptive integrator).
 
 import numpy as np
 
-from qoc_amd.core import batch, structure
+from qoc_amd.core import batch
 from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
                                  strip_controls)
 from qoc_amd.core.device import LindbladEvaluator
@@ -164,34 +164,16 @@ class GrapeLindbladBatchResult(batch.BatchResult):
     final_field = "best_final_densities"
 
 
-class _ResidentOps(object):
+def _ResidentOps(engine, control_costs=(), complex_controls=False):
     """engine.lindblad_* (the Lindblad problem's resident buffers) as the resident loop of
-    core/batch.py calls them."""
-
-    def __init__(self, engine, control_costs=(), complex_controls=False):
-        self.engine = engine
-        self.control_costs = list(control_costs)
-        self.complex_controls = complex_controls
-        self.opt_begin = (engine.lindblad_opt_begin_complex if complex_controls
-                          else engine.lindblad_opt_begin)
-        self.opt_clip = engine.lindblad_opt_clip
-        self.eval_resident = engine.eval_lindblad_resident
-        self.download_costs = engine.lindblad_download_costs
-        self.opt_step = engine.lindblad_opt_step
-
-    def upload_controls(self, controls):
-        if self.control_costs:
-            self.engine.set_control_costs(PATH_LINDBLAD, self.complex_controls, self.control_costs)
-        self.engine.lindblad_upload_controls(
-            structure.to_real_controls(controls, self.complex_controls))
-
-    def opt_download_best(self):
-        controls, finals = self.engine.lindblad_opt_download_best()
-        return structure.from_real_gradients(controls, self.complex_controls), finals
-
-    def finish(self):
-        if self.control_costs:  # evaluate_batch and the single-seed entry points keep them on the host
-            self.engine.set_control_costs(PATH_LINDBLAD, self.complex_controls, [])
+    core/batch.py calls them. A function under the name of the class it replaced."""
+    return batch.ResidentOps(
+        engine, PATH_LINDBLAD, control_costs, complex_controls,
+        upload_controls=engine.lindblad_upload_controls,
+        opt_begin=engine.lindblad_opt_begin_complex if complex_controls else engine.lindblad_opt_begin,
+        opt_clip=engine.lindblad_opt_clip, eval_resident=engine.eval_lindblad_resident,
+        download_costs=engine.lindblad_download_costs, opt_step=engine.lindblad_opt_step,
+        opt_download_best=engine.lindblad_opt_download_best)
 
 
 def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evolution_time,

@@ -9,7 +9,7 @@ MI355X through qoc_amd.core.device.SchroedingerEvaluator.
 
 import numpy as np
 
-from qoc_amd.core import batch, structure
+from qoc_amd.core import batch
 from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
                                  strip_controls)
 from qoc_amd.core.device import SchroedingerEvaluator
@@ -168,39 +168,16 @@ class GrapeSchroedingerBatchResult(batch.BatchResult):
     final_field = "best_final_states"
 
 
-class _ResidentOps(object):
+def _ResidentOps(engine, control_costs=(), complex_controls=False):
     """engine.opt_* as the resident loop of core/batch.py calls it (final states [B, S, n, 1]).
-    control_costs: the descriptors of the costs of the controls alone, which the engine then
-    adds to every resident evaluation until finish(); complex_controls: the loop's complex arrays
-    travel as two real channels per control and the engine clips a copy of the parameters."""
-
-    def __init__(self, engine, control_costs=(), complex_controls=False):
-        self.engine = engine
-        self.control_costs = list(control_costs)
-        self.complex_controls = complex_controls
-
-    def __getattr__(self, name):
-        return getattr(self.engine, name)
-
-    def upload_controls(self, controls):
-        if self.control_costs:
-            self.engine.set_control_costs(PATH_SCHROEDINGER, self.complex_controls,
-                                          self.control_costs)
-        self.engine.upload_controls(structure.to_real_controls(controls, self.complex_controls))
-
-    def opt_begin(self):
-        if self.complex_controls:
-            self.engine.opt_begin_complex()
-        else:
-            self.engine.opt_begin()
-
-    def opt_download_best(self):
-        controls, finals = self.engine.opt_download_best()
-        return structure.from_real_gradients(controls, self.complex_controls), finals[..., None]
-
-    def finish(self):
-        if self.control_costs:  # evaluate_batch and the single-seed entry points keep them on the host
-            self.engine.set_control_costs(PATH_SCHROEDINGER, self.complex_controls, [])
+    A function under the name of the class it replaced: tools and tests build their ops with it."""
+    return batch.ResidentOps(
+        engine, PATH_SCHROEDINGER, control_costs, complex_controls, column_states=True,
+        upload_controls=engine.upload_controls,
+        opt_begin=engine.opt_begin_complex if complex_controls else engine.opt_begin,
+        opt_clip=engine.opt_clip, eval_resident=engine.eval_resident,
+        download_costs=engine.download_costs, opt_step=engine.opt_step,
+        opt_download_best=engine.opt_download_best)
 
 
 def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, evolution_time,

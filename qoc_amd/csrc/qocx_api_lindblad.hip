@@ -1,0 +1,1104 @@
+// qocx_api_lindblad.hip - the Lindblad path of the C ABI (include/qocx.h): problem upload,
+// sub-interval grids and sub-division planning, the evaluation from host buffers and the resident one
+// of the multi-start driver, density cotangents and the downloads.
+#include <time.h>
+
+#include "dop853_tableau.h"
+#include "qocx_host.h"
+
+namespace {
+
+// Largest singular value of a complex n x n matrix (row-major, interleaved), for the step-size
+// rule of the Lindblad integrator: power iteration on A^H A from a fixed start vector, stopped at
+// 1e-4 relative change; the estimate comes from below, so 2 % are added, and it never exceeds the
+// rigorous bound sqrt(||A||_1 ||A||_inf). (The 1-norm used before over-estimates the 2-norm of a
+// dense Hermitian matrix by 2-3x, i.e. made the integrator take 2-3x more sub-intervals than the
+// same threshold on the operator norm asks for.)
+double two_norm(const double* m, int n) {
+    double n1 = one_norm(m, n), ninf = 0;
+    for (int r = 0; r < n; ++r) {
+        double sum = 0;
+        for (int c = 0; c < n; ++c) sum += hypot(m[2 * ((size_t)r * n + c)], m[2 * ((size_t)r * n + c) + 1]);
+        ninf = std::max(ninf, sum);
+    }
+    const double upper = std::sqrt(n1 * ninf);
+    if (!(upper > 0) || !(upper < 1e300)) return upper;
+    std::vector<double> v(2 * n), w(2 * n);
+    double nv = 0;
+    for (int i = 0; i < n; ++i) {
+        v[2 * i] = 1.0 + 0.37 * i / n;
+        v[2 * i + 1] = 0.11 * ((i * 7) % 5);
+        nv += v[2 * i] * v[2 * i] + v[2 * i + 1] * v[2 * i + 1];
+    }
+    nv = std::sqrt(nv);
+    for (auto& e : v) e /= nv;
+    double sigma = 0, prev = -1;
+    for (int it = 0; it < 200; ++it) {
+        double nw = 0;
+        for (int r = 0; r < n; ++r) {  // w = A v
+            double re = 0, im = 0;
+            for (int c = 0; c < n; ++c) {
+                const double ar = m[2 * ((size_t)r * n + c)], ai = m[2 * ((size_t)r * n + c) + 1];
+                re += ar * v[2 * c] - ai * v[2 * c + 1];
+                im += ar * v[2 * c + 1] + ai * v[2 * c];
+            }
+            w[2 * r] = re; w[2 * r + 1] = im;
+            nw += re * re + im * im;
+        }
+        sigma = std::sqrt(nw);  // ||A v||, ||v|| = 1
+        if (!(sigma > 0)) break;
+        if (it >= 6 && std::fabs(sigma - prev) <= 1e-4 * sigma) break;
+        prev = sigma;
+        double nn = 0;
+        for (int c = 0; c < n; ++c) {  // v = A^H w, normalised
+            double re = 0, im = 0;
+            for (int r = 0; r < n; ++r) {
+                const double ar = m[2 * ((size_t)r * n + c)], ai = m[2 * ((size_t)r * n + c) + 1];
+                re += ar * w[2 * r] + ai * w[2 * r + 1];
+                im += ar * w[2 * r + 1] - ai * w[2 * r];
+            }
+            v[2 * c] = re; v[2 * c + 1] = im;
+            nn += re * re + im * im;
+        }
+        nn = std::sqrt(nn);
+        if (!(nn > 0)) break;
+        for (auto& e : v) e /= nn;
+    }
+    return std::min(1.02 * sigma, upper);
+}
+
+// C-layout dump of an n x n matrix padded to 16 nb: reg r of tile (ti, tj) of lane l <-> element
+// (row 16 ti + 4 r + (l >> 4), col 16 tj + (l & 15)), index ((ti nb + tj) 4 + r) 64 + l
+int dump_tiles(int n) { return n <= 16 ? 1 : 2; }
+
+}  // namespace
+
+namespace qocx::host {
+
+int dump_elems(int n) { return 256 * dump_tiles(n) * dump_tiles(n); }
+
+void from_c_dump(const double2* d, int n, double* out) {
+    const int nb = dump_tiles(n);
+    for (int ti = 0; ti < nb; ++ti)
+        for (int tj = 0; tj < nb; ++tj)
+            for (int r = 0; r < 4; ++r)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int row = 16 * ti + 4 * r + (lane >> 4), col = 16 * tj + (lane & 15);
+                    if (row < n && col < n) {
+                        const double2 e = d[((ti * nb + tj) * 4 + r) * 64 + lane];
+                        out[2 * ((size_t)row * n + col)] = e.x;
+                        out[2 * ((size_t)row * n + col) + 1] = e.y;
+                    }
+                }
+}
+
+}  // namespace qocx::host
+
+extern "C" {
+
+// ---- Lindblad ----------------------------------------------------------------------------
+
+extern "C++" {
+namespace {
+
+typedef std::vector<double> cmat;  // row-major n x n complex, interleaved
+
+cmat cm_zero(int n) { return cmat((size_t)2 * n * n, 0.0); }
+
+cmat cm_from(const double* p, int n) { return cmat(p, p + (size_t)2 * n * n); }
+
+// M = M^H to rounding: max |M - M^H| <= 64 eps max |M|
+bool cm_is_hermitian(const cmat& a, int n) {
+    double big = 0, diff = 0;
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c <= r; ++c) {
+            const double xr = a[2 * ((size_t)r * n + c)], xi = a[2 * ((size_t)r * n + c) + 1];
+            const double yr = a[2 * ((size_t)c * n + r)], yi = a[2 * ((size_t)c * n + r) + 1];
+            big = std::max(big, std::max(fabs(xr), fabs(xi)));
+            diff = std::max(diff, std::max(fabs(xr - yr), fabs(xi + yi)));
+        }
+    return diff <= 1.5e-14 * big;
+}
+
+cmat cm_adjoint(const cmat& a, int n) {
+    cmat o = cm_zero(n);
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) {
+            o[2 * ((size_t)c * n + r)] = a[2 * ((size_t)r * n + c)];
+            o[2 * ((size_t)c * n + r) + 1] = -a[2 * ((size_t)r * n + c) + 1];
+        }
+    return o;
+}
+
+cmat cm_transpose(const cmat& a, int n) {
+    cmat o = cm_zero(n);
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) {
+            o[2 * ((size_t)c * n + r)] = a[2 * ((size_t)r * n + c)];
+            o[2 * ((size_t)c * n + r) + 1] = a[2 * ((size_t)r * n + c) + 1];
+        }
+    return o;
+}
+
+cmat cm_mul(const cmat& a, const cmat& b, int n) {
+    cmat o = cm_zero(n);
+    for (int r = 0; r < n; ++r)
+        for (int k = 0; k < n; ++k) {
+            const double ar = a[2 * ((size_t)r * n + k)], ai = a[2 * ((size_t)r * n + k) + 1];
+            for (int c = 0; c < n; ++c) {
+                const double br = b[2 * ((size_t)k * n + c)], bi = b[2 * ((size_t)k * n + c) + 1];
+                o[2 * ((size_t)r * n + c)] += ar * br - ai * bi;
+                o[2 * ((size_t)r * n + c) + 1] += ar * bi + ai * br;
+            }
+        }
+    return o;
+}
+
+// o = alpha * a (alpha complex)
+cmat cm_scale(const cmat& a, double sr, double si) {
+    cmat o(a.size());
+    for (size_t e = 0; e < a.size(); e += 2) {
+        o[e] = sr * a[e] - si * a[e + 1];
+        o[e + 1] = sr * a[e + 1] + si * a[e];
+    }
+    return o;
+}
+
+void cm_axpy(cmat& y, double alpha, const cmat& x) {
+    for (size_t e = 0; e < y.size(); ++e) y[e] += alpha * x[e];
+}
+
+
+void c_dump(const cmat& m, int n, double2* out) {
+    const int nb = dump_tiles(n);
+    for (int ti = 0; ti < nb; ++ti)
+        for (int tj = 0; tj < nb; ++tj)
+            for (int r = 0; r < 4; ++r)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int row = 16 * ti + 4 * r + (lane >> 4), col = 16 * tj + (lane & 15);
+                    double2 e = make_double2(0, 0);
+                    if (row < n && col < n) {
+                        e.x = m[2 * ((size_t)row * n + col)];
+                        e.y = m[2 * ((size_t)row * n + col) + 1];
+                    }
+                    out[((ti * nb + tj) * 4 + r) * 64 + lane] = e;
+                }
+}
+
+
+double cm_norm_inf(const cmat& m, int n) {
+    double best = 0;
+    for (int r = 0; r < n; ++r) {
+        double s = 0;
+        for (int c = 0; c < n; ++c) s += hypot(m[2 * ((size_t)r * n + c)], m[2 * ((size_t)r * n + c) + 1]);
+        best = std::max(best, s);
+    }
+    return best;
+}
+
+// Spectral norm of the control-free Liouvillian X -> A_L X + X A_R + sum_i gamma_i L_i X L_i^H as
+// an operator on C^(n x n) (Frobenius inner product): matrix-free power iteration on its
+// adjoint-times-itself, stopped at 1e-4 relative change, + 2 % (the estimate comes from below).
+// The sum of the parts' bounds (2 ||H0||_2 + 2 sum gamma ||L||_2^2) over-estimates it 2-3x when
+// the dissipators are stiff in a few levels only (a^H a of a 16-level oscillator), and the
+// integrator's sub-division count is proportional to this number.
+double liouvillian_norm(const cmat& al, const cmat& ar, const std::vector<cmat>& ops,
+                        const std::vector<double>& gammas, int n) {
+    const cmat alh = cm_adjoint(al, n), arh = cm_adjoint(ar, n);
+    std::vector<cmat> opsh;
+    for (const auto& o : ops) opsh.push_back(cm_adjoint(o, n));
+    auto apply = [&](const cmat& x, bool adjoint) {
+        cmat y = cm_mul(adjoint ? alh : al, x, n);
+        cm_axpy(y, 1.0, cm_mul(x, adjoint ? arh : ar, n));
+        for (size_t i = 0; i < ops.size(); ++i)
+            cm_axpy(y, gammas[i], adjoint ? cm_mul(cm_mul(opsh[i], x, n), ops[i], n)
+                                          : cm_mul(cm_mul(ops[i], x, n), opsh[i], n));
+        return y;
+    };
+    auto fro = [](const cmat& x) {
+        double s = 0;
+        for (double e : x) s += e * e;
+        return std::sqrt(s);
+    };
+    cmat x((size_t)2 * n * n);
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) {
+            x[2 * ((size_t)r * n + c)] = 1.0 / (1.0 + r + c) + (r == c ? 1.0 : 0.0);
+            x[2 * ((size_t)r * n + c) + 1] = 0.3 * ((3 * r + c) % 4) - 0.4;
+        }
+    double nx = fro(x);
+    for (auto& e : x) e /= nx;
+    double sigma = 0, prev = -1;
+    for (int it = 0; it < 400; ++it) {
+        const cmat y = apply(x, false);
+        sigma = fro(y);
+        if (!(sigma > 0) || !(sigma < 1e300)) break;
+        if (it >= 8 && std::fabs(sigma - prev) <= 1e-4 * sigma) break;
+        prev = sigma;
+        x = apply(y, true);
+        nx = fro(x);
+        if (!(nx > 0)) break;
+        for (auto& e : x) e /= nx;
+    }
+    return 1.02 * sigma;
+}
+
+int upload_dumps(DevBuf<double2>& dst, const std::vector<cmat>& mats, int n, hipStream_t st) {
+    const size_t md = dump_elems(n);
+    std::vector<double2> img(mats.size() * md);
+    for (size_t i = 0; i < mats.size(); ++i) c_dump(mats[i], n, img.data() + i * md);
+    return dst.upload(img, st);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
+    if (!ctx || !p) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (p->struct_size != (int32_t)sizeof(qocx_lindblad_problem))
+        return fail(QOCX_ERR_ARG, "qocx_lindblad_problem.struct_size does not match this "
+                                  "library's header (stale binding?)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int n = p->hilbert_size, S = p->density_count, K = p->control_count;
+    const int N = p->system_eval_count, nc = p->control_eval_count, L = p->operator_count;
+    if (n < 1 || n > 32)
+        return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..32 for the Lindblad engine");
+    if (S < 1 || S > 64) return fail(QOCX_ERR_ARG, "density_count must be in 1..64");
+    if (K < 0 || K > QOCX_LINDBLAD_MAX_K) return fail(QOCX_ERR_ARG, "control_count must be in 0..8");
+    // (1..4 operators: the several-wave / tile-per-wave stage loops; 5..8: the one-wave kernels, whose stage
+    // loop walks any number of operators)
+    if (L < 0 || L > 8) return fail(QOCX_ERR_ARG, "operator_count must be in 0..8");
+    if (N < 2) return fail(QOCX_ERR_ARG, "system_eval_count must be >= 2");
+    if (K > 0 && nc < 2) return fail(QOCX_ERR_ARG, "control_eval_count must be >= 2");
+    if (p->cost_eval_step < 1) return fail(QOCX_ERR_ARG, "cost_eval_step must be >= 1");
+    if (!p->initial_densities || (K > 0 && !p->g) || (L > 0 && (!p->operators || !p->dissipators)))
+        return fail(QOCX_ERR_ARG, "missing problem arrays");
+    // densities, cotangents and stage derivatives live in LDS when they fit (n <= 16), else in
+    // per-seed HBM scratch
+    ctx->lb.global_scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;
+    if (qocx::lindblad_lds_size(n, S, L, ctx->lb.global_scratch, K) > 160 * 1024)
+        return fail(QOCX_ERR_ARG, "too many operators for the kernel's LDS");
+    // several waves per seed (generator terms | one per operator | control cotangents) whenever
+    // that layout fits LDS: the recursion in time is serial, this shortens every stage
+    // (ONE operator - the T1 problem - runs the several-wave launches as two, the second one zero: the
+    // four-wave stage loops of section 14 exist for L = 2 only and are 1.5 times faster than the three-wave
+    // form of L = 1 although they multiply by that zero: 17.2 -> 11.5 ms on configs[3]'s sizes)
+    ctx->lb.pad_op = (L == 1 && n <= 16 && p->op_stages == nullptr && ctx->knob("lindblad_pad_operator", 1) != 0) ? 1 : 0;
+    const int Lmw = ctx->lb.pad_op ? 2 : L;
+    ctx->lb.multi_wave = (!ctx->lb.global_scratch && L > 0 && L <= 4 &&
+                          qocx::lindblad_lds_size(n, S, Lmw, 2, K) <= 160 * 1024 &&
+                          !qocx::diag_getenv("QOCX_LINDBLAD_SINGLE_WAVE")) ? 1 : 0;
+    ctx->lb.cache_gen = (ctx->lb.multi_wave && p->fixed_subdivision <= 0 &&
+                         qocx::lindblad_lds_size(n, S, Lmw, 3, K) <= 160 * 1024) ? 1 : 0;
+    auto& lb = ctx->lb;
+    lb.has_problem = false;
+    lb.control_costs.clear();
+    lb.n = n; lb.S = S; lb.K = K; lb.nc = nc; lb.N = N; lb.nsteps = N - 1; lb.ces = p->cost_eval_step;
+    lb.nops = L; lb.T = p->evolution_time; lb.dt = p->evolution_time / (N - 1);
+
+    const cmat h0 = p->h0 ? cm_from(p->h0, n) : cm_zero(n);
+    cmat decay = cm_zero(n);  // sum gamma_i L_i^H L_i
+    std::vector<cmat> ops;
+    std::vector<double> gammas(L);
+    lb.diss_norm = 0;
+    for (int i = 0; i < L; ++i) {
+        ops.push_back(cm_from(p->operators + (size_t)i * n * n * 2, n));
+        gammas[i] = p->dissipators[i];
+        cm_axpy(decay, gammas[i], cm_mul(cm_adjoint(ops[i], n), ops[i], n));
+        // || rho -> gamma (L rho L^H - {L^H L, rho} / 2) || <= 2 gamma ||L||_2^2 (the factor 2 is
+        // applied where the bound is formed)
+        const double opn = two_norm(ops[i].data(), n);
+        lb.diss_norm += fabs(gammas[i]) * opn * opn;
+    }
+    if (lb.pad_op) {
+        ops.push_back(cm_zero(n));
+        gammas.push_back(0.0);
+    }
+    lb.ops_real = p->op_stages == nullptr;
+    for (const cmat& op : ops)
+        for (size_t e = 0; e < (size_t)n * n; ++e)
+            if (op[2 * e + 1] != 0.0) lb.ops_real = false;
+    // A0L = -i H0 - decay/2 ; A0R = +i H0 - decay/2   (mathmethods.py:188, :200-203)
+    cmat a0l = cm_scale(h0, 0.0, -1.0), a0r = cm_scale(h0, 0.0, 1.0);
+    cm_axpy(a0l, -0.5, decay);
+    cm_axpy(a0r, -0.5, decay);
+    lb.hermitian = p->h0_stages == nullptr && p->g_stages == nullptr && p->op_stages == nullptr &&
+                   cm_is_hermitian(h0, n) && cm_is_hermitian(decay, n);
+    lb.h0_norm = two_norm(h0.data(), n);
+    // static problem: the control-free Liouvillian as a whole (never above the sum of the parts)
+    lb.l0_norm = std::min(liouvillian_norm(a0l, a0r, ops, gammas, n),
+                          2 * lb.h0_norm + 2 * lb.diss_norm);
+    if (!(lb.l0_norm < 1e300)) lb.l0_norm = 2 * lb.h0_norm + 2 * lb.diss_norm;
+    std::vector<cmat> gp, gpd, gpt;
+    lb.g_norm.assign(K, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const cmat gk = cm_from(p->g + (size_t)k * n * n * 2, n);
+        lb.g_norm[k] = two_norm(gk.data(), n);
+        lb.hermitian = lb.hermitian && cm_is_hermitian(gk, n);
+        gp.push_back(cm_scale(gk, 0.0, -1.0));  // Gp = -i G
+        gpd.push_back(cm_adjoint(gp.back(), n));
+        gpt.push_back(cm_transpose(gp.back(), n));
+    }
+    if (upload_dumps(lb.a0l, {a0l}, n, ctx->stream) || upload_dumps(lb.a0r, {a0r}, n, ctx->stream) ||
+        upload_dumps(lb.a0ld, {cm_adjoint(a0l, n)}, n, ctx->stream) ||
+        upload_dumps(lb.a0rd, {cm_adjoint(a0r, n)}, n, ctx->stream) ||
+        upload_dumps(lb.gp, gp, n, ctx->stream) || upload_dumps(lb.gpd, gpd, n, ctx->stream) ||
+        upload_dumps(lb.gpt, gpt, n, ctx->stream) || upload_dumps(lb.ops, ops, n, ctx->stream) ||
+        lb.gammas.upload(gammas, ctx->stream))
+        return QOCX_ERR_HIP;
+    // Time-dependent Hamiltonian: samples at the stage times of the fixed sub-division
+    // (qocx_lindblad_stage_times), turned into per-stage generator dumps.
+    lb.fixed_ksub = 0;
+    lb.a0_tab.release();
+    lb.gp_tab.release();
+    lb.op_tab.release();
+    lb.gamma_tab.release();
+    const bool td_ops = p->op_stages != nullptr && L > 0;
+    if ((p->op_stages != nullptr) != (p->diss_stages != nullptr))
+        return fail(QOCX_ERR_ARG, "diss_stages and op_stages go together");
+    if (td_ops && p->fixed_subdivision <= 0)
+        return fail(QOCX_ERR_ARG, "time-dependent lindblad_data needs fixed_subdivision > 0");
+    if (p->fixed_subdivision > 0) {
+        if (!p->h0_stages) return fail(QOCX_ERR_ARG, "h0_stages missing");
+        int64_t count = 0;
+        int rc = qocx_lindblad_stage_times(p->evolution_time, N, nc, K, p->fixed_subdivision, nullptr,
+                                           0, &count);
+        if (rc) return rc;
+        const size_t md = dump_elems(n);
+        std::vector<double2> tab((size_t)count * 4 * md);
+        lb.h0_norm = 0;
+        std::vector<double2> otab(td_ops ? (size_t)count * L * md : 0);
+        std::vector<double> gtab_d(td_ops ? (size_t)count * L : 0);
+        if (td_ops) lb.diss_norm = 0;
+        for (int64_t st = 0; st < count; ++st) {
+            const cmat h = cm_from(p->h0_stages + (size_t)st * n * n * 2, n);
+            // (norms on every fourth stage sample: they vary smoothly in time, the host picked
+            // the sub-division with a 25 % margin, and a power iteration per sample is what made
+            // this loop slow)
+            const bool norm_sample = (st % 4 == 0) || st == count - 1;
+            if (norm_sample) lb.h0_norm = std::max(lb.h0_norm, two_norm(h.data(), n));
+            cmat l = cm_scale(h, 0.0, -1.0), r = cm_scale(h, 0.0, 1.0);
+            cmat decay_st = decay;
+            if (td_ops) {  // -1/2 sum_i gamma_i(t) L_i(t)^H L_i(t) of THIS stage time
+                decay_st = cm_zero(n);
+                double dn = 0;
+                for (int i = 0; i < L; ++i) {
+                    const cmat li = cm_from(p->op_stages + ((size_t)st * L + i) * n * n * 2, n);
+                    const double gi = p->diss_stages[(size_t)st * L + i];
+                    cm_axpy(decay_st, gi, cm_mul(cm_adjoint(li, n), li, n));
+                    c_dump(li, n, otab.data() + ((size_t)st * L + i) * md);
+                    gtab_d[(size_t)st * L + i] = gi;
+                    if (norm_sample) {
+                        const double opn = two_norm(li.data(), n);
+                        dn += fabs(gi) * opn * opn;
+                    }
+                }
+                lb.diss_norm = std::max(lb.diss_norm, dn);
+            }
+            cm_axpy(l, -0.5, decay_st);
+            cm_axpy(r, -0.5, decay_st);
+            c_dump(l, n, tab.data() + ((size_t)st * 4 + 0) * md);
+            c_dump(r, n, tab.data() + ((size_t)st * 4 + 1) * md);
+            c_dump(cm_adjoint(l, n), n, tab.data() + ((size_t)st * 4 + 2) * md);
+            c_dump(cm_adjoint(r, n), n, tab.data() + ((size_t)st * 4 + 3) * md);
+        }
+        if (lb.a0_tab.upload(tab, ctx->stream)) return QOCX_ERR_HIP;
+        if (td_ops && (lb.op_tab.upload(otab, ctx->stream) || lb.gamma_tab.upload(gtab_d, ctx->stream)))
+            return QOCX_ERR_HIP;
+        if (p->g_stages && K > 0) {
+            std::vector<double2> gtab((size_t)count * K * 3 * md);
+            lb.g_norm.assign(K, 0.0);
+            for (int64_t st = 0; st < count; ++st)
+                for (int k = 0; k < K; ++k) {
+                    const cmat gk = cm_from(p->g_stages + ((size_t)st * K + k) * n * n * 2, n);
+                    if (st % 4 == 0 || st == count - 1)
+                        lb.g_norm[k] = std::max(lb.g_norm[k], two_norm(gk.data(), n));
+                    const cmat gpk = cm_scale(gk, 0.0, -1.0);
+                    double2* dst = gtab.data() + (((size_t)st * K + k) * 3) * md;
+                    c_dump(gpk, n, dst);
+                    c_dump(cm_adjoint(gpk, n), n, dst + md);
+                    c_dump(cm_transpose(gpk, n), n, dst + 2 * md);
+                }
+            if (lb.gp_tab.upload(gtab, ctx->stream)) return QOCX_ERR_HIP;
+        }
+        lb.fixed_ksub = p->fixed_subdivision;
+    }
+    std::vector<cmat> rho0;
+    for (int s = 0; s < S; ++s) rho0.push_back(cm_from(p->initial_densities + (size_t)s * n * n * 2, n));
+    if (upload_dumps(lb.rho0, rho0, n, ctx->stream)) return QOCX_ERR_HIP;
+    for (const cmat& r : rho0) lb.hermitian = lb.hermitian && cm_is_hermitian(r, n);
+
+    std::vector<qocx::DevCost> dcosts;
+    std::vector<cmat> pool;
+    std::vector<int> counts;
+    lb.has_step_costs = 0;
+    for (int ci = 0; ci < p->cost_count; ++ci) {
+        const qocx_cost_desc& c = p->costs[ci];
+        qocx::DevCost d;
+        d.step_cost = c.step_cost ? 1 : 0;
+        d.scale = c.scale;
+        d.vec_offset = (int)pool.size();
+        d.cnt_offset = (int)counts.size();
+        if (!c.vectors) return fail(QOCX_ERR_ARG, "cost matrices missing");
+        int nmat = S;
+        if (c.kind == QOCX_COST_TARGET_DENSITY) {
+            d.kind = QOCX_DEV_COST_TARGET_DENSITY;
+        } else if (c.kind == QOCX_COST_FORBID_DENSITY) {
+            d.kind = QOCX_DEV_COST_FORBID_DENSITY;
+            if (!c.counts) return fail(QOCX_ERR_ARG, "forbid counts missing");
+            nmat = 0;
+            for (int s = 0; s < S; ++s) {
+                if (c.counts[s] < 1) return fail(QOCX_ERR_ARG, "forbid count < 1");
+                counts.push_back(c.counts[s]);
+                nmat += c.counts[s];
+            }
+        } else {
+            return fail(QOCX_ERR_ARG, "cost kind not valid for the Lindblad path");
+        }
+        for (int m = 0; m < nmat; ++m) pool.push_back(cm_from(c.vectors + (size_t)m * n * n * 2, n));
+        if (d.step_cost) lb.has_step_costs = 1;
+        dcosts.push_back(d);
+    }
+    for (const cmat& m : pool) lb.hermitian = lb.hermitian && cm_is_hermitian(m, n);
+    lb.cost_count = (int)dcosts.size();
+    lb.unit_ok = dcosts.size() == 1 && !dcosts[0].step_cost &&
+                 dcosts[0].kind == QOCX_DEV_COST_TARGET_DENSITY;
+    if (lb.costs.upload(dcosts, ctx->stream) || upload_dumps(lb.cost_matrices, pool, n, ctx->stream) ||
+        lb.cost_counts.upload(counts, ctx->stream))
+        return QOCX_ERR_HIP;
+    lb.grids.clear();  // (frees the tables of the old problem's grids)
+    lb.has_problem = true;
+    lb.have_results = false;
+    lb.res_B = lb.ms.batch = 0;  // resident controls and optimizer states belong to the old problem
+    lb.res_have_results = false;
+    lb.inj_count = 0;
+    return 0;
+}
+
+extern "C++" {
+namespace {
+
+// End points of the sub-intervals of system step `step`: `ksub` uniform pieces, cut at the
+// control knots that fall inside the step.
+std::vector<double> lindblad_points(double T, int nsteps, int nc, int K, int ksub, int step) {
+    const double dt = T / nsteps;
+    const double t0 = step * dt, t1 = (step + 1) * dt;
+    std::vector<double> pts;
+    for (int q = 0; q < ksub; ++q) pts.push_back(t0 + (t1 - t0) * q / ksub);
+    pts.push_back(t1);
+    if (K > 0)
+        for (int i = 0; i < nc; ++i) {
+            const double kn = (i == nc - 1) ? T : i * (T / (nc - 1));
+            if (kn > t0 + 1e-12 * dt && kn < t1 - 1e-12 * dt) pts.push_back(kn);
+        }
+    std::sort(pts.begin(), pts.end());
+    pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+    return pts;
+}
+}  // extern "C++"
+
+// Sub-interval table of one sub-division count: uniform pieces per system step, cut at control
+// knots, with the interpolation weights of both ends and the CSR of their transpose.
+int build_lindblad_grid(qocx_ctx* ctx, int ksub, qocx_ctx::Lindblad::Grid& gr) {
+    auto& lb = ctx->lb;
+    const int K = lb.K, nc = lb.nc, nsteps = lb.nsteps;
+    std::vector<double> knots(K > 0 ? nc : 0);
+    for (int i = 0; i < (int)knots.size(); ++i) knots[i] = i * (lb.T / (nc - 1));
+    if (!knots.empty()) knots.back() = lb.T;
+    std::vector<qocx::SubStep> subs;
+    for (int step = 0; step < nsteps; ++step) {
+        const std::vector<double> pts = lindblad_points(lb.T, nsteps, nc, K, ksub, step);
+        for (size_t i = 0; i + 1 < pts.size(); ++i) {
+            qocx::SubStep ss;
+            ss.h = pts[i + 1] - pts[i];
+            // both ends interpolate on the knot interval that contains the sub-interval
+            int m1 = 0, m2 = 0;
+            if (!knots.empty()) {
+                const double mid = 0.5 * (pts[i] + pts[i + 1]);
+                if (mid <= knots[0]) { m1 = 0; m2 = 1; }
+                else if (mid >= knots[nc - 1]) { m1 = nc - 2; m2 = nc - 1; }
+                else {
+                    int idx = 0;
+                    while (!(mid <= knots[idx])) ++idx;
+                    m1 = idx - 1; m2 = idx;
+                }
+            }
+            auto end_weights = [&](double x, double& w1, double& w2) {
+                if (knots.empty()) { w1 = 1; w2 = 0; return; }
+                const double theta = (x - knots[m1]) / (knots[m2] - knots[m1]);
+                w1 = 1.0 - theta; w2 = theta;
+            };
+            ss.ia1 = ss.ib1 = m1; ss.ia2 = ss.ib2 = m2;
+            end_weights(pts[i], ss.wa1, ss.wa2);
+            end_weights(pts[i + 1], ss.wb1, ss.wb2);
+            ss.step = step;
+            ss.first_of_step = (i == 0) ? 1 : 0;
+            subs.push_back(ss);
+        }
+    }
+    const int nsub = (int)subs.size();
+    std::vector<std::vector<std::pair<int, double>>> rows(K > 0 ? nc : 0);
+    if (K > 0)
+        for (int q = 0; q < nsub; ++q) {
+            rows[subs[q].ia1].push_back({2 * q, subs[q].wa1});
+            rows[subs[q].ia2].push_back({2 * q, subs[q].wa2});
+            rows[subs[q].ib1].push_back({2 * q + 1, subs[q].wb1});
+            rows[subs[q].ib2].push_back({2 * q + 1, subs[q].wb2});
+        }
+    std::vector<int> row_ptr(1, 0), col;
+    std::vector<double> weight;
+    for (auto& r : rows) {
+        for (auto& e : r) { col.push_back(e.first); weight.push_back(e.second); }
+        row_ptr.push_back((int)col.size());
+    }
+    if (gr.substeps.upload(subs, ctx->stream) || gr.row_ptr.upload(row_ptr, ctx->stream) ||
+        gr.col.upload(col, ctx->stream) || gr.weight.upload(weight, ctx->stream))
+        return QOCX_ERR_HIP;
+    gr.nsub = nsub;
+    return 0;
+}
+
+}  // namespace
+
+int qocx_lindblad_stage_times(double evolution_time, int32_t system_eval_count,
+                              int32_t control_eval_count, int32_t control_count,
+                              int32_t subdivision, double* times_out, int64_t capacity,
+                              int64_t* count_out) {
+    if (system_eval_count < 2 || subdivision < 1 || !count_out ||
+        (control_count > 0 && control_eval_count < 2))
+        return fail(QOCX_ERR_ARG, "bad argument");
+    const int nsteps = system_eval_count - 1;
+    int64_t count = 0;
+    for (int step = 0; step < nsteps; ++step) {
+        const std::vector<double> pts = lindblad_points(evolution_time, nsteps, control_eval_count,
+                                                        control_count, subdivision, step);
+        for (size_t i = 0; i + 1 < pts.size(); ++i)
+            for (int st = 0; st < QOCX_RK_STAGES; ++st) {
+                if (times_out && count < capacity)
+                    times_out[count] = pts[i] + QOCX_RK_C[st] * (pts[i + 1] - pts[i]);
+                ++count;
+            }
+    }
+    *count_out = count;
+    return 0;
+}
+
+extern "C++" {
+namespace {
+
+// ---- qocx_eval_lindblad in three parts, shared with the resident driver (qocx_lindblad_*) ----------
+
+// max_i |controls[b][i][k]| -> umax[b][k], in knot order (a NaN is carried as lindblad_subdivisions
+// expects; control_maxima_kernel of qocx_optim.hip is the same scan on the device)
+void lindblad_control_maxima(const double* controls, int B, int nc, int K, double* umax) {
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < K; ++k) {
+            double um = 0;
+            for (int i = 0; i < nc; ++i) {
+                const double a = fabs(controls[((size_t)b * nc + i) * K + k]);
+                if (!(a <= um)) um = a;
+            }
+            umax[(size_t)b * K + k] = um;
+        }
+}
+
+// Each seed picks its own sub-division count from ITS controls (|| Liouvillian || * length <= 0.4
+// per sub-interval), so a seed's result never depends on its batch neighbours. umax: [B][K] control
+// maxima of the seeds; NULL with a fixed sub-division only (every seed then takes that one, unchecked).
+int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<int>& ksub_of) {
+    auto& lb = ctx->lb;
+    const int K = lb.K, nsteps = lb.nsteps;
+    ksub_of.assign(B, lb.fixed_ksub);
+    if (!umax) return lb.fixed_ksub > 0 ? 0 : fail(QOCX_ERR_STATE, "no control maxima");
+    for (int b = 0; b < B; ++b) {
+        // || Liouvillian ||_2 <= || control-free part ||_2 + sum_k |u_k| 2 ||G_k||_2; with a
+        // time-dependent Hamiltonian / lindblad_data (tables) the control-free part is bounded by
+        // the sum of its parts' bounds over the samples
+        double ctl = 0;
+        for (int k = 0; k < K; ++k) ctl += umax[(size_t)b * K + k] * lb.g_norm[k];
+        const double base = lb.fixed_ksub > 0 ? 2 * lb.h0_norm + 2 * lb.diss_norm : lb.l0_norm;
+        const double bound = base + 2 * ctl;
+        if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or operators");
+        const double pieces = ceil(bound * fabs(lb.dt) / 0.4);
+        if (pieces * nsteps > (double)(1 << 24))
+            return fail(QOCX_ERR_CAPACITY, "too many sub-intervals");
+        ksub_of[b] = std::max(1, (int)pieces);
+        if (lb.fixed_ksub > 0) {
+            // the time samples of the Hamiltonian exist for one grid only
+            if (ksub_of[b] > lb.fixed_ksub)
+                return fail(QOCX_ERR_CAPACITY,
+                            "controls need a finer sub-division than the Hamiltonian was sampled for");
+            ksub_of[b] = lb.fixed_ksub;
+        }
+    }
+    return 0;
+}
+
+// What an evaluation of these sub-division counts launches: seeds with equal counts are evaluated
+// together (`lb.order` lists the seeds group by group), the grid tables and the evaluation's
+// buffers for them.
+struct LindbladPlan {
+    std::map<int, std::vector<int>> groups;
+    size_t stage_budget = 0;  // double2 elements
+    bool two_sided_ok = false, two_sided_tiles = false;
+};
+
+int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of, LindbladPlan& plan) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = (int)ksub_of.size();
+    const size_t md = dump_elems(n);
+    auto& groups = plan.groups;
+    for (int b = 0; b < B; ++b) groups[ksub_of[b]].push_back(b);
+    if (lb.grids.size() > 64) lb.grids.clear();  // bounded cache of sub-interval tables
+    size_t ckpt_total = 0, gsub_total = 0;
+    lb.order.clear();
+    lb.last_subintervals = 0;
+    for (auto& kv : groups) {
+        auto it = lb.grids.find(kv.first);
+        if (it == lb.grids.end()) {
+            int rc = build_lindblad_grid(ctx, kv.first, lb.grids[kv.first]);
+            if (rc) return rc;
+            it = lb.grids.find(kv.first);
+        }
+        ckpt_total += kv.second.size() * (size_t)it->second.nsub * S * md;
+        gsub_total += kv.second.size() * (size_t)it->second.nsub * 2 * std::max(K, 1);
+        lb.last_subintervals += (int64_t)kv.second.size() * it->second.nsub;
+        for (int b : kv.second) lb.order.push_back(b);
+    }
+    // The stage values of the forward pass are kept for the adjoint (12 x the checkpoints of the
+    // seeds in flight); a group of seeds that does not fit is launched in pieces that do, and
+    // only if a piece would fall below 256 seeds does the adjoint recompute the stages instead.
+    // Two-sided evaluation (LindbladArgs::phase): where it applies the adjoint's stage cotangents
+    // need a buffer like the forward's stage values, and gsub holds complex numbers
+    // (n > 16: the tile-per-wave kernel of qocx_lindblad4t.hip in its phases, constant tables only)
+    const bool two_sided_small = n <= 16 && lb.nops >= 1 && lb.multi_wave && !lb.global_scratch &&
+                                 lb.dbg_wave_mode != 1;
+    const bool two_sided_tiles = plan.two_sided_tiles = n > 16 && ctx->knob("lindblad_4t", 1) != 0 && lb.nops <= 4;
+    const bool two_sided_ok = plan.two_sided_ok = want_grad && lb.unit_ok && lb.inj_count == 0 &&
+                              (two_sided_small || two_sided_tiles) && lb.fixed_ksub == 0 &&
+                              (int)ctx->sweep_streams.size() >= 1 &&
+                              ctx->knob("lindblad_two_sided", 1) != 0;
+    if (two_sided_ok)
+        if (lb.lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
+    size_t& stage_budget = plan.stage_budget;
+    if (want_grad) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        stage_budget = (size_t)(0.45 * (double)(free_b + (lb.ystages.count + lb.kbstages.count) *
+                                                              sizeof(double2))) /
+                       sizeof(double2);
+        if (two_sided_ok) stage_budget /= 2;  // kbar_i beside Y_i
+        size_t want = 0;
+        for (auto& kv : groups) {
+            const size_t per_seed = (size_t)lb.grids[kv.first].nsub * S * md * 12;
+            const size_t fit = lb.dbg_stage_seeds > 0 ? (size_t)lb.dbg_stage_seeds
+                                                      : std::max<size_t>(1, stage_budget / per_seed);
+            const size_t piece = std::min<size_t>(kv.second.size(), fit);
+            if (piece == kv.second.size() || piece >= (size_t)lb.dbg_min_piece)
+                want = std::max(want, piece * per_seed);
+        }
+        if (want > 0 && lb.ystages.ensure(want)) return QOCX_ERR_HIP;
+        if (want > 0 && two_sided_ok && lb.kbstages.ensure(want)) return QOCX_ERR_HIP;
+    }
+    if (lb.global_scratch &&
+        lb.scratch.ensure((size_t)B * qocx::lindblad_scratch_elems(n, S)))
+        return QOCX_ERR_HIP;
+    const size_t csz = (size_t)nc * K;
+    if (lb.controls.ensure((size_t)B * std::max<size_t>(csz, 1)) || lb.cost_out.ensure(B) ||
+        lb.grads.ensure((size_t)B * std::max<size_t>(csz, 1)) || lb.gsub.ensure(gsub_total) ||
+        lb.checkpoints.ensure(ckpt_total) || lb.final_out.ensure((size_t)B * S * md))
+        return QOCX_ERR_HIP;
+    if (ctx->keep_step_states)
+        if (lb.step_densities.ensure((size_t)B * (nsteps + 1) * S * md)) return QOCX_ERR_HIP;
+    return 0;
+}
+
+// The launches group by group, piece by piece: results in lb.cost_out / grads / final_out in group
+// order. The controls are in lb.controls, in group order, on ctx->stream before this.
+int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& plan) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = (int)lb.order.size();
+    const size_t md = dump_elems(n), csz = (size_t)nc * K;
+    const size_t stage_budget = plan.stage_budget;
+    const bool two_sided_ok = plan.two_sided_ok;
+    const bool two_sided_tiles = plan.two_sided_tiles;
+    if (lb.inj_count > 0) {
+        if (lb.inj_batch != B)
+            return fail(QOCX_ERR_STATE, "density cotangents were set for a different batch size");
+        std::vector<int> index(nsteps + 1, -1);
+        for (int c = 0; c < lb.inj_count; ++c) index[lb.inj_steps[c]] = c;
+        const size_t per_seed = (size_t)lb.inj_count * S;
+        std::vector<double2> dumps((size_t)B * per_seed * md);
+        for (int pos = 0; pos < B; ++pos)
+            for (size_t v = 0; v < per_seed; ++v) {
+                cmat m(lb.inj_host.begin() + (((size_t)lb.order[pos] * per_seed + v) * n * n * 2),
+                       lb.inj_host.begin() + (((size_t)lb.order[pos] * per_seed + v + 1) * n * n * 2));
+                c_dump(m, n, dumps.data() + ((size_t)pos * per_seed + v) * md);
+            }
+        if (lb.inj_index.upload(index, ctx->stream) || lb.inj_bars.upload(dumps, ctx->stream))
+            return QOCX_ERR_HIP;
+    }
+    size_t pos0 = 0, ckpt_off = 0, gsub_off = 0;
+    for (auto& kv : plan.groups) {
+        const auto& gr = lb.grids[kv.first];
+        const int Bg = (int)kv.second.size(), nsub = gr.nsub;
+        const size_t per_seed_stage = (size_t)nsub * S * md * 12;
+        int piece = Bg;
+        bool keep_stages = false;
+        if (want_grad) {
+            const size_t fit = lb.dbg_stage_seeds > 0
+                                   ? (size_t)lb.dbg_stage_seeds
+                                   : std::max<size_t>(1, stage_budget / per_seed_stage);
+            if (fit >= (size_t)Bg) { keep_stages = true; }
+            else if (fit >= (size_t)lb.dbg_min_piece) { keep_stages = true; piece = (int)fit; }
+        }
+        // Several waves per seed (one seed per CU) whenever the kernel is built for this problem;
+        // batches beyond the CU count go in rounds of one seed per CU. (Round 1 switched to one wave
+        // per seed, two seeds per CU, beyond 256 seeds; measured on configs[3] at 300 / 512 / 768 /
+        // 1024 seeds: 73.7 / 80.7 / 126.6 / 123.7 ms against 74.4 / 76.6 / 82.7 / 104.8 ms in rounds.)
+        bool multi = lb.multi_wave != 0;
+        if (lb.dbg_wave_mode == 1) multi = false;
+        if (multi && lb.dbg_wave_mode != 2) piece = std::min(piece, ctx->cu_count);
+        for (int p0 = 0; p0 < Bg; p0 += piece) {
+            const int Bp = std::min(piece, Bg - p0);
+            qocx::LindbladArgs la;
+            la.controls = lb.controls.p + pos0 * csz; la.substeps = gr.substeps.p;
+            la.a0l_cimg = lb.a0l.p; la.a0r_cimg = lb.a0r.p; la.a0ld_cimg = lb.a0ld.p; la.a0rd_cimg = lb.a0rd.p;
+            la.gp_cimg = lb.gp.p; la.gpd_cimg = lb.gpd.p; la.gpt_cimg = lb.gpt.p; la.op_cimg = lb.ops.p;
+            la.gammas = lb.gammas.p; la.rho0_cimg = lb.rho0.p;
+            la.a0_tab = lb.fixed_ksub > 0 ? lb.a0_tab.p : nullptr;
+            la.gp_tab = (lb.fixed_ksub > 0 && lb.gp_tab.p) ? lb.gp_tab.p : nullptr;
+            la.op_tab = (lb.fixed_ksub > 0 && lb.op_tab.p) ? lb.op_tab.p : nullptr;
+            la.gamma_tab = la.op_tab ? lb.gamma_tab.p : nullptr;
+            la.n = n; la.S = S; la.K = K; la.nc = nc; la.nops = (multi && lb.pad_op) ? 2 : lb.nops; la.nsub = nsub;
+            la.nsteps = nsteps;
+            la.cost_eval_step = lb.ces; la.want_grad = want_grad; la.has_step_costs = lb.has_step_costs;
+            la.cost_count = lb.cost_count; la.costs = lb.costs.p; la.cost_matrices = lb.cost_matrices.p;
+            la.cost_counts = lb.cost_counts.p;
+            la.checkpoints = lb.checkpoints.p + ckpt_off; la.gsub = lb.gsub.p + gsub_off;
+            la.ystages = keep_stages ? lb.ystages.p : nullptr;  // reused piece after piece
+            la.scratch = lb.global_scratch ? lb.scratch.p : nullptr;  // likewise
+            // several waves per seed shorten a seed's serial chain by ~1.4x but hold one seed
+            // per CU instead of two: worth it while the batch leaves CUs idle
+            la.multi_wave = multi ? 1 : 0;
+            la.cache_gen = (la.multi_wave && lb.cache_gen) ? 1 : 0;
+            la.cost_out = lb.cost_out.p + pos0;
+            la.final_out = lb.final_out.p + pos0 * S * md;
+            la.step_densities = ctx->keep_step_states
+                                    ? lb.step_densities.p + pos0 * (nsteps + 1) * S * md : nullptr;
+            la.tile4 = ctx->knob("lindblad_4t", 1) != 0 ? 1 : 0;
+            la.hermitian = (lb.hermitian && lb.inj_count == 0 && ctx->knob("lindblad_hermitian", 1) != 0) ? 1 : 0;
+            la.stamps = nullptr;
+            if (ctx->knob("lindblad_stamps", 0)) {
+                // ([B] sets of the forward pass / classic launch, then [B] of the unit adjoint)
+                if (ctx->stamps.ensure((size_t)B * 96)) return QOCX_ERR_HIP;
+                HIP_TRY(hipMemsetAsync(ctx->stamps.p, 0, (size_t)B * 96 * sizeof(unsigned long long),
+                                       ctx->stream));
+                la.stamps = ctx->stamps.p + pos0 * 48;
+            }
+            la.inj_count = lb.inj_count;
+            la.inj_index = lb.inj_count > 0 ? lb.inj_index.p : nullptr;
+            la.inj_bars = lb.inj_count > 0 ? lb.inj_bars.p + pos0 * lb.inj_count * S * md : nullptr;
+            // Two-sided: forward pass and unit adjoint as two launches, then the combine kernel on
+            // the whole chip. While both launches find CUs of their own they run on two streams
+            // (2 Bp CUs busy instead of Bp); a bigger piece runs them one after the other - the
+            // same three kernels, so a seed's result does not depend on the batch it is part of.
+            bool two_sided = two_sided_ok && keep_stages && (multi || two_sided_tiles);
+            if (two_sided && n > 16) {
+                // above one tile only the tile-per-wave kernel knows the phases: ask IT whether it
+                // takes these launches (the one-wave form would run the whole evaluation twice)
+                qocx::LindbladArgs probe = la;
+                probe.phase = 1;
+                probe.kbstages = lb.kbstages.p;
+                if (!qocx::lindblad4t_supports(probe)) two_sided = false;
+            }
+            if (two_sided) {
+                const int side_limit = (int)ctx->knob("lindblad_side_limit", ctx->cu_count / 2);
+                hipStream_t side = Bp <= side_limit ? ctx->sweep_streams[0] : ctx->stream;
+                la.kbstages = lb.kbstages.p;
+                la.lam_scale = lb.lam_scale.p + pos0 * S;
+                // everything enqueued so far (uploads, earlier pieces that reuse the stage buffers)
+                if (side != ctx->stream) {
+                    HIP_TRY(hipEventRecord(ctx->ev_factored[0], ctx->stream));
+                    HIP_TRY(hipStreamWaitEvent(side, ctx->ev_factored[0], 0));
+                }
+                qocx::LindbladArgs fwd = la, adj = la;
+                fwd.phase = 1;
+                adj.phase = 2;
+                fwd.q2 = adj.q2 = ctx->knob("lindblad_q2", 1) != 0 ? 1 : 0;
+                fwd.chain = adj.chain = ctx->knob("lindblad_chain", 1) != 0 ? 1 : 0;
+                fwd.ops_real = adj.ops_real = (lb.ops_real && ctx->knob("lindblad_real_ops", 1) != 0) ? 1 : 0;
+                if (la.stamps != nullptr) adj.stamps = la.stamps + (size_t)B * 48;
+                time_begin(ctx, 5, ctx->stream);
+                qocx::launch_lindblad(fwd, Bp, ctx->stream);
+                time_end(ctx, ctx->stream);
+                time_begin(ctx, 5, side);
+                qocx::launch_lindblad(adj, Bp, side);
+                time_end(ctx, side);
+                if (side != ctx->stream) {
+                    HIP_TRY(hipEventRecord(ctx->ev_swept[0], side));
+                    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_swept[0], 0));
+                }
+                time_begin(ctx, 6, ctx->stream);
+                qocx::launch_lindblad_combine(la, Bp, ctx->stream);
+                time_end(ctx, ctx->stream);
+            } else {
+                time_begin(ctx, 5, ctx->stream);
+                qocx::launch_lindblad(la, Bp, ctx->stream);
+                time_end(ctx, ctx->stream);
+            }
+            if (want_grad) {
+                qocx::ScatterArgs sc;
+                sc.gstep = la.gsub; sc.row_ptr = gr.row_ptr.p; sc.col_step = gr.col.p;
+                sc.weight = gr.weight.p; sc.grads = lb.grads.p + pos0 * csz;
+                sc.B = Bp; sc.nc = nc; sc.K = K; sc.nsteps = 2 * nsub;
+
+                time_begin(ctx, 3, ctx->stream);
+                qocx::launch_scatter(sc, ctx->stream);
+                time_end(ctx, ctx->stream);
+            }
+            pos0 += Bp;
+            ckpt_off += (size_t)Bp * nsub * S * md;
+            gsub_off += (size_t)Bp * nsub * 2 * std::max(K, 1);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int32_t want_grad,
+                       double* cost_out, double* grad_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set");
+    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, B = batch;
+    const size_t md = dump_elems(n);
+    want_grad = (want_grad && K > 0) ? 1 : 0;
+    if (K > 0 && !controls) return fail(QOCX_ERR_ARG, "controls is NULL");
+    const bool trace_host = qocx::diag_getenv("QOCX_TRACE_HOST") != nullptr;
+    auto now_ms = [] {
+        timespec ts;
+        clock_gettime(CLOCK_MONOTONIC, &ts);
+        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+    };
+    const double t_enter = now_ms();
+    double t_alloc = 0, t_enq = 0, t_sync = 0;
+
+    std::vector<double> umax(std::max<size_t>(1, (size_t)B * K));
+    lindblad_control_maxima(controls, B, nc, K, umax.data());
+    std::vector<int> ksub_of;
+    LindbladPlan plan;
+    int rc = lindblad_subdivisions(ctx, B, umax.data(), ksub_of);
+    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
+    if (rc) return rc;
+    const size_t csz = (size_t)nc * K;
+    if (K > 0) {
+        // gathered group by group into the pinned staging buffer (a pageable source of 2 MB costs
+        // the copy 10-25 ms of page pinning per call at 256 seeds; from pinned memory it is a DMA)
+        const size_t total = (size_t)B * csz;
+        if (ctx->pin_controls_cap < total) {
+            if (ctx->pin_controls) (void)hipHostFree(ctx->pin_controls);
+            ctx->pin_controls = nullptr;
+            ctx->pin_controls_cap = 0;
+            HIP_TRY(hipHostMalloc((void**)&ctx->pin_controls, total * sizeof(double), hipHostMallocDefault));
+            ctx->pin_controls_cap = total;
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // nothing in flight still reads the staging buffer
+        for (int pos = 0; pos < B; ++pos)
+            memcpy(ctx->pin_controls + (size_t)pos * csz, controls + (size_t)lb.order[pos] * csz,
+                   csz * sizeof(double));
+        HIP_TRY(hipMemcpyAsync(lb.controls.p, ctx->pin_controls, total * sizeof(double),
+                               hipMemcpyHostToDevice, ctx->stream));
+    }
+    t_alloc = now_ms();
+    rc = lindblad_launch_groups(ctx, want_grad, plan);
+    if (rc) return rc;
+    t_enq = now_ms();
+    std::vector<double2> fin(final_out ? (size_t)B * S * md : 0);
+    std::vector<double> cst(B), grd(want_grad && grad_out ? (size_t)B * csz : 0);
+    HIP_TRY(hipMemcpyAsync(cst.data(), lb.cost_out.p, (size_t)B * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    if (!grd.empty())
+        HIP_TRY(hipMemcpyAsync(grd.data(), lb.grads.p, grd.size() * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    if (final_out)
+        HIP_TRY(hipMemcpyAsync(fin.data(), lb.final_out.p, fin.size() * sizeof(double2),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    t_sync = now_ms();
+    time_collect(ctx);
+    if (trace_host)
+        fprintf(stderr, "qocx_eval_lindblad B=%d: set-up %.2f ms, enqueue %.2f ms, wait %.2f ms\n", B,
+                t_alloc - t_enter, t_enq - t_alloc, t_sync - t_enq);
+    for (int pos = 0; pos < B; ++pos) {
+        const int b = lb.order[pos];
+        if (cost_out) cost_out[b] = cst[pos];
+        if (!grd.empty())
+            memcpy(grad_out + (size_t)b * csz, grd.data() + (size_t)pos * csz, csz * sizeof(double));
+        if (final_out)
+            for (int s = 0; s < S; ++s)
+                from_c_dump(fin.data() + ((size_t)pos * S + s) * md, n,
+                            final_out + ((size_t)b * S + s) * n * n * 2);
+    }
+    lb.B = B;
+    lb.have_results = true;
+    lb.have_steps = ctx->keep_step_states != 0;
+    return 0;
+}
+
+int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, const int32_t* steps,
+                                const double* bars) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set");
+    if (count <= 0) {
+        lb.inj_count = 0;
+        return 0;
+    }
+    if (batch < 1 || !steps || !bars) return fail(QOCX_ERR_ARG, "bad argument");
+    std::vector<bool> seen(lb.nsteps + 1, false);
+    for (int c = 0; c < count; ++c) {
+        if (steps[c] < 1 || steps[c] > lb.nsteps || seen[steps[c]])
+            return fail(QOCX_ERR_ARG, "cotangent steps must be distinct and in 1..N-1");
+        seen[steps[c]] = true;
+    }
+    lb.inj_steps.assign(steps, steps + count);
+    lb.inj_host.assign(bars, bars + (size_t)batch * count * lb.S * lb.n * lb.n * 2);
+    lb.inj_count = count;
+    lb.inj_batch = batch;
+    return 0;
+}
+
+int qocx_download_step_densities(qocx_ctx* ctx, double* densities_out) {
+    if (!ctx || !densities_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (!lb.have_results || !lb.have_steps)
+        return fail(QOCX_ERR_STATE, "step densities were not kept (qocx_set_keep_step_states)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t per_seed = (size_t)(lb.nsteps + 1) * lb.S;
+    const size_t md = dump_elems(lb.n);
+    std::vector<double2> tmp((size_t)lb.B * per_seed * md);
+    HIP_TRY(hipMemcpy(tmp.data(), lb.step_densities.p, tmp.size() * sizeof(double2),
+                      hipMemcpyDeviceToHost));
+    for (int pos = 0; pos < lb.B; ++pos)
+        for (size_t v = 0; v < per_seed; ++v)
+            from_c_dump(tmp.data() + ((size_t)pos * per_seed + v) * md, lb.n,
+                        densities_out + ((size_t)lb.order[pos] * per_seed + v) * lb.n * lb.n * 2);
+    return 0;
+}
+
+// ---- the Lindblad multi-start driver: resident controls, results and optimizer states ------------
+
+int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
+    if (!ctx || !controls) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.K < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_upload_controls needs a Lindblad problem with controls");
+    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    const size_t csz = (size_t)lb.nc * lb.K;
+    if (csz > 65535u * 256u) return fail(QOCX_ERR_ARG, "control arrays too large for the driver kernels' grids");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (lb.res_controls.ensure((size_t)batch * csz)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(lb.res_controls.p, controls, (size_t)batch * csz * sizeof(double),
+                           hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // controls is the caller's memory
+    // the host has these controls: their maxima cost nothing here and spare eval_resident a round trip
+    lb.umax_host.assign((size_t)batch * lb.K, 0.0);
+    lindblad_control_maxima(controls, batch, lb.nc, lb.K, lb.umax_host.data());
+    lb.umax_valid = true;
+    lb.res_B = batch;
+    lb.res_have_results = false;
+    return 0;
+}
+
+int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "no resident Lindblad controls (qocx_lindblad_upload_controls)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, K = lb.K, S = lb.S;
+    const size_t csz = (size_t)lb.nc * K, md = dump_elems(lb.n);
+    want_grad = want_grad ? 1 : 0;
+    lb.res_have_results = false;
+    // the sub-division decision needs the control maxima on the host, except on a fixed grid
+    if (lb.fixed_ksub == 0 && !lb.umax_valid) {
+        if (lb.umax.ensure((size_t)B * K)) return QOCX_ERR_HIP;
+        lb.umax_host.resize((size_t)B * K);
+        qocx::launch_control_maxima(lb.res_controls.p, B, lb.nc, K, lb.umax.p, ctx->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(lb.umax_host.data(), lb.umax.p, (size_t)B * K * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        lb.umax_valid = true;
+    }
+    std::vector<int> ksub_of;
+    LindbladPlan plan;
+    int rc = lindblad_subdivisions(ctx, B, lb.fixed_ksub == 0 ? lb.umax_host.data() : nullptr, ksub_of);
+    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
+    if (rc) return rc;
+    if (lb.res_cost.ensure(B) || lb.res_grads.ensure((size_t)B * csz) ||
+        lb.res_final.ensure((size_t)B * S * md) || lb.order_dev.upload(lb.order, ctx->stream))
+        return QOCX_ERR_HIP;
+    // seed order -> group order: the device-side form of qocx_eval_lindblad's staging copy
+    qocx::launch_gather_seeds(lb.res_controls.p, lb.controls.p, csz, lb.order_dev.p, B, ctx->stream);
+    rc = lindblad_launch_groups(ctx, want_grad, plan);
+    if (rc) return rc;
+    qocx::launch_scatter_seeds(lb.cost_out.p, lb.res_cost.p, want_grad ? lb.grads.p : nullptr,
+                               lb.res_grads.p, csz, lb.final_out.p, lb.res_final.p, (size_t)S * md,
+                               lb.order_dev.p, B, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    if (lb.control_costs.count > 0) {  // the costs of the controls, on the seeds' resident controls
+        ControlCosts& cc = lb.control_costs;
+        if (int rc2 = run_control_costs(ctx, cc, B, lb.nc, K, lb.res_controls.p, want_grad != 0)) return rc2;
+        qocx::launch_add_control_costs(lb.res_cost.p, cc.cost.p, want_grad ? lb.res_grads.p : nullptr, cc.grad.p,
+                                       B, csz, ctx->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (ctx->timing) {  // (the events of the launches are read once they have run)
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        time_collect(ctx);
+    }
+    lb.B = B;
+    lb.have_results = true;
+    lb.have_steps = ctx->keep_step_states != 0;
+    lb.res_have_results = true;
+    lb.res_have_grads = want_grad != 0;
+    return 0;
+}
+
+int qocx_lindblad_download_results(qocx_ctx* ctx, double* cost_out, double* grad_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.res_have_results) return fail(QOCX_ERR_STATE, "no resident Lindblad evaluation results");
+    if (grad_out && !lb.res_have_grads) return fail(QOCX_ERR_STATE, "the last evaluation had no gradients");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, S = lb.S, n = lb.n;
+    const size_t csz = (size_t)lb.nc * lb.K, md = dump_elems(n);
+    if (cost_out)
+        HIP_TRY(hipMemcpyAsync(cost_out, lb.res_cost.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (grad_out)
+        HIP_TRY(hipMemcpyAsync(grad_out, lb.res_grads.p, (size_t)B * csz * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double2> fin(final_out ? (size_t)B * S * md : 0);
+    if (final_out)
+        HIP_TRY(hipMemcpyAsync(fin.data(), lb.res_final.p, fin.size() * sizeof(double2), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (final_out)
+        for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
+    return 0;
+}
+
+int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out) {
+    if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    return qocx_lindblad_download_results(ctx, cost_out, nullptr, nullptr);
+}
+
+}  // extern "C"

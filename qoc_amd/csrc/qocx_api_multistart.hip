@@ -1,0 +1,562 @@
+// qocx_api_multistart.hip - the multi-start GRAPE driver of the C ABI (include/qocx.h): one
+// device-resident optimizer driver for both paths (qocx_opt_* / qocx_lindblad_opt_*), the costs of the
+// controls alone (qocx_set_control_costs) and the host-side helpers of the driver.
+#include <thread>
+
+#include "qocx_host.h"
+
+// ---- host-side helpers of the multi-start GRAPE driver (include/qocx.h) ---------------------------
+namespace {
+template <class F>
+void host_parallel_rows(int64_t count, F f) {
+    const unsigned hw = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
+    const int64_t nthreads = std::max<int64_t>(1, std::min<int64_t>((int64_t)hw, count / 8));
+    if (nthreads <= 1) {
+        f(0, count);
+        return;
+    }
+    std::vector<std::thread> pool;
+    const int64_t per = (count + nthreads - 1) / nthreads;
+    for (int64_t t = 1; t < nthreads; ++t) {
+        const int64_t lo = t * per, hi = std::min(count, lo + per);
+        if (lo < hi) pool.emplace_back([=] { f(lo, hi); });
+    }
+    f(0, std::min(count, per));  // the calling thread takes the first share
+    for (auto& th : pool) th.join();
+}
+
+// One row of Adam.update. Every product and sum is rounded on its own, as NumPy's array
+// operations are (no contraction into fused multiply-adds); division and square root are the
+// IEEE ones in scalar and in vector form alike, so the AVX2 clone gives the same bits.
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+__attribute__((target_clones("avx2", "default")))
+#endif
+void adam_row(double* __restrict x, const double* __restrict g, double* __restrict m,
+              double* __restrict v, int64_t p, double learning_rate, double beta_1, double beta_2,
+              double one_m_b1, double one_m_b2, double epsilon, double corr_1, double corr_2,
+              int apply_clip, double clip) {
+#pragma clang fp contract(off)
+    for (int64_t i = 0; i < p; ++i) {
+        double gi = g[i];
+        if (apply_clip) gi = gi < -clip ? -clip : (gi > clip ? clip : gi);
+        const double a = beta_1 * m[i], b = one_m_b1 * gi;
+        const double mi = a + b;
+        const double sq = gi * gi;
+        const double c = beta_2 * v[i], d = one_m_b2 * sq;
+        const double vi = c + d;
+        m[i] = mi;
+        v[i] = vi;
+        const double mh = mi / corr_1, vh = vi / corr_2;
+        const double den = sqrt(vh) + epsilon;
+        const double q = mh / den;
+        const double s = learning_rate * q;
+        x[i] = x[i] - s;
+    }
+}
+}  // namespace
+
+namespace qocx::host {
+
+// ---- costs of the controls alone (qocx_set_control_costs) -----------------------------------------
+
+// cc.cost [B] and, if want_grad, cc.grad [B][nc][Kr] of the control sets `controls` on the device
+int run_control_costs(qocx_ctx* ctx, ControlCosts& cc, int B, int nc, int Kr, const double* controls,
+                      bool want_grad) {
+    if (cc.Kr != Kr || cc.nc != nc)
+        return fail(QOCX_ERR_STATE, "the control costs were set for another control layout "
+                                    "(qocx_set_control_costs after qocx_set_ensemble)");
+    const size_t total = (size_t)B * nc * Kr;
+    if ((size_t)nc * Kr > 0x7fffffffu) return fail(QOCX_ERR_ARG, "control arrays too large for the control-cost kernels");
+    if (cc.cost.ensure((size_t)B) || (want_grad && cc.grad.ensure(total)) ||
+        (cc.variation && (cc.work0.ensure(total) || cc.work1.ensure(total))))
+        return QOCX_ERR_HIP;
+    qocx::CtrlCostArgs a;
+    a.controls = controls; a.cost = cc.cost.p; a.grad = want_grad ? cc.grad.p : nullptr;
+    a.work0 = cc.work0.p; a.work1 = cc.work1.p;
+    a.descs = cc.descs.p; a.count = cc.elementwise;
+    a.B = B; a.nc = nc; a.Kr = Kr; a.cplx = cc.cplx;
+    qocx::launch_control_costs(a, ctx->stream);
+    int pmax = 0;  // (one allocation for all bandwidth costs: none while a kernel is in flight)
+    for (const auto& bw : cc.bandwidth) pmax = std::max(pmax, bw.pmax);
+    if (pmax > 0) {
+        if (cc.spectrum.ensure((size_t)B * Kr * pmax) || (want_grad && cc.ybar.ensure((size_t)B * cc.K * pmax)))
+            return QOCX_ERR_HIP;
+        if ((size_t)B * (1 + cc.cplx) / 8 + 1 > 65535u)
+            return fail(QOCX_ERR_ARG, "batch too large for the bandwidth kernels' grids");
+    }
+    for (const auto& bw : cc.bandwidth) {
+        qocx::BandwidthArgs w;
+        w.controls = controls; w.twiddle = cc.twiddle.p;
+        w.bins = cc.ints.p + bw.bins; w.bin_ptr = cc.ints.p + bw.bin_ptr;
+        w.spectrum = cc.spectrum.p; w.ybar = cc.ybar.p;
+        w.cost = cc.cost.p; w.grad = want_grad ? cc.grad.p : nullptr;
+        w.multiplier = bw.multiplier;
+        w.B = B; w.nc = nc; w.Kr = Kr; w.K = cc.K; w.cplx = cc.cplx; w.pmax = bw.pmax;
+        qocx::launch_bandwidth_cost(w, ctx->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace qocx::host
+
+// ---- the multi-start driver: resident optimizer states of the seeds of one path -------------------
+namespace {
+
+// What the driver needs of a path: its seeds' resident controls and results. Built by value from
+// the path's own state at every call (an evaluation may have moved the buffers since).
+struct SeedView {
+    int seeds, channels, nc;  // seeds; control channels per seed; control knots
+    double* controls;         // [seeds][nc][channels]
+    double* grads;            // [seeds][nc][channels]
+    double2* finals;          // [seeds][final_elems]
+    size_t final_elems;       // elements of final state per seed
+    size_t per_seed() const { return (size_t)nc * channels; }
+    size_t total() const { return (size_t)seeds * nc * channels; }
+};
+
+// (ensemble: a seed's K_r channels, and the final states of its M items)
+SeedView schroedinger_seeds(qocx_ctx* ctx) {
+    const size_t items = ctx->ens_M > 0 ? (size_t)ctx->ens_M : 1;
+    return SeedView{seed_count(ctx), seed_channels(ctx), ctx->nc, seed_controls(ctx), seed_grads(ctx),
+                    ctx->final_out.p, items * ctx->S * ctx->np};
+}
+
+SeedView lindblad_seeds(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    return SeedView{lb.res_B, lb.K, lb.nc, lb.res_controls.p, lb.res_grads.p, lb.res_final.p,
+                    (size_t)lb.S * dump_elems(lb.n)};
+}
+
+// the seeds' optimizer states, zeroed; complex controls: the parameters start as the seeds' controls
+int multistart_begin(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, int batch, bool complex_controls) {
+    const size_t total = v.total();
+    if (ms.opt_m.ensure(total) || ms.opt_v.ensure(total) || ms.opt_best_controls.ensure(total) ||
+        ms.opt_best_final.ensure((size_t)v.seeds * v.final_elems) ||
+        ms.opt_flags.ensure(2 * (size_t)v.seeds) || ms.opt_max_norms.ensure((size_t)v.channels))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipMemsetAsync(ms.opt_m.p, 0, total * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.opt_v.p, 0, total * sizeof(double), ctx->stream));
+    ms.batch = batch;
+    ms.complex_controls = false;
+    if (!complex_controls) return 0;
+    if (v.channels % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
+    if (ms.opt_params.ensure(total)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(ms.opt_params.p, v.controls, total * sizeof(double), hipMemcpyDeviceToDevice,
+                           ctx->stream));
+    ms.complex_controls = true;
+    return 0;
+}
+
+// max_norms to the device and the clip of the seeds' controls, enqueued: the caller synchronises
+// (max_norms is its caller's memory). Complex controls: max_norms [channels / 2] bound the moduli.
+int multistart_clip(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const double* max_norms) {
+    const int Kn = ms.complex_controls ? v.channels / 2 : v.channels;
+    HIP_TRY(hipMemcpyAsync(ms.opt_max_norms.p, max_norms, Kn * sizeof(double), hipMemcpyHostToDevice,
+                           ctx->stream));
+    if (ms.complex_controls)
+        qocx::launch_clip_complex(ms.opt_params.p, v.controls, v.total() / 2, Kn, ms.opt_max_norms.p,
+                                  ctx->stream);
+    else
+        qocx::launch_clip_controls(v.controls, v.total(), v.channels, ms.opt_max_norms.p, ctx->stream);
+    return 0;
+}
+
+// the update rule of one optimizer step (Adam.update / SGD.update of the host loop)
+struct StepRule {
+    int32_t kind;  // 0 SGD, 1 Adam
+    double learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2;
+    int32_t apply_clip_grads;
+    double clip_grads;
+};
+
+// keeps the controls and final states of the improved seeds, then steps the seeds flagged in `update`
+int multistart_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const StepRule& rule,
+                    const uint8_t* improved, const uint8_t* update) {
+    const int B = v.seeds;
+    HIP_TRY(hipMemcpyAsync(ms.opt_flags.p, improved, B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ms.opt_flags.p + B, update, B, hipMemcpyHostToDevice, ctx->stream));
+    qocx::launch_keep_best(v.controls, ms.opt_best_controls.p, v.per_seed(), v.finals, ms.opt_best_final.p,
+                           v.final_elems, ms.opt_flags.p, B, ctx->stream);
+    qocx::OptimArgs a;
+    a.kind = rule.kind;
+    a.params = ms.complex_controls ? ms.opt_params.p : v.controls; a.grads = v.grads;
+    a.moment = ms.opt_m.p; a.square_moment = ms.opt_v.p;
+    a.update = ms.opt_flags.p + B;
+    a.per_seed = v.per_seed();
+    a.learning_rate = rule.learning_rate; a.beta_1 = rule.beta_1; a.beta_2 = rule.beta_2;
+    a.one_m_b1 = 1 - rule.beta_1; a.one_m_b2 = 1 - rule.beta_2;
+    a.epsilon = rule.epsilon; a.corr_1 = rule.corr_1; a.corr_2 = rule.corr_2;
+    a.clip = rule.clip_grads; a.apply_clip = rule.apply_clip_grads ? 1 : 0;
+    qocx::launch_optimizer_update(a, B, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the flag arrays are the caller's memory
+    return 0;
+}
+
+// the best controls as they are and the best final states in the device's layout (`fin`, where wanted)
+int multistart_download_best(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, double* controls_out,
+                             std::vector<double2>* fin) {
+    if (controls_out)
+        HIP_TRY(hipMemcpyAsync(controls_out, ms.opt_best_controls.p, v.total() * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    if (fin) {
+        fin->resize((size_t)v.seeds * v.final_elems);
+        HIP_TRY(hipMemcpyAsync(fin->data(), ms.opt_best_final.p, fin->size() * sizeof(double2),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int schroedinger_opt_begin(qocx_ctx* ctx, bool complex_controls) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->has_problem || ctx->B < 1 || ctx->K < 1 || ctx->explicit_mode)
+        return fail(QOCX_ERR_STATE, "qocx_opt_begin needs uploaded controls of a structured problem");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (the seeds' optimizer states; the best final states of every item)
+    return multistart_begin(ctx, ctx->ms, schroedinger_seeds(ctx), ctx->B, complex_controls);
+}
+
+int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin needs resident Lindblad controls");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return multistart_begin(ctx, lb.ms, lindblad_seeds(ctx), lb.res_B, complex_controls);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the Schroedinger path: the seeds of qocx_upload_controls ---------------------------------------
+
+int qocx_opt_begin(qocx_ctx* ctx) { return schroedinger_opt_begin(ctx, false); }
+
+int qocx_opt_begin_complex(qocx_ctx* ctx) { return schroedinger_opt_begin(ctx, true); }
+
+int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
+    if (!ctx || !max_norms) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // after the clip |u_k| <= max_norms[k]: the squaring capacity follows from that bound
+    // (ensemble: |s_mk u_k| <= max_norms[k] max_m |s_mk| on the K_r seed channels, |delta_mj| beyond)
+    const bool ens = ctx->ens_M > 0;
+    const SeedView v = schroedinger_seeds(ctx);
+    const int Ks = v.channels;
+    // (complex controls: max_norms [Ks / 2] bound the moduli, hence both channels of a control)
+    std::vector<double> channel_norms((size_t)Ks);
+    for (int k = 0; k < Ks; ++k) channel_norms[k] = max_norms[ctx->ms.complex_controls ? k / 2 : k];
+    double bound = ctx->h0_norm_max;
+    for (int k = 0; k < Ks; ++k) {
+        if (!(channel_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
+        bound += (ens ? channel_norms[k] * ctx->ens_scale_max[k] : channel_norms[k]) * ctx->g_norm_max[k];
+    }
+    for (int j = 0; ens && j < ctx->ens_J; ++j) bound += ctx->ens_offset_max[j] * ctx->g_norm_max[Ks + j];
+    bound += quad_bound(ctx, channel_norms.data());  // (quadratic terms: ||Q_q||_1 max_norms_k max_norms_l)
+    bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
+    if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
+    const int sb = pade_scale_count(bound);
+    if (sb > 10)
+        return fail(QOCX_ERR_CAPACITY,
+                    "||dt H||_1 bound needs more than 2^10 squaring sub-steps per step; reduce dt");
+    ctx->sbound = std::max(ctx->sbound, sb);
+    ctx->norm_bound = std::max(ctx->norm_bound, bound);
+    ctx->norm_bound_mid = 1e300;  // (the controls move on the device from here on)
+    ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
+    // (the Lindblad path checks the second of these grid limits in qocx_lindblad_upload_controls and has
+    // no check of the first: to be revisited)
+    if ((v.total() + 255) / 256 > 0x7fffffffu || v.per_seed() > 65535u * 256u)
+        return fail(QOCX_ERR_ARG, "control arrays too large for the optimizer kernels' grids");
+    if (int rc = multistart_clip(ctx, ctx->ms, v, max_norms)) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
+    ctx->have_results = false;
+    ctx->ens_stale = ens;  // (the next evaluation expands the clipped seed controls)
+    return 0;
+}
+
+int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const uint8_t* update,
+                  double learning_rate, double beta_1, double beta_2, double epsilon, double corr_1,
+                  double corr_2, int32_t apply_clip_grads, double clip_grads) {
+    if (!ctx || !improved || !update) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (kind != 0 && kind != 1) return fail(QOCX_ERR_ARG, "kind must be 0 (SGD) or 1 (Adam)");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    if (!ctx->have_results || !ctx->have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
+    if (int rc = multistart_step(ctx, ctx->ms, schroedinger_seeds(ctx), rule, improved, update)) return rc;
+    ctx->have_results = false;  // the resident controls are no longer those of the last evaluation
+    ctx->ens_stale = ctx->ens_M > 0;
+    return 0;
+}
+
+int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<double2> fin;
+    if (int rc = multistart_download_best(ctx, ctx->ms, schroedinger_seeds(ctx), controls_out,
+                                          final_out ? &fin : nullptr))
+        return rc;
+    const int np = ctx->np, n = ctx->n;
+    if (final_out)
+        for (size_t v = 0; v < (size_t)ctx->B * ctx->S; ++v)
+            for (int i = 0; i < n; ++i) {
+                final_out[2 * (v * n + i)] = fin[v * np + i].x;
+                final_out[2 * (v * n + i) + 1] = fin[v * np + i].y;
+            }
+    return 0;
+}
+
+// ---- the Lindblad path: the seeds of qocx_lindblad_upload_controls ----------------------------------
+
+int qocx_lindblad_opt_begin(qocx_ctx* ctx) { return lindblad_opt_begin(ctx, false); }
+
+int qocx_lindblad_opt_begin_complex(qocx_ctx* ctx) { return lindblad_opt_begin(ctx, true); }
+
+int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
+    if (!ctx || !max_norms) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    const int Kn = lb.ms.complex_controls ? lb.K / 2 : lb.K;  // (complex controls: one modulus bound per control)
+    for (int k = 0; k < Kn; ++k)
+        if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, K = lb.K;
+    if (int rc = multistart_clip(ctx, lb.ms, lindblad_seeds(ctx), max_norms)) return rc;
+    // the maxima of the clipped controls decide the next evaluation's sub-divisions: they come back
+    // with the synchronisation the clip needs anyway (none on a fixed grid)
+    const bool maxima = lb.fixed_ksub == 0;
+    if (maxima) {
+        if (lb.umax.ensure((size_t)B * K)) return QOCX_ERR_HIP;
+        lb.umax_host.resize((size_t)B * K);
+        qocx::launch_control_maxima(lb.res_controls.p, B, lb.nc, K, lb.umax.p, ctx->stream);
+        HIP_TRY(hipMemcpyAsync(lb.umax_host.data(), lb.umax.p, (size_t)B * K * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
+    lb.umax_valid = maxima;
+    lb.res_have_results = false;
+    return 0;
+}
+
+int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const uint8_t* update,
+                           double learning_rate, double beta_1, double beta_2, double epsilon,
+                           double corr_1, double corr_2, int32_t apply_clip_grads, double clip_grads) {
+    if (!ctx || !improved || !update) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (kind != 0 && kind != 1) return fail(QOCX_ERR_ARG, "kind must be 0 (SGD) or 1 (Adam)");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    if (!lb.res_have_results || !lb.res_have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
+    if (int rc = multistart_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update)) return rc;
+    lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
+    lb.umax_valid = false;
+    return 0;
+}
+
+int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.res_B, S = lb.S, n = lb.n;
+    const size_t md = dump_elems(n);
+    std::vector<double2> fin;
+    if (int rc = multistart_download_best(ctx, lb.ms, lindblad_seeds(ctx), controls_out,
+                                          final_out ? &fin : nullptr))
+        return rc;
+    if (final_out)
+        for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
+    return 0;
+}
+
+// ---- costs of the controls alone; complex controls in the resident drivers -------------------------
+
+static ControlCosts* control_costs_of(qocx_ctx* ctx, int32_t path, int& nc, int& Kr) {
+    if (path == QOCX_PATH_SCHROEDINGER && ctx->has_problem) {
+        nc = ctx->nc;
+        Kr = ctx->ens_M > 0 ? ctx->ens_Kr : ctx->K;
+        return &ctx->control_costs;
+    }
+    if (path == QOCX_PATH_LINDBLAD && ctx->lb.has_problem) {
+        nc = ctx->lb.nc;
+        Kr = ctx->lb.K;
+        return &ctx->lb.control_costs;
+    }
+    return nullptr;
+}
+
+int qocx_set_control_costs(qocx_ctx* ctx, int32_t path, int32_t complex_controls, int32_t count,
+                           const qocx_control_cost_desc* descs) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (path != QOCX_PATH_SCHROEDINGER && path != QOCX_PATH_LINDBLAD) return fail(QOCX_ERR_ARG, "unknown path");
+    int nc = 0, Kr = 0;
+    ControlCosts* ccp = control_costs_of(ctx, path, nc, Kr);
+    if (!ccp) return fail(QOCX_ERR_STATE, "no problem set on this path");
+    ControlCosts& cc = *ccp;
+    cc.clear();
+    if (count <= 0) return 0;
+    if (!descs) return fail(QOCX_ERR_ARG, "descs is NULL");
+    const int cplx = complex_controls ? 1 : 0;
+    if (Kr < 1 || nc < 2) return fail(QOCX_ERR_ARG, "control costs need a problem with controls");
+    if (Kr > 128) return fail(QOCX_ERR_ARG, "control costs take up to 128 control channels");
+    if (cplx && Kr % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
+    const int K = Kr >> cplx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<double> arrays;
+    std::vector<int> ints;
+    std::vector<qocx::CtrlCostDev> dev;
+    std::vector<size_t> offsets;  // of max_norms | weights in `arrays`, per elementwise descriptor
+    bool variation = false;
+    for (int d = 0; d < count; ++d) {
+        const qocx_control_cost_desc& c = descs[d];
+        if (!std::isfinite(c.multiplier)) return fail(QOCX_ERR_ARG, "non-finite cost multiplier");
+        for (int k = 0; k < K; ++k)
+            if ((c.max_norms && !std::isfinite(c.max_norms[k])) || (c.weights && !std::isfinite(c.weights[k])))
+                return fail(QOCX_ERR_ARG, "non-finite max_norms / weights");
+        if (c.kind == QOCX_CONTROL_BANDWIDTH_MAX) {
+            if (!c.bins || !c.bin_ptr || c.bin_ptr[0] != 0) return fail(QOCX_ERR_ARG, "bandwidth cost without bins");
+            ControlCosts::Bandwidth bw;
+            bw.multiplier = c.multiplier;
+            bw.pmax = 0;
+            for (int k = 0; k < K; ++k) {
+                const int np = c.bin_ptr[k + 1] - c.bin_ptr[k];
+                if (np < 1) return fail(QOCX_ERR_ARG, "a control without penalised DFT bins (empty P_k)");
+                for (int i = c.bin_ptr[k]; i < c.bin_ptr[k + 1]; ++i)
+                    if (c.bins[i] < 0 || c.bins[i] >= nc || (i > c.bin_ptr[k] && c.bins[i] <= c.bins[i - 1]))
+                        return fail(QOCX_ERR_ARG, "DFT bins must be ascending and in 0..Nc-1");
+                bw.pmax = std::max(bw.pmax, np);
+            }
+            bw.bins = ints.size();
+            ints.insert(ints.end(), c.bins, c.bins + c.bin_ptr[K]);
+            bw.bin_ptr = ints.size();
+            ints.insert(ints.end(), c.bin_ptr, c.bin_ptr + K + 1);
+            cc.bandwidth.push_back(bw);
+            continue;
+        }
+        if (c.kind != QOCX_CONTROL_NORM && c.kind != QOCX_CONTROL_VARIATION && c.kind != QOCX_CONTROL_AREA) {
+            cc.clear();
+            return fail(QOCX_ERR_ARG, "unknown control cost kind");
+        }
+        if (c.kind == QOCX_CONTROL_VARIATION && (c.order < 1 || c.order >= nc)) {
+            cc.clear();
+            return fail(QOCX_ERR_ARG, "ControlVariation needs 1 <= order < control_eval_count");
+        }
+        if (c.kind == QOCX_CONTROL_AREA && !c.max_norms) {
+            cc.clear();
+            return fail(QOCX_ERR_ARG, "ControlArea needs max_norms");
+        }
+        variation = variation || c.kind == QOCX_CONTROL_VARIATION;
+        qocx::CtrlCostDev e;
+        e.kind = c.kind; e.order = c.order; e.multiplier = c.multiplier;
+        e.max_norms = e.weights = nullptr;
+        offsets.push_back(arrays.size());
+        for (int k = 0; k < K; ++k) arrays.push_back(c.max_norms ? c.max_norms[k] : 1.0);
+        for (int k = 0; k < K; ++k) arrays.push_back(c.weights ? c.weights[k] : 1.0);
+        dev.push_back(e);
+    }
+    if (cc.arrays.upload(arrays, ctx->stream) || cc.ints.upload(ints, ctx->stream)) {
+        cc.clear();
+        return QOCX_ERR_HIP;
+    }
+    for (size_t d = 0; d < dev.size(); ++d) {
+        dev[d].max_norms = cc.arrays.p + offsets[d];
+        dev[d].weights = cc.arrays.p + offsets[d] + K;
+    }
+    if (!cc.bandwidth.empty()) {  // exp(-2 pi i m / Nc), m = 0 .. Nc-1, rounded from extended precision
+        std::vector<double2> tw((size_t)nc);
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        for (int m = 0; m < nc; ++m) {
+            const long double th = two_pi * (long double)m / (long double)nc;
+            tw[m] = make_double2((double)cosl(th), (double)-sinl(th));
+        }
+        if (cc.twiddle.upload(tw, ctx->stream)) {
+            cc.clear();
+            return QOCX_ERR_HIP;
+        }
+    }
+    if (cc.descs.upload(dev, ctx->stream)) {
+        cc.clear();
+        return QOCX_ERR_HIP;
+    }
+    cc.count = count;
+    cc.cplx = cplx; cc.K = K; cc.Kr = Kr; cc.nc = nc;
+    cc.elementwise = (int)dev.size();
+    cc.variation = variation;
+    return 0;
+}
+
+int qocx_eval_control_costs(qocx_ctx* ctx, int32_t path, int32_t batch, const double* controls,
+                            double* cost_out, double* grad_out) {
+    if (!ctx || !controls || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    int nc = 0, Kr = 0;
+    ControlCosts* cc = control_costs_of(ctx, path, nc, Kr);
+    if (!cc || cc->count == 0) return fail(QOCX_ERR_STATE, "no control costs set on this path");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t total = (size_t)batch * nc * Kr;
+    if (cc->stage.ensure(total)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(cc->stage.p, controls, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = run_control_costs(ctx, *cc, batch, nc, Kr, cc->stage.p, grad_out != nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(cost_out, cc->cost.p, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_out)
+        HIP_TRY(hipMemcpyAsync(grad_out, cc->grad.p, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_host_clip_controls(double* controls, int64_t batch, int64_t nc, int32_t k,
+                            const double* max_norms) {
+    if (!controls || !max_norms || batch < 0 || nc < 0 || k < 0) return fail(QOCX_ERR_ARG, "bad argument");
+    host_parallel_rows(batch, [=](int64_t lo, int64_t hi) {
+        for (int64_t b = lo; b < hi; ++b) {
+            double* row = controls + (size_t)b * nc * k;
+            for (int64_t j = 0; j < nc; ++j)
+                for (int32_t c = 0; c < k; ++c) {
+                    const double v = row[j * k + c], mod = fabs(v);
+                    if (max_norms[c] < mod) row[j * k + c] = (v / mod) * max_norms[c];
+                }
+        }
+    });
+    return 0;
+}
+
+int qocx_host_optimizer_update(int32_t kind, double* params, const double* grads, double* moment,
+                               double* square_moment, int64_t p, const int64_t* rows,
+                               int64_t row_count, double learning_rate, double beta_1,
+                               double beta_2, double epsilon, double corr_1, double corr_2,
+                               int32_t apply_clip_grads, double clip_grads) {
+    if (!params || !grads || !rows || p < 0 || row_count < 0) return fail(QOCX_ERR_ARG, "bad argument");
+    if (kind != 0 && (!moment || !square_moment)) return fail(QOCX_ERR_ARG, "moments missing");
+    const double one_m_b1 = 1 - beta_1, one_m_b2 = 1 - beta_2;
+    host_parallel_rows(row_count, [=](int64_t lo, int64_t hi) {
+// every product and sum is rounded on its own, as NumPy's array operations are
+#pragma clang fp contract(off)
+        for (int64_t r = lo; r < hi; ++r) {
+            const size_t off = (size_t)rows[r] * (size_t)p;
+            double* x = params + off;
+            const double* g = grads + off;
+            if (kind == 0) {
+                for (int64_t i = 0; i < p; ++i) {
+                    const double s = learning_rate * g[i];
+                    x[i] = x[i] - s;
+                }
+                continue;
+            }
+            adam_row(x, g, moment + off, square_moment + off, p, learning_rate, beta_1, beta_2,
+                     one_m_b1, one_m_b2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads);
+        }
+    });
+    return 0;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // qocx_device.h - argument blocks shared by the kernels (qocx_kernels.hip) and the host side of
-// the C ABI (qocx_api.hip). Plain structs of device pointers and sizes.
+// the C ABI (qocx_api*.hip, qocx_host_resident.hip). Plain structs of device pointers and sizes.
 #ifndef QOCX_DEVICE_H
 #define QOCX_DEVICE_H
 

@@ -1,0 +1,330 @@
+// qocx_host.h - what the host translation units of the C ABI (include/qocx.h) share: the error
+// string, device buffers, the context and the helpers more than one of the files uses. Internal:
+// not installed with include/qocx.h. The host files hold no device code; the kernels and their
+// launch_* functions are declared in qocx_device.h.
+#ifndef QOCX_HOST_H
+#define QOCX_HOST_H
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/qocx.h"
+#include "qocx_device.h"
+#include "qocx_diag.h"
+
+namespace qocx::host {
+
+// records msg as the calling thread's last error (qocx_last_error) and returns code
+int fail(int code, const std::string& msg);
+
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return fail(QOCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// A device allocation and its owner: freed with the buffer's owner (the context, a ControlCosts, a
+// local), or early by release().
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t count = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    int ensure(size_t n) {
+        if (n <= count && p != nullptr) return 0;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        count = 0;
+        if (n == 0) return 0;
+        hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+        if (e != hipSuccess) {
+            return fail(QOCX_ERR_HIP, std::string("hipMalloc(") + std::to_string(n * sizeof(T)) +
+                                          " bytes): " + hipGetErrorString(e));
+        }
+        count = n;
+        return 0;
+    }
+    int upload(const std::vector<T>& v, hipStream_t st) {
+        int rc = ensure(v.size());
+        if (rc) return rc;
+        if (v.empty()) return 0;
+        hipError_t e = hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return fail(QOCX_ERR_HIP, hipGetErrorString(e));
+        e = hipStreamSynchronize(st);  // v may be a temporary
+        if (e != hipSuccess) return fail(QOCX_ERR_HIP, hipGetErrorString(e));
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        count = 0;
+    }
+};
+
+struct TimingRec {
+    int which;
+    hipEvent_t a, b;
+};
+
+// RCCL entry points, resolved lazily so that single-GPU use never loads librccl.
+struct Rccl {
+    void* lib = nullptr;
+    int (*GetUniqueId)(void*) = nullptr;
+    int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
+    int (*CommDestroy)(void*) = nullptr;
+    const char* (*GetErrorString)(int) = nullptr;
+};
+
+// The costs of the controls alone of one path (qocx_set_control_costs, qocx_ctrlcost.hip)
+struct ControlCosts {
+    int count = 0;        // 0: none set
+    int cplx = 0, K = 0;  // complex controls; controls (channels / 2 when complex)
+    int Kr = 0, nc = 0;   // the channels and knots they were set for
+    int elementwise = 0;  // descriptors of the kernel of NORM / VARIATION / AREA
+    bool variation = false;
+    struct Bandwidth {
+        double multiplier;
+        int pmax;
+        size_t bins, bin_ptr;  // offsets into `ints`
+    };
+    std::vector<Bandwidth> bandwidth;
+    DevBuf<qocx::CtrlCostDev> descs;
+    DevBuf<double> arrays;  // the per-control arrays of the descriptors
+    DevBuf<int> ints;       // bins and bin_ptr of the bandwidth costs
+    DevBuf<double2> twiddle;
+    // per evaluation
+    DevBuf<double> cost, grad, work0, work1, stage;
+    DevBuf<double2> spectrum, ybar;
+    void clear() {
+        count = 0;
+        bandwidth.clear();
+    }
+};
+
+// The device-resident state of one path's multi-start optimizer driver (qocx_opt_* /
+// qocx_lindblad_opt_*, qocx_api_multistart.hip)
+struct MultiStart {
+    DevBuf<double> opt_m, opt_v, opt_best_controls, opt_max_norms;
+    DevBuf<double2> opt_best_final;
+    DevBuf<unsigned char> opt_flags;  // [2][B]: improved | update
+    DevBuf<double> opt_params;        // complex controls: the optimizer's parameters - the seed controls
+                                      // are then the copy clipped by modulus that is evaluated
+    int batch = 0;                    // the path's batch the states were set up for (0: none)
+    bool complex_controls = false;    // qocx_opt_begin_complex / qocx_lindblad_opt_begin_complex
+};
+
+}  // namespace qocx::host
+
+// (the host files name the shared helpers as the single file they were cut from did)
+using namespace qocx::host;
+
+struct qocx_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    // ---- problem ----
+    bool has_problem = false;
+    int n = 0, nb = 0, np = 0, S = 0, K = 0, nc = 0, N = 0, nsteps = 0, ces = 1, nt = 1;
+    double T = 0, dt = 0;
+    int has_step_costs = 0, cost_count = 0;
+    double h0_norm_max = 0;
+    std::vector<double> g_norm_max;
+    DevBuf<double2> h0_cimg, g_cimg, h0_rimg, g_rimg, h0_timg, g_timg, psi0, cost_vectors;
+    DevBuf<qocx::StepInterp> interp;
+    DevBuf<qocx::DevCost> costs;
+    DevBuf<int> cost_counts, row_ptr, col_step;
+    DevBuf<double> weight;
+    // ---- evaluation state ----
+    int B = 0;
+    int sbound = 0;
+    int last_chunk = 0;         // seeds of the last memory chunk of the last evaluation (its step table is in s_arr)
+    double norm_bound = 1e300;  // host bound of ||step generator||_1 of the uploaded controls / generators
+    // M2, control knots at the system times (Nc = N): a bound of the step generators at their MIDPOINTS,
+    // where u is the mean of two knots - what the step table's per-step bound can reach at most; 1e300 when
+    // it does not apply. Decides only whether the two-wave K1a is launched beside the three-wave one.
+    double norm_bound_mid = 1e300;
+    size_t slot_cap = 0;
+    int chunk_user = 0;
+    int pipe_user = 0;
+    std::vector<hipStream_t> sweep_streams;
+    hipStream_t lu_stream = nullptr;       // K1b of a segment beside K1a of the next one (n > 32)
+    std::vector<hipEvent_t> ev_pq;         // K1a of segment i has finished
+    std::vector<hipEvent_t> ev_factored, ev_swept, ev_fwd;
+    bool unit_ok = false;          // the only cost is one separable final cost (qocx_sweep_common.h)
+    MultiStart ms;  // multi-start driver on the device (qocx_opt_*)
+    ControlCosts control_costs;  // qocx_set_control_costs(QOCX_PATH_SCHROEDINGER)
+    DevBuf<double2> lam_scale;     // unit adjoint: [B][S]
+    DevBuf<int> offs_x;            // unit adjoint: [chunk][nsteps + 1]
+    int keep_step_states = 0;
+    bool have_results = false, have_grads = false, have_step_states = false;
+    DevBuf<double> controls, cost_out, grads, gstep;
+    double* pin_controls = nullptr;  // pinned staging of the controls (qocx_upload_controls)
+    size_t pin_controls_cap = 0;
+    DevBuf<double2> final_out, step_states;
+    DevBuf<double2> q_img, lu_img, dinv, states, xs;
+    DevBuf<double2> qt_img;  // one control set (sweep_umode): the transposed propagator images
+    DevBuf<int> perm, iperm, s_arr, offs, status;
+    DevBuf<int> lu_fallbacks;  // [1] matrices that left the diagonal-pivot MFMA factorisation (qocx_lu_fallbacks)
+    DevBuf<int> lu_redo;  // 33 <= n <= 64: matrices the MFMA factorisation hands to the general one (LuArgs::redo)
+    // ---- Lindblad problem / evaluation state ----
+    // ---- Magnus M4/M6 ----
+    int nodes = 1;
+    int cu_count = 256;
+    int hermitian = 0;  // every h0[t], g[t][k] equals its conjugate transpose bit for bit
+    bool general_path = false;  // the evaluation runs on qocx_general.hip (n > 64, or S beyond the sweep's LDS)
+    DevBuf<double2> m_rm, mbar_rm, magnus_scratch, lam_buf;
+    // M4 with time-independent H0 / G_k as a linear problem in Ke effective controls (M4LinArgs)
+    int m4lin_Ke = 0;  // 0: not available for this problem
+    DevBuf<double2> ge_cimg, ge_rimg, ge_timg;
+    DevBuf<qocx::StepInterp> interp_id;
+    DevBuf<double> veff, gnode;
+    // H quadratic in the real controls (qocx_set_quadratic_terms, QuadArgs): the augmented images
+    // ge_* (G_k then Q_q) and veff / gnode are shared with M4 on a linear system, which needs
+    // magnus_policy M4 - the two never coexist
+    int quad_count = 0;                  // 0: no quadratic terms
+    std::vector<int> quad_pairs;         // [count][2]
+    std::vector<double> quad_norm;       // ||Q_q||_1
+    DevBuf<int> quad_pairs_dev;
+    int hermitian_linear = 0;            // `hermitian` of H0 / G_k alone (qocx_set_quadratic_terms folds in the Q_q)
+    // Hamiltonian ensemble (qocx_set_ensemble, EnsembleArgs): the last ens_J of the problem's K channels
+    // are fixed perturbation channels; controls, costs and gradients of the seeds live in ens_* and the
+    // evaluation buffers (controls, cost_out, grads, final_out) hold the B x M member items
+    int ens_M = 0;                       // 0: no ensemble
+    int ens_J = 0, ens_Kr = 0;           // fixed channels, seed channels (K = ens_Kr + ens_J)
+    int ens_B = 0;                       // seeds of the last upload (ctx->B = ens_B * ens_M)
+    bool ens_stale = false;              // ens_controls moved (qocx_opt_clip / _step) since the expansion
+    std::vector<double> ens_scales_h, ens_offsets_h;    // [M][Kr], [M][J]
+    std::vector<double> ens_scale_max, ens_offset_max;  // max_m |s_mk|, max_m |delta_mj|
+    DevBuf<double> ens_scales, ens_offsets, ens_weights;
+    DevBuf<double> ens_controls, ens_cost, ens_grads;   // [B][nc][Kr], [B], [B][nc][Kr]
+    DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
+    // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
+    bool explicit_mode = false;
+    int explicit_hermitian = 0;
+    DevBuf<double2> gen_rm, genbar_rm;  // [B][nsteps] row-major padded generators / cotangents
+    // ---- host-supplied state cotangents ----
+    int inj_count = 0, inj_batch = 0;
+    DevBuf<int> inj_index;
+    DevBuf<double2> inj_bars;
+    struct Lindblad {
+        bool has_problem = false, have_results = false, have_grads = false, have_steps = false;
+        int n = 0, S = 0, K = 0, nc = 0, N = 0, nsteps = 0, ces = 1, nops = 0;
+        double T = 0, dt = 0, h0_norm = 0, diss_norm = 0, l0_norm = 0;
+        std::vector<double> g_norm;
+        int has_step_costs = 0, cost_count = 0;
+        DevBuf<double2> a0l, a0r, a0ld, a0rd, gp, gpd, gpt, ops, rho0, cost_matrices;
+        DevBuf<double> gammas;
+        DevBuf<qocx::DevCost> costs;
+        DevBuf<int> cost_counts;
+        // sub-interval tables, by sub-division count
+        struct Grid {
+            int nsub = 0;
+            DevBuf<qocx::SubStep> substeps;
+            DevBuf<int> row_ptr, col;
+            DevBuf<double> weight;
+        };
+        std::map<int, Grid> grids;
+        // per evaluation
+        int B = 0;
+        std::vector<int> order;  // device position -> seed
+        // host-supplied density cotangents
+        int inj_count = 0, inj_batch = 0;
+        std::vector<int> inj_steps;
+        std::vector<double> inj_host;  // [B][count][S][n][n] complex
+        DevBuf<int> inj_index;
+        DevBuf<double2> inj_bars;
+        DevBuf<double> gsub, cost_out, grads, controls;
+        DevBuf<double2> checkpoints, final_out, step_densities, ystages, scratch;
+        DevBuf<double2> kbstages, lam_scale;  // two-sided evaluation (LindbladArgs::phase)
+        bool unit_ok = false;                 // one final TargetDensityInfidelity, one density
+        bool hermitian = false;               // H0, G_k, sum gamma L^H L, initial densities and cost matrices
+                                              // are Hermitian: so is every density and every cotangent
+        bool ops_real = false;                // every Lindblad operator has a zero imaginary part
+        int global_scratch = 0, multi_wave = 0, cache_gen = 0;
+        int pad_op = 0;  // L = 1: a zero second operator behind the real one, for the four-wave launches
+        int fixed_ksub = 0;              // > 0: time-dependent Hamiltonian sampled for this grid
+        // qocx_debug_lindblad_knobs (tests force the kernel variants large batches / little HBM use)
+        int64_t last_subintervals = 0;   // sum over the seeds of the last evaluation
+        int64_t dbg_stage_seeds = 0;     // seeds whose stage values may be kept; 0: 45 % of free HBM
+        int dbg_min_piece = 256;         // below this many seeds per piece the adjoint recomputes
+        int dbg_wave_mode = 0;           // 0 auto, 1 one wave per seed, 2 several whenever built for
+        DevBuf<double2> a0_tab, gp_tab, op_tab;
+        DevBuf<double> gamma_tab;
+        // multi-start driver on the device (qocx_lindblad_upload_controls / _opt_*): controls and
+        // results in seed order, apart from the evaluation's buffers above (group order)
+        int res_B = 0;
+        bool res_have_results = false, res_have_grads = false;
+        bool umax_valid = false;          // umax_host holds the control maxima of res_controls
+        std::vector<double> umax_host;    // [B][K]
+        DevBuf<double> res_controls, res_cost, res_grads, umax;
+        DevBuf<double2> res_final;        // [B][S] dumps
+        DevBuf<int> order_dev;            // lb.order on the device
+        MultiStart ms;                    // qocx_lindblad_opt_*
+        ControlCosts control_costs;       // qocx_set_control_costs(QOCX_PATH_LINDBLAD)
+    } lb;
+    // ---- qocx_debug_set_knob: kernel-variant switches for A/B measurements and tests ----
+    std::map<std::string, int64_t> knobs;
+    DevBuf<unsigned long long> stamps;  // sweep3 diagnostic build
+    int64_t knob(const char* name, int64_t dflt) const {
+        auto it = knobs.find(name);
+        return it == knobs.end() ? dflt : it->second;
+    }
+    // ---- timing ----
+    int timing = 0;            // 0 off, 1 every launch, 2 + k the launches of kernel k only
+    bool time_active = false;  // the launch between the last time_begin / time_end is being timed
+    std::vector<TimingRec> pending;
+    std::vector<double> timeline;  // (which, start, end) of the last evaluation's launches
+    std::vector<hipEvent_t> ev_pool;
+    size_t ev_used = 0;
+    int64_t t_launch[7] = {0, 0, 0, 0, 0, 0, 0};
+    double t_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+    // ---- comm ----
+    Rccl rccl;
+    void* comm = nullptr;
+    DevBuf<double> comm_buf;
+};
+
+namespace qocx::host {
+
+// ---- qocx_api.hip: kernel timing (qocx_set_timing) ----
+void time_begin(qocx_ctx* ctx, int which, hipStream_t st);
+void time_end(qocx_ctx* ctx, hipStream_t st);
+void time_collect(qocx_ctx* ctx);
+
+// ---- qocx_api.hip: norm bounds of the step generators; the seed-level view ----
+int pade_scale_count(double norm1);
+double one_norm(const double* m, int n);  // complex row-major
+double pade_eps_max(double theta);
+double magnus_norm_bound(int nodes, double bound);
+double quad_bound(const qocx_ctx* ctx, const double* umax);
+int seed_count(const qocx_ctx* ctx);
+int seed_channels(const qocx_ctx* ctx);
+double* seed_controls(qocx_ctx* ctx);
+double* seed_costs(qocx_ctx* ctx);
+double* seed_grads(qocx_ctx* ctx);
+
+// ---- qocx_host_resident.hip ----
+int eval_items(qocx_ctx* ctx, int32_t want_grad);
+
+// ---- qocx_api_lindblad.hip: the C-layout dumps of the densities ----
+int dump_elems(int n);
+void from_c_dump(const double2* d, int n, double* out);
+
+// ---- qocx_api_multistart.hip ----
+int run_control_costs(qocx_ctx* ctx, ControlCosts& cc, int B, int nc, int Kr, const double* controls,
+                      bool want_grad);
+
+}  // namespace qocx::host
+
+#endif

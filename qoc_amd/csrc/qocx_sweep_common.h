@@ -105,7 +105,7 @@ __device__ __forceinline__ double eval_costs(const SweepArgs& args, bool step_pa
 // adjoint recursion is linear in lam, so it can run on lam_s = t_s WITHOUT knowing the forward
 // result - the classic GRAPE back-propagation of the target - and K3 applies c_s to x = P^-H lam'
 // when it forms the gradient. The forward and the adjoint sweep then only meet in K3, and the
-// pipeline runs them side by side (qocx_api.hip). args.unit_adjoint selects it; args.lam_scale
+// pipeline runs them side by side (qocx_host_resident.hip). args.unit_adjoint selects it; args.lam_scale
 // [B][S] carries the scalars from the end of the forward sweep to K3.
 template <int NB>
 __device__ __forceinline__ void unit_adjoint_scales(const SweepArgs& args, const double2* vecs, int b,

@@ -6,8 +6,8 @@ product takes from them.
 Every other fixture of the suite draws its controls as sigma * standard_normal with one sigma per
 problem: one Pade order, one squaring count and one pivoting regime per launch. The product decides
 per step (step_table_kernel, qocx_kernels.hip; the K1a kernels from the matrix they built) and per
-upload (qocx_upload_controls / qocx_opt_clip, qocx_api.hip: norm_bound, norm_bound_mid, sbound, and
-from them prefer_low, the three-wave K1a with order_max 5, all_dominant, pack8, the slot layout).
+upload (qocx_upload_controls, qocx_api.hip / qocx_opt_clip, qocx_api_multistart.hip: norm_bound,
+norm_bound_mid, sbound, and from them prefer_low, the three-wave K1a with order_max 5, all_dominant, pack8, the slot layout).
 The pulses here make those decisions differ between neighbouring steps and between the seeds of a
 batch; tests/test_mixed_pulses_host.py proves on the CPU that they do, tests/test_gpu_mixed_steps.py
 runs them on the device.

@@ -240,3 +240,55 @@ def test_three_qubits_with_six_lindblad_operators_on_gpu():
         initial_controls=controls.copy(), iteration_count=5, log_iteration_step=0, optimizer=Adam(learning_rate=5e-2),
         max_control_norms=np.full(3, 3.0))
     assert grape.best_error < result.error
+
+
+def _free_device_memory():
+    """Free device memory in bytes: hipMemGetInfo of the HIP runtime libqocx.so is linked against,
+    found through the library's own handle (a symbol lookup there covers its dependencies); None
+    where that fails."""
+    import ctypes
+    from qoc_amd import engine
+    try:
+        query = engine.load_library().hipMemGetInfo
+    except AttributeError:
+        return None
+    query.restype = ctypes.c_int
+    query.argtypes = [ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    return int(free.value) if query(ctypes.byref(free), ctypes.byref(total)) == 0 else None
+
+
+def test_destroying_a_context_with_time_dependent_operators_frees_their_tables():
+    """qocx_destroy releases everything the context allocated, the operator / rate tables of a
+    time-dependent lindblad_data (uploaded by qocx_set_lindblad_problem) included: twenty contexts with
+    the problem of test_time_dependent_lindblad_data_fixture, each evaluated once and closed, leave
+    free device memory where it was after the first of them.
+    Bound: one 2 MiB fragment, the unit the runtime backs device allocations with - a buffer freed
+    and allocated again may land so that the free figure moves by one of them, while a table left
+    behind by each of nineteen contexts adds up to many (measured without the release: 6 MiB per
+    context with an evaluation, 8 MiB without one).
+    The runtime's own pools are not full after one context of a process: measured, with or without
+    the release above, one step of 48 MiB at the second context and nothing at the thirty-eight
+    after it. So two contexts come and go before the twenty. (The figure is the card's: another
+    process allocating on it during the test would show up here.)"""
+    if _free_device_memory() is None:
+        pytest.skip("free device memory cannot be read through libqocx.so's HIP runtime")
+    case = cases_mod.lindblad_case_by_name("lindblad_timedep_data")
+    costs = product_cost_list(case)
+
+    def create_evaluate_destroy():
+        ev = device.LindbladEvaluator(case.T, case.initial_densities, case.N, costs=costs,
+                                      hamiltonian=case.hamiltonian(), lindblad_data=case.lindblad_data(),
+                                      control_count=case.K, control_eval_count=case.Nc)
+        ev.evaluate_batch(np.stack(case.controls))
+        ev.backend.close()
+
+    for _ in range(2):
+        create_evaluate_destroy()
+    create_evaluate_destroy()
+    before = _free_device_memory()
+    for _ in range(19):
+        create_evaluate_destroy()
+    after = _free_device_memory()
+    print("free device memory after 1 and after 20 contexts:", before, after)
+    assert before - after <= 2 << 20
