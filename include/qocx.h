@@ -526,6 +526,34 @@ int qocx_eval_control_costs(qocx_ctx* ctx, int32_t path, int32_t batch, const do
 int qocx_opt_begin_complex(qocx_ctx* ctx);
 int qocx_lindblad_opt_begin_complex(qocx_ctx* ctx);
 
+/* ---- L-BFGS in the resident drivers -------------------------------------------------------------
+ * Limited-memory BFGS with an Armijo backtracking line search for every seed of the resident batch,
+ * its state in HBM (qocx_lbfgs.hip). qoc_amd/standard/optimizers/lbfgs.py states the algorithm as a
+ * per-seed state machine that consumes one (parameters, error, gradients) triple per evaluation and
+ * gives the next trial point; the kernel does the same arithmetic - every product and sum rounded on
+ * its own, IEEE division and square root, every inner product in that file's one defined order - so a
+ * seed walks the host loop's trajectory bit for bit, whatever the batch.
+ *   *_opt_lbfgs_begin  after *_opt_begin / *_opt_begin_complex: allocate and zero the state of the
+ *                      current batch with P = Nc * channels parameters per seed: accepted point,
+ *                      its gradient, the direction, `history` pairs (s, y, rho) and the scalars.
+ *                      QOCX_ERR_ARG for history outside 1..64, QOCX_ERR_CAPACITY if the state does
+ *                      not fit the free device memory.
+ *   *_opt_lbfgs_step   improved[b] != 0: best controls / final states of seed b := those of the last
+ *                      evaluation (as *_opt_step). Then, for update[b] != 0, seed b's state machine
+ *                      takes the last evaluation's total cost and gradient (with an ensemble the
+ *                      reduced ones; control costs included) and the trial point goes into the
+ *                      resident parameters. finished_out [B]: 1 for a seed whose steepest-descent
+ *                      direction has run out of backtracks - its parameters are back at its last
+ *                      accepted point and it takes no further steps. */
+int qocx_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history);
+int qocx_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const uint8_t* update,
+                        double first_step, double armijo, double shrink, int32_t max_backtracks,
+                        uint8_t* finished_out);
+int qocx_lindblad_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history);
+int qocx_lindblad_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const uint8_t* update,
+                                 double first_step, double armijo, double shrink,
+                                 int32_t max_backtracks, uint8_t* finished_out);
+
 /* ---- host-side helpers of the multi-start GRAPE driver (no GPU work, no context) --------------
  * The reference's driver loop clips the controls and applies its optimizer plugin to ONE control
  * set per process (qoc/core/common.py:8-30, qoc/standard/optimizers/adam.py:110-165, sgd.py). The

@@ -8,7 +8,9 @@ schroedingerdiscrete.py:293-353 / lindbladdiscrete.py:297-352 per seed): clip ->
 evaluate -> best-so-far (strict <) -> optimizer update with its own optimizer state, its own
 termination at error <= min_error (a finished seed is frozen). Two routes: the host loop (any
 evaluator, any step-wise optimizer plugin) and the device-resident one, where controls, gradients,
-Adam moments and the best so far stay in HBM and the host sees B costs per iteration.
+optimizer state (Adam moments, the L-BFGS history) and the best so far stay in HBM and the host sees
+B costs per iteration. An optimizer with `needs_error` (LBFGS) also takes the seed's error and may
+declare a seed `finished`: such a seed leaves the loop as one stopped by min_error does.
 """
 
 import numpy as np
@@ -16,7 +18,7 @@ import numpy as np
 from qoc_amd.core import structure
 from qoc_amd.core.common import initialize_controls, strip_controls
 from qoc_amd.models import Dummy
-from qoc_amd.standard.optimizers import SGD, Adam
+from qoc_amd.standard.optimizers import LBFGS, SGD, Adam
 
 
 class BatchResult(object):
@@ -57,6 +59,8 @@ def _optimizer_clone(optimizer, flat_controls):
             "the multi-start GRAPE drivers step the optimizer one update at a time and need its "
             "update(grads, params) (Adam, SGD); {} only offers run().".format(optimizer))
     clone = copy.deepcopy(optimizer)
+    if getattr(clone, "needs_error", False) and hasattr(clone, "reset"):
+        clone.reset()  # (LBFGS and its subclasses: every seed starts from fresh state)
     if hasattr(clone, "gradient_moment"):  # Adam.run(), adam.py:83-88 of the reference
         clone.iteration_count = 0
         clone.gradient_moment = np.zeros_like(flat_controls)
@@ -200,9 +204,28 @@ class _BatchedAdam(object):
             self.count[sel] = step
 
 
+class _BatchedLBFGS(object):
+    """B per-seed LBFGS state machines (the arithmetic of a seed is not elementwise: each keeps its
+    own history and line-search state); `finished` [B] is read by the loop after every update."""
+
+    needs_error = True
+
+    def __init__(self, optimizer, params):
+        self.seeds = [_optimizer_clone(optimizer, p) for p in params]
+        self.finished = np.zeros(params.shape[0], dtype=bool)
+
+    def update(self, grads, params, rows, errors):
+        """params[rows] <- the seeds' next trial points, in place."""
+        for b in rows:
+            params[b] = self.seeds[b].update(grads[b], params[b], errors[b])
+            self.finished[b] = self.seeds[b].finished
+
+
 def batched_stepper(optimizer, params):
     """The [B, P] form of the built-in step-wise optimizers; None for any other plugin (those keep
-    one deep copy per seed and their own update())."""
+    one deep copy per seed and their own update()). The LBFGS stepper also takes the seeds' errors."""
+    if type(optimizer) is LBFGS:
+        return _BatchedLBFGS(optimizer, params)
     if type(optimizer) is Adam:
         return _BatchedAdam(optimizer, params)
     if type(optimizer) is SGD:
@@ -276,9 +299,13 @@ def prepare_seeds(initial_controls, complex_controls, control_count, control_eva
 
 
 def resident_route(stepper, optimizer, pstate, evaluator, batch):
-    """The device-resident loop applies: built-in Adam / SGD without scale_grads, no control
+    """The device-resident loop applies: built-in Adam / SGD without scale_grads or LBFGS, no control
     conditions, and an evaluator that can keep everything on the device (structured Hamiltonian,
-    device costs and built-in costs of the controls; real or complex controls)."""
+    device costs and built-in costs of the controls; real or complex controls). LBFGS also needs
+    the backend's L-BFGS calls: a stand-in backend without them takes the host loop."""
+    if type(optimizer) is LBFGS and not (hasattr(evaluator, "resident_lbfgs_capable")
+                                         and evaluator.resident_lbfgs_capable()):
+        return False
     return (batch > 0 and stepper is not None and pstate.impose_control_conditions is None
             and not getattr(optimizer, "apply_scale_grads", False)
             and hasattr(evaluator, "resident_capable") and evaluator.resident_capable())
@@ -300,7 +327,7 @@ class ResidentOps(object):
     """One path's resident driver of the engine as run_batch_resident calls it. `calls` are the
     engine's bound methods of that path under the loop's names: upload_controls, opt_begin (the
     complex one for complex controls), opt_clip, eval_resident, download_costs, opt_step,
-    opt_download_best.
+    opt_download_best, and for LBFGS opt_lbfgs_begin, opt_lbfgs_step.
     control_costs: the descriptors of the costs of the controls alone, which the engine then adds
     to every resident evaluation of `path` until finish(); complex_controls: the loop's complex
     arrays travel as two real channels per control and the engine clips a copy of the parameters;
@@ -351,6 +378,7 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
                         min_error, comm, result):
     B = params.shape[0]
     is_adam = type(optimizer) is Adam
+    is_lbfgs = type(optimizer) is LBFGS
     _log_header(log_iteration_step, comm)
     shape = (B,) + tuple(pstate.controls_shape)
     if pstate.complex_controls:
@@ -359,6 +387,8 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
     else:
         ops.upload_controls(params.reshape(shape))
     ops.opt_begin()
+    if is_lbfgs:
+        ops.opt_lbfgs_begin(optimizer.history)
     active = np.ones(B, dtype=bool)
     count = 0  # optimizer steps taken so far (every active seed has taken all of them)
     should_log = log_iteration_step != 0
@@ -378,7 +408,12 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
                 print("{:^6d} | {:^1.8e} | {:^1.8e} | {:^6d}".format(iteration, total, low,
                                                                      int(seeds)))
         active &= ~(errors <= min_error)
-        if is_adam:
+        if is_lbfgs:
+            o = optimizer
+            finished = ops.opt_lbfgs_step(improved, active, o.first_step, o.armijo, o.shrink,
+                                          o.max_backtracks)
+            active &= ~finished  # (a finished seed is back at its accepted point and stays there)
+        elif is_adam:
             o = optimizer
             if o.apply_learning_rate_decay:
                 learning_rate = (o.initial_learning_rate
@@ -411,6 +446,7 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
     B = params.shape[0]
     shape = tuple(pstate.controls_shape)
     optimizers = None if stepper is not None else [_optimizer_clone(optimizer, p) for p in params]
+    needs_error = bool(getattr(stepper if stepper is not None else optimizer, "needs_error", False))
     _log_header(log_iteration_step, comm)
     active = np.ones(B, dtype=bool)
     best_controls = best_finals = None
@@ -447,11 +483,18 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
         rows = np.nonzero(active)[0]
         if len(rows):
             flat_grads = _strip_batch(pstate.complex_controls, np.asarray(grads))
-            if stepper is not None:
+            if stepper is not None and needs_error:
+                stepper.update(flat_grads, params, rows, errors)
+                active &= ~stepper.finished
+            elif stepper is not None:
                 stepper.update(flat_grads, params, rows)
             else:
                 for b in rows:
-                    params[b] = optimizers[b].update(flat_grads[b], params[b])
+                    if needs_error:
+                        params[b] = optimizers[b].update(flat_grads[b], params[b], errors[b])
+                        active[b] = not getattr(optimizers[b], "finished", False)
+                    else:
+                        params[b] = optimizers[b].update(flat_grads[b], params[b])
         still = comm.allreduce_sum(np.array([float(np.sum(active))]))[0]
         if still == 0:
             break

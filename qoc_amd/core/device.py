@@ -359,6 +359,10 @@ class SchroedingerEvaluator(object):
                 and controls_stay_resident(self.backend, self.control_cost_descriptors,
                                            self.complex_controls, "opt_begin_complex"))
 
+    def resident_lbfgs_capable(self):
+        """resident_capable() with a backend that also has the L-BFGS calls of the resident driver."""
+        return self.resident_capable() and hasattr(self.backend, "opt_lbfgs_step")
+
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
         """
         controls_batch :: (B x Nc x K) (or None / an int B when control_count == 0).
@@ -697,6 +701,10 @@ class LindbladEvaluator(object):
                 and hasattr(self.backend, "lindblad_opt_step")
                 and controls_stay_resident(self.backend, self.control_cost_descriptors,
                                            self.complex_controls, "lindblad_opt_begin_complex"))
+
+    def resident_lbfgs_capable(self):
+        """resident_capable() with a backend that also has the L-BFGS calls of the resident driver."""
+        return self.resident_capable() and hasattr(self.backend, "lindblad_opt_lbfgs_step")
 
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_densities=False):
         """

@@ -173,7 +173,9 @@ def _ResidentOps(engine, control_costs=(), complex_controls=False):
         opt_begin=engine.lindblad_opt_begin_complex if complex_controls else engine.lindblad_opt_begin,
         opt_clip=engine.lindblad_opt_clip, eval_resident=engine.eval_lindblad_resident,
         download_costs=engine.lindblad_download_costs, opt_step=engine.lindblad_opt_step,
-        opt_download_best=engine.lindblad_opt_download_best)
+        opt_download_best=engine.lindblad_opt_download_best,
+        opt_lbfgs_begin=getattr(engine, "lindblad_opt_lbfgs_begin", None),
+        opt_lbfgs_step=getattr(engine, "lindblad_opt_lbfgs_step", None))
 
 
 def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evolution_time,
@@ -196,8 +198,8 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     (B x control_eval_count x control_count), each conforming to max_control_norms. comm
     (qoc_amd.parallel communicator, optional): the seed axis is sharded over its ranks, result
     arrays are rank local. With costs the device evaluates (the built-in density costs and the four
-    built-in costs of the controls), a Hamiltonian linear in the controls, the built-in Adam / SGD
-    and no control conditions, controls, gradients, optimizer states and the best so far stay in HBM
+    built-in costs of the controls), a Hamiltonian linear in the controls, the built-in Adam / SGD /
+    LBFGS and no control conditions, controls, gradients, optimizer states and the best so far stay in HBM
     (qocx_lindblad_opt_*; real or complex controls); otherwise the host drives
     LindbladEvaluator.evaluate_batch. Both routes give the same numbers to rounding (bit for bit
     without costs of the controls and without a clip acting on a complex control).

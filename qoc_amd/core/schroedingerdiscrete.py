@@ -177,7 +177,9 @@ def _ResidentOps(engine, control_costs=(), complex_controls=False):
         opt_begin=engine.opt_begin_complex if complex_controls else engine.opt_begin,
         opt_clip=engine.opt_clip, eval_resident=engine.eval_resident,
         download_costs=engine.download_costs, opt_step=engine.opt_step,
-        opt_download_best=engine.opt_download_best)
+        opt_download_best=engine.opt_download_best,
+        opt_lbfgs_begin=getattr(engine, "opt_lbfgs_begin", None),
+        opt_lbfgs_step=getattr(engine, "opt_lbfgs_step", None))
 
 
 def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, evolution_time,
@@ -206,6 +208,10 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     errors are the weighted sums, the final states have a member axis, and member_errors[b] holds
     seed b's unweighted member costs at its best controls (one forward evaluation of all seeds
     after the loop).
+    optimizer: any step-wise plugin (update(grads, params)); Adam, SGD and LBFGS also run with their
+    state resident on the device. With LBFGS a seed whose line search is exhausted is `finished`:
+    frozen at its last accepted point like a seed stopped by min_error. LBFGSB (SciPy's loop) is
+    single-seed only.
     Returns GrapeSchroedingerBatchResult.
     """
     comm, pstate, params = batch.prepare_seeds(

@@ -109,6 +109,7 @@ struct SeedView {
     int seeds, channels, nc;  // seeds; control channels per seed; control knots
     double* controls;         // [seeds][nc][channels]
     double* grads;            // [seeds][nc][channels]
+    double* cost;             // [seeds] total costs of the last resident evaluation
     double2* finals;          // [seeds][final_elems]
     size_t final_elems;       // elements of final state per seed
     size_t per_seed() const { return (size_t)nc * channels; }
@@ -119,12 +120,12 @@ struct SeedView {
 SeedView schroedinger_seeds(qocx_ctx* ctx) {
     const size_t items = ctx->ens_M > 0 ? (size_t)ctx->ens_M : 1;
     return SeedView{seed_count(ctx), seed_channels(ctx), ctx->nc, seed_controls(ctx), seed_grads(ctx),
-                    ctx->final_out.p, items * ctx->S * ctx->np};
+                    seed_costs(ctx), ctx->final_out.p, items * ctx->S * ctx->np};
 }
 
 SeedView lindblad_seeds(qocx_ctx* ctx) {
     auto& lb = ctx->lb;
-    return SeedView{lb.res_B, lb.K, lb.nc, lb.res_controls.p, lb.res_grads.p, lb.res_final.p,
+    return SeedView{lb.res_B, lb.K, lb.nc, lb.res_controls.p, lb.res_grads.p, lb.res_cost.p, lb.res_final.p,
                     (size_t)lb.S * dump_elems(lb.n)};
 }
 
@@ -138,6 +139,7 @@ int multistart_begin(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, int batch
     HIP_TRY(hipMemsetAsync(ms.opt_m.p, 0, total * sizeof(double), ctx->stream));
     HIP_TRY(hipMemsetAsync(ms.opt_v.p, 0, total * sizeof(double), ctx->stream));
     ms.batch = batch;
+    ms.lbfgs_history = 0;  // (L-BFGS state is set up per batch: qocx_opt_lbfgs_begin)
     ms.complex_controls = false;
     if (!complex_controls) return 0;
     if (v.channels % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
@@ -190,6 +192,71 @@ int multistart_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const Step
     a.clip = rule.clip_grads; a.apply_clip = rule.apply_clip_grads ? 1 : 0;
     qocx::launch_optimizer_update(a, B, ctx->stream);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the flag arrays are the caller's memory
+    return 0;
+}
+
+// the L-BFGS state of the seeds, zeroed: accepted point, its gradient, direction, `history` pairs
+int multistart_lbfgs_begin(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, int history) {
+    if (history < 1 || history > qocx::LBFGS_MAX_HISTORY)
+        return fail(QOCX_ERR_ARG, "history must be in 1..64");
+    ms.lbfgs_history = 0;
+    const size_t total = v.total(), ring = total * (size_t)history;
+    const size_t bytes = (3 * total + 2 * ring + (size_t)v.seeds * history) * sizeof(double) +
+                         (size_t)v.seeds * (sizeof(qocx::LbfgsSeed) + 1);
+    size_t held = 0;  // (what a previous run of the same size left allocated is taken again)
+    for (const DevBuf<double>* buf : {&ms.lb_x, &ms.lb_g, &ms.lb_d, &ms.lb_s, &ms.lb_y, &ms.lb_rho})
+        held += buf->count * sizeof(double);
+    size_t free_bytes = 0, device_bytes = 0;
+    HIP_TRY(hipMemGetInfo(&free_bytes, &device_bytes));
+    if (bytes > held && bytes - held > free_bytes)
+        return fail(QOCX_ERR_CAPACITY, "the L-BFGS state of " + std::to_string(v.seeds) + " seeds (" +
+                                           std::to_string(bytes) + " bytes) does not fit the free device memory");
+    if (ms.lb_x.ensure(total) || ms.lb_g.ensure(total) || ms.lb_d.ensure(total) || ms.lb_s.ensure(ring) ||
+        ms.lb_y.ensure(ring) || ms.lb_rho.ensure((size_t)v.seeds * history) ||
+        ms.lb_seed.ensure((size_t)v.seeds) || ms.lb_finished.ensure((size_t)v.seeds))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipMemsetAsync(ms.lb_x.p, 0, total * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_g.p, 0, total * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_d.p, 0, total * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_s.p, 0, ring * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_y.p, 0, ring * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_rho.p, 0, (size_t)v.seeds * history * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_seed.p, 0, (size_t)v.seeds * sizeof(qocx::LbfgsSeed), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.lb_finished.p, 0, (size_t)v.seeds, ctx->stream));
+    ms.lbfgs_history = history;
+    return 0;
+}
+
+// the step rule of LBFGS.update (qoc_amd/standard/optimizers/lbfgs.py)
+struct LbfgsRule {
+    double first_step, armijo, shrink;
+    int32_t max_backtracks;
+};
+
+// keeps the controls and final states of the improved seeds, then runs the L-BFGS state machine of the
+// seeds flagged in `update` on the last evaluation's costs and gradients; finished_out [seeds]
+int multistart_lbfgs_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const LbfgsRule& rule,
+                          const uint8_t* improved, const uint8_t* update, uint8_t* finished_out) {
+    const int B = v.seeds;
+    HIP_TRY(hipMemcpyAsync(ms.opt_flags.p, improved, B, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ms.opt_flags.p + B, update, B, hipMemcpyHostToDevice, ctx->stream));
+    qocx::launch_keep_best(v.controls, ms.opt_best_controls.p, v.per_seed(), v.finals, ms.opt_best_final.p,
+                           v.final_elems, ms.opt_flags.p, B, ctx->stream);
+    qocx::LbfgsArgs a;
+    a.params = ms.complex_controls ? ms.opt_params.p : v.controls;
+    a.grads = v.grads; a.cost = v.cost;
+    a.x = ms.lb_x.p; a.g = ms.lb_g.p; a.d = ms.lb_d.p; a.s = ms.lb_s.p; a.y = ms.lb_y.p;
+    a.rho = ms.lb_rho.p; a.seed = ms.lb_seed.p;
+    a.update = ms.opt_flags.p + B; a.finished = ms.lb_finished.p;
+    a.per_seed = v.per_seed();
+    a.interleaved = ms.complex_controls ? 1 : 0;
+    a.history = ms.lbfgs_history;
+    a.first_step = rule.first_step; a.armijo = rule.armijo; a.shrink = rule.shrink;
+    a.max_backtracks = rule.max_backtracks;
+    qocx::launch_lbfgs_step(a, B, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(finished_out, ms.lb_finished.p, B, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the flag arrays are the caller's memory
     return 0;
 }
@@ -293,6 +360,28 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
     return 0;
 }
 
+int qocx_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return multistart_lbfgs_begin(ctx, ctx->ms, schroedinger_seeds(ctx), history);
+}
+
+int qocx_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const uint8_t* update, double first_step,
+                        double armijo, double shrink, int32_t max_backtracks, uint8_t* finished_out) {
+    if (!ctx || !improved || !update || !finished_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    if (ctx->ms.lbfgs_history < 1) return fail(QOCX_ERR_STATE, "qocx_opt_lbfgs_begin has not run for this batch");
+    if (!ctx->have_results || !ctx->have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const LbfgsRule rule{first_step, armijo, shrink, max_backtracks};
+    if (int rc = multistart_lbfgs_step(ctx, ctx->ms, schroedinger_seeds(ctx), rule, improved, update, finished_out))
+        return rc;
+    ctx->have_results = false;  // the resident controls are no longer those of the last evaluation
+    ctx->ens_stale = ctx->ens_M > 0;
+    return 0;
+}
+
 int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_out) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
@@ -357,6 +446,34 @@ int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
     HIP_TRY(hipSetDevice(ctx->device));
     const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
     if (int rc = multistart_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update)) return rc;
+    lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
+    lb.umax_valid = false;
+    return 0;
+}
+
+int qocx_lindblad_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return multistart_lbfgs_begin(ctx, lb.ms, lindblad_seeds(ctx), history);
+}
+
+int qocx_lindblad_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const uint8_t* update,
+                                 double first_step, double armijo, double shrink, int32_t max_backtracks,
+                                 uint8_t* finished_out) {
+    if (!ctx || !improved || !update || !finished_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    if (lb.ms.lbfgs_history < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_lbfgs_begin has not run for this batch");
+    if (!lb.res_have_results || !lb.res_have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const LbfgsRule rule{first_step, armijo, shrink, max_backtracks};
+    if (int rc = multistart_lbfgs_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update, finished_out))
+        return rc;
     lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
     lb.umax_valid = false;
     return 0;

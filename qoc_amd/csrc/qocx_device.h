@@ -425,6 +425,38 @@ void launch_optimizer_update(const OptimArgs& a, int batch, hipStream_t st);
 void launch_clip_complex(const double* params, double* controls, size_t pairs, int k,
                          const double* max_norms, hipStream_t st);
 
+// L-BFGS with Armijo backtracking for the seeds of the multi-start driver (qocx_lbfgs.hip;
+// qoc_amd/standard/optimizers/lbfgs.py is the statement of the algorithm)
+enum { LBFGS_MAX_HISTORY = 64 };
+struct LbfgsSeed {  // the scalars of one seed
+    double f, t, gamma;  // accepted error; step along d; s.y / y.y of the newest pair
+    int bt, steepest, started, finished;
+    int head, count;     // ring of pairs: slot of the oldest, pairs stored
+};
+struct LbfgsArgs {
+    double* params;              // [B][per_seed]: the evaluated point in, the next trial point out
+    const double* grads;         // [B][per_seed] gradients of the last evaluation
+    const double* cost;          // [B] its total costs
+    double* x;                   // [B][per_seed] accepted point
+    double* g;                   // [B][per_seed] its gradient
+    double* d;                   // [B][per_seed] direction (the two-loop recursion's q on the way)
+    double* s;                   // [B][history][per_seed] ring of steps
+    double* y;                   // [B][history][per_seed] ring of gradient differences
+    double* rho;                 // [B][history] 1 / s.y
+    LbfgsSeed* seed;             // [B]
+    const unsigned char* update; // [B]: seeds that take the step
+    unsigned char* finished;     // [B] out
+    size_t per_seed;
+    // complex controls: element i of the host's parameter vector (all real parts, then all imaginary
+    // parts) lives at 2 i / 2 (i - per_seed / 2) + 1 in the device's interleaved channels; inner
+    // products run in the host's element order
+    int interleaved;
+    int history;
+    double first_step, armijo, shrink;
+    int max_backtracks;
+};
+void launch_lbfgs_step(const LbfgsArgs& a, int batch, hipStream_t st);
+
 // Costs of the controls alone (qocx_ctrlcost.hip; qoc/standard/costs/control*.py)
 struct CtrlCostDev {
     int kind, order;    // QOCX_CONTROL_*; ControlVariation: order of the difference

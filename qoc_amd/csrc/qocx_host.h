@@ -121,6 +121,11 @@ struct MultiStart {
     DevBuf<unsigned char> opt_flags;  // [2][B]: improved | update
     DevBuf<double> opt_params;        // complex controls: the optimizer's parameters - the seed controls
                                       // are then the copy clipped by modulus that is evaluated
+    // L-BFGS (qocx_opt_lbfgs_begin): accepted point, its gradient, direction, the rings of pairs
+    DevBuf<double> lb_x, lb_g, lb_d, lb_s, lb_y, lb_rho;
+    DevBuf<qocx::LbfgsSeed> lb_seed;
+    DevBuf<unsigned char> lb_finished;
+    int lbfgs_history = 0;            // 0: no L-BFGS state for this batch
     int batch = 0;                    // the path's batch the states were set up for (0: none)
     bool complex_controls = false;    // qocx_opt_begin_complex / qocx_lindblad_opt_begin_complex
 };

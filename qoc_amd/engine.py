@@ -195,6 +195,12 @@ SIGNATURES = {
                                                _c_double_p]),
     "qocx_opt_begin_complex": (ctypes.c_int, [_VP]),
     "qocx_lindblad_opt_begin_complex": (ctypes.c_int, [_VP]),
+    "qocx_opt_lbfgs_begin": (ctypes.c_int, [_VP, _I32]),
+    "qocx_opt_lbfgs_step": (ctypes.c_int, [_VP, _U8P, _U8P, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, _I32, _U8P]),
+    "qocx_lindblad_opt_lbfgs_begin": (ctypes.c_int, [_VP, _I32]),
+    "qocx_lindblad_opt_lbfgs_step": (ctypes.c_int, [_VP, _U8P, _U8P, ctypes.c_double,
+                                                    ctypes.c_double, ctypes.c_double, _I32, _U8P]),
     "qocx_host_clip_controls": (ctypes.c_int, [_c_double_p, _I64, _I64, _I32, _c_double_p]),
     "qocx_host_optimizer_update": (ctypes.c_int, [
         _I32, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _I64, ctypes.POINTER(_I64), _I64,
@@ -665,6 +671,25 @@ class Engine(object):
             float(corr_2), 0 if clip_grads is None else 1,
             0.0 if clip_grads is None else float(clip_grads)))
 
+    def opt_lbfgs_begin(self, history):
+        """After opt_begin / opt_begin_complex: the seeds' L-BFGS state, zeroed (qocx_opt_lbfgs_begin)."""
+        self._check(self._lib.qocx_opt_lbfgs_begin(self._ctx, int(history)))
+
+    def _lbfgs_step(self, call, improved, update, first_step, armijo, shrink, max_backtracks):
+        improved = np.ascontiguousarray(improved, dtype=np.uint8)
+        update = np.ascontiguousarray(update, dtype=np.uint8)
+        finished = np.zeros(len(update), dtype=np.uint8)
+        self._check(call(self._ctx, improved.ctypes.data_as(_U8P), update.ctypes.data_as(_U8P),
+                         float(first_step), float(armijo), float(shrink), int(max_backtracks),
+                         finished.ctypes.data_as(_U8P)))
+        return finished.astype(bool)
+
+    def opt_lbfgs_step(self, improved, update, first_step, armijo, shrink, max_backtracks):
+        """The best-so-far bookkeeping of opt_step, then one LBFGS.update of the seeds flagged in
+        `update` on the last evaluation's costs and gradients; returns finished [B] (bool)."""
+        return self._lbfgs_step(self._lib.qocx_opt_lbfgs_step, improved, update, first_step, armijo,
+                                shrink, max_backtracks)
+
     def opt_download_best(self):
         pr, B = self._problem, self.batch
         controls = np.empty((B, pr["Nc"], self._seed_channels()), dtype=np.float64)
@@ -722,6 +747,13 @@ class Engine(object):
             float(learning_rate), float(beta_1), float(beta_2), float(epsilon), float(corr_1),
             float(corr_2), 0 if clip_grads is None else 1,
             0.0 if clip_grads is None else float(clip_grads)))
+
+    def lindblad_opt_lbfgs_begin(self, history):
+        self._check(self._lib.qocx_lindblad_opt_lbfgs_begin(self._ctx, int(history)))
+
+    def lindblad_opt_lbfgs_step(self, improved, update, first_step, armijo, shrink, max_backtracks):
+        return self._lbfgs_step(self._lib.qocx_lindblad_opt_lbfgs_step, improved, update, first_step,
+                                armijo, shrink, max_backtracks)
 
     def lindblad_opt_download_best(self):
         pr, B = self._lindblad, self._lindblad_resident_batch

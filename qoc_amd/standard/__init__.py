@@ -9,7 +9,7 @@ from .costs import (ControlArea, ControlBandwidthMax, ControlNorm, ControlVariat
 from .functions import (column_vector_list_to_matrix, commutator, conjugate_transpose, expm,
                         krons, matmuls, matrix_to_column_vector_list, rms_norm)
 from .hamiltonians import HamiltonianEnsemble, QuadraticHamiltonian
-from .optimizers import LBFGSB, SGD, Adam
+from .optimizers import LBFGS, LBFGSB, SGD, Adam
 from .utils import CustomJSONEncoder, generate_save_file_path
 
 __all__ = [
@@ -20,7 +20,7 @@ __all__ = [
     "TargetStateInfidelity", "TargetStateInfidelityTime",
     "commutator", "conjugate_transpose", "expm", "krons", "rms_norm", "matmuls",
     "column_vector_list_to_matrix", "matrix_to_column_vector_list",
-    "Adam", "LBFGSB", "SGD",
+    "Adam", "LBFGS", "LBFGSB", "SGD",
     "HamiltonianEnsemble", "QuadraticHamiltonian",
     "generate_save_file_path", "CustomJSONEncoder",
 ]
