@@ -204,6 +204,9 @@ int qocx_download_generator_cotangents(qocx_ctx* ctx, double* cotangents_out);
  * QOCX_ERR_CAPACITY when a time-dependent problem's augmented tables (nt x (K + count) padded
  * matrices, three images below hilbert_size 65) would exceed 4 GiB. Controls must be uploaded
  * again afterwards.
+ * With an ensemble (below; the two setters may come in either order) control_count is K_r + J: the
+ * limit is K_r + J + count <= 64, the tables hold nt x (K_r + J + count) matrices, and the pairs
+ * index the seeds' channels, l_q < K_r (QOCX_ERR_ARG otherwise, from whichever setter comes second).
  */
 int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs, const double* matrices);
 
@@ -215,8 +218,18 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
  *     r[j][k] = s_mk u_b[j][k] (k < K_r),   r[j][K_r + i] = delta_mi (every knot)
  * i.e. H_m(u, t) = H(s_m . u, t) + sum_i delta_mi D_i.
  *   scales  [M][K_r] (NULL: all 1)   offsets [M][J] (NULL exactly when J = 0)   weights [M] >= 0
- * QOCX_ERR_ARG unless 1 <= M <= 1024, 0 <= J < control_count, every input is finite and no
- * quadratic terms are set. A new problem clears the ensemble. Controls must be uploaded afterwards.
+ * QOCX_ERR_ARG unless 1 <= M <= 1024, 0 <= J < control_count and every input is finite. A new
+ * problem clears the ensemble. Controls must be uploaded afterwards.
+ * With quadratic terms (qocx_set_quadratic_terms, before or after this call) member m of seed b is
+ *     H_(b,m)(t) = H_lin(s_m . u_b, t) + sum_i delta_mi D_i + sum_q c_mq (s_m,kq r_kq)(s_m,lq r_lq) Q_q
+ * with r the seed's real channels and c_mq = 1 unless qocx_set_ensemble_quadratic_scales sets them.
+ * An evaluation then runs: expansion of the seeds into the B x M items, the items' effective
+ * controls (r_k, c_mq r_k r_l), the factor / sweep / gradient kernels of any batch, the chain rule
+ * back to the items' real channels, the scatter to the knots, and the reduction below. The
+ * squaring bound of the quadratic share is that of the expanded items,
+ *     sum_q ||Q_q||_1 max_m |c_mq| (max_m |s_m,kq| max |r_kq|) (max_m |s_m,lq| max |r_lq|)
+ * (the product of the members' maxima, not the maximum of the members' products), on an upload from
+ * the uploaded controls and in qocx_opt_clip with max_norms in their place.
  * With an ensemble set:
  *   qocx_upload_controls(ctx, B, controls [B][Nc][K_r]) keeps the seed controls on the device and
  *     expands them into the B x M items (item b * M + m); the squaring bounds are those of the
@@ -233,6 +246,15 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
 int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
                       const double* offsets, const double* weights);
 int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out);
+
+/*
+ * Per-member scales of the quadratic terms of an ensemble (an uncertain Stark coefficient):
+ *   scales [M][count] real, c_mq multiplying term q of member m; NULL clears them (all 1).
+ * Needs qocx_set_ensemble with that M and qocx_set_quadratic_terms with that count, in either
+ * order, before it; QOCX_ERR_ARG otherwise and for non-finite values. A new problem, a new
+ * ensemble and new quadratic terms clear the scales. Controls must be uploaded again afterwards.
+ */
+int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t count, const double* scales);
 
 /* Optional: all system-step states of the last evaluation, [B][N][S][n] complex
  * (what save_intermediate_states persists, schroedingerdiscrete.py:395-402). */

@@ -155,13 +155,15 @@ class SchroedingerEvaluator(object):
         # A HamiltonianEnsemble: its linear base goes in structured form with the perturbation
         # matrices D_j appended to the G_k as J extra channels, and the engine expands every seed
         # into the M members' (K_r + J)-channel controls (qocx_set_ensemble). Evaluations return
-        # the weighted seed costs and gradients, and final states with a member axis.
+        # the weighted seed costs and gradients, and final states with a member axis. A
+        # QuadraticHamiltonian base under M2 goes on into the quadratic route above: its terms
+        # index the seeds' K_r channels and act on the members' scaled controls.
         self.ensemble = None
         if isinstance(hamiltonian, HamiltonianEnsemble):
             if backend is None:
                 backend = make_backend()
             hamiltonian = self._ensemble_base(hamiltonian, control_count, complex_controls,
-                                              backend)
+                                              backend, magnus_policy)
         if isinstance(hamiltonian, QuadraticHamiltonian) and backend is None:
             backend = make_backend()  # (the route depends on what the backend takes)
         if (isinstance(hamiltonian, QuadraticHamiltonian) and magnus_policy == MagnusPolicy.M2
@@ -244,19 +246,31 @@ class SchroedingerEvaluator(object):
             self.backend.set_quadratic_terms(*self.quadratic_terms)
         if self.ensemble is not None:
             self.backend.set_ensemble(*self._ensemble_args)
+            if (self.quadratic_terms is not None and len(self.quadratic_terms[0])
+                    and self.ensemble.quadratic_scales is not None):
+                self.backend.set_ensemble_quadratic_scales(self.ensemble.quadratic_scales)
 
     # -- Hamiltonian ensembles ------------------------------------------------------------------
-    def _ensemble_base(self, ensemble, control_count, complex_controls, backend):
+    def _ensemble_base(self, ensemble, control_count, complex_controls, backend, magnus_policy):
         """Checks an ensemble against this problem and the backend; returns its base Hamiltonian
-        (probed like any linear one)."""
+        (probed like any linear one, or taken apart like any QuadraticHamiltonian)."""
         base = ensemble.hamiltonian
         if control_count == 0:
             raise NotImplementedError("a HamiltonianEnsemble needs at least one control "
                                       "(control_count = 0)")
-        if isinstance(base, (QuadraticHamiltonian, HamiltonianEnsemble)):
+        # a quadratic base: under M2, on a backend that takes quadratic terms and ensembles (and
+        # the members' term scales, where the ensemble has them)
+        quadratic_ok = (
+            isinstance(base, QuadraticHamiltonian) and magnus_policy == MagnusPolicy.M2
+            and hasattr(backend, "set_quadratic_terms") and hasattr(backend, "set_ensemble")
+            and (ensemble.quadratic_scales is None
+                 or hasattr(backend, "set_ensemble_quadratic_scales")))
+        if isinstance(base, HamiltonianEnsemble) or (isinstance(base, QuadraticHamiltonian)
+                                                     and not quadratic_ok):
             raise NotImplementedError(
-                "a HamiltonianEnsemble needs a base hamiltonian linear in the controls, got {!r}"
-                "".format(base))
+                "a HamiltonianEnsemble needs a base hamiltonian linear in the controls (or a "
+                "QuadraticHamiltonian under MagnusPolicy.M2 on a backend that takes quadratic "
+                "terms and their member scales), got {!r}".format(base))
         if not hasattr(backend, "set_ensemble"):
             raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian ensembles "
                                       "(no set_ensemble)".format(backend))

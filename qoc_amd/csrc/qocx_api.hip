@@ -380,6 +380,7 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     }
     ctx->quad_count = 0;  // a new problem clears the quadratic terms
     ctx->ens_M = 0;       // ... and the ensemble
+    ctx->ens_qscales_set = false;
     // Hamiltonian images + norms for the squaring bound
     std::vector<double2> img((size_t)nt * mat);
     ctx->h0_norm_max = 0;
@@ -545,11 +546,10 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
     if (count < 0) return fail(QOCX_ERR_ARG, "count must be >= 0");
-    if (ctx->ens_M > 0 && count > 0)
-        return fail(QOCX_ERR_ARG, "quadratic terms do not combine with an ensemble (qocx_set_ensemble)");
     HIP_TRY(hipSetDevice(ctx->device));
     if (count == 0) {
         ctx->quad_count = 0;
+        ctx->ens_qscales_set = false;
         ctx->hermitian = ctx->hermitian_linear;
         ctx->have_results = false;
         ctx->B = 0;  // the norm bound of the uploaded controls no longer applies
@@ -561,10 +561,17 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     if (ctx->explicit_mode) return fail(QOCX_ERR_ARG, "quadratic terms do not apply to explicit generators");
     const int n = ctx->n, K = ctx->K, nt = ctx->nt, nb = ctx->nb, np = ctx->np;
     if (K < 1) return fail(QOCX_ERR_ARG, "quadratic terms need control_count >= 1");
+    // (with an ensemble K = K_r + J: the fixed channels count towards the limit, and the pairs index
+    // the seeds' K_r channels - qocx_set_ensemble makes the same check when it comes second)
     if (K + count > 64) return fail(QOCX_ERR_ARG, "control_count + quadratic term count must be <= 64");
     for (int q = 0; q < count; ++q)
         if (pairs[2 * q] < 0 || pairs[2 * q] > pairs[2 * q + 1] || pairs[2 * q + 1] >= K)
             return fail(QOCX_ERR_ARG, "quadratic term pairs must satisfy 0 <= k <= l < control_count");
+    if (ctx->ens_M > 0)
+        for (int q = 0; q < count; ++q)
+            if (pairs[2 * q + 1] >= ctx->ens_Kr)
+                return fail(QOCX_ERR_ARG, "quadratic term pairs must index the ensemble's seed channels "
+                                          "(l < control_count - fixed)");
     const size_t nn = (size_t)n * n, mat = (size_t)np * np;
     const int Ke = K + count;
     // With a time-dependent linear part the K1a / K3 tables are [nt][Ke]: every table entry carries
@@ -614,6 +621,7 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     ctx->quad_pairs = pr;
     ctx->quad_norm = norms;
     ctx->quad_count = count;
+    ctx->ens_qscales_set = false;  // (scales of the previous terms)
     ctx->hermitian = herm ? 1 : 0;
     ctx->have_results = false;
     ctx->B = 0;  // controls must be uploaded again: their norm bound now includes the Q_q
@@ -631,9 +639,13 @@ int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const doubl
     if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed perturbation channels need offsets");
     if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 perturbation channels");
     if (!weights) return fail(QOCX_ERR_ARG, "weights missing");
-    if (ctx->quad_count > 0)
-        return fail(QOCX_ERR_ARG, "an ensemble needs a Hamiltonian linear in the controls (no quadratic terms)");
     const int M = members, J = fixed, Kr = ctx->K - fixed;
+    // quadratic terms are products of the seeds' channels (qocx_set_quadratic_terms checks the same
+    // when it comes second)
+    for (int q = 0; q < ctx->quad_count; ++q)
+        if (ctx->quad_pairs[2 * q + 1] >= Kr)
+            return fail(QOCX_ERR_ARG, "quadratic term pairs must index the ensemble's seed channels "
+                                      "(l < control_count - fixed)");
     std::vector<double> sc((size_t)M * Kr, 1.0), off((size_t)M * J), w(weights, weights + M);
     if (scales) sc.assign(scales, scales + sc.size());
     if (J > 0) off.assign(offsets, offsets + off.size());
@@ -662,8 +674,39 @@ int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const doubl
     ctx->ens_Kr = Kr;
     ctx->ens_B = 0;
     ctx->ens_stale = false;
+    ctx->ens_qscales_set = false;  // (scales of the previous ensemble's members)
     ctx->have_results = false;
     ctx->B = 0;  // controls must be uploaded again (as seed controls)
+    ctx->ms.batch = 0;
+    return 0;
+}
+
+int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t count, const double* scales) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
+    if (ctx->ens_M == 0) return fail(QOCX_ERR_ARG, "quadratic term scales need an ensemble (qocx_set_ensemble)");
+    if (ctx->quad_count == 0)
+        return fail(QOCX_ERR_ARG, "quadratic term scales need quadratic terms (qocx_set_quadratic_terms)");
+    if (members != ctx->ens_M) return fail(QOCX_ERR_ARG, "members does not match the ensemble's");
+    if (count != ctx->quad_count) return fail(QOCX_ERR_ARG, "count does not match the quadratic terms'");
+    if (!scales) {
+        ctx->ens_qscales_set = false;
+    } else {
+        std::vector<double> c(scales, scales + (size_t)members * count), cmax(count, 0.0);
+        for (int m = 0; m < members; ++m)
+            for (int q = 0; q < count; ++q) {
+                const double v = c[(size_t)m * count + q];
+                if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite quadratic term scale");
+                cmax[q] = std::max(cmax[q], fabs(v));
+            }
+        HIP_TRY(hipSetDevice(ctx->device));
+        if (ctx->ens_qscales.upload(c, ctx->stream)) return QOCX_ERR_HIP;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ctx->ens_qscale_max = cmax;
+        ctx->ens_qscales_set = true;
+    }
+    ctx->have_results = false;
+    ctx->B = 0;  // controls must be uploaded again: their norm bound includes the scales
     ctx->ms.batch = 0;
     return 0;
 }
@@ -711,11 +754,23 @@ double magnus_norm_bound(int nodes, double bound) {
 }
 
 // sum_q ||Q_q||_1 umax[k_q] umax[l_q]: with umax[k] >= max_t |r_k(t)|, a bound of the quadratic
-// terms' share of ||H(t)||_1 at every time, between knots included
+// terms' share of ||H(t)||_1 at every time, between knots included.
+// With an ensemble umax are bounds of the SEEDS' channels and the bound is that of the expanded
+// items: sum_q ||Q_q||_1 max_m |c_mq| (max_m |s_m,kq| umax[k_q]) (max_m |s_m,lq| umax[l_q]) - the
+// product of the maxima over the members, not the (tighter) maximum over the members of the
+// product: it needs no pass over the members per upload and can only cost a squaring, not digits.
 double quad_bound(const qocx_ctx* ctx, const double* umax) {
     double b = 0.0;
-    for (int q = 0; q < ctx->quad_count; ++q)
-        b += ctx->quad_norm[q] * fabs(umax[ctx->quad_pairs[2 * q]]) * fabs(umax[ctx->quad_pairs[2 * q + 1]]);
+    const bool ens = ctx->ens_M > 0;
+    for (int q = 0; q < ctx->quad_count; ++q) {
+        const int k = ctx->quad_pairs[2 * q], l = ctx->quad_pairs[2 * q + 1];
+        if (!ens) {
+            b += ctx->quad_norm[q] * fabs(umax[k]) * fabs(umax[l]);
+            continue;
+        }
+        const double c = ctx->ens_qscales_set ? ctx->ens_qscale_max[q] : 1.0;
+        b += ctx->quad_norm[q] * c * (ctx->ens_scale_max[k] * fabs(umax[k])) * (ctx->ens_scale_max[l] * fabs(umax[l]));
+    }
     return b;
 }
 
@@ -866,7 +921,10 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // Quadratic terms: r_k(t) r_l(t) is not convex between knots (r_k 0 -> a, r_l a -> 0 peaks at
         // a^2 / 4 mid-interval), so the knot sums above do not bound it. |r_k(t)| <= max over the knots of
         // |r_k| does hold everywhere (linear interpolation): ||Q_q||_1 max|r_k| max|r_l| bounds every step.
-        if (ctx->quad_count > 0) bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, K).data());
+        // (with an ensemble the staging buffer holds the seeds' K_r channels, unscaled: quad_bound
+        // applies the members' scales)
+        if (ctx->quad_count > 0)
+            bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, ens ? ctx->ens_Kr : K).data());
         if (ens) {
             if (int rc = ensemble_upload(ctx, batch, stage)) return rc;
         } else {

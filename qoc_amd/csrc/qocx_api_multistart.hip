@@ -322,7 +322,9 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
         bound += (ens ? channel_norms[k] * ctx->ens_scale_max[k] : channel_norms[k]) * ctx->g_norm_max[k];
     }
     for (int j = 0; ens && j < ctx->ens_J; ++j) bound += ctx->ens_offset_max[j] * ctx->g_norm_max[Ks + j];
-    bound += quad_bound(ctx, channel_norms.data());  // (quadratic terms: ||Q_q||_1 max_norms_k max_norms_l)
+    // (quadratic terms: ||Q_q||_1 max_norms_k max_norms_l, with an ensemble times its members' largest
+    // scales as in qocx_upload_controls)
+    bound += quad_bound(ctx, channel_norms.data());
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
     const int sb = pade_scale_count(bound);

@@ -246,6 +246,12 @@ struct QuadArgs {
     const double2* lam_scale;  // unit adjoint: [B][S] (see ScatterArgs), or nullptr
     double* greal;             // chain kernel out: [B][nsteps][K], read by scatter_kernel
     size_t total;              // B * nsteps
+    // Per-member scales of the terms (qocx_set_ensemble_quadratic_scales): item i of the evaluation
+    // is member i % M of its seed, and its term q is c_(m,q) r_k r_l Q_q. nullptr: no scales - the
+    // launch then takes the kernels without them.
+    const double* term_scales = nullptr;  // [M][count]
+    int M = 1;
+    size_t item0 = 0;          // evaluation index of the chunk's first item (B above is the chunk's)
 };
 
 // Hamiltonian ensemble (qocx_ensemble.hip): B seeds x M members, K = Kr + J channels per member

@@ -213,6 +213,10 @@ struct qocx_ctx {
     std::vector<double> ens_scale_max, ens_offset_max;  // max_m |s_mk|, max_m |delta_mj|
     DevBuf<double> ens_scales, ens_offsets, ens_weights;
     DevBuf<double> ens_controls, ens_cost, ens_grads;   // [B][nc][Kr], [B], [B][nc][Kr]
+    // ... with quadratic terms: the members' scales c_mq of the terms (qocx_set_ensemble_quadratic_scales)
+    bool ens_qscales_set = false;
+    std::vector<double> ens_qscale_max;                 // max_m |c_mq|
+    DevBuf<double> ens_qscales;                         // [M][count]
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;

@@ -25,16 +25,21 @@ static int finish_items(qocx_ctx* ctx, int want_grad) {
     return 0;
 }
 
-// QuadArgs of a chunk of `bc` seeds whose real controls start at `controls`. The chain kernel writes
-// the per-step real-control cotangents into gnode, which scatter_kernel then reads (real, with
-// lam_scale already applied) - the m4lin arrangement.
-static qocx::QuadArgs quad_args(qocx_ctx* ctx, const double* controls, const double2* lam_scale, int bc) {
+// QuadArgs of a chunk of `bc` seeds, the first of them item `b0` of the evaluation, whose real
+// controls start at `controls`. The chain kernel writes the per-step real-control cotangents into
+// gnode, which scatter_kernel then reads (real, with lam_scale already applied) - the m4lin
+// arrangement. With an ensemble the items are its members, whose controls the expansion has scaled;
+// its term scales, if set, go along (qocx_set_ensemble_quadratic_scales).
+static qocx::QuadArgs quad_args(qocx_ctx* ctx, const double* controls, const double2* lam_scale, int b0, int bc) {
     qocx::QuadArgs qa;
     qa.controls = controls; qa.interp = ctx->interp.p; qa.pairs = ctx->quad_pairs_dev.p;
     qa.K = ctx->K; qa.count = ctx->quad_count; qa.Ke = ctx->K + ctx->quad_count;
     qa.nc = ctx->nc; qa.nsteps = ctx->nsteps; qa.S = ctx->S;
     qa.veff = ctx->veff.p; qa.gstep = ctx->gstep.p; qa.lam_scale = lam_scale; qa.greal = ctx->gnode.p;
     qa.total = (size_t)bc * ctx->nsteps;
+    if (ctx->ens_M > 0 && ctx->ens_qscales_set) {
+        qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->ens_M; qa.item0 = (size_t)b0;
+    }
     return qa;
 }
 
@@ -117,7 +122,7 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
         }
         qocx::QuadArgs qa;
         if (quad) {
-            qa = quad_args(ctx, fa.controls, nullptr, bc);
+            qa = quad_args(ctx, fa.controls, nullptr, b0, bc);
             qocx::launch_quad_controls(qa, cs);
             fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_rm = ctx->ge_timg.p;
             fa.K = Kk; fa.nc = nsteps;
@@ -444,7 +449,7 @@ struct ResidentChunk {
             fa.K = r.Kk; fa.nc = nsteps;
         }
         if (r.quad) {
-            qa = quad_args(ctx, fa.controls, r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr, bc);
+            qa = quad_args(ctx, fa.controls, r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr, b0, bc);
             time_begin(ctx, 0, cs);
             qocx::launch_quad_controls(qa, cs);
             time_end(ctx, cs);

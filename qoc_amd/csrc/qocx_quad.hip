@@ -7,12 +7,17 @@
 // through the identity interpolation (one row per step), the sweeps and K3 run unchanged on Ke
 // controls, and the chain kernel folds the Ke per-step cotangents back into the K real controls
 // before the usual scatter_kernel carries them to the knots.
+//
+// With an ensemble whose members scale the terms (QuadArgs::term_scales) item i carries
+// c_(i % M, q) r_kq r_lq in effective control K + q, and its cotangent takes the same factor on the
+// way back. SCALED is a template parameter: without scales the kernels are the ones they were.
 #include "qocx_device.h"
 #include "qocx_wave.h"
 
 namespace qocx {
 
 // One thread per (seed, step): w = [r_k(t_mid), r_kq(t_mid) r_lq(t_mid)].
+template <bool SCALED>
 __global__ __launch_bounds__(256) void quad_controls_kernel(QuadArgs args) {
     const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= args.total) return;
@@ -23,12 +28,20 @@ __global__ __launch_bounds__(256) void quad_controls_kernel(QuadArgs args) {
     double* v = args.veff + w * args.Ke;
     for (int k = 0; k < K; ++k) v[k] = control_at(ctl_b, si, K, k);
     // (control_at again rather than a local array indexed by the pair: no scratch, same bits)
-    for (int q = 0; q < args.count; ++q)
-        v[K + q] = control_at(ctl_b, si, K, args.pairs[2 * q]) * control_at(ctl_b, si, K, args.pairs[2 * q + 1]);
+    const double* cm = nullptr;  // the item's member's term scales
+    (void)cm;
+    if constexpr (SCALED) cm = args.term_scales + ((args.item0 + b) % (size_t)args.M) * (size_t)args.count;
+    for (int q = 0; q < args.count; ++q) {
+        const double rr = control_at(ctl_b, si, K, args.pairs[2 * q]) * control_at(ctl_b, si, K, args.pairs[2 * q + 1]);
+        if constexpr (SCALED) v[K + q] = cm[q] * rr;
+        else v[K + q] = rr;
+    }
 }
 
 // One thread per (seed, step): dC/dr_k = gbar_k + sum_q c_q r_other gbar_(K+q), c_q = 2 for a
 // square, 1 for a cross pair. Writes greal [B][nsteps][K] (real), which scatter_kernel reads.
+// SCALED: gbar_(K+q) is first multiplied by the item's c_(m,q).
+template <bool SCALED>
 __global__ __launch_bounds__(256) void quad_chain_kernel(QuadArgs args) {
     const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= args.total) return;
@@ -37,13 +50,21 @@ __global__ __launch_bounds__(256) void quad_chain_kernel(QuadArgs args) {
     const double* ctl_b = args.controls + b * args.nc * K;
     const StepInterp si = args.interp[step];
     // cotangent of effective control e
-    auto ge = [&](int e) -> double {
+    auto ge_plain = [&](int e) -> double {
         if (args.lam_scale != nullptr) {  // unit adjoint: Re(conj(c) gamma), as scatter_kernel
             const double2 c = args.lam_scale[b * args.S];
             const double* g = args.gstep + (w * Ke + e) * 2;
             return fma(c.y, g[1], c.x * g[0]);
         }
         return args.gstep[w * Ke + e];
+    };
+    const double* cm = nullptr;
+    (void)cm;
+    if constexpr (SCALED) cm = args.term_scales + ((args.item0 + b) % (size_t)args.M) * (size_t)args.count;
+    auto ge = [&](int e) -> double {
+        if constexpr (SCALED)
+            if (e >= K) return cm[e - K] * ge_plain(e);
+        return ge_plain(e);
     };
     double* out = args.greal + w * K;
     for (int k = 0; k < K; ++k) {
@@ -59,10 +80,18 @@ __global__ __launch_bounds__(256) void quad_chain_kernel(QuadArgs args) {
 }
 
 void launch_quad_controls(const QuadArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(quad_controls_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
+    if (a.term_scales != nullptr) {
+        hipLaunchKernelGGL(quad_controls_kernel<true>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
+        return;
+    }
+    hipLaunchKernelGGL(quad_controls_kernel<false>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
 }
 void launch_quad_chain(const QuadArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(quad_chain_kernel, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
+    if (a.term_scales != nullptr) {
+        hipLaunchKernelGGL(quad_chain_kernel<true>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
+        return;
+    }
+    hipLaunchKernelGGL(quad_chain_kernel<false>, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, st, a);
 }
 
 }  // namespace qocx

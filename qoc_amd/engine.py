@@ -135,6 +135,7 @@ SIGNATURES = {
     "qocx_set_quadratic_terms": (ctypes.c_int, [_VP, _I32, _c_int_p, _c_double_p]),
     "qocx_set_ensemble": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p, _c_double_p]),
     "qocx_ensemble_download_members": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_set_ensemble_quadratic_scales": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_set_keep_step_states": (ctypes.c_int, [_VP, _I32]),
     "qocx_download_step_states": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_lindblad_problem": (ctypes.c_int, [_VP, ctypes.POINTER(_LindbladProblem)]),
@@ -268,6 +269,7 @@ class Engine(object):
         self._check(self._lib.qocx_create(int(device), ctypes.byref(self._ctx)))
         self._problem = None
         self._ensemble = None
+        self._quadratic_count = 0
         self._keepalive = []
         self.batch = 0
 
@@ -338,6 +340,7 @@ class Engine(object):
         self._check(self._lib.qocx_set_schroedinger_problem(self._ctx, ctypes.byref(p)))
         self._problem = dict(n=n, S=S, K=K, Nc=int(control_eval_count), N=int(system_eval_count))
         self._ensemble = None
+        self._quadratic_count = 0
         self.batch = 0
 
     def set_quadratic_terms(self, pairs, matrices):
@@ -350,6 +353,7 @@ class Engine(object):
         mats = _as_complex(matrices if count else np.zeros((0, n, n)), (count, n, n))
         self._check(self._lib.qocx_set_quadratic_terms(
             self._ctx, count, pairs.ctypes.data_as(_c_int_p), _dp(mats)))
+        self._quadratic_count = count
         self.batch = 0
 
     def set_ensemble(self, scales, offsets, weights):
@@ -369,6 +373,22 @@ class Engine(object):
             self._ctx, M, J, none if sc is None else _dp(sc), none if off is None else _dp(off),
             _dp(weights)))
         self._ensemble = dict(M=M, J=J, Kr=kr)
+        self.batch = 0
+
+    def set_ensemble_quadratic_scales(self, scales):
+        """c_mq of an ensemble with quadratic terms (qocx_set_ensemble_quadratic_scales): scales ::
+        (M, count) real, member m's factor of term q; None clears them (all 1). Both set_ensemble
+        and set_quadratic_terms come first. Controls must be uploaded again afterwards."""
+        M = 0 if self._ensemble is None else self._ensemble["M"]
+        if scales is None:
+            self._check(self._lib.qocx_set_ensemble_quadratic_scales(
+                self._ctx, M, self._quadratic_count, ctypes.cast(None, _c_double_p)))
+        else:
+            sc = np.ascontiguousarray(scales, dtype=np.float64)
+            if sc.ndim != 2:
+                raise ValueError("scales must be (M, count), got shape {}".format(sc.shape))
+            self._check(self._lib.qocx_set_ensemble_quadratic_scales(
+                self._ctx, sc.shape[0], sc.shape[1], _dp(sc)))
         self.batch = 0
 
     def ensemble_member_costs(self):

@@ -11,10 +11,12 @@ problem linear in the effective controls (r_k, r_k r_l) - no call of the callabl
 per evaluation (qocx_set_quadratic_terms). The Piccolo Hamiltonian of the reference's report
 (report.tex:22-32, an AC-Stark term in epsilon_sb^2) has this form.
 
-HamiltonianEnsemble is NOT a callable: it is M copies of a linear Hamiltonian with scaled controls
-and fixed perturbation terms, all driven by the same controls (robust GRAPE). The Schroedinger
-evaluator sets it up as one structured problem whose extra control channels are the perturbation
-matrices, and the engine expands every seed into its M members on the device (qocx_set_ensemble).
+HamiltonianEnsemble is NOT a callable: it is M copies of a linear or quadratic Hamiltonian with
+scaled controls and fixed perturbation terms, all driven by the same controls (robust GRAPE). The
+Schroedinger evaluator sets it up as one structured problem whose extra control channels are the
+perturbation matrices, and the engine expands every seed into its M members on the device
+(qocx_set_ensemble). A QuadraticHamiltonian base keeps its terms on the device as well, each
+optionally scaled per member (quadratic_scales, qocx_set_ensemble_quadratic_scales).
 """
 
 import numbers
@@ -125,21 +127,30 @@ def _real_array(value, name, ndim):
 class HamiltonianEnsemble(object):
     """
     E = HamiltonianEnsemble(hamiltonian, perturbations=None, offsets=None, control_scales=None,
-                            weights=None)
+                            weights=None, quadratic_scales=None)
 
     M copies of a system, all driven by the same controls (robust GRAPE). Member m is
 
         H_m(u, t) = hamiltonian(s_m * u, t) + sum_j offsets[m, j] D_j
 
+    and, for a QuadraticHamiltonian base with real channels r of u and terms (k_q, l_q, Q_q),
+
+        H_m(u, t) = linear(s_m * u, t) + sum_j offsets[m, j] D_j
+                    + sum_q quadratic_scales[m, q] (s_m,kq r_kq) (s_m,lq r_lq) Q_q
+
     hamiltonian :: (controls, time) -> (n x n), real-linear in the controls (time dependence
-        allowed).
+        allowed), or a QuadraticHamiltonian (MagnusPolicy.M2).
     perturbations :: (J, n, n) complex - the fixed matrices D_j (detuning, crosstalk, ...).
     offsets :: (M, J) real - delta_mj; given exactly when perturbations are.
     control_scales :: (M, control_count) real - s_mk (amplitude errors); a complex control's
         scale multiplies its real and imaginary parts alike. Default: all 1.
     weights :: (M,) real >= 0 - w_m; default 1 / M.
+    quadratic_scales :: (M, Q) real - c_mq, member m's factor of the base's q-th merged quadratic
+        term, in the order of hamiltonian.pairs (an uncertain Stark coefficient). Only for a
+        QuadraticHamiltonian base with Q terms. Default: all 1.
 
-    M is read from whichever of offsets, control_scales and weights is given; they must agree.
+    M is read from whichever of offsets, control_scales, weights and quadratic_scales is given; they
+    must agree.
     Passed as the `hamiltonian` of evolve_schroedinger_discrete, grape_schroedinger_discrete or
     grape_schroedinger_discrete_batch, the cost is sum_m w_m c_m over the members' device costs
     (costs of the controls alone are added once), and the gradient is that of this sum. The
@@ -147,7 +158,7 @@ class HamiltonianEnsemble(object):
     """
 
     def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
-                 weights=None):
+                 weights=None, quadratic_scales=None):
         if not callable(hamiltonian):
             raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
         counts = {}
@@ -176,11 +187,21 @@ class HamiltonianEnsemble(object):
             if np.any(weights < 0):
                 raise ValueError("weights must be >= 0")
             counts["weights"] = weights.shape[0]
+        if quadratic_scales is not None:
+            if not isinstance(hamiltonian, QuadraticHamiltonian):
+                raise ValueError("quadratic_scales need a QuadraticHamiltonian base, got {!r}"
+                                 "".format(hamiltonian))
+            quadratic_scales = _real_array(quadratic_scales, "quadratic_scales", 2)
+            if quadratic_scales.shape[1] != len(hamiltonian.pairs):
+                raise ValueError("quadratic_scales must be (M, Q) with Q = {} quadratic terms, got "
+                                 "shape {}".format(len(hamiltonian.pairs), quadratic_scales.shape))
+            counts["quadratic_scales"] = quadratic_scales.shape[0]
         if not counts:
             raise ValueError("an ensemble needs offsets, control_scales or weights (M is read "
                              "from them)")
         if len(set(counts.values())) > 1:
-            raise ValueError("offsets, control_scales and weights disagree on the member count: {}"
+            raise ValueError("offsets, control_scales, weights and quadratic_scales disagree on "
+                             "the member count: {}"
                              "".format(", ".join("{} {}".format(k, v) for k, v in counts.items())))
         M = next(iter(counts.values()))
         if M == 0:
@@ -191,6 +212,7 @@ class HamiltonianEnsemble(object):
         self.offsets = offsets
         self.control_scales = control_scales
         self.weights = weights if weights is not None else np.full(M, 1.0 / M)
+        self.quadratic_scales = quadratic_scales
         self.member_count = M
 
     @property
@@ -229,12 +251,34 @@ class HamiltonianEnsemble(object):
             shift = np.einsum("j,jab->ab", self.offsets[m].astype(np.complex128),
                               self.perturbations)
 
+        quadratic = isinstance(base, QuadraticHamiltonian) and len(base.pairs) > 0
+        term_scales = None if self.quadratic_scales is None else self.quadratic_scales[m]
+
         def hamiltonian(controls, time):
             u = controls
             if scales is not None and controls is not None:
                 u = np.asarray(controls) * scales
-            out = np.asarray(base(u, time), dtype=np.complex128)
-            return out if shift is None else out + shift
+            if not quadratic:
+                out = np.asarray(base(u, time), dtype=np.complex128)
+                return out if shift is None else out + shift
+            # a quadratic base: its linear part on the scaled controls, and the terms here -
+            # c_mq (s r)_k (s r)_l Q_q in the real channels r of the controls
+            out = np.asarray(base.linear_hamiltonian(u, time), dtype=np.complex128)
+            if shift is not None:
+                out = out + shift
+            if u is None:
+                raise ValueError("a QuadraticHamiltonian with quadratic terms needs controls")
+            u = np.asarray(u)
+            if np.iscomplexobj(u):
+                r = np.empty(2 * u.shape[-1])
+                r[0::2], r[1::2] = u.real, u.imag
+            else:
+                r = np.asarray(u, dtype=np.float64)
+            base.check_real_control_count(r.shape[0])
+            for q, ((k, l), mat) in enumerate(zip(base.pairs, base.matrices)):
+                c = 1.0 if term_scales is None else term_scales[q]
+                out = out + (c * (r[k] * r[l])) * mat
+            return out
         return hamiltonian
 
     def __repr__(self):
