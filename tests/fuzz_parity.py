@@ -5,7 +5,11 @@ counts / time steps (so that 0..4 squarings occur), all three Magnus policies, H
 non-Hermitian generators, all state-cost kinds at once. With shapes=True (fuzz_parity.one) each
 seed of a draw gets a pulse family of tests/mixed_pulses.py (quiet, bell, spike, square, ramp,
 loud) and an amplitude of its own instead of one shared Gaussian scale, so that the steps of one
-upload differ in Pade order, squaring count and pivoting regime.
+upload differ in Pade order, squaring count and pivoting regime. With drive=True the drive operators
+depend on time as well, G_k(t) = cos(w_k t + k) G_k + sin(w_k t) G'_k with w_k dt in 0.5 .. 1.0 (the
+rotating drives of tests/time_dependent_drive.py), and every draw is time dependent; what that adds is
+drawn from a generator of its own, seeded by `index`, so the draws of the shared stream - and with
+them every problem of the tests that leave drive at False - stay what they are.
 
     python -m tests.fuzz_parity [count] [seed] [nmin] [nmax] [smin] [smax]
 """
@@ -26,7 +30,7 @@ NODES = {"M2": (0.5,), "M4": (0.5 - 3 ** 0.5 / 6, 0.5 + 3 ** 0.5 / 6),
          "M6": (0.5 - 15 ** 0.5 / 10, 0.5, 0.5 + 15 ** 0.5 / 10)}
 
 
-def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shapes=False):
+def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shapes=False, drive=False):
     n = int(rng.integers(nmin, nmax + 1))
     N = int(rng.integers(2, 14))
     K = int(rng.integers(1, 4))
@@ -45,10 +49,23 @@ def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shape
         g[0] = g[0] + 0.2j * gue(rng, n)
     omega = float(rng.uniform(0.5, 4.0))
     T = dt * (N - 1)
+    if drive:
+        time_dep = True
+        own = np.random.default_rng([index, 0x6472697665])
+        g_sin = [gue(own, n) for _ in range(K)]
+        if not hermitian:
+            g_sin[0] = g_sin[0] + 0.2j * gue(own, n)
+        g_omega = np.sort(own.uniform(0.5, 1.0, K)) / dt
+
+    def g_at(t):
+        if not drive:
+            return g
+        return [np.cos(g_omega[k] * t + k) * g[k] + np.sin(g_omega[k] * t) * g_sin[k] for k in range(K)]
 
     def hamiltonian(u, t):
         base = h0 * (1 + 0.3 * np.cos(omega * t)) if time_dep else h0
-        return base + sum(u[k] * g[k] for k in range(K))
+        gt = g_at(t)
+        return base + sum(u[k] * gt[k] for k in range(K))
 
     init = rng.standard_normal((S, n)) + 1j * rng.standard_normal((S, n))
     init /= np.linalg.norm(init, axis=1, keepdims=True)
@@ -70,13 +87,15 @@ def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shape
     if time_dep:
         times = [j * dt + c * dt for j in range(N - 1) for c in NODES[policy]]
         h0s = np.stack([h0 * (1 + 0.3 * np.cos(omega * t)) for t in times])
-        gs = np.stack([np.stack(g) for _ in times])
+        gs = np.stack([np.stack(g_at(t)).reshape(K, n, n) for t in times])
     else:
         h0s, gs = h0[None], np.stack(g)[None]
     engine.set_schroedinger_problem(n, S, K, Nc, N, T, h0s, gs, init, costs=descs,
                                     cost_eval_step=ces, magnus_policy=policy)
     tag = "n={} N={} Nc={} K={} S={} ces={} {} herm={} tdep={} dt={:.3g} |H|={:.3g}".format(
         n, N, Nc, K, S, ces, policy, hermitian, time_dep, dt, scale)
+    if drive:
+        tag += " drive w dt=" + ",".join("{:.2f}".format(w * dt) for w in g_omega)
     if shapes:
         # (peak amplitude three times the Gaussian scale of the default draw: its 3 sigma)
         picks = [(FAMILIES[int(rng.integers(0, len(FAMILIES)))], 3 * float(10 ** rng.uniform(-1, 0.5)))

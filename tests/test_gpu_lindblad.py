@@ -355,6 +355,22 @@ def test_lindblad_tile_kernel_time_dependent_tables(engine):
         assert np.max(np.abs(a - b)) < 1e-12 * max(1.0, np.max(np.abs(b)))
     assert np.max(np.abs(out[0][1])) > 1e-7
     assert np.max(np.abs(out[1][1] - out[0][1])) < 1e-9 * np.max(np.abs(out[0][1]))
+    # ... and both against the model of the device algorithm on the callables the tables sample
+    # (tolerances of test_lindblad_edge_shapes_against_model)
+    system = lm.StructuredLindblad(
+        h_a, g_a, gam, o_a, h0_of_t=lambda t: h_a + np.cos(1.3 * t) * h_b,
+        g_of_t=lambda t: [g_a[k] + np.sin(0.7 * t + k) * g_b[k] for k in range(K)],
+        data_of_t=lambda t: (gam * (1.0 + 0.3 * np.cos(t)), o_a + np.sin(0.9 * t) * o_b))
+    costs = [ol.TargetDensityInfidelity(targ, cost_multiplier=0.8),
+             ol.ForbidDensities(forb.reshape(S, 2, n, n), N, cost_multiplier=0.1 * (N - 1) * S)]
+    for b in range(3):
+        m_err, m_grads, m_final = lm.evaluate_with_grad(system, controls[b], rho0, T, N, costs, 1,
+                                                        want_grad=True, subdivision=ksub)
+        for knob in (1, 0):
+            cost, grads, final = out[knob]
+            assert abs(cost[b] - m_err) < 1e-12
+            assert np.max(np.abs(final[b] - m_final)) < 1e-12
+            assert np.max(np.abs(grads[b] - m_grads)) < 1e-10 * max(np.max(np.abs(m_grads)), 1e-3)
 
 
 def test_lindblad_tile_kernel_recompute_and_host_cotangents(engine):
