@@ -17,6 +17,7 @@ import numpy as np
 
 from qoc_amd.core import structure
 from qoc_amd.core.common import initialize_controls, strip_controls
+from qoc_amd.engine import PATH_LINDBLAD
 from qoc_amd.models import Dummy
 from qoc_amd.standard.optimizers import LBFGS, SGD, Adam
 
@@ -324,24 +325,33 @@ def _finish(result, comm):
 
 
 class ResidentOps(object):
-    """One path's resident driver of the engine as run_batch_resident calls it. `calls` are the
-    engine's bound methods of that path under the loop's names: upload_controls, opt_begin (the
-    complex one for complex controls), opt_clip, eval_resident, download_costs, opt_step,
-    opt_download_best, and for LBFGS opt_lbfgs_begin, opt_lbfgs_step.
+    """One path's resident driver of the engine as run_batch_resident calls it: the engine's bound
+    methods of `path` under the loop's names upload_controls, opt_begin (the complex one for
+    complex controls), opt_clip, eval_resident, download_costs, opt_step, opt_download_best, and
+    for LBFGS opt_lbfgs_begin, opt_lbfgs_step (None on a backend without them). PATH_SCHROEDINGER
+    has them under these names, PATH_LINDBLAD behind `lindblad_`.
     control_costs: the descriptors of the costs of the controls alone, which the engine then adds
     to every resident evaluation of `path` until finish(); complex_controls: the loop's complex
-    arrays travel as two real channels per control and the engine clips a copy of the parameters;
-    column_states: the final states come back as columns ([B, S, n, 1], Schroedinger)."""
+    arrays travel as two real channels per control and the engine clips a copy of the parameters.
+    The Schroedinger path's final states come back as columns ([B, S, n, 1])."""
 
-    def __init__(self, engine, path, control_costs, complex_controls, column_states=False, **calls):
+    def __init__(self, engine, path, control_costs=(), complex_controls=False):
         self.engine = engine
         self.path = path
         self.control_costs = list(control_costs)
         self.complex_controls = complex_controls
-        self.column_states = column_states
-        self._upload_controls = calls.pop("upload_controls")
-        self._opt_download_best = calls.pop("opt_download_best")
-        self.__dict__.update(calls)  # opt_begin, opt_clip, eval_resident, download_costs, opt_step
+        lindblad = path == PATH_LINDBLAD
+        self.column_states = not lindblad
+        prefix = "lindblad_" if lindblad else ""
+        self._upload_controls = getattr(engine, prefix + "upload_controls")
+        self._opt_download_best = getattr(engine, prefix + "opt_download_best")
+        self.opt_begin = getattr(engine, prefix + ("opt_begin_complex" if complex_controls
+                                                   else "opt_begin"))
+        self.eval_resident = engine.eval_lindblad_resident if lindblad else engine.eval_resident
+        for name in ("opt_clip", "download_costs", "opt_step"):
+            setattr(self, name, getattr(engine, prefix + name))
+        for name in ("opt_lbfgs_begin", "opt_lbfgs_step"):
+            setattr(self, name, getattr(engine, prefix + name, None))
 
     def upload_controls(self, controls):
         if self.control_costs:

@@ -101,3 +101,13 @@ def strip_controls(complex_controls, controls):
     if complex_controls:
         controls = np.hstack((np.real(controls), np.imag(controls)))
     return controls
+
+
+def _cost_format(flat_controls, pstate):
+    """optimizer format -> clipped, conditioned cost-function format of the single-seed GRAPE
+    drivers (schroedingerdiscrete.py:308-315, lindbladdiscrete.py:272-280)."""
+    controls = slap_controls(pstate.complex_controls, flat_controls, pstate.controls_shape)
+    clip_control_norms(controls, pstate.max_control_norms)  # in place, aliases real params
+    if pstate.impose_control_conditions is not None:
+        controls = pstate.impose_control_conditions(controls)
+    return controls

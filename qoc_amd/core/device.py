@@ -99,7 +99,217 @@ def user_controls_bar(cost, controls, states, step):
     return out
 
 
-class SchroedingerEvaluator(object):
+class _Evaluator(object):
+    """
+    What the Schroedinger and the Lindblad evaluator share: cost triage, the batch protocol of
+    evaluate_batch (one or two device passes, step states kept for exactly as long as they are
+    needed), the host's share of the costs and the resident-capability test. "States" are state
+    vectors or densities. A subclass probes and sets its problem and supplies
+      _pass(controls_batch, device_controls, want_grad, again) -> (cost, grads, final),
+      _download_steps(), _set_cotangents(steps, bars), _problem_stays_resident(),
+      _set_linearized_problem(controls, device_controls),
+    and the class attributes below.
+    """
+
+    opt_prefix = ""           # of the backend's resident-driver methods (opt_step, ...)
+    subtotal_costs = True     # the order in which evaluate_batch sums the host's costs (see there)
+    linearized_route = ""     # names the linearised route in an error message
+    linearized_hamiltonian = None
+    _cost_controls = None     # controls the costs see in place of the evaluated ones
+
+    def _triage_costs(self, item_count):
+        """Splits self.costs into device_costs (they have a device_descriptor(); returns those
+        descriptors), host_costs (of the controls alone) and opaque_costs (user costs of the
+        states, evaluated on the host)."""
+        self.device_costs, self.host_costs, self.opaque_costs = [], [], []
+        descriptors = []
+        for cost in self.costs:
+            desc = cost.device_descriptor(item_count, self.hilbert_size) \
+                if hasattr(cost, "device_descriptor") else None
+            if desc is not None:
+                self.device_costs.append(cost)
+                descriptors.append(desc)
+            elif (getattr(cost, "uses_states", True) is False
+                  and not cost.requires_step_evaluation):
+                self.host_costs.append(cost)
+            else:
+                self.opaque_costs.append(cost)
+        # the same costs as the resident multi-start driver hands them to the engine
+        self.control_cost_descriptors = control_cost_descriptors(
+            self.host_costs, self.control_count, self.control_eval_count, self.complex_controls)
+        return descriptors
+
+    def resident_capable(self):
+        """True when a multi-start driver may keep controls and optimizer states on the device
+        (engine.opt_* / engine.lindblad_opt_*): a problem the device holds in structured form
+        (_problem_stays_resident), every cost evaluated on the device - the built-in costs of the
+        controls alone included, through their control_descriptor() -, and a backend that has the
+        entry points (the real engine; complex controls need its complex clip)."""
+        return (self.linearized_hamiltonian is None and self._problem_stays_resident()
+                and self.control_count > 0 and not self.opaque_costs
+                and hasattr(self.backend, self.opt_prefix + "opt_step")
+                and controls_stay_resident(self.backend, self.control_cost_descriptors,
+                                           self.complex_controls,
+                                           self.opt_prefix + "opt_begin_complex"))
+
+    def resident_lbfgs_capable(self):
+        """resident_capable() with a backend that also has the L-BFGS calls of the resident driver."""
+        return self.resident_capable() and hasattr(self.backend, self.opt_prefix + "opt_lbfgs_step")
+
+    def _prepare(self, device_controls):
+        """Before the first pass of an evaluation (the Lindblad time tables)."""
+
+    def _kept_pass(self, controls_batch, device_controls, want_grad, need_steps):
+        """One pass -> (cost, grads, final, step states or None); the backend keeps step states
+        during it when they are needed, and never after it (an engine error included)."""
+        if need_steps:
+            self.backend.set_keep_step_states(True)
+        try:
+            cost, grads, final = self._pass(controls_batch, device_controls, want_grad)
+            return cost, grads, final, self._download_steps() if need_steps else None
+        finally:
+            if need_steps:
+                self.backend.set_keep_step_states(False)
+
+    def _evaluate_linearized(self, controls_batch, device_controls, want_grad, need_steps):
+        """One control array at a time: the tangent problem of the callable at THAT array, set as
+        a structured time-dependent problem (_set_linearized_problem) and evaluated at it - the
+        route of callables that are not linear in the controls, which the reference evaluates one
+        control array at a time as well. The backend is left holding the tangent problem of the
+        LAST array."""
+        outs = []
+        for b in range(controls_batch.shape[0]):
+            self._set_linearized_problem(controls_batch[b], device_controls[b])
+            out = self._kept_pass(controls_batch[b:b + 1], device_controls[b:b + 1], want_grad,
+                                  need_steps)
+            outs.append([None if x is None else x[0] for x in out])
+        costs, grads, finals, steps = zip(*outs)
+        return (np.array(costs), np.stack(grads) if want_grad else None, np.stack(finals),
+                np.stack(steps) if need_steps else None)
+
+    def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
+        """
+        controls_batch :: (B x Nc x K) (or None / an int B when control_count == 0).
+        Returns (errors[B], grads[B x Nc x K] or None, final states, step states or None): final
+        states [B x S x n x 1] and step states [B x N x S x n x 1] on the Schroedinger path (with
+        an ensemble a member axis M follows B), densities [B x S x n x n] and [B x N x S x n x n]
+        on the Lindblad path.
+        """
+        if self.control_count == 0:
+            batch = 1 if controls_batch is None else int(controls_batch)
+            want_grad = False
+            device_controls = batch
+        else:
+            controls_batch = np.asarray(controls_batch)
+            batch = controls_batch.shape[0]
+            device_controls = structure.to_real_controls(controls_batch, self.complex_controls)
+        self._prepare(device_controls)
+        need_steps = want_step_states or bool(self.opaque_costs)
+        two_pass = want_grad and bool(self.opaque_costs)
+        if self.linearized_hamiltonian is not None:
+            if two_pass:
+                raise NotImplementedError(
+                    "user costs without a device descriptor together with a hamiltonian that is "
+                    "not linear in the controls " + self.linearized_route)
+            run = self._evaluate_linearized
+        else:
+            run = self._kept_pass
+        cost, grads, final, step_states = run(controls_batch, device_controls,
+                                              want_grad and not two_pass, need_steps)
+        opaque_grads = None
+        if two_pass:
+            # User costs without a device descriptor: the host supplies the cotangent of the
+            # states at every cost step (the cost's own states_bar() hook, else central
+            # differences of its cost()), the engine's adjoint sweep carries it back.
+            steps, bars, opaque_grads = self._opaque_cotangents(controls_batch, step_states)
+            self._set_cotangents(steps, bars)
+            try:
+                cost, grads, final = self._pass(controls_batch, device_controls, True, again=True)
+            finally:
+                self._set_cotangents(None, None)
+        errors = np.array(cost, dtype=np.float64)
+        if grads is not None:
+            grads = structure.from_real_gradients(grads, self.complex_controls)
+            if not self.complex_controls:
+                grads = np.array(grads, dtype=np.float64)
+            if opaque_grads is not None:
+                grads = grads + (opaque_grads if self.complex_controls
+                                 else np.real(opaque_grads))
+        # The host's share of the costs: those of the controls alone, then the user's cost() at its
+        # steps. The two paths round differently and each keeps its order: with subtotal_costs the
+        # host costs are summed from 0.0 and each user cost over its steps from 0.0 before they
+        # join errors[b] / grads[b]; without, every term is added to errors[b] / grads[b] in turn.
+        for b in range(batch):
+            controls = None if self.control_count == 0 else controls_batch[b]
+            if self._cost_controls is not None:
+                controls = self._cost_controls
+            if self.subtotal_costs:
+                value, host_grad = self._add_host_costs(0.0, None, controls, want_grad)
+                errors[b] += value
+                if host_grad is not None:
+                    grads[b] = grads[b] + host_grad
+                for cost in self.opaque_costs:
+                    errors[b] += self._add_user_cost(0.0, cost, controls, step_states[b])
+            else:
+                errors[b], host_grad = self._add_host_costs(
+                    errors[b], grads[b] if want_grad else None, controls, want_grad)
+                if host_grad is not None:
+                    grads[b] = host_grad
+                for cost in self.opaque_costs:
+                    errors[b] = self._add_user_cost(errors[b], cost, controls, step_states[b])
+        return errors, grads, final, step_states
+
+    def _add_host_costs(self, value, grad, controls, want_grad):
+        """(value + c_1 + c_2 + ..., grad + bar_1 + bar_2 + ...) over the costs of the controls
+        alone, left to right; grad = None starts the second sum at bar_1."""
+        for cost in self.host_costs:
+            value = value + cost.cost(controls, None, self.final_system_eval_step)
+            if want_grad:
+                bar = cost.controls_bar(controls, None, self.final_system_eval_step)
+                if bar is None:
+                    raise NotImplementedError("cost {} has no controls_bar()".format(cost))
+                grad = bar if grad is None else grad + bar
+        return value, grad
+
+    def _add_user_cost(self, value, cost, controls, states_by_step):
+        """value + the user's cost() at each of its steps, in step order."""
+        for step in self._cost_steps(cost):
+            value = value + cost.cost(controls, states_by_step[step], step)
+        return value
+
+    def _cost_steps(self, cost):
+        if not cost.requires_step_evaluation:
+            return [self.final_system_eval_step]
+        return list(range(self.cost_eval_step, self.system_eval_count, self.cost_eval_step))
+
+    def _opaque_cotangents(self, controls_batch, step_states):
+        """(steps, bars[B, len(steps)] + cotangent_shape, control_grads[B, Nc, K] complex) of the
+        user costs."""
+        steps = sorted({st for c in self.opaque_costs for st in self._cost_steps(c)})
+        row = {st: r for r, st in enumerate(steps)}
+        batch = controls_batch.shape[0]
+        bars = np.zeros((batch, len(steps)) + self.cotangent_shape, dtype=np.complex128)
+        cgrads = np.zeros(controls_batch.shape, dtype=np.complex128)
+        for b in range(batch):
+            for cost in self.opaque_costs:
+                for st in self._cost_steps(cost):
+                    states = step_states[b][st]
+                    bars[b, row[st]] += user_states_bar(
+                        cost, controls_batch[b], states, st).reshape(self.cotangent_shape)
+                    cgrads[b] += user_controls_bar(cost, controls_batch[b], states, st)
+        return steps, bars, cgrads
+
+    def evaluate(self, controls, want_grad=True, want_step_states=False):
+        """Single control array, the reference's calling convention."""
+        batch = None if controls is None else np.asarray(controls)[None]
+        errors, grads, final, steps = self.evaluate_batch(batch, want_grad, want_step_states)
+        return (float(errors[0]), None if grads is None else grads[0], final[0],
+                None if steps is None else steps[0])
+
+
+class SchroedingerEvaluator(_Evaluator):
+    linearized_route = "under MagnusPolicy.M4 / M6"
+
     def __init__(self, evolution_time, hamiltonian, initial_states, system_eval_count,
                  control_count=0, control_eval_count=0, complex_controls=False, costs=(),
                  cost_eval_step=1, interpolation_policy=InterpolationPolicy.LINEAR,
@@ -125,6 +335,7 @@ class SchroedingerEvaluator(object):
         initial_states = np.asarray(initial_states)
         self.state_count = initial_states.shape[0]
         self.hilbert_size = initial_states.shape[1]
+        self.cotangent_shape = (self.state_count, self.hilbert_size)
         self.control_count = control_count
         self.control_eval_count = control_eval_count
         self.complex_controls = complex_controls
@@ -198,22 +409,7 @@ class SchroedingerEvaluator(object):
                 self._rows = structure.interpolation_rows(evolution_time, control_eval_count, times)
                 h0 = np.zeros((1, self.hilbert_size, self.hilbert_size), dtype=np.complex128)
                 g = None
-        self.device_costs, self.host_costs, self.opaque_costs = [], [], []
-        descriptors = []
-        for cost in self.costs:
-            desc = cost.device_descriptor(self.state_count, self.hilbert_size) \
-                if hasattr(cost, "device_descriptor") else None
-            if desc is not None:
-                self.device_costs.append(cost)
-                descriptors.append(desc)
-            elif (getattr(cost, "uses_states", True) is False
-                  and not cost.requires_step_evaluation):
-                self.host_costs.append(cost)
-            else:
-                self.opaque_costs.append(cost)
-        # the same costs as the resident multi-start driver hands them to the engine
-        self.control_cost_descriptors = control_cost_descriptors(
-            self.host_costs, control_count, control_eval_count, complex_controls)
+        descriptors = self._triage_costs(self.state_count)
         if self.ensemble is not None:
             if self.opaque_costs:
                 raise NotImplementedError(
@@ -320,172 +516,42 @@ class SchroedingerEvaluator(object):
                 if self.complex_controls else grads
         return cost, grads, final
 
-    def _evaluate_linearized(self, controls_batch, device_controls, want_grad, need_steps):
-        """One control array at a time: the tangent problem of the callable at THAT array (node
-        times of the Magnus policy), set as a structured time-dependent problem, evaluated at it.
-        Host cost per array: (4 K + 1) evaluations of the callable per node time for the tangent, one
-        re-upload of the nsteps x nodes x (1 + K) tables and a one-seed evaluation - the route of
-        callables that are not linear in the controls, which the reference evaluates one control
-        array at a time as well. The backend is left holding the tangent problem of the LAST array."""
-        costs, grads, finals, steps = [], [], [], []
-        for b in range(controls_batch.shape[0]):
-            h0, g = structure.linearize_hamiltonian(
-                self.linearized_hamiltonian, controls_batch[b], self._evolution_time,
-                self._node_times, self.hilbert_size, self.complex_controls)
-            self._set_problem(h0, g)
-            if need_steps:
-                self.backend.set_keep_step_states(True)
-            try:
-                self.backend.upload_controls(device_controls[b:b + 1])
-                self.backend.eval_resident(want_grad)
-                c, gr, f = self.backend.download_results(want_grad=want_grad)
-                costs.append(c[0])
-                finals.append(f[0])
-                if want_grad:
-                    grads.append(gr[0])
-                if need_steps:
-                    steps.append(self.backend.download_step_states()[0])
-            finally:  # (an engine error must not leave step-state keeping on)
-                if need_steps:
-                    self.backend.set_keep_step_states(False)
-        return (np.array(costs), np.stack(grads) if want_grad else None, np.stack(finals),
-                np.stack(steps)[..., None] if need_steps else None)
+    def _set_linearized_problem(self, controls, device_controls):
+        """The tangent of the callable at `controls` on the node times of the Magnus policy. Host
+        cost per array: (4 K + 1) evaluations of the callable per node time, one re-upload of the
+        nsteps x nodes x (1 + K) tables and a one-seed evaluation."""
+        self._set_problem(*structure.linearize_hamiltonian(
+            self.linearized_hamiltonian, controls, self._evolution_time, self._node_times,
+            self.hilbert_size, self.complex_controls))
 
-    def _host_terms(self, controls, want_grad):
-        value, grad = 0.0, None
-        for cost in self.host_costs:
-            value = value + cost.cost(controls, None, self.final_system_eval_step)
-            if want_grad:
-                bar = cost.controls_bar(controls, None, self.final_system_eval_step)
-                if bar is None:
-                    raise NotImplementedError("cost {} has no controls_bar()".format(cost))
-                grad = bar if grad is None else grad + bar
-        return value, grad
-
-    def resident_capable(self):
-        """True when a multi-start driver may keep controls and optimizer states on the device
-        (engine.opt_*): structured Hamiltonian, every cost evaluated on the device - the built-in
-        costs of the controls alone included, through their control_descriptor() -, and a backend
-        that has the entry points (the real engine; complex controls need its complex clip)."""
-        return (self.opaque_hamiltonian is None and self.linearized_hamiltonian is None
-                and self.control_count > 0 and not self.opaque_costs
-                and hasattr(self.backend, "opt_step")
-                and controls_stay_resident(self.backend, self.control_cost_descriptors,
-                                           self.complex_controls, "opt_begin_complex"))
-
-    def resident_lbfgs_capable(self):
-        """resident_capable() with a backend that also has the L-BFGS calls of the resident driver."""
-        return self.resident_capable() and hasattr(self.backend, "opt_lbfgs_step")
-
-    def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
-        """
-        controls_batch :: (B x Nc x K) (or None / an int B when control_count == 0).
-        Returns (errors[B], grads[B x Nc x K] or None, final_states[B x S x n x 1], step_states);
-        with an ensemble the final states are [B x M x S x n x 1] and the step states, if asked
-        for, [B x M x N x S x n x 1].
-        """
-        if self.control_count == 0:
-            batch = 1 if controls_batch is None else int(controls_batch)
-            want_grad = False
-            device_controls = batch
-        else:
-            controls_batch = np.asarray(controls_batch)
-            batch = controls_batch.shape[0]
-            device_controls = structure.to_real_controls(controls_batch, self.complex_controls)
-        need_steps = want_step_states or bool(self.opaque_costs)
-        two_pass = want_grad and bool(self.opaque_costs)
-        if self.linearized_hamiltonian is not None:
-            if two_pass:
-                raise NotImplementedError(
-                    "user costs without a device descriptor together with a hamiltonian that is "
-                    "not linear in the controls under MagnusPolicy.M4 / M6")
-            cost, grads, final, step_states = self._evaluate_linearized(
-                controls_batch, device_controls, want_grad, need_steps)
-        else:
-            if need_steps:
-                self.backend.set_keep_step_states(True)
+    def _pass(self, controls_batch, device_controls, want_grad, again=False):
+        """again: the second pass of one evaluation, the backend still holds the controls."""
+        if not again:
             self._upload(controls_batch, device_controls)
-            self.backend.eval_resident(want_grad and not two_pass)
-            cost, grads, final = self._download(controls_batch, want_grad and not two_pass)
-            step_states = None
-            if need_steps:
-                step_states = self.backend.download_step_states()[..., None]
-                self.backend.set_keep_step_states(False)
-        opaque_grads = None
-        if two_pass:
-            # User costs without a device descriptor: the host supplies the cotangent of the
-            # states at every cost step (the cost's own states_bar() hook, else central
-            # differences of its cost()), the engine's adjoint sweep carries it back.
-            steps, bars, opaque_grads = self._opaque_cotangents(controls_batch, step_states)
-            self.backend.set_state_cotangents(steps, bars)
-            try:
-                self.backend.eval_resident(True)
-                cost, grads, final = self._download(controls_batch, True)
-            finally:
-                self.backend.set_state_cotangents(None, None)
-        errors = np.array(cost, dtype=np.float64)
-        final = final[..., None]
-        if grads is not None:
-            grads = structure.from_real_gradients(grads, self.complex_controls)
-            if not self.complex_controls:
-                grads = np.array(grads, dtype=np.float64)
-            if opaque_grads is not None:
-                grads = grads + (opaque_grads if self.complex_controls
-                                 else np.real(opaque_grads))
-        for b in range(batch):
-            controls = None if self.control_count == 0 else controls_batch[b]
-            value, host_grad = self._host_terms(controls, want_grad)
-            errors[b] += value
-            if host_grad is not None:
-                grads[b] = grads[b] + host_grad
-            for cost in self.opaque_costs:  # the host evaluates the user's cost()
-                errors[b] += self._opaque_value(cost, controls, step_states[b])
-        return errors, grads, final, step_states
+        self.backend.eval_resident(want_grad)
+        cost, grads, final = self._download(controls_batch, want_grad)
+        return cost, grads, final[..., None]
 
-    def _cost_steps(self, cost):
-        if not cost.requires_step_evaluation:
-            return [self.final_system_eval_step]
-        return list(range(self.cost_eval_step, self.system_eval_count, self.cost_eval_step))
+    def _download_steps(self):
+        return self.backend.download_step_states()[..., None]
 
-    def _opaque_cotangents(self, controls_batch, step_states):
-        """(steps, bars[B, len(steps), S, n], control_grads[B, Nc, K] complex) of the user costs."""
-        steps = sorted({st for c in self.opaque_costs for st in self._cost_steps(c)})
-        row = {st: r for r, st in enumerate(steps)}
-        batch = controls_batch.shape[0]
-        bars = np.zeros((batch, len(steps), self.state_count, self.hilbert_size),
-                        dtype=np.complex128)
-        cgrads = np.zeros(controls_batch.shape, dtype=np.complex128)
-        for b in range(batch):
-            for cost in self.opaque_costs:
-                for st in self._cost_steps(cost):
-                    states = step_states[b][st]
-                    bars[b, row[st]] += user_states_bar(cost, controls_batch[b], states, st)[:, :, 0]
-                    cgrads[b] += user_controls_bar(cost, controls_batch[b], states, st)
-        return steps, bars, cgrads
+    def _set_cotangents(self, steps, bars):
+        self.backend.set_state_cotangents(steps, bars)
 
-    def _opaque_value(self, cost, controls, states_by_step):
-        if not cost.requires_step_evaluation:
-            return cost.cost(controls, states_by_step[-1], self.final_system_eval_step)
-        total = 0.0
-        for step in range(self.cost_eval_step, self.system_eval_count, self.cost_eval_step):
-            total = total + cost.cost(controls, states_by_step[step], step)
-        return total
-
-    def evaluate(self, controls, want_grad=True, want_step_states=False):
-        """Single control array, the reference's calling convention."""
-        batch = None if controls is None else np.asarray(controls)[None]
-        errors, grads, final, steps = self.evaluate_batch(batch, want_grad, want_step_states)
-        return (float(errors[0]), None if grads is None else grads[0], final[0],
-                None if steps is None else steps[0])
+    def _problem_stays_resident(self):
+        return self.opaque_hamiltonian is None
 
 
-class LindbladEvaluator(object):
+class LindbladEvaluator(_Evaluator):
     """
     Plays the role of `_evaluate_lindblad_discrete` and of its `ans_jacobian`
     (qoc/core/lindbladdiscrete.py:321-322, :357-441) through qocx_eval_lindblad.
     """
 
     MAX_HILBERT_SIZE = 32
+    opt_prefix = "lindblad_"
+    subtotal_costs = False
+    linearized_route = "on the Lindblad GRAPE path"
 
     def __init__(self, evolution_time, initial_densities, system_eval_count, hamiltonian=None,
                  lindblad_data=None, control_count=0, control_eval_count=0,
@@ -505,7 +571,6 @@ class LindbladEvaluator(object):
         if isinstance(hamiltonian, HamiltonianEnsemble):
             raise NotImplementedError("Hamiltonian ensembles are evaluated on the Schroedinger path "
                                       "only, not on the Lindblad path")
-        self._cost_controls = None
         if frozen_controls is not None:
             if need_gradients:
                 raise structure.NonLinearHamiltonianError(
@@ -550,37 +615,22 @@ class LindbladEvaluator(object):
         # cost and the same control gradient -, one control array at a time.
         self.linearized_hamiltonian = None
         self._evolution_time = evolution_time
+        probe = lambda h: structure.probe_static_lindblad_system(  # noqa: E731
+            h, lindblad_data, self.hilbert_size, control_count, complex_controls, evolution_time,
+            probe_times=self._coarse_times)
         try:
-            h0, g, dissipators, operators, self.time_dependent = \
-                structure.probe_static_lindblad_system(
-                    hamiltonian, lindblad_data, self.hilbert_size, control_count, complex_controls,
-                    evolution_time, probe_times=self._coarse_times)
+            h0, g, dissipators, operators, self.time_dependent, data_dependent = probe(hamiltonian)
         except structure.NonLinearHamiltonianError:
             if frozen_controls is not None or control_count == 0:
                 raise
             self.linearized_hamiltonian = hamiltonian
-            h0, g, dissipators, operators, _ = structure.probe_static_lindblad_system(
-                None, lindblad_data, self.hilbert_size, control_count, complex_controls,
-                evolution_time, probe_times=self._coarse_times)
+            h0, g, dissipators, operators, _, data_dependent = probe(None)
             self.time_dependent = True
             hamiltonian = None
-        self._lindblad_data = lindblad_data if getattr(
-            structure.probe_static_lindblad_system, "lindblad_time_dependent", False) else None
-        self.device_costs, self.host_costs, self.opaque_costs = [], [], []
-        descriptors = []
-        for cost in self.costs:
-            desc = cost.device_descriptor(self.density_count, self.hilbert_size) \
-                if hasattr(cost, "device_descriptor") else None
-            if desc is not None:
-                self.device_costs.append(cost)
-                descriptors.append(desc)
-            elif (getattr(cost, "uses_states", True) is False
-                  and not cost.requires_step_evaluation):
-                self.host_costs.append(cost)
-            else:
-                self.opaque_costs.append(cost)
-        self.control_cost_descriptors = control_cost_descriptors(
-            self.host_costs, control_count, control_eval_count, complex_controls)
+        # a time-dependent lindblad_data is sampled at the stage times like the Hamiltonian
+        self._lindblad_data = lindblad_data if data_dependent else None
+        self.cotangent_shape = (self.density_count, self.hilbert_size, self.hilbert_size)
+        descriptors = self._triage_costs(self.density_count)
         self._problem_args = (self.hilbert_size, self.density_count, self.kr, control_eval_count,
                               system_eval_count, evolution_time, h0, g, dissipators, operators,
                               initial_densities)
@@ -598,61 +648,19 @@ class LindbladEvaluator(object):
                                2 if complex_controls else 1)
             self._set_time_dependent_problem(bounds)
 
-    def _set_time_dependent_problem(self, bounds):
-        """Sample the time-dependent Hamiltonian at the stage times of a sub-division fine
-        enough for controls up to `bounds` and hand the samples to the engine."""
-        (n, _, kr, nc, n_eval, evolution_time, h0, g, dissipators, operators, _) = \
-            self._problem_args
-        dt = evolution_time / (n_eval - 1)
-        if self._coarse_samples is None and self._hamiltonian is None:
-            self._coarse_samples = (np.asarray(h0, dtype=np.complex128)[None],
-                                    np.zeros((1, kr, n, n), dtype=np.complex128))
-        if self._coarse_samples is None:  # H on the coarsest stage grid: norms for the bound
-            self._coarse_samples = structure.probe_hamiltonian(
-                self._hamiltonian, n, self.control_count, self.complex_controls,
-                list(self._coarse_times))
-        h_probe, g_probe = self._coarse_samples
-        h_norm = max(np.linalg.norm(m, 2) for m in h_probe)
-        g_norms = [max(np.linalg.norm(g_probe[t, k], 2) for t in range(g_probe.shape[0]))
-                   for k in range(kr)]
-        ksub = structure.lindblad_subdivision(h_norm, g_norms, bounds, dissipators, operators, dt)
-        if self._lindblad_data is not None:  # the largest dissipative norm over the coarse grid
-            if self._coarse_lindblad is None:
-                self._coarse_lindblad = structure.sample_lindblad_data(
-                    self._lindblad_data, n, list(self._coarse_times))
-            ksub = max(structure.lindblad_subdivision(h_norm, g_norms, bounds, d, o, dt)
-                       for d, o in zip(*self._coarse_lindblad))
-        times = self.backend.lindblad_stage_times(evolution_time, n_eval, nc, kr, ksub)
-        if self._hamiltonian is None:
-            h0_stages = np.repeat(np.asarray(h0, dtype=np.complex128)[None], len(times), axis=0)
-            g_stages = None
-        else:
-            h0_stages, g_stages = structure.sample_lindblad_hamiltonian(
-                self._hamiltonian, n, self.control_count, self.complex_controls, times)
-        extra = {}
-        if self._lindblad_data is not None:
-            diss_stages, op_stages = structure.sample_lindblad_data(self._lindblad_data, n, times)
-            extra = dict(diss_stages=diss_stages, op_stages=op_stages)
-        self.backend.set_lindblad_problem(*self._problem_args, fixed_subdivision=ksub,
-                                          h0_stages=h0_stages, g_stages=g_stages, **extra,
-                                          **self._problem_kw)
-        self._table_bounds = np.asarray(bounds, dtype=np.float64)
-
-    def _set_linearized_problem(self, controls, device_controls):
-        """Tangent of the non-linear callable at `controls` (Nc x K) on the stage grid of a
-        sub-division fine enough for this control array, handed to the engine as tables."""
+    def _set_stage_tables(self, coarse_samples, bounds, sample):
+        """The tail of both table builders. coarse_samples :: (h0, g) on the coarsest stage grid:
+        their norms and `bounds` on the controls give the sub-division; sample(times) ->
+        (h0_stages, g_stages) on its stage times; a time-dependent lindblad_data is sampled there
+        as well, and the engine takes the lot."""
         (n, _, kr, nc, n_eval, evolution_time, _, _, dissipators, operators, _) = self._problem_args
         dt = evolution_time / (n_eval - 1)
-        lin = lambda times: structure.linearize_hamiltonian(  # noqa: E731
-            self.linearized_hamiltonian, controls, evolution_time, list(times), n,
-            self.complex_controls)
-        h_probe, g_probe = lin(self._coarse_times)
-        bounds = np.max(np.abs(device_controls.reshape(-1, kr)), axis=0)
+        h_probe, g_probe = coarse_samples
         h_norm = max(np.linalg.norm(m, 2) for m in h_probe)
         g_norms = [max(np.linalg.norm(g_probe[t, k], 2) for t in range(g_probe.shape[0]))
                    for k in range(kr)]
         pairs = [(dissipators, operators)]
-        if self._lindblad_data is not None:
+        if self._lindblad_data is not None:  # the largest dissipative norm over the coarse grid
             if self._coarse_lindblad is None:
                 self._coarse_lindblad = structure.sample_lindblad_data(
                     self._lindblad_data, n, list(self._coarse_times))
@@ -660,7 +668,7 @@ class LindbladEvaluator(object):
         ksub = max(structure.lindblad_subdivision(h_norm, g_norms, bounds, d, o, dt)
                    for d, o in pairs)
         times = self.backend.lindblad_stage_times(evolution_time, n_eval, nc, kr, ksub)
-        h0_stages, g_stages = lin(times)
+        h0_stages, g_stages = sample(times)
         extra = {}
         if self._lindblad_data is not None:
             diss_stages, op_stages = structure.sample_lindblad_data(self._lindblad_data, n, times)
@@ -669,28 +677,37 @@ class LindbladEvaluator(object):
                                           h0_stages=h0_stages, g_stages=g_stages, **extra,
                                           **self._problem_kw)
 
-    def _evaluate_linearized(self, controls_batch, device_controls, want_grad, need_steps):
-        costs, grads, finals, steps = [], [], [], []
-        for b in range(controls_batch.shape[0]):
-            self._set_linearized_problem(controls_batch[b], device_controls[b])
-            if need_steps:
-                self.backend.set_keep_step_states(True)
-            try:
-                c, gr, f = self.backend.evaluate_lindblad(device_controls[b:b + 1],
-                                                          want_grad=want_grad)
-                if need_steps:
-                    steps.append(self.backend.download_step_densities()[0])
-            finally:
-                if need_steps:
-                    self.backend.set_keep_step_states(False)
-            costs.append(c[0])
-            finals.append(f[0])
-            if want_grad:
-                grads.append(gr[0])
-        return (np.array(costs), np.stack(grads) if want_grad else None, np.stack(finals),
-                np.stack(steps) if need_steps else None)
+    def _set_time_dependent_problem(self, bounds):
+        """Sample the time-dependent Hamiltonian at the stage times of a sub-division fine
+        enough for controls up to `bounds` and hand the samples to the engine."""
+        n, kr, h0 = self._problem_args[0], self.kr, self._problem_args[6]
+        if self._coarse_samples is None and self._hamiltonian is None:
+            self._coarse_samples = (np.asarray(h0, dtype=np.complex128)[None],
+                                    np.zeros((1, kr, n, n), dtype=np.complex128))
+        if self._coarse_samples is None:  # H on the coarsest stage grid: norms for the bound
+            self._coarse_samples = structure.probe_hamiltonian(
+                self._hamiltonian, n, self.control_count, self.complex_controls,
+                list(self._coarse_times))
 
-    def _ensure_time_table(self, device_controls):
+        def sample(times):
+            if self._hamiltonian is None:
+                return np.repeat(np.asarray(h0, dtype=np.complex128)[None], len(times), axis=0), None
+            return structure.sample_lindblad_hamiltonian(
+                self._hamiltonian, n, self.control_count, self.complex_controls, times)
+        self._set_stage_tables(self._coarse_samples, bounds, sample)
+        self._table_bounds = np.asarray(bounds, dtype=np.float64)
+
+    def _set_linearized_problem(self, controls, device_controls):
+        """Tangent of the non-linear callable at `controls` (Nc x K) on the stage grid of a
+        sub-division fine enough for this control array, handed to the engine as tables."""
+        lin = lambda times: structure.linearize_hamiltonian(  # noqa: E731
+            self.linearized_hamiltonian, controls, self._evolution_time, list(times),
+            self.hilbert_size, self.complex_controls)
+        bounds = np.max(np.abs(device_controls.reshape(-1, self.kr)), axis=0)
+        self._set_stage_tables(lin(self._coarse_times), bounds, lin)
+
+    def _prepare(self, device_controls):
+        """A time-dependent problem's tables cover the controls seen so far: widen them first."""
         if not self.time_dependent or self.linearized_hamiltonian is not None:
             return
         if self.control_count == 0:
@@ -701,115 +718,26 @@ class LindbladEvaluator(object):
             old = np.zeros_like(need) if self._table_bounds is None else self._table_bounds
             self._set_time_dependent_problem(np.maximum(old, need))
 
-    def resident_capable(self):
-        """True when a multi-start driver may keep controls and optimizer states on the device
-        (engine.lindblad_opt_*): a Hamiltonian linear in the controls (time-dependent ones
-        included: their tables cover max_control_norms, which the driver's clip enforces), every
-        cost evaluated on the device - the built-in costs of the controls alone included -, and a
-        backend that has the entry points (the real engine; complex controls need its complex
-        clip)."""
-        return (self.linearized_hamiltonian is None and self._cost_controls is None
-                and self.control_count > 0
-                and (not self.time_dependent or self._table_bounds is not None)
-                and not self.opaque_costs
-                and hasattr(self.backend, "lindblad_opt_step")
-                and controls_stay_resident(self.backend, self.control_cost_descriptors,
-                                           self.complex_controls, "lindblad_opt_begin_complex"))
+    def _pass(self, controls_batch, device_controls, want_grad, again=False):
+        return self.backend.evaluate_lindblad(device_controls, want_grad=want_grad)
 
-    def resident_lbfgs_capable(self):
-        """resident_capable() with a backend that also has the L-BFGS calls of the resident driver."""
-        return self.resident_capable() and hasattr(self.backend, "lindblad_opt_lbfgs_step")
+    def _download_steps(self):
+        return self.backend.download_step_densities()
+
+    def _set_cotangents(self, steps, bars):
+        self.backend.set_density_cotangents(steps, bars)
+
+    def _problem_stays_resident(self):
+        """Time-dependent Hamiltonians included once their tables cover max_control_norms, which
+        the resident driver's clip enforces; not the frozen controls of a forward evaluation."""
+        return (self._cost_controls is None
+                and (not self.time_dependent or self._table_bounds is not None))
 
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_densities=False):
-        """
-        controls_batch :: (B x Nc x K) (or None / an int B when control_count == 0).
-        Returns (errors[B], grads or None, final_densities[B x S x n x n], step_densities).
-        """
-        if self.control_count == 0:
-            batch = 1 if controls_batch is None else int(controls_batch)
-            want_grad = False
-            device_controls = batch
-        else:
-            controls_batch = np.asarray(controls_batch)
-            batch = controls_batch.shape[0]
-            device_controls = structure.to_real_controls(controls_batch, self.complex_controls)
-        self._ensure_time_table(device_controls if self.control_count else None)
-        need_steps = want_step_densities or bool(self.opaque_costs)
-        two_pass = want_grad and bool(self.opaque_costs)
-        if self.linearized_hamiltonian is not None:
-            if two_pass:
-                raise NotImplementedError(
-                    "user costs without a device descriptor together with a hamiltonian that is "
-                    "not linear in the controls on the Lindblad GRAPE path")
-            cost, grads, final, step_densities = self._evaluate_linearized(
-                controls_batch, device_controls, want_grad, need_steps)
-        else:
-            if need_steps:
-                self.backend.set_keep_step_states(True)
-            try:
-                cost, grads, final = self.backend.evaluate_lindblad(
-                    device_controls, want_grad=want_grad and not two_pass)
-                step_densities = self.backend.download_step_densities() if need_steps else None
-            finally:
-                if need_steps:
-                    self.backend.set_keep_step_states(False)
-        opaque_grads = None
-        if two_pass:  # user costs: host-supplied density cotangents (see SchroedingerEvaluator)
-            steps, bars, opaque_grads = self._opaque_cotangents(controls_batch, step_densities)
-            self.backend.set_density_cotangents(steps, bars)
-            try:
-                cost, grads, final = self.backend.evaluate_lindblad(device_controls,
-                                                                    want_grad=True)
-            finally:
-                self.backend.set_density_cotangents(None, None)
-        errors = np.array(cost, dtype=np.float64)
-        if grads is not None:
-            grads = structure.from_real_gradients(grads, self.complex_controls)
-            if not self.complex_controls:
-                grads = np.array(grads, dtype=np.float64)
-            if opaque_grads is not None:
-                grads = grads + (opaque_grads if self.complex_controls
-                                 else np.real(opaque_grads))
-        for b in range(batch):
-            controls = None if self.control_count == 0 else controls_batch[b]
-            if self._cost_controls is not None:
-                controls = self._cost_controls
-            for cost_ in self.host_costs:
-                errors[b] += cost_.cost(controls, None, self.final_system_eval_step)
-                if want_grad:
-                    bar = cost_.controls_bar(controls, None, self.final_system_eval_step)
-                    if bar is None:
-                        raise NotImplementedError("cost {} has no controls_bar()".format(cost_))
-                    grads[b] = grads[b] + bar
-            for cost_ in self.opaque_costs:  # the host evaluates the user's cost()
-                for step in self._cost_steps(cost_):
-                    errors[b] += cost_.cost(controls, step_densities[b][step], step)
-        return errors, grads, final, step_densities
-
-    def _cost_steps(self, cost):
-        if not cost.requires_step_evaluation:
-            return [self.final_system_eval_step]
-        return list(range(self.cost_eval_step, self.system_eval_count, self.cost_eval_step))
-
-    def _opaque_cotangents(self, controls_batch, step_densities):
-        steps = sorted({st for c in self.opaque_costs for st in self._cost_steps(c)})
-        row = {st: r for r, st in enumerate(steps)}
-        batch = controls_batch.shape[0]
-        bars = np.zeros((batch, len(steps), self.density_count, self.hilbert_size,
-                         self.hilbert_size), dtype=np.complex128)
-        cgrads = np.zeros(controls_batch.shape, dtype=np.complex128)
-        for b in range(batch):
-            for cost in self.opaque_costs:
-                for st in self._cost_steps(cost):
-                    dens = step_densities[b][st]
-                    bars[b, row[st]] += user_states_bar(cost, controls_batch[b], dens, st)
-                    cgrads[b] += user_controls_bar(cost, controls_batch[b], dens, st)
-        return steps, bars, cgrads
+        """_Evaluator.evaluate_batch; the step states are densities [B x N x S x n x n]."""
+        return _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_densities)
 
     def evaluate(self, controls, want_grad=True, want_step_densities=False):
-        batch = None if controls is None else np.asarray(controls)[None]
         if self._cost_controls is not None:  # frozen controls: the device's dummy control is zero
-            batch = np.zeros((1, self.control_eval_count, 1))
-        errors, grads, final, steps = self.evaluate_batch(batch, want_grad, want_step_densities)
-        return (float(errors[0]), None if grads is None else grads[0], final[0],
-                None if steps is None else steps[0])
+            controls = np.zeros((self.control_eval_count, 1))
+        return _Evaluator.evaluate(self, controls, want_grad, want_step_densities)

@@ -13,8 +13,7 @@ the parity tolerances that follow from replacing an adaptive integrator).
 import numpy as np
 
 from qoc_amd.core import batch
-from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
-                                 strip_controls)
+from qoc_amd.core.common import _cost_format, initialize_controls, strip_controls
 from qoc_amd.core.device import LindbladEvaluator
 from qoc_amd.core.structure import NonLinearHamiltonianError
 from qoc_amd.engine import PATH_LINDBLAD
@@ -117,15 +116,6 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
     return result
 
 
-def _cost_format(flat_controls, pstate):
-    """optimizer format -> clipped, conditioned cost-function format (:272-280)."""
-    controls = slap_controls(pstate.complex_controls, flat_controls, pstate.controls_shape)
-    clip_control_norms(controls, pstate.max_control_norms)
-    if pstate.impose_control_conditions is not None:
-        controls = pstate.impose_control_conditions(controls)
-    return controls
-
-
 def _eld_wrap(controls, pstate, reporter, result):
     controls = _cost_format(controls, pstate)
     error, _, final_densities, _ = pstate.evaluator.evaluate(controls, want_grad=False)
@@ -167,15 +157,7 @@ class GrapeLindbladBatchResult(batch.BatchResult):
 def _ResidentOps(engine, control_costs=(), complex_controls=False):
     """engine.lindblad_* (the Lindblad problem's resident buffers) as the resident loop of
     core/batch.py calls them. A function under the name of the class it replaced."""
-    return batch.ResidentOps(
-        engine, PATH_LINDBLAD, control_costs, complex_controls,
-        upload_controls=engine.lindblad_upload_controls,
-        opt_begin=engine.lindblad_opt_begin_complex if complex_controls else engine.lindblad_opt_begin,
-        opt_clip=engine.lindblad_opt_clip, eval_resident=engine.eval_lindblad_resident,
-        download_costs=engine.lindblad_download_costs, opt_step=engine.lindblad_opt_step,
-        opt_download_best=engine.lindblad_opt_download_best,
-        opt_lbfgs_begin=getattr(engine, "lindblad_opt_lbfgs_begin", None),
-        opt_lbfgs_step=getattr(engine, "lindblad_opt_lbfgs_step", None))
+    return batch.ResidentOps(engine, PATH_LINDBLAD, control_costs, complex_controls)
 
 
 def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evolution_time,

@@ -10,8 +10,7 @@ MI355X through qoc_amd.core.device.SchroedingerEvaluator.
 import numpy as np
 
 from qoc_amd.core import batch
-from qoc_amd.core.common import (clip_control_norms, initialize_controls, slap_controls,
-                                 strip_controls)
+from qoc_amd.core.common import _cost_format, initialize_controls, strip_controls
 from qoc_amd.core.device import SchroedingerEvaluator
 from qoc_amd.engine import PATH_SCHROEDINGER
 from qoc_amd.models import (Dummy, EvolveSchroedingerDiscreteState, EvolveSchroedingerResult,
@@ -119,15 +118,6 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     return result
 
 
-def _cost_format(flat_controls, pstate):
-    """optimizer format -> clipped, conditioned cost-function format (:308-315)."""
-    controls = slap_controls(pstate.complex_controls, flat_controls, pstate.controls_shape)
-    clip_control_norms(controls, pstate.max_control_norms)  # in place, aliases real params
-    if pstate.impose_control_conditions is not None:
-        controls = pstate.impose_control_conditions(controls)
-    return controls
-
-
 def _esd_wrap(controls, pstate, reporter, result):
     """function(params, *args) -> (error, terminate); used by optimizers that ask for values."""
     controls = _cost_format(controls, pstate)
@@ -171,15 +161,7 @@ class GrapeSchroedingerBatchResult(batch.BatchResult):
 def _ResidentOps(engine, control_costs=(), complex_controls=False):
     """engine.opt_* as the resident loop of core/batch.py calls it (final states [B, S, n, 1]).
     A function under the name of the class it replaced: tools and tests build their ops with it."""
-    return batch.ResidentOps(
-        engine, PATH_SCHROEDINGER, control_costs, complex_controls, column_states=True,
-        upload_controls=engine.upload_controls,
-        opt_begin=engine.opt_begin_complex if complex_controls else engine.opt_begin,
-        opt_clip=engine.opt_clip, eval_resident=engine.eval_resident,
-        download_costs=engine.download_costs, opt_step=engine.opt_step,
-        opt_download_best=engine.opt_download_best,
-        opt_lbfgs_begin=getattr(engine, "opt_lbfgs_begin", None),
-        opt_lbfgs_step=getattr(engine, "opt_lbfgs_step", None))
+    return batch.ResidentOps(engine, PATH_SCHROEDINGER, control_costs, complex_controls)
 
 
 def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, evolution_time,

@@ -214,14 +214,15 @@ def probe_static_lindblad_system(hamiltonian, lindblad_data, hilbert_size, contr
     Structure of the Lindblad path's inputs (qoc/core/lindbladdiscrete.py:444-493):
     hamiltonian(controls, time) and lindblad_data(time) -> (dissipators, operators).
     Returns (h0 (n, n), g (Kr, n, n), dissipators (L,) or None, operators (L, n, n) or None,
-    time_dependent). Explicit time dependence of the Hamiltonian is decided on `probe_times` -
-    the caller passes the integrator's own stage-time grid (every time the device would ever
-    read H at for the coarsest sub-division), so a periodic drive cannot alias to a constant - by
-    comparing H(0, t) and H(u_random, t) with their values at the first time, bit for bit. A
-    time-dependent Hamiltonian is then sampled at the stage times (sample_lindblad_hamiltonian),
-    and so is a time-dependent lindblad_data (sample_lindblad_data; the reference calls both at
-    every right-hand side, lindbladdiscrete.py:483-492). `time_dependent` covers either; the
-    function attribute `lindblad_time_dependent` says whether lindblad_data was the (or a) cause.
+    time_dependent, data_dependent). Explicit time dependence of the Hamiltonian is decided on
+    `probe_times` - the caller passes the integrator's own stage-time grid (every time the device
+    would ever read H at for the coarsest sub-division), so a periodic drive cannot alias to a
+    constant - by comparing H(0, t) and H(u_random, t) with their values at the first time, bit
+    for bit. A time-dependent Hamiltonian is then sampled at the stage times
+    (sample_lindblad_hamiltonian), and so is a time-dependent lindblad_data (sample_lindblad_data;
+    the reference calls both at every right-hand side, lindbladdiscrete.py:483-492).
+    `time_dependent` covers either; `data_dependent` says whether lindblad_data was the (or a)
+    cause.
     """
     n = hilbert_size
     times = list(decision_times(evolution_time) if probe_times is None else probe_times)
@@ -278,8 +279,7 @@ def probe_static_lindblad_system(hamiltonian, lindblad_data, hilbert_size, contr
                 time_dependent = True
                 lindblad_time_dependent = True
                 break
-    probe_static_lindblad_system.lindblad_time_dependent = lindblad_time_dependent
-    return h0[0], g[0], dissipators, operators, time_dependent
+    return h0[0], g[0], dissipators, operators, time_dependent, lindblad_time_dependent
 
 
 def sample_lindblad_hamiltonian(hamiltonian, hilbert_size, control_count, complex_controls, times):

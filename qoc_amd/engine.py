@@ -402,7 +402,10 @@ class Engine(object):
         """Control channels of a seed: the problem's K, or K - J with an ensemble set."""
         return self._problem["K"] if self._ensemble is None else self._ensemble["Kr"]
 
-    def _final_shape(self, B):
+    def _final_shape(self, B, path=PATH_SCHROEDINGER):
+        if path == PATH_LINDBLAD:
+            pr = self._lindblad
+            return (B, pr["S"], pr["n"], pr["n"])
         pr = self._problem
         members = () if self._ensemble is None else (self._ensemble["M"],)
         return (B,) + members + (pr["S"], pr["n"])
@@ -438,16 +441,8 @@ class Engine(object):
         self._check(self._lib.qocx_eval_resident(self._ctx, int(bool(want_grad))))
 
     def download_results(self, want_grad=True, want_final=True):
-        pr, B = self._problem, self.batch
-        cost = np.empty(B, dtype=np.float64)
-        want_grad = want_grad and pr["K"] > 0
-        grads = (np.empty((B, pr["Nc"], self._seed_channels()), dtype=np.float64) if want_grad
-                 else None)
-        final = np.empty(self._final_shape(B), dtype=np.complex128) if want_final else None
-        self._check(self._lib.qocx_download_results(
-            self._ctx, _dp(cost), _dp(grads) if want_grad else None,
-            _dp(final) if want_final else None))
-        return cost, grads, final
+        return self._download_results(self._lib.qocx_download_results, PATH_SCHROEDINGER,
+                                      want_grad, want_final)
 
     def evaluate(self, controls, want_grad=True):
         """(cost[B], grads[B,Nc,K] or None, final_states[B,S,n]) for controls[B,Nc,K]."""
@@ -663,37 +658,40 @@ class Engine(object):
         self._check(self._lib.qocx_comm_init(self._ctx, buf, int(rank), int(world)))
 
     # -- multi-start driver with the optimizer states on the device -----------------------------
-    def opt_begin(self):
-        self._check(self._lib.qocx_opt_begin(self._ctx))
+    # The Schroedinger and the Lindblad problem have their own resident buffers and their own C
+    # entry points with one signature; each public method below names its C function and, where
+    # shapes are needed, its path.
+    def _resident_batch(self, path):
+        return self._lindblad_resident_batch if path == PATH_LINDBLAD else self.batch
 
-    def opt_begin_complex(self):
-        """opt_begin for complex controls (channels 2k, 2k+1): the optimizer's parameters stay
-        unclipped, opt_clip takes one modulus bound per complex control (qocx_opt_begin_complex)."""
-        self._check(self._lib.qocx_opt_begin_complex(self._ctx))
+    def _download_results(self, call, path, want_grad, want_final):
+        B, (nc, channels) = self._resident_batch(path), self._control_channels(path)
+        cost = np.empty(B, dtype=np.float64)
+        want_grad = want_grad and channels > 0
+        grads = np.empty((B, nc, channels), dtype=np.float64) if want_grad else None
+        final = np.empty(self._final_shape(B, path), dtype=np.complex128) if want_final else None
+        self._check(call(self._ctx, _dp(cost), _dp(grads) if want_grad else None,
+                         _dp(final) if want_final else None))
+        return cost, grads, final
 
-    def opt_clip(self, max_norms):
-        max_norms = np.ascontiguousarray(max_norms, dtype=np.float64)
-        self._check(self._lib.qocx_opt_clip(self._ctx, _dp(max_norms)))
-
-    def download_costs(self):
-        cost = np.empty(self.batch, dtype=np.float64)
-        self._check(self._lib.qocx_download_costs(self._ctx, _dp(cost)))
+    def _download_costs(self, call, path):
+        cost = np.empty(self._resident_batch(path), dtype=np.float64)
+        self._check(call(self._ctx, _dp(cost)))
         return cost
 
-    def opt_step(self, kind, improved, update, learning_rate, beta_1=0.0, beta_2=0.0, epsilon=0.0,
-                 corr_1=1.0, corr_2=1.0, clip_grads=None):
+    def _opt_clip(self, call, max_norms):
+        max_norms = np.ascontiguousarray(max_norms, dtype=np.float64)
+        self._check(call(self._ctx, _dp(max_norms)))
+
+    def _opt_step(self, call, kind, improved, update, learning_rate, beta_1, beta_2, epsilon,
+                  corr_1, corr_2, clip_grads):
         improved = np.ascontiguousarray(improved, dtype=np.uint8)
         update = np.ascontiguousarray(update, dtype=np.uint8)
-        u8 = ctypes.POINTER(ctypes.c_uint8)
-        self._check(self._lib.qocx_opt_step(
-            self._ctx, int(kind), improved.ctypes.data_as(u8), update.ctypes.data_as(u8),
+        self._check(call(
+            self._ctx, int(kind), improved.ctypes.data_as(_U8P), update.ctypes.data_as(_U8P),
             float(learning_rate), float(beta_1), float(beta_2), float(epsilon), float(corr_1),
             float(corr_2), 0 if clip_grads is None else 1,
             0.0 if clip_grads is None else float(clip_grads)))
-
-    def opt_lbfgs_begin(self, history):
-        """After opt_begin / opt_begin_complex: the seeds' L-BFGS state, zeroed (qocx_opt_lbfgs_begin)."""
-        self._check(self._lib.qocx_opt_lbfgs_begin(self._ctx, int(history)))
 
     def _lbfgs_step(self, call, improved, update, first_step, armijo, shrink, max_backtracks):
         improved = np.ascontiguousarray(improved, dtype=np.uint8)
@@ -704,6 +702,36 @@ class Engine(object):
                          finished.ctypes.data_as(_U8P)))
         return finished.astype(bool)
 
+    def _opt_download_best(self, call, path):
+        B = self._resident_batch(path)
+        controls = np.empty((B,) + self._control_channels(path), dtype=np.float64)
+        final = np.empty(self._final_shape(B, path), dtype=np.complex128)
+        self._check(call(self._ctx, _dp(controls), _dp(final)))
+        return controls, final
+
+    def opt_begin(self):
+        self._check(self._lib.qocx_opt_begin(self._ctx))
+
+    def opt_begin_complex(self):
+        """opt_begin for complex controls (channels 2k, 2k+1): the optimizer's parameters stay
+        unclipped, opt_clip takes one modulus bound per complex control (qocx_opt_begin_complex)."""
+        self._check(self._lib.qocx_opt_begin_complex(self._ctx))
+
+    def opt_clip(self, max_norms):
+        self._opt_clip(self._lib.qocx_opt_clip, max_norms)
+
+    def download_costs(self):
+        return self._download_costs(self._lib.qocx_download_costs, PATH_SCHROEDINGER)
+
+    def opt_step(self, kind, improved, update, learning_rate, beta_1=0.0, beta_2=0.0, epsilon=0.0,
+                 corr_1=1.0, corr_2=1.0, clip_grads=None):
+        self._opt_step(self._lib.qocx_opt_step, kind, improved, update, learning_rate, beta_1,
+                       beta_2, epsilon, corr_1, corr_2, clip_grads)
+
+    def opt_lbfgs_begin(self, history):
+        """After opt_begin / opt_begin_complex: the seeds' L-BFGS state, zeroed (qocx_opt_lbfgs_begin)."""
+        self._check(self._lib.qocx_opt_lbfgs_begin(self._ctx, int(history)))
+
     def opt_lbfgs_step(self, improved, update, first_step, armijo, shrink, max_backtracks):
         """The best-so-far bookkeeping of opt_step, then one LBFGS.update of the seeds flagged in
         `update` on the last evaluation's costs and gradients; returns finished [B] (bool)."""
@@ -711,11 +739,7 @@ class Engine(object):
                                 shrink, max_backtracks)
 
     def opt_download_best(self):
-        pr, B = self._problem, self.batch
-        controls = np.empty((B, pr["Nc"], self._seed_channels()), dtype=np.float64)
-        final = np.empty(self._final_shape(B), dtype=np.complex128)
-        self._check(self._lib.qocx_opt_download_best(self._ctx, _dp(controls), _dp(final)))
-        return controls, final
+        return self._opt_download_best(self._lib.qocx_opt_download_best, PATH_SCHROEDINGER)
 
     # -- the same for the Lindblad problem (its own resident buffers, seed order) -----------------
     def lindblad_upload_controls(self, controls):
@@ -732,20 +756,11 @@ class Engine(object):
 
     def lindblad_download_results(self, want_grad=True, want_final=True):
         """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n] or None), seed order."""
-        pr, B = self._lindblad, self._lindblad_resident_batch
-        cost = np.empty(B, dtype=np.float64)
-        grads = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64) if want_grad else None
-        final = (np.empty((B, pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
-                 if want_final else None)
-        self._check(self._lib.qocx_lindblad_download_results(
-            self._ctx, _dp(cost), _dp(grads) if want_grad else None,
-            _dp(final) if want_final else None))
-        return cost, grads, final
+        return self._download_results(self._lib.qocx_lindblad_download_results, PATH_LINDBLAD,
+                                      want_grad, want_final)
 
     def lindblad_download_costs(self):
-        cost = np.empty(self._lindblad_resident_batch, dtype=np.float64)
-        self._check(self._lib.qocx_lindblad_download_costs(self._ctx, _dp(cost)))
-        return cost
+        return self._download_costs(self._lib.qocx_lindblad_download_costs, PATH_LINDBLAD)
 
     def lindblad_opt_begin(self):
         self._check(self._lib.qocx_lindblad_opt_begin(self._ctx))
@@ -754,19 +769,12 @@ class Engine(object):
         self._check(self._lib.qocx_lindblad_opt_begin_complex(self._ctx))
 
     def lindblad_opt_clip(self, max_norms):
-        max_norms = np.ascontiguousarray(max_norms, dtype=np.float64)
-        self._check(self._lib.qocx_lindblad_opt_clip(self._ctx, _dp(max_norms)))
+        self._opt_clip(self._lib.qocx_lindblad_opt_clip, max_norms)
 
     def lindblad_opt_step(self, kind, improved, update, learning_rate, beta_1=0.0, beta_2=0.0,
                           epsilon=0.0, corr_1=1.0, corr_2=1.0, clip_grads=None):
-        improved = np.ascontiguousarray(improved, dtype=np.uint8)
-        update = np.ascontiguousarray(update, dtype=np.uint8)
-        u8 = ctypes.POINTER(ctypes.c_uint8)
-        self._check(self._lib.qocx_lindblad_opt_step(
-            self._ctx, int(kind), improved.ctypes.data_as(u8), update.ctypes.data_as(u8),
-            float(learning_rate), float(beta_1), float(beta_2), float(epsilon), float(corr_1),
-            float(corr_2), 0 if clip_grads is None else 1,
-            0.0 if clip_grads is None else float(clip_grads)))
+        self._opt_step(self._lib.qocx_lindblad_opt_step, kind, improved, update, learning_rate,
+                       beta_1, beta_2, epsilon, corr_1, corr_2, clip_grads)
 
     def lindblad_opt_lbfgs_begin(self, history):
         self._check(self._lib.qocx_lindblad_opt_lbfgs_begin(self._ctx, int(history)))
@@ -776,11 +784,7 @@ class Engine(object):
                                 armijo, shrink, max_backtracks)
 
     def lindblad_opt_download_best(self):
-        pr, B = self._lindblad, self._lindblad_resident_batch
-        controls = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64)
-        final = np.empty((B, pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
-        self._check(self._lib.qocx_lindblad_opt_download_best(self._ctx, _dp(controls), _dp(final)))
-        return controls, final
+        return self._opt_download_best(self._lib.qocx_lindblad_opt_download_best, PATH_LINDBLAD)
 
     # -- costs of the controls alone on the device ------------------------------------------------
     def _control_channels(self, path):

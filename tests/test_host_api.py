@@ -381,6 +381,43 @@ def test_user_cost_with_explicit_control_dependence():
     assert abs(fd - np.sum(grads * d)) < 1e-7 * max(1.0, abs(fd))
 
 
+def test_engine_error_does_not_leave_step_states_kept():
+    """A user cost without device_descriptor() has the evaluator keep the step states during its
+    first pass. An engine error in that pass (a failed allocation, say) must switch the keeping
+    off again: the backend would otherwise hold N x S x n step states for every later evaluation.
+    The evaluator stays usable and gives what a fresh one gives."""
+    from tests.test_control_costs_host import evaluator
+
+    class FailsOnce(OracleBackend):
+        fail = True
+        keep_calls = ()
+
+        def set_keep_step_states(self, keep):
+            self.keep_calls += (bool(keep),)
+            super().set_keep_step_states(keep)
+
+        def eval_resident(self, want_grad=True):
+            if self.fail:
+                self.fail = False
+                raise RuntimeError("hipMalloc failed")
+            super().eval_resident(want_grad)
+
+    user = _UserFinalPlusControls()  # (the base class's device_descriptor() declines)
+    ev, _ = evaluator(FailsOnce(), [user])  # K = 2, Nc = 6, n = 3, N = 7
+    assert ev.opaque_costs == [user]
+    u = 0.3 * np.random.default_rng(4).standard_normal((2, 6, 2))
+    with pytest.raises(RuntimeError, match="hipMalloc"):
+        ev.evaluate_batch(u)
+    assert ev.backend.keep_calls == (True, False)
+    after = ev.evaluate_batch(u)
+    backend = FailsOnce()
+    backend.fail = False
+    fresh = evaluator(backend, [_UserFinalPlusControls()])[0].evaluate_batch(u)
+    for x, y in zip(after, fresh):
+        assert np.array_equal(x, y)
+    assert ev.backend.keep_calls[-1] is False
+
+
 def test_file_and_json_helpers(tmp_path):
     import json
     from qoc_amd.standard import CustomJSONEncoder, generate_save_file_path

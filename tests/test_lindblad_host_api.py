@@ -357,14 +357,14 @@ def test_periodic_drive_does_not_alias_to_time_independent():
     T, N = 6.0, 13
     from qoc_amd.engine import Engine
     times = Engine.lindblad_stage_times(T, N, N, 1, 1)
-    _, _, _, _, dep = structure.probe_static_lindblad_system(hamiltonian, None, 2, 1, False, T,
-                                                            probe_times=times)
+    _, _, _, _, dep, _ = structure.probe_static_lindblad_system(hamiltonian, None, 2, 1, False, T,
+                                                               probe_times=times)
     assert dep
     # the fallback grid (no integrator at hand) does not alias either
-    _, _, _, _, dep = structure.probe_static_lindblad_system(hamiltonian, None, 2, 1, False, T)
+    _, _, _, _, dep, _ = structure.probe_static_lindblad_system(hamiltonian, None, 2, 1, False, T)
     assert dep
     # a constant H stays constant
-    _, _, _, _, dep = structure.probe_static_lindblad_system(
+    _, _, _, _, dep, _ = structure.probe_static_lindblad_system(
         lambda u, t: Z + u[0] * X, None, 2, 1, False, T, probe_times=times)
     assert not dep
     # end to end (oracle backend on CPU): the evaluator takes the time-dependent route and the
@@ -375,6 +375,35 @@ def test_periodic_drive_does_not_alias_to_time_independent():
     r_frozen = qoc_amd.evolve_lindblad_discrete(
         T, rho0, N, controls=u, hamiltonian=lambda c, t: Z + X + c[0] * X)
     assert np.max(np.abs(r_dep.final_densities - r_frozen.final_densities)) > 1e-3
+
+
+def test_time_dependent_lindblad_data_is_known_per_evaluator():
+    """Whether lindblad_data depends on time is an answer of the probe call an evaluator made for
+    itself, not a state shared between evaluators: A (time-dependent data) is built, then B
+    (constant data) on the same backend class, then A is evaluated. A hands the engine the data
+    sampled at the stage times, B does not."""
+    class Recording(OracleBackend):
+        def set_lindblad_problem(self, *args, **kw):
+            self.problem_kw = kw
+            super().set_lindblad_problem(*args, **kw)
+
+    case = cases_mod.lindblad_case_by_name("lindblad_timedep_data")
+    data = case.lindblad_data()
+    constant = data(0.0)
+
+    def build(lindblad_data):
+        return device.LindbladEvaluator(
+            case.T, case.initial_densities, case.N, hamiltonian=case.hamiltonian(),
+            lindblad_data=lindblad_data, control_count=case.K, control_eval_count=case.Nc,
+            costs=product_cost_list(case), cost_eval_step=case.cost_eval_step,
+            need_gradients=False, backend=Recording())
+    a = build(data)
+    b = build(lambda time: constant)
+    a.evaluate(case.controls[0], want_grad=False)
+    b.evaluate(case.controls[0], want_grad=False)
+    assert a.time_dependent and a.backend.problem_kw.get("diss_stages") is not None
+    assert a.backend.problem_kw["op_stages"].shape[1:] == case.operators.shape
+    assert b.backend.problem_kw.get("diss_stages") is None
 
 
 def check_opaque_lindblad_grape(name="lindblad_opaque_wc"):
