@@ -576,6 +576,45 @@ int qocx_lindblad_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const u
                                  double first_step, double armijo, double shrink,
                                  int32_t max_backtracks, uint8_t* finished_out);
 
+/* ---- a control basis in the resident drivers ------------------------------------------------------
+ * The optimizer's parameters are P coefficients per control channel, the evaluated pulse is their image
+ * under a real matrix M [Nc][P]: u[b][j][c] = sum_p M[j][p] coef[b][p][c] (qocx_ctrlbasis.hip;
+ * qoc_amd/standard/controlbasis.py states the arithmetic). Both directions run in one defined order -
+ * the expansion over p = 0 .. P-1, the projection h[b][p][c] = sum_j M[j][p] g[b][j][c] over
+ * j = 0 .. Nc-1, acc = acc + M * x from +0.0, the product and the sum each rounded on its own - so a
+ * seed walks the host loop's trajectory bit for bit. The clip follows the complex-controls precedent
+ * above: the coefficients are never clipped, the expanded copy is.
+ *   *_opt_begin_basis  in the place of *_opt_begin / *_opt_begin_complex, after *_upload_controls of
+ *                      the start pulses (expanded by the caller): the driver keeps `coefficients`
+ *                      [B][P][channels] as its parameters, apart from the evaluation buffer, and M on
+ *                      the device in both orientations. The optimizer state (Adam moments, and what
+ *                      *_opt_lbfgs_begin allocates and checks against the free memory) is sized by
+ *                      P * channels per seed. complex_controls: channels 2k, 2k+1 are one control
+ *                      (the clip by modulus, the parameter order of L-BFGS), mapped channel by channel.
+ *                      QOCX_ERR_ARG for P < 1, a non-finite matrix, odd channels with
+ *                      complex_controls; QOCX_ERR_STATE without uploaded controls. A later
+ *                      *_opt_begin / *_opt_begin_complex clears the basis.
+ *   *_opt_clip         expands the coefficients into the evaluation buffer, then clips that buffer
+ *                      (per channel, or by modulus) as without a basis; the squaring capacity and the
+ *                      Lindblad sub-divisions follow from the clipped buffer as before.
+ *   *_opt_step, *_opt_lbfgs_step   keep the coefficients of the improved seeds beside their controls,
+ *                      project the last evaluation's gradients (control costs included) to
+ *                      [B][P][channels] and run the optimizer on the coefficients and that gradient.
+ *   *_opt_download_best_params   the coefficients [B][P][channels] behind the best controls;
+ *                      QOCX_ERR_STATE without a basis. */
+int qocx_opt_begin_basis(qocx_ctx* ctx, int32_t complex_controls, int32_t p, const double* matrix,
+                         const double* coefficients);
+int qocx_opt_download_best_params(qocx_ctx* ctx, double* params_out);
+int qocx_lindblad_opt_begin_basis(qocx_ctx* ctx, int32_t complex_controls, int32_t p,
+                                  const double* matrix, const double* coefficients);
+int qocx_lindblad_opt_download_best_params(qocx_ctx* ctx, double* params_out);
+/* The two maps alone, host arrays in and out, no state kept: matrix [nc][p];
+ * transpose = 0: in [batch][p][channels] -> out [batch][nc][channels] (expansion),
+ * transpose != 0: in [batch][nc][channels] -> out [batch][p][channels] (projection).
+ * A seed's numbers do not depend on the batch it is part of. */
+int qocx_control_basis_apply(qocx_ctx* ctx, int32_t transpose, int32_t batch, int32_t nc, int32_t p,
+                             int32_t channels, const double* matrix, const double* in, double* out);
+
 /* ---- host-side helpers of the multi-start GRAPE driver (no GPU work, no context) --------------
  * The reference's driver loop clips the controls and applies its optimizer plugin to ONE control
  * set per process (qoc/core/common.py:8-30, qoc/standard/optimizers/adam.py:110-165, sgd.py). The

@@ -16,7 +16,8 @@ declare a seed `finished`: such a seed leaves the loop as one stopped by min_err
 import numpy as np
 
 from qoc_amd.core import structure
-from qoc_amd.core.common import initialize_controls, strip_controls
+from qoc_amd.core.common import (initialize_coefficients, initialize_controls, slap_controls,
+                                 strip_controls)
 from qoc_amd.engine import PATH_LINDBLAD
 from qoc_amd.models import Dummy
 from qoc_amd.standard.optimizers import LBFGS, SGD, Adam
@@ -39,6 +40,8 @@ class BatchResult(object):
         self.global_best_error = None
         # Hamiltonian ensembles: per seed, the members' unweighted costs at the best controls
         self.member_errors = [None] * seed_count
+        # with a ControlBasis: per seed, the coefficients (P x control_count) behind best_controls
+        self.best_coefficients = [None] * seed_count
 
     @property
     def best(self):
@@ -49,6 +52,7 @@ class BatchResult(object):
             **{self.final_field: getattr(self, self.final_field)[b]})
         if self.member_errors[b] is not None:
             out.member_errors = self.member_errors[b]
+        out.best_coefficients = self.best_coefficients[b]
         return out
 
 
@@ -234,12 +238,25 @@ def batched_stepper(optimizer, params):
     return None
 
 
+def _coefficients_batch(params, pstate):
+    """The rows of params [B, P] as coefficient arrays (B x P x control_count) of a ControlBasis."""
+    shape = (params.shape[0],) + tuple(pstate.coefficients_shape)
+    if pstate.complex_controls:
+        half = params.shape[1] // 2
+        return (params[:, :half] + 1j * params[:, half:]).reshape(shape)
+    return params.reshape(shape)
+
+
 def _cost_format_batch(params, pstate):
     """_cost_format on all rows of params [B, P] at once: (B x Nc x K) controls, clipped in place
-    (a view of params for real controls, as in the single-seed driver), conditions per seed."""
+    (a view of params for real controls, as in the single-seed driver), conditions per seed. With a
+    ControlBasis the rows are coefficients: they stay as they are, their expansion is clipped."""
     B = params.shape[0]
     shape = (B,) + tuple(pstate.controls_shape)
-    if pstate.complex_controls:
+    basis = getattr(pstate, "control_basis", None)
+    if basis is not None:
+        controls = basis.expand(_coefficients_batch(params, pstate))
+    elif pstate.complex_controls:
         half = params.shape[1] // 2
         controls = (params[:, :half] + 1j * params[:, half:]).reshape(shape)
     else:
@@ -271,31 +288,51 @@ def _strip_batch(complex_controls, arrays):
 
 
 def prepare_seeds(initial_controls, complex_controls, control_count, control_eval_count,
-                  evolution_time, max_control_norms, impose_control_conditions, comm):
+                  evolution_time, max_control_norms, impose_control_conditions, comm,
+                  control_basis=None):
     """This rank's block of the seeds, checked as the single-seed drivers check one control array:
-    (comm, pstate for _cost_format_batch, params [B, P] in the optimizer's format)."""
+    (comm, pstate for _cost_format_batch, params [B, P] in the optimizer's format). With a
+    control_basis the seeds are coefficient arrays (seed_count x P x control_count) and so are the
+    parameters; their expansions are checked as start controls."""
     from qoc_amd import parallel
+    if control_basis is not None and initial_controls is None:
+        raise ValueError("with a control_basis, initial_controls must hold the initial "
+                         "coefficients (seed_count x P x control_count)")
     initial_controls = np.asarray(initial_controls)
     if initial_controls.ndim != 3:
-        raise ValueError("initial_controls must be (seed_count x control_eval_count x "
-                         "control_count), got shape {}".format(initial_controls.shape))
+        raise ValueError("initial_controls must be (seed_count x {} x control_count), got shape {}"
+                         "".format("control_eval_count" if control_basis is None else "P",
+                                   initial_controls.shape))
     comm = comm if comm is not None else parallel.SingleComm()
     lo, hi = parallel.shard_bounds(initial_controls.shape[0], comm.rank, comm.world)
     if max_control_norms is None:  # the default of initialize_controls, also for a rank without seeds
         max_control_norms = np.ones(control_count)
     seeds = []
     for b in range(lo, hi):
-        controls_b, max_control_norms = initialize_controls(
-            complex_controls, control_count, control_eval_count, evolution_time,
-            initial_controls[b], max_control_norms)
+        if control_basis is not None:
+            controls_b, _, max_control_norms = initialize_coefficients(
+                control_basis, complex_controls, control_count, control_eval_count,
+                evolution_time, initial_controls[b], max_control_norms)
+        else:
+            controls_b, max_control_norms = initialize_controls(
+                complex_controls, control_count, control_eval_count, evolution_time,
+                initial_controls[b], max_control_norms)
         seeds.append(np.array(controls_b))
     pstate = Dummy()
+    pstate.control_basis = control_basis
+    knots = control_eval_count
+    if control_basis is not None:
+        if control_basis.knot_count != control_eval_count:  # (also for a rank without seeds)
+            raise ValueError("control_basis maps to {} knots, control_eval_count is {}"
+                             "".format(control_basis.knot_count, control_eval_count))
+        knots = control_basis.coefficient_count
+        pstate.coefficients_shape = (knots, control_count)
     pstate.complex_controls = complex_controls
     pstate.controls_shape = (control_eval_count, control_count)
     pstate.max_control_norms = max_control_norms
     pstate.impose_control_conditions = impose_control_conditions
     params = (np.stack([strip_controls(complex_controls, c) for c in seeds]) if seeds
-              else np.zeros((0, control_eval_count * control_count)))
+              else np.zeros((0, knots * control_count)))
     return comm, pstate, np.array(params, dtype=np.float64)
 
 
@@ -306,6 +343,10 @@ def resident_route(stepper, optimizer, pstate, evaluator, batch):
     the backend's L-BFGS calls: a stand-in backend without them takes the host loop."""
     if type(optimizer) is LBFGS and not (hasattr(evaluator, "resident_lbfgs_capable")
                                          and evaluator.resident_lbfgs_capable()):
+        return False
+    # (a ControlBasis needs the backend's basis calls in the same way)
+    if getattr(pstate, "control_basis", None) is not None and not (
+            hasattr(evaluator, "resident_basis_capable") and evaluator.resident_basis_capable()):
         return False
     return (batch > 0 and stepper is not None and pstate.impose_control_conditions is None
             and not getattr(optimizer, "apply_scale_grads", False)
@@ -352,6 +393,9 @@ class ResidentOps(object):
             setattr(self, name, getattr(engine, prefix + name))
         for name in ("opt_lbfgs_begin", "opt_lbfgs_step"):
             setattr(self, name, getattr(engine, prefix + name, None))
+        # a ControlBasis (None on a backend without the calls)
+        self._opt_begin_basis = getattr(engine, prefix + "opt_begin_basis", None)
+        self._opt_download_best_params = getattr(engine, prefix + "opt_download_best_params", None)
 
     def upload_controls(self, controls):
         if self.control_costs:
@@ -363,6 +407,17 @@ class ResidentOps(object):
         return (structure.from_real_gradients(controls, self.complex_controls),
                 finals[..., None] if self.column_states else finals)
 
+    def opt_begin_basis(self, basis, coefficients):
+        """Instead of opt_begin, after upload_controls of the expanded start pulses: the driver's
+        parameters are `coefficients` (B x P x control_count, complex for complex controls)."""
+        self._opt_begin_basis(self.complex_controls, basis.matrix,
+                              structure.to_real_controls(coefficients, self.complex_controls))
+
+    def opt_download_best_params(self):
+        """The coefficients (B x P x control_count) behind the best controls."""
+        return structure.from_real_gradients(self._opt_download_best_params(),
+                                             self.complex_controls)
+
     def finish(self):
         if self.control_costs:  # evaluate_batch and the single-seed entry points keep them on the host
             self.engine.set_control_costs(self.path, self.complex_controls, [])
@@ -373,7 +428,8 @@ def run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iter
     """The loop with everything but the decisions on the device: ops.opt_clip -> ops.eval_resident
     -> B costs to the host -> ops.opt_step. `ops` is the engine's resident driver of one problem
     (upload_controls, opt_begin, opt_clip, eval_resident, download_costs, opt_step,
-    opt_download_best -> (controls [B, Nc, K], finals in the result's shape)); controls go in and
+    opt_download_best -> (controls [B, Nc, K], finals in the result's shape); with a ControlBasis
+    opt_begin_basis in the place of opt_begin and opt_download_best_params); controls go in and
     come back in the cost-function format (complex arrays for complex controls: ops holds them as
     two real channels each and keeps the optimizer's parameters unclipped, as _cost_format_batch
     does on the host). ops.finish(), if there is one, runs when the loop ends, however it ends."""
@@ -391,12 +447,20 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
     is_lbfgs = type(optimizer) is LBFGS
     _log_header(log_iteration_step, comm)
     shape = (B,) + tuple(pstate.controls_shape)
-    if pstate.complex_controls:
+    basis = getattr(pstate, "control_basis", None)
+    if basis is not None:
+        # the start pulses expanded here; from opt_begin_basis on the coefficients are the driver's
+        # parameters and every opt_clip expands them again on the device
+        coefficients = _coefficients_batch(params, pstate)
+        ops.upload_controls(basis.expand(coefficients))
+        ops.opt_begin_basis(basis, coefficients)
+    elif pstate.complex_controls:
         half = params.shape[1] // 2
         ops.upload_controls((params[:, :half] + 1j * params[:, half:]).reshape(shape))
+        ops.opt_begin()
     else:
         ops.upload_controls(params.reshape(shape))
-    ops.opt_begin()
+        ops.opt_begin()
     if is_lbfgs:
         ops.opt_lbfgs_begin(optimizer.history)
     active = np.ones(B, dtype=bool)
@@ -441,11 +505,14 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
         if still == 0:
             break
     best_controls, best_finals = ops.opt_download_best()
+    best_coefficients = ops.opt_download_best_params() if basis is not None else None
     finals = getattr(result, result.final_field)
     for b in range(B):
         if result.best_iteration[b] >= 0:
             result.best_controls[b] = best_controls[b]
             finals[b] = best_finals[b]
+            if basis is not None:
+                result.best_coefficients[b] = np.array(best_coefficients[b])
     return _finish(result, comm)
 
 
@@ -460,6 +527,8 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
     _log_header(log_iteration_step, comm)
     active = np.ones(B, dtype=bool)
     best_controls = best_finals = None
+    basis = getattr(pstate, "control_basis", None)
+    best_params = np.zeros_like(params) if basis is not None else None
     should_log = log_iteration_step != 0
     for iteration in range(iteration_count):
         # cost-function format of every seed (clipping acts in place on the optimizer's params
@@ -478,6 +547,8 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
                 best_finals = np.zeros_like(finals)
             best_controls[improved] = controls[improved]
             best_finals[improved] = finals[improved]
+            if basis is not None:
+                best_params[improved] = params[improved]
             result.best_error[improved] = errors[improved]
             result.best_iteration[improved] = iteration
         if should_log and (iteration % log_iteration_step == 0 or iteration == iteration_count - 1):
@@ -492,7 +563,10 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
         active &= ~(errors <= min_error)
         rows = np.nonzero(active)[0]
         if len(rows):
-            flat_grads = _strip_batch(pstate.complex_controls, np.asarray(grads))
+            grads = np.asarray(grads)
+            if basis is not None:  # d error / d coefficients (the derivative of the clip is ignored)
+                grads = basis.project(grads)
+            flat_grads = _strip_batch(pstate.complex_controls, grads)
             if stepper is not None and needs_error:
                 stepper.update(flat_grads, params, rows, errors)
                 active &= ~stepper.finished
@@ -513,4 +587,7 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
         if result.best_iteration[b] >= 0:
             result.best_controls[b] = best_controls[b]
             finals[b] = best_finals[b]
+            if basis is not None:
+                result.best_coefficients[b] = np.array(slap_controls(
+                    pstate.complex_controls, best_params[b], pstate.coefficients_shape))
     return _finish(result, comm)

@@ -105,9 +105,65 @@ def strip_controls(complex_controls, controls):
 
 def _cost_format(flat_controls, pstate):
     """optimizer format -> clipped, conditioned cost-function format of the single-seed GRAPE
-    drivers (schroedingerdiscrete.py:308-315, lindbladdiscrete.py:272-280)."""
-    controls = slap_controls(pstate.complex_controls, flat_controls, pstate.controls_shape)
+    drivers (schroedingerdiscrete.py:308-315, lindbladdiscrete.py:272-280). With a ControlBasis
+    the parameters are coefficients: they stay unclipped, their expansion - a copy - is clipped."""
+    basis = getattr(pstate, "control_basis", None)
+    if basis is not None:
+        controls = basis.expand(slap_controls(pstate.complex_controls, flat_controls,
+                                              pstate.coefficients_shape))
+    else:
+        controls = slap_controls(pstate.complex_controls, flat_controls, pstate.controls_shape)
     clip_control_norms(controls, pstate.max_control_norms)  # in place, aliases real params
     if pstate.impose_control_conditions is not None:
         controls = pstate.impose_control_conditions(controls)
     return controls
+
+
+def initialize_coefficients(control_basis, complex_controls, control_count, control_eval_count,
+                            evolution_time, initial_coefficients, max_control_norms):
+    """The checks of the drivers' control_basis keyword: initial_controls holds the coefficients
+    (P x control_count) of one seed, whose expansion must conform to max_control_norms as start
+    controls do. Returns (coefficients, expanded start controls, max_control_norms)."""
+    if not (hasattr(control_basis, "expand") and hasattr(control_basis, "project")):
+        raise ValueError("control_basis must be a qoc_amd.standard.ControlBasis")
+    if control_basis.knot_count != control_eval_count:
+        raise ValueError("control_basis maps to {} knots, control_eval_count is {}"
+                         "".format(control_basis.knot_count, control_eval_count))
+    if initial_coefficients is None:
+        raise ValueError("with a control_basis, initial_controls must hold the initial "
+                         "coefficients (P x control_count)")
+    coefficients = np.asarray(initial_coefficients)
+    shape = (control_basis.coefficient_count, control_count)
+    if coefficients.shape != shape:
+        raise ValueError("with this control_basis, initial_controls must be the coefficients "
+                         "{}, got shape {}".format(shape, coefficients.shape))
+    dtype = np.complex128 if np.iscomplexobj(coefficients) else np.float64
+    coefficients = np.array(coefficients, dtype=dtype)
+    controls, max_control_norms = initialize_controls(
+        complex_controls, control_count, control_eval_count, evolution_time,
+        control_basis.expand(coefficients), max_control_norms)
+    return coefficients, controls, max_control_norms
+
+
+def reject_basis_save(control_basis, save_file_path):
+    if control_basis is not None and save_file_path is not None:
+        raise NotImplementedError("save files are not written with a control_basis "
+                                  "(save_file_path must be None)")
+
+
+def _param_gradient(grads, pstate):
+    """d error / d controls (cost-function format) -> the gradient in the optimizer's format: with
+    a ControlBasis projected onto the coefficients first (the derivative of the clip is ignored)."""
+    basis = getattr(pstate, "control_basis", None)
+    if basis is not None:
+        grads = basis.project(grads)
+    return strip_controls(pstate.complex_controls, grads)
+
+
+def _coefficients_of(flat_controls, pstate):
+    """A copy of the optimizer's parameters as coefficients (P x control_count); None without a
+    ControlBasis."""
+    if getattr(pstate, "control_basis", None) is None:
+        return None
+    return np.array(slap_controls(pstate.complex_controls, flat_controls,
+                                  pstate.coefficients_shape))

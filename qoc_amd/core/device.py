@@ -156,6 +156,13 @@ class _Evaluator(object):
         """resident_capable() with a backend that also has the L-BFGS calls of the resident driver."""
         return self.resident_capable() and hasattr(self.backend, self.opt_prefix + "opt_lbfgs_step")
 
+    def resident_basis_capable(self):
+        """resident_capable() with a backend that also has the ControlBasis calls of the resident
+        driver."""
+        return (self.resident_capable()
+                and hasattr(self.backend, self.opt_prefix + "opt_begin_basis")
+                and hasattr(self.backend, self.opt_prefix + "opt_download_best_params"))
+
     def _prepare(self, device_controls):
         """Before the first pass of an evaluation (the Lindblad time tables)."""
 

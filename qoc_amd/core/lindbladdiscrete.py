@@ -13,7 +13,9 @@ the parity tolerances that follow from replacing an adaptive integrator).
 import numpy as np
 
 from qoc_amd.core import batch
-from qoc_amd.core.common import _cost_format, initialize_controls, strip_controls
+from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
+                                 initialize_coefficients, initialize_controls,
+                                 reject_basis_save, strip_controls)
 from qoc_amd.core.device import LindbladEvaluator
 from qoc_amd.core.structure import NonLinearHamiltonianError
 from qoc_amd.engine import PATH_LINDBLAD
@@ -83,23 +85,36 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
                             iteration_count=1000, lindblad_data=None, log_iteration_step=10,
                             max_control_norms=None, min_error=0, optimizer=Adam(),
                             save_file_path=None, save_intermediate_densities=False,
-                            save_iteration_step=0):
+                            save_iteration_step=0, control_basis=None):
     """
     Optimize time-discrete controls for the evolution of a set of densities under the Lindblad
     equation (GRAPE). Arguments as in the reference (lindbladdiscrete.py:106-212).
+    control_basis (qoc_amd.standard.ControlBasis, optional): as in grape_schroedinger_discrete -
+    initial_controls holds the coefficients (P x control_count), the expanded pulse clipped to
+    max_control_norms is evaluated, the result gains best_coefficients.
     Returns GrapeLindbladResult{best_controls, best_error, best_final_densities,
     best_iteration}.
     """
     _reject_ensemble(hamiltonian)
-    initial_controls, max_control_norms = initialize_controls(
-        complex_controls, control_count, control_eval_count, evolution_time, initial_controls,
-        max_control_norms)
+    reject_basis_save(control_basis, save_file_path)
+    coefficients = None
+    if control_basis is not None:
+        coefficients, initial_controls, max_control_norms = initialize_coefficients(
+            control_basis, complex_controls, control_count, control_eval_count, evolution_time,
+            initial_controls, max_control_norms)
+    else:
+        initial_controls, max_control_norms = initialize_controls(
+            complex_controls, control_count, control_eval_count, evolution_time,
+            initial_controls, max_control_norms)
     pstate = GrapeLindbladDiscreteState(
         complex_controls, control_count, control_eval_count, cost_eval_step, costs,
         evolution_time, hamiltonian, impose_control_conditions, initial_controls,
         initial_densities, interpolation_policy, iteration_count, lindblad_data,
         log_iteration_step, max_control_norms, min_error, optimizer, save_file_path,
         save_intermediate_densities, save_iteration_step, system_eval_count)
+    pstate.control_basis = control_basis
+    if control_basis is not None:
+        pstate.coefficients_shape = coefficients.shape
     pstate.evaluator = LindbladEvaluator(
         evolution_time, initial_densities, system_eval_count, hamiltonian=hamiltonian,
         lindblad_data=lindblad_data, control_count=control_count,
@@ -110,7 +125,8 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
     reporter = Dummy()
     reporter.iteration = 0
     result = GrapeLindbladResult()
-    flat_controls = strip_controls(pstate.complex_controls, pstate.initial_controls)
+    flat_controls = strip_controls(pstate.complex_controls, pstate.initial_controls
+                                   if control_basis is None else coefficients)
     pstate.optimizer.run(_eld_wrap, pstate.iteration_count, flat_controls, _eldj_wrap,
                          args=(pstate, reporter, result))
     return result
@@ -125,6 +141,7 @@ def _eld_wrap(controls, pstate, reporter, result):
 
 
 def _eldj_wrap(controls, pstate, reporter, result):
+    params = controls
     controls = _cost_format(controls, pstate)
     save_densities = pstate.save_intermediate_densities_
     error, grads, final_densities, step_densities = pstate.evaluator.evaluate(
@@ -135,12 +152,13 @@ def _eldj_wrap(controls, pstate, reporter, result):
         pstate.save_all_intermediate_densities(reporter.iteration, step_densities)
     if error < result.best_error:  # strict, as lindbladdiscrete.py:334
         result.best_controls = controls
+        result.best_coefficients = _coefficients_of(params, pstate)
         result.best_error = error
         result.best_final_densities = final_densities
         result.best_iteration = reporter.iteration
     pstate.log_and_save(controls, error, final_densities, grads, reporter.iteration)
     reporter.iteration += 1
-    return strip_controls(pstate.complex_controls, grads), bool(error <= pstate.min_error)
+    return _param_gradient(grads, pstate), bool(error <= pstate.min_error)
 
 
 # ---- multi-start GRAPE: B independent optimisations in lock step (core/batch.py) -----------------
@@ -167,7 +185,7 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
                                   interpolation_policy=InterpolationPolicy.LINEAR,
                                   iteration_count=1000, lindblad_data=None, log_iteration_step=10,
                                   max_control_norms=None, min_error=0, optimizer=Adam(),
-                                  comm=None):
+                                  comm=None, control_basis=None):
     """
     Multi-start Lindblad GRAPE: B = len(initial_controls) independent optimisations of the same
     problem, one batched device evaluation per iteration. Seed b follows EXACTLY the iteration of
@@ -185,12 +203,16 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     (qocx_lindblad_opt_*; real or complex controls); otherwise the host drives
     LindbladEvaluator.evaluate_batch. Both routes give the same numbers to rounding (bit for bit
     without costs of the controls and without a clip acting on a complex control).
+    control_basis (qoc_amd.standard.ControlBasis, optional): as in
+    grape_schroedinger_discrete_batch - initial_controls holds the coefficients
+    (B x P x control_count), the result gains best_coefficients per seed
+    (qocx_lindblad_opt_begin_basis on the resident route).
     Returns GrapeLindbladBatchResult.
     """
     _reject_ensemble(hamiltonian)
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
-        max_control_norms, impose_control_conditions, comm)
+        max_control_norms, impose_control_conditions, comm, control_basis)
     B = params.shape[0]
     evaluator = LindbladEvaluator(
         evolution_time, initial_densities, system_eval_count, hamiltonian=hamiltonian,

@@ -10,7 +10,9 @@ MI355X through qoc_amd.core.device.SchroedingerEvaluator.
 import numpy as np
 
 from qoc_amd.core import batch
-from qoc_amd.core.common import _cost_format, initialize_controls, strip_controls
+from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
+                                 initialize_coefficients, initialize_controls,
+                                 reject_basis_save, strip_controls)
 from qoc_amd.core.device import SchroedingerEvaluator
 from qoc_amd.engine import PATH_SCHROEDINGER
 from qoc_amd.models import (Dummy, EvolveSchroedingerDiscreteState, EvolveSchroedingerResult,
@@ -79,25 +81,42 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
                                 iteration_count=1000, log_iteration_step=10,
                                 magnus_policy=MagnusPolicy.M2, max_control_norms=None,
                                 min_error=0, optimizer=Adam(), save_file_path=None,
-                                save_intermediate_states=False, save_iteration_step=0):
+                                save_intermediate_states=False, save_iteration_step=0,
+                                control_basis=None):
     """
     Optimize time-discrete controls for the evolution of a set of states (GRAPE).
     Arguments as in the reference (schroedingerdiscrete.py:106-212).
+    control_basis (qoc_amd.standard.ControlBasis, optional): the optimizer's parameters are the
+    coefficients (P x control_count) of the pulse in that basis and initial_controls holds their
+    start. Each iteration evaluates the expanded pulse clipped to max_control_norms (the
+    coefficients are never clipped; the derivative of the clip is ignored, as for complex
+    controls); costs of the controls and impose_control_conditions act on that pulse. The result's
+    best_controls is the evaluated pulse, best_coefficients the coefficients behind it.
     Returns GrapeSchroedingerResult{best_controls, best_error, best_final_states, best_iteration}.
     With a HamiltonianEnsemble the error is the weighted sum over its members, best_final_states
     has a member axis, and member_errors holds each member's unweighted device cost at
     best_controls (one forward evaluation after the loop).
     """
     _check_ensemble_save(hamiltonian, save_file_path)
-    initial_controls, max_control_norms = initialize_controls(
-        complex_controls, control_count, control_eval_count, evolution_time, initial_controls,
-        max_control_norms)
+    reject_basis_save(control_basis, save_file_path)
+    coefficients = None
+    if control_basis is not None:
+        coefficients, initial_controls, max_control_norms = initialize_coefficients(
+            control_basis, complex_controls, control_count, control_eval_count, evolution_time,
+            initial_controls, max_control_norms)
+    else:
+        initial_controls, max_control_norms = initialize_controls(
+            complex_controls, control_count, control_eval_count, evolution_time,
+            initial_controls, max_control_norms)
     pstate = GrapeSchroedingerDiscreteState(
         complex_controls, control_count, control_eval_count, cost_eval_step, costs,
         evolution_time, hamiltonian, impose_control_conditions, initial_controls, initial_states,
         interpolation_policy, iteration_count, log_iteration_step, max_control_norms,
         magnus_policy, min_error, optimizer, save_file_path, save_intermediate_states,
         save_iteration_step, system_eval_count)
+    pstate.control_basis = control_basis
+    if control_basis is not None:
+        pstate.coefficients_shape = coefficients.shape
     pstate.evaluator = SchroedingerEvaluator(
         evolution_time, hamiltonian, initial_states, system_eval_count,
         control_count=control_count, control_eval_count=control_eval_count,
@@ -108,7 +127,8 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     reporter = Dummy()
     reporter.iteration = 0
     result = GrapeSchroedingerResult()
-    flat_controls = strip_controls(pstate.complex_controls, pstate.initial_controls)
+    flat_controls = strip_controls(pstate.complex_controls, pstate.initial_controls
+                                   if control_basis is None else coefficients)
     pstate.optimizer.run(_esd_wrap, pstate.iteration_count, flat_controls, _esdj_wrap,
                          args=(pstate, reporter, result))
     if (getattr(pstate.evaluator, "ensemble", None) is not None
@@ -129,6 +149,7 @@ def _esd_wrap(controls, pstate, reporter, result):
 
 def _esdj_wrap(controls, pstate, reporter, result):
     """jacobian(params, *args) -> (grads, terminate); one device evaluation per call."""
+    params = controls
     controls = _cost_format(controls, pstate)
     save_states = pstate.save_intermediate_states_
     error, grads, final_states, step_states = pstate.evaluator.evaluate(
@@ -139,12 +160,13 @@ def _esdj_wrap(controls, pstate, reporter, result):
         pstate.save_all_intermediate_states(reporter.iteration, step_states)
     if error < result.best_error:  # strict, as schroedingerdiscrete.py:333
         result.best_controls = controls
+        result.best_coefficients = _coefficients_of(params, pstate)
         result.best_error = error
         result.best_final_states = final_states
         result.best_iteration = reporter.iteration
     pstate.log_and_save(controls, error, final_states, grads, reporter.iteration)
     reporter.iteration += 1
-    return strip_controls(pstate.complex_controls, grads), bool(error <= pstate.min_error)
+    return _param_gradient(grads, pstate), bool(error <= pstate.min_error)
 
 
 # ---- multi-start GRAPE: B independent optimisations in lock step ---------------
@@ -171,7 +193,8 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
                                       interpolation_policy=InterpolationPolicy.LINEAR,
                                       iteration_count=1000, log_iteration_step=10,
                                       magnus_policy=MagnusPolicy.M2, max_control_norms=None,
-                                      min_error=0, optimizer=Adam(), comm=None):
+                                      min_error=0, optimizer=Adam(), comm=None,
+                                      control_basis=None):
     """
     Multi-start GRAPE: B = len(initial_controls) independent optimisations of the same problem,
     one batched device evaluation per iteration (the engine's batch axis; the reference runs one
@@ -194,11 +217,16 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     state resident on the device. With LBFGS a seed whose line search is exhausted is `finished`:
     frozen at its last accepted point like a seed stopped by min_error. LBFGSB (SciPy's loop) is
     single-seed only.
+    control_basis (qoc_amd.standard.ControlBasis, optional): as in grape_schroedinger_discrete, per
+    seed - initial_controls holds the coefficients (B x P x control_count), the result's
+    best_coefficients[b] the coefficients behind best_controls[b]. On the resident route the
+    coefficients, the optimizer state sized by them and the map itself stay on the device
+    (qocx_opt_begin_basis, qocx_ctrlbasis.hip).
     Returns GrapeSchroedingerBatchResult.
     """
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
-        max_control_norms, impose_control_conditions, comm)
+        max_control_norms, impose_control_conditions, comm, control_basis)
     B = params.shape[0]
     # (latency mode up to 128 evaluated items: an ensemble evaluates M per seed)
     items = B * (hamiltonian.member_count if isinstance(hamiltonian, HamiltonianEnsemble) else 1)

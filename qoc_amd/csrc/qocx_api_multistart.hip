@@ -129,18 +129,90 @@ SeedView lindblad_seeds(qocx_ctx* ctx) {
                     (size_t)lb.S * dump_elems(lb.n)};
 }
 
-// the seeds' optimizer states, zeroed; complex controls: the parameters start as the seeds' controls
-int multistart_begin(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, int batch, bool complex_controls) {
-    const size_t total = v.total();
-    if (ms.opt_m.ensure(total) || ms.opt_v.ensure(total) || ms.opt_best_controls.ensure(total) ||
+// What the optimizer works on, as distinct from what is evaluated (the SeedView): the seeds' controls
+// and their gradients themselves, the unclipped copy of complex controls, or - with a control basis -
+// the coefficients and the projected gradients, P * channels per seed. Every optimizer state (Adam
+// moments, the L-BFGS vectors, ring and capacity check) is sized by it.
+struct ParamView {
+    double* params;       // [seeds][per_seed]
+    const double* grads;  // [seeds][per_seed]
+    size_t per_seed, total;
+};
+
+// (the sizes alone are valid from the top of multistart_begin on: they follow from ms.basis_P)
+ParamView optimizer_params(MultiStart& ms, const SeedView& v) {
+    if (ms.basis_P > 0) {
+        const size_t per = (size_t)ms.basis_P * v.channels;
+        return ParamView{ms.opt_params.p, ms.basis_grads.p, per, (size_t)v.seeds * per};
+    }
+    return ParamView{ms.complex_controls ? ms.opt_params.p : v.controls, v.grads, v.per_seed(), v.total()};
+}
+
+// A control basis for multistart_begin: M [nc][P] and the seeds' coefficients [seeds][P][channels] on
+// the host (P = 0: none)
+struct BasisStart {
+    int P = 0;
+    const double* matrix = nullptr;
+    const double* coefficients = nullptr;
+};
+
+// the seeds' optimizer states, zeroed; complex controls: the parameters start as the seeds' controls;
+// a control basis: the parameters are its coefficients
+int multistart_begin(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, int batch, bool complex_controls,
+                     const BasisStart& basis = BasisStart()) {
+    ms.basis_P = 0;
+    std::vector<double> transposed;
+    if (basis.P > 0) {
+        ms.batch = 0;  // (until the basis stands)
+        if (complex_controls && v.channels % 2)
+            return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
+        const size_t entries = (size_t)v.nc * basis.P;
+        for (size_t i = 0; i < entries; ++i)
+            if (!std::isfinite(basis.matrix[i])) return fail(QOCX_ERR_ARG, "non-finite basis matrix");
+        if ((size_t)basis.P * v.channels > 65535u * 256u)
+            return fail(QOCX_ERR_ARG, "coefficient arrays too large for the optimizer kernels' grids");
+        transposed.resize(entries);
+        for (int j = 0; j < v.nc; ++j)
+            for (int p = 0; p < basis.P; ++p) transposed[(size_t)p * v.nc + j] = basis.matrix[(size_t)j * basis.P + p];
+        ms.basis_P = basis.P;
+    }
+    const size_t total = v.total(), ptotal = optimizer_params(ms, v).total;
+    if (ms.opt_m.ensure(ptotal) || ms.opt_v.ensure(ptotal) || ms.opt_best_controls.ensure(total) ||
         ms.opt_best_final.ensure((size_t)v.seeds * v.final_elems) ||
-        ms.opt_flags.ensure(2 * (size_t)v.seeds) || ms.opt_max_norms.ensure((size_t)v.channels))
+        ms.opt_flags.ensure(2 * (size_t)v.seeds) || ms.opt_max_norms.ensure((size_t)v.channels)) {
+        ms.basis_P = 0;
         return QOCX_ERR_HIP;
-    HIP_TRY(hipMemsetAsync(ms.opt_m.p, 0, total * sizeof(double), ctx->stream));
-    HIP_TRY(hipMemsetAsync(ms.opt_v.p, 0, total * sizeof(double), ctx->stream));
-    ms.batch = batch;
+    }
+    HIP_TRY(hipMemsetAsync(ms.opt_m.p, 0, ptotal * sizeof(double), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ms.opt_v.p, 0, ptotal * sizeof(double), ctx->stream));
     ms.lbfgs_history = 0;  // (L-BFGS state is set up per batch: qocx_opt_lbfgs_begin)
     ms.complex_controls = false;
+    if (basis.P > 0) {
+        const size_t entries = (size_t)v.nc * basis.P;
+        if (ms.opt_params.ensure(ptotal) || ms.opt_best_params.ensure(ptotal) || ms.basis_grads.ensure(ptotal) ||
+            ms.basis_matrix.ensure(entries) || ms.basis_matrix_t.ensure(entries)) {
+            ms.basis_P = 0;
+            return QOCX_ERR_HIP;
+        }
+        hipError_t e = hipMemcpyAsync(ms.basis_matrix.p, basis.matrix, entries * sizeof(double),
+                                      hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(ms.basis_matrix_t.p, transposed.data(), entries * sizeof(double),
+                               hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(ms.opt_params.p, basis.coefficients, ptotal * sizeof(double),
+                               hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(ms.opt_best_params.p, 0, ptotal * sizeof(double), ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the arrays are the caller's (and local) memory
+        if (e != hipSuccess) {
+            ms.basis_P = 0;
+            return fail(QOCX_ERR_HIP, std::string("control basis upload: ") + hipGetErrorString(e));
+        }
+        ms.complex_controls = complex_controls;
+        ms.batch = batch;
+        return 0;
+    }
+    ms.batch = batch;
     if (!complex_controls) return 0;
     if (v.channels % 2) return fail(QOCX_ERR_ARG, "complex controls need an even number of channels");
     if (ms.opt_params.ensure(total)) return QOCX_ERR_HIP;
@@ -156,7 +228,14 @@ int multistart_clip(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const doub
     const int Kn = ms.complex_controls ? v.channels / 2 : v.channels;
     HIP_TRY(hipMemcpyAsync(ms.opt_max_norms.p, max_norms, Kn * sizeof(double), hipMemcpyHostToDevice,
                            ctx->stream));
-    if (ms.complex_controls)
+    if (ms.basis_P > 0) {  // the coefficients expanded into the evaluation buffer, which is then clipped
+        qocx::launch_basis_expand(ms.basis_matrix_t.p, ms.opt_params.p, v.controls, v.seeds, v.nc, ms.basis_P,
+                                  v.channels, ctx->stream);
+        if (ms.complex_controls)  // (in place: every thread reads its pair before it writes it)
+            qocx::launch_clip_complex(v.controls, v.controls, v.total() / 2, Kn, ms.opt_max_norms.p, ctx->stream);
+        else
+            qocx::launch_clip_controls(v.controls, v.total(), v.channels, ms.opt_max_norms.p, ctx->stream);
+    } else if (ms.complex_controls)
         qocx::launch_clip_complex(ms.opt_params.p, v.controls, v.total() / 2, Kn, ms.opt_max_norms.p,
                                   ctx->stream);
     else
@@ -172,20 +251,38 @@ struct StepRule {
     double clip_grads;
 };
 
-// keeps the controls and final states of the improved seeds, then steps the seeds flagged in `update`
-int multistart_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const StepRule& rule,
-                    const uint8_t* improved, const uint8_t* update) {
+// The head of every optimizer step: the flags to the device, the controls and final states of the
+// improved seeds kept; with a control basis their coefficients too, and the evaluation's gradients
+// projected onto the coefficients. Returns what the optimizer kernel then works on.
+int multistart_keep_best(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const uint8_t* improved,
+                         const uint8_t* update, ParamView& pv) {
     const int B = v.seeds;
     HIP_TRY(hipMemcpyAsync(ms.opt_flags.p, improved, B, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ms.opt_flags.p + B, update, B, hipMemcpyHostToDevice, ctx->stream));
     qocx::launch_keep_best(v.controls, ms.opt_best_controls.p, v.per_seed(), v.finals, ms.opt_best_final.p,
                            v.final_elems, ms.opt_flags.p, B, ctx->stream);
+    pv = optimizer_params(ms, v);
+    if (ms.basis_P > 0) {
+        qocx::launch_keep_best(ms.opt_params.p, ms.opt_best_params.p, pv.per_seed, nullptr, nullptr, 0,
+                               ms.opt_flags.p, B, ctx->stream);
+        qocx::launch_basis_project(ms.basis_matrix.p, v.grads, ms.basis_grads.p, B, v.nc, ms.basis_P, v.channels,
+                                   ctx->stream);
+    }
+    return 0;
+}
+
+// keeps the controls and final states of the improved seeds, then steps the seeds flagged in `update`
+int multistart_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const StepRule& rule,
+                    const uint8_t* improved, const uint8_t* update) {
+    const int B = v.seeds;
+    ParamView pv;
+    if (int rc = multistart_keep_best(ctx, ms, v, improved, update, pv)) return rc;
     qocx::OptimArgs a;
     a.kind = rule.kind;
-    a.params = ms.complex_controls ? ms.opt_params.p : v.controls; a.grads = v.grads;
+    a.params = pv.params; a.grads = pv.grads;
     a.moment = ms.opt_m.p; a.square_moment = ms.opt_v.p;
     a.update = ms.opt_flags.p + B;
-    a.per_seed = v.per_seed();
+    a.per_seed = pv.per_seed;
     a.learning_rate = rule.learning_rate; a.beta_1 = rule.beta_1; a.beta_2 = rule.beta_2;
     a.one_m_b1 = 1 - rule.beta_1; a.one_m_b2 = 1 - rule.beta_2;
     a.epsilon = rule.epsilon; a.corr_1 = rule.corr_1; a.corr_2 = rule.corr_2;
@@ -201,7 +298,7 @@ int multistart_lbfgs_begin(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, int
     if (history < 1 || history > qocx::LBFGS_MAX_HISTORY)
         return fail(QOCX_ERR_ARG, "history must be in 1..64");
     ms.lbfgs_history = 0;
-    const size_t total = v.total(), ring = total * (size_t)history;
+    const size_t total = optimizer_params(ms, v).total, ring = total * (size_t)history;
     const size_t bytes = (3 * total + 2 * ring + (size_t)v.seeds * history) * sizeof(double) +
                          (size_t)v.seeds * (sizeof(qocx::LbfgsSeed) + 1);
     size_t held = 0;  // (what a previous run of the same size left allocated is taken again)
@@ -239,17 +336,15 @@ struct LbfgsRule {
 int multistart_lbfgs_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const LbfgsRule& rule,
                           const uint8_t* improved, const uint8_t* update, uint8_t* finished_out) {
     const int B = v.seeds;
-    HIP_TRY(hipMemcpyAsync(ms.opt_flags.p, improved, B, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ms.opt_flags.p + B, update, B, hipMemcpyHostToDevice, ctx->stream));
-    qocx::launch_keep_best(v.controls, ms.opt_best_controls.p, v.per_seed(), v.finals, ms.opt_best_final.p,
-                           v.final_elems, ms.opt_flags.p, B, ctx->stream);
+    ParamView pv;
+    if (int rc = multistart_keep_best(ctx, ms, v, improved, update, pv)) return rc;
     qocx::LbfgsArgs a;
-    a.params = ms.complex_controls ? ms.opt_params.p : v.controls;
-    a.grads = v.grads; a.cost = v.cost;
+    a.params = pv.params;
+    a.grads = pv.grads; a.cost = v.cost;
     a.x = ms.lb_x.p; a.g = ms.lb_g.p; a.d = ms.lb_d.p; a.s = ms.lb_s.p; a.y = ms.lb_y.p;
     a.rho = ms.lb_rho.p; a.seed = ms.lb_seed.p;
     a.update = ms.opt_flags.p + B; a.finished = ms.lb_finished.p;
-    a.per_seed = v.per_seed();
+    a.per_seed = pv.per_seed;
     a.interleaved = ms.complex_controls ? 1 : 0;
     a.history = ms.lbfgs_history;
     a.first_step = rule.first_step; a.armijo = rule.armijo; a.shrink = rule.shrink;
@@ -276,22 +371,42 @@ int multistart_download_best(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, d
     return 0;
 }
 
-int schroedinger_opt_begin(qocx_ctx* ctx, bool complex_controls) {
+// the coefficients [seeds][P][channels] of the best so far (a driver begun with a control basis)
+int multistart_download_best_params(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, double* params_out) {
+    if (!params_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (ms.basis_P < 1) return fail(QOCX_ERR_STATE, "the driver was not begun with a control basis");
+    HIP_TRY(hipMemcpyAsync(params_out, ms.opt_best_params.p, optimizer_params(ms, v).total * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int schroedinger_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& basis = BasisStart()) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem || ctx->B < 1 || ctx->K < 1 || ctx->explicit_mode)
         return fail(QOCX_ERR_STATE, "qocx_opt_begin needs uploaded controls of a structured problem");
     HIP_TRY(hipSetDevice(ctx->device));
     // (the seeds' optimizer states; the best final states of every item)
-    return multistart_begin(ctx, ctx->ms, schroedinger_seeds(ctx), ctx->B, complex_controls);
+    return multistart_begin(ctx, ctx->ms, schroedinger_seeds(ctx), ctx->B, complex_controls, basis);
 }
 
-int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls) {
+int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& basis = BasisStart()) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
     if (!lb.has_problem || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin needs resident Lindblad controls");
     HIP_TRY(hipSetDevice(ctx->device));
-    return multistart_begin(ctx, lb.ms, lindblad_seeds(ctx), lb.res_B, complex_controls);
+    return multistart_begin(ctx, lb.ms, lindblad_seeds(ctx), lb.res_B, complex_controls, basis);
+}
+
+// the arguments of *_opt_begin_basis, checked
+int basis_start(int32_t p, const double* matrix, const double* coefficients, BasisStart& out) {
+    if (p < 1) return fail(QOCX_ERR_ARG, "a control basis needs P >= 1 coefficients");
+    if (!matrix || !coefficients) return fail(QOCX_ERR_ARG, "NULL argument");
+    out.P = p;
+    out.matrix = matrix;
+    out.coefficients = coefficients;
+    return 0;
 }
 
 }  // namespace
@@ -303,6 +418,20 @@ extern "C" {
 int qocx_opt_begin(qocx_ctx* ctx) { return schroedinger_opt_begin(ctx, false); }
 
 int qocx_opt_begin_complex(qocx_ctx* ctx) { return schroedinger_opt_begin(ctx, true); }
+
+int qocx_opt_begin_basis(qocx_ctx* ctx, int32_t complex_controls, int32_t p, const double* matrix,
+                         const double* coefficients) {
+    BasisStart basis;
+    if (int rc = basis_start(p, matrix, coefficients, basis)) return rc;
+    return schroedinger_opt_begin(ctx, complex_controls != 0, basis);
+}
+
+int qocx_opt_download_best_params(qocx_ctx* ctx, double* params_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return multistart_download_best_params(ctx, ctx->ms, schroedinger_seeds(ctx), params_out);
+}
 
 int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     if (!ctx || !max_norms) return fail(QOCX_ERR_ARG, "NULL argument");
@@ -407,6 +536,22 @@ int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_ou
 int qocx_lindblad_opt_begin(qocx_ctx* ctx) { return lindblad_opt_begin(ctx, false); }
 
 int qocx_lindblad_opt_begin_complex(qocx_ctx* ctx) { return lindblad_opt_begin(ctx, true); }
+
+int qocx_lindblad_opt_begin_basis(qocx_ctx* ctx, int32_t complex_controls, int32_t p, const double* matrix,
+                                  const double* coefficients) {
+    BasisStart basis;
+    if (int rc = basis_start(p, matrix, coefficients, basis)) return rc;
+    return lindblad_opt_begin(ctx, complex_controls != 0, basis);
+}
+
+int qocx_lindblad_opt_download_best_params(qocx_ctx* ctx, double* params_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return multistart_download_best_params(ctx, lb.ms, lindblad_seeds(ctx), params_out);
+}
 
 int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     if (!ctx || !max_norms) return fail(QOCX_ERR_ARG, "NULL argument");
@@ -629,6 +774,34 @@ int qocx_eval_control_costs(qocx_ctx* ctx, int32_t path, int32_t batch, const do
     HIP_TRY(hipMemcpyAsync(cost_out, cc->cost.p, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (grad_out)
         HIP_TRY(hipMemcpyAsync(grad_out, cc->grad.p, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_control_basis_apply(qocx_ctx* ctx, int32_t transpose, int32_t batch, int32_t nc, int32_t p,
+                             int32_t channels, const double* matrix, const double* in, double* out) {
+    if (!ctx || !matrix || !in || !out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (batch < 1 || nc < 1 || p < 1 || channels < 1) return fail(QOCX_ERR_ARG, "batch, nc, p and channels must be >= 1");
+    const size_t entries = (size_t)nc * p;
+    const size_t wide = (size_t)batch * nc * channels, narrow = (size_t)batch * p * channels;
+    if ((wide + 255) / 256 > 0x7fffffffu || (narrow + 255) / 256 > 0x7fffffffu)
+        return fail(QOCX_ERR_ARG, "arrays too large for the basis kernels' grids");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // (each kernel reads the matrix in the orientation in which its threads' index is contiguous)
+    std::vector<double> mat(matrix, matrix + entries);
+    if (!transpose)
+        for (int j = 0; j < nc; ++j)
+            for (int q = 0; q < p; ++q) mat[(size_t)q * nc + j] = matrix[(size_t)j * p + q];
+    const size_t in_count = transpose ? wide : narrow, out_count = transpose ? narrow : wide;
+    DevBuf<double> dmat, din, dout;
+    if (dmat.upload(mat, ctx->stream) || din.ensure(in_count) || dout.ensure(out_count)) return QOCX_ERR_HIP;
+    HIP_TRY(hipMemcpyAsync(din.p, in, in_count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (transpose)
+        qocx::launch_basis_project(dmat.p, din.p, dout.p, batch, nc, p, channels, ctx->stream);
+    else
+        qocx::launch_basis_expand(dmat.p, din.p, dout.p, batch, nc, p, channels, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, dout.p, out_count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -431,6 +431,15 @@ void launch_optimizer_update(const OptimArgs& a, int batch, hipStream_t st);
 void launch_clip_complex(const double* params, double* controls, size_t pairs, int k,
                          const double* max_norms, hipStream_t st);
 
+// The linear map of a control basis (qocx_ctrlbasis.hip; qoc_amd/standard/controlbasis.py): each
+// output summed in increasing index, acc = acc + M * x from +0.0, product and sum rounded on their own
+// matrix_t [P][Nc], coef [B][P][C] -> out [B][Nc][C]
+void launch_basis_expand(const double* matrix_t, const double* coef, double* out, int batch, int nc,
+                         int p_count, int channels, hipStream_t st);
+// matrix [Nc][P], grads [B][Nc][C] -> out [B][P][C]
+void launch_basis_project(const double* matrix, const double* grads, double* out, int batch, int nc,
+                          int p_count, int channels, hipStream_t st);
+
 // L-BFGS with Armijo backtracking for the seeds of the multi-start driver (qocx_lbfgs.hip;
 // qoc_amd/standard/optimizers/lbfgs.py is the statement of the algorithm)
 enum { LBFGS_MAX_HISTORY = 64 };

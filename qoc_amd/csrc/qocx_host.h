@@ -125,6 +125,12 @@ struct MultiStart {
     DevBuf<double> lb_x, lb_g, lb_d, lb_s, lb_y, lb_rho;
     DevBuf<qocx::LbfgsSeed> lb_seed;
     DevBuf<unsigned char> lb_finished;
+    // a control basis (qocx_opt_begin_basis): opt_params are then the coefficients [B][P][channels],
+    // the seed controls their expanded, clipped image
+    DevBuf<double> basis_matrix, basis_matrix_t;  // M [Nc][P] (projection), its transpose [P][Nc] (expansion)
+    DevBuf<double> basis_grads;                   // [B][P][channels]: the projected gradients
+    DevBuf<double> opt_best_params;               // [B][P][channels]: the coefficients of the best so far
+    int basis_P = 0;                  // 0: no basis
     int lbfgs_history = 0;            // 0: no L-BFGS state for this batch
     int batch = 0;                    // the path's batch the states were set up for (0: none)
     bool complex_controls = false;    // qocx_opt_begin_complex / qocx_lindblad_opt_begin_complex

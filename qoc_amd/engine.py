@@ -202,6 +202,12 @@ SIGNATURES = {
     "qocx_lindblad_opt_lbfgs_begin": (ctypes.c_int, [_VP, _I32]),
     "qocx_lindblad_opt_lbfgs_step": (ctypes.c_int, [_VP, _U8P, _U8P, ctypes.c_double,
                                                     ctypes.c_double, ctypes.c_double, _I32, _U8P]),
+    "qocx_opt_begin_basis": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p]),
+    "qocx_opt_download_best_params": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_lindblad_opt_begin_basis": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p]),
+    "qocx_lindblad_opt_download_best_params": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_control_basis_apply": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _c_double_p,
+                                                _c_double_p, _c_double_p]),
     "qocx_host_clip_controls": (ctypes.c_int, [_c_double_p, _I64, _I64, _I32, _c_double_p]),
     "qocx_host_optimizer_update": (ctypes.c_int, [
         _I32, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _I64, ctypes.POINTER(_I64), _I64,
@@ -272,6 +278,7 @@ class Engine(object):
         self._quadratic_count = 0
         self._keepalive = []
         self.batch = 0
+        self._basis_P = {}  # path -> coefficients per channel of the resident driver's basis
 
     # -- plumbing ----------------------------------------------------------------------------
     def _check(self, code):
@@ -709,8 +716,44 @@ class Engine(object):
         self._check(call(self._ctx, _dp(controls), _dp(final)))
         return controls, final
 
+    def _opt_begin_basis(self, call, path, complex_controls, matrix, coefficients):
+        nc, channels = self._control_channels(path)
+        matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+        if matrix.ndim != 2 or matrix.shape[0] != nc:
+            raise ValueError("the basis matrix must be ({} x P), got shape {}".format(nc, matrix.shape))
+        P = matrix.shape[1]
+        coefficients = np.ascontiguousarray(coefficients, dtype=np.float64)
+        if P > 0:
+            coefficients = coefficients.reshape(-1, P, channels)
+            if coefficients.shape[0] != self._resident_batch(path) > 0:
+                raise ValueError("coefficients for {} seeds, {} are resident".format(
+                    coefficients.shape[0], self._resident_batch(path)))
+        self._basis_P[path] = 0
+        self._check(call(self._ctx, int(bool(complex_controls)), P, _dp(matrix), _dp(coefficients)))
+        self._basis_P[path] = P
+
+    def _opt_download_best_params(self, call, path):
+        _, channels = self._control_channels(path)
+        params = np.empty((self._resident_batch(path), max(1, self._basis_P.get(path, 0)), channels),
+                          dtype=np.float64)
+        self._check(call(self._ctx, _dp(params)))
+        return params
+
     def opt_begin(self):
         self._check(self._lib.qocx_opt_begin(self._ctx))
+
+    def opt_begin_basis(self, complex_controls, matrix, coefficients):
+        """In the place of opt_begin / opt_begin_complex, after upload_controls of the expanded start
+        pulses: the optimizer's parameters are `coefficients` [B, P, channels] of the basis `matrix`
+        [Nc, P]; opt_clip expands them into the evaluated controls and clips those, opt_step /
+        opt_lbfgs_step work on the coefficients and the projected gradient (qocx_opt_begin_basis)."""
+        self._opt_begin_basis(self._lib.qocx_opt_begin_basis, PATH_SCHROEDINGER, complex_controls,
+                              matrix, coefficients)
+
+    def opt_download_best_params(self):
+        """The coefficients [B, P, channels] behind the best controls (qocx_opt_download_best_params)."""
+        return self._opt_download_best_params(self._lib.qocx_opt_download_best_params,
+                                              PATH_SCHROEDINGER)
 
     def opt_begin_complex(self):
         """opt_begin for complex controls (channels 2k, 2k+1): the optimizer's parameters stay
@@ -767,6 +810,14 @@ class Engine(object):
 
     def lindblad_opt_begin_complex(self):
         self._check(self._lib.qocx_lindblad_opt_begin_complex(self._ctx))
+
+    def lindblad_opt_begin_basis(self, complex_controls, matrix, coefficients):
+        self._opt_begin_basis(self._lib.qocx_lindblad_opt_begin_basis, PATH_LINDBLAD,
+                              complex_controls, matrix, coefficients)
+
+    def lindblad_opt_download_best_params(self):
+        return self._opt_download_best_params(self._lib.qocx_lindblad_opt_download_best_params,
+                                              PATH_LINDBLAD)
 
     def lindblad_opt_clip(self, max_norms):
         self._opt_clip(self._lib.qocx_lindblad_opt_clip, max_norms)
@@ -837,6 +888,23 @@ class Engine(object):
             self._ctx, int(path), controls.shape[0], _dp(controls), _dp(cost),
             _dp(grads) if want_grad else None))
         return cost, grads
+
+    def control_basis_apply(self, matrix, array, transpose=False):
+        """The map of a control basis alone, host arrays in and out (qocx_control_basis_apply):
+        matrix [Nc, P]; array [B, P, channels] -> [B, Nc, channels], or with transpose
+        [B, Nc, channels] -> [B, P, channels]."""
+        matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+        nc, P = matrix.shape
+        array = np.ascontiguousarray(array, dtype=np.float64)
+        rows_in, rows_out = (nc, P) if transpose else (P, nc)
+        if array.ndim != 3 or array.shape[1] != rows_in:
+            raise ValueError("array must be (B x {} x channels), got shape {}".format(rows_in,
+                                                                                     array.shape))
+        out = np.empty((array.shape[0], rows_out, array.shape[2]), dtype=np.float64)
+        self._check(self._lib.qocx_control_basis_apply(
+            self._ctx, int(bool(transpose)), array.shape[0], nc, P, array.shape[2], _dp(matrix),
+            _dp(array), _dp(out)))
+        return out
 
     def reduce_results(self, allreduce=False, want_grad=True):
         """(sum of the costs, sum of the gradients [Nc x K] or None) over the seeds of the last

@@ -183,3 +183,5 @@ class GrapeLindbladResult(object):
         self.best_error = best_error
         self.best_final_densities = best_final_densities
         self.best_iteration = best_iteration
+        # with a ControlBasis: the coefficients (P x control_count) behind best_controls
+        self.best_coefficients = None

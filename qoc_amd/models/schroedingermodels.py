@@ -197,4 +197,6 @@ class GrapeSchroedingerResult(object):
         self.best_error = best_error
         self.best_final_states = best_final_states
         self.best_iteration = best_iteration
+        # with a ControlBasis: the coefficients (P x control_count) behind best_controls
+        self.best_coefficients = None
         self.member_errors = member_errors

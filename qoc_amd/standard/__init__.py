@@ -2,6 +2,7 @@
 
 from .constants import (SIGMA_MINUS, SIGMA_PLUS, SIGMA_X, SIGMA_Y, SIGMA_Z,
                         get_annihilation_operator, get_creation_operator, get_eij)
+from .controlbasis import ControlBasis
 from .costs import (ControlArea, ControlBandwidthMax, ControlNorm, ControlVariation,
                     ForbidDensities, ForbidStates, TargetDensityInfidelity,
                     TargetDensityInfidelityTime, TargetStateInfidelity,
@@ -21,6 +22,6 @@ __all__ = [
     "commutator", "conjugate_transpose", "expm", "krons", "rms_norm", "matmuls",
     "column_vector_list_to_matrix", "matrix_to_column_vector_list",
     "Adam", "LBFGS", "LBFGSB", "SGD",
-    "HamiltonianEnsemble", "QuadraticHamiltonian",
+    "HamiltonianEnsemble", "QuadraticHamiltonian", "ControlBasis",
     "generate_save_file_path", "CustomJSONEncoder",
 ]
