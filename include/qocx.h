@@ -47,6 +47,10 @@ typedef struct qocx_ctx qocx_ctx;
 #define QOCX_MAGNUS_M4 4
 #define QOCX_MAGNUS_M6 6
 
+/* qoc_amd.models.InterpolationPolicy (qocx_set_interpolation_policy) */
+#define QOCX_INTERP_LINEAR 1
+#define QOCX_INTERP_PIECEWISE_CONSTANT 2
+
 /* State-cost kinds evaluated on the device (qoc/standard/costs/). */
 #define QOCX_COST_TARGET_COHERENT 0   /* TargetStateInfidelity[Time], neglect_relative_pahse=False:
                                          scale * (1 - |sum_s <t_s|psi_s>|^2 / S^2)
@@ -153,6 +157,22 @@ int qocx_synchronize(qocx_ctx* ctx);
  * GrapeSchroedingerDiscreteState does for the evolve loop: dt, control_eval_times,
  * step-cost selection (programstate.py:41-61). */
 int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem* problem);
+
+/*
+ * How the controls are read between their grid points. Sticky on the context: the NEXT
+ * qocx_set_schroedinger_problem / qocx_set_lindblad_problem reads it (a problem already set keeps
+ * the policy it was set under); a context that never calls this interpolates linearly.
+ *   QOCX_INTERP_LINEAR              controls[j] is the knot at t = j T / (Nc - 1), linear between
+ *                                   knots (mathmethods.py:14-67).
+ *   QOCX_INTERP_PIECEWISE_CONSTANT  controls[j] is the value on slice j of Nc equal slices:
+ *                                   u(t) = controls[min(floor(t Nc / T), Nc - 1)]. Every quadrature
+ *                                   node reads the slice it lies in; Lindblad sub-intervals are cut
+ *                                   at the slice edges j T / Nc, which are the cut points
+ *                                   qocx_lindblad_stage_times gives for control_eval_count = Nc + 1.
+ * Array shapes, gradients, costs of the controls and the qocx_opt_* calls are the same under both.
+ * QOCX_ERR_ARG for any other value.
+ */
+int qocx_set_interpolation_policy(qocx_ctx* ctx, int32_t policy);
 
 /*
  * One batched evaluation == B calls of _evaluate_schroedinger_discrete (+ its reverse-mode

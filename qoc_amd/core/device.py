@@ -23,6 +23,19 @@ def make_backend(device=-1):
 _FD_STEP = 1e-6
 
 
+def interpolation_keywords(backend, setter, interpolation_policy):
+    """The keyword a backend's problem setter takes for `interpolation_policy`: none for LINEAR
+    (every backend's default), interpolation="piecewise_constant" otherwise - from a backend
+    whose setter takes it; there is no fallback to another policy."""
+    if interpolation_policy == InterpolationPolicy.LINEAR:
+        return {}
+    import inspect
+    if "interpolation" not in inspect.signature(getattr(backend, setter)).parameters:
+        raise NotImplementedError("the backend {!r} does not evaluate the interpolation policy {}"
+                                  "".format(backend, interpolation_policy))
+    return dict(interpolation=interpolation_policy.short)
+
+
 def control_cost_descriptors(host_costs, control_count, control_eval_count, complex_controls):
     """One entry per cost of the controls alone: the dict engine.set_control_costs() takes, or None
     where only the host can evaluate the cost (a user plugin without control_descriptor(), or a
@@ -334,9 +347,10 @@ class SchroedingerEvaluator(_Evaluator):
         against 4.1 ms with the blocked one - a single 16 x 16 block leaves nothing to overlap)
         and n > 32 (not built there).
         """
-        if interpolation_policy != InterpolationPolicy.LINEAR:
+        if not isinstance(interpolation_policy, InterpolationPolicy):
             raise NotImplementedError("The interpolation policy {} is not yet supported for this "
                                       "method.".format(interpolation_policy))
+        self.interpolation_policy = interpolation_policy
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
         initial_states = np.asarray(initial_states)
@@ -413,7 +427,8 @@ class SchroedingerEvaluator(_Evaluator):
                 self.opaque_hamiltonian = hamiltonian
                 self._dt = dt
                 self._mid_times = times
-                self._rows = structure.interpolation_rows(evolution_time, control_eval_count, times)
+                self._rows = structure.interpolation_rows(evolution_time, control_eval_count, times,
+                                                          interpolation_policy)
                 h0 = np.zeros((1, self.hilbert_size, self.hilbert_size), dtype=np.complex128)
                 g = None
         descriptors = self._triage_costs(self.state_count)
@@ -438,7 +453,9 @@ class SchroedingerEvaluator(_Evaluator):
              system_eval_count, evolution_time),
             initial_states.reshape(self.state_count, self.hilbert_size),
             dict(costs=descriptors, cost_eval_step=cost_eval_step,
-                 magnus_policy=magnus_policy.short))
+                 magnus_policy=magnus_policy.short,
+                 **interpolation_keywords(self.backend, "set_schroedinger_problem",
+                                          interpolation_policy)))
         self._set_problem(h0, g)
         self.cost_eval_step = cost_eval_step
 
@@ -529,7 +546,7 @@ class SchroedingerEvaluator(_Evaluator):
         nsteps x nodes x (1 + K) tables and a one-seed evaluation."""
         self._set_problem(*structure.linearize_hamiltonian(
             self.linearized_hamiltonian, controls, self._evolution_time, self._node_times,
-            self.hilbert_size, self.complex_controls))
+            self.hilbert_size, self.complex_controls, self.interpolation_policy))
 
     def _pass(self, controls_batch, device_controls, want_grad, again=False):
         """again: the second pass of one evaluation, the backend still holds the controls."""
@@ -558,6 +575,7 @@ class LindbladEvaluator(_Evaluator):
     MAX_HILBERT_SIZE = 32
     opt_prefix = "lindblad_"
     subtotal_costs = False
+    _frozen_slices = None     # (callable, controls) of piecewise-constant frozen controls
     linearized_route = "on the Lindblad GRAPE path"
 
     def __init__(self, evolution_time, initial_densities, system_eval_count, hamiltonian=None,
@@ -572,9 +590,10 @@ class LindbladEvaluator(_Evaluator):
         control-free, time-dependent Hamiltonian t -> hamiltonian(u(t), t), which the engine takes
         as per-stage samples like any other time dependence. Costs still see the controls.
         """
-        if interpolation_policy != InterpolationPolicy.LINEAR:
+        if not isinstance(interpolation_policy, InterpolationPolicy):
             raise NotImplementedError("This operation does not yet support the interpolation "
                                       "policy {}.".format(interpolation_policy))
+        self.interpolation_policy = interpolation_policy
         if isinstance(hamiltonian, HamiltonianEnsemble):
             raise NotImplementedError("Hamiltonian ensembles are evaluated on the Schroedinger path "
                                       "only, not on the Lindblad path")
@@ -586,14 +605,18 @@ class LindbladEvaluator(_Evaluator):
             frozen_controls = np.asarray(frozen_controls)
             self._cost_controls = frozen_controls
             user_hamiltonian, frozen_nc = hamiltonian, frozen_controls.shape[0]
+            if interpolation_policy == InterpolationPolicy.PIECEWISE_CONSTANT:
+                self._frozen_slices = (user_hamiltonian, frozen_controls)
 
             def hamiltonian(_, time):
-                rows = structure.interpolation_rows(evolution_time, frozen_nc, [time])
+                rows = structure.interpolation_rows(evolution_time, frozen_nc, [time],
+                                                    interpolation_policy)
                 return user_hamiltonian(structure.controls_at(frozen_controls, rows, [time])[0],
                                         time)
             # one dummy control with a zero coupling keeps the control knots in the integrator's
             # grid: u(t) has kinks there, and a sub-interval that straddled one would lose the
-            # integrator's order (the engine cuts sub-intervals at knots only when it has controls)
+            # integrator's order (the engine cuts sub-intervals at knots only when it has controls;
+            # piecewise constant it cuts at the slice edges, where u(t) jumps)
             control_count, control_eval_count, complex_controls = 1, frozen_nc, False
         initial_densities = np.asarray(initial_densities)
         self.density_count = initial_densities.shape[0]
@@ -613,8 +636,11 @@ class LindbladEvaluator(_Evaluator):
         self.kr = control_count * (2 if complex_controls else 1)
         # time dependence is decided on the integrator's own grid: every stage time of the
         # coarsest sub-division (12 per sub-interval), never on a handful of equispaced probes
+        # (piecewise constant: the edges of Nc slices are the cut points of Nc + 1 linear knots)
+        self._stage_knots = control_eval_count + (
+            1 if interpolation_policy == InterpolationPolicy.PIECEWISE_CONSTANT else 0)
         self._coarse_times = self.backend.lindblad_stage_times(
-            evolution_time, system_eval_count, control_eval_count, self.kr, 1)
+            evolution_time, system_eval_count, self._stage_knots, self.kr, 1)
         # A hamiltonian(controls, time) that is not linear in the controls (the reference takes any
         # callable, lindbladdiscrete.py:486-489): the engine gets the TANGENT of the callable at the
         # control array being evaluated, sampled at the integrator's stage times
@@ -641,7 +667,9 @@ class LindbladEvaluator(_Evaluator):
         self._problem_args = (self.hilbert_size, self.density_count, self.kr, control_eval_count,
                               system_eval_count, evolution_time, h0, g, dissipators, operators,
                               initial_densities)
-        self._problem_kw = dict(costs=descriptors, cost_eval_step=cost_eval_step)
+        self._problem_kw = dict(costs=descriptors, cost_eval_step=cost_eval_step,
+                                **interpolation_keywords(self.backend, "set_lindblad_problem",
+                                                         interpolation_policy))
         self._hamiltonian = hamiltonian
         self._table_bounds = None
         self._coarse_samples = None
@@ -674,7 +702,8 @@ class LindbladEvaluator(_Evaluator):
             pairs = list(zip(*self._coarse_lindblad))
         ksub = max(structure.lindblad_subdivision(h_norm, g_norms, bounds, d, o, dt)
                    for d, o in pairs)
-        times = self.backend.lindblad_stage_times(evolution_time, n_eval, nc, kr, ksub)
+        times = self.backend.lindblad_stage_times(evolution_time, n_eval, self._stage_knots, kr,
+                                                  ksub)
         h0_stages, g_stages = sample(times)
         extra = {}
         if self._lindblad_data is not None:
@@ -697,6 +726,15 @@ class LindbladEvaluator(_Evaluator):
                 list(self._coarse_times))
 
         def sample(times):
+            if self._frozen_slices is not None:
+                # piecewise-constant frozen controls: by sub-interval, not by time - a stage ON a
+                # slice edge belongs to the slice of its sub-interval
+                call, controls = self._frozen_slices
+                rows = structure.lindblad_stage_rows(
+                    self._evolution_time, controls.shape[0], times, self.interpolation_policy)
+                u = structure.controls_at(controls, rows, times)
+                return np.stack([np.asarray(call(u[q], t), dtype=np.complex128)
+                                 for q, t in enumerate(times)]), None
             if self._hamiltonian is None:
                 return np.repeat(np.asarray(h0, dtype=np.complex128)[None], len(times), axis=0), None
             return structure.sample_lindblad_hamiltonian(
@@ -709,7 +747,9 @@ class LindbladEvaluator(_Evaluator):
         sub-division fine enough for this control array, handed to the engine as tables."""
         lin = lambda times: structure.linearize_hamiltonian(  # noqa: E731
             self.linearized_hamiltonian, controls, self._evolution_time, list(times),
-            self.hilbert_size, self.complex_controls)
+            self.hilbert_size, self.complex_controls, self.interpolation_policy,
+            rows=structure.lindblad_stage_rows(self._evolution_time, controls.shape[0], times,
+                                               self.interpolation_policy))
         bounds = np.max(np.abs(device_controls.reshape(-1, self.kr)), axis=0)
         self._set_stage_tables(lin(self._coarse_times), bounds, lin)
 

@@ -15,6 +15,8 @@ no CPU fallback.
 
 import numpy as np
 
+from qoc_amd.models.policies import InterpolationPolicy
+
 
 class NonLinearHamiltonianError(ValueError):
     pass
@@ -81,12 +83,22 @@ class TimeDependentSystemError(NotImplementedError):
 
 # ---- opaque Hamiltonians: the host samples the step generators itself --------------------------
 
-def interpolation_rows(evolution_time, control_eval_count, times):
+def interpolation_rows(evolution_time, control_eval_count, times,
+                       interpolation_policy=InterpolationPolicy.LINEAR):
     """
     Linear interpolation of the controls at `times`, the reference's rule
     (qoc/core/mathmethods.py:36-67: the two lowest / highest knots beyond the ends, else the
     first knot >= t and its predecessor). Returns (i1, i2, x1, x2): index and abscissa arrays.
+    PIECEWISE_CONSTANT: the slice min(floor(t Nc / T), Nc - 1) of Nc equal slices as ONE index
+    with weight 1 - i1 == i2 and (x1, x2) = (t, t + 1), so that controls_at returns
+    y1 + ((y1 - y1) / 1) * 0 = y1 bit for bit and generator_gradients gives row i1 the whole
+    cotangent.
     """
+    if interpolation_policy == InterpolationPolicy.PIECEWISE_CONSTANT:
+        t = np.asarray(times, dtype=np.float64)
+        slices = np.floor(t * control_eval_count / evolution_time)
+        i1 = np.clip(slices, 0, control_eval_count - 1).astype(np.int64)
+        return i1, i1.copy(), t, t + 1.0
     xs = np.linspace(0, evolution_time, control_eval_count)
     i1 = np.empty(len(times), dtype=np.int64)
     i2 = np.empty(len(times), dtype=np.int64)
@@ -99,6 +111,24 @@ def interpolation_rows(evolution_time, control_eval_count, times):
             index = int(np.argmax(t <= xs))
             i1[q], i2[q] = index - 1, index
     return i1, i2, xs[i1], xs[i2]
+
+
+# times per sub-interval in Engine.lindblad_stage_times (the 12 stages of DOP853)
+LINDBLAD_STAGES = 12
+
+
+def lindblad_stage_rows(evolution_time, control_eval_count, times,
+                        interpolation_policy=InterpolationPolicy.LINEAR):
+    """interpolation_rows at the Lindblad stage times. PIECEWISE_CONSTANT: every stage of a
+    sub-interval takes the slice that contains the sub-interval (that of its midpoint) - its
+    first and last stage lie ON slice edges, and the last one must not read the next slice."""
+    if interpolation_policy != InterpolationPolicy.PIECEWISE_CONSTANT:
+        return interpolation_rows(evolution_time, control_eval_count, times)
+    t = np.asarray(times, dtype=np.float64).reshape(-1, LINDBLAD_STAGES)
+    mid = np.repeat(0.5 * (t[:, 0] + t[:, -1]), LINDBLAD_STAGES)
+    i1 = interpolation_rows(evolution_time, control_eval_count, mid, interpolation_policy)[0]
+    t = t.reshape(-1)
+    return i1, i1.copy(), t, t + 1.0
 
 
 def controls_at(controls, rows, times):
@@ -145,7 +175,8 @@ def hamiltonian_slopes(hamiltonian, u, t, complex_controls):
 
 
 def linearize_hamiltonian(hamiltonian, controls, evolution_time, times, hilbert_size,
-                          complex_controls):
+                          complex_controls, interpolation_policy=InterpolationPolicy.LINEAR,
+                          rows=None):
     """
     The tangent of a hamiltonian(controls, time) that is NOT linear in the controls, at the
     control array `controls` (Nc x K): at every time t of `times`
@@ -154,7 +185,8 @@ def linearize_hamiltonian(hamiltonian, controls, evolution_time, times, hilbert_
         G'(t) = d H / d u at (u(t), t)   (4th-order central differences of the callable),
         H0'(t) = H(u(t), t) - sum_k Re(u_k(t)) G'_{re,k}(t) + Im(u_k(t)) G'_{im,k}(t),
 
-    with u(t) the reference's linear interpolation of `controls`. H_lin(u(t), t) = H(u(t), t) and
+    with u(t) the interpolation of `controls` under `interpolation_policy` (or the given
+    interpolation `rows` of `times`: lindblad_stage_rows on the Lindblad path). H_lin(u(t), t) = H(u(t), t) and
     d H_lin / d v = d H / d u there, so a structured, time-dependent problem built from (H0', G')
     and evaluated AT `controls` has the cost and the control gradient of the original one - under
     any Magnus policy and on the Lindblad path (the reference differentiates the callable itself
@@ -164,7 +196,8 @@ def linearize_hamiltonian(hamiltonian, controls, evolution_time, times, hilbert_
     controls = np.asarray(controls)
     k = controls.shape[1]
     kr = k * (2 if complex_controls else 1)
-    rows = interpolation_rows(evolution_time, controls.shape[0], times)
+    if rows is None:
+        rows = interpolation_rows(evolution_time, controls.shape[0], times, interpolation_policy)
     u = controls_at(controls, rows, times)
     h0 = np.empty((len(times), hilbert_size, hilbert_size), dtype=np.complex128)
     g = np.empty((len(times), kr, hilbert_size, hilbert_size), dtype=np.complex128)

@@ -486,7 +486,20 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
         {0.5 - std::sqrt(15.0) / 10, 0.5, 0.5 + std::sqrt(15.0) / 10}};
     std::vector<qocx::StepInterp> interp((size_t)nsteps * nodes);
     std::vector<std::vector<std::pair<int, double>>> rows(K > 0 ? nc : 0);
-    if (K > 0) {
+    ctx->pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
+    if (K > 0 && ctx->pwc) {
+        // piecewise constant: a node reads the slice it lies in, u = controls[min(floor(x nc / T), nc - 1)]
+        // (right-continuous at the interior edges). i1 == i2, dx = 1, off = 0: control_at returns
+        // y1 + ((y1 - y1) / 1) * 0 = y1 bit for bit, and the slice's row takes the node's cotangent whole.
+        for (int j = 0; j < nsteps; ++j)
+            for (int q = 0; q < nodes; ++q) {
+                const double x = j * ctx->dt + ctx->dt * node_c[nodes - 1][q];
+                const double f = std::floor(x * nc / p->evolution_time);
+                const int slice = f >= nc - 1 ? nc - 1 : (f > 0 ? (int)f : 0);
+                interp[(size_t)j * nodes + q] = qocx::StepInterp{slice, slice, 1.0, 0.0};
+                rows[slice].push_back(std::make_pair(j * nodes + q, 1.0));
+            }
+    } else if (K > 0) {
         std::vector<double> xs(nc);
         const double stepx = p->evolution_time / (nc - 1);  // numpy.linspace
         for (int i = 0; i < nc; ++i) xs[i] = i * stepx;
@@ -539,6 +552,15 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     ctx->have_results = false;
     ctx->B = 0;
     ctx->inj_count = 0;
+    return 0;
+}
+
+int qocx_set_interpolation_policy(qocx_ctx* ctx, int32_t policy) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (policy != QOCX_INTERP_LINEAR && policy != QOCX_INTERP_PIECEWISE_CONSTANT)
+        return fail(QOCX_ERR_ARG, "interpolation policy must be QOCX_INTERP_LINEAR or "
+                                  "QOCX_INTERP_PIECEWISE_CONSTANT");
+    ctx->interp_policy = policy;  // read by the next problem setter
     return 0;
 }
 
@@ -913,7 +935,9 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
             }
             sprev = srow;
         }
-        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->quad_count == 0)
+        // (piecewise constant: a step reads ONE slice, never the mean of two rows - the knot sums
+        // above are then exact for every step and the midpoint bound does not apply)
+        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->quad_count == 0 && !ctx->pwc)
             ctx->norm_bound_mid = (bound + smid) * fabs(ctx->dt) * (1.0 + 1e-12);
         else
             ctx->norm_bound_mid = 1e300;

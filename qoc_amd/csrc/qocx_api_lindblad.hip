@@ -295,6 +295,7 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.control_costs.clear();
     lb.n = n; lb.S = S; lb.K = K; lb.nc = nc; lb.N = N; lb.nsteps = N - 1; lb.ces = p->cost_eval_step;
     lb.nops = L; lb.T = p->evolution_time; lb.dt = p->evolution_time / (N - 1);
+    lb.pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
 
     const cmat h0 = p->h0 ? cm_from(p->h0, n) : cm_zero(n);
     cmat decay = cm_zero(n);  // sum gamma_i L_i^H L_i
@@ -361,8 +362,9 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     if (p->fixed_subdivision > 0) {
         if (!p->h0_stages) return fail(QOCX_ERR_ARG, "h0_stages missing");
         int64_t count = 0;
-        int rc = qocx_lindblad_stage_times(p->evolution_time, N, nc, K, p->fixed_subdivision, nullptr,
-                                           0, &count);
+        // (piecewise constant: the slice edges are the cut points of nc + 1 linear knots)
+        int rc = qocx_lindblad_stage_times(p->evolution_time, N, lb.pwc ? nc + 1 : nc, K,
+                                           p->fixed_subdivision, nullptr, 0, &count);
         if (rc) return rc;
         const size_t md = dump_elems(n);
         std::vector<double2> tab((size_t)count * 4 * md);
@@ -501,7 +503,12 @@ std::vector<double> lindblad_points(double T, int nsteps, int nc, int K, int ksu
 // knots, with the interpolation weights of both ends and the CSR of their transpose.
 int build_lindblad_grid(qocx_ctx* ctx, int ksub, qocx_ctx::Lindblad::Grid& gr) {
     auto& lb = ctx->lb;
-    const int K = lb.K, nc = lb.nc, nsteps = lb.nsteps;
+    const int K = lb.K, nsteps = lb.nsteps;
+    // Piecewise constant: the nc slices are the knot intervals of nc + 1 knots at j T / nc. A
+    // sub-interval never straddles an edge, and both its ends take the value of the slice that
+    // contains it: one index, weights (1, 0), so u_a = u_b = 1 * u + 0 * u bit for bit.
+    const bool pwc = lb.pwc && K > 0;
+    const int nc = pwc ? lb.nc + 1 : lb.nc;  // knots (rows of the control array: lb.nc)
     std::vector<double> knots(K > 0 ? nc : 0);
     for (int i = 0; i < (int)knots.size(); ++i) knots[i] = i * (lb.T / (nc - 1));
     if (!knots.empty()) knots.back() = lb.T;
@@ -531,14 +538,24 @@ int build_lindblad_grid(qocx_ctx* ctx, int ksub, qocx_ctx::Lindblad::Grid& gr) {
             ss.ia1 = ss.ib1 = m1; ss.ia2 = ss.ib2 = m2;
             end_weights(pts[i], ss.wa1, ss.wa2);
             end_weights(pts[i + 1], ss.wb1, ss.wb2);
+            if (pwc) {  // slice m1 (0 .. lb.nc - 1) at both ends
+                ss.ia2 = ss.ib2 = m1;
+                ss.wa1 = ss.wb1 = 1.0;
+                ss.wa2 = ss.wb2 = 0.0;
+            }
             ss.step = step;
             ss.first_of_step = (i == 0) ? 1 : 0;
             subs.push_back(ss);
         }
     }
     const int nsub = (int)subs.size();
-    std::vector<std::vector<std::pair<int, double>>> rows(K > 0 ? nc : 0);
-    if (K > 0)
+    std::vector<std::vector<std::pair<int, double>>> rows(K > 0 ? lb.nc : 0);
+    if (pwc)
+        for (int q = 0; q < nsub; ++q) {
+            rows[subs[q].ia1].push_back({2 * q, 1.0});
+            rows[subs[q].ib1].push_back({2 * q + 1, 1.0});
+        }
+    else if (K > 0)
         for (int q = 0; q < nsub; ++q) {
             rows[subs[q].ia1].push_back({2 * q, subs[q].wa1});
             rows[subs[q].ia2].push_back({2 * q, subs[q].wa2});

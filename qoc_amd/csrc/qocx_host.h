@@ -148,6 +148,8 @@ struct qocx_ctx {
     bool has_problem = false;
     int n = 0, nb = 0, np = 0, S = 0, K = 0, nc = 0, N = 0, nsteps = 0, ces = 1, nt = 1;
     double T = 0, dt = 0;
+    int interp_policy = QOCX_INTERP_LINEAR;  // qocx_set_interpolation_policy: read by the next problem setter
+    bool pwc = false;                        // the Schroedinger problem was set piecewise constant
     int has_step_costs = 0, cost_count = 0;
     double h0_norm_max = 0;
     std::vector<double> g_norm_max;
@@ -236,6 +238,7 @@ struct qocx_ctx {
         bool has_problem = false, have_results = false, have_grads = false, have_steps = false;
         int n = 0, S = 0, K = 0, nc = 0, N = 0, nsteps = 0, ces = 1, nops = 0;
         double T = 0, dt = 0, h0_norm = 0, diss_norm = 0, l0_norm = 0;
+        bool pwc = false;  // set piecewise constant: nc slices, sub-intervals cut at j T / nc
         std::vector<double> g_norm;
         int has_step_costs = 0, cost_count = 0;
         DevBuf<double2> a0l, a0r, a0ld, a0rd, gp, gpd, gpt, ops, rho0, cost_matrices;

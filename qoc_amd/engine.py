@@ -22,6 +22,8 @@ COST_TARGET_DENSITY = 3
 COST_FORBID_DENSITY = 4
 
 MAGNUS_CODES = {"M2": 2, "M4": 4, "M6": 6}
+# QOCX_INTERP_* of include/qocx.h, by InterpolationPolicy.short
+INTERPOLATION_CODES = {"linear": 1, "piecewise_constant": 2}
 
 PATH_SCHROEDINGER = 0
 PATH_LINDBLAD = 1
@@ -125,6 +127,7 @@ SIGNATURES = {
     "qocx_destroy": (ctypes.c_int, [_VP]),
     "qocx_synchronize": (ctypes.c_int, [_VP]),
     "qocx_set_schroedinger_problem": (ctypes.c_int, [_VP, ctypes.POINTER(_SchroedingerProblem)]),
+    "qocx_set_interpolation_policy": (ctypes.c_int, [_VP, _I32]),
     "qocx_eval_schroedinger": (ctypes.c_int, [_VP, _I32, _c_double_p, _I32, _c_double_p,
                                               _c_double_p, _c_double_p]),
     "qocx_upload_controls": (ctypes.c_int, [_VP, _I32, _c_double_p]),
@@ -278,6 +281,7 @@ class Engine(object):
         self._quadratic_count = 0
         self._keepalive = []
         self.batch = 0
+        self._interpolation = INTERPOLATION_CODES["linear"]  # of the context (its default)
         self._basis_P = {}  # path -> coefficients per channel of the resident driver's basis
 
     # -- plumbing ----------------------------------------------------------------------------
@@ -303,14 +307,31 @@ class Engine(object):
         self._check(self._lib.qocx_synchronize(self._ctx))
 
     # -- problem -------------------------------------------------------------------------------
+    def set_interpolation_policy(self, interpolation):
+        """How the NEXT problem set on this context reads the controls between their grid points
+        (qocx_set_interpolation_policy, sticky): "linear", "piecewise_constant", a
+        qoc_amd.models.InterpolationPolicy or one of the QOCX_INTERP_* codes."""
+        name = getattr(interpolation, "short", interpolation)
+        code = INTERPOLATION_CODES.get(name, name)
+        if isinstance(code, str):
+            raise ValueError("Unrecognized interpolation {!r}.".format(interpolation))
+        # (the call is made only when the context's policy changes: a context that only ever
+        # sets linear problems never makes it)
+        if int(code) != self._interpolation:
+            self._check(self._lib.qocx_set_interpolation_policy(self._ctx, int(code)))
+            self._interpolation = int(code)
+
     def set_schroedinger_problem(self, hilbert_size, state_count, control_count,
                                  control_eval_count, system_eval_count, evolution_time,
                                  h0, g, initial_states, costs=(), cost_eval_step=1,
-                                 magnus_policy="M2"):
+                                 magnus_policy="M2", interpolation="linear"):
         """
         h0 :: (nt, n, n) complex, g :: (nt, K, n, n) complex, initial_states :: (S, n) complex,
         costs :: iterable of dicts {kind, step_cost, scale, vectors, counts(optional)}.
+        interpolation: as set_interpolation_policy; it is set on the context before the problem, so
+        a later problem set without the argument is linear again.
         """
+        self.set_interpolation_policy(interpolation)
         n, S, K = int(hilbert_size), int(state_count), int(control_count)
         h0 = _as_complex(h0)
         if h0.ndim == 2:
@@ -490,12 +511,17 @@ class Engine(object):
                              control_eval_count, system_eval_count, evolution_time,
                              h0, g, dissipators, operators, initial_densities, costs=(),
                              cost_eval_step=1, fixed_subdivision=0, h0_stages=None,
-                             g_stages=None, diss_stages=None, op_stages=None):
+                             g_stages=None, diss_stages=None, op_stages=None,
+                             interpolation="linear"):
         """
         h0 :: (n, n), g :: (K, n, n), dissipators :: (L,), operators :: (L, n, n),
         initial_densities :: (S, n, n); costs :: dicts {kind (3|4), step_cost, scale,
         vectors (matrices), counts(optional)}.
+        interpolation: as in set_schroedinger_problem. Piecewise constant, the stage tables are
+        those of lindblad_stage_times(..., control_eval_count + 1, ...): the slice edges are the
+        cut points of one knot more.
         """
+        self.set_interpolation_policy(interpolation)
         n, S, K = int(hilbert_size), int(density_count), int(control_count)
         h0 = _as_complex(h0, (n, n))
         g = _as_complex(g if K > 0 else np.zeros((0, n, n)), (K, n, n))

@@ -42,11 +42,24 @@ class MagnusPolicy(_NamedEnum):
 
 
 class InterpolationPolicy(_NamedEnum):
-    """How time-discrete controls are evaluated between their grid points."""
+    """How time-discrete controls are evaluated between their grid points.
+
+    LINEAR: row j of the (control_eval_count x control_count) array is the knot at
+    t = j T / (control_eval_count - 1), and u(t) is linear between knots (the reference's only
+    policy). PIECEWISE_CONSTANT: row j is the value on slice j of control_eval_count equal slices,
+    u(t) = controls[min(floor(t control_eval_count / T), control_eval_count - 1)] - the pulse of
+    GRAPE as published and of an arbitrary waveform generator. The array's shape, the gradient's,
+    the costs of the controls and the optimizers are the same under both.
+    """
     LINEAR = 1
+    PIECEWISE_CONSTANT = 2
 
     def _labels(self):
-        return {1: "interpolation_linear"}
+        return {1: "interpolation_linear", 2: "interpolation_piecewise_constant"}
+
+    @property
+    def short(self):
+        return {1: "linear", 2: "piecewise_constant"}[self.value]
 
 
 class ProgramType(_NamedEnum):

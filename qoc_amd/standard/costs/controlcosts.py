@@ -161,7 +161,13 @@ class ControlArea(Cost):
 
 
 class ControlBandwidthMax(Cost):
-    """Spectral weight of each control above its maximum bandwidth."""
+    """Spectral weight of each control above its maximum bandwidth.
+
+    The sample spacing of the DFT is taken from the `evolution_time` given HERE:
+    evolution_time / (control_eval_count - 1), the knot spacing of InterpolationPolicy.LINEAR.
+    Under InterpolationPolicy.PIECEWISE_CONSTANT the rows are T / control_eval_count apart: pass
+    evolution_time = T (control_eval_count - 1) / control_eval_count for frequencies in the same
+    units."""
     name = "control_bandwidth_max"
     requires_step_evaluation = False
     uses_states = False
