@@ -34,6 +34,21 @@ int pade_scale_count(double norm1) {
     return s;
 }
 
+int commit_step_bound(qocx_ctx* ctx, double bound, bool keep_larger, const char* needs) {
+    const int sb = pade_scale_count(bound);
+    if (!keep_larger) ctx->sbound = sb, ctx->norm_bound = bound;  // (an upload: even where refused below)
+    if (sb > 10)
+        return fail(QOCX_ERR_CAPACITY, std::string("||dt H||_1 ") + needs +
+                                           " more than 2^10 squaring sub-steps per step; reduce dt");
+    if (keep_larger) {  // qocx_opt_clip: the controls move on the device from here on
+        ctx->sbound = std::max(ctx->sbound, sb);
+        ctx->norm_bound = std::max(ctx->norm_bound, bound);
+        ctx->norm_bound_mid = 1e300;
+    }
+    ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
+    return 0;
+}
+
 double one_norm(const double* m, int n) {  // complex row-major
     double best = 0;
     for (int c = 0; c < n; ++c) {
@@ -83,6 +98,23 @@ void r_image(const double* m, int n, int np, bool transpose, double2* out) {
         }
 }
 
+// m equals its conjugate transpose bit for bit
+bool hermitian_bitwise(const double* m, int n) {
+    for (int r = 0; r < n; ++r)
+        for (int c = r; c < n; ++c)
+            if (m[2 * ((size_t)r * n + c)] != m[2 * ((size_t)c * n + r)] ||
+                m[2 * ((size_t)r * n + c) + 1] != -m[2 * ((size_t)c * n + r) + 1])
+                return false;
+    return true;
+}
+
+// step j reads row j of a [nsteps][Ke] control array whole (EffectiveControls::interp_id)
+std::vector<qocx::StepInterp> identity_interp(int nsteps) {
+    std::vector<qocx::StepInterp> ident(nsteps);
+    for (int j = 0; j < nsteps; ++j) ident[j] = qocx::StepInterp{j, j, 1.0, 0.0};
+    return ident;
+}
+
 // timing events come from a grow-only pool: creating and destroying ~100 events per evaluation
 // makes the runtime stall for tens of milliseconds every few evaluations
 hipEvent_t pooled_event(qocx_ctx* ctx) {
@@ -97,6 +129,20 @@ hipEvent_t pooled_event(qocx_ctx* ctx) {
 }  // namespace
 
 namespace qocx::host {
+
+int OperatorImages::build(const double* m, size_t count, int n, int nb, hipStream_t st, bool t_only) {
+    const int np = 16 * nb;
+    const size_t mat = (size_t)np * np, nn2 = (size_t)n * n * 2;
+    std::vector<double2> img(count * mat);
+    for (int pass = t_only ? 2 : 0; pass < 3; ++pass) {
+        for (size_t i = 0; i < count; ++i) {
+            if (pass == 0) c_image(m + i * nn2, n, nb, img.data() + i * mat);
+            else r_image(m + i * nn2, n, np, pass == 2, img.data() + i * mat);
+        }
+        if (layout(pass).upload(img, st)) return QOCX_ERR_HIP;
+    }
+    return 0;
+}
 
 void time_begin(qocx_ctx* ctx, int which, hipStream_t st) {
     // timing 1: every launch; 2 + k: the launches of kernel k only (qocx_set_timing)
@@ -209,6 +255,195 @@ int upload_costs(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
     if (ctx->cost_counts.upload(counts, ctx->stream)) return QOCX_ERR_HIP;
     return 0;
 }
+
+// ---- the stages of qocx_set_schroedinger_problem -------------------------------------------------
+
+int check_problem(const qocx_schroedinger_problem* p) {
+    if (p->struct_size != (int32_t)sizeof(qocx_schroedinger_problem))
+        return fail(QOCX_ERR_ARG, "qocx_schroedinger_problem.struct_size does not match this "
+                                  "library's header (stale binding?)");
+    const int n = p->hilbert_size, S = p->state_count, K = p->control_count, N = p->system_eval_count;
+    if (n < 1 || n > 1024)
+        return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..1024 (1..64: the wavefront kernels; 65..1024: the general "
+                                  "path of qocx_general.hip)");
+    // (a full propagator has n states: up to 256 of them on the general path)
+    if (S < 1 || S > (n > 64 ? 1024 : 64)) return fail(QOCX_ERR_ARG, "state_count must be in 1..64 (1..1024 above hilbert_size 64)");
+    if (K < 0 || K > 64) return fail(QOCX_ERR_ARG, "control_count must be in 0..64");
+    if (N < 2) return fail(QOCX_ERR_ARG, "system_eval_count must be >= 2");
+    if (K > 0 && p->control_eval_count < 2) return fail(QOCX_ERR_ARG, "control_eval_count must be >= 2");
+    if (p->cost_eval_step < 1) return fail(QOCX_ERR_ARG, "cost_eval_step must be >= 1");
+    if (p->magnus_policy != QOCX_MAGNUS_M2 && p->magnus_policy != QOCX_MAGNUS_M4 &&
+        p->magnus_policy != QOCX_MAGNUS_M6)
+        return fail(QOCX_ERR_ARG, "unknown magnus_policy");
+    // quadrature nodes per step: magnus_policy / 2 = 1, 2, 3
+    if (p->nt != 1 && p->nt != (N - 1) * (p->magnus_policy / 2))
+        return fail(QOCX_ERR_ARG, "nt must be 1 or (N-1) * (quadrature nodes of the policy)");
+    if (!p->h0 || !p->initial_states || (K > 0 && !p->g))
+        return fail(QOCX_ERR_ARG, "h0 / g / initial_states missing");
+    if (p->cost_count < 0 || (p->cost_count > 0 && !p->costs))
+        return fail(QOCX_ERR_ARG, "costs missing");
+    return 0;
+}
+
+// every h0[t], g[t][k] Hermitian bit for bit
+void set_hermitian_flags(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
+    const size_t nn2 = (size_t)ctx->n * ctx->n * 2;
+    bool herm = true;
+    for (int t = 0; t < ctx->nt && herm; ++t) {
+        herm = hermitian_bitwise(p->h0 + (size_t)t * nn2, ctx->n);
+        for (int k = 0; k < ctx->K && herm; ++k)
+            herm = hermitian_bitwise(p->g + ((size_t)t * ctx->K + k) * nn2, ctx->n);
+    }
+    ctx->hermitian = herm ? 1 : 0;
+    ctx->hermitian_linear = ctx->hermitian;
+}
+
+// Hamiltonian images + norms for the squaring bound
+int upload_operators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
+    const int n = ctx->n, K = ctx->K, nt = ctx->nt;
+    const size_t nn2 = (size_t)n * n * 2;
+    ctx->h0_norm_max = 0;
+    ctx->g_norm_max.assign(K, 0.0);
+    for (int t = 0; t < nt; ++t) {
+        ctx->h0_norm_max = std::max(ctx->h0_norm_max, one_norm(p->h0 + (size_t)t * nn2, n));
+        for (int k = 0; k < K; ++k)
+            ctx->g_norm_max[k] = std::max(ctx->g_norm_max[k], one_norm(p->g + ((size_t)t * K + k) * nn2, n));
+    }
+    return ctx->h0.build(p->h0, (size_t)nt, n, ctx->nb, ctx->stream) ||
+                   ctx->g.build(p->g, (size_t)nt * K, n, ctx->nb, ctx->stream) ||
+                   (K > 0 && ctx->g_norm_dev.upload(ctx->g_norm_max, ctx->stream))  // step table
+               ? QOCX_ERR_HIP : 0;
+}
+
+// M4, time-independent H0 / G_k: the commutators leave the time loop (M4LinArgs). Constant
+// matrices G_k, A_k = -i [G_k, H0], B_kl = -i [G_k, G_l] (k < l); Hermitian when H0 and the
+// G_k are (made so bit for bit, the Hermitian kernel forms rely on it).
+int upload_m4_commutators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
+    const int n = ctx->n, K = ctx->K, Ke = 2 * K + K * (K - 1) / 2;
+    if (ctx->nodes != 2 || ctx->nt != 1 || K < 1 || K > QOCX_M4LIN_MAX_K) return 0;
+    const size_t nn = (size_t)n * n;
+    std::vector<double> ge((size_t)Ke * nn * 2);
+    std::copy(p->g, p->g + (size_t)K * nn * 2, ge.begin());
+    auto neg_i_commutator = [&](const double* x, const double* y, double* out) {
+        for (int r = 0; r < n; ++r)
+            for (int c = 0; c < n; ++c) {
+                double re = 0, im = 0;  // (x y - y x)[r][c]
+                for (int q = 0; q < n; ++q) {
+                    const double* xa = x + 2 * ((size_t)r * n + q);
+                    const double* yb = y + 2 * ((size_t)q * n + c);
+                    const double* ya = y + 2 * ((size_t)r * n + q);
+                    const double* xb = x + 2 * ((size_t)q * n + c);
+                    re += xa[0] * yb[0] - xa[1] * yb[1] - (ya[0] * xb[0] - ya[1] * xb[1]);
+                    im += xa[0] * yb[1] + xa[1] * yb[0] - (ya[0] * xb[1] + ya[1] * xb[0]);
+                }
+                out[2 * ((size_t)r * n + c)] = im;       // -i (re + i im) = im - i re
+                out[2 * ((size_t)r * n + c) + 1] = -re;
+            }
+        if (ctx->hermitian)
+            for (int r = 0; r < n; ++r)
+                for (int c = r; c < n; ++c) {
+                    double* a = out + 2 * ((size_t)r * n + c);
+                    double* b = out + 2 * ((size_t)c * n + r);
+                    const double re = 0.5 * (a[0] + b[0]), im = (r == c) ? 0.0 : 0.5 * (a[1] - b[1]);
+                    a[0] = re; a[1] = im;
+                    b[0] = re; b[1] = -im;
+                }
+    };
+    for (int k = 0; k < K; ++k)
+        neg_i_commutator(p->g + (size_t)k * nn * 2, p->h0, ge.data() + (size_t)(K + k) * nn * 2);
+    int e = 2 * K;
+    for (int k = 0; k < K; ++k)
+        for (int l = k + 1; l < K; ++l, ++e)
+            neg_i_commutator(p->g + (size_t)k * nn * 2, p->g + (size_t)l * nn * 2,
+                             ge.data() + (size_t)e * nn * 2);
+    if (ctx->eff.images.build(ge.data(), (size_t)Ke, n, ctx->nb, ctx->stream) ||
+        ctx->eff.interp_id.upload(identity_interp(ctx->nsteps), ctx->stream))
+        return QOCX_ERR_HIP;
+    ctx->eff.kind = EffectiveControls::M4_LINEAR;
+    ctx->eff.Ke = Ke;
+    return 0;
+}
+
+// initial states, padded
+int upload_initial_states(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
+    const int n = ctx->n, np = ctx->np, S = ctx->S;
+    std::vector<double2> psi((size_t)S * np, make_double2(0, 0));
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < n; ++i)
+            psi[(size_t)s * np + i] = make_double2(p->initial_states[2 * ((size_t)s * n + i)],
+                                                   p->initial_states[2 * ((size_t)s * n + i) + 1]);
+    return ctx->psi0.upload(psi, ctx->stream) ? QOCX_ERR_HIP : 0;
+}
+
+// interpolation table at the quadrature times t_j + c_q dt of the Magnus policy
+// (mathmethods.py:54-65; nodes :72, :96-97, :125-127), and its transpose for scatter_kernel
+int upload_interpolation(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
+    const int K = ctx->K, nc = ctx->nc, nsteps = ctx->nsteps, nodes = ctx->nodes;
+    static const double node_c[3][3] = {
+        {0.5, 0, 0},
+        {0.5 - std::sqrt(3.0) / 6, 0.5 + std::sqrt(3.0) / 6, 0},
+        {0.5 - std::sqrt(15.0) / 10, 0.5, 0.5 + std::sqrt(15.0) / 10}};
+    std::vector<qocx::StepInterp> interp((size_t)nsteps * nodes);
+    std::vector<std::vector<std::pair<int, double>>> rows(K > 0 ? nc : 0);
+    ctx->pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
+    if (K > 0 && ctx->pwc) {
+        // piecewise constant: a node reads the slice it lies in, u = controls[min(floor(x nc / T), nc - 1)]
+        // (right-continuous at the interior edges). i1 == i2, dx = 1, off = 0: control_at returns
+        // y1 + ((y1 - y1) / 1) * 0 = y1 bit for bit, and the slice's row takes the node's cotangent whole.
+        for (int j = 0; j < nsteps; ++j)
+            for (int q = 0; q < nodes; ++q) {
+                const double x = j * ctx->dt + ctx->dt * node_c[nodes - 1][q];
+                const double f = std::floor(x * nc / p->evolution_time);
+                const int slice = f >= nc - 1 ? nc - 1 : (f > 0 ? (int)f : 0);
+                interp[(size_t)j * nodes + q] = qocx::StepInterp{slice, slice, 1.0, 0.0};
+                rows[slice].push_back(std::make_pair(j * nodes + q, 1.0));
+            }
+    } else if (K > 0) {
+        std::vector<double> xs(nc);
+        const double stepx = p->evolution_time / (nc - 1);  // numpy.linspace
+        for (int i = 0; i < nc; ++i) xs[i] = i * stepx;
+        xs[nc - 1] = p->evolution_time;
+        for (int j = 0; j < nsteps; ++j)
+            for (int q = 0; q < nodes; ++q) {
+                const double time = j * ctx->dt;
+                const double x = time + ctx->dt * node_c[nodes - 1][q];
+                int i1, i2;
+                if (x <= xs[0]) {
+                    i1 = 0; i2 = 1;
+                } else if (x >= xs[nc - 1]) {
+                    i1 = nc - 2; i2 = nc - 1;
+                } else {
+                    int idx = 0;
+                    while (!(x <= xs[idx])) ++idx;
+                    i1 = idx - 1; i2 = idx;
+                }
+                qocx::StepInterp& e = interp[(size_t)j * nodes + q];
+                e.i1 = i1; e.i2 = i2;
+                e.dx = xs[i2] - xs[i1];
+                e.off = x - xs[i1];
+                const double theta = e.off / e.dx;
+                rows[i1].push_back(std::make_pair(j * nodes + q, 1.0 - theta));
+                rows[i2].push_back(std::make_pair(j * nodes + q, theta));
+            }
+    } else {
+        for (auto& e : interp) e = qocx::StepInterp{0, 0, 1.0, 0.0};
+    }
+    if (ctx->interp.upload(interp, ctx->stream)) return QOCX_ERR_HIP;
+    std::vector<int> row_ptr(1, 0), col_step;
+    std::vector<double> weight;
+    for (auto& r : rows) {
+        for (auto& e : r) {
+            col_step.push_back(e.first);
+            weight.push_back(e.second);
+        }
+        row_ptr.push_back((int)col_step.size());
+    }
+    if (ctx->row_ptr.upload(row_ptr, ctx->stream)) return QOCX_ERR_HIP;
+    if (ctx->col_step.upload(col_step, ctx->stream)) return QOCX_ERR_HIP;
+    if (ctx->weight.upload(weight, ctx->stream)) return QOCX_ERR_HIP;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -320,234 +555,34 @@ int qocx_synchronize(qocx_ctx* ctx) {
 
 int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
     if (!ctx || !p) return fail(QOCX_ERR_ARG, "NULL argument");
-    if (p->struct_size != (int32_t)sizeof(qocx_schroedinger_problem))
-        return fail(QOCX_ERR_ARG, "qocx_schroedinger_problem.struct_size does not match this "
-                                  "library's header (stale binding?)");
+    if (int rc = check_problem(p)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const int n = p->hilbert_size, S = p->state_count, K = p->control_count;
-    const int N = p->system_eval_count, nc = p->control_eval_count;
-    if (n < 1 || n > 1024)
-        return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..1024 (1..64: the wavefront kernels; 65..1024: the general "
-                                  "path of qocx_general.hip)");
-
-    // (a full propagator has n states: up to 256 of them on the general path)
-    if (S < 1 || S > (n > 64 ? 1024 : 64)) return fail(QOCX_ERR_ARG, "state_count must be in 1..64 (1..1024 above hilbert_size 64)");
-    if (K < 0 || K > 64) return fail(QOCX_ERR_ARG, "control_count must be in 0..64");
-    if (N < 2) return fail(QOCX_ERR_ARG, "system_eval_count must be >= 2");
-    if (K > 0 && nc < 2) return fail(QOCX_ERR_ARG, "control_eval_count must be >= 2");
-    if (p->cost_eval_step < 1) return fail(QOCX_ERR_ARG, "cost_eval_step must be >= 1");
-    if (p->magnus_policy != QOCX_MAGNUS_M2 && p->magnus_policy != QOCX_MAGNUS_M4 &&
-        p->magnus_policy != QOCX_MAGNUS_M6)
-        return fail(QOCX_ERR_ARG, "unknown magnus_policy");
-    const int nsteps = N - 1;
-    const int nodes = p->magnus_policy / 2;  // quadrature nodes per step: 1, 2, 3
-    if (p->nt != 1 && p->nt != nsteps * nodes)
-        return fail(QOCX_ERR_ARG, "nt must be 1 or (N-1) * (quadrature nodes of the policy)");
-    if (!p->h0 || !p->initial_states || (K > 0 && !p->g))
-        return fail(QOCX_ERR_ARG, "h0 / g / initial_states missing");
-    if (p->cost_count < 0 || (p->cost_count > 0 && !p->costs))
-        return fail(QOCX_ERR_ARG, "costs missing");
-
     // matrices are padded to 16, 32 or 64: one, four or sixteen MFMA tiles (33 <= n <= 64 runs on
     // the four-wave K1a of qocx_pade4.hip and the NB = 4 forms of K1b / K2 / K3)
     // (n > 64: nb = ceil(n / 16) > 4 selects the general path; it reads the row-major padded matrices that
-    // h0_timg / g_timg hold - the column-major images of the transposes)
-    const int nb = (n <= 16) ? 1 : (n <= 32 ? 2 : (n <= 64 ? 4 : (n + 15) / 16)), np = 16 * nb, mat = np * np, nt = p->nt;
+    // the t-images hold - the column-major images of the transposes)
+    const int n = p->hilbert_size, N = p->system_eval_count;
+    const int nb = (n <= 16) ? 1 : (n <= 32 ? 2 : (n <= 64 ? 4 : (n + 15) / 16));
     ctx->has_problem = false;
     ctx->control_costs.clear();
-    ctx->n = n; ctx->nb = nb; ctx->np = np; ctx->S = S; ctx->K = K; ctx->nc = nc; ctx->N = N;
-    ctx->nsteps = nsteps; ctx->ces = p->cost_eval_step; ctx->nt = nt; ctx->nodes = nodes;
+    ctx->n = n; ctx->nb = nb; ctx->np = 16 * nb; ctx->S = p->state_count; ctx->K = p->control_count;
+    ctx->nc = p->control_eval_count; ctx->N = N; ctx->nsteps = N - 1; ctx->ces = p->cost_eval_step;
+    ctx->nt = p->nt; ctx->nodes = p->magnus_policy / 2;
     ctx->T = p->evolution_time;
     ctx->dt = p->evolution_time / (N - 1);  // programstate.py:44
-
-    {
-        auto is_hermitian = [n](const double* m) {
-            for (int r = 0; r < n; ++r)
-                for (int c = r; c < n; ++c)
-                    if (m[2 * ((size_t)r * n + c)] != m[2 * ((size_t)c * n + r)] ||
-                        m[2 * ((size_t)r * n + c) + 1] != -m[2 * ((size_t)c * n + r) + 1])
-                        return false;
-            return true;
-        };
-        bool herm = true;
-        for (int t = 0; t < p->nt && herm; ++t) {
-            herm = is_hermitian(p->h0 + (size_t)t * n * n * 2);
-            for (int k = 0; k < K && herm; ++k)
-                herm = is_hermitian(p->g + ((size_t)t * K + k) * n * n * 2);
-        }
-        ctx->hermitian = herm ? 1 : 0;
-        ctx->hermitian_linear = ctx->hermitian;
-    }
-    ctx->quad_count = 0;  // a new problem clears the quadratic terms
-    ctx->ens_M = 0;       // ... and the ensemble
+    ctx->eff.kind = EffectiveControls::NONE;  // a new problem clears the quadratic terms
+    ctx->ens_M = 0;                           // ... and the ensemble
     ctx->ens_qscales_set = false;
-    // Hamiltonian images + norms for the squaring bound
-    std::vector<double2> img((size_t)nt * mat);
-    ctx->h0_norm_max = 0;
-    for (int t = 0; t < nt; ++t) {
-        const double* m = p->h0 + (size_t)t * n * n * 2;
-        ctx->h0_norm_max = std::max(ctx->h0_norm_max, one_norm(m, n));
-        c_image(m, n, nb, img.data() + (size_t)t * mat);
-    }
-    if (ctx->h0_cimg.upload(img, ctx->stream)) return QOCX_ERR_HIP;
-    for (int t = 0; t < nt; ++t) r_image(p->h0 + (size_t)t * n * n * 2, n, np, false, img.data() + (size_t)t * mat);
-    if (ctx->h0_rimg.upload(img, ctx->stream)) return QOCX_ERR_HIP;
-    for (int t = 0; t < nt; ++t) r_image(p->h0 + (size_t)t * n * n * 2, n, np, true, img.data() + (size_t)t * mat);
-    if (ctx->h0_timg.upload(img, ctx->stream)) return QOCX_ERR_HIP;
-    ctx->g_norm_max.assign(K, 0.0);
-    std::vector<double2> gimg((size_t)nt * K * mat);
-    for (int pass = 0; pass < 3; ++pass) {
-        for (int t = 0; t < nt; ++t)
-            for (int k = 0; k < K; ++k) {
-                const double* m = p->g + ((size_t)t * K + k) * n * n * 2;
-                double2* dst = gimg.data() + ((size_t)t * K + k) * mat;
-                if (pass == 0) {
-                    ctx->g_norm_max[k] = std::max(ctx->g_norm_max[k], one_norm(m, n));
-                    c_image(m, n, nb, dst);
-                } else {
-                    r_image(m, n, np, pass == 2, dst);
-                }
-            }
-        DevBuf<double2>& dst = pass == 0 ? ctx->g_cimg : (pass == 1 ? ctx->g_rimg : ctx->g_timg);
-        if (dst.upload(gimg, ctx->stream)) return QOCX_ERR_HIP;
-    }
-    if (K > 0 && ctx->g_norm_dev.upload(ctx->g_norm_max, ctx->stream)) return QOCX_ERR_HIP;  // step table
 
-    // M4, time-independent H0 / G_k: the commutators leave the time loop (M4LinArgs). Constant
-    // matrices G_k, A_k = -i [G_k, H0], B_kl = -i [G_k, G_l] (k < l); Hermitian when H0 and the
-    // G_k are (made so bit for bit, the Hermitian kernel forms rely on it).
-    ctx->m4lin_Ke = 0;
-    if (nodes == 2 && nt == 1 && K >= 1 && K <= QOCX_M4LIN_MAX_K) {
-        const int Ke = 2 * K + K * (K - 1) / 2;
-        const size_t nn = (size_t)n * n;
-        std::vector<double> ge((size_t)Ke * nn * 2);
-        std::copy(p->g, p->g + (size_t)K * nn * 2, ge.begin());
-        auto neg_i_commutator = [&](const double* x, const double* y, double* out) {
-            for (int r = 0; r < n; ++r)
-                for (int c = 0; c < n; ++c) {
-                    double re = 0, im = 0;  // (x y - y x)[r][c]
-                    for (int q = 0; q < n; ++q) {
-                        const double* xa = x + 2 * ((size_t)r * n + q);
-                        const double* yb = y + 2 * ((size_t)q * n + c);
-                        const double* ya = y + 2 * ((size_t)r * n + q);
-                        const double* xb = x + 2 * ((size_t)q * n + c);
-                        re += xa[0] * yb[0] - xa[1] * yb[1] - (ya[0] * xb[0] - ya[1] * xb[1]);
-                        im += xa[0] * yb[1] + xa[1] * yb[0] - (ya[0] * xb[1] + ya[1] * xb[0]);
-                    }
-                    out[2 * ((size_t)r * n + c)] = im;       // -i (re + i im) = im - i re
-                    out[2 * ((size_t)r * n + c) + 1] = -re;
-                }
-            if (ctx->hermitian)
-                for (int r = 0; r < n; ++r)
-                    for (int c = r; c < n; ++c) {
-                        double* a = out + 2 * ((size_t)r * n + c);
-                        double* b = out + 2 * ((size_t)c * n + r);
-                        const double re = 0.5 * (a[0] + b[0]), im = (r == c) ? 0.0 : 0.5 * (a[1] - b[1]);
-                        a[0] = re; a[1] = im;
-                        b[0] = re; b[1] = -im;
-                    }
-        };
-        for (int k = 0; k < K; ++k)
-            neg_i_commutator(p->g + (size_t)k * nn * 2, p->h0, ge.data() + (size_t)(K + k) * nn * 2);
-        int e = 2 * K;
-        for (int k = 0; k < K; ++k)
-            for (int l = k + 1; l < K; ++l, ++e)
-                neg_i_commutator(p->g + (size_t)k * nn * 2, p->g + (size_t)l * nn * 2,
-                                 ge.data() + (size_t)e * nn * 2);
-        std::vector<double2> eimg((size_t)Ke * mat);
-        for (int pass = 0; pass < 3; ++pass) {
-            for (int k = 0; k < Ke; ++k) {
-                const double* m = ge.data() + (size_t)k * nn * 2;
-                if (pass == 0) c_image(m, n, nb, eimg.data() + (size_t)k * mat);
-                else r_image(m, n, np, pass == 2, eimg.data() + (size_t)k * mat);
-            }
-            DevBuf<double2>& dst = pass == 0 ? ctx->ge_cimg : (pass == 1 ? ctx->ge_rimg : ctx->ge_timg);
-            if (dst.upload(eimg, ctx->stream)) return QOCX_ERR_HIP;
-        }
-        std::vector<qocx::StepInterp> ident(nsteps);
-        for (int j = 0; j < nsteps; ++j) ident[j] = qocx::StepInterp{j, j, 1.0, 0.0};
-        if (ctx->interp_id.upload(ident, ctx->stream)) return QOCX_ERR_HIP;
-        ctx->m4lin_Ke = Ke;
-    }
-
-    // initial states, padded
-    std::vector<double2> psi((size_t)S * np, make_double2(0, 0));
-    for (int s = 0; s < S; ++s)
-        for (int i = 0; i < n; ++i)
-            psi[(size_t)s * np + i] = make_double2(p->initial_states[2 * ((size_t)s * n + i)],
-                                                   p->initial_states[2 * ((size_t)s * n + i) + 1]);
-    if (ctx->psi0.upload(psi, ctx->stream)) return QOCX_ERR_HIP;
-
-    // interpolation table at the quadrature times t_j + c_q dt of the Magnus policy
-    // (mathmethods.py:54-65; nodes :72, :96-97, :125-127)
-    static const double node_c[3][3] = {
-        {0.5, 0, 0},
-        {0.5 - std::sqrt(3.0) / 6, 0.5 + std::sqrt(3.0) / 6, 0},
-        {0.5 - std::sqrt(15.0) / 10, 0.5, 0.5 + std::sqrt(15.0) / 10}};
-    std::vector<qocx::StepInterp> interp((size_t)nsteps * nodes);
-    std::vector<std::vector<std::pair<int, double>>> rows(K > 0 ? nc : 0);
-    ctx->pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
-    if (K > 0 && ctx->pwc) {
-        // piecewise constant: a node reads the slice it lies in, u = controls[min(floor(x nc / T), nc - 1)]
-        // (right-continuous at the interior edges). i1 == i2, dx = 1, off = 0: control_at returns
-        // y1 + ((y1 - y1) / 1) * 0 = y1 bit for bit, and the slice's row takes the node's cotangent whole.
-        for (int j = 0; j < nsteps; ++j)
-            for (int q = 0; q < nodes; ++q) {
-                const double x = j * ctx->dt + ctx->dt * node_c[nodes - 1][q];
-                const double f = std::floor(x * nc / p->evolution_time);
-                const int slice = f >= nc - 1 ? nc - 1 : (f > 0 ? (int)f : 0);
-                interp[(size_t)j * nodes + q] = qocx::StepInterp{slice, slice, 1.0, 0.0};
-                rows[slice].push_back(std::make_pair(j * nodes + q, 1.0));
-            }
-    } else if (K > 0) {
-        std::vector<double> xs(nc);
-        const double stepx = p->evolution_time / (nc - 1);  // numpy.linspace
-        for (int i = 0; i < nc; ++i) xs[i] = i * stepx;
-        xs[nc - 1] = p->evolution_time;
-        for (int j = 0; j < nsteps; ++j)
-            for (int q = 0; q < nodes; ++q) {
-                const double time = j * ctx->dt;
-                const double x = time + ctx->dt * node_c[nodes - 1][q];
-                int i1, i2;
-                if (x <= xs[0]) {
-                    i1 = 0; i2 = 1;
-                } else if (x >= xs[nc - 1]) {
-                    i1 = nc - 2; i2 = nc - 1;
-                } else {
-                    int idx = 0;
-                    while (!(x <= xs[idx])) ++idx;
-                    i1 = idx - 1; i2 = idx;
-                }
-                qocx::StepInterp& e = interp[(size_t)j * nodes + q];
-                e.i1 = i1; e.i2 = i2;
-                e.dx = xs[i2] - xs[i1];
-                e.off = x - xs[i1];
-                const double theta = e.off / e.dx;
-                rows[i1].push_back(std::make_pair(j * nodes + q, 1.0 - theta));
-                rows[i2].push_back(std::make_pair(j * nodes + q, theta));
-            }
-    } else {
-        for (auto& e : interp) e = qocx::StepInterp{0, 0, 1.0, 0.0};
-    }
-    if (ctx->interp.upload(interp, ctx->stream)) return QOCX_ERR_HIP;
-    std::vector<int> row_ptr(1, 0), col_step;
-    std::vector<double> weight;
-    for (auto& r : rows) {
-        for (auto& e : r) {
-            col_step.push_back(e.first);
-            weight.push_back(e.second);
-        }
-        row_ptr.push_back((int)col_step.size());
-    }
-    if (ctx->row_ptr.upload(row_ptr, ctx->stream)) return QOCX_ERR_HIP;
-    if (ctx->col_step.upload(col_step, ctx->stream)) return QOCX_ERR_HIP;
-    if (ctx->weight.upload(weight, ctx->stream)) return QOCX_ERR_HIP;
-
+    set_hermitian_flags(ctx, p);
+    if (int rc = upload_operators(ctx, p)) return rc;
+    if (int rc = upload_m4_commutators(ctx, p)) return rc;
+    if (int rc = upload_initial_states(ctx, p)) return rc;
+    if (int rc = upload_interpolation(ctx, p)) return rc;
     if (int rc = upload_costs(ctx, p)) return rc;
     // More states than the wavefront sweep's LDS holds (33 <= n <= 64: more than 13 - a full propagator there
     // has n): the general path, whose sweep keeps its vectors in HBM, takes the problem where it can
-    ctx->general_path = nb > 4;
-    if (nb <= 4 && qocx::sweep_lds_bytes(nb, S) > 160 * 1024) ctx->general_path = true;
+    ctx->general_path = nb > 4 || qocx::sweep_lds_bytes(nb, ctx->S) > 160 * 1024;
     ctx->has_problem = true;
     ctx->have_results = false;
     ctx->B = 0;
@@ -570,7 +605,7 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     if (count < 0) return fail(QOCX_ERR_ARG, "count must be >= 0");
     HIP_TRY(hipSetDevice(ctx->device));
     if (count == 0) {
-        ctx->quad_count = 0;
+        if (ctx->eff.kind == EffectiveControls::QUADRATIC) ctx->eff.kind = EffectiveControls::NONE;
         ctx->ens_qscales_set = false;
         ctx->hermitian = ctx->hermitian_linear;
         ctx->have_results = false;
@@ -581,7 +616,7 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     if (ctx->nodes != 1)
         return fail(QOCX_ERR_ARG, "quadratic terms need magnus_policy M2 (M4 / M6 take the callable's tangent)");
     if (ctx->explicit_mode) return fail(QOCX_ERR_ARG, "quadratic terms do not apply to explicit generators");
-    const int n = ctx->n, K = ctx->K, nt = ctx->nt, nb = ctx->nb, np = ctx->np;
+    const int n = ctx->n, K = ctx->K, nt = ctx->nt, np = ctx->np;
     if (K < 1) return fail(QOCX_ERR_ARG, "quadratic terms need control_count >= 1");
     // (with an ensemble K = K_r + J: the fixed channels count towards the limit, and the pairs index
     // the seeds' K_r channels - qocx_set_ensemble makes the same check when it comes second)
@@ -608,41 +643,30 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
         for (size_t e = 0; e < nn * 2; ++e)
             if (!std::isfinite(m[e])) return fail(QOCX_ERR_ARG, "non-finite quadratic term matrix");
         norms[q] = one_norm(m, n);
-        for (int r = 0; r < n && herm; ++r)  // Hermitian bit for bit, as qocx_set_schroedinger_problem
-            for (int c = r; c < n && herm; ++c)
-                herm = m[2 * ((size_t)r * n + c)] == m[2 * ((size_t)c * n + r)] &&
-                       m[2 * ((size_t)r * n + c) + 1] == -m[2 * ((size_t)c * n + r) + 1];
+        herm = herm && hermitian_bitwise(m, n);
     }
     // augmented images [nt][G_0 .. G_K-1, Q_0 .. Q_count-1], built on the device from the G_k images
-    std::vector<double2> qimg((size_t)count * mat);
-    DevBuf<double2> qdev;
-    for (int pass = ctx->general_path ? 2 : 0; pass < 3; ++pass) {
-        for (int q = 0; q < count; ++q) {
-            const double* m = matrices + (size_t)q * nn * 2;
-            if (pass == 0) c_image(m, n, nb, qimg.data() + (size_t)q * mat);
-            else r_image(m, n, np, pass == 2, qimg.data() + (size_t)q * mat);
-        }
-        if (qdev.upload(qimg, ctx->stream)) return QOCX_ERR_HIP;
-        DevBuf<double2>& src = pass == 0 ? ctx->g_cimg : (pass == 1 ? ctx->g_rimg : ctx->g_timg);
-        DevBuf<double2>& dst = pass == 0 ? ctx->ge_cimg : (pass == 1 ? ctx->ge_rimg : ctx->ge_timg);
+    OperatorImages q;
+    if (q.build(matrices, (size_t)count, n, ctx->nb, ctx->stream, ctx->general_path)) return QOCX_ERR_HIP;
+    const size_t gbytes = (size_t)K * mat * sizeof(double2), qbytes = (size_t)count * mat * sizeof(double2);
+    for (int i = ctx->general_path ? 2 : 0; i < 3; ++i) {
+        DevBuf<double2>& dst = ctx->eff.images.layout(i);
         if (dst.ensure((size_t)nt * Ke * mat)) return QOCX_ERR_HIP;
-        const size_t gbytes = (size_t)K * mat * sizeof(double2), qbytes = (size_t)count * mat * sizeof(double2);
-        HIP_TRY(hipMemcpy2DAsync(dst.p, gbytes + qbytes, src.p, gbytes, gbytes, nt, hipMemcpyDeviceToDevice,
-                                 ctx->stream));
+        HIP_TRY(hipMemcpy2DAsync(dst.p, gbytes + qbytes, ctx->g.layout(i).p, gbytes, gbytes, nt,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
         for (int t = 0; t < nt; ++t)
-            HIP_TRY(hipMemcpyAsync(dst.p + ((size_t)t * Ke + K) * mat, qdev.p, qbytes, hipMemcpyDeviceToDevice,
+            HIP_TRY(hipMemcpyAsync(dst.p + ((size_t)t * Ke + K) * mat, q.layout(i).p, qbytes, hipMemcpyDeviceToDevice,
                                    ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // qdev is released at the end of this scope
     }
-    qdev.release();
-    std::vector<qocx::StepInterp> ident(ctx->nsteps);
-    for (int j = 0; j < ctx->nsteps; ++j) ident[j] = qocx::StepInterp{j, j, 1.0, 0.0};
     std::vector<int> pr(pairs, pairs + 2 * (size_t)count);
-    if (ctx->interp_id.upload(ident, ctx->stream) || ctx->quad_pairs_dev.upload(pr, ctx->stream)) return QOCX_ERR_HIP;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->quad_pairs = pr;
-    ctx->quad_norm = norms;
-    ctx->quad_count = count;
+    if (ctx->eff.interp_id.upload(identity_interp(ctx->nsteps), ctx->stream) ||
+        ctx->eff.pairs_dev.upload(pr, ctx->stream))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // q is released at the end of this scope
+    ctx->eff.pairs = pr;
+    ctx->eff.norm = norms;
+    ctx->eff.kind = EffectiveControls::QUADRATIC;
+    ctx->eff.Ke = Ke;
     ctx->ens_qscales_set = false;  // (scales of the previous terms)
     ctx->hermitian = herm ? 1 : 0;
     ctx->have_results = false;
@@ -664,8 +688,8 @@ int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const doubl
     const int M = members, J = fixed, Kr = ctx->K - fixed;
     // quadratic terms are products of the seeds' channels (qocx_set_quadratic_terms checks the same
     // when it comes second)
-    for (int q = 0; q < ctx->quad_count; ++q)
-        if (ctx->quad_pairs[2 * q + 1] >= Kr)
+    for (int q = 0; q < ctx->eff.quad_count(); ++q)
+        if (ctx->eff.pairs[2 * q + 1] >= Kr)
             return fail(QOCX_ERR_ARG, "quadratic term pairs must index the ensemble's seed channels "
                                       "(l < control_count - fixed)");
     std::vector<double> sc((size_t)M * Kr, 1.0), off((size_t)M * J), w(weights, weights + M);
@@ -707,10 +731,10 @@ int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t c
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
     if (ctx->ens_M == 0) return fail(QOCX_ERR_ARG, "quadratic term scales need an ensemble (qocx_set_ensemble)");
-    if (ctx->quad_count == 0)
+    if (ctx->eff.quad_count() == 0)
         return fail(QOCX_ERR_ARG, "quadratic term scales need quadratic terms (qocx_set_quadratic_terms)");
     if (members != ctx->ens_M) return fail(QOCX_ERR_ARG, "members does not match the ensemble's");
-    if (count != ctx->quad_count) return fail(QOCX_ERR_ARG, "count does not match the quadratic terms'");
+    if (count != ctx->eff.quad_count()) return fail(QOCX_ERR_ARG, "count does not match the quadratic terms'");
     if (!scales) {
         ctx->ens_qscales_set = false;
     } else {
@@ -783,15 +807,17 @@ double magnus_norm_bound(int nodes, double bound) {
 // product: it needs no pass over the members per upload and can only cost a squaring, not digits.
 double quad_bound(const qocx_ctx* ctx, const double* umax) {
     double b = 0.0;
+    if (ctx->effctl_kind(false) != EffectiveControls::QUADRATIC) return b;
+    const EffectiveControls& eff = ctx->eff;
     const bool ens = ctx->ens_M > 0;
-    for (int q = 0; q < ctx->quad_count; ++q) {
-        const int k = ctx->quad_pairs[2 * q], l = ctx->quad_pairs[2 * q + 1];
+    for (int q = 0; q < eff.quad_count(); ++q) {
+        const int k = eff.pairs[2 * q], l = eff.pairs[2 * q + 1];
         if (!ens) {
-            b += ctx->quad_norm[q] * fabs(umax[k]) * fabs(umax[l]);
+            b += eff.norm[q] * fabs(umax[k]) * fabs(umax[l]);
             continue;
         }
         const double c = ctx->ens_qscales_set ? ctx->ens_qscale_max[q] : 1.0;
-        b += ctx->quad_norm[q] * c * (ctx->ens_scale_max[k] * fabs(umax[k])) * (ctx->ens_scale_max[l] * fabs(umax[l]));
+        b += eff.norm[q] * c * (ctx->ens_scale_max[k] * fabs(umax[k])) * (ctx->ens_scale_max[l] * fabs(umax[l]));
     }
     return b;
 }
@@ -937,7 +963,7 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         }
         // (piecewise constant: a step reads ONE slice, never the mean of two rows - the knot sums
         // above are then exact for every step and the midpoint bound does not apply)
-        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->quad_count == 0 && !ctx->pwc)
+        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->eff.quad_count() == 0 && !ctx->pwc)
             ctx->norm_bound_mid = (bound + smid) * fabs(ctx->dt) * (1.0 + 1e-12);
         else
             ctx->norm_bound_mid = 1e300;
@@ -947,7 +973,7 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // |r_k| does hold everywhere (linear interpolation): ||Q_q||_1 max|r_k| max|r_l| bounds every step.
         // (with an ensemble the staging buffer holds the seeds' K_r channels, unscaled: quad_bound
         // applies the members' scales)
-        if (ctx->quad_count > 0)
+        if (ctx->eff.quad_count() > 0)
             bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, ens ? ctx->ens_Kr : K).data());
         if (ens) {
             if (int rc = ensemble_upload(ctx, batch, stage)) return rc;
@@ -959,12 +985,7 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     }
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or Hamiltonian");
-    ctx->sbound = pade_scale_count(bound);
-    ctx->norm_bound = bound;
-    if (ctx->sbound > 10)
-        return fail(QOCX_ERR_CAPACITY,
-                    "||dt H||_1 bound needs more than 2^10 squaring sub-steps per step; reduce dt");
-    ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
+    if (int rc = commit_step_bound(ctx, bound, false, "bound needs")) return rc;
     ctx->B = ens ? batch * ctx->ens_M : batch;
     ctx->ens_B = ens ? batch : 0;
     ctx->have_results = false;
@@ -1003,13 +1024,8 @@ int qocx_upload_generators(qocx_ctx* ctx, int32_t batch, const double* generator
         if (!(norm1 <= worst)) worst = norm1;
     }
     if (!(worst < 1e300)) return fail(QOCX_ERR_ARG, "non-finite generator");
-    ctx->sbound = pade_scale_count(worst);
-    ctx->norm_bound = worst;
     ctx->norm_bound_mid = 1e300;
-    if (ctx->sbound > 10)
-        return fail(QOCX_ERR_CAPACITY,
-                    "||dt H||_1 needs more than 2^10 squaring sub-steps per step; reduce dt");
-    ctx->slot_cap = ((size_t)nsteps << ctx->sbound) + 1;
+    if (int rc = commit_step_bound(ctx, worst, false, "needs")) return rc;
     if (ctx->gen_rm.upload(padded, ctx->stream)) return QOCX_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->B = batch;

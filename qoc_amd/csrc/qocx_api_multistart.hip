@@ -456,14 +456,7 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     bound += quad_bound(ctx, channel_norms.data());
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
-    const int sb = pade_scale_count(bound);
-    if (sb > 10)
-        return fail(QOCX_ERR_CAPACITY,
-                    "||dt H||_1 bound needs more than 2^10 squaring sub-steps per step; reduce dt");
-    ctx->sbound = std::max(ctx->sbound, sb);
-    ctx->norm_bound = std::max(ctx->norm_bound, bound);
-    ctx->norm_bound_mid = 1e300;  // (the controls move on the device from here on)
-    ctx->slot_cap = ((size_t)ctx->nsteps << ctx->sbound) + 1;
+    if (int rc = commit_step_bound(ctx, bound, true, "bound needs")) return rc;
     // (the Lindblad path checks the second of these grid limits in qocx_lindblad_upload_controls and has
     // no check of the first: to be revisited)
     if ((v.total() + 255) / 256 > 0x7fffffffu || v.per_seed() > 65535u * 256u)

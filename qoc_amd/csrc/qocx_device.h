@@ -215,37 +215,34 @@ struct MagnusArgs {
     int n = 0;                 // Hilbert size (qocx_magnus4w.hip: 33..48 -> the three-wave form)
 };
 
-// Magnus M4 with time-independent H0, G_k ("commutator-free" form, qocx_magnus.hip): the step
-// generator is LINEAR in effective controls with constant matrices,
-//   m4 = -i dt (H0 + sum_k v_k G_k + sum_k w_k A_k + sum_{k<l} z_kl B_kl),
-//   A_k = -i [G_k, H0], B_kl = -i [G_k, G_l],
-//   v_k = (u1_k + u2_k) / 2, w_k = F0 dt (u2_k - u1_k), z_kl = F0 dt (u2_k u1_l - u2_l u1_k)
-// with u1, u2 the controls at the two quadrature nodes, so the M2 kernels run it unchanged on
-// Ke = 2 K + K (K - 1) / 2 effective controls given per step.
-#define QOCX_M4LIN_MAX_K 8
-struct M4LinArgs {
+// Effective controls (qocx_effctl.hip): a step generator that is LINEAR in Ke effective controls
+// over an augmented operator set runs on the M2 kernels unchanged. What the two routes share:
+struct EffCtlArgs {
     const double* controls;    // [B][nc][K]
-    const StepInterp* interp;  // [nsteps * 2]
+    const StepInterp* interp;  // the problem's table: [nsteps * 2] (M4-linear), [nsteps] (quadratic)
     int K, Ke, nc, nsteps, S;
-    double f0dt;               // F0 * dt
     double* veff;              // controls kernel out: [B][nsteps][Ke]
     const double* gstep;       // chain kernel in: [B][nsteps][Ke] (x 2: complex, unit adjoint)
     const double2* lam_scale;  // unit adjoint: [B][S] (see ScatterArgs), or nullptr
-    double* gnode;             // chain kernel out: [B][nsteps * 2][K]
+    double* gchain;            // chain kernel out, read by scatter_kernel (real, lam_scale applied):
+                               // [B][nsteps * 2][K] (M4-linear), [B][nsteps][K] (quadratic)
     size_t total;              // B * nsteps
 };
 
-// Hamiltonian quadratic in the real controls (qocx_quad.hip): Ke = K + count effective controls
-struct QuadArgs {
-    const double* controls;    // [B][nc][K]
-    const StepInterp* interp;  // [nsteps]
+// Magnus M4 with time-independent H0, G_k ("commutator-free" form):
+//   m4 = -i dt (H0 + sum_k v_k G_k + sum_k w_k A_k + sum_{k<l} z_kl B_kl),
+//   A_k = -i [G_k, H0], B_kl = -i [G_k, G_l],
+//   v_k = (u1_k + u2_k) / 2, w_k = F0 dt (u2_k - u1_k), z_kl = F0 dt (u2_k u1_l - u2_l u1_k)
+// with u1, u2 the controls at the two quadrature nodes: Ke = 2 K + K (K - 1) / 2.
+#define QOCX_M4LIN_MAX_K 8
+struct M4LinArgs : EffCtlArgs {
+    double f0dt;               // F0 * dt
+};
+
+// Hamiltonian quadratic in the real controls: Ke = K + count effective controls
+struct QuadArgs : EffCtlArgs {
     const int* pairs;          // [count][2], k <= l
-    int K, Ke, count, nc, nsteps, S;
-    double* veff;              // controls kernel out: [B][nsteps][Ke]
-    const double* gstep;       // chain kernel in: [B][nsteps][Ke] (x 2: complex, unit adjoint)
-    const double2* lam_scale;  // unit adjoint: [B][S] (see ScatterArgs), or nullptr
-    double* greal;             // chain kernel out: [B][nsteps][K], read by scatter_kernel
-    size_t total;              // B * nsteps
+    int count;
     // Per-member scales of the terms (qocx_set_ensemble_quadratic_scales): item i of the evaluation
     // is member i % M of its seed, and its term q is c_(m,q) r_k r_l Q_q. nullptr: no scales - the
     // launch then takes the kernels without them.

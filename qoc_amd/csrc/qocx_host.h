@@ -136,6 +136,31 @@ struct MultiStart {
     bool complex_controls = false;    // qocx_opt_begin_complex / qocx_lindblad_opt_begin_complex
 };
 
+// Padded device images of operators (h0, g, an augmented set): the MFMA tile layout of K1a and the
+// Magnus kernels; column-major and its transpose for K3 (`t` is the general path's row-major matrix)
+struct OperatorImages {
+    DevBuf<double2> c, r, t;
+    DevBuf<double2>& layout(int i) { return i == 0 ? c : (i == 1 ? r : t); }
+    // from `count` row-major complex n x n matrices (every operator of every time sample)
+    int build(const double* m, size_t count, int n, int nb, hipStream_t st, bool t_only = false);
+};
+
+// What a problem that runs on the M2 kernels through Ke effective controls keeps (EffCtlArgs): M4
+// on a time-independent system, or H quadratic in the real controls (qocx_set_quadratic_terms),
+// which needs M2 - the two never coexist.
+struct EffectiveControls {
+    enum Kind { NONE, M4_LINEAR, QUADRATIC };
+    Kind kind = NONE;                    // what the problem offers (qocx_ctx::effctl_kind: what an evaluation uses)
+    int Ke = 0;                          // effective controls per step
+    OperatorImages images;               // the augmented set: G_k, A_k, B_kl | [nt][G_k(t), Q_q]
+    DevBuf<qocx::StepInterp> interp_id;  // row j of veff for step j
+    DevBuf<double> veff, gchain;         // per evaluation: EffCtlArgs::veff, ::gchain
+    std::vector<int> pairs;              // quadratic terms: [count][2]
+    std::vector<double> norm;            // ||Q_q||_1
+    DevBuf<int> pairs_dev;
+    int quad_count() const { return kind == QUADRATIC ? (int)pairs.size() / 2 : 0; }
+};
+
 }  // namespace qocx::host
 
 // (the host files name the shared helpers as the single file they were cut from did)
@@ -153,7 +178,8 @@ struct qocx_ctx {
     int has_step_costs = 0, cost_count = 0;
     double h0_norm_max = 0;
     std::vector<double> g_norm_max;
-    DevBuf<double2> h0_cimg, g_cimg, h0_rimg, g_rimg, h0_timg, g_timg, psi0, cost_vectors;
+    OperatorImages h0, g;  // [nt], [nt][K]
+    DevBuf<double2> psi0, cost_vectors;
     DevBuf<qocx::StepInterp> interp;
     DevBuf<qocx::DevCost> costs;
     DevBuf<int> cost_counts, row_ptr, col_step;
@@ -197,19 +223,16 @@ struct qocx_ctx {
     int hermitian = 0;  // every h0[t], g[t][k] equals its conjugate transpose bit for bit
     bool general_path = false;  // the evaluation runs on qocx_general.hip (n > 64, or S beyond the sweep's LDS)
     DevBuf<double2> m_rm, mbar_rm, magnus_scratch, lam_buf;
-    // M4 with time-independent H0 / G_k as a linear problem in Ke effective controls (M4LinArgs)
-    int m4lin_Ke = 0;  // 0: not available for this problem
-    DevBuf<double2> ge_cimg, ge_rimg, ge_timg;
-    DevBuf<qocx::StepInterp> interp_id;
-    DevBuf<double> veff, gnode;
-    // H quadratic in the real controls (qocx_set_quadratic_terms, QuadArgs): the augmented images
-    // ge_* (G_k then Q_q) and veff / gnode are shared with M4 on a linear system, which needs
-    // magnus_policy M4 - the two never coexist
-    int quad_count = 0;                  // 0: no quadratic terms
-    std::vector<int> quad_pairs;         // [count][2]
-    std::vector<double> quad_norm;       // ||Q_q||_1
-    DevBuf<int> quad_pairs_dev;
-    int hermitian_linear = 0;            // `hermitian` of H0 / G_k alone (qocx_set_quadratic_terms folds in the Q_q)
+    EffectiveControls eff;
+    // Which effective-control route an evaluation takes. The knob "m4_linear" switches M4-linear off
+    // on the resident route only: the general route (eval_general) has never consulted it.
+    EffectiveControls::Kind effctl_kind(bool resident) const {
+        using E = EffectiveControls;
+        if (explicit_mode) return E::NONE;
+        if (eff.kind == E::M4_LINEAR && nodes == 2 && (!resident || knob("m4_linear", 1))) return E::M4_LINEAR;
+        return eff.kind == E::QUADRATIC && nodes == 1 ? E::QUADRATIC : E::NONE;
+    }
+    int hermitian_linear = 0;  // `hermitian` of H0 / G_k alone (qocx_set_quadratic_terms folds in the Q_q)
     // Hamiltonian ensemble (qocx_set_ensemble, EnsembleArgs): the last ens_J of the problem's K channels
     // are fixed perturbation channels; controls, costs and gradients of the seeds live in ens_* and the
     // evaluation buffers (controls, cost_out, grads, final_out) hold the B x M member items
@@ -322,6 +345,8 @@ void time_collect(qocx_ctx* ctx);
 
 // ---- qocx_api.hip: norm bounds of the step generators; the seed-level view ----
 int pade_scale_count(double norm1);
+// sbound, norm_bound and slot_cap from a bound of ||step generator||_1; `needs`: the caller's wording
+int commit_step_bound(qocx_ctx* ctx, double bound, bool keep_larger, const char* needs);
 double one_norm(const double* m, int n);  // complex row-major
 double pade_eps_max(double theta);
 double magnus_norm_bound(int nodes, double bound);

@@ -25,36 +25,99 @@ static int finish_items(qocx_ctx* ctx, int want_grad) {
     return 0;
 }
 
-// QuadArgs of a chunk of `bc` seeds, the first of them item `b0` of the evaluation, whose real
-// controls start at `controls`. The chain kernel writes the per-step real-control cotangents into
-// gnode, which scatter_kernel then reads (real, with lam_scale already applied) - the m4lin
-// arrangement. With an ensemble the items are its members, whose controls the expansion has scaled;
-// its term scales, if set, go along (qocx_set_ensemble_quadratic_scales).
-static qocx::QuadArgs quad_args(qocx_ctx* ctx, const double* controls, const double2* lam_scale, int b0, int bc) {
+using EffKind = EffectiveControls::Kind;
+
+// The effective-control route of a chunk of `bc` seeds from item `b0` of the evaluation
+// (qocx_effctl.hip): the controls kernel in front of K1a, the argument blocks of K1a and K3
+// redirected to what it wrote, the chain kernel in front of scatter_kernel. With an ensemble the
+// items are its members; its term scales, if set, go along (qocx_set_ensemble_quadratic_scales).
+struct EffCtlChunk {
+    qocx_ctx* ctx = nullptr;
+    EffKind kind = EffectiveControls::NONE;
+    hipStream_t st = nullptr;
+    qocx::M4LinArgs m4;
     qocx::QuadArgs qa;
-    qa.controls = controls; qa.interp = ctx->interp.p; qa.pairs = ctx->quad_pairs_dev.p;
-    qa.K = ctx->K; qa.count = ctx->quad_count; qa.Ke = ctx->K + ctx->quad_count;
-    qa.nc = ctx->nc; qa.nsteps = ctx->nsteps; qa.S = ctx->S;
-    qa.veff = ctx->veff.p; qa.gstep = ctx->gstep.p; qa.lam_scale = lam_scale; qa.greal = ctx->gnode.p;
-    qa.total = (size_t)bc * ctx->nsteps;
-    if (ctx->ens_M > 0 && ctx->ens_qscales_set) {
-        qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->ens_M; qa.item0 = (size_t)b0;
+
+    static int channels(const qocx_ctx* ctx, EffKind kind) { return kind ? ctx->eff.Ke : ctx->K; }  // as K1a / K3 see them
+    // veff and the chain output of chunks of `cm` (seed, step) pairs
+    static int reserve(qocx_ctx* ctx, EffKind kind, size_t cm, int want_grad) {
+        if (!kind) return 0;
+        const size_t per_step = kind == EffectiveControls::M4_LINEAR ? 2 * ctx->K : ctx->K;
+        return ctx->eff.veff.ensure(cm * ctx->eff.Ke) || ctx->eff.gchain.ensure(want_grad ? cm * per_step : 1);
     }
-    return qa;
+
+    // fills the args, launches the controls kernel (`timed`: as a launch of K1a); lam_scale: the
+    // chunk's scalars under the unit adjoint, which the chain kernel then applies
+    void begin(qocx_ctx* c, EffKind k, const double* controls, const double2* lam_scale, int b0, int bc,
+               hipStream_t stream, bool timed) {
+        ctx = c; kind = k; st = stream;
+        if (!kind) return;
+        qocx::EffCtlArgs& a = kind == EffectiveControls::M4_LINEAR ? (qocx::EffCtlArgs&)m4 : qa;
+        a.controls = controls; a.interp = ctx->interp.p;
+        a.K = ctx->K; a.Ke = ctx->eff.Ke; a.nc = ctx->nc; a.nsteps = ctx->nsteps; a.S = ctx->S;
+        a.veff = ctx->eff.veff.p; a.gstep = ctx->gstep.p; a.lam_scale = lam_scale; a.gchain = ctx->eff.gchain.p;
+        a.total = (size_t)bc * ctx->nsteps;
+        if (timed) time_begin(ctx, 0, st);
+        if (kind == EffectiveControls::M4_LINEAR) {
+            m4.f0dt = (std::sqrt(3.0) / 12) * ctx->dt;
+            qocx::launch_m4lin_controls(m4, st);
+        } else {
+            qa.pairs = ctx->eff.pairs_dev.p; qa.count = ctx->eff.quad_count();
+            if (ctx->ens_M > 0 && ctx->ens_qscales_set) {
+                qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->ens_M; qa.item0 = (size_t)b0;
+            }
+            qocx::launch_quad_controls(qa, st);
+        }
+        if (timed) time_end(ctx, st);
+    }
+
+    // K1a: a row of Ke effective controls per step through the identity table; `g`: its operator images
+    template <class Args>
+    void redirect(Args& a, const double2*& g, const DevBuf<double2>& image) const {
+        if (!kind) return;
+        a.controls = ctx->eff.veff.p; a.interp = ctx->eff.interp_id.p; g = image.p;
+        a.K = ctx->eff.Ke; a.nc = ctx->nsteps;
+    }
+    void redirect(qocx::KrylovArgs& ka) const {  // (K3's controls follow FactorArgs)
+        if (kind) { ka.g_rimg = ctx->eff.images.r.p; ka.g_timg = ctx->eff.images.t.p; }
+    }
+
+    // launches the chain kernel; returns the buffer scatter_kernel must read
+    const double* chain(const double* gstep) const {
+        if (!kind) return gstep;
+        if (kind == EffectiveControls::M4_LINEAR) qocx::launch_m4lin_chain(m4, st);
+        else qocx::launch_quad_chain(qa, st);
+        return ctx->eff.gchain.p;
+    }
+};
+
+// per-step control cotangents -> the control gradients of the chunk [b0, b0 + bc); lam_scale: the
+// chunk's scalars under the unit adjoint (the chain kernel, where there is one, has applied them)
+static void scatter_gradients(qocx_ctx* ctx, const EffCtlChunk& eff, const double* gstep, const double2* lam_scale,
+                              int b0, int bc, hipStream_t cs) {
+    qocx::ScatterArgs sc;
+    sc.row_ptr = ctx->row_ptr.p; sc.col_step = ctx->col_step.p; sc.weight = ctx->weight.p;
+    sc.grads = ctx->grads.p + (size_t)b0 * ctx->nc * ctx->K;
+    sc.B = bc; sc.nc = ctx->nc; sc.K = ctx->K; sc.nsteps = ctx->nsteps * ctx->nodes;
+    sc.lam_scale = eff.kind ? nullptr : lam_scale;
+    sc.S = ctx->S;
+    time_begin(ctx, 3, cs);
+    sc.gstep = eff.chain(gstep);
+    qocx::launch_scatter(sc, cs);
+    time_end(ctx, cs);
 }
 
 static int eval_general(qocx_ctx* ctx, int want_grad) {
     const int B = ctx->B, np = ctx->np, S = ctx->S, K = ctx->K, nsteps = ctx->nsteps;
     const size_t mat = (size_t)np * np;
     const bool explicit_gen = ctx->explicit_mode;
-    // M4 with a time-independent system: linear in Ke effective controls with constant matrices (M4LinArgs)
-    const bool m4lin = ctx->m4lin_Ke > 0 && ctx->nodes == 2 && !explicit_gen;
+    // M4 with a time-independent system, or M2 with H quadratic in the real controls: linear in
+    // effective controls over constant / augmented matrices (EffCtlChunk)
+    const EffKind effk = ctx->effctl_kind(false);
     // M6, and M4 on a time-dependent system: generators and reverse rules by qocx_general.hip's magnus_kernel
-    const bool magnus = ctx->nodes > 1 && !m4lin && !explicit_gen;
-    // M2, H quadratic in the real controls: linear in Ke = K + count effective controls (QuadArgs)
-    const bool quad = ctx->quad_count > 0 && ctx->nodes == 1 && !explicit_gen;
+    const bool magnus = ctx->nodes > 1 && effk != EffectiveControls::M4_LINEAR && !explicit_gen;
     const int nodes = magnus ? ctx->nodes : 1;
-    const int Kk = m4lin ? ctx->m4lin_Ke : (quad ? K + ctx->quad_count : K);
+    const int Kk = EffCtlChunk::channels(ctx, effk);
     const size_t per_seed = (size_t)nsteps * (mat * 32 + 4) + ctx->slot_cap * S * np * 32 +
                             (size_t)(nsteps + 1) * 4 + (size_t)nsteps * std::max(Kk, 1) * 40;
     // (persistent workgroups with 7 scratch matrices each: as many as 16 GB hold, two per CU at most)
@@ -76,8 +139,7 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
         ctx->states.ensure((size_t)chunk * ctx->slot_cap * S * np) ||
         ctx->xs.ensure(want_grad ? (size_t)chunk * ctx->slot_cap * S * np : 1) ||
         ctx->offs.ensure((size_t)chunk * (nsteps + 1)) || ctx->gstep.ensure(cm * std::max(Kk, 1)) ||
-        (m4lin && (ctx->veff.ensure(cm * Kk) || ctx->gnode.ensure(want_grad ? cm * 2 * K : 1))) ||
-        (quad && (ctx->veff.ensure(cm * Kk) || ctx->gnode.ensure(want_grad ? cm * K : 1))) ||
+        EffCtlChunk::reserve(ctx, effk, cm, want_grad) ||
         ctx->cost_out.ensure(B) || ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) ||
         ctx->final_out.ensure((size_t)B * S * np) || ctx->lam_buf.ensure((size_t)chunk * S * np) ||
         ctx->magnus_scratch.ensure((size_t)blocks * 7 * mat))
@@ -101,37 +163,21 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
         fa.np = np; fa.K = K; fa.nc = ctx->nc; fa.nsteps = nsteps; fa.nt = ctx->nt; fa.dt = ctx->dt;
         fa.controls = ctx->controls.p ? ctx->controls.p + (size_t)b0 * ctx->nc * K : nullptr;
         fa.interp = ctx->interp.p;
-        fa.h0_rm = ctx->h0_timg.p; fa.g_rm = ctx->g_timg.p;
+        fa.h0_rm = ctx->h0.t.p; fa.g_rm = ctx->g.t.p;
         fa.gen_rm = explicit_gen ? ctx->gen_rm.p + (size_t)b0 * nsteps * mat : nullptr;
         fa.pade_policy = (int)ctx->knob("pade_order", 0);
         fa.sq_max = std::min(30, ctx->sbound);
         fa.q_img = ctx->q_img.p; fa.pinv_img = ctx->lu_img.p; fa.s_arr = ctx->s_arr.p; fa.status = ctx->status.p;
         fa.scratch = ctx->magnus_scratch.p;
         fa.total = (size_t)bc * nsteps;
-        qocx::M4LinArgs m4;
-        if (m4lin) {
-            m4.controls = fa.controls; m4.interp = ctx->interp.p;
-            m4.K = K; m4.Ke = Kk; m4.nc = ctx->nc; m4.nsteps = nsteps; m4.S = S;
-            m4.f0dt = (std::sqrt(3.0) / 12) * ctx->dt;
-            m4.veff = ctx->veff.p; m4.gstep = ctx->gstep.p; m4.gnode = ctx->gnode.p;
-            m4.lam_scale = nullptr;
-            m4.total = fa.total;
-            qocx::launch_m4lin_controls(m4, cs);
-            fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_rm = ctx->ge_timg.p;
-            fa.K = Kk; fa.nc = nsteps;
-        }
-        qocx::QuadArgs qa;
-        if (quad) {
-            qa = quad_args(ctx, fa.controls, nullptr, b0, bc);
-            qocx::launch_quad_controls(qa, cs);
-            fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_rm = ctx->ge_timg.p;
-            fa.K = Kk; fa.nc = nsteps;
-        }
+        EffCtlChunk eff;
+        eff.begin(ctx, effk, fa.controls, nullptr, b0, bc, cs, false);
+        eff.redirect(fa, fa.g_rm, ctx->eff.images.t);
         const int fblocks = (int)std::min<size_t>(fa.total, (size_t)blocks);
         qocx::MagnusArgs ma;
         if (magnus) {
             ma.controls = fa.controls; ma.interp = ctx->interp.p;
-            ma.h0_cimg = ctx->h0_timg.p; ma.g_cimg = ctx->g_timg.p;  // (row-major padded matrices here)
+            ma.h0_cimg = ctx->h0.t.p; ma.g_cimg = ctx->g.t.p;  // (row-major padded matrices here)
             ma.K = K; ma.nc = ctx->nc; ma.nsteps = nsteps; ma.nt = ctx->nt; ma.nodes = nodes;
             ma.step0 = 0; ma.seg_len = nsteps; ma.skew = 0; ma.dt = ctx->dt;
             ma.m_rm = ctx->m_rm.p; ma.mbar_rm = nullptr; ma.gstep = nullptr;
@@ -203,25 +249,7 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
                 qocx::launch_general_magnus(ma, true, std::min(fblocks, mg_blocks), cs);
                 time_end(ctx, cs);
             }
-            if (!explicit_gen) {
-                qocx::ScatterArgs sc;
-                sc.gstep = ka.gstep; sc.row_ptr = ctx->row_ptr.p; sc.col_step = ctx->col_step.p;
-                sc.weight = ctx->weight.p;
-                sc.grads = ctx->grads.p + (size_t)b0 * ctx->nc * K;
-                sc.B = bc; sc.nc = ctx->nc; sc.K = K; sc.nsteps = nsteps * ctx->nodes;
-                sc.lam_scale = nullptr; sc.S = S;
-                time_begin(ctx, 3, cs);
-                if (m4lin) {  // effective-control cotangents -> node cotangents
-                    qocx::launch_m4lin_chain(m4, cs);
-                    sc.gstep = ctx->gnode.p;
-                }
-                if (quad) {  // effective-control cotangents -> real-control cotangents per step
-                    qocx::launch_quad_chain(qa, cs);
-                    sc.gstep = ctx->gnode.p;
-                }
-                qocx::launch_scatter(sc, cs);
-                time_end(ctx, cs);
-            }
+            if (!explicit_gen) scatter_gradients(ctx, eff, ka.gstep, nullptr, b0, bc, cs);
         }
     }
     return finish_items(ctx, want_grad);
@@ -235,8 +263,7 @@ namespace {
 // across those (tests/test_gpu_engine.py::test_chunked_equals_unchunked, test_gpu_fullsize.py).
 struct ResidentRoute {
     bool latency;        // one control set at a time (the host's single-evaluation entry points)
-    bool m4lin;          // M4 on the M2 kernels (M4LinArgs): Ke controls per step, one node
-    bool quad;           // H quadratic in the real controls (QuadArgs): K + count controls per step
+    EffKind eff;         // effective controls on the M2 kernels: M4-linear (one node) or quadratic
     int Kk;              // controls as K1a / K3 see them
     int nodes;           // nodes of the generator kernels
     bool dense;          // dense-state sweep (qocx_sweepd.hip)
@@ -262,14 +289,13 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // steps: 1.1 against 2.1 / 1.8 ms (profiles/r03_latency.jsonl) - so it takes precedence
     // over "sweep_impl" = 3 there.
     r.latency = ctx->knob("latency", 0) != 0;
-    r.m4lin = ctx->m4lin_Ke > 0 && ctx->nodes == 2 && !explicit_gen && ctx->knob("m4_linear", 1);
-    // The quadratic route makes the m4lin decisions below, each for the same reason: one effective
-    // control row per step read through interp_id (nodes 1), the unit adjoint with the scalar applied
-    // by the chain kernel, no step table (it interpolates the K real controls at the knots and bounds
-    // with ||G_k||_1 alone, blind to the Q_q), no pack8 (kept to the plain structured problem).
-    r.quad = ctx->quad_count > 0 && ctx->nodes == 1 && !explicit_gen;
-    r.Kk = r.m4lin ? ctx->m4lin_Ke : (r.quad ? ctx->K + ctx->quad_count : ctx->K);
-    r.nodes = r.m4lin ? 1 : ctx->nodes;
+    // Both effective-control routes: one control row per step read through interp_id (nodes 1), the
+    // unit adjoint with the scalar applied by the chain kernel, no step table (it interpolates the K
+    // real controls at the knots and bounds with ||G_k||_1 alone, blind to the augmented operators),
+    // no pack8 (kept to the plain structured problem).
+    r.eff = ctx->effctl_kind(true);
+    r.Kk = EffCtlChunk::channels(ctx, r.eff);
+    r.nodes = r.eff == EffectiveControls::M4_LINEAR ? 1 : ctx->nodes;
     // 8..32 states of a seed as the columns of MFMA GEMMs, with P^-1 in place of the LU factors
     r.dense = qocx::sweepd_supports(nb, S) && ctx->knob("sweep_dense", 1) != 0;
     // a sub-step is two matrix-vector products with P^-1 from inv_kernel instead of two triangular
@@ -279,7 +305,7 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     r.inverse_sweep = (r.latency || (nb == 1 && ctx->knob("sweep_inverse_small", 1))) && !r.dense &&
                       qocx::sweepi_supports(nb, S) && ctx->knob("sweep_inverse", 1) != 0;
     r.unit = ctx->unit_ok && want_grad && ctx->inj_count == 0 && !explicit_gen && !r.dense &&
-             (ctx->nodes == 1 || r.m4lin) && ctx->knob("unit_adjoint", 1);
+             (ctx->nodes == 1 || r.eff == EffectiveControls::M4_LINEAR) && ctx->knob("unit_adjoint", 1);
     // "sweep_impl": 1 (default) column-chain sweep, 3 blocked sweep. Measured
     // (profiles/r02_sweep_ab.jsonl): the blocked sweep takes 2.1 us per step against 3.2 us when it
     // has the chip to itself, but inside the segmented pipeline at 256 seeds it loses (14.3 against
@@ -296,7 +322,7 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // every step and decides its Pade order and squaring count from the bound dt (||H0||_1 + sum |u_k|
     // ||G_k||_1); K1a and K3 then read both instead of interpolating and (K1a) reducing a norm behind
     // a barrier.
-    r.step_table = nb == 2 && !r.one_wave_k1a && !explicit_gen && r.nodes == 1 && !r.m4lin && !r.quad && !r.dense &&
+    r.step_table = nb == 2 && !r.one_wave_k1a && !explicit_gen && r.nodes == 1 && !r.eff && !r.dense &&
                    ctx->K > 0 && ctx->g_norm_dev.p != nullptr;
     // every Pade denominator of the evaluation diagonally dominant by the margin of qocx_lu5.h
     // (eps_m(theta) <= 0.40 for every order m at the host's bound theta of the step norm)
@@ -304,7 +330,7 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // n <= 8: two consecutive steps of a seed as the diagonal blocks of one 16 x 16 tile through K1a
     // and K1b (pade_pq8_kernel, inv16_dpp_kernel<1, true>); the sweeps and K3 see the usual images
     r.pack8 = nb == 1 && ctx->n <= 8 && r.inverse_sweep && !r.dense && r.all_dominant && !explicit_gen &&
-              r.nodes == 1 && !r.m4lin && !r.quad && ctx->knob("pack8", 1) != 0;
+              r.nodes == 1 && !r.eff && ctx->knob("pack8", 1) != 0;
     // One control set at a time, inverse-image sweep: K1b's sibling umul_kernel leaves the propagator
     // itself in the Q image; the sweeps apply ONE matrix per sub-step, the adjoint sweep hands lambda'
     // to K3, which forms x = P^-H lambda' from the P^-1 image (knob "sweep_umode").
@@ -337,8 +363,7 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
         ctx->xs.ensure(want_grad ? (size_t)chunk * ctx->slot_cap * S * np : 1) ||
         ctx->offs.ensure((size_t)chunk * (nsteps + 1)) ||
         ctx->gstep.ensure(cm * r.nodes * std::max(r.Kk, 1) * (r.unit ? 2 : 1)) || ctx->cost_out.ensure(B) ||
-        (r.m4lin && (ctx->veff.ensure(cm * r.Kk) || ctx->gnode.ensure(want_grad ? cm * 2 * K : 1))) ||
-        (r.quad && (ctx->veff.ensure(cm * r.Kk) || ctx->gnode.ensure(want_grad ? cm * K : 1))) ||
+        EffCtlChunk::reserve(ctx, r.eff, cm, want_grad) ||
         (r.unit && ctx->offs_x.ensure((size_t)chunk * (nsteps + 1))) ||
         ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) ||
         ctx->final_out.ensure((size_t)B * S * np) ||
@@ -395,8 +420,7 @@ struct ResidentChunk {
     int dbg_skip;  // "dbg_skip" (timing experiments only, results are garbage): bit 0 no forward
                    // sweep, bit 1 no adjoint sweep, bit 2 no K3, bit 3 K1a stores no Q
     qocx::FactorArgs fa;
-    qocx::M4LinArgs m4;
-    qocx::QuadArgs qa;
+    EffCtlChunk eff;
     qocx::LuArgs la;
     qocx::MagnusArgs ma;
     qocx::SweepArgs sa;
@@ -421,41 +445,25 @@ struct ResidentChunk {
         dbg_skip = (int)ctx->knob("dbg_skip", 0);
     }
 
+    // the chunk's scalars of the unit adjoint
+    double2* lam_scale() const { return r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr; }
+
     int init() {
         if (int rc = init_factor()) return rc;
         return init_sweep();
     }
 
-    // FactorArgs, M4LinArgs, LuArgs; launches the M4 control kernel and the step table
+    // FactorArgs, LuArgs; launches the effective-controls kernel and the step table
     int init_factor() {
         const int K = ctx->K, nsteps = ctx->nsteps;
         const bool explicit_gen = ctx->explicit_mode;
         fa.controls = ctx->controls.p ? ctx->controls.p + (size_t)b0 * ctx->nc * K : nullptr;
         fa.interp = ctx->interp.p;
-        fa.h0_cimg = ctx->h0_cimg.p;
-        fa.g_cimg = ctx->g_cimg.p;
+        fa.h0_cimg = ctx->h0.c.p;
+        fa.g_cimg = ctx->g.c.p;
         fa.K = K; fa.nc = ctx->nc; fa.nsteps = nsteps; fa.nt = ctx->nt; fa.dt = ctx->dt;
-        if (r.m4lin) {
-            m4.controls = fa.controls; m4.interp = ctx->interp.p;
-            m4.K = K; m4.Ke = r.Kk; m4.nc = ctx->nc; m4.nsteps = nsteps; m4.S = ctx->S;
-            m4.f0dt = (std::sqrt(3.0) / 12) * ctx->dt;
-            m4.veff = ctx->veff.p; m4.gstep = ctx->gstep.p; m4.gnode = ctx->gnode.p;
-            m4.lam_scale = r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr;
-            m4.total = (size_t)bc * nsteps;
-            time_begin(ctx, 0, cs);
-            qocx::launch_m4lin_controls(m4, cs);
-            time_end(ctx, cs);
-            fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_cimg = ctx->ge_cimg.p;
-            fa.K = r.Kk; fa.nc = nsteps;
-        }
-        if (r.quad) {
-            qa = quad_args(ctx, fa.controls, r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr, b0, bc);
-            time_begin(ctx, 0, cs);
-            qocx::launch_quad_controls(qa, cs);
-            time_end(ctx, cs);
-            fa.controls = ctx->veff.p; fa.interp = ctx->interp_id.p; fa.g_cimg = ctx->ge_cimg.p;
-            fa.K = r.Kk; fa.nc = nsteps;
-        }
+        eff.begin(ctx, r.eff, fa.controls, lam_scale(), b0, bc, cs, true);
+        eff.redirect(fa, fa.g_cimg, ctx->eff.images.c);
         fa.hermitian = explicit_gen ? ctx->explicit_hermitian : ctx->hermitian;
         fa.n = ctx->n;
         fa.skip_q = (dbg_skip & 8) ? 1 : 0;
@@ -534,7 +542,7 @@ struct ResidentChunk {
         const size_t mat = (size_t)np * np;
         const bool explicit_gen = ctx->explicit_mode;
         ma.controls = fa.controls; ma.interp = ctx->interp.p;
-        ma.h0_cimg = ctx->h0_cimg.p; ma.g_cimg = ctx->g_cimg.p;
+        ma.h0_cimg = ctx->h0.c.p; ma.g_cimg = ctx->g.c.p;
         ma.K = ctx->K; ma.nc = ctx->nc; ma.nsteps = nsteps; ma.nt = ctx->nt; ma.nodes = r.nodes;
         ma.dt = ctx->dt; ma.scratch = ctx->magnus_scratch.p; ma.n = ctx->n;
         ma.skew = ctx->hermitian;
@@ -568,7 +576,7 @@ struct ResidentChunk {
             sa.stamps = ctx->stamps.p + (size_t)b0 * 32;
         }
         sa.unit_adjoint = r.unit ? 1 : 0;
-        sa.lam_scale = r.unit ? ctx->lam_scale.p + (size_t)b0 * S : nullptr;
+        sa.lam_scale = lam_scale();
         sa.offs_x = r.unit ? ctx->offs_x.p : nullptr;
         sa.inj_count = ctx->inj_count;
         sa.inj_index = ctx->inj_count > 0 ? ctx->inj_index.p : nullptr;
@@ -576,9 +584,9 @@ struct ResidentChunk {
                           ? ctx->inj_bars.p + (size_t)b0 * ctx->inj_count * S * np : nullptr;
         ka.controls = fa.controls;
         ka.interp = fa.interp;
-        ka.h0_rimg = ctx->h0_rimg.p; ka.h0_timg = ctx->h0_timg.p;
-        ka.g_rimg = (r.m4lin || r.quad) ? ctx->ge_rimg.p : ctx->g_rimg.p;
-        ka.g_timg = (r.m4lin || r.quad) ? ctx->ge_timg.p : ctx->g_timg.p;
+        ka.h0_rimg = ctx->h0.r.p; ka.h0_timg = ctx->h0.t.p;
+        ka.g_rimg = ctx->g.r.p; ka.g_timg = ctx->g.t.p;
+        eff.redirect(ka);
         ka.K = fa.K; ka.nc = fa.nc; ka.nsteps = nsteps; ka.nt = ctx->nt; ka.S = S;
         ka.umode = r.umode ? 1 : 0;
         ka.pinv_img = fa.lu_img;
@@ -793,31 +801,6 @@ int run_two_sided(ResidentChunk& c) {
     return 0;
 }
 
-// per-step control cotangents -> the chunk's control gradients
-void scatter_gradients(ResidentChunk& c) {
-    qocx_ctx* ctx = c.ctx;
-    qocx::ScatterArgs sc;
-    sc.gstep = c.ka.gstep; sc.row_ptr = ctx->row_ptr.p; sc.col_step = ctx->col_step.p;
-    sc.weight = ctx->weight.p;
-    sc.grads = ctx->grads.p + (size_t)c.b0 * ctx->nc * ctx->K;
-    sc.B = c.bc; sc.nc = ctx->nc; sc.K = ctx->K; sc.nsteps = ctx->nsteps * ctx->nodes;
-    sc.lam_scale = c.r.unit ? ctx->lam_scale.p + (size_t)c.b0 * ctx->S : nullptr;
-    sc.S = ctx->S;
-    time_begin(ctx, 3, c.cs);
-    if (c.r.m4lin) {  // effective-control cotangents -> node cotangents (applies the scalar)
-        qocx::launch_m4lin_chain(c.m4, c.cs);
-        sc.gstep = ctx->gnode.p;
-        sc.lam_scale = nullptr;
-    }
-    if (c.r.quad) {  // effective-control cotangents -> real-control cotangents (applies the scalar)
-        qocx::launch_quad_chain(c.qa, c.cs);
-        sc.gstep = ctx->gnode.p;
-        sc.lam_scale = nullptr;
-    }
-    qocx::launch_scatter(sc, c.cs);
-    time_end(ctx, c.cs);
-}
-
 }  // namespace
 
 namespace qocx::host {
@@ -844,7 +827,7 @@ int eval_items(qocx_ctx* ctx, int32_t want_grad) {
         ctx->last_chunk = c.bc;
         if (int rc = c.init()) return rc;
         if (int rc = c.two_sided ? run_two_sided(c) : run_one_sided(c)) return rc;
-        if (want_grad) scatter_gradients(c);
+        if (want_grad) scatter_gradients(ctx, c.eff, c.ka.gstep, c.lam_scale(), b0, c.bc, c.cs);
     }
     return finish_items(ctx, want_grad);
 }

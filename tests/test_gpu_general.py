@@ -339,11 +339,14 @@ def test_general_path_many_states(engine, n, S, N):
 
 
 @pytest.mark.parametrize("policy, n, K, time_dep", [("M6", 70, 2, True), ("M4", 80, 2, True), ("M4", 66, 9, False),
-                                                    ("M6", 40, 1, False)])
+                                                    ("M6", 40, 1, False), ("M4", 66, 2, False),
+                                                    ("M4", 40, 2, False)])
 def test_general_path_magnus_policies(engine, policy, n, K, time_dep):
     """M4 / M6 on the general path (magnus_kernel: node generators, commutators as products on the matrix cores,
     the reverse rules of mathmethods.py:96-164): time-dependent systems, M4 with more controls than its linear form
     takes (8), and - n = 40 with 20 states - a size the wavefront kernels hand over because of the state count.
+    The two time-independent M4 rows with K = 2 take the general path's effective-control (M4-linear) branch
+    instead of magnus_kernel: by size (n = 66) and by state count (n = 40).
     Against the oracle at the 1e-10 / 1e-8 gates."""
     from qoc_amd.engine import COST_TARGET_COHERENT, COST_TARGET_INCOHERENT
     from tests.fuzz_parity import NODES
