@@ -316,6 +316,42 @@ int qocx_lindblad_last_subintervals(qocx_ctx* ctx, int64_t* total);
 int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, const int32_t* steps,
                                 const double* bars);
 
+/*
+ * Hamiltonian ensembles on the Lindblad path (robust GRAPE under decoherence): the twin of
+ * qocx_set_ensemble with its argument rules. Call after qocx_set_lindblad_problem, whose LAST `fixed`
+ * = J control channels are the perturbation matrices D_j; K_r = control_count - J channels remain for
+ * the seeds, and control_count = K_r + J <= QOCX_LINDBLAD_MAX_K as for any Lindblad problem. Member m
+ * of seed b is the Lindblad problem with the Hamiltonian H(s_m . u_b, t) + sum_i delta_mi D_i; the
+ * lindblad_data, initial densities and costs are the problem's. It is, bit for bit, the plain
+ * (K_r + J)-channel problem on the expanded controls
+ *     r[j][k] = s_mk u_b[j][k] (k < K_r),   r[j][K_r + i] = delta_mi (every knot).
+ *   scales  [M][K_r] (NULL: all 1)   offsets [M][J] (NULL exactly when J = 0)   weights [M] >= 0
+ * QOCX_ERR_ARG unless 1 <= M <= 1024, 0 <= J < control_count and every input is finite. A new
+ * Lindblad problem clears the ensemble; setting one clears the resident controls, the results and
+ * the costs of the controls (qocx_set_control_costs comes after it, for K_r channels).
+ * With an ensemble set:
+ *   qocx_eval_lindblad, qocx_lindblad_upload_controls, qocx_lindblad_download_results,
+ *     qocx_lindblad_download_costs and qocx_lindblad_opt_* take and return the seeds: controls and
+ *     gradients [B][Nc][K_r], costs [B] (qocx_lindblad_opt_clip: max_norms [K_r]). Final densities are
+ *     those of the items, [B][M][S][n][n]; qocx_download_step_densities returns [B][M][N][S][n][n].
+ *   An evaluation expands the seeds into the B x M items (item b * M + m) on the device. EVERY ITEM
+ *     picks its own sub-division count, from the maxima |s_mk| max|u_bk| (k < K_r) and |delta_mj| -
+ *     those of the expanded array -, so the items of one seed may run in different groups and no
+ *     result depends on the batch neighbours. The items are evaluated as any batch, go back to item
+ *     order and are reduced in member order:
+ *       cost_b = sum_m w_m c_bm, grad_b[j][k] = sum_m w_m s_mk dc_bm / dr[j][k] (k < K_r).
+ *   Costs of the controls act once per seed on the seeds' controls, after the reduction.
+ *   qocx_set_density_cotangents (count > 0) is QOCX_ERR_STATE, and so is this call while cotangents
+ *     are set.
+ * qocx_lindblad_ensemble_download_members: the unweighted cost of every item of the last evaluation
+ * (qocx_eval_lindblad or qocx_eval_lindblad_resident), [B][M]; QOCX_ERR_STATE without an ensemble.
+ * Not built: per-member dissipation rates (an uncertain T1), per-member targets, gradients with
+ * respect to delta.
+ */
+int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
+                               const double* offsets, const double* weights);
+int qocx_lindblad_ensemble_download_members(qocx_ctx* ctx, double* cost_out);
+
 /* Per-kernel timing, measured with HIP events on the launch streams.
  * enable: 0 off, 1 every launch, 2 + k the launches of kernel k only (two events per timed launch
  * cost the evaluation 2-3 % when all ~45 launches of it carry them; bench.py times its roofline

@@ -59,6 +59,16 @@ def controls_stay_resident(backend, descriptors, complex_controls, begin_complex
     return (all(d is not None for d in descriptors) and hasattr(backend, "set_control_costs"))
 
 
+def reject_costless_lindblad_ensemble(hamiltonian, costs):
+    """An ensemble on the Lindblad path needs at least one cost: its error is the weighted sum of
+    the members' costs and member_errors is what it returns - with no cost there is nothing to
+    weigh."""
+    if isinstance(hamiltonian, HamiltonianEnsemble) and len(list(costs)) == 0:
+        raise NotImplementedError(
+            "a HamiltonianEnsemble on the Lindblad path needs at least one cost: its error is the "
+            "weighted sum of the members' costs (costs is empty)")
+
+
 def user_states_bar(cost, controls, states, step):
     """
     d cost / d Re(states) + i d cost / d Im(states) of a user Cost: its states_bar() hook when it
@@ -129,6 +139,55 @@ class _Evaluator(object):
     linearized_route = ""     # names the linearised route in an error message
     linearized_hamiltonian = None
     _cost_controls = None     # controls the costs see in place of the evaluated ones
+    ensemble = None           # the HamiltonianEnsemble being evaluated
+    ensemble_setter = "set_ensemble"                 # the backend's entry points for one
+    ensemble_member_costs = "ensemble_member_costs"
+
+    # -- Hamiltonian ensembles ------------------------------------------------------------------
+    def _ensemble_base(self, ensemble, control_count, complex_controls, backend,
+                       quadratic_ok=False):
+        """Checks an ensemble against this problem and the backend, keeps it with the arguments
+        of the backend's setter (self._ensemble_args) and returns its base Hamiltonian.
+        quadratic_ok: this path takes a QuadraticHamiltonian base on this backend."""
+        base = ensemble.hamiltonian
+        if control_count == 0:
+            raise NotImplementedError("a HamiltonianEnsemble needs at least one control "
+                                      "(control_count = 0)")
+        if isinstance(base, HamiltonianEnsemble) or (isinstance(base, QuadraticHamiltonian)
+                                                     and not quadratic_ok):
+            raise NotImplementedError(self._ensemble_base_message.format(base))
+        if not hasattr(backend, self.ensemble_setter):
+            raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian ensembles "
+                                      "(no {})".format(backend, self.ensemble_setter))
+        if ensemble.hilbert_size is not None and ensemble.hilbert_size != self.hilbert_size:
+            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
+                ensemble.hilbert_size, self.hilbert_size))
+        scales = ensemble.real_channel_scales(control_count, complex_controls)
+        self.ensemble = ensemble
+        self._ensemble_scales = scales
+        self._ensemble_args = (scales if ensemble.control_scales is not None else None,
+                               ensemble.offsets, ensemble.weights)
+        return base
+
+    def _reject_opaque_ensemble_costs(self):
+        if self.opaque_costs:
+            raise NotImplementedError(
+                "a HamiltonianEnsemble takes costs evaluated on the device (with a "
+                "device_descriptor()) and costs of the controls alone; {} is neither"
+                "".format(self.opaque_costs[0]))
+
+    def _append_perturbations(self, g):
+        """G (nt, K_r, n, n) -> [G_1 .. G_K_r, D_1 .. D_J] in every one of the nt tables."""
+        d = self.ensemble.perturbations
+        if d is None:
+            return g
+        g = np.asarray(g, dtype=np.complex128)
+        return np.concatenate([g, np.broadcast_to(d[None], (g.shape[0],) + d.shape)], axis=1)
+
+    def member_errors(self):
+        """The unweighted device cost of every member of every seed of the last evaluation,
+        (B, M)."""
+        return getattr(self.backend, self.ensemble_member_costs)()
 
     def _triage_costs(self, item_count):
         """Splits self.costs into device_costs (they have a device_descriptor(); returns those
@@ -433,11 +492,7 @@ class SchroedingerEvaluator(_Evaluator):
                 g = None
         descriptors = self._triage_costs(self.state_count)
         if self.ensemble is not None:
-            if self.opaque_costs:
-                raise NotImplementedError(
-                    "a HamiltonianEnsemble takes costs evaluated on the device (with a "
-                    "device_descriptor()) and costs of the controls alone; {} is neither"
-                    "".format(self.opaque_costs[0]))
+            self._reject_opaque_ensemble_costs()
             g = self._append_perturbations(g)
         self.backend = backend if backend is not None else make_backend()
         if hasattr(self.backend, "set_knob"):
@@ -471,50 +526,23 @@ class SchroedingerEvaluator(_Evaluator):
                 self.backend.set_ensemble_quadratic_scales(self.ensemble.quadratic_scales)
 
     # -- Hamiltonian ensembles ------------------------------------------------------------------
+    _ensemble_base_message = (
+        "a HamiltonianEnsemble needs a base hamiltonian linear in the controls (or a "
+        "QuadraticHamiltonian under MagnusPolicy.M2 on a backend that takes quadratic "
+        "terms and their member scales), got {!r}")
+
     def _ensemble_base(self, ensemble, control_count, complex_controls, backend, magnus_policy):
-        """Checks an ensemble against this problem and the backend; returns its base Hamiltonian
-        (probed like any linear one, or taken apart like any QuadraticHamiltonian)."""
-        base = ensemble.hamiltonian
-        if control_count == 0:
-            raise NotImplementedError("a HamiltonianEnsemble needs at least one control "
-                                      "(control_count = 0)")
-        # a quadratic base: under M2, on a backend that takes quadratic terms and ensembles (and
-        # the members' term scales, where the ensemble has them)
+        """_Evaluator._ensemble_base; a quadratic base goes under M2, on a backend that takes
+        quadratic terms and ensembles (and the members' term scales, where the ensemble has
+        them)."""
         quadratic_ok = (
-            isinstance(base, QuadraticHamiltonian) and magnus_policy == MagnusPolicy.M2
+            isinstance(ensemble.hamiltonian, QuadraticHamiltonian)
+            and magnus_policy == MagnusPolicy.M2
             and hasattr(backend, "set_quadratic_terms") and hasattr(backend, "set_ensemble")
             and (ensemble.quadratic_scales is None
                  or hasattr(backend, "set_ensemble_quadratic_scales")))
-        if isinstance(base, HamiltonianEnsemble) or (isinstance(base, QuadraticHamiltonian)
-                                                     and not quadratic_ok):
-            raise NotImplementedError(
-                "a HamiltonianEnsemble needs a base hamiltonian linear in the controls (or a "
-                "QuadraticHamiltonian under MagnusPolicy.M2 on a backend that takes quadratic "
-                "terms and their member scales), got {!r}".format(base))
-        if not hasattr(backend, "set_ensemble"):
-            raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian ensembles "
-                                      "(no set_ensemble)".format(backend))
-        if ensemble.hilbert_size is not None and ensemble.hilbert_size != self.hilbert_size:
-            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
-                ensemble.hilbert_size, self.hilbert_size))
-        scales = ensemble.real_channel_scales(control_count, complex_controls)
-        self.ensemble = ensemble
-        self._ensemble_args = (scales if ensemble.control_scales is not None else None,
-                               ensemble.offsets, ensemble.weights)
-        return base
-
-    def _append_perturbations(self, g):
-        """G (nt, K_r, n, n) -> [G_1 .. G_K_r, D_1 .. D_J] in every one of the nt tables."""
-        d = self.ensemble.perturbations
-        if d is None:
-            return g
-        g = np.asarray(g, dtype=np.complex128)
-        return np.concatenate([g, np.broadcast_to(d[None], (g.shape[0],) + d.shape)], axis=1)
-
-    def member_errors(self):
-        """The unweighted device cost of every member of every seed of the last evaluation,
-        (B, M)."""
-        return self.backend.ensemble_member_costs()
+        return _Evaluator._ensemble_base(self, ensemble, control_count, complex_controls, backend,
+                                         quadratic_ok)
 
     # -- device round trip: structured controls, or generators sampled from an opaque callable ----
     def _upload(self, controls_batch, device_controls):
@@ -577,6 +605,13 @@ class LindbladEvaluator(_Evaluator):
     subtotal_costs = False
     _frozen_slices = None     # (callable, controls) of piecewise-constant frozen controls
     linearized_route = "on the Lindblad GRAPE path"
+    MAX_CHANNELS = 8          # QOCX_LINDBLAD_MAX_K: real control channels of a Lindblad problem
+    ensemble_setter = "set_lindblad_ensemble"
+    ensemble_member_costs = "lindblad_ensemble_member_costs"
+    _ensemble_base_message = (
+        "a HamiltonianEnsemble on the Lindblad path needs a base hamiltonian linear in the "
+        "controls (the tangent and frozen-controls routes evaluate one control array at a "
+        "time), got {!r}")
 
     def __init__(self, evolution_time, initial_densities, system_eval_count, hamiltonian=None,
                  lindblad_data=None, control_count=0, control_eval_count=0,
@@ -589,14 +624,25 @@ class LindbladEvaluator(_Evaluator):
         callable per RHS evaluation, lindbladdiscrete.py:479-483): the controls are folded into a
         control-free, time-dependent Hamiltonian t -> hamiltonian(u(t), t), which the engine takes
         as per-stage samples like any other time dependence. Costs still see the controls.
+
+        hamiltonian may be a HamiltonianEnsemble whose base is linear in the controls: the
+        perturbation matrices D_j go to the engine as J constant channels behind the K_r real
+        channels of the seeds (K_r + J <= 8, the Lindblad engine's channel limit), the engine
+        expands every seed into its M members (qocx_lindblad_set_ensemble), and evaluations
+        return the weighted seed errors and gradients and final densities with a member axis
+        (B x M x S x n x n). An ensemble on this path needs at least one cost: the error IS the
+        weighted sum of the members' costs. lindblad_data, densities and costs are the same
+        for all members.
         """
         if not isinstance(interpolation_policy, InterpolationPolicy):
             raise NotImplementedError("This operation does not yet support the interpolation "
                                       "policy {}.".format(interpolation_policy))
         self.interpolation_policy = interpolation_policy
-        if isinstance(hamiltonian, HamiltonianEnsemble):
-            raise NotImplementedError("Hamiltonian ensembles are evaluated on the Schroedinger path "
-                                      "only, not on the Lindblad path")
+        ensemble = hamiltonian if isinstance(hamiltonian, HamiltonianEnsemble) else None
+        if ensemble is not None:
+            reject_costless_lindblad_ensemble(ensemble, costs)
+            if frozen_controls is not None:
+                raise NotImplementedError(self._ensemble_base_message.format(ensemble.hamiltonian))
         if frozen_controls is not None:
             if need_gradients:
                 raise structure.NonLinearHamiltonianError(
@@ -634,6 +680,16 @@ class LindbladEvaluator(_Evaluator):
         self.costs = list(costs)
         self.backend = backend if backend is not None else make_backend()
         self.kr = control_count * (2 if complex_controls else 1)
+        self.device_k = self.kr   # the problem's channels: with an ensemble K_r + J
+        if ensemble is not None:
+            hamiltonian = self._ensemble_base(ensemble, control_count, complex_controls,
+                                              self.backend)
+            self.device_k = self.kr + ensemble.perturbation_count
+            if self.device_k > self.MAX_CHANNELS:
+                raise NotImplementedError(
+                    "the Lindblad engine takes up to {} real control channels: this ensemble "
+                    "needs K_r + J = {} + {}".format(self.MAX_CHANNELS, self.kr,
+                                                     ensemble.perturbation_count))
         # time dependence is decided on the integrator's own grid: every stage time of the
         # coarsest sub-division (12 per sub-interval), never on a handful of equispaced probes
         # (piecewise constant: the edges of Nc slices are the cut points of Nc + 1 linear knots)
@@ -654,6 +710,8 @@ class LindbladEvaluator(_Evaluator):
         try:
             h0, g, dissipators, operators, self.time_dependent, data_dependent = probe(hamiltonian)
         except structure.NonLinearHamiltonianError:
+            if self.ensemble is not None:
+                raise NotImplementedError(self._ensemble_base_message.format(hamiltonian))
             if frozen_controls is not None or control_count == 0:
                 raise
             self.linearized_hamiltonian = hamiltonian
@@ -664,9 +722,12 @@ class LindbladEvaluator(_Evaluator):
         self._lindblad_data = lindblad_data if data_dependent else None
         self.cotangent_shape = (self.density_count, self.hilbert_size, self.hilbert_size)
         descriptors = self._triage_costs(self.density_count)
-        self._problem_args = (self.hilbert_size, self.density_count, self.kr, control_eval_count,
-                              system_eval_count, evolution_time, h0, g, dissipators, operators,
-                              initial_densities)
+        if self.ensemble is not None:
+            self._reject_opaque_ensemble_costs()
+            g = self._append_perturbations(np.asarray(g)[None])[0]
+        self._problem_args = (self.hilbert_size, self.density_count, self.device_k,
+                              control_eval_count, system_eval_count, evolution_time, h0, g,
+                              dissipators, operators, initial_densities)
         self._problem_kw = dict(costs=descriptors, cost_eval_step=cost_eval_step,
                                 **interpolation_keywords(self.backend, "set_lindblad_problem",
                                                          interpolation_policy))
@@ -677,11 +738,28 @@ class LindbladEvaluator(_Evaluator):
         if self.linearized_hamiltonian is not None:
             pass  # the tables depend on the controls: set per evaluation (_set_linearized_problem)
         elif not self.time_dependent:
-            self.backend.set_lindblad_problem(*self._problem_args, **self._problem_kw)
+            self._set_problem()
         elif control_bounds is not None:  # GRAPE: max_control_norms bound the controls for good
             bounds = np.repeat(np.asarray(control_bounds, dtype=np.float64),
                                2 if complex_controls else 1)
             self._set_time_dependent_problem(bounds)
+
+    def _set_problem(self, **tables):
+        """The problem (with its stage tables, if any) to the backend, then the ensemble: a new
+        problem clears it."""
+        self.backend.set_lindblad_problem(*self._problem_args, **tables, **self._problem_kw)
+        if self.ensemble is not None:
+            self.backend.set_lindblad_ensemble(*self._ensemble_args)
+
+    def _item_bounds(self, bounds):
+        """Bounds of the seeds' K_r channels -> bounds of the evaluated channels: with an ensemble
+        those of the items, bound_k max_m |s_mk| and max_m |delta_mj| for the J fixed channels."""
+        if self.ensemble is None:
+            return bounds
+        scaled = np.asarray(bounds, dtype=np.float64) * np.max(np.abs(self._ensemble_scales), axis=0)
+        if self.ensemble.offsets is None:
+            return scaled
+        return np.concatenate([scaled, np.max(np.abs(self.ensemble.offsets), axis=0)])
 
     def _set_stage_tables(self, coarse_samples, bounds, sample):
         """The tail of both table builders. coarse_samples :: (h0, g) on the coarsest stage grid:
@@ -709,21 +787,28 @@ class LindbladEvaluator(_Evaluator):
         if self._lindblad_data is not None:
             diss_stages, op_stages = structure.sample_lindblad_data(self._lindblad_data, n, times)
             extra = dict(diss_stages=diss_stages, op_stages=op_stages)
-        self.backend.set_lindblad_problem(*self._problem_args, fixed_subdivision=ksub,
-                                          h0_stages=h0_stages, g_stages=g_stages, **extra,
-                                          **self._problem_kw)
+        self._set_problem(fixed_subdivision=ksub, h0_stages=h0_stages, g_stages=g_stages, **extra)
 
     def _set_time_dependent_problem(self, bounds):
         """Sample the time-dependent Hamiltonian at the stage times of a sub-division fine
         enough for controls up to `bounds` and hand the samples to the engine."""
         n, kr, h0 = self._problem_args[0], self.kr, self._problem_args[6]
+
+        def with_perturbations(tables):
+            """(h0, g) samples of the base -> those of the problem: with an ensemble the D_j are
+            repeated in every table of g (none where g is constant: the problem's own g has
+            them)."""
+            h, g = tables
+            if self.ensemble is None or g is None:
+                return h, g
+            return h, self._append_perturbations(g)
         if self._coarse_samples is None and self._hamiltonian is None:
             self._coarse_samples = (np.asarray(h0, dtype=np.complex128)[None],
                                     np.zeros((1, kr, n, n), dtype=np.complex128))
         if self._coarse_samples is None:  # H on the coarsest stage grid: norms for the bound
-            self._coarse_samples = structure.probe_hamiltonian(
+            self._coarse_samples = with_perturbations(structure.probe_hamiltonian(
                 self._hamiltonian, n, self.control_count, self.complex_controls,
-                list(self._coarse_times))
+                list(self._coarse_times)))
 
         def sample(times):
             if self._frozen_slices is not None:
@@ -737,9 +822,9 @@ class LindbladEvaluator(_Evaluator):
                                  for q, t in enumerate(times)]), None
             if self._hamiltonian is None:
                 return np.repeat(np.asarray(h0, dtype=np.complex128)[None], len(times), axis=0), None
-            return structure.sample_lindblad_hamiltonian(
-                self._hamiltonian, n, self.control_count, self.complex_controls, times)
-        self._set_stage_tables(self._coarse_samples, bounds, sample)
+            return with_perturbations(structure.sample_lindblad_hamiltonian(
+                self._hamiltonian, n, self.control_count, self.complex_controls, times))
+        self._set_stage_tables(self._coarse_samples, self._item_bounds(bounds), sample)
         self._table_bounds = np.asarray(bounds, dtype=np.float64)
 
     def _set_linearized_problem(self, controls, device_controls):
@@ -781,7 +866,8 @@ class LindbladEvaluator(_Evaluator):
                 and (not self.time_dependent or self._table_bounds is not None))
 
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_densities=False):
-        """_Evaluator.evaluate_batch; the step states are densities [B x N x S x n x n]."""
+        """_Evaluator.evaluate_batch; the step states are densities [B x N x S x n x n] (with an
+        ensemble a member axis M follows B, in the final densities too)."""
         return _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_densities)
 
     def evaluate(self, controls, want_grad=True, want_step_densities=False):

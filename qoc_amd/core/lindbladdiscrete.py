@@ -16,7 +16,7 @@ from qoc_amd.core import batch
 from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
                                  initialize_coefficients, initialize_controls,
                                  reject_basis_save, strip_controls)
-from qoc_amd.core.device import LindbladEvaluator
+from qoc_amd.core.device import LindbladEvaluator, reject_costless_lindblad_ensemble
 from qoc_amd.core.structure import NonLinearHamiltonianError
 from qoc_amd.engine import PATH_LINDBLAD
 from qoc_amd.models import (Dummy, EvolveLindbladDiscreteState, EvolveLindbladResult,
@@ -26,11 +26,28 @@ from qoc_amd.standard.hamiltonians import HamiltonianEnsemble
 from qoc_amd.standard.optimizers import Adam
 
 
-def _reject_ensemble(hamiltonian):
-    """Before any save file is touched: ensembles run on the Schroedinger path only."""
-    if isinstance(hamiltonian, HamiltonianEnsemble):
-        raise NotImplementedError("Hamiltonian ensembles are evaluated on the Schroedinger path "
-                                  "only, not on the Lindblad path")
+def _check_ensemble(hamiltonian, costs, save_file_path=None):
+    """Before any save file is touched and before a backend is made: a HamiltonianEnsemble on the
+    Lindblad path needs at least one cost (its error is the weighted sum of the members' costs)
+    and writes no save file."""
+    if not isinstance(hamiltonian, HamiltonianEnsemble):
+        return
+    reject_costless_lindblad_ensemble(hamiltonian, costs)
+    if save_file_path is not None:
+        raise NotImplementedError("save files are not written for a HamiltonianEnsemble on the "
+                                  "Lindblad path (save_file_path must be None)")
+
+
+def _ensemble_member_errors(evaluator, result):
+    """result.member_errors[b]: the members' unweighted costs at seed b's best controls, from one
+    forward evaluation of every seed that has best controls."""
+    seeds = [b for b in range(len(result.best_controls)) if result.best_controls[b] is not None]
+    if not seeds:
+        return
+    evaluator.evaluate_batch(np.stack([result.best_controls[b] for b in seeds]), want_grad=False)
+    members = evaluator.member_errors()
+    for i, b in enumerate(seeds):
+        result.member_errors[b] = members[i]
 
 
 def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_count,
@@ -42,9 +59,15 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
     error. Arguments as in the reference (lindbladdiscrete.py:31-91):
     initial_densities :: (density_count x n x n); hamiltonian :: (controls, time) -> (n x n);
     lindblad_data :: (time) -> (dissipators (L), operators (L x n x n)).
-    Returns EvolveLindbladResult{error, final_densities}.
+    Returns EvolveLindbladResult{error, final_densities}. With a HamiltonianEnsemble
+    (qoc_amd.standard) whose base is linear in the controls every member evolves under the same
+    lindblad_data: the error is the weighted sum over the members, final_densities gains a member
+    axis (M x density_count x n x n) and the result's member_errors holds each member's
+    unweighted device cost. Such an ensemble needs at least one cost (costs of the densities with
+    a device descriptor, and costs of the controls alone), K_r + J <= 8 real control channels and
+    perturbations, and no save file.
     """
-    _reject_ensemble(hamiltonian)
+    _check_ensemble(hamiltonian, costs, save_file_path)
     if controls is not None:
         controls = np.asarray(controls)
         control_eval_count, control_count = controls.shape[0], controls.shape[1]
@@ -74,7 +97,11 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
         want_step_densities=pstate.save_intermediate_densities_)
     if pstate.save_intermediate_densities_:
         pstate.save_all_intermediate_densities(0, step_densities)
-    return EvolveLindbladResult(error=error, final_densities=final_densities)
+    member_errors = None
+    if evaluator.ensemble is not None:
+        member_errors = evaluator.member_errors()[0]
+    return EvolveLindbladResult(error=error, final_densities=final_densities,
+                                member_errors=member_errors)
 
 
 def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_time,
@@ -93,9 +120,13 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
     initial_controls holds the coefficients (P x control_count), the expanded pulse clipped to
     max_control_norms is evaluated, the result gains best_coefficients.
     Returns GrapeLindbladResult{best_controls, best_error, best_final_densities,
-    best_iteration}.
+    best_iteration}. With a HamiltonianEnsemble (robust GRAPE under decoherence; conditions as in
+    evolve_lindblad_discrete: at least one cost, K_r + J <= 8, no save file) the error is the
+    weighted sum over its members, best_final_densities has a member axis, and member_errors
+    holds each member's unweighted device cost at best_controls (one forward evaluation after the
+    loop).
     """
-    _reject_ensemble(hamiltonian)
+    _check_ensemble(hamiltonian, costs, save_file_path)
     reject_basis_save(control_basis, save_file_path)
     coefficients = None
     if control_basis is not None:
@@ -129,6 +160,9 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
                                    if control_basis is None else coefficients)
     pstate.optimizer.run(_eld_wrap, pstate.iteration_count, flat_controls, _eldj_wrap,
                          args=(pstate, reporter, result))
+    if pstate.evaluator.ensemble is not None and result.best_controls is not None:
+        pstate.evaluator.evaluate(result.best_controls, want_grad=False)
+        result.member_errors = pstate.evaluator.member_errors()[0]
     return result
 
 
@@ -207,9 +241,14 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     grape_schroedinger_discrete_batch - initial_controls holds the coefficients
     (B x P x control_count), the result gains best_coefficients per seed
     (qocx_lindblad_opt_begin_basis on the resident route).
+    With a HamiltonianEnsemble (conditions as in evolve_lindblad_discrete: at least one cost,
+    K_r + J <= 8) every seed is evaluated over its M members on either route: the errors are the
+    weighted sums, the final densities have a member axis, and member_errors[b] holds seed b's
+    unweighted member costs at its best controls (one forward evaluation of all seeds after the
+    loop).
     Returns GrapeLindbladBatchResult.
     """
-    _reject_ensemble(hamiltonian)
+    _check_ensemble(hamiltonian, costs)
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
         max_control_norms, impose_control_conditions, comm, control_basis)
@@ -225,5 +264,9 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     run = (iteration_count, log_iteration_step, min_error, comm, result)
     if batch.resident_route(stepper, optimizer, pstate, evaluator, B):
         ops = _ResidentOps(evaluator.backend, evaluator.control_cost_descriptors, complex_controls)
-        return batch.run_batch_resident(ops, optimizer, params, pstate, *run)
-    return batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
+        out = batch.run_batch_resident(ops, optimizer, params, pstate, *run)
+    else:
+        out = batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
+    if evaluator.ensemble is not None:
+        _ensemble_member_errors(evaluator, out)
+    return out

@@ -474,6 +474,51 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.res_B = lb.ms.batch = 0;  // resident controls and optimizer states belong to the old problem
     lb.res_have_results = false;
     lb.inj_count = 0;
+    lb.ens_M = lb.ens_J = lb.ens_Kr = 0;  // ... and so does the ensemble
+    lb.ens_members_B = 0;
+    return 0;
+}
+
+int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
+                               const double* offsets, const double* weights) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set (qocx_set_lindblad_problem first)");
+    if (members < 1 || members > 1024) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
+    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
+    // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
+    if (fixed >= lb.K)
+        return fail(QOCX_ERR_ARG, "an ensemble needs fixed < control_count (at least one seed control)");
+    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed perturbation channels need offsets");
+    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 perturbation channels");
+    if (!weights) return fail(QOCX_ERR_ARG, "weights missing");
+    if (lb.inj_count > 0)
+        return fail(QOCX_ERR_STATE, "density cotangents are set (qocx_set_density_cotangents): an ensemble "
+                                    "takes none");
+    const int M = members, J = fixed, Kr = lb.K - fixed;
+    std::vector<double> sc((size_t)M * Kr, 1.0), off((size_t)M * J), w(weights, weights + M);
+    if (scales) sc.assign(scales, scales + sc.size());
+    if (J > 0) off.assign(offsets, offsets + off.size());
+    for (double v : sc)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble control scale");
+    for (double v : off)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble offset");
+    for (double v : w)
+        if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "ensemble weights must be finite and >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (lb.ens_scales.upload(sc, ctx->stream) || lb.ens_weights.upload(w, ctx->stream) ||
+        (J > 0 && lb.ens_offsets.upload(off, ctx->stream)))
+        return QOCX_ERR_HIP;
+    lb.ens_scales_h = sc;
+    lb.ens_offsets_h = off;
+    lb.ens_M = M;
+    lb.ens_J = J;
+    lb.ens_Kr = Kr;
+    lb.ens_members_B = 0;
+    lb.have_results = false;
+    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
+    lb.res_have_results = false;
+    lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
     return 0;
 }
 
@@ -617,6 +662,21 @@ void lindblad_control_maxima(const double* controls, int B, int nc, int K, doubl
             }
             umax[(size_t)b * K + k] = um;
         }
+}
+
+// The pinned staging buffer of the controls, at least `total` doubles, with nothing in flight that
+// still reads it (a pageable source of 2 MB costs the copy 10-25 ms of page pinning per call at 256
+// seeds; from pinned memory it is a DMA)
+int pinned_controls(qocx_ctx* ctx, size_t total) {
+    if (ctx->pin_controls_cap < total) {
+        if (ctx->pin_controls) (void)hipHostFree(ctx->pin_controls);
+        ctx->pin_controls = nullptr;
+        ctx->pin_controls_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&ctx->pin_controls, total * sizeof(double), hipHostMallocDefault));
+        ctx->pin_controls_cap = total;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // Each seed picks its own sub-division count from ITS controls (|| Liouvillian || * length <= 0.4
@@ -883,6 +943,125 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
     return 0;
 }
 
+// ---- Hamiltonian ensembles (qocx_lindblad_set_ensemble): the member items of `seeds` seeds ---------
+
+// The maxima lindblad_subdivisions reads, per item: |s_mk| umax_bk on the seeds' channels, |delta_mj|
+// beyond. |s u| = |s| |u| exactly and rounding is monotone, so these are the maxima of the expanded
+// array, bit for bit (a NaN of umax is carried).
+std::vector<double> lindblad_item_maxima(const qocx_ctx::Lindblad& lb, int seeds, const double* umax) {
+    const int M = lb.ens_M, Kr = lb.ens_Kr, J = lb.ens_J, K = lb.K;
+    std::vector<double> out((size_t)seeds * M * K);
+    for (int b = 0; b < seeds; ++b)
+        for (int m = 0; m < M; ++m) {
+            double* o = out.data() + ((size_t)b * M + m) * K;
+            for (int k = 0; k < Kr; ++k) o[k] = fabs(lb.ens_scales_h[(size_t)m * Kr + k]) * umax[(size_t)b * Kr + k];
+            for (int j = 0; j < J; ++j) o[Kr + j] = fabs(lb.ens_offsets_h[(size_t)m * J + j]);
+        }
+    return out;
+}
+
+qocx::EnsembleArgs lindblad_ensemble_args(qocx_ctx* ctx, int seeds, const double* seed_controls, double* cost,
+                                          double* grads) {
+    auto& lb = ctx->lb;
+    qocx::EnsembleArgs a;
+    a.seed_controls = seed_controls; a.scales = lb.ens_scales.p;
+    a.offsets = lb.ens_J > 0 ? lb.ens_offsets.p : nullptr; a.weights = lb.ens_weights.p;
+    a.controls = lb.ens_items.p;
+    a.member_cost = lb.ens_cost.p; a.member_grads = lb.ens_grads.p;
+    a.cost = cost; a.grads = grads;
+    a.B = seeds; a.M = lb.ens_M; a.nc = lb.nc; a.K = lb.K; a.Kr = lb.ens_Kr; a.J = lb.ens_J;
+    return a;
+}
+
+// The seeds' controls [seeds][nc][K_r] on the device expanded into their items, each item's own
+// sub-division count, the plan, the items gathered into group order and the launches of any batch:
+// results in lb.cost_out / grads / final_out in group order, lb.order / order_dev of the items.
+// umax: [seeds][K_r] control maxima of the seeds; NULL on a fixed grid (as lindblad_subdivisions).
+int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_controls, const double* umax,
+                             int want_grad) {
+    auto& lb = ctx->lb;
+    if ((int64_t)seeds * lb.ens_M > 0x7fffffff)
+        return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
+    const int items = seeds * lb.ens_M;
+    const size_t csz = (size_t)lb.nc * lb.K, total = (size_t)items * csz;
+    if ((total + 255) / 256 > 0x7fffffffu) return fail(QOCX_ERR_ARG, "ensemble control arrays too large");
+    if (csz > 65535u * 256u) return fail(QOCX_ERR_ARG, "control arrays too large for the driver kernels' grids");
+    if (lb.ens_items.ensure(total)) return QOCX_ERR_HIP;
+    qocx::launch_ensemble_expand(lindblad_ensemble_args(ctx, seeds, seed_controls, nullptr, nullptr), ctx->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> item_umax;
+    if (umax) item_umax = lindblad_item_maxima(lb, seeds, umax);
+    std::vector<int> ksub_of;
+    LindbladPlan plan;
+    int rc = lindblad_subdivisions(ctx, items, umax ? item_umax.data() : nullptr, ksub_of);
+    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
+    if (rc) return rc;
+    if (lb.order_dev.upload(lb.order, ctx->stream)) return QOCX_ERR_HIP;
+    qocx::launch_gather_seeds(lb.ens_items.p, lb.controls.p, csz, lb.order_dev.p, items, ctx->stream);
+    return lindblad_launch_groups(ctx, want_grad, plan);
+}
+
+// The items' results back to item order (final densities into final_items [seeds][M][S] dumps) and
+// folded in member order into the seeds' cost [seeds] and grads [seeds][nc][K_r].
+int lindblad_ensemble_reduce(qocx_ctx* ctx, int seeds, int want_grad, double* cost, double* grads,
+                             double2* final_items) {
+    auto& lb = ctx->lb;
+    const int items = seeds * lb.ens_M;
+    const size_t csz = (size_t)lb.nc * lb.K, md = dump_elems(lb.n);
+    if (lb.ens_cost.ensure(items) || (want_grad && lb.ens_grads.ensure((size_t)items * csz))) return QOCX_ERR_HIP;
+    qocx::launch_scatter_seeds(lb.cost_out.p, lb.ens_cost.p, want_grad ? lb.grads.p : nullptr, lb.ens_grads.p,
+                               csz, lb.final_out.p, final_items, (size_t)lb.S * md, lb.order_dev.p, items,
+                               ctx->stream);
+    qocx::launch_ensemble_reduce(lindblad_ensemble_args(ctx, seeds, nullptr, cost, want_grad ? grads : nullptr),
+                                 ctx->stream);
+    HIP_TRY(hipGetLastError());
+    lb.ens_members_B = seeds;
+    return 0;
+}
+
+// qocx_eval_lindblad with an ensemble set: controls, costs and gradients of the seeds, final densities
+// of the items
+int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int want_grad, double* cost_out,
+                           double* grad_out, double* final_out) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, S = lb.S, Kr = lb.ens_Kr, nc = lb.nc, M = lb.ens_M;
+    const size_t csz = (size_t)nc * Kr, md = dump_elems(n);
+    if (!controls) return fail(QOCX_ERR_ARG, "controls is NULL");
+    if ((int64_t)B * M > 0x7fffffff) return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
+    const size_t items = (size_t)B * M;
+    lb.have_results = false;
+    std::vector<double> umax((size_t)B * Kr);
+    lindblad_control_maxima(controls, B, nc, Kr, umax.data());
+    if (lb.ens_seed_controls.ensure((size_t)B * csz) || lb.ens_seed_cost.ensure(B) ||
+        (want_grad && lb.ens_seed_grads.ensure((size_t)B * csz)) || lb.ens_final.ensure(items * S * md))
+        return QOCX_ERR_HIP;
+    if (int rc2 = pinned_controls(ctx, (size_t)B * csz)) return rc2;
+    memcpy(ctx->pin_controls, controls, (size_t)B * csz * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(lb.ens_seed_controls.p, ctx->pin_controls, (size_t)B * csz * sizeof(double),
+                           hipMemcpyHostToDevice, ctx->stream));
+    int rc = lindblad_ensemble_launch(ctx, B, lb.ens_seed_controls.p, umax.data(), want_grad);
+    if (!rc) rc = lindblad_ensemble_reduce(ctx, B, want_grad, lb.ens_seed_cost.p, lb.ens_seed_grads.p, lb.ens_final.p);
+    if (rc) return rc;
+    std::vector<double2> fin(final_out ? items * S * md : 0);
+    if (cost_out)
+        HIP_TRY(hipMemcpyAsync(cost_out, lb.ens_seed_cost.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (want_grad && grad_out)
+        HIP_TRY(hipMemcpyAsync(grad_out, lb.ens_seed_grads.p, (size_t)B * csz * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    if (final_out)
+        HIP_TRY(hipMemcpyAsync(fin.data(), lb.ens_final.p, fin.size() * sizeof(double2), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    time_collect(ctx);
+    if (final_out)
+        for (size_t v = 0; v < items * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
+    lb.B = (int)items;
+    lb.have_results = true;
+    lb.have_steps = ctx->keep_step_states != 0;
+    return 0;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -896,6 +1075,7 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
     const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, B = batch;
     const size_t md = dump_elems(n);
     want_grad = (want_grad && K > 0) ? 1 : 0;
+    if (lb.ens_M > 0) return eval_lindblad_ensemble(ctx, B, controls, want_grad, cost_out, grad_out, final_out);
     if (K > 0 && !controls) return fail(QOCX_ERR_ARG, "controls is NULL");
     const bool trace_host = qocx::diag_getenv("QOCX_TRACE_HOST") != nullptr;
     auto now_ms = [] {
@@ -915,17 +1095,9 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
     if (rc) return rc;
     const size_t csz = (size_t)nc * K;
     if (K > 0) {
-        // gathered group by group into the pinned staging buffer (a pageable source of 2 MB costs
-        // the copy 10-25 ms of page pinning per call at 256 seeds; from pinned memory it is a DMA)
+        // gathered group by group into the pinned staging buffer
         const size_t total = (size_t)B * csz;
-        if (ctx->pin_controls_cap < total) {
-            if (ctx->pin_controls) (void)hipHostFree(ctx->pin_controls);
-            ctx->pin_controls = nullptr;
-            ctx->pin_controls_cap = 0;
-            HIP_TRY(hipHostMalloc((void**)&ctx->pin_controls, total * sizeof(double), hipHostMallocDefault));
-            ctx->pin_controls_cap = total;
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // nothing in flight still reads the staging buffer
+        if (int rc2 = pinned_controls(ctx, total)) return rc2;
         for (int pos = 0; pos < B; ++pos)
             memcpy(ctx->pin_controls + (size_t)pos * csz, controls + (size_t)lb.order[pos] * csz,
                    csz * sizeof(double));
@@ -978,6 +1150,8 @@ int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, con
         return 0;
     }
     if (batch < 1 || !steps || !bars) return fail(QOCX_ERR_ARG, "bad argument");
+    if (lb.ens_M > 0)
+        return fail(QOCX_ERR_STATE, "density cotangents are not taken with an ensemble (qocx_lindblad_set_ensemble)");
     std::vector<bool> seen(lb.nsteps + 1, false);
     for (int c = 0; c < count; ++c) {
         if (steps[c] < 1 || steps[c] > lb.nsteps || seen[steps[c]])
@@ -1017,16 +1191,20 @@ int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* co
     if (!lb.has_problem || lb.K < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_upload_controls needs a Lindblad problem with controls");
     if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
-    const size_t csz = (size_t)lb.nc * lb.K;
+    // (with an ensemble the caller's array holds the seeds' K_r channels)
+    const int Ks = lb.seed_channels();
+    const size_t csz = (size_t)lb.nc * Ks;
     if (csz > 65535u * 256u) return fail(QOCX_ERR_ARG, "control arrays too large for the driver kernels' grids");
+    if ((int64_t)batch * (int64_t)lb.seed_items() > 0x7fffffff)
+        return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
     HIP_TRY(hipSetDevice(ctx->device));
     if (lb.res_controls.ensure((size_t)batch * csz)) return QOCX_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(lb.res_controls.p, controls, (size_t)batch * csz * sizeof(double),
                            hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // controls is the caller's memory
     // the host has these controls: their maxima cost nothing here and spare eval_resident a round trip
-    lb.umax_host.assign((size_t)batch * lb.K, 0.0);
-    lindblad_control_maxima(controls, batch, lb.nc, lb.K, lb.umax_host.data());
+    lb.umax_host.assign((size_t)batch * Ks, 0.0);
+    lindblad_control_maxima(controls, batch, lb.nc, Ks, lb.umax_host.data());
     lb.umax_valid = true;
     lb.res_B = batch;
     lb.res_have_results = false;
@@ -1039,8 +1217,10 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
     if (!lb.has_problem || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "no resident Lindblad controls (qocx_lindblad_upload_controls)");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = lb.res_B, K = lb.K, S = lb.S;
-    const size_t csz = (size_t)lb.nc * K, md = dump_elems(lb.n);
+    // (K: the seeds' channels - with an ensemble K_r, and `items` evaluated items per seed)
+    const int B = lb.res_B, K = lb.seed_channels(), S = lb.S;
+    const size_t csz = (size_t)lb.nc * K, md = dump_elems(lb.n), items = lb.seed_items();
+    const bool ens = lb.ens_M > 0;
     want_grad = want_grad ? 1 : 0;
     lb.res_have_results = false;
     // the sub-division decision needs the control maxima on the host, except on a fixed grid
@@ -1054,23 +1234,33 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         lb.umax_valid = true;
     }
-    std::vector<int> ksub_of;
-    LindbladPlan plan;
-    int rc = lindblad_subdivisions(ctx, B, lb.fixed_ksub == 0 ? lb.umax_host.data() : nullptr, ksub_of);
-    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
-    if (rc) return rc;
+    const double* umax = lb.fixed_ksub == 0 ? lb.umax_host.data() : nullptr;
     if (lb.res_cost.ensure(B) || lb.res_grads.ensure((size_t)B * csz) ||
-        lb.res_final.ensure((size_t)B * S * md) || lb.order_dev.upload(lb.order, ctx->stream))
+        lb.res_final.ensure((size_t)B * items * S * md))
         return QOCX_ERR_HIP;
-    // seed order -> group order: the device-side form of qocx_eval_lindblad's staging copy
-    qocx::launch_gather_seeds(lb.res_controls.p, lb.controls.p, csz, lb.order_dev.p, B, ctx->stream);
-    rc = lindblad_launch_groups(ctx, want_grad, plan);
-    if (rc) return rc;
-    qocx::launch_scatter_seeds(lb.cost_out.p, lb.res_cost.p, want_grad ? lb.grads.p : nullptr,
-                               lb.res_grads.p, csz, lb.final_out.p, lb.res_final.p, (size_t)S * md,
-                               lb.order_dev.p, B, ctx->stream);
-    HIP_TRY(hipGetLastError());
-    if (lb.control_costs.count > 0) {  // the costs of the controls, on the seeds' resident controls
+    if (ens) {
+        // the member items of the seeds' current controls (expanded anew: the driver may have moved
+        // them), evaluated as any batch, then reduced in member order into the seeds' results
+        int rc = lindblad_ensemble_launch(ctx, B, lb.res_controls.p, umax, want_grad);
+        if (!rc) rc = lindblad_ensemble_reduce(ctx, B, want_grad, lb.res_cost.p, lb.res_grads.p, lb.res_final.p);
+        if (rc) return rc;
+    } else {
+        std::vector<int> ksub_of;
+        LindbladPlan plan;
+        int rc = lindblad_subdivisions(ctx, B, umax, ksub_of);
+        if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
+        if (rc) return rc;
+        if (lb.order_dev.upload(lb.order, ctx->stream)) return QOCX_ERR_HIP;
+        // seed order -> group order: the device-side form of qocx_eval_lindblad's staging copy
+        qocx::launch_gather_seeds(lb.res_controls.p, lb.controls.p, csz, lb.order_dev.p, B, ctx->stream);
+        rc = lindblad_launch_groups(ctx, want_grad, plan);
+        if (rc) return rc;
+        qocx::launch_scatter_seeds(lb.cost_out.p, lb.res_cost.p, want_grad ? lb.grads.p : nullptr,
+                                   lb.res_grads.p, csz, lb.final_out.p, lb.res_final.p, (size_t)S * md,
+                                   lb.order_dev.p, B, ctx->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (lb.control_costs.count > 0) {  // the costs of the controls, once per seed on its resident controls
         ControlCosts& cc = lb.control_costs;
         if (int rc2 = run_control_costs(ctx, cc, B, lb.nc, K, lb.res_controls.p, want_grad != 0)) return rc2;
         qocx::launch_add_control_costs(lb.res_cost.p, cc.cost.p, want_grad ? lb.res_grads.p : nullptr, cc.grad.p,
@@ -1081,7 +1271,7 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         time_collect(ctx);
     }
-    lb.B = B;
+    lb.B = B * (int)items;
     lb.have_results = true;
     lb.have_steps = ctx->keep_step_states != 0;
     lb.res_have_results = true;
@@ -1095,8 +1285,9 @@ int qocx_lindblad_download_results(qocx_ctx* ctx, double* cost_out, double* grad
     if (!lb.res_have_results) return fail(QOCX_ERR_STATE, "no resident Lindblad evaluation results");
     if (grad_out && !lb.res_have_grads) return fail(QOCX_ERR_STATE, "the last evaluation had no gradients");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = lb.res_B, S = lb.S, n = lb.n;
-    const size_t csz = (size_t)lb.nc * lb.K, md = dump_elems(n);
+    // (with an ensemble: the seeds' K_r channels, the final densities of every item)
+    const int B = lb.res_B, S = lb.S * (int)lb.seed_items(), n = lb.n;
+    const size_t csz = (size_t)lb.nc * lb.seed_channels(), md = dump_elems(n);
     if (cost_out)
         HIP_TRY(hipMemcpyAsync(cost_out, lb.res_cost.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
@@ -1116,6 +1307,18 @@ int qocx_lindblad_download_results(qocx_ctx* ctx, double* cost_out, double* grad
 int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out) {
     if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
     return qocx_lindblad_download_results(ctx, cost_out, nullptr, nullptr);
+}
+
+int qocx_lindblad_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
+    if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (lb.ens_M == 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_lindblad_set_ensemble)");
+    if (lb.ens_members_B < 1 || !lb.have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(cost_out, lb.ens_cost.p, (size_t)lb.ens_members_B * lb.ens_M * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 }  // extern "C"

@@ -123,10 +123,11 @@ SeedView schroedinger_seeds(qocx_ctx* ctx) {
                     seed_costs(ctx), ctx->final_out.p, items * ctx->S * ctx->np};
 }
 
+// (ensemble: a seed's K_r channels, and the final densities of its M items)
 SeedView lindblad_seeds(qocx_ctx* ctx) {
     auto& lb = ctx->lb;
-    return SeedView{lb.res_B, lb.K, lb.nc, lb.res_controls.p, lb.res_grads.p, lb.res_cost.p, lb.res_final.p,
-                    (size_t)lb.S * dump_elems(lb.n)};
+    return SeedView{lb.res_B, lb.seed_channels(), lb.nc, lb.res_controls.p, lb.res_grads.p, lb.res_cost.p,
+                    lb.res_final.p, lb.seed_items() * lb.S * dump_elems(lb.n)};
 }
 
 // What the optimizer works on, as distinct from what is evaluated (the SeedView): the seeds' controls
@@ -551,11 +552,12 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     auto& lb = ctx->lb;
     if (lb.ms.batch != lb.res_B || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
-    const int Kn = lb.ms.complex_controls ? lb.K / 2 : lb.K;  // (complex controls: one modulus bound per control)
+    // (with an ensemble the seeds' K_r channels: the next evaluation expands the clipped seeds anew)
+    const int B = lb.res_B, K = lb.seed_channels();
+    const int Kn = lb.ms.complex_controls ? K / 2 : K;  // (complex controls: one modulus bound per control)
     for (int k = 0; k < Kn; ++k)
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = lb.res_B, K = lb.K;
     if (int rc = multistart_clip(ctx, lb.ms, lindblad_seeds(ctx), max_norms)) return rc;
     // the maxima of the clipped controls decide the next evaluation's sub-divisions: they come back
     // with the synchronisation the clip needs anyway (none on a fixed grid)
@@ -625,7 +627,7 @@ int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double*
     if (lb.ms.batch != lb.res_B || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = lb.res_B, S = lb.S, n = lb.n;
+    const int B = lb.res_B, S = lb.S * (int)lb.seed_items(), n = lb.n;  // (ensemble: every item's densities)
     const size_t md = dump_elems(n);
     std::vector<double2> fin;
     if (int rc = multistart_download_best(ctx, lb.ms, lindblad_seeds(ctx), controls_out,
@@ -646,7 +648,7 @@ static ControlCosts* control_costs_of(qocx_ctx* ctx, int32_t path, int& nc, int&
     }
     if (path == QOCX_PATH_LINDBLAD && ctx->lb.has_problem) {
         nc = ctx->lb.nc;
-        Kr = ctx->lb.K;
+        Kr = ctx->lb.seed_channels();
         return &ctx->lb.control_costs;
     }
     return nullptr;

@@ -313,6 +313,23 @@ struct qocx_ctx {
         DevBuf<int> order_dev;            // lb.order on the device
         MultiStart ms;                    // qocx_lindblad_opt_*
         ControlCosts control_costs;       // qocx_set_control_costs(QOCX_PATH_LINDBLAD)
+        // Hamiltonian ensemble (qocx_lindblad_set_ensemble, EnsembleArgs): the last ens_J of the problem's
+        // K channels are fixed perturbation channels. The seed-level calls take and return the seeds'
+        // K_r channels; an evaluation runs on the B x M member items (item b * M + m), each with its own
+        // sub-division count, and the buffers above (controls, cost_out, grads, final_out, order, B)
+        // are then those of the items.
+        int ens_M = 0;                    // 0: no ensemble
+        int ens_J = 0, ens_Kr = 0;        // fixed channels, seed channels (K = ens_Kr + ens_J)
+        std::vector<double> ens_scales_h, ens_offsets_h;  // [M][Kr], [M][J]
+        DevBuf<double> ens_scales, ens_offsets, ens_weights;
+        DevBuf<double> ens_seed_controls;  // [B][nc][Kr]: the seeds of qocx_eval_lindblad
+        DevBuf<double> ens_seed_cost, ens_seed_grads;  // ... and their reduced results
+        DevBuf<double> ens_items;          // [B][M][nc][K]: the expanded controls, item order
+        DevBuf<double> ens_cost, ens_grads;  // [B][M], [B][M][nc][K]: the items' results, item order
+        DevBuf<double2> ens_final;         // [B][M][S] dumps, item order (qocx_eval_lindblad)
+        int ens_members_B = 0;             // seeds whose member costs ens_cost holds (0: none)
+        int seed_channels() const { return ens_M > 0 ? ens_Kr : K; }
+        size_t seed_items() const { return ens_M > 0 ? (size_t)ens_M : 1; }
     } lb;
     // ---- qocx_debug_set_knob: kernel-variant switches for A/B measurements and tests ----
     std::map<std::string, int64_t> knobs;

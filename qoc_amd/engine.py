@@ -150,6 +150,9 @@ SIGNATURES = {
     "qocx_lindblad_last_subintervals": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "qocx_set_density_cotangents": (ctypes.c_int, [_VP, _I32, _I32, _c_int_p, _c_double_p]),
     "qocx_set_state_cotangents": (ctypes.c_int, [_VP, _I32, _I32, _c_int_p, _c_double_p]),
+    "qocx_lindblad_set_ensemble": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p,
+                                                  _c_double_p]),
+    "qocx_lindblad_ensemble_download_members": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_timing": (ctypes.c_int, [_VP, _I32]),
     "qocx_get_timing": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(_I64), _c_double_p]),
     "qocx_reset_timing": (ctypes.c_int, [_VP]),
@@ -278,6 +281,7 @@ class Engine(object):
         self._check(self._lib.qocx_create(int(device), ctypes.byref(self._ctx)))
         self._problem = None
         self._ensemble = None
+        self._lindblad_ensemble = None
         self._quadratic_count = 0
         self._keepalive = []
         self.batch = 0
@@ -433,7 +437,7 @@ class Engine(object):
     def _final_shape(self, B, path=PATH_SCHROEDINGER):
         if path == PATH_LINDBLAD:
             pr = self._lindblad
-            return (B, pr["S"], pr["n"], pr["n"])
+            return (B,) + self._lindblad_members() + (pr["S"], pr["n"], pr["n"])
         pr = self._problem
         members = () if self._ensemble is None else (self._ensemble["M"],)
         return (B,) + members + (pr["S"], pr["n"])
@@ -573,26 +577,66 @@ class Engine(object):
                               N=int(system_eval_count))
         self._lindblad_batch = 0
         self._lindblad_resident_batch = 0
+        self._lindblad_ensemble = None
+        self._lindblad_seeds = 0
+
+    def set_lindblad_ensemble(self, scales, offsets, weights):
+        """An ensemble of M members on the current Lindblad problem (qocx_lindblad_set_ensemble): the
+        problem's last J control channels are the perturbation matrices D_j. scales :: (M, K - J) or
+        None (all 1), offsets :: (M, J) or None (J = 0), weights :: (M,). From here on
+        evaluate_lindblad and the lindblad_* calls take and return the seeds' K - J channels, final
+        densities carry a member axis (B, M, S, n, n) and step densities are (B, M, N, S, n, n)."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        M = weights.shape[0]
+        J = 0 if offsets is None else np.asarray(offsets).size // max(M, 1)
+        kr = self._lindblad["K"] - J
+        none = ctypes.cast(None, _c_double_p)
+        sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64).reshape(M, kr)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float64).reshape(M, J)
+        self._check(self._lib.qocx_lindblad_set_ensemble(
+            self._ctx, M, J, none if sc is None else _dp(sc), none if off is None else _dp(off),
+            _dp(weights)))
+        self._lindblad_ensemble = dict(M=M, J=J, Kr=kr)
+        self._lindblad_batch = self._lindblad_seeds = 0
+        self._lindblad_resident_batch = 0
+
+    def lindblad_ensemble_member_costs(self):
+        """The unweighted cost of every member of every seed of the last Lindblad evaluation, (B, M)
+        (qocx_lindblad_ensemble_download_members)."""
+        M = 1 if self._lindblad_ensemble is None else self._lindblad_ensemble["M"]
+        out = np.empty((max(1, self._lindblad_seeds), M), dtype=np.float64)
+        self._check(self._lib.qocx_lindblad_ensemble_download_members(self._ctx, _dp(out)))
+        return out
+
+    def _lindblad_members(self):
+        return () if self._lindblad_ensemble is None else (self._lindblad_ensemble["M"],)
+
+    def _lindblad_seed_channels(self):
+        """Control channels of a Lindblad seed: the problem's K, or K - J with an ensemble set."""
+        ens = self._lindblad_ensemble
+        return self._lindblad["K"] if ens is None else ens["Kr"]
 
     def evaluate_lindblad(self, controls, want_grad=True, want_final=True):
-        """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n]) for controls[B,Nc,K]."""
+        """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n]) for controls[B,Nc,K]; with an
+        ensemble K is the seeds' K - J channels and the final densities are [B,M,S,n,n]."""
         pr = self._lindblad
+        K = self._lindblad_seed_channels()
         if pr["K"] > 0:
             controls = np.ascontiguousarray(controls, dtype=np.float64)
-            controls = controls.reshape(-1, pr["Nc"], pr["K"])
+            controls = controls.reshape(-1, pr["Nc"], K)
             B = controls.shape[0]
         else:
             B = 1 if controls is None else int(controls)
             controls = None
         cost = np.empty(B, dtype=np.float64)
         want_grad = bool(want_grad) and pr["K"] > 0
-        grads = np.empty((B, pr["Nc"], pr["K"]), dtype=np.float64) if want_grad else None
-        final = (np.empty((B, pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
+        grads = np.empty((B, pr["Nc"], K), dtype=np.float64) if want_grad else None
+        final = (np.empty(self._final_shape(B, PATH_LINDBLAD), dtype=np.complex128)
                  if want_final else None)
         self._check(self._lib.qocx_eval_lindblad(
             self._ctx, B, _dp(controls) if controls is not None else None, int(want_grad),
             _dp(cost), _dp(grads) if want_grad else None, _dp(final) if want_final else None))
-        self._lindblad_batch = B
+        self._lindblad_batch = self._lindblad_seeds = B
         return cost, grads, final
 
     def lindblad_last_subintervals(self):
@@ -614,7 +658,8 @@ class Engine(object):
 
     def download_step_densities(self):
         pr, B = self._lindblad, self._lindblad_batch
-        out = np.empty((B, pr["N"], pr["S"], pr["n"], pr["n"]), dtype=np.complex128)
+        out = np.empty((B,) + self._lindblad_members() + (pr["N"], pr["S"], pr["n"], pr["n"]),
+                       dtype=np.complex128)
         self._check(self._lib.qocx_download_step_densities(self._ctx, _dp(out)))
         return out
 
@@ -812,16 +857,18 @@ class Engine(object):
 
     # -- the same for the Lindblad problem (its own resident buffers, seed order) -----------------
     def lindblad_upload_controls(self, controls):
-        """controls :: (B, Nc, K) real, kept in HBM for eval_lindblad_resident / lindblad_opt_*."""
+        """controls :: (B, Nc, K) real, kept in HBM for eval_lindblad_resident / lindblad_opt_* (with
+        an ensemble the seeds' K - J channels)."""
         pr = self._lindblad
-        controls = np.ascontiguousarray(controls, dtype=np.float64).reshape(-1, pr["Nc"], pr["K"])
+        controls = np.ascontiguousarray(controls, dtype=np.float64).reshape(
+            -1, pr["Nc"], self._lindblad_seed_channels())
         self._check(self._lib.qocx_lindblad_upload_controls(self._ctx, controls.shape[0],
                                                             _dp(controls)))
         self._lindblad_resident_batch = controls.shape[0]
 
     def eval_lindblad_resident(self, want_grad=True):
         self._check(self._lib.qocx_eval_lindblad_resident(self._ctx, int(bool(want_grad))))
-        self._lindblad_batch = self._lindblad_resident_batch
+        self._lindblad_batch = self._lindblad_seeds = self._lindblad_resident_batch
 
     def lindblad_download_results(self, want_grad=True, want_final=True):
         """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n] or None), seed order."""
@@ -866,7 +913,7 @@ class Engine(object):
     # -- costs of the controls alone on the device ------------------------------------------------
     def _control_channels(self, path):
         if path == PATH_LINDBLAD:
-            return self._lindblad["Nc"], self._lindblad["K"]
+            return self._lindblad["Nc"], self._lindblad_seed_channels()
         return self._problem["Nc"], self._seed_channels()
 
     def set_control_costs(self, path, complex_controls, descriptors):

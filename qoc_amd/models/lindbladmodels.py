@@ -68,10 +68,14 @@ class EvolveLindbladDiscreteState(ProgramState):
 
 
 class EvolveLindbladResult(object):
-    def __init__(self, error=None, final_densities=None):
+    """member_errors: with a HamiltonianEnsemble, the unweighted device cost of each member (M,);
+    None otherwise."""
+
+    def __init__(self, error=None, final_densities=None, member_errors=None):
         super().__init__()
         self.error = error
         self.final_densities = final_densities
+        self.member_errors = member_errors
 
 
 class GrapeLindbladDiscreteState(GrapeState):
@@ -176,12 +180,16 @@ class GrapeLindbladDiscreteState(GrapeState):
 
 
 class GrapeLindbladResult(object):
+    """member_errors: with a HamiltonianEnsemble, the unweighted device cost of each member (M,)
+    at best_controls, from one forward evaluation after the optimisation; None otherwise."""
+
     def __init__(self, best_controls=None, best_error=np.finfo(np.float64).max,
-                 best_final_densities=None, best_iteration=None):
+                 best_final_densities=None, best_iteration=None, member_errors=None):
         super().__init__()
         self.best_controls = best_controls
         self.best_error = best_error
         self.best_final_densities = best_final_densities
         self.best_iteration = best_iteration
+        self.member_errors = member_errors
         # with a ControlBasis: the coefficients (P x control_count) behind best_controls
         self.best_coefficients = None
