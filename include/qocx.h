@@ -345,12 +345,29 @@ int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, con
  *     are set.
  * qocx_lindblad_ensemble_download_members: the unweighted cost of every item of the last evaluation
  * (qocx_eval_lindblad or qocx_eval_lindblad_resident), [B][M]; QOCX_ERR_STATE without an ensemble.
- * Not built: per-member dissipation rates (an uncertain T1), per-member targets, gradients with
- * respect to delta.
+ * Not built: per-member operators or targets, gradients with respect to delta or to the rates below.
  */
 int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
                                const double* offsets, const double* weights);
 int qocx_lindblad_ensemble_download_members(qocx_ctx* ctx, double* cost_out);
+
+/* Per-member dissipation rates of the ensemble (an uncertain T1 / T2): member m decays with
+ *     gamma_mi = rate_scales[m][i] * dissipators[i]      (one product, one rounding)
+ * under the problem's operators, and is otherwise the member of qocx_lindblad_set_ensemble. Its
+ * control-free generators, its rates and its norm bound are, bit for bit, those of the plain problem set
+ * with dissipators = rate_scales[m] . dissipators - so is its sub-division count (item (b, m) reads
+ * member m's bound), and so are its cost, gradient and densities. The seeds' results are reduced as
+ * before; the gradient is with respect to the seeds' controls only.
+ *   after qocx_lindblad_set_ensemble; rate_scales [M][L], L = operator_count; NULL clears the rates
+ *   (members and operators are then not read).
+ * QOCX_ERR_STATE without an ensemble, or on a problem set with stage tables (fixed_subdivision > 0: the
+ * control-free generator then lives in per-stage tables - one set, not M). QOCX_ERR_ARG if members != M,
+ * operators != operator_count, or an entry is non-finite or negative. qocx_set_lindblad_problem and
+ * qocx_lindblad_set_ensemble both clear the rates (as qocx_set_ensemble clears the quadratic scales);
+ * this call may be repeated. It clears the resident controls and the results, not the costs of the
+ * controls. */
+int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t operators,
+                                     const double* rate_scales);
 
 /* Per-kernel timing, measured with HIP events on the launch streams.
  * enable: 0 off, 1 every launch, 2 + k the launches of kernel k only (two events per timed launch

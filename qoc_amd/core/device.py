@@ -451,6 +451,11 @@ class SchroedingerEvaluator(_Evaluator):
         # index the seeds' K_r channels and act on the members' scaled controls.
         self.ensemble = None
         if isinstance(hamiltonian, HamiltonianEnsemble):
+            if hamiltonian.rate_scales is not None:
+                raise ValueError(
+                    "rate_scales scale the dissipation rates of lindblad_data: the Schroedinger "
+                    "path has none, so there is nothing to scale (use the Lindblad entry points, "
+                    "or drop rate_scales)")
             if backend is None:
                 backend = make_backend()
             hamiltonian = self._ensemble_base(hamiltonian, control_count, complex_controls,
@@ -608,6 +613,7 @@ class LindbladEvaluator(_Evaluator):
     MAX_CHANNELS = 8          # QOCX_LINDBLAD_MAX_K: real control channels of a Lindblad problem
     ensemble_setter = "set_lindblad_ensemble"
     ensemble_member_costs = "lindblad_ensemble_member_costs"
+    ensemble_rates_setter = "set_lindblad_ensemble_rates"
     _ensemble_base_message = (
         "a HamiltonianEnsemble on the Lindblad path needs a base hamiltonian linear in the "
         "controls (the tangent and frozen-controls routes evaluate one control array at a "
@@ -631,8 +637,11 @@ class LindbladEvaluator(_Evaluator):
         expands every seed into its M members (qocx_lindblad_set_ensemble), and evaluations
         return the weighted seed errors and gradients and final densities with a member axis
         (B x M x S x n x n). An ensemble on this path needs at least one cost: the error IS the
-        weighted sum of the members' costs. lindblad_data, densities and costs are the same
-        for all members.
+        weighted sum of the members' costs. Densities and costs are the same for all members,
+        and so is lindblad_data unless the ensemble has rate_scales (M x L): member m then decays
+        with the rates c_m * dissipators (qocx_lindblad_set_ensemble_rates). Those need a
+        time-independent system: with a time-dependent hamiltonian or lindblad_data the engine
+        holds the control-free generator in per-stage tables, one set, not M.
         """
         if not isinstance(interpolation_policy, InterpolationPolicy):
             raise NotImplementedError("This operation does not yet support the interpolation "
@@ -690,6 +699,11 @@ class LindbladEvaluator(_Evaluator):
                     "the Lindblad engine takes up to {} real control channels: this ensemble "
                     "needs K_r + J = {} + {}".format(self.MAX_CHANNELS, self.kr,
                                                      ensemble.perturbation_count))
+            if (ensemble.rate_scales is not None
+                    and not hasattr(self.backend, self.ensemble_rates_setter)):
+                raise NotImplementedError(
+                    "the backend {!r} does not take per-member dissipation rates (no {})".format(
+                        self.backend, self.ensemble_rates_setter))
         # time dependence is decided on the integrator's own grid: every stage time of the
         # coarsest sub-division (12 per sub-interval), never on a handful of equispaced probes
         # (piecewise constant: the edges of Nc slices are the cut points of Nc + 1 linear knots)
@@ -718,6 +732,8 @@ class LindbladEvaluator(_Evaluator):
             h0, g, dissipators, operators, _, data_dependent = probe(None)
             self.time_dependent = True
             hamiltonian = None
+        if self.ensemble is not None and self.ensemble.rate_scales is not None:
+            self._check_rate_scales(dissipators, data_dependent)
         # a time-dependent lindblad_data is sampled at the stage times like the Hamiltonian
         self._lindblad_data = lindblad_data if data_dependent else None
         self.cotangent_shape = (self.density_count, self.hilbert_size, self.hilbert_size)
@@ -750,6 +766,23 @@ class LindbladEvaluator(_Evaluator):
         self.backend.set_lindblad_problem(*self._problem_args, **tables, **self._problem_kw)
         if self.ensemble is not None:
             self.backend.set_lindblad_ensemble(*self._ensemble_args)
+            if self.ensemble.rate_scales is not None:
+                getattr(self.backend, self.ensemble_rates_setter)(self.ensemble.rate_scales)
+
+    def _check_rate_scales(self, dissipators, data_dependent):
+        """rate_scales against the probed lindblad_data, before the backend sees a problem: (M, L)
+        for its L operators, and a time-independent system."""
+        rates = self.ensemble.rate_scales
+        L = 0 if dissipators is None else len(dissipators)
+        if rates.shape[1] != L:
+            raise ValueError("rate_scales must be (M, L) with L = {} Lindblad operators of "
+                             "lindblad_data, got shape {}".format(L, rates.shape))
+        if self.time_dependent:
+            raise NotImplementedError(
+                "rate_scales need a time-independent system: {} is time dependent, so the engine "
+                "holds the control-free generator in per-stage tables (fixed_subdivision > 0) - "
+                "one set, not one per member".format(
+                    "lindblad_data" if data_dependent else "the hamiltonian (base or drives)"))
 
     def _item_bounds(self, bounds):
         """Bounds of the seeds' K_r channels -> bounds of the evaluated channels: with an ensemble

@@ -65,7 +65,9 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
     axis (M x density_count x n x n) and the result's member_errors holds each member's
     unweighted device cost. Such an ensemble needs at least one cost (costs of the densities with
     a device descriptor, and costs of the controls alone), K_r + J <= 8 real control channels and
-    perturbations, and no save file.
+    perturbations, and no save file. An ensemble with rate_scales (M x L) gives member m the
+    dissipation rates rate_scales[m] * dissipators of lindblad_data (an uncertain T1 / T2); that
+    needs a hamiltonian and a lindblad_data without explicit time dependence.
     """
     _check_ensemble(hamiltonian, costs, save_file_path)
     if controls is not None:

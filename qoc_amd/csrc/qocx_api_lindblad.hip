@@ -250,6 +250,38 @@ int upload_dumps(DevBuf<double2>& dst, const std::vector<cmat>& mats, int n, hip
     return dst.upload(img, st);
 }
 
+// The control-free part of a static problem as a function of (H0, L_i, gamma_i): A0L = -i H0 - decay / 2,
+// A0R = +i H0 - decay / 2 with decay = sum_i gamma_i L_i^H L_i (mathmethods.py:188, :200-203), and the two
+// bounds the sub-division rule reads. `ops` / `gammas` may end in the zero operator of pad_op; the first
+// `L` are the problem's own. op_norms: ||L_i||_2 of those. The plain problem calls this once, per-member
+// rates (qocx_lindblad_set_ensemble_rates) once per member: a member's generators and bounds are those of
+// the plain problem with its rates, bit for bit.
+struct ControlFree {
+    cmat a0l, a0r, decay;
+    double diss_norm = 0, l0_norm = 0;
+};
+
+ControlFree control_free_part(const cmat& h0, double h0_norm, const std::vector<cmat>& ops,
+                              const std::vector<double>& gammas, const std::vector<double>& op_norms, int L,
+                              int n) {
+    ControlFree cf;
+    cf.decay = cm_zero(n);
+    for (int i = 0; i < L; ++i) {
+        cm_axpy(cf.decay, gammas[i], cm_mul(cm_adjoint(ops[i], n), ops[i], n));
+        // || rho -> gamma (L rho L^H - {L^H L, rho} / 2) || <= 2 gamma ||L||_2^2 (the factor 2 is
+        // applied where the bound is formed)
+        cf.diss_norm += fabs(gammas[i]) * op_norms[i] * op_norms[i];
+    }
+    cf.a0l = cm_scale(h0, 0.0, -1.0);
+    cf.a0r = cm_scale(h0, 0.0, 1.0);
+    cm_axpy(cf.a0l, -0.5, cf.decay);
+    cm_axpy(cf.a0r, -0.5, cf.decay);
+    // static problem: the control-free Liouvillian as a whole (never above the sum of the parts)
+    cf.l0_norm = std::min(liouvillian_norm(cf.a0l, cf.a0r, ops, gammas, n), 2 * h0_norm + 2 * cf.diss_norm);
+    if (!(cf.l0_norm < 1e300)) cf.l0_norm = 2 * h0_norm + 2 * cf.diss_norm;
+    return cf;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -298,18 +330,12 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
 
     const cmat h0 = p->h0 ? cm_from(p->h0, n) : cm_zero(n);
-    cmat decay = cm_zero(n);  // sum gamma_i L_i^H L_i
     std::vector<cmat> ops;
-    std::vector<double> gammas(L);
-    lb.diss_norm = 0;
+    std::vector<double> gammas(L), op_norms(L);
     for (int i = 0; i < L; ++i) {
         ops.push_back(cm_from(p->operators + (size_t)i * n * n * 2, n));
         gammas[i] = p->dissipators[i];
-        cm_axpy(decay, gammas[i], cm_mul(cm_adjoint(ops[i], n), ops[i], n));
-        // || rho -> gamma (L rho L^H - {L^H L, rho} / 2) || <= 2 gamma ||L||_2^2 (the factor 2 is
-        // applied where the bound is formed)
-        const double opn = two_norm(ops[i].data(), n);
-        lb.diss_norm += fabs(gammas[i]) * opn * opn;
+        op_norms[i] = two_norm(ops[i].data(), n);
     }
     if (lb.pad_op) {
         ops.push_back(cm_zero(n));
@@ -319,17 +345,18 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     for (const cmat& op : ops)
         for (size_t e = 0; e < (size_t)n * n; ++e)
             if (op[2 * e + 1] != 0.0) lb.ops_real = false;
-    // A0L = -i H0 - decay/2 ; A0R = +i H0 - decay/2   (mathmethods.py:188, :200-203)
-    cmat a0l = cm_scale(h0, 0.0, -1.0), a0r = cm_scale(h0, 0.0, 1.0);
-    cm_axpy(a0l, -0.5, decay);
-    cm_axpy(a0r, -0.5, decay);
+    lb.h0_norm = two_norm(h0.data(), n);
+    const ControlFree cf = control_free_part(h0, lb.h0_norm, ops, gammas, op_norms, L, n);
+    const cmat &a0l = cf.a0l, &a0r = cf.a0r, &decay = cf.decay;  // decay: sum gamma_i L_i^H L_i
+    lb.diss_norm = cf.diss_norm;
+    lb.l0_norm = cf.l0_norm;
     lb.hermitian = p->h0_stages == nullptr && p->g_stages == nullptr && p->op_stages == nullptr &&
                    cm_is_hermitian(h0, n) && cm_is_hermitian(decay, n);
-    lb.h0_norm = two_norm(h0.data(), n);
-    // static problem: the control-free Liouvillian as a whole (never above the sum of the parts)
-    lb.l0_norm = std::min(liouvillian_norm(a0l, a0r, ops, gammas, n),
-                          2 * lb.h0_norm + 2 * lb.diss_norm);
-    if (!(lb.l0_norm < 1e300)) lb.l0_norm = 2 * lb.h0_norm + 2 * lb.diss_norm;
+    // (kept for qocx_lindblad_set_ensemble_rates, which builds the members' control-free parts from them)
+    lb.h0_h = h0;
+    lb.ops_h = ops;
+    lb.gammas_h = gammas;
+    lb.op_norms_h = op_norms;
     std::vector<cmat> gp, gpd, gpt;
     lb.g_norm.assign(K, 0.0);
     for (int k = 0; k < K; ++k) {
@@ -474,8 +501,9 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.res_B = lb.ms.batch = 0;  // resident controls and optimizer states belong to the old problem
     lb.res_have_results = false;
     lb.inj_count = 0;
-    lb.ens_M = lb.ens_J = lb.ens_Kr = 0;  // ... and so does the ensemble
+    lb.ens_M = lb.ens_J = lb.ens_Kr = 0;  // ... and so does the ensemble, with its rates
     lb.ens_members_B = 0;
+    lb.ens_rates = false;
     return 0;
 }
 
@@ -515,10 +543,60 @@ int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, co
     lb.ens_J = J;
     lb.ens_Kr = Kr;
     lb.ens_members_B = 0;
+    lb.ens_rates = false;        // (qocx_lindblad_set_ensemble_rates comes after, as the quadratic scales do)
     lb.have_results = false;
     lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
     lb.res_have_results = false;
     lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
+    return 0;
+}
+
+int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t operators, const double* rate_scales) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.ens_M == 0)
+        return fail(QOCX_ERR_STATE, "no Lindblad ensemble set (qocx_lindblad_set_ensemble first)");
+    if (lb.fixed_ksub > 0)
+        return fail(QOCX_ERR_STATE, "per-member rates need a static problem: this one was set with stage tables "
+                                    "(fixed_subdivision > 0), which hold one control-free generator per stage");
+    auto invalidate = [&] {
+        lb.ens_members_B = 0;
+        lb.have_results = false;
+        lb.res_B = lb.ms.batch = 0;
+        lb.res_have_results = false;
+    };
+    if (!rate_scales) {
+        lb.ens_rates = false;
+        invalidate();
+        return 0;
+    }
+    const int M = lb.ens_M, L = lb.nops, n = lb.n;
+    if (members != M) return fail(QOCX_ERR_ARG, "rate_scales: members differs from the ensemble's");
+    if (operators != L) return fail(QOCX_ERR_ARG, "rate_scales: operators differs from the problem's operator_count");
+    for (size_t e = 0; e < (size_t)M * L; ++e)
+        if (!std::isfinite(rate_scales[e]) || !(rate_scales[e] >= 0))
+            return fail(QOCX_ERR_ARG, "rate_scales must be finite and >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // member m: the control-free part of the plain problem with gamma_mi = c_mi * gamma_i (one product, one
+    // rounding); [M][4] dumps A0L, A0R, A0L^H, A0R^H and [M][L'] rates, L' with the zero operator of pad_op
+    const size_t md = dump_elems(n), Lp = lb.gammas_h.size();
+    std::vector<double2> img((size_t)M * 4 * md);
+    std::vector<double> gam((size_t)M * std::max<size_t>(Lp, 1), 0.0);
+    lb.rate_l0_norm.assign(M, 0.0);
+    for (int m = 0; m < M; ++m) {
+        std::vector<double> gm(lb.gammas_h);
+        for (int i = 0; i < L; ++i) gm[i] = rate_scales[(size_t)m * L + i] * lb.gammas_h[i];
+        const ControlFree cf = control_free_part(lb.h0_h, lb.h0_norm, lb.ops_h, gm, lb.op_norms_h, L, n);
+        c_dump(cf.a0l, n, img.data() + ((size_t)m * 4 + 0) * md);
+        c_dump(cf.a0r, n, img.data() + ((size_t)m * 4 + 1) * md);
+        c_dump(cm_adjoint(cf.a0l, n), n, img.data() + ((size_t)m * 4 + 2) * md);
+        c_dump(cm_adjoint(cf.a0r, n), n, img.data() + ((size_t)m * 4 + 3) * md);
+        for (size_t i = 0; i < Lp; ++i) gam[(size_t)m * Lp + i] = gm[i];
+        lb.rate_l0_norm[m] = cf.l0_norm;
+    }
+    if (lb.rate_a0.upload(img, ctx->stream) || lb.rate_gammas.upload(gam, ctx->stream)) return QOCX_ERR_HIP;
+    lb.ens_rates = true;
+    invalidate();
     return 0;
 }
 
@@ -693,7 +771,11 @@ int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<
         // the sum of its parts' bounds over the samples
         double ctl = 0;
         for (int k = 0; k < K; ++k) ctl += umax[(size_t)b * K + k] * lb.g_norm[k];
-        const double base = lb.fixed_ksub > 0 ? 2 * lb.h0_norm + 2 * lb.diss_norm : lb.l0_norm;
+        // (per-member rates: B counts items b * M + m, and item (b, m) takes member m's bound - the
+        // sub-division count the plain problem with that member's rates would pick)
+        const double base = lb.fixed_ksub > 0 ? 2 * lb.h0_norm + 2 * lb.diss_norm
+                            : lb.ens_rates    ? lb.rate_l0_norm[b % lb.ens_M]
+                                              : lb.l0_norm;
         const double bound = base + 2 * ctl;
         if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or operators");
         const double pieces = ceil(bound * fabs(lb.dt) / 0.4);
@@ -843,6 +925,21 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
             la.a0l_cimg = lb.a0l.p; la.a0r_cimg = lb.a0r.p; la.a0ld_cimg = lb.a0ld.p; la.a0rd_cimg = lb.a0rd.p;
             la.gp_cimg = lb.gp.p; la.gpd_cimg = lb.gpd.p; la.gpt_cimg = lb.gpt.p; la.op_cimg = lb.ops.p;
             la.gammas = lb.gammas.p; la.rho0_cimg = lb.rho0.p;
+            qocx::LindbladMembers mem;
+            if (lb.ens_rates) {
+                // per-member rates: workgroup i of this launch reads the tables of member item_member[i]
+                mem.item_member = lb.order_dev.p + B + pos0;
+                la.a0l_cimg = lb.rate_a0.p; la.a0r_cimg = lb.rate_a0.p + md;
+                la.a0ld_cimg = lb.rate_a0.p + 2 * md; la.a0rd_cimg = lb.rate_a0.p + 3 * md;
+                la.gammas = lb.rate_gammas.p;
+                mem.a0_stride = 4 * md;
+                mem.gamma_stride = lb.gammas_h.size();
+            }
+            // (kernels of their own behind the member table: qocx_lindblad_rates.hip, qocx_lindblad4t_rates.hip)
+            auto launch = [&](const qocx::LindbladArgs& args, hipStream_t st) {
+                if (lb.ens_rates) qocx::launch_lindblad_rates(args, mem, Bp, st);
+                else qocx::launch_lindblad(args, Bp, st);
+            };
             la.a0_tab = lb.fixed_ksub > 0 ? lb.a0_tab.p : nullptr;
             la.gp_tab = (lb.fixed_ksub > 0 && lb.gp_tab.p) ? lb.gp_tab.p : nullptr;
             la.op_tab = (lb.fixed_ksub > 0 && lb.op_tab.p) ? lb.op_tab.p : nullptr;
@@ -907,10 +1004,10 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
                 fwd.ops_real = adj.ops_real = (lb.ops_real && ctx->knob("lindblad_real_ops", 1) != 0) ? 1 : 0;
                 if (la.stamps != nullptr) adj.stamps = la.stamps + (size_t)B * 48;
                 time_begin(ctx, 5, ctx->stream);
-                qocx::launch_lindblad(fwd, Bp, ctx->stream);
+                launch(fwd, ctx->stream);
                 time_end(ctx, ctx->stream);
                 time_begin(ctx, 5, side);
-                qocx::launch_lindblad(adj, Bp, side);
+                launch(adj, side);
                 time_end(ctx, side);
                 if (side != ctx->stream) {
                     HIP_TRY(hipEventRecord(ctx->ev_swept[0], side));
@@ -921,7 +1018,7 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
                 time_end(ctx, ctx->stream);
             } else {
                 time_begin(ctx, 5, ctx->stream);
-                qocx::launch_lindblad(la, Bp, ctx->stream);
+                launch(la, ctx->stream);
                 time_end(ctx, ctx->stream);
             }
             if (want_grad) {
@@ -996,7 +1093,14 @@ int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_contro
     int rc = lindblad_subdivisions(ctx, items, umax ? item_umax.data() : nullptr, ksub_of);
     if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
     if (rc) return rc;
-    if (lb.order_dev.upload(lb.order, ctx->stream)) return QOCX_ERR_HIP;
+    if (lb.ens_rates) {
+        // behind the order: the member of every launched item, in launch order (LindbladMembers::item_member)
+        std::vector<int> both(lb.order);
+        for (int i = 0; i < items; ++i) both.push_back(lb.order[i] % lb.ens_M);
+        if (lb.order_dev.upload(both, ctx->stream)) return QOCX_ERR_HIP;
+    } else if (lb.order_dev.upload(lb.order, ctx->stream)) {
+        return QOCX_ERR_HIP;
+    }
     qocx::launch_gather_seeds(lb.ens_items.p, lb.controls.p, csz, lb.order_dev.p, items, ctx->stream);
     return lindblad_launch_groups(ctx, want_grad, plan);
 }

@@ -341,6 +341,27 @@ struct LindbladArgs {
     double2* lam_scale = nullptr;  // [B][S]: phase 1 out
 };
 
+// Per-member dissipation rates (qocx_lindblad_set_ensemble_rates), the second argument of the kernels of
+// qocx_lindblad_rates.hip / qocx_lindblad4t_rates.hip: workgroup b of the launch belongs to ensemble member
+// item_member[b], and a0l / a0r / a0ld / a0rd_cimg and gammas of the LindbladArgs are the tables of member 0
+// with these strides (in elements) to the next member. An argument of its own: LindbladArgs, and with it
+// every kernel that runs without rates, is what it was without them.
+struct LindbladMembers {
+    const int* item_member = nullptr;  // [B], launch order
+    size_t a0_stride = 0, gamma_stride = 0;
+    // Called once at the top of a kernel, on its by-value copy of the arguments: folds the workgroup's member
+    // into the base pointers, so no read site below knows about members. The index is uniform over the
+    // workgroup (one scalar load of item_member[blockIdx.x]); nothing is added inside a stage.
+    __device__ __forceinline__ void select(LindbladArgs& a) const {
+        const size_t m = (size_t)item_member[blockIdx.x];
+        a.a0l_cimg += m * a0_stride;
+        a.a0r_cimg += m * a0_stride;
+        a.a0ld_cimg += m * a0_stride;
+        a.a0rd_cimg += m * a0_stride;
+        a.gammas += m * gamma_stride;
+    }
+};
+
 // ---- Hilbert sizes above 64 (qocx_general.hip): row-major padded np x np matrices in HBM, np = 16 ceil(n / 16) ----
 struct GeneralArgs {  // K1a + K1b: one work item per (seed, step), `total` = seeds * nsteps
     int np, K, nc, nsteps, nt;
@@ -517,6 +538,8 @@ void launch_lindblad_combine(const LindbladArgs& a, int batch, hipStream_t st);
 bool lindblad4t_supports(const LindbladArgs& a);
 void launch_lindblad4t(const LindbladArgs& a, int batch, hipStream_t st);
 void launch_lindblad4t_combine(const LindbladArgs& a, int batch, hipStream_t st);
+void launch_lindblad_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st);
+void launch_lindblad4t_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st);
 int lindblad_lds_size(int n, int S, int nops, int mode, int K);
 size_t lindblad_scratch_elems(int n, int S);
 

@@ -328,6 +328,15 @@ struct qocx_ctx {
         DevBuf<double> ens_cost, ens_grads;  // [B][M], [B][M][nc][K]: the items' results, item order
         DevBuf<double2> ens_final;         // [B][M][S] dumps, item order (qocx_eval_lindblad)
         int ens_members_B = 0;             // seeds whose member costs ens_cost holds (0: none)
+        // ... with per-member dissipation rates gamma_mi = c_mi gamma_i (qocx_lindblad_set_ensemble_rates):
+        // every member has its own control-free generators, rates and sub-division bound, built from the
+        // problem's host copies below as the plain setter builds its own
+        bool ens_rates = false;
+        std::vector<double> h0_h, gammas_h, op_norms_h;  // H0; gamma_i [L'] (L' with pad_op's zero); ||L_i||_2 [L]
+        std::vector<std::vector<double>> ops_h;          // L_i [L']
+        std::vector<double> rate_l0_norm;                // [M]: l0_norm of the members
+        DevBuf<double2> rate_a0;                         // [M][4] dumps A0L, A0R, A0L^H, A0R^H
+        DevBuf<double> rate_gammas;                      // [M][L']
         int seed_channels() const { return ens_M > 0 ? ens_Kr : K; }
         size_t seed_items() const { return ens_M > 0 ? (size_t)ens_M : 1; }
     } lb;

@@ -153,6 +153,7 @@ SIGNATURES = {
     "qocx_lindblad_set_ensemble": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p,
                                                   _c_double_p]),
     "qocx_lindblad_ensemble_download_members": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_lindblad_set_ensemble_rates": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_set_timing": (ctypes.c_int, [_VP, _I32]),
     "qocx_get_timing": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(_I64), _c_double_p]),
     "qocx_reset_timing": (ctypes.c_int, [_VP]),
@@ -597,6 +598,24 @@ class Engine(object):
             self._ctx, M, J, none if sc is None else _dp(sc), none if off is None else _dp(off),
             _dp(weights)))
         self._lindblad_ensemble = dict(M=M, J=J, Kr=kr)
+        self._lindblad_batch = self._lindblad_seeds = 0
+        self._lindblad_resident_batch = 0
+
+    def set_lindblad_ensemble_rates(self, rate_scales):
+        """Per-member dissipation rates of the current Lindblad ensemble
+        (qocx_lindblad_set_ensemble_rates): rate_scales :: (M, L) finite and >= 0, member m decays
+        with the rates rate_scales[m] * dissipators; None clears them. After set_lindblad_ensemble;
+        a new problem or a new ensemble clears the rates. Static problems only (no stage tables)."""
+        if rate_scales is None:
+            self._check(self._lib.qocx_lindblad_set_ensemble_rates(
+                self._ctx, 0, 0, ctypes.cast(None, _c_double_p)))
+        else:
+            rates = np.ascontiguousarray(rate_scales, dtype=np.float64)
+            if rates.ndim != 2:
+                raise ValueError("rate_scales must be (M, L), got shape {}".format(rates.shape))
+            keep = rates if rates.size else np.zeros(1)  # (L = 0: nothing is read)
+            self._check(self._lib.qocx_lindblad_set_ensemble_rates(
+                self._ctx, rates.shape[0], rates.shape[1], _dp(keep)))
         self._lindblad_batch = self._lindblad_seeds = 0
         self._lindblad_resident_batch = 0
 

@@ -16,7 +16,9 @@ scaled controls and fixed perturbation terms, all driven by the same controls (r
 Schroedinger evaluator sets it up as one structured problem whose extra control channels are the
 perturbation matrices, and the engine expands every seed into its M members on the device
 (qocx_set_ensemble). A QuadraticHamiltonian base keeps its terms on the device as well, each
-optionally scaled per member (quadratic_scales, qocx_set_ensemble_quadratic_scales).
+optionally scaled per member (quadratic_scales, qocx_set_ensemble_quadratic_scales). On the Lindblad
+path every member may scale the dissipation rates as well (rate_scales, an uncertain T1 / T2:
+qocx_lindblad_set_ensemble_rates).
 """
 
 import numbers
@@ -127,7 +129,7 @@ def _real_array(value, name, ndim):
 class HamiltonianEnsemble(object):
     """
     E = HamiltonianEnsemble(hamiltonian, perturbations=None, offsets=None, control_scales=None,
-                            weights=None, quadratic_scales=None)
+                            weights=None, quadratic_scales=None, rate_scales=None)
 
     M copies of a system, all driven by the same controls (robust GRAPE). Member m is
 
@@ -149,8 +151,13 @@ class HamiltonianEnsemble(object):
         term, in the order of hamiltonian.pairs (an uncertain Stark coefficient). Only for a
         QuadraticHamiltonian base with Q terms. Default: all 1.
 
-    M is read from whichever of offsets, control_scales, weights and quadratic_scales is given; they
-    must agree.
+    rate_scales :: (M, L) real, finite and >= 0 - c_mi, member m's factor of the i-th dissipation
+        rate of the problem's lindblad_data: gamma_mi = c_mi * gamma_i (an uncertain T1 / T2). Lindblad
+        entry points only, with L the number of Lindblad operators and a time-independent system
+        (hamiltonian and lindblad_data). Default: every member takes the rates as given.
+
+    M is read from whichever of offsets, control_scales, weights, quadratic_scales and rate_scales is
+    given; they must agree.
     Passed as the `hamiltonian` of evolve_schroedinger_discrete, grape_schroedinger_discrete or
     grape_schroedinger_discrete_batch, the cost is sum_m w_m c_m over the members' device costs
     (costs of the controls alone are added once), and the gradient is that of this sum. The
@@ -158,7 +165,7 @@ class HamiltonianEnsemble(object):
     """
 
     def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
-                 weights=None, quadratic_scales=None):
+                 weights=None, quadratic_scales=None, rate_scales=None):
         if not callable(hamiltonian):
             raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
         counts = {}
@@ -196,12 +203,17 @@ class HamiltonianEnsemble(object):
                 raise ValueError("quadratic_scales must be (M, Q) with Q = {} quadratic terms, got "
                                  "shape {}".format(len(hamiltonian.pairs), quadratic_scales.shape))
             counts["quadratic_scales"] = quadratic_scales.shape[0]
+        if rate_scales is not None:
+            rate_scales = _real_array(rate_scales, "rate_scales", 2)
+            if np.any(rate_scales < 0):
+                raise ValueError("rate_scales must be >= 0 (they multiply dissipation rates)")
+            counts["rate_scales"] = rate_scales.shape[0]
         if not counts:
             raise ValueError("an ensemble needs offsets, control_scales or weights (M is read "
                              "from them)")
         if len(set(counts.values())) > 1:
-            raise ValueError("offsets, control_scales, weights and quadratic_scales disagree on "
-                             "the member count: {}"
+            raise ValueError("offsets, control_scales, weights, quadratic_scales and rate_scales "
+                             "disagree on the member count: {}"
                              "".format(", ".join("{} {}".format(k, v) for k, v in counts.items())))
         M = next(iter(counts.values()))
         if M == 0:
@@ -213,6 +225,7 @@ class HamiltonianEnsemble(object):
         self.control_scales = control_scales
         self.weights = weights if weights is not None else np.full(M, 1.0 / M)
         self.quadratic_scales = quadratic_scales
+        self.rate_scales = rate_scales
         self.member_count = M
 
     @property
@@ -281,6 +294,30 @@ class HamiltonianEnsemble(object):
             return out
         return hamiltonian
 
+    def member_lindblad_data(self, m, lindblad_data):
+        """Member m's lindblad_data as a plain callable time -> (c_m * dissipators, operators): the
+        problem's own where the ensemble has no rate_scales."""
+        m = int(m)
+        if not 0 <= m < self.member_count:
+            raise IndexError("member {} out of range for {} members".format(m, self.member_count))
+        if not callable(lindblad_data):
+            raise ValueError("lindblad_data must be a callable time -> (dissipators, operators)")
+        if self.rate_scales is None:
+            return lindblad_data
+        factors = self.rate_scales[m]
+
+        def member_data(time):
+            dissipators, operators = lindblad_data(time)
+            dissipators = np.asarray(dissipators)
+            if dissipators.shape != factors.shape:
+                raise ValueError("rate_scales must be (M, L) with L = {} Lindblad operators, got shape "
+                                 "{}".format(dissipators.shape[0] if dissipators.ndim else 0,
+                                             self.rate_scales.shape))
+            return factors * dissipators, operators
+        return member_data
+
     def __repr__(self):
-        return "HamiltonianEnsemble({!r}, {} members, {} perturbations)".format(
-            self.hamiltonian, self.member_count, self.perturbation_count)
+        rates = "" if self.rate_scales is None else ", rate_scales {}".format(
+            "x".join(str(d) for d in self.rate_scales.shape))
+        return "HamiltonianEnsemble({!r}, {} members, {} perturbations{})".format(
+            self.hamiltonian, self.member_count, self.perturbation_count, rates)
