@@ -276,6 +276,39 @@ int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out);
  */
 int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t count, const double* scales);
 
+/*
+ * Hamiltonian sweeps: B seeds, each a system of its own with a pulse of its own (gate-time sweeps,
+ * calibration families) - the complement of an ensemble, which drives M systems with one pulse.
+ * Call after qocx_set_schroedinger_problem, whose LAST `fixed` = J control channels are the fixed
+ * matrices D_j; K_r = control_count - J channels remain for the seeds. Seed b evaluates the problem
+ * on the K-channel controls
+ *     r_b[j][k] = s_bk u_b[j][k] (k < K_r),   r_b[j][K_r + i] = delta_bi (every knot)
+ * i.e. H_b(u, t) = H(s_b . u, t) + sum_i delta_bi D_i. A duration T_b = tau_b T is the case where the
+ * drift is the fixed channel D_0 = H0 of a problem with H0 = 0: delta_b0 = tau_b, s_bk = tau_b s_k.
+ *   scales  [seeds][K_r] (NULL: all 1)   offsets [seeds][J] (NULL exactly when J = 0)
+ * QOCX_ERR_ARG unless seeds >= 1, 0 <= J < control_count and every entry is finite; QOCX_ERR_STATE
+ * while an ensemble or quadratic terms are set, and qocx_set_ensemble / qocx_set_quadratic_terms
+ * return QOCX_ERR_STATE while a sweep is set. A new problem clears the sweep. Controls must be
+ * uploaded afterwards.
+ * With a sweep set:
+ *   qocx_upload_controls(ctx, seeds, controls [seeds][Nc][K_r]) keeps the seed controls on the device
+ *     and expands them into the items; any other batch size is QOCX_ERR_ARG. The squaring bounds are
+ *     those of the expanded array, bit for bit: item b is the plain K-channel problem on r_b.
+ *   qocx_eval_resident evaluates the items as any batch; cost_b is the item's cost and
+ *     grad_b[j][k] = s_bk dc_b / dr[j][k] (k < K_r, one rounding).
+ *   qocx_download_results (costs [B], gradients [B][Nc][K_r], final states [B][S][n]),
+ *   qocx_download_costs, qocx_reduce_results, qocx_set_control_costs and qocx_opt_* (the basis,
+ *     complex and L-BFGS calls included) act on the B seeds and their K_r channels; qocx_opt_clip
+ *     takes max_norms [K_r] and bounds the items with max_norms_k max_b |s_bk| and max_b |delta_bi|.
+ * qocx_sweep_download_sensitivities, after an evaluation with gradients (QOCX_ERR_STATE otherwise):
+ *     scales_out [B][K_r]  dE_b / ds_bk     = sum_j u_b[j][k] dc_b / dr[j][k]
+ *     offsets_out [B][J]   dE_b / ddelta_bi = sum_j dc_b / dr[j][K_r + i]
+ *   (either may be NULL), each sum in the fixed order stated in qocx_sweep.hip: 64 partial sums over
+ *   the knots l, l + 64, ... ascending, then a halving tree - independent of the launch.
+ */
+int qocx_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* scales, const double* offsets);
+int qocx_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out);
+
 /* Optional: all system-step states of the last evaluation, [B][N][S][n] complex
  * (what save_intermediate_states persists, schroedingerdiscrete.py:395-402). */
 int qocx_set_keep_step_states(qocx_ctx* ctx, int32_t keep); /* before the evaluation */

@@ -42,6 +42,9 @@ class BatchResult(object):
         self.member_errors = [None] * seed_count
         # with a ControlBasis: per seed, the coefficients (P x control_count) behind best_controls
         self.best_coefficients = [None] * seed_count
+        # with a HamiltonianSweep: dict(control_scales (B x control_count), offsets (B x J)[,
+        # evolution_time_gradients (B)]) at every seed's best controls
+        self.sweep_sensitivities = None
 
     @property
     def best(self):
@@ -334,6 +337,40 @@ def prepare_seeds(initial_controls, complex_controls, control_count, control_eva
     params = (np.stack([strip_controls(complex_controls, c) for c in seeds]) if seeds
               else np.zeros((0, knots * control_count)))
     return comm, pstate, np.array(params, dtype=np.float64)
+
+
+def rank_sweep(sweep, seed_total, comm):
+    """The block of a HamiltonianSweep that this rank's seeds (parallel.shard_bounds) belong to.
+    The sweep must have one system per seed of the whole batch."""
+    from qoc_amd import parallel
+    if seed_total != sweep.seed_count:
+        raise ValueError("a HamiltonianSweep of {} seeds needs initial_controls for exactly that "
+                         "many seeds, got {}".format(sweep.seed_count, seed_total))
+    comm = comm if comm is not None else parallel.SingleComm()
+    lo, hi = parallel.shard_bounds(seed_total, comm.rank, comm.world)
+    if hi == lo:  # (a rank without seeds sets up a problem that it never evaluates)
+        return sweep.slice(0, 1)
+    return sweep.slice(lo, hi)
+
+
+def sweep_sensitivities(evaluator, result):
+    """result.sweep_sensitivities: the sweep's sensitivities at every seed's best controls, from one
+    evaluation with gradients of all seeds after the loop (a seed without best controls is
+    evaluated at zero controls and its rows are NaN)."""
+    B = len(result.best_controls)
+    if B == 0:
+        return
+    have = np.array([c is not None for c in result.best_controls])
+    if not have.any():
+        return
+    template = result.best_controls[int(np.nonzero(have)[0][0])]
+    controls = np.stack([c if c is not None else np.zeros_like(template)
+                         for c in result.best_controls])
+    evaluator.evaluate_batch(controls, want_grad=True)
+    out = evaluator.sweep_sensitivities()
+    for value in out.values():
+        value[~have] = np.nan
+    result.sweep_sensitivities = out
 
 
 def resident_route(stepper, optimizer, pstate, evaluator, batch):

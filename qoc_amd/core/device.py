@@ -11,7 +11,8 @@ import numpy as np
 
 from qoc_amd.core import structure
 from qoc_amd.models.policies import InterpolationPolicy, MagnusPolicy
-from qoc_amd.standard.hamiltonians import HamiltonianEnsemble, QuadraticHamiltonian
+from qoc_amd.standard.hamiltonians import (HamiltonianEnsemble, HamiltonianSweep,
+                                            QuadraticHamiltonian)
 
 def make_backend(device=-1):
     """The HIP engine. There is no CPU fallback: this raises when libqocx.so or the GPU is
@@ -67,6 +68,12 @@ def reject_costless_lindblad_ensemble(hamiltonian, costs):
         raise NotImplementedError(
             "a HamiltonianEnsemble on the Lindblad path needs at least one cost: its error is the "
             "weighted sum of the members' costs (costs is empty)")
+
+
+def reject_sweep(hamiltonian, where, hint=""):
+    """The entry points that do not take a HamiltonianSweep say so by name."""
+    if isinstance(hamiltonian, HamiltonianSweep):
+        raise NotImplementedError("a HamiltonianSweep is not evaluated by {}{}".format(where, hint))
 
 
 def user_states_bar(cost, controls, states, step):
@@ -140,6 +147,7 @@ class _Evaluator(object):
     linearized_hamiltonian = None
     _cost_controls = None     # controls the costs see in place of the evaluated ones
     ensemble = None           # the HamiltonianEnsemble being evaluated
+    sweep = None              # the HamiltonianSweep being evaluated
     ensemble_setter = "set_ensemble"                 # the backend's entry points for one
     ensemble_member_costs = "ensemble_member_costs"
 
@@ -153,8 +161,8 @@ class _Evaluator(object):
         if control_count == 0:
             raise NotImplementedError("a HamiltonianEnsemble needs at least one control "
                                       "(control_count = 0)")
-        if isinstance(base, HamiltonianEnsemble) or (isinstance(base, QuadraticHamiltonian)
-                                                     and not quadratic_ok):
+        if isinstance(base, (HamiltonianEnsemble, HamiltonianSweep)) or (
+                isinstance(base, QuadraticHamiltonian) and not quadratic_ok):
             raise NotImplementedError(self._ensemble_base_message.format(base))
         if not hasattr(backend, self.ensemble_setter):
             raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian ensembles "
@@ -178,7 +186,7 @@ class _Evaluator(object):
 
     def _append_perturbations(self, g):
         """G (nt, K_r, n, n) -> [G_1 .. G_K_r, D_1 .. D_J] in every one of the nt tables."""
-        d = self.ensemble.perturbations
+        d = self.ensemble.perturbations if self.ensemble is not None else self._sweep_matrices
         if d is None:
             return g
         g = np.asarray(g, dtype=np.complex128)
@@ -281,6 +289,9 @@ class _Evaluator(object):
         else:
             controls_batch = np.asarray(controls_batch)
             batch = controls_batch.shape[0]
+            if self.sweep is not None and batch != self.sweep.seed_count:
+                raise ValueError("a HamiltonianSweep of {} seeds takes a batch of exactly that "
+                                 "many control arrays, got {}".format(self.sweep.seed_count, batch))
             device_controls = structure.to_real_controls(controls_batch, self.complex_controls)
         self._prepare(device_controls)
         need_steps = want_step_states or bool(self.opaque_costs)
@@ -460,6 +471,16 @@ class SchroedingerEvaluator(_Evaluator):
                 backend = make_backend()
             hamiltonian = self._ensemble_base(hamiltonian, control_count, complex_controls,
                                               backend, magnus_policy)
+        # A HamiltonianSweep: the same structured problem - the base with the fixed matrices D_j
+        # appended as J channels - but seed b is item b, with scales and offsets of its own
+        # (qocx_set_sweep); evaluations take exactly B control arrays and return B errors and
+        # gradients, and sweep_sensitivities() the derivatives with respect to the tables.
+        self.sweep = None
+        if isinstance(hamiltonian, HamiltonianSweep):
+            if backend is None:
+                backend = make_backend()
+            hamiltonian = self._sweep_base(hamiltonian, control_count, complex_controls, backend,
+                                           times)
         if isinstance(hamiltonian, QuadraticHamiltonian) and backend is None:
             backend = make_backend()  # (the route depends on what the backend takes)
         if (isinstance(hamiltonian, QuadraticHamiltonian) and magnus_policy == MagnusPolicy.M2
@@ -477,6 +498,10 @@ class SchroedingerEvaluator(_Evaluator):
             if self.ensemble is not None:
                 raise NotImplementedError(
                     "a HamiltonianEnsemble needs a base hamiltonian linear in the controls "
+                    "({})".format(exc))
+            if self.sweep is not None:
+                raise NotImplementedError(
+                    "a HamiltonianSweep needs a base hamiltonian linear in the controls "
                     "({})".format(exc))
             if self.quadratic_terms is not None:
                 raise
@@ -499,6 +524,9 @@ class SchroedingerEvaluator(_Evaluator):
         if self.ensemble is not None:
             self._reject_opaque_ensemble_costs()
             g = self._append_perturbations(g)
+        if self.sweep is not None:
+            self._reject_sweep_costs()
+            g = self._append_perturbations(g)
         self.backend = backend if backend is not None else make_backend()
         if hasattr(self.backend, "set_knob"):
             self.backend.set_knob(
@@ -508,6 +536,8 @@ class SchroedingerEvaluator(_Evaluator):
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:
             device_k += self.ensemble.perturbation_count
+        if self.sweep is not None:
+            device_k += self.sweep.perturbation_count
         self._problem_static = (
             (self.hilbert_size, self.state_count, device_k, control_eval_count if device_k else 0,
              system_eval_count, evolution_time),
@@ -529,6 +559,62 @@ class SchroedingerEvaluator(_Evaluator):
             if (self.quadratic_terms is not None and len(self.quadratic_terms[0])
                     and self.ensemble.quadratic_scales is not None):
                 self.backend.set_ensemble_quadratic_scales(self.ensemble.quadratic_scales)
+        if self.sweep is not None:
+            self.backend.set_sweep(*self._sweep_args)
+
+    # -- Hamiltonian sweeps -----------------------------------------------------------------------
+    def _sweep_base(self, sweep, control_count, complex_controls, backend, times):
+        """Checks a sweep against this problem and the backend, keeps it with the arguments of the
+        backend's setter (self._sweep_args) and its fixed matrices, and returns its base."""
+        base = sweep.hamiltonian
+        if control_count == 0:
+            raise NotImplementedError("a HamiltonianSweep needs at least one control "
+                                      "(control_count = 0)")
+        if isinstance(base, (HamiltonianEnsemble, HamiltonianSweep, QuadraticHamiltonian)):
+            raise NotImplementedError(
+                "a HamiltonianSweep needs a plain base hamiltonian linear in the controls (sweep x "
+                "ensemble and sweep x QuadraticHamiltonian are not evaluated), got {!r}"
+                "".format(base))
+        if not hasattr(backend, "set_sweep"):
+            raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian sweeps "
+                                      "(no set_sweep)".format(backend))
+        matrices = sweep.resolve(control_count, complex_controls, self.hilbert_size, times)
+        if matrices is not None and matrices.shape[1] != self.hilbert_size:
+            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
+                matrices.shape[1], self.hilbert_size))
+        self.sweep = sweep
+        self._sweep_matrices = matrices
+        self._sweep_args = (sweep.real_channel_scales(control_count, complex_controls),
+                            sweep.offsets)
+        return base
+
+    def _reject_sweep_costs(self):
+        if self.opaque_costs:
+            raise NotImplementedError(
+                "a HamiltonianSweep takes costs evaluated on the device (with a "
+                "device_descriptor()) and costs of the controls alone; {} is neither (user costs "
+                "without a device descriptor)".format(self.opaque_costs[0]))
+        if self.sweep.time_scaled:
+            from qoc_amd.standard.costs import ControlBandwidthMax
+            for cost in self.host_costs:
+                if isinstance(cost, ControlBandwidthMax):
+                    raise NotImplementedError(
+                        "ControlBandwidthMax with a duration sweep: its frequency bins depend on "
+                        "the evolution time, which differs from seed to seed")
+
+    def sweep_sensitivities(self):
+        """Of the last evaluation with gradients: dict(control_scales = d error_b / d s_bk
+        (B x control_count; a complex control's two channels added), offsets = d error_b /
+        d delta_bj (B x J)), and for a duration sweep evolution_time_gradients = d error_b / d T_b
+        (B). Costs of the controls alone do not depend on the tables and do not enter."""
+        scales, offsets = self.backend.sweep_sensitivities()
+        scales, offsets = np.asarray(scales), np.asarray(offsets)
+        if self.complex_controls:
+            scales = scales[:, 0::2] + scales[:, 1::2]
+        out = dict(control_scales=scales, offsets=offsets)
+        if self.sweep.time_scaled:
+            out["evolution_time_gradients"] = self.sweep.time_gradients(scales, offsets)
+        return out
 
     # -- Hamiltonian ensembles ------------------------------------------------------------------
     _ensemble_base_message = (
@@ -647,6 +733,8 @@ class LindbladEvaluator(_Evaluator):
             raise NotImplementedError("This operation does not yet support the interpolation "
                                       "policy {}.".format(interpolation_policy))
         self.interpolation_policy = interpolation_policy
+        reject_sweep(hamiltonian, "the Lindblad path",
+                     ": a duration there scales the dissipation rates as well, which is not built")
         ensemble = hamiltonian if isinstance(hamiltonian, HamiltonianEnsemble) else None
         if ensemble is not None:
             reject_costless_lindblad_ensemble(ensemble, costs)

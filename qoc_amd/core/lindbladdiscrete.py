@@ -16,7 +16,8 @@ from qoc_amd.core import batch
 from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
                                  initialize_coefficients, initialize_controls,
                                  reject_basis_save, strip_controls)
-from qoc_amd.core.device import LindbladEvaluator, reject_costless_lindblad_ensemble
+from qoc_amd.core.device import (LindbladEvaluator, reject_costless_lindblad_ensemble,
+                                 reject_sweep)
 from qoc_amd.core.structure import NonLinearHamiltonianError
 from qoc_amd.engine import PATH_LINDBLAD
 from qoc_amd.models import (Dummy, EvolveLindbladDiscreteState, EvolveLindbladResult,
@@ -30,6 +31,8 @@ def _check_ensemble(hamiltonian, costs, save_file_path=None):
     """Before any save file is touched and before a backend is made: a HamiltonianEnsemble on the
     Lindblad path needs at least one cost (its error is the weighted sum of the members' costs)
     and writes no save file."""
+    reject_sweep(hamiltonian, "the Lindblad entry points",
+                 ": a duration there scales the dissipation rates as well, which is not built")
     if not isinstance(hamiltonian, HamiltonianEnsemble):
         return
     reject_costless_lindblad_ensemble(hamiltonian, costs)

@@ -13,13 +13,18 @@ from qoc_amd.core import batch
 from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
                                  initialize_coefficients, initialize_controls,
                                  reject_basis_save, strip_controls)
-from qoc_amd.core.device import SchroedingerEvaluator
+from qoc_amd.core.device import SchroedingerEvaluator, reject_sweep
 from qoc_amd.engine import PATH_SCHROEDINGER
 from qoc_amd.models import (Dummy, EvolveSchroedingerDiscreteState, EvolveSchroedingerResult,
                             GrapeSchroedingerDiscreteState, GrapeSchroedingerResult,
                             InterpolationPolicy, MagnusPolicy)
-from qoc_amd.standard.hamiltonians import HamiltonianEnsemble
+from qoc_amd.standard.hamiltonians import HamiltonianEnsemble, HamiltonianSweep
 from qoc_amd.standard.optimizers import Adam
+
+
+_SWEEP_HINT = (": it is B systems with controls of their own - pass it to "
+               "grape_schroedinger_discrete_batch, or evaluate one of its systems as "
+               "sweep.member(b)")
 
 
 def _check_ensemble_save(hamiltonian, save_file_path):
@@ -45,6 +50,7 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
     member axis (M x state_count x n x 1) and the result's member_errors holds each member's
     unweighted device cost.
     """
+    reject_sweep(hamiltonian, "evolve_schroedinger_discrete", _SWEEP_HINT)
     _check_ensemble_save(hamiltonian, save_file_path)
     if controls is not None:
         controls = np.asarray(controls)
@@ -97,6 +103,7 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     has a member axis, and member_errors holds each member's unweighted device cost at
     best_controls (one forward evaluation after the loop).
     """
+    reject_sweep(hamiltonian, "grape_schroedinger_discrete", _SWEEP_HINT)
     _check_ensemble_save(hamiltonian, save_file_path)
     reject_basis_save(control_basis, save_file_path)
     coefficients = None
@@ -222,8 +229,19 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     best_coefficients[b] the coefficients behind best_controls[b]. On the resident route the
     coefficients, the optimizer state sized by them and the map itself stay on the device
     (qocx_opt_begin_basis, qocx_ctrlbasis.hip).
+    With a HamiltonianSweep (qoc_amd.standard) of B seeds, B = len(initial_controls) over all ranks,
+    seed b is optimised on the sweep's system b (with a communicator every rank sets its block,
+    sweep.slice); max_control_norms bound the seeds' own controls. The result's
+    sweep_sensitivities holds d error_b / d control_scales (B x control_count) and / d offsets
+    (B x J) at the seeds' best controls (one evaluation with gradients after the loop), and for a
+    duration sweep evolution_time_gradients (B). User costs without a device descriptor, and
+    ControlBandwidthMax with a duration sweep, are refused.
     Returns GrapeSchroedingerBatchResult.
     """
+    if isinstance(hamiltonian, HamiltonianSweep):
+        initial_controls = np.asarray(initial_controls)
+        if initial_controls.ndim == 3:  # (prepare_seeds reports any other shape)
+            hamiltonian = batch.rank_sweep(hamiltonian, initial_controls.shape[0], comm)
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
         max_control_norms, impose_control_conditions, comm, control_basis)
@@ -250,6 +268,8 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
         out = batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
     if getattr(evaluator, "ensemble", None) is not None:
         _ensemble_member_errors(evaluator, out)
+    if getattr(evaluator, "sweep", None) is not None:
+        batch.sweep_sensitivities(evaluator, out)
     return out
 
 

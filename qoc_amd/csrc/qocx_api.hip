@@ -573,6 +573,7 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     ctx->eff.kind = EffectiveControls::NONE;  // a new problem clears the quadratic terms
     ctx->ens_M = 0;                           // ... and the ensemble
     ctx->ens_qscales_set = false;
+    ctx->swp_B = 0;                           // ... and the sweep
 
     set_hermitian_flags(ctx, p);
     if (int rc = upload_operators(ctx, p)) return rc;
@@ -613,6 +614,8 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
         return 0;
     }
     if (!pairs || !matrices) return fail(QOCX_ERR_ARG, "pairs / matrices missing");
+    if (ctx->swp_B > 0)
+        return fail(QOCX_ERR_STATE, "a sweep is set (qocx_set_sweep): it does not take quadratic terms");
     if (ctx->nodes != 1)
         return fail(QOCX_ERR_ARG, "quadratic terms need magnus_policy M2 (M4 / M6 take the callable's tangent)");
     if (ctx->explicit_mode) return fail(QOCX_ERR_ARG, "quadratic terms do not apply to explicit generators");
@@ -678,6 +681,8 @@ int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const doubl
                       const double* offsets, const double* weights) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
+    if (ctx->swp_B > 0)
+        return fail(QOCX_ERR_STATE, "a sweep is set (qocx_set_sweep): a problem takes a sweep or an ensemble");
     if (members < 1 || members > 1024) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
     if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
     if (fixed >= ctx->K)
@@ -727,10 +732,59 @@ int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const doubl
     return 0;
 }
 
+int qocx_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* scales, const double* offsets) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
+    if (ctx->ens_M > 0 && ctx->swp_B == 0)
+        return fail(QOCX_ERR_STATE, "an ensemble is set (qocx_set_ensemble): a problem takes a sweep or an ensemble");
+    if (ctx->eff.quad_count() > 0)
+        return fail(QOCX_ERR_STATE, "quadratic terms are set (qocx_set_quadratic_terms): a sweep does not take them");
+    if (seeds < 1) return fail(QOCX_ERR_ARG, "sweep seeds must be >= 1");
+    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
+    if (fixed >= ctx->K)
+        return fail(QOCX_ERR_ARG, "a sweep needs fixed < control_count (at least one seed control)");
+    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed channels need offsets");
+    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 channels");
+    const int B = seeds, J = fixed, Kr = ctx->K - fixed;
+    std::vector<double> sc((size_t)B * Kr, 1.0), off((size_t)B * J);
+    if (scales) sc.assign(scales, scales + sc.size());
+    if (J > 0) off.assign(offsets, offsets + off.size());
+    for (double v : sc)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep control scale");
+    for (double v : off)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep offset");
+    std::vector<double> smax(Kr, 0.0), omax(J, 0.0);
+    for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < Kr; ++k) smax[k] = std::max(smax[k], fabs(sc[(size_t)b * Kr + k]));
+        for (int j = 0; j < J; ++j) omax[j] = std::max(omax[j], fabs(off[(size_t)b * J + j]));
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->swp_scales.upload(sc, ctx->stream) || (J > 0 && ctx->swp_offsets.upload(off, ctx->stream)))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->swp_scales_h = sc;
+    ctx->swp_offsets_h = off;
+    ctx->swp_B = B;
+    // the seed-level view: one item per seed (qocx_host.h)
+    ctx->ens_scale_max = smax;
+    ctx->ens_offset_max = omax;
+    ctx->ens_M = 1;
+    ctx->ens_J = J;
+    ctx->ens_Kr = Kr;
+    ctx->ens_B = 0;
+    ctx->ens_stale = false;
+    ctx->ens_qscales_set = false;
+    ctx->have_results = false;
+    ctx->B = 0;  // controls must be uploaded again (as seed controls)
+    ctx->ms.batch = 0;
+    return 0;
+}
+
 int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t count, const double* scales) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
-    if (ctx->ens_M == 0) return fail(QOCX_ERR_ARG, "quadratic term scales need an ensemble (qocx_set_ensemble)");
+    if (ctx->ens_M == 0 || ctx->swp_B > 0)
+        return fail(QOCX_ERR_ARG, "quadratic term scales need an ensemble (qocx_set_ensemble)");
     if (ctx->eff.quad_count() == 0)
         return fail(QOCX_ERR_ARG, "quadratic term scales need quadratic terms (qocx_set_quadratic_terms)");
     if (members != ctx->ens_M) return fail(QOCX_ERR_ARG, "members does not match the ensemble's");
@@ -887,9 +941,50 @@ void ensemble_stage(const qocx_ctx* ctx, int batch, const double* controls, doub
         }
 }
 
-// expand the seeds' controls into the member items of ctx->controls
+// ---- Hamiltonian sweeps (qocx_set_sweep) ------------------------------------------------------------
+
+qocx::SystemSweepArgs sweep_args(qocx_ctx* ctx) {
+    qocx::SystemSweepArgs a;
+    a.seed_controls = ctx->ens_controls.p; a.scales = ctx->swp_scales.p;
+    a.offsets = ctx->ens_J > 0 ? ctx->swp_offsets.p : nullptr;
+    a.controls = ctx->controls.p;
+    a.item_cost = ctx->cost_out.p; a.item_grads = ctx->grads.p;
+    a.cost = ctx->ens_cost.p; a.grads = ctx->ens_grads.p;
+    a.scale_sens = ctx->swp_scale_sens.p; a.offset_sens = ctx->swp_offset_sens.p;
+    a.B = ctx->swp_B; a.nc = ctx->nc; a.K = ctx->K; a.Kr = ctx->ens_Kr; a.J = ctx->ens_J;
+    return a;
+}
+
+// ensemble_stage for a sweep: the bounds of the expanded [B][nc][K] array, row by row in the order of
+// the plain upload (s_bk u_bjk for k < K_r, delta_bj beyond) - bit for bit those of an upload of the
+// expanded array, so item b takes the Pade orders, squarings and kernel variants of the plain problem.
+void sweep_stage(const qocx_ctx* ctx, const double* controls, double* stage, double& smax, double& smid) {
+    const int B = ctx->swp_B, Kr = ctx->ens_Kr, J = ctx->ens_J, nc = ctx->nc;
+    const double* gn = ctx->g_norm_max.data();
+    memcpy(stage, controls, (size_t)B * nc * Kr * sizeof(double));
+    double sprev = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const double* s = ctx->swp_scales_h.data() + (size_t)b * Kr;
+        const double* d = ctx->swp_offsets_h.data() + (size_t)b * J;
+        for (int j = 0; j < nc; ++j) {
+            const double* u = controls + ((size_t)b * nc + j) * Kr;
+            double srow = 0.0;
+            for (int k = 0; k < Kr; ++k) srow += fabs(s[k] * u[k]) * gn[k];
+            for (int k = 0; k < J; ++k) srow += fabs(d[k]) * gn[Kr + k];
+            if (!(srow <= smax)) smax = srow;  // also catches NaN
+            if (j != 0) {
+                const double mid = 0.5 * (sprev + srow);
+                if (!(mid <= smid)) smid = mid;
+            }
+            sprev = srow;
+        }
+    }
+}
+
+// expand the seeds' controls into the member items of ctx->controls (a sweep: into its B items)
 int ensemble_expand(qocx_ctx* ctx, int seeds) {
-    qocx::launch_ensemble_expand(ensemble_args(ctx, seeds), ctx->stream);
+    if (ctx->swp_B > 0) qocx::launch_sweep_expand(sweep_args(ctx), ctx->stream);
+    else qocx::launch_ensemble_expand(ensemble_args(ctx, seeds), ctx->stream);
     HIP_TRY(hipGetLastError());
     ctx->ens_stale = false;
     return 0;
@@ -916,6 +1011,8 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
     HIP_TRY(hipSetDevice(ctx->device));
     const bool ens = ctx->ens_M > 0;
+    if (ctx->swp_B > 0 && batch != ctx->swp_B)
+        return fail(QOCX_ERR_ARG, "a sweep takes exactly its own seed count as the batch (qocx_set_sweep)");
     if (ens && (int64_t)batch * ctx->ens_M > 0x7fffffff)
         return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
     // (with an ensemble the caller's array holds the seeds' K_r channels)
@@ -943,7 +1040,8 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // per-step bound (launch_step_table) - tighter than sum_k max_t |u_k(t)| ||G_k||_1
         double smax = 0.0, smid = 0.0, sprev = 0.0;
         double* stage = ctx->pin_controls;
-        if (ens) ensemble_stage(ctx, batch, controls, stage, smax, smid);
+        if (ctx->swp_B > 0) sweep_stage(ctx, controls, stage, smax, smid);
+        else if (ens) ensemble_stage(ctx, batch, controls, stage, smax, smid);
         for (size_t row = 0; !ens && row < (size_t)batch * ctx->nc; ++row) {
             const double* src = controls + row * K;
             double* dst = stage + row * K;
@@ -1115,9 +1213,15 @@ static int eval_seeds(qocx_ctx* ctx, int32_t want_grad) {
     if (ctx->ens_cost.ensure((size_t)seeds) ||
         (ctx->have_grads && ctx->ens_grads.ensure((size_t)seeds * ctx->nc * ctx->ens_Kr)))
         return QOCX_ERR_HIP;
-    qocx::EnsembleArgs a = ensemble_args(ctx, seeds);
-    if (!ctx->have_grads) a.grads = nullptr;
-    qocx::launch_ensemble_reduce(a, ctx->stream);
+    if (ctx->swp_B > 0) {
+        qocx::SystemSweepArgs a = sweep_args(ctx);
+        if (!ctx->have_grads) a.grads = nullptr;
+        qocx::launch_sweep_reduce(a, ctx->stream);
+    } else {
+        qocx::EnsembleArgs a = ensemble_args(ctx, seeds);
+        if (!ctx->have_grads) a.grads = nullptr;
+        qocx::launch_ensemble_reduce(a, ctx->stream);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -1334,11 +1438,33 @@ int qocx_download_costs(qocx_ctx* ctx, double* cost_out) {
 
 int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
     if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
-    if (ctx->ens_M == 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_set_ensemble)");
+    if (ctx->ens_M == 0 || ctx->swp_B > 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_set_ensemble)");
     if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(cost_out, ctx->cost_out.p, (size_t)ctx->B * sizeof(double),
                            hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (ctx->swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_set_sweep)");
+    // (the seed controls on the device are those of the evaluation exactly while its results stand:
+    // qocx_opt_clip / _step and an upload clear have_results)
+    if (!ctx->have_results || !ctx->have_grads || ctx->ens_stale)
+        return fail(QOCX_ERR_STATE, "sweep sensitivities need an evaluation with gradients");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t ns = (size_t)ctx->swp_B * ctx->ens_Kr, no = (size_t)ctx->swp_B * ctx->ens_J;
+    if (ctx->swp_scale_sens.ensure(ns) || ctx->swp_offset_sens.ensure(no)) return QOCX_ERR_HIP;
+    qocx::launch_sweep_sensitivity(sweep_args(ctx), ctx->stream);
+    HIP_TRY(hipGetLastError());
+    if (scales_out)
+        HIP_TRY(hipMemcpyAsync(scales_out, ctx->swp_scale_sens.p, ns * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (offsets_out && no > 0)
+        HIP_TRY(hipMemcpyAsync(offsets_out, ctx->swp_offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

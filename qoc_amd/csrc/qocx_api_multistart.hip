@@ -439,7 +439,8 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
     HIP_TRY(hipSetDevice(ctx->device));
     // after the clip |u_k| <= max_norms[k]: the squaring capacity follows from that bound
-    // (ensemble: |s_mk u_k| <= max_norms[k] max_m |s_mk| on the K_r seed channels, |delta_mj| beyond)
+    // (ensemble: |s_mk u_k| <= max_norms[k] max_m |s_mk| on the K_r seed channels, |delta_mj| beyond;
+    // a sweep keeps max_b |s_bk| and max_b |delta_bj| in the same two vectors)
     const bool ens = ctx->ens_M > 0;
     const SeedView v = schroedinger_seeds(ctx);
     const int Ks = v.channels;

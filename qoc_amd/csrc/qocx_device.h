@@ -265,6 +265,22 @@ struct EnsembleArgs {
     int B, M, nc, K, Kr, J;
 };
 
+// Hamiltonian sweep (qocx_sweep.hip): B seeds, each its own item on K = Kr + J channels
+#define QOCX_SWEEP_LANES 64     // partial sums of a sensitivity (the summation order: qocx_sweep.hip)
+struct SystemSweepArgs {
+    const double* seed_controls;  // expand / sensitivity in: [B][nc][Kr]
+    const double* scales;         // [B][Kr]
+    const double* offsets;        // [B][J] (J > 0)
+    double* controls;             // expand out: [B][nc][K]
+    const double* item_cost;      // reduce in: [B]
+    const double* item_grads;     // reduce / sensitivity in: [B][nc][K]
+    double* cost;                 // reduce out: [B]
+    double* grads;                // reduce out: [B][nc][Kr], or nullptr (no gradients)
+    double* scale_sens;           // sensitivity out: [B][Kr]
+    double* offset_sens;          // sensitivity out: [B][J] (J > 0)
+    int B, nc, K, Kr, J;
+};
+
 struct ScatterArgs {
     const double* gstep;
     const int* row_ptr;   // [nc+1]
@@ -601,6 +617,9 @@ void launch_quad_controls(const QuadArgs& a, hipStream_t st);
 void launch_quad_chain(const QuadArgs& a, hipStream_t st);
 void launch_ensemble_expand(const EnsembleArgs& a, hipStream_t st);
 void launch_ensemble_reduce(const EnsembleArgs& a, hipStream_t st);
+void launch_sweep_expand(const SystemSweepArgs& a, hipStream_t st);
+void launch_sweep_reduce(const SystemSweepArgs& a, hipStream_t st);
+void launch_sweep_sensitivity(const SystemSweepArgs& a, hipStream_t st);
 void launch_selftest(double* out, hipStream_t st);
 
 }  // namespace qocx

@@ -248,6 +248,15 @@ struct qocx_ctx {
     bool ens_qscales_set = false;
     std::vector<double> ens_qscale_max;                 // max_m |c_mq|
     DevBuf<double> ens_qscales;                         // [M][count]
+    // Hamiltonian sweep (qocx_set_sweep, SystemSweepArgs): seed b is a system of its own, item b. It is the
+    // ensemble's seed-level state above with ONE item per seed (ens_M = 1: ens_Kr, ens_J, ens_B,
+    // ens_stale, ens_controls / _cost / _grads, and ens_scale_max / ens_offset_max as maxima over the
+    // seeds), so every seed-level call (qocx_opt_*, control costs, downloads) serves it unchanged;
+    // its tables are per SEED and live here, and its expansion, reduction and staging are its own.
+    int swp_B = 0;                                      // 0: no sweep; else the only batch size it takes
+    std::vector<double> swp_scales_h, swp_offsets_h;    // [B][Kr], [B][J]
+    DevBuf<double> swp_scales, swp_offsets;
+    DevBuf<double> swp_scale_sens, swp_offset_sens;     // [B][Kr], [B][J] (qocx_sweep_download_sensitivities)
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;

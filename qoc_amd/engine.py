@@ -139,6 +139,8 @@ SIGNATURES = {
     "qocx_set_ensemble": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p, _c_double_p]),
     "qocx_ensemble_download_members": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_ensemble_quadratic_scales": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
+    "qocx_set_sweep": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p]),
+    "qocx_sweep_download_sensitivities": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
     "qocx_set_keep_step_states": (ctypes.c_int, [_VP, _I32]),
     "qocx_download_step_states": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_lindblad_problem": (ctypes.c_int, [_VP, ctypes.POINTER(_LindbladProblem)]),
@@ -282,6 +284,7 @@ class Engine(object):
         self._check(self._lib.qocx_create(int(device), ctypes.byref(self._ctx)))
         self._problem = None
         self._ensemble = None
+        self._sweep = None
         self._lindblad_ensemble = None
         self._quadratic_count = 0
         self._keepalive = []
@@ -373,6 +376,7 @@ class Engine(object):
         self._check(self._lib.qocx_set_schroedinger_problem(self._ctx, ctypes.byref(p)))
         self._problem = dict(n=n, S=S, K=K, Nc=int(control_eval_count), N=int(system_eval_count))
         self._ensemble = None
+        self._sweep = None
         self._quadratic_count = 0
         self.batch = 0
 
@@ -431,8 +435,48 @@ class Engine(object):
         self._check(self._lib.qocx_ensemble_download_members(self._ctx, _dp(out)))
         return out
 
+    def set_sweep(self, scales, offsets):
+        """A sweep of B seeds on the current problem (qocx_set_sweep): seed b is a system of its own,
+        the problem on the controls [scales[b] * u_b, offsets[b]]; the problem's last J control
+        channels are the fixed matrices D_j. scales :: (B, K - J) or None (all 1), offsets :: (B, J)
+        or None (J = 0); one of them is needed (B is read from it). From here on the seed-level
+        calls take and return the seeds' K - J channels and the batch is exactly B."""
+        if scales is None and offsets is None:
+            raise ValueError("a sweep needs scales or offsets (the seed count is read from them)")
+        none = ctypes.cast(None, _c_double_p)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float64)
+        if off is not None and off.ndim != 2:
+            raise ValueError("offsets must be (B, J), got shape {}".format(off.shape))
+        J = 0 if off is None else off.shape[1]
+        kr = self._problem["K"] - J
+        sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64)
+        B = off.shape[0] if sc is None else sc.shape[0]
+        if sc is not None and sc.shape != (B, kr):
+            raise ValueError("scales must be (B, K - J) = ({}, {}), got shape {}".format(B, kr, sc.shape))
+        if off is not None and off.shape[0] != B:
+            raise ValueError("scales and offsets disagree on the seed count")
+        if J == 0:
+            off = None
+        self._check(self._lib.qocx_set_sweep(
+            self._ctx, B, J, none if sc is None else _dp(sc), none if off is None else _dp(off)))
+        self._sweep = dict(B=B, J=J, Kr=kr)
+        self.batch = 0
+
+    def sweep_sensitivities(self):
+        """(dE_b / d scales [B, K - J], dE_b / d offsets [B, J]) of the last evaluation with
+        gradients (qocx_sweep_download_sensitivities)."""
+        sw = self._sweep
+        if sw is None:
+            raise ValueError("no sweep set (set_sweep)")
+        scales = np.empty((sw["B"], sw["Kr"]), dtype=np.float64)
+        offsets = np.empty((sw["B"], sw["J"]), dtype=np.float64)
+        self._check(self._lib.qocx_sweep_download_sensitivities(self._ctx, _dp(scales), _dp(offsets)))
+        return scales, offsets
+
     def _seed_channels(self):
-        """Control channels of a seed: the problem's K, or K - J with an ensemble set."""
+        """Control channels of a seed: the problem's K, or K - J with an ensemble or a sweep set."""
+        if self._sweep is not None:
+            return self._sweep["Kr"]
         return self._problem["K"] if self._ensemble is None else self._ensemble["Kr"]
 
     def _final_shape(self, B, path=PATH_SCHROEDINGER):

@@ -19,6 +19,11 @@ perturbation matrices, and the engine expands every seed into its M members on t
 optionally scaled per member (quadratic_scales, qocx_set_ensemble_quadratic_scales). On the Lindblad
 path every member may scale the dissipation rates as well (rate_scales, an uncertain T1 / T2:
 qocx_lindblad_set_ensemble_rates).
+
+HamiltonianSweep is not a callable either: it is B systems, each with controls of its own - scaled
+controls and fixed terms per SEED (a gate-time sweep, a calibration family). The Schroedinger
+evaluator sets it up as the ensemble's structured problem and the engine expands seed b into item b
+on the device (qocx_set_sweep).
 """
 
 import numbers
@@ -166,6 +171,10 @@ class HamiltonianEnsemble(object):
 
     def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
                  weights=None, quadratic_scales=None, rate_scales=None):
+        if isinstance(hamiltonian, HamiltonianSweep):
+            raise NotImplementedError(
+                "a HamiltonianSweep inside a HamiltonianEnsemble is not evaluated: the engine "
+                "takes a sweep or an ensemble per problem (sweep x ensemble is out of scope)")
         if not callable(hamiltonian):
             raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
         counts = {}
@@ -321,3 +330,282 @@ class HamiltonianEnsemble(object):
             "x".join(str(d) for d in self.rate_scales.shape))
         return "HamiltonianEnsemble({!r}, {} members, {} perturbations{})".format(
             self.hamiltonian, self.member_count, self.perturbation_count, rates)
+
+
+class HamiltonianSweep(object):
+    """
+    W = HamiltonianSweep(hamiltonian, perturbations=None, offsets=None, control_scales=None)
+
+    B systems, each driven by controls of its own (a gate-time sweep, a calibration family) - the
+    complement of a HamiltonianEnsemble, which drives M systems with one pulse. Seed b is
+
+        H_b(u, t) = hamiltonian(s_b * u, t) + sum_j offsets[b, j] D_j
+
+    hamiltonian :: (controls, time) -> (n x n), real-linear in the controls (time dependence
+        allowed); not a QuadraticHamiltonian, a HamiltonianEnsemble or another sweep.
+    perturbations :: (J, n, n) complex - the fixed matrices D_j.
+    offsets :: (B, J) real - delta_bj; given exactly when perturbations are.
+    control_scales :: (B, control_count) real - s_bk; a complex control's scale multiplies its
+        real and imaginary parts alike. Default: all 1.
+
+    B is read from whichever of offsets and control_scales is given; they must agree.
+    Passed as the `hamiltonian` of grape_schroedinger_discrete_batch (B = initial_controls.shape[0])
+    or of SchroedingerEvaluator (evaluate_batch with a batch of B), seed b is optimised or
+    evaluated on system b; the engine expands the seeds on the device (qocx_set_sweep) and returns
+    sweep_sensitivities, d error_b / d s_bk and d error_b / d delta_bj. The object is not itself
+    callable: member(b) is seed b's system as a plain callable, slice(lo, hi) the sweep of a
+    contiguous block of seeds.
+
+    HamiltonianSweep.durations(...) builds the sweep in which seed b runs for its own evolution
+    time.
+    """
+
+    time_scaled = False
+    evolution_times = None
+    reference_time = None
+
+    def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None):
+        if not callable(hamiltonian):
+            raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
+        counts = {}
+        if perturbations is not None:
+            perturbations = np.array(perturbations, dtype=np.complex128)
+            if perturbations.ndim != 3 or perturbations.shape[1] != perturbations.shape[2]:
+                raise ValueError("perturbations must be (J, n, n), got shape {}"
+                                 "".format(perturbations.shape))
+            if not np.all(np.isfinite(perturbations)):
+                raise ValueError("perturbations is not finite")
+            if offsets is None:
+                raise ValueError("perturbations need offsets of shape (B, J)")
+        if offsets is not None:
+            if perturbations is None:
+                raise ValueError("offsets need perturbations (the matrices D_j they multiply)")
+            offsets = _real_array(offsets, "offsets", 2)
+            if offsets.shape[1] != perturbations.shape[0]:
+                raise ValueError("offsets must be (B, J) with J = {} perturbations, got shape {}"
+                                 "".format(perturbations.shape[0], offsets.shape))
+            counts["offsets"] = offsets.shape[0]
+        if control_scales is not None:
+            control_scales = _real_array(control_scales, "control_scales", 2)
+            counts["control_scales"] = control_scales.shape[0]
+        if not counts:
+            raise ValueError("a sweep needs offsets or control_scales (B is read from them)")
+        if len(set(counts.values())) > 1:
+            raise ValueError("offsets and control_scales disagree on the seed count: {}"
+                             "".format(", ".join("{} {}".format(k, v) for k, v in counts.items())))
+        B = next(iter(counts.values()))
+        if B == 0:
+            raise ValueError("a sweep needs at least one seed (B = 0 in {})"
+                             "".format(", ".join(counts)))
+        self.hamiltonian = hamiltonian
+        self.perturbations = perturbations
+        self.offsets = offsets
+        self.control_scales = control_scales
+        self.seed_count = B
+        self._source = None          # durations(): the user's hamiltonian, whose drift is D_0
+        self._extra_perturbations = None
+        self._tau = None
+        self._user_scales = control_scales   # s0, delta0 of time_gradients: the values before tau
+        self._user_offsets = offsets
+
+    @classmethod
+    def durations(cls, hamiltonian, evolution_times, reference_time, control_scales=None,
+                  perturbations=None, offsets=None):
+        """
+        The sweep in which seed b runs for evolution_times[b]: with tau_b = T_b / reference_time,
+
+            tau_b * hamiltonian(u, t)  on  [0, reference_time]
+
+        is the system on [0, T_b] - exact for a time-independent hamiltonian under every Magnus
+        policy (scaling H is scaling time). The sweep's base is hamiltonian(u, t) - hamiltonian(0, t),
+        its first fixed matrix D_0 = hamiltonian(0, .) with offset tau_b, every control scale and
+        every further offset is multiplied by tau_b. The caller passes evolution_time =
+        reference_time to the entry point.
+
+        evolution_times :: (B,) finite and > 0; reference_time :: finite and > 0.
+        control_scales, perturbations, offsets: as in the constructor, before the factor tau_b.
+        A time-dependent hamiltonian is a ValueError: here when control_scales tell the control
+        count, else when the sweep meets its problem (the probe of qoc_amd.core.structure).
+        The sweep carries evolution_times, reference_time and time_scaled = True;
+        time_gradients() turns its sensitivities into d error_b / d T_b.
+        """
+        if not callable(hamiltonian):
+            raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
+        if isinstance(hamiltonian, (QuadraticHamiltonian, HamiltonianEnsemble, HamiltonianSweep)):
+            raise NotImplementedError(
+                "a duration sweep needs a plain hamiltonian linear in the controls, got {!r}"
+                "".format(hamiltonian))
+        times = _real_array(evolution_times, "evolution_times", 1)
+        if times.shape[0] == 0:
+            raise ValueError("a sweep needs at least one seed (evolution_times is empty)")
+        if np.any(times <= 0):
+            raise ValueError("evolution_times must be > 0")
+        reference_time = float(reference_time)
+        if not np.isfinite(reference_time) or reference_time <= 0:
+            raise ValueError("reference_time must be finite and > 0")
+        B = times.shape[0]
+        tau = times / reference_time
+        user_offsets = None
+        if perturbations is not None or offsets is not None:
+            # (the constructor's checks, on the user's own values)
+            probe = cls(hamiltonian, perturbations, offsets, None)
+            if probe.seed_count != B:
+                raise ValueError("offsets are for {} seeds, evolution_times for {}"
+                                 "".format(probe.seed_count, B))
+            perturbations, user_offsets = probe.perturbations, probe.offsets
+        user_scales = None
+        if control_scales is not None:
+            user_scales = _real_array(control_scales, "control_scales", 2)
+            if user_scales.shape[0] != B:
+                raise ValueError("control_scales are for {} seeds, evolution_times for {}"
+                                 "".format(user_scales.shape[0], B))
+
+        def base(controls, time):
+            u = np.asarray(controls)
+            return (np.asarray(hamiltonian(u, time), dtype=np.complex128)
+                    - np.asarray(hamiltonian(np.zeros_like(u), time), dtype=np.complex128))
+
+        self = cls.__new__(cls)
+        self.hamiltonian = base
+        self._source = hamiltonian
+        self._extra_perturbations = perturbations   # D_1 ..: the user's; D_0 is resolved later
+        self.perturbations = None
+        columns = [tau[:, None]]
+        if user_offsets is not None:
+            columns.append(tau[:, None] * user_offsets)
+        self.offsets = np.concatenate(columns, axis=1)
+        self._user_scales = user_scales
+        self._user_offsets = np.concatenate(
+            [np.ones((B, 1))] + ([user_offsets] if user_offsets is not None else []), axis=1)
+        # (scales of all 1 are kept implicit until the control count is known)
+        self.control_scales = None if user_scales is None else tau[:, None] * user_scales
+        self._tau = tau
+        self.seed_count = B
+        self.time_scaled = True
+        self.evolution_times = times
+        self.reference_time = reference_time
+        if user_scales is not None:
+            self.resolve(user_scales.shape[1], False, None,
+                         [0.0, reference_time / 3.0, reference_time])
+        return self
+
+    @property
+    def perturbation_count(self):
+        """J, the number of fixed matrices (a duration sweep: the drift D_0 among them)."""
+        return 0 if self.offsets is None else self.offsets.shape[1]
+
+    @property
+    def hilbert_size(self):
+        """n of the fixed matrices (None without them, or before a duration sweep is resolved)."""
+        return None if self.perturbations is None else self.perturbations.shape[1]
+
+    def resolve(self, control_count, complex_controls, hilbert_size, times):
+        """The fixed matrices (J, n, n) for a problem with this control count; None for J = 0. A
+        duration sweep forms D_0 = hamiltonian(0, .) here and raises ValueError when hamiltonian
+        depends on time at `times` (structure.probe_hamiltonian's own decision)."""
+        if not self.time_scaled:
+            return self.perturbations
+        from qoc_amd.core import structure
+        if control_count < 1:
+            raise NotImplementedError("a HamiltonianSweep needs at least one control")
+        zero = np.zeros(control_count, dtype=np.complex128 if complex_controls else np.float64)
+        drift = np.asarray(self._source(zero, times[0]), dtype=np.complex128)
+        if drift.ndim != 2 or drift.shape[0] != drift.shape[1]:
+            raise ValueError("hamiltonian returned shape {}, expected a square matrix"
+                             "".format(drift.shape))
+        n = drift.shape[0] if hilbert_size is None else hilbert_size
+        h0, g = structure.probe_hamiltonian(self._source, n, control_count, complex_controls,
+                                            list(times))
+        if h0.shape[0] != 1:
+            raise ValueError(
+                "a duration sweep needs a time-independent hamiltonian: scaling H by T_b / "
+                "reference_time is scaling time only then (hamiltonian(controls, time) depends "
+                "on time)")
+        if not np.all(np.isfinite(h0)):
+            raise ValueError("hamiltonian(0, .) is not finite")
+        extra = self._extra_perturbations
+        if extra is not None and extra.shape[1] != n:
+            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
+                extra.shape[1], n))
+        self.perturbations = h0 if extra is None else np.concatenate([h0, extra], axis=0)
+        return self.perturbations
+
+    def real_channel_scales(self, control_count, complex_controls):
+        """s_bk per real control channel, (B, K_r): the scales as given for real controls, each
+        repeated for Re and Im of a complex control (channels 2k and 2k + 1)."""
+        scales = self.control_scales
+        if scales is None:
+            scales = np.ones((self.seed_count, control_count))
+            if self.time_scaled:
+                scales = scales * self._tau[:, None]
+        if scales.shape[1] != control_count:
+            raise ValueError("control_scales must be (B, control_count) = ({}, {}), got shape {}"
+                             "".format(self.seed_count, control_count, scales.shape))
+        if complex_controls:
+            return np.repeat(scales, 2, axis=1)
+        return scales.copy()
+
+    def member(self, b):
+        """Seed b's system as a plain callable (controls, time) -> (n x n). For a duration sweep
+        that is tau_b * hamiltonian(u, t)."""
+        b = int(b)
+        if not 0 <= b < self.seed_count:
+            raise IndexError("seed {} out of range for {} seeds".format(b, self.seed_count))
+        base, source = self.hamiltonian, self._source
+        scales = None if self.control_scales is None else self.control_scales[b]
+        if scales is None and self.time_scaled:
+            scales = self._tau[b]
+        offsets = None if self.offsets is None else self.offsets[b]
+        fixed = self._extra_perturbations if self.time_scaled else self.perturbations
+        first = 1 if self.time_scaled else 0
+        shift = None
+        if fixed is not None:
+            shift = np.einsum("j,jab->ab", offsets[first:].astype(np.complex128), fixed)
+
+        def hamiltonian(controls, time):
+            u = np.asarray(controls) * scales if scales is not None else controls
+            out = np.asarray(base(u, time), dtype=np.complex128)
+            if source is not None:  # the drift D_0 = hamiltonian(0, .), times tau_b
+                out = out + offsets[0] * np.asarray(
+                    source(np.zeros_like(np.asarray(controls)), time), dtype=np.complex128)
+            return out if shift is None else out + shift
+        return hamiltonian
+
+    def slice(self, lo, hi):
+        """The sweep of seeds lo .. hi - 1 (what a rank of a communicator evaluates)."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= self.seed_count:
+            raise IndexError("slice [{}, {}) out of range for {} seeds (at least one seed)"
+                             "".format(lo, hi, self.seed_count))
+        import copy
+        out = copy.copy(self)
+        for name in ("offsets", "control_scales", "_user_scales", "_user_offsets",
+                     "evolution_times", "_tau"):
+            value = getattr(self, name, None)
+            if value is not None:
+                setattr(out, name, value[lo:hi].copy())
+        out.seed_count = hi - lo
+        return out
+
+    def time_gradients(self, scale_sens, offset_sens):
+        """d error_b / d T_b (B,) of a duration sweep from its sensitivities (the chain rule through
+        tau_b = T_b / reference_time): (sum_k dE/ds_bk s0_bk + sum_j dE/ddelta_bj delta0_bj) /
+        reference_time with s0, delta0 the values before the factor tau_b (delta0 = 1 for D_0).
+        scale_sens :: (B, control_count), offset_sens :: (B, J)."""
+        if not self.time_scaled:
+            raise ValueError("time_gradients belong to a duration sweep "
+                             "(HamiltonianSweep.durations)")
+        scale_sens = np.asarray(scale_sens, dtype=np.float64)
+        offset_sens = np.asarray(offset_sens, dtype=np.float64)
+        s0 = np.ones_like(scale_sens) if self._user_scales is None else self._user_scales
+        if scale_sens.shape != s0.shape or offset_sens.shape != self._user_offsets.shape:
+            raise ValueError("sensitivities must be (B, control_count) and (B, J) = {}, got {} "
+                             "and {}".format(self._user_offsets.shape, scale_sens.shape,
+                                             offset_sens.shape))
+        return (np.sum(scale_sens * s0, axis=1)
+                + np.sum(offset_sens * self._user_offsets, axis=1)) / self.reference_time
+
+    def __repr__(self):
+        return "HamiltonianSweep({!r}, {} seeds, {} fixed matrices{})".format(
+            self._source if self._source is not None else self.hamiltonian, self.seed_count,
+            self.perturbation_count, ", durations" if self.time_scaled else "")
