@@ -378,7 +378,8 @@ int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, con
  *     are set.
  * qocx_lindblad_ensemble_download_members: the unweighted cost of every item of the last evaluation
  * (qocx_eval_lindblad or qocx_eval_lindblad_resident), [B][M]; QOCX_ERR_STATE without an ensemble.
- * Not built: per-member operators or targets, gradients with respect to delta or to the rates below.
+ * Not built: per-member operators or targets, gradients with respect to delta or to the rates below
+ * (a sweep has them: qocx_lindblad_sweep_download_sensitivities).
  */
 int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
                                const double* offsets, const double* weights);
@@ -401,6 +402,54 @@ int qocx_lindblad_ensemble_download_members(qocx_ctx* ctx, double* cost_out);
  * controls. */
 int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t operators,
                                      const double* rate_scales);
+
+/*
+ * Lindblad sweeps: the twin of qocx_set_sweep on the Lindblad path - B seeds, each an open system of its
+ * own with a pulse of its own (a gate-time sweep under T1 / T2, a calibration family). Call after
+ * qocx_set_lindblad_problem, whose LAST `fixed` = J control channels are the fixed matrices D_j;
+ * K_r = control_count - J channels remain for the seeds. Item b IS seed b, the plain problem on
+ *     r_b[j][k] = s_bk u_b[j][k] (k < K_r),   r_b[j][K_r + i] = delta_bi (every knot)
+ * and, with rate_scales, with the rates gamma_bl = rate_scales[b][l] * dissipators[l] (one product, one
+ * rounding): its control-free generators, rates and norm bound are built by the function that builds the
+ * plain problem's, so seed b is bit for bit the plain (K_r + J)-channel problem set with dissipators =
+ * rate_scales[b] . dissipators on [s_b . u_b, delta_b] - cost, gradient (after the one product with
+ * s_bk), densities and the sub-division count, which seed b picks from its own control maxima and bound.
+ * A duration T_b = tau_b T is delta_b0 = tau_b on D_0 = H0 (a problem with H0 = 0), s_bk = tau_b s_k and
+ * rate_scales[b][l] = tau_b c_bl: scaling the whole Lindbladian is scaling time.
+ *   scales [seeds][K_r] (NULL: all 1)   offsets [seeds][J] (NULL exactly when J = 0)
+ *   rate_scales [seeds][L], L = operator_count (NULL: every seed takes the problem's rates, and the
+ *   kernels of a run without rates are launched)
+ * QOCX_ERR_ARG unless 1 <= seeds <= 1024 (the rates tables' member limit), 0 <= J < control_count, every
+ * entry is finite and every rate factor >= 0. QOCX_ERR_STATE while an ensemble is set (and
+ * qocx_lindblad_set_ensemble / _set_ensemble_rates while a sweep is set), for rate_scales on a problem
+ * with stage tables (fixed_subdivision > 0), and while density cotangents are set (they are refused with
+ * a sweep set). A new problem clears the sweep; setting one clears the resident controls, the results
+ * and the costs of the controls (qocx_set_control_costs comes after it, for K_r channels).
+ * With a sweep set qocx_eval_lindblad, qocx_lindblad_upload_controls, qocx_eval_lindblad_resident,
+ * qocx_lindblad_download_results / _costs, qocx_lindblad_opt_* (the basis, complex and L-BFGS calls
+ * included) and qocx_set_control_costs act on the B seeds and their K_r channels; any other batch size
+ * is QOCX_ERR_ARG. Final densities are [B][S][n][n], without a member axis.
+ *
+ * qocx_lindblad_sweep_download_sensitivities, after an evaluation with gradients whose seed controls
+ * still stand (QOCX_ERR_STATE otherwise); each output may be NULL:
+ *     scales_out [B][K_r]  dE_b / ds_bk     = sum_j u_b[j][k] dc_b / dr[j][k]
+ *     offsets_out [B][J]   dE_b / ddelta_bi = sum_j dc_b / dr[j][K_r + i]
+ *   in the summation order of qocx_sweep.hip (its kernels run here as they are), and
+ *     rates_out [B][L]     dE_b / dc_bl, c_bl the factor of seed b's l-th rate (1 without rate_scales):
+ *   the exact derivative of the discrete scheme on its frozen grid (qocx_lindblad_ratesens.hip, which
+ *   states its summation order). rates_out is QOCX_ERR_STATE unless the evaluation was asked for them -
+ *   qocx_lindblad_sweep_want_rate_sensitivities(ctx, 1) before it; the flag is cleared by a new problem
+ *   or sweep - and EVERY piece of it ran two-sided: one final target-density cost and no step cost, 1 to 4
+ *   operators, no stage tables, stage values that fit the memory (a piece that recomputes them has no
+ *   stage cotangents to contract), and the knobs lindblad_two_sided (and lindblad_4t for n > 16) on.
+ * Not built: rate sensitivities on the classic one-launch adjoint; per-seed operators, targets or
+ * densities; optimising the duration itself.
+ */
+int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* scales,
+                            const double* offsets, const double* rate_scales);
+int qocx_lindblad_sweep_want_rate_sensitivities(qocx_ctx* ctx, int32_t on);
+int qocx_lindblad_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out,
+                                               double* rates_out);
 
 /* Per-kernel timing, measured with HIP events on the launch streams.
  * enable: 0 off, 1 every launch, 2 + k the launches of kernel k only (two events per timed launch

@@ -43,7 +43,9 @@ class BatchResult(object):
         # with a ControlBasis: per seed, the coefficients (P x control_count) behind best_controls
         self.best_coefficients = [None] * seed_count
         # with a HamiltonianSweep: dict(control_scales (B x control_count), offsets (B x J)[,
-        # evolution_time_gradients (B)]) at every seed's best controls
+        # evolution_time_gradients (B)]) at every seed's best controls; a LindbladSweep adds
+        # rate_scales (B x L), which - with evolution_time_gradients - is None where the
+        # sensitivity evaluation did not run two-sided
         self.sweep_sensitivities = None
 
     @property
@@ -366,10 +368,19 @@ def sweep_sensitivities(evaluator, result):
     template = result.best_controls[int(np.nonzero(have)[0][0])]
     controls = np.stack([c if c is not None else np.zeros_like(template)
                          for c in result.best_controls])
-    evaluator.evaluate_batch(controls, want_grad=True)
-    out = evaluator.sweep_sensitivities()
+    # (the Lindblad path: rate sensitivities are asked for in this one evaluation only)
+    want_rates = getattr(evaluator, "want_rate_sensitivities", None)
+    if want_rates is not None:
+        want_rates(True)
+    try:
+        evaluator.evaluate_batch(controls, want_grad=True)
+        out = evaluator.sweep_sensitivities()
+    finally:
+        if want_rates is not None:
+            want_rates(False)
     for value in out.values():
-        value[~have] = np.nan
+        if value is not None:
+            value[~have] = np.nan
     result.sweep_sensitivities = out
 
 

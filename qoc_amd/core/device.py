@@ -11,7 +11,7 @@ import numpy as np
 
 from qoc_amd.core import structure
 from qoc_amd.models.policies import InterpolationPolicy, MagnusPolicy
-from qoc_amd.standard.hamiltonians import (HamiltonianEnsemble, HamiltonianSweep,
+from qoc_amd.standard.hamiltonians import (HamiltonianEnsemble, HamiltonianSweep, LindbladSweep,
                                             QuadraticHamiltonian)
 
 def make_backend(device=-1):
@@ -70,10 +70,28 @@ def reject_costless_lindblad_ensemble(hamiltonian, costs):
             "weighted sum of the members' costs (costs is empty)")
 
 
-def reject_sweep(hamiltonian, where, hint=""):
-    """The entry points that do not take a HamiltonianSweep say so by name."""
+def reject_sweep(hamiltonian, where, hint="", lindblad_sweep_ok=False):
+    """The entry points that do not take a HamiltonianSweep say so by name. lindblad_sweep_ok: this
+    one takes a LindbladSweep (the batch entry points of the Lindblad path)."""
+    if lindblad_sweep_ok and isinstance(hamiltonian, LindbladSweep):
+        return
     if isinstance(hamiltonian, HamiltonianSweep):
-        raise NotImplementedError("a HamiltonianSweep is not evaluated by {}{}".format(where, hint))
+        raise NotImplementedError("a {} is not evaluated by {}{}".format(
+            type(hamiltonian).__name__, where, hint))
+
+
+LINDBLAD_SWEEP_HINT = (": a duration there scales the dissipation rates as well, which a plain "
+                       "HamiltonianSweep does not state (a LindbladSweep does: pass one to "
+                       "grape_lindblad_discrete_batch or LindbladEvaluator)")
+
+
+def reject_lindblad_sweep(hamiltonian):
+    """The Schroedinger entry points: a LindbladSweep scales dissipation rates, and there are none."""
+    if isinstance(hamiltonian, LindbladSweep):
+        raise ValueError(
+            "a LindbladSweep scales the dissipation rates of lindblad_data: the Schroedinger path "
+            "has none, so there is nothing to scale (use the Lindblad entry points, or a "
+            "HamiltonianSweep)")
 
 
 def user_states_bar(cost, controls, states, step):
@@ -150,6 +168,7 @@ class _Evaluator(object):
     sweep = None              # the HamiltonianSweep being evaluated
     ensemble_setter = "set_ensemble"                 # the backend's entry points for one
     ensemble_member_costs = "ensemble_member_costs"
+    sweep_setter = "set_sweep"                       # ... and for a sweep
 
     # -- Hamiltonian ensembles ------------------------------------------------------------------
     def _ensemble_base(self, ensemble, control_count, complex_controls, backend,
@@ -196,6 +215,46 @@ class _Evaluator(object):
         """The unweighted device cost of every member of every seed of the last evaluation,
         (B, M)."""
         return getattr(self.backend, self.ensemble_member_costs)()
+
+    # -- Hamiltonian sweeps -----------------------------------------------------------------------
+    def _sweep_base(self, sweep, control_count, complex_controls, backend, times):
+        """Checks a sweep against this problem and the backend, keeps it with the arguments of the
+        backend's setter (self._sweep_args) and its fixed matrices, and returns its base."""
+        base = sweep.hamiltonian
+        if control_count == 0:
+            raise NotImplementedError("a HamiltonianSweep needs at least one control "
+                                      "(control_count = 0)")
+        if isinstance(base, (HamiltonianEnsemble, HamiltonianSweep, QuadraticHamiltonian)):
+            raise NotImplementedError(
+                "a HamiltonianSweep needs a plain base hamiltonian linear in the controls (sweep x "
+                "ensemble and sweep x QuadraticHamiltonian are not evaluated), got {!r}"
+                "".format(base))
+        if not hasattr(backend, self.sweep_setter):
+            raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian sweeps "
+                                      "(no {})".format(backend, self.sweep_setter))
+        matrices = sweep.resolve(control_count, complex_controls, self.hilbert_size, times)
+        if matrices is not None and matrices.shape[1] != self.hilbert_size:
+            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
+                matrices.shape[1], self.hilbert_size))
+        self.sweep = sweep
+        self._sweep_matrices = matrices
+        self._sweep_args = (sweep.real_channel_scales(control_count, complex_controls),
+                            sweep.offsets)
+        return base
+
+    def _reject_sweep_costs(self):
+        if self.opaque_costs:
+            raise NotImplementedError(
+                "a HamiltonianSweep takes costs evaluated on the device (with a "
+                "device_descriptor()) and costs of the controls alone; {} is neither (user costs "
+                "without a device descriptor)".format(self.opaque_costs[0]))
+        if self.sweep.time_scaled:
+            from qoc_amd.standard.costs import ControlBandwidthMax
+            for cost in self.host_costs:
+                if isinstance(cost, ControlBandwidthMax):
+                    raise NotImplementedError(
+                        "ControlBandwidthMax with a duration sweep: its frequency bins depend on "
+                        "the evolution time, which differs from seed to seed")
 
     def _triage_costs(self, item_count):
         """Splits self.costs into device_costs (they have a device_descriptor(); returns those
@@ -476,6 +535,7 @@ class SchroedingerEvaluator(_Evaluator):
         # (qocx_set_sweep); evaluations take exactly B control arrays and return B errors and
         # gradients, and sweep_sensitivities() the derivatives with respect to the tables.
         self.sweep = None
+        reject_lindblad_sweep(hamiltonian)
         if isinstance(hamiltonian, HamiltonianSweep):
             if backend is None:
                 backend = make_backend()
@@ -563,45 +623,6 @@ class SchroedingerEvaluator(_Evaluator):
             self.backend.set_sweep(*self._sweep_args)
 
     # -- Hamiltonian sweeps -----------------------------------------------------------------------
-    def _sweep_base(self, sweep, control_count, complex_controls, backend, times):
-        """Checks a sweep against this problem and the backend, keeps it with the arguments of the
-        backend's setter (self._sweep_args) and its fixed matrices, and returns its base."""
-        base = sweep.hamiltonian
-        if control_count == 0:
-            raise NotImplementedError("a HamiltonianSweep needs at least one control "
-                                      "(control_count = 0)")
-        if isinstance(base, (HamiltonianEnsemble, HamiltonianSweep, QuadraticHamiltonian)):
-            raise NotImplementedError(
-                "a HamiltonianSweep needs a plain base hamiltonian linear in the controls (sweep x "
-                "ensemble and sweep x QuadraticHamiltonian are not evaluated), got {!r}"
-                "".format(base))
-        if not hasattr(backend, "set_sweep"):
-            raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian sweeps "
-                                      "(no set_sweep)".format(backend))
-        matrices = sweep.resolve(control_count, complex_controls, self.hilbert_size, times)
-        if matrices is not None and matrices.shape[1] != self.hilbert_size:
-            raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
-                matrices.shape[1], self.hilbert_size))
-        self.sweep = sweep
-        self._sweep_matrices = matrices
-        self._sweep_args = (sweep.real_channel_scales(control_count, complex_controls),
-                            sweep.offsets)
-        return base
-
-    def _reject_sweep_costs(self):
-        if self.opaque_costs:
-            raise NotImplementedError(
-                "a HamiltonianSweep takes costs evaluated on the device (with a "
-                "device_descriptor()) and costs of the controls alone; {} is neither (user costs "
-                "without a device descriptor)".format(self.opaque_costs[0]))
-        if self.sweep.time_scaled:
-            from qoc_amd.standard.costs import ControlBandwidthMax
-            for cost in self.host_costs:
-                if isinstance(cost, ControlBandwidthMax):
-                    raise NotImplementedError(
-                        "ControlBandwidthMax with a duration sweep: its frequency bins depend on "
-                        "the evolution time, which differs from seed to seed")
-
     def sweep_sensitivities(self):
         """Of the last evaluation with gradients: dict(control_scales = d error_b / d s_bk
         (B x control_count; a complex control's two channels added), offsets = d error_b /
@@ -700,6 +721,7 @@ class LindbladEvaluator(_Evaluator):
     ensemble_setter = "set_lindblad_ensemble"
     ensemble_member_costs = "lindblad_ensemble_member_costs"
     ensemble_rates_setter = "set_lindblad_ensemble_rates"
+    sweep_setter = "set_lindblad_sweep"
     _ensemble_base_message = (
         "a HamiltonianEnsemble on the Lindblad path needs a base hamiltonian linear in the "
         "controls (the tangent and frozen-controls routes evaluate one control array at a "
@@ -728,13 +750,26 @@ class LindbladEvaluator(_Evaluator):
         with the rates c_m * dissipators (qocx_lindblad_set_ensemble_rates). Those need a
         time-independent system: with a time-dependent hamiltonian or lindblad_data the engine
         holds the control-free generator in per-stage tables, one set, not M.
+
+        hamiltonian may be a LindbladSweep whose base is linear in the controls: its fixed
+        matrices D_j go to the engine as J constant channels behind the K_r real channels of the
+        seeds (K_r + J <= 8), seed b is item b with scales, offsets and rate factors of its own
+        (qocx_lindblad_set_sweep), evaluations take exactly B control arrays and return B errors,
+        gradients and final densities (B x S x n x n, no member axis), and sweep_sensitivities()
+        the derivatives with respect to the tables. costs may be empty. With rates of its own
+        (rate_scales, or any duration sweep) the system must be time independent, as above.
         """
         if not isinstance(interpolation_policy, InterpolationPolicy):
             raise NotImplementedError("This operation does not yet support the interpolation "
                                       "policy {}.".format(interpolation_policy))
         self.interpolation_policy = interpolation_policy
-        reject_sweep(hamiltonian, "the Lindblad path",
-                     ": a duration there scales the dissipation rates as well, which is not built")
+        reject_sweep(hamiltonian, "the Lindblad path", LINDBLAD_SWEEP_HINT, lindblad_sweep_ok=True)
+        sweep = hamiltonian if isinstance(hamiltonian, LindbladSweep) else None
+        if sweep is not None and frozen_controls is not None:
+            raise NotImplementedError(
+                "a LindbladSweep needs a base hamiltonian linear in the controls (the frozen-"
+                "controls route evaluates one control array at a time)")
+        self.sweep = None
         ensemble = hamiltonian if isinstance(hamiltonian, HamiltonianEnsemble) else None
         if ensemble is not None:
             reject_costless_lindblad_ensemble(ensemble, costs)
@@ -799,6 +834,25 @@ class LindbladEvaluator(_Evaluator):
             1 if interpolation_policy == InterpolationPolicy.PIECEWISE_CONSTANT else 0)
         self._coarse_times = self.backend.lindblad_stage_times(
             evolution_time, system_eval_count, self._stage_knots, self.kr, 1)
+        if sweep is not None:
+            try:
+                hamiltonian = self._sweep_base(sweep, control_count, complex_controls,
+                                               self.backend, list(self._coarse_times))
+            except ValueError as exc:
+                if sweep.time_scaled and "time-independent" in str(exc):
+                    # (the sweep's own probe; here it is the rates' refusal, as _check_rate_scales)
+                    raise NotImplementedError(
+                        "rate_scales need a time-independent system (a duration sweep scales every "
+                        "seed's rates): the hamiltonian (base or drives) is time dependent, so the "
+                        "engine holds the control-free generator in per-stage tables "
+                        "(fixed_subdivision > 0) - one set, not one per seed")
+                raise
+            self.device_k = self.kr + sweep.perturbation_count
+            if self.device_k > self.MAX_CHANNELS:
+                raise NotImplementedError(
+                    "the Lindblad engine takes up to {} real control channels: this sweep needs "
+                    "K_r + J = {} + {}".format(self.MAX_CHANNELS, self.kr,
+                                               sweep.perturbation_count))
         # A hamiltonian(controls, time) that is not linear in the controls (the reference takes any
         # callable, lindbladdiscrete.py:486-489): the engine gets the TANGENT of the callable at the
         # control array being evaluated, sampled at the integrator's stage times
@@ -814,6 +868,10 @@ class LindbladEvaluator(_Evaluator):
         except structure.NonLinearHamiltonianError:
             if self.ensemble is not None:
                 raise NotImplementedError(self._ensemble_base_message.format(hamiltonian))
+            if self.sweep is not None:
+                raise NotImplementedError(
+                    "a LindbladSweep needs a base hamiltonian linear in the controls (the tangent "
+                    "route evaluates one control array at a time), got {!r}".format(hamiltonian))
             if frozen_controls is not None or control_count == 0:
                 raise
             self.linearized_hamiltonian = hamiltonian
@@ -821,13 +879,22 @@ class LindbladEvaluator(_Evaluator):
             self.time_dependent = True
             hamiltonian = None
         if self.ensemble is not None and self.ensemble.rate_scales is not None:
-            self._check_rate_scales(dissipators, data_dependent)
+            self._check_rate_scales(self.ensemble.rate_scales, dissipators, data_dependent,
+                                    "(M, L)", "member")
+        if self.sweep is not None:
+            rates = self.sweep.resolved_rate_scales(0 if dissipators is None else len(dissipators))
+            if rates is not None:
+                self._check_rate_scales(rates, dissipators, data_dependent, "(B, L)", "seed")
+            self._sweep_args = self._sweep_args + (rates,)
         # a time-dependent lindblad_data is sampled at the stage times like the Hamiltonian
         self._lindblad_data = lindblad_data if data_dependent else None
         self.cotangent_shape = (self.density_count, self.hilbert_size, self.hilbert_size)
         descriptors = self._triage_costs(self.density_count)
         if self.ensemble is not None:
             self._reject_opaque_ensemble_costs()
+            g = self._append_perturbations(np.asarray(g)[None])[0]
+        if self.sweep is not None:
+            self._reject_sweep_costs()
             g = self._append_perturbations(np.asarray(g)[None])[0]
         self._problem_args = (self.hilbert_size, self.density_count, self.device_k,
                               control_eval_count, system_eval_count, evolution_time, h0, g,
@@ -849,38 +916,45 @@ class LindbladEvaluator(_Evaluator):
             self._set_time_dependent_problem(bounds)
 
     def _set_problem(self, **tables):
-        """The problem (with its stage tables, if any) to the backend, then the ensemble: a new
-        problem clears it."""
+        """The problem (with its stage tables, if any) to the backend, then the ensemble or the
+        sweep: a new problem clears them."""
         self.backend.set_lindblad_problem(*self._problem_args, **tables, **self._problem_kw)
+        if self.sweep is not None:
+            getattr(self.backend, self.sweep_setter)(*self._sweep_args)
         if self.ensemble is not None:
             self.backend.set_lindblad_ensemble(*self._ensemble_args)
             if self.ensemble.rate_scales is not None:
                 getattr(self.backend, self.ensemble_rates_setter)(self.ensemble.rate_scales)
 
-    def _check_rate_scales(self, dissipators, data_dependent):
-        """rate_scales against the probed lindblad_data, before the backend sees a problem: (M, L)
-        for its L operators, and a time-independent system."""
-        rates = self.ensemble.rate_scales
+    def _check_rate_scales(self, rates, dissipators, data_dependent, shape, each):
+        """rate_scales (an ensemble's (M, L), a sweep's (B, L)) against the probed lindblad_data,
+        before the backend sees a problem: L operators, and a time-independent system."""
         L = 0 if dissipators is None else len(dissipators)
         if rates.shape[1] != L:
-            raise ValueError("rate_scales must be (M, L) with L = {} Lindblad operators of "
-                             "lindblad_data, got shape {}".format(L, rates.shape))
+            raise ValueError("rate_scales must be {} with L = {} Lindblad operators of "
+                             "lindblad_data, got shape {}".format(shape, L, rates.shape))
         if self.time_dependent:
             raise NotImplementedError(
                 "rate_scales need a time-independent system: {} is time dependent, so the engine "
                 "holds the control-free generator in per-stage tables (fixed_subdivision > 0) - "
-                "one set, not one per member".format(
-                    "lindblad_data" if data_dependent else "the hamiltonian (base or drives)"))
+                "one set, not one per {}".format(
+                    "lindblad_data" if data_dependent else "the hamiltonian (base or drives)",
+                    each))
 
     def _item_bounds(self, bounds):
         """Bounds of the seeds' K_r channels -> bounds of the evaluated channels: with an ensemble
-        those of the items, bound_k max_m |s_mk| and max_m |delta_mj| for the J fixed channels."""
-        if self.ensemble is None:
+        those of the items, bound_k max_m |s_mk| and max_m |delta_mj| for the J fixed channels (a
+        sweep: the maxima over its seeds)."""
+        if self.sweep is not None:
+            scales, offsets = self._sweep_args[0], self._sweep_args[1]
+        elif self.ensemble is not None:
+            scales, offsets = self._ensemble_scales, self.ensemble.offsets
+        else:
             return bounds
-        scaled = np.asarray(bounds, dtype=np.float64) * np.max(np.abs(self._ensemble_scales), axis=0)
-        if self.ensemble.offsets is None:
+        scaled = np.asarray(bounds, dtype=np.float64) * np.max(np.abs(scales), axis=0)
+        if offsets is None:
             return scaled
-        return np.concatenate([scaled, np.max(np.abs(self.ensemble.offsets), axis=0)])
+        return np.concatenate([scaled, np.max(np.abs(offsets), axis=0)])
 
     def _set_stage_tables(self, coarse_samples, bounds, sample):
         """The tail of both table builders. coarse_samples :: (h0, g) on the coarsest stage grid:
@@ -920,7 +994,7 @@ class LindbladEvaluator(_Evaluator):
             repeated in every table of g (none where g is constant: the problem's own g has
             them)."""
             h, g = tables
-            if self.ensemble is None or g is None:
+            if (self.ensemble is None and self.sweep is None) or g is None:
                 return h, g
             return h, self._append_perturbations(g)
         if self._coarse_samples is None and self._hamiltonian is None:
@@ -990,6 +1064,37 @@ class LindbladEvaluator(_Evaluator):
         """_Evaluator.evaluate_batch; the step states are densities [B x N x S x n x n] (with an
         ensemble a member axis M follows B, in the final densities too)."""
         return _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_densities)
+
+    # -- Lindblad sweeps ------------------------------------------------------------------------
+    def want_rate_sensitivities(self, on):
+        """Ask the evaluations from here on for the sweep's rate sensitivities (one more kernel
+        launch per piece of an evaluation with gradients); sweep_sensitivities() returns them."""
+        if hasattr(self.backend, "lindblad_sweep_want_rate_sensitivities"):
+            self.backend.lindblad_sweep_want_rate_sensitivities(bool(on))
+
+    def sweep_sensitivities(self):
+        """Of the last evaluation with gradients: dict(control_scales = d error_b / d s_bk
+        (B x control_count; a complex control's two channels added), offsets = d error_b /
+        d delta_bj (B x J), rate_scales = d error_b / d c_bl (B x L)), and for a duration sweep
+        evolution_time_gradients = d error_b / d T_b (B). Costs of the controls alone do not depend
+        on the tables and do not enter. rate_scales, and with it evolution_time_gradients, is None
+        unless the evaluation was asked for it (want_rate_sensitivities) and ran two-sided in
+        every piece: one final TargetDensityInfidelity and no other cost, 1 to 4 Lindblad
+        operators, a time-independent system, stage values that fit the device memory. Without
+        Lindblad operators rate_scales is (B x 0) and the time gradients are the Hamiltonian part."""
+        scales, offsets, rates = self.backend.lindblad_sweep_sensitivities()
+        scales, offsets = np.asarray(scales), np.asarray(offsets)
+        if self.complex_controls:
+            scales = scales[:, 0::2] + scales[:, 1::2]
+        if rates is None and len(self._problem_args[8] if self._problem_args[8] is not None
+                                 else ()) == 0:
+            rates = np.zeros((scales.shape[0], 0))
+        out = dict(control_scales=scales, offsets=offsets,
+                   rate_scales=None if rates is None else np.asarray(rates))
+        if self.sweep.time_scaled:
+            out["evolution_time_gradients"] = (
+                None if rates is None else self.sweep.time_gradients(scales, offsets, rates))
+        return out
 
     def evaluate(self, controls, want_grad=True, want_step_densities=False):
         if self._cost_controls is not None:  # frozen controls: the device's dummy control is zero

@@ -16,23 +16,32 @@ from qoc_amd.core import batch
 from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
                                  initialize_coefficients, initialize_controls,
                                  reject_basis_save, strip_controls)
-from qoc_amd.core.device import (LindbladEvaluator, reject_costless_lindblad_ensemble,
-                                 reject_sweep)
+from qoc_amd.core.device import (LINDBLAD_SWEEP_HINT, LindbladEvaluator,
+                                 reject_costless_lindblad_ensemble, reject_sweep)
 from qoc_amd.core.structure import NonLinearHamiltonianError
 from qoc_amd.engine import PATH_LINDBLAD
 from qoc_amd.models import (Dummy, EvolveLindbladDiscreteState, EvolveLindbladResult,
                             GrapeLindbladDiscreteState, GrapeLindbladResult,
                             InterpolationPolicy)
-from qoc_amd.standard.hamiltonians import HamiltonianEnsemble
+from qoc_amd.standard.hamiltonians import HamiltonianEnsemble, LindbladSweep
 from qoc_amd.standard.optimizers import Adam
 
 
-def _check_ensemble(hamiltonian, costs, save_file_path=None):
+_SWEEP_HINT = (": it is B open systems with controls of their own - pass it to "
+               "grape_lindblad_discrete_batch, or evaluate one of its systems as sweep.member(b) "
+               "with sweep.member_lindblad_data(b, lindblad_data); save files go with these "
+               "entry points and are not written for a sweep")
+
+
+def _check_ensemble(hamiltonian, costs, save_file_path=None, where=None):
     """Before any save file is touched and before a backend is made: a HamiltonianEnsemble on the
     Lindblad path needs at least one cost (its error is the weighted sum of the members' costs)
-    and writes no save file."""
-    reject_sweep(hamiltonian, "the Lindblad entry points",
-                 ": a duration there scales the dissipation rates as well, which is not built")
+    and writes no save file. A plain HamiltonianSweep is refused everywhere on this path, a
+    LindbladSweep by the single-problem entry points (`where` names one)."""
+    if where is not None and isinstance(hamiltonian, LindbladSweep):
+        reject_sweep(hamiltonian, where, _SWEEP_HINT)
+    reject_sweep(hamiltonian, "the Lindblad entry points", LINDBLAD_SWEEP_HINT,
+                 lindblad_sweep_ok=True)
     if not isinstance(hamiltonian, HamiltonianEnsemble):
         return
     reject_costless_lindblad_ensemble(hamiltonian, costs)
@@ -72,7 +81,7 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
     dissipation rates rate_scales[m] * dissipators of lindblad_data (an uncertain T1 / T2); that
     needs a hamiltonian and a lindblad_data without explicit time dependence.
     """
-    _check_ensemble(hamiltonian, costs, save_file_path)
+    _check_ensemble(hamiltonian, costs, save_file_path, "evolve_lindblad_discrete")
     if controls is not None:
         controls = np.asarray(controls)
         control_eval_count, control_count = controls.shape[0], controls.shape[1]
@@ -131,7 +140,7 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
     holds each member's unweighted device cost at best_controls (one forward evaluation after the
     loop).
     """
-    _check_ensemble(hamiltonian, costs, save_file_path)
+    _check_ensemble(hamiltonian, costs, save_file_path, "grape_lindblad_discrete")
     reject_basis_save(control_basis, save_file_path)
     coefficients = None
     if control_basis is not None:
@@ -251,9 +260,26 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     weighted sums, the final densities have a member axis, and member_errors[b] holds seed b's
     unweighted member costs at its best controls (one forward evaluation of all seeds after the
     loop).
+    With a LindbladSweep (qoc_amd.standard) of B seeds, B = len(initial_controls) over all ranks,
+    seed b is optimised on the sweep's open system b - its own scales, offsets and rate factors
+    (with a communicator every rank sets its block, sweep.slice) - on either route;
+    max_control_norms bound the seeds' own controls, costs may be empty, and the final densities
+    have no member axis. The result's sweep_sensitivities holds d error_b / d control_scales
+    (B x control_count), / d offsets (B x J) and / d rate_scales (B x L) at the seeds' best
+    controls (one evaluation with gradients after the loop), and for a duration sweep
+    evolution_time_gradients (B). The last two are None unless that evaluation ran two-sided: ONE
+    cost, a final TargetDensityInfidelity (no step cost), 1 to 4 Lindblad operators, a
+    time-independent system and stage values that fit the device memory. Refused: user costs
+    without a device descriptor, ControlBandwidthMax with a duration sweep, a QuadraticHamiltonian,
+    ensemble, sweep or non-linear base, K_r + J > 8, and - with rates of its own, so for every
+    duration sweep - a time-dependent hamiltonian or lindblad_data.
     Returns GrapeLindbladBatchResult.
     """
     _check_ensemble(hamiltonian, costs)
+    if isinstance(hamiltonian, LindbladSweep):
+        initial_controls = np.asarray(initial_controls)
+        if initial_controls.ndim == 3:  # (prepare_seeds reports any other shape)
+            hamiltonian = batch.rank_sweep(hamiltonian, initial_controls.shape[0], comm)
     comm, pstate, params = batch.prepare_seeds(
         initial_controls, complex_controls, control_count, control_eval_count, evolution_time,
         max_control_norms, impose_control_conditions, comm, control_basis)
@@ -274,4 +300,6 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
         out = batch.run_batch_host(evaluator, stepper, optimizer, params, pstate, *run)
     if evaluator.ensemble is not None:
         _ensemble_member_errors(evaluator, out)
+    if evaluator.sweep is not None:
+        batch.sweep_sensitivities(evaluator, out)
     return out

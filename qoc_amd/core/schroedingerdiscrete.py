@@ -13,7 +13,7 @@ from qoc_amd.core import batch
 from qoc_amd.core.common import (_coefficients_of, _cost_format, _param_gradient,
                                  initialize_coefficients, initialize_controls,
                                  reject_basis_save, strip_controls)
-from qoc_amd.core.device import SchroedingerEvaluator, reject_sweep
+from qoc_amd.core.device import SchroedingerEvaluator, reject_lindblad_sweep, reject_sweep
 from qoc_amd.engine import PATH_SCHROEDINGER
 from qoc_amd.models import (Dummy, EvolveSchroedingerDiscreteState, EvolveSchroedingerResult,
                             GrapeSchroedingerDiscreteState, GrapeSchroedingerResult,
@@ -50,6 +50,7 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
     member axis (M x state_count x n x 1) and the result's member_errors holds each member's
     unweighted device cost.
     """
+    reject_lindblad_sweep(hamiltonian)
     reject_sweep(hamiltonian, "evolve_schroedinger_discrete", _SWEEP_HINT)
     _check_ensemble_save(hamiltonian, save_file_path)
     if controls is not None:
@@ -103,6 +104,7 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     has a member axis, and member_errors holds each member's unweighted device cost at
     best_controls (one forward evaluation after the loop).
     """
+    reject_lindblad_sweep(hamiltonian)
     reject_sweep(hamiltonian, "grape_schroedinger_discrete", _SWEEP_HINT)
     _check_ensemble_save(hamiltonian, save_file_path)
     reject_basis_save(control_basis, save_file_path)
@@ -238,6 +240,7 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     ControlBandwidthMax with a duration sweep, are refused.
     Returns GrapeSchroedingerBatchResult.
     """
+    reject_lindblad_sweep(hamiltonian)
     if isinstance(hamiltonian, HamiltonianSweep):
         initial_controls = np.asarray(initial_controls)
         if initial_controls.ndim == 3:  # (prepare_seeds reports any other shape)

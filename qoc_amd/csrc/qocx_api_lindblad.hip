@@ -504,6 +504,8 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.ens_M = lb.ens_J = lb.ens_Kr = 0;  // ... and so does the ensemble, with its rates
     lb.ens_members_B = 0;
     lb.ens_rates = false;
+    lb.swp_B = 0;  // ... and the sweep
+    lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
     return 0;
 }
 
@@ -512,6 +514,8 @@ int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, co
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
     if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set (qocx_set_lindblad_problem first)");
+    if (lb.swp_B > 0)
+        return fail(QOCX_ERR_STATE, "a sweep is set (qocx_lindblad_set_sweep): a problem takes a sweep or an ensemble");
     if (members < 1 || members > 1024) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
     if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
     // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
@@ -551,34 +555,15 @@ int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, co
     return 0;
 }
 
-int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t operators, const double* rate_scales) {
-    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+extern "C++" {
+namespace {
+
+// The rates tables of `count` members (an ensemble's members, a sweep's seeds) from rate_scales [count][L]:
+// member m is the control-free part of the plain problem with gamma_mi = c_mi * gamma_i (one product, one
+// rounding); [count][4] dumps A0L, A0R, A0L^H, A0R^H and [count][L'] rates, L' with the zero operator of pad_op
+int build_rate_tables(qocx_ctx* ctx, int count, const double* rate_scales) {
     auto& lb = ctx->lb;
-    if (!lb.has_problem || lb.ens_M == 0)
-        return fail(QOCX_ERR_STATE, "no Lindblad ensemble set (qocx_lindblad_set_ensemble first)");
-    if (lb.fixed_ksub > 0)
-        return fail(QOCX_ERR_STATE, "per-member rates need a static problem: this one was set with stage tables "
-                                    "(fixed_subdivision > 0), which hold one control-free generator per stage");
-    auto invalidate = [&] {
-        lb.ens_members_B = 0;
-        lb.have_results = false;
-        lb.res_B = lb.ms.batch = 0;
-        lb.res_have_results = false;
-    };
-    if (!rate_scales) {
-        lb.ens_rates = false;
-        invalidate();
-        return 0;
-    }
-    const int M = lb.ens_M, L = lb.nops, n = lb.n;
-    if (members != M) return fail(QOCX_ERR_ARG, "rate_scales: members differs from the ensemble's");
-    if (operators != L) return fail(QOCX_ERR_ARG, "rate_scales: operators differs from the problem's operator_count");
-    for (size_t e = 0; e < (size_t)M * L; ++e)
-        if (!std::isfinite(rate_scales[e]) || !(rate_scales[e] >= 0))
-            return fail(QOCX_ERR_ARG, "rate_scales must be finite and >= 0");
-    HIP_TRY(hipSetDevice(ctx->device));
-    // member m: the control-free part of the plain problem with gamma_mi = c_mi * gamma_i (one product, one
-    // rounding); [M][4] dumps A0L, A0R, A0L^H, A0R^H and [M][L'] rates, L' with the zero operator of pad_op
+    const int M = count, L = lb.nops, n = lb.n;
     const size_t md = dump_elems(n), Lp = lb.gammas_h.size();
     std::vector<double2> img((size_t)M * 4 * md);
     std::vector<double> gam((size_t)M * std::max<size_t>(Lp, 1), 0.0);
@@ -595,8 +580,112 @@ int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t ope
         lb.rate_l0_norm[m] = cf.l0_norm;
     }
     if (lb.rate_a0.upload(img, ctx->stream) || lb.rate_gammas.upload(gam, ctx->stream)) return QOCX_ERR_HIP;
+    return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t operators, const double* rate_scales) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.ens_M == 0 || lb.swp_B > 0)
+        return fail(QOCX_ERR_STATE, "no Lindblad ensemble set (qocx_lindblad_set_ensemble first)");
+    if (lb.fixed_ksub > 0)
+        return fail(QOCX_ERR_STATE, "per-member rates need a static problem: this one was set with stage tables "
+                                    "(fixed_subdivision > 0), which hold one control-free generator per stage");
+    auto invalidate = [&] {
+        lb.ens_members_B = 0;
+        lb.have_results = false;
+        lb.res_B = lb.ms.batch = 0;
+        lb.res_have_results = false;
+    };
+    if (!rate_scales) {
+        lb.ens_rates = false;
+        invalidate();
+        return 0;
+    }
+    const int M = lb.ens_M, L = lb.nops;
+    if (members != M) return fail(QOCX_ERR_ARG, "rate_scales: members differs from the ensemble's");
+    if (operators != L) return fail(QOCX_ERR_ARG, "rate_scales: operators differs from the problem's operator_count");
+    for (size_t e = 0; e < (size_t)M * L; ++e)
+        if (!std::isfinite(rate_scales[e]) || !(rate_scales[e] >= 0))
+            return fail(QOCX_ERR_ARG, "rate_scales must be finite and >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = build_rate_tables(ctx, M, rate_scales)) return rc;
     lb.ens_rates = true;
     invalidate();
+    return 0;
+}
+
+int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* scales, const double* offsets,
+                            const double* rate_scales) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set (qocx_set_lindblad_problem first)");
+    if (lb.ens_M > 0 && lb.swp_B == 0)
+        return fail(QOCX_ERR_STATE, "an ensemble is set (qocx_lindblad_set_ensemble): a problem takes a sweep or an "
+                                    "ensemble");
+    if (lb.inj_count > 0)
+        return fail(QOCX_ERR_STATE, "density cotangents are set (qocx_set_density_cotangents): a sweep takes none");
+    // (the rates tables hold at most this many members)
+    if (seeds < 1 || seeds > 1024) return fail(QOCX_ERR_ARG, "sweep seeds must be 1 .. 1024");
+    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
+    // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
+    if (fixed >= lb.K) return fail(QOCX_ERR_ARG, "a sweep needs fixed < control_count (at least one seed control)");
+    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed channels need offsets");
+    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 channels");
+    const bool rates = rate_scales != nullptr && lb.nops > 0;
+    if (rates && lb.fixed_ksub > 0)
+        return fail(QOCX_ERR_STATE, "per-seed rates need a static problem: this one was set with stage tables "
+                                    "(fixed_subdivision > 0), which hold one control-free generator per stage");
+    const int B = seeds, J = fixed, Kr = lb.K - fixed, L = lb.nops, n = lb.n;
+    std::vector<double> sc((size_t)B * Kr, 1.0), off((size_t)B * J);
+    if (scales) sc.assign(scales, scales + sc.size());
+    if (J > 0) off.assign(offsets, offsets + off.size());
+    for (double v : sc)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep control scale");
+    for (double v : off)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep offset");
+    for (size_t e = 0; rates && e < (size_t)B * L; ++e)
+        if (!std::isfinite(rate_scales[e]) || !(rate_scales[e] >= 0))
+            return fail(QOCX_ERR_ARG, "rate_scales must be finite and >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (lb.swp_scales.upload(sc, ctx->stream) || (J > 0 && lb.swp_offsets.upload(off, ctx->stream)))
+        return QOCX_ERR_HIP;
+    // seed b: the control-free part of the plain problem with the rates c_b * gamma, built as the plain
+    // setter builds its own (build_rate_tables)
+    if (rates)
+        if (int rc = build_rate_tables(ctx, B, rate_scales)) return rc;
+    // M_l = L_l^H L_l of the problem's own operators, for the rate sensitivities
+    if (L > 0) {
+        std::vector<cmat> ldl;
+        for (int i = 0; i < L; ++i) ldl.push_back(cm_mul(cm_adjoint(lb.ops_h[i], n), lb.ops_h[i], n));
+        if (upload_dumps(lb.swp_ldl, ldl, n, ctx->stream)) return QOCX_ERR_HIP;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    lb.swp_scales_h = sc;
+    lb.swp_offsets_h = off;
+    lb.swp_B = B;
+    lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
+    lb.swp_seed_controls = nullptr;
+    // the seed-level view: one item per seed (qocx_host.h)
+    lb.ens_M = 1;
+    lb.ens_J = J;
+    lb.ens_Kr = Kr;
+    lb.ens_members_B = 0;
+    lb.ens_rates = rates;
+    lb.have_results = false;
+    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
+    lb.res_have_results = false;
+    lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
+    return 0;
+}
+
+int qocx_lindblad_sweep_want_rate_sensitivities(qocx_ctx* ctx, int32_t on) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (ctx->lb.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
+    ctx->lb.swp_want_rates = on != 0;
     return 0;
 }
 
@@ -772,9 +861,9 @@ int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<
         double ctl = 0;
         for (int k = 0; k < K; ++k) ctl += umax[(size_t)b * K + k] * lb.g_norm[k];
         // (per-member rates: B counts items b * M + m, and item (b, m) takes member m's bound - the
-        // sub-division count the plain problem with that member's rates would pick)
+        // sub-division count the plain problem with that member's rates would pick; a sweep: item b is seed b)
         const double base = lb.fixed_ksub > 0 ? 2 * lb.h0_norm + 2 * lb.diss_norm
-                            : lb.ens_rates    ? lb.rate_l0_norm[b % lb.ens_M]
+                            : lb.ens_rates    ? lb.rate_l0_norm[lb.swp_B > 0 ? b : b % lb.ens_M]
                                               : lb.l0_norm;
         const double bound = base + 2 * ctl;
         if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or operators");
@@ -897,7 +986,16 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
         if (lb.inj_index.upload(index, ctx->stream) || lb.inj_bars.upload(dumps, ctx->stream))
             return QOCX_ERR_HIP;
     }
-    size_t pos0 = 0, ckpt_off = 0, gsub_off = 0;
+    // Rate sensitivities of a sweep (qocx_lindblad_sweep_want_rate_sensitivities): a launch of
+    // qocx_lindblad_ratesens.hip behind every piece's combine launch; a piece that does not run two-sided
+    // (or a problem with more than four operators) leaves the evaluation without them.
+    const int rate_ops = lb.nops;
+    const bool want_rates = lb.swp_B > 0 && lb.swp_want_rates && want_grad;
+    lb.swp_rates_ok = want_rates && rate_ops >= 1 && rate_ops <= 4;
+    if (lb.swp_rates_ok && (lb.swp_rate_partials.ensure((size_t)lb.last_subintervals * rate_ops) ||
+                            lb.swp_rate_sens.ensure((size_t)B * rate_ops)))
+        return QOCX_ERR_HIP;
+    size_t pos0 = 0, ckpt_off = 0, gsub_off = 0, rate_off = 0;
     for (auto& kv : plan.groups) {
         const auto& gr = lb.grids[kv.first];
         const int Bg = (int)kv.second.size(), nsub = gr.nsub;
@@ -1016,7 +1114,17 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
                 time_begin(ctx, 6, ctx->stream);
                 qocx::launch_lindblad_combine(la, Bp, ctx->stream);
                 time_end(ctx, ctx->stream);
+                if (lb.swp_rates_ok) {
+                    // on the stream of the forward launches, so before the next piece's (and, through
+                    // ev_factored, before its adjoint's on the side stream): they reuse the stage buffers
+                    qocx::RateSensArgs rs;
+                    rs.ldl_cimg = lb.swp_ldl.p; rs.gammas = lb.gammas.p; rs.nops = rate_ops;
+                    rs.partials = lb.swp_rate_partials.p + rate_off;
+                    rs.out = lb.swp_rate_sens.p + pos0 * rate_ops;
+                    qocx::launch_lindblad_ratesens(la, rs, Bp, ctx->stream);
+                }
             } else {
+                lb.swp_rates_ok = false;
                 time_begin(ctx, 5, ctx->stream);
                 launch(la, ctx->stream);
                 time_end(ctx, ctx->stream);
@@ -1034,6 +1142,7 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
             pos0 += Bp;
             ckpt_off += (size_t)Bp * nsub * S * md;
             gsub_off += (size_t)Bp * nsub * 2 * std::max(K, 1);
+            rate_off += (size_t)Bp * nsub * rate_ops;
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1048,13 +1157,33 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
 std::vector<double> lindblad_item_maxima(const qocx_ctx::Lindblad& lb, int seeds, const double* umax) {
     const int M = lb.ens_M, Kr = lb.ens_Kr, J = lb.ens_J, K = lb.K;
     std::vector<double> out((size_t)seeds * M * K);
+    // (a sweep: M = 1 and the tables are the seed's own rows)
+    const bool swp = lb.swp_B > 0;
+    const double* scales = swp ? lb.swp_scales_h.data() : lb.ens_scales_h.data();
+    const double* offsets = swp ? lb.swp_offsets_h.data() : lb.ens_offsets_h.data();
     for (int b = 0; b < seeds; ++b)
         for (int m = 0; m < M; ++m) {
+            const size_t row = swp ? (size_t)b : (size_t)m;
             double* o = out.data() + ((size_t)b * M + m) * K;
-            for (int k = 0; k < Kr; ++k) o[k] = fabs(lb.ens_scales_h[(size_t)m * Kr + k]) * umax[(size_t)b * Kr + k];
-            for (int j = 0; j < J; ++j) o[Kr + j] = fabs(lb.ens_offsets_h[(size_t)m * J + j]);
+            for (int k = 0; k < Kr; ++k) o[k] = fabs(scales[row * Kr + k]) * umax[(size_t)b * Kr + k];
+            for (int j = 0; j < J; ++j) o[Kr + j] = fabs(offsets[row * J + j]);
         }
     return out;
+}
+
+// the kernels of qocx_sweep.hip on the Lindblad buffers: seed controls -> items (expand), the items'
+// results in item order -> the seeds' (reduce), and the channel sensitivities
+qocx::SystemSweepArgs lindblad_sweep_args(qocx_ctx* ctx, const double* seed_controls, double* cost, double* grads) {
+    auto& lb = ctx->lb;
+    qocx::SystemSweepArgs a;
+    a.seed_controls = seed_controls; a.scales = lb.swp_scales.p;
+    a.offsets = lb.ens_J > 0 ? lb.swp_offsets.p : nullptr;
+    a.controls = lb.ens_items.p;
+    a.item_cost = lb.ens_cost.p; a.item_grads = lb.ens_grads.p;
+    a.cost = cost; a.grads = grads;
+    a.scale_sens = lb.swp_scale_sens.p; a.offset_sens = lb.swp_offset_sens.p;
+    a.B = lb.swp_B; a.nc = lb.nc; a.K = lb.K; a.Kr = lb.ens_Kr; a.J = lb.ens_J;
+    return a;
 }
 
 qocx::EnsembleArgs lindblad_ensemble_args(qocx_ctx* ctx, int seeds, const double* seed_controls, double* cost,
@@ -1084,8 +1213,14 @@ int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_contro
     if ((total + 255) / 256 > 0x7fffffffu) return fail(QOCX_ERR_ARG, "ensemble control arrays too large");
     if (csz > 65535u * 256u) return fail(QOCX_ERR_ARG, "control arrays too large for the driver kernels' grids");
     if (lb.ens_items.ensure(total)) return QOCX_ERR_HIP;
-    qocx::launch_ensemble_expand(lindblad_ensemble_args(ctx, seeds, seed_controls, nullptr, nullptr), ctx->stream);
+    const bool swp = lb.swp_B > 0;
+    if (swp && seeds != lb.swp_B)
+        return fail(QOCX_ERR_ARG, "a sweep takes exactly its own seed count as the batch (qocx_lindblad_set_sweep)");
+    if (swp) qocx::launch_sweep_expand(lindblad_sweep_args(ctx, seed_controls, nullptr, nullptr), ctx->stream);
+    else qocx::launch_ensemble_expand(lindblad_ensemble_args(ctx, seeds, seed_controls, nullptr, nullptr), ctx->stream);
     HIP_TRY(hipGetLastError());
+    lb.swp_seed_controls = swp ? seed_controls : nullptr;
+    lb.swp_have_grads = false;
     std::vector<double> item_umax;
     if (umax) item_umax = lindblad_item_maxima(lb, seeds, umax);
     std::vector<int> ksub_of;
@@ -1096,13 +1231,16 @@ int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_contro
     if (lb.ens_rates) {
         // behind the order: the member of every launched item, in launch order (LindbladMembers::item_member)
         std::vector<int> both(lb.order);
-        for (int i = 0; i < items; ++i) both.push_back(lb.order[i] % lb.ens_M);
+        // (a sweep: the launched seed's own index)
+        for (int i = 0; i < items; ++i) both.push_back(swp ? lb.order[i] : lb.order[i] % lb.ens_M);
         if (lb.order_dev.upload(both, ctx->stream)) return QOCX_ERR_HIP;
     } else if (lb.order_dev.upload(lb.order, ctx->stream)) {
         return QOCX_ERR_HIP;
     }
     qocx::launch_gather_seeds(lb.ens_items.p, lb.controls.p, csz, lb.order_dev.p, items, ctx->stream);
-    return lindblad_launch_groups(ctx, want_grad, plan);
+    if (int rc2 = lindblad_launch_groups(ctx, want_grad, plan)) return rc2;
+    lb.swp_have_grads = swp && want_grad;
+    return 0;
 }
 
 // The items' results back to item order (final densities into final_items [seeds][M][S] dumps) and
@@ -1116,8 +1254,11 @@ int lindblad_ensemble_reduce(qocx_ctx* ctx, int seeds, int want_grad, double* co
     qocx::launch_scatter_seeds(lb.cost_out.p, lb.ens_cost.p, want_grad ? lb.grads.p : nullptr, lb.ens_grads.p,
                                csz, lb.final_out.p, final_items, (size_t)lb.S * md, lb.order_dev.p, items,
                                ctx->stream);
-    qocx::launch_ensemble_reduce(lindblad_ensemble_args(ctx, seeds, nullptr, cost, want_grad ? grads : nullptr),
-                                 ctx->stream);
+    if (lb.swp_B > 0)
+        qocx::launch_sweep_reduce(lindblad_sweep_args(ctx, nullptr, cost, want_grad ? grads : nullptr), ctx->stream);
+    else
+        qocx::launch_ensemble_reduce(lindblad_ensemble_args(ctx, seeds, nullptr, cost, want_grad ? grads : nullptr),
+                                     ctx->stream);
     HIP_TRY(hipGetLastError());
     lb.ens_members_B = seeds;
     return 0;
@@ -1255,7 +1396,9 @@ int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, con
     }
     if (batch < 1 || !steps || !bars) return fail(QOCX_ERR_ARG, "bad argument");
     if (lb.ens_M > 0)
-        return fail(QOCX_ERR_STATE, "density cotangents are not taken with an ensemble (qocx_lindblad_set_ensemble)");
+        return fail(QOCX_ERR_STATE, lb.swp_B > 0
+                                        ? "density cotangents are not taken with a sweep (qocx_lindblad_set_sweep)"
+                                        : "density cotangents are not taken with an ensemble (qocx_lindblad_set_ensemble)");
     std::vector<bool> seen(lb.nsteps + 1, false);
     for (int c = 0; c < count; ++c) {
         if (steps[c] < 1 || steps[c] > lb.nsteps || seen[steps[c]])
@@ -1295,6 +1438,8 @@ int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* co
     if (!lb.has_problem || lb.K < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_upload_controls needs a Lindblad problem with controls");
     if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
+    if (lb.swp_B > 0 && batch != lb.swp_B)
+        return fail(QOCX_ERR_ARG, "a sweep takes exactly its own seed count as the batch (qocx_lindblad_set_sweep)");
     // (with an ensemble the caller's array holds the seeds' K_r channels)
     const int Ks = lb.seed_channels();
     const size_t csz = (size_t)lb.nc * Ks;
@@ -1312,6 +1457,7 @@ int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* co
     lb.umax_valid = true;
     lb.res_B = batch;
     lb.res_have_results = false;
+    lb.swp_have_grads = false;  // (the seed controls of the last evaluation may just have been overwritten)
     return 0;
 }
 
@@ -1416,12 +1562,51 @@ int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out) {
 int qocx_lindblad_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
     if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
     auto& lb = ctx->lb;
-    if (lb.ens_M == 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_lindblad_set_ensemble)");
+    if (lb.ens_M == 0 || lb.swp_B > 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_lindblad_set_ensemble)");
     if (lb.ens_members_B < 1 || !lb.have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(cost_out, lb.ens_cost.p, (size_t)lb.ens_members_B * lb.ens_M * sizeof(double),
                            hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_lindblad_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out,
+                                               double* rates_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (lb.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
+    // (the seed controls on the device are those of the evaluation exactly while its results stand: the
+    // resident ones move with qocx_lindblad_opt_clip / _step, which clear res_have_results)
+    const bool resident = lb.swp_seed_controls != nullptr && lb.swp_seed_controls == lb.res_controls.p;
+    if (!lb.have_results || !lb.swp_have_grads || lb.swp_seed_controls == nullptr ||
+        (resident && !(lb.res_have_results && lb.res_have_grads)))
+        return fail(QOCX_ERR_STATE, "sweep sensitivities need an evaluation with gradients");
+    if (rates_out && !lb.swp_rates_ok)
+        return fail(QOCX_ERR_STATE, "no rate sensitivities: the last evaluation was not asked for them "
+                                    "(qocx_lindblad_sweep_want_rate_sensitivities), or a piece of it did not run "
+                                    "two-sided with 1 .. 4 operators");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int B = lb.swp_B, L = lb.nops;
+    const size_t ns = (size_t)B * lb.ens_Kr, no = (size_t)B * lb.ens_J;
+    if (lb.swp_scale_sens.ensure(ns) || lb.swp_offset_sens.ensure(no)) return QOCX_ERR_HIP;
+    // (the items' gradients in item order are the reduce launch's input, ens_grads)
+    qocx::launch_sweep_sensitivity(lindblad_sweep_args(ctx, lb.swp_seed_controls, nullptr, nullptr), ctx->stream);
+    HIP_TRY(hipGetLastError());
+    if (scales_out)
+        HIP_TRY(hipMemcpyAsync(scales_out, lb.swp_scale_sens.p, ns * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (offsets_out && no > 0)
+        HIP_TRY(hipMemcpyAsync(offsets_out, lb.swp_offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    std::vector<double> launched(rates_out ? (size_t)B * L : 0);
+    if (rates_out)
+        HIP_TRY(hipMemcpyAsync(launched.data(), lb.swp_rate_sens.p, launched.size() * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (rates_out)  // launch order -> seed order
+        for (int pos = 0; pos < B; ++pos)
+            memcpy(rates_out + (size_t)lb.order[pos] * L, launched.data() + (size_t)pos * L, L * sizeof(double));
     return 0;
 }
 

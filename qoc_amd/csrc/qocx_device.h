@@ -378,6 +378,16 @@ struct LindbladMembers {
     }
 };
 
+// Rate sensitivities of a two-sided evaluation (qocx_lindblad_ratesens.hip), the second argument of its
+// kernels beside the LindbladArgs of the piece's combine launch (ystages, kbstages, lam_scale, op_cimg).
+struct RateSensArgs {
+    const double2* ldl_cimg = nullptr;  // [L] C-dumps of L_l^H L_l
+    const double* gammas = nullptr;     // [L] the problem's own rates gamma_l (never a member's)
+    double* partials = nullptr;         // kernel out: [Bp][nsub][L], one per (item, sub-interval, l)
+    double* out = nullptr;              // reduce out: [Bp][L], launch order
+    int nops = 0;                       // L: the problem's operators (without the zero one of pad_op)
+};
+
 // ---- Hilbert sizes above 64 (qocx_general.hip): row-major padded np x np matrices in HBM, np = 16 ceil(n / 16) ----
 struct GeneralArgs {  // K1a + K1b: one work item per (seed, step), `total` = seeds * nsteps
     int np, K, nc, nsteps, nt;
@@ -556,6 +566,7 @@ void launch_lindblad4t(const LindbladArgs& a, int batch, hipStream_t st);
 void launch_lindblad4t_combine(const LindbladArgs& a, int batch, hipStream_t st);
 void launch_lindblad_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st);
 void launch_lindblad4t_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st);
+void launch_lindblad_ratesens(const LindbladArgs& a, const RateSensArgs& r, int batch, hipStream_t st);
 int lindblad_lds_size(int n, int S, int nops, int mode, int K);
 size_t lindblad_scratch_elems(int n, int S);
 

@@ -346,6 +346,23 @@ struct qocx_ctx {
         std::vector<double> rate_l0_norm;                // [M]: l0_norm of the members
         DevBuf<double2> rate_a0;                         // [M][4] dumps A0L, A0R, A0L^H, A0R^H
         DevBuf<double> rate_gammas;                      // [M][L']
+        // Hamiltonian sweep (qocx_lindblad_set_sweep, SystemSweepArgs): seed b is a system of its own, item b.
+        // As on the Schroedinger path it is the ensemble's seed-level state with ONE item per seed
+        // (ens_M = 1: ens_Kr, ens_J, the seed / item buffers above), its tables per SEED live here, and its
+        // expansion, reduction and channel sensitivities are the kernels of qocx_sweep.hip. With rate
+        // factors the rates tables above hold one entry per seed (ens_rates, rate_a0, rate_gammas,
+        // rate_l0_norm [B]) and item_member is the launched seed's own index.
+        int swp_B = 0;                                      // 0: no sweep; else the only batch size it takes
+        std::vector<double> swp_scales_h, swp_offsets_h;    // [B][Kr], [B][J]
+        DevBuf<double> swp_scales, swp_offsets;
+        DevBuf<double> swp_scale_sens, swp_offset_sens;     // [B][Kr], [B][J]
+        const double* swp_seed_controls = nullptr;          // the seed controls of the last evaluation (device)
+        bool swp_have_grads = false;                        // ... which had gradients, and whose results stand
+        // rate sensitivities (qocx_lindblad_ratesens.hip): asked for, and whether every piece of the last
+        // evaluation ran two-sided with 1 .. 4 operators
+        bool swp_want_rates = false, swp_rates_ok = false;
+        DevBuf<double2> swp_ldl;                            // [L] dumps of L_l^H L_l
+        DevBuf<double> swp_rate_partials, swp_rate_sens;    // [sub-intervals of the evaluation][L]; [B][L], launch order
         int seed_channels() const { return ens_M > 0 ? ens_Kr : K; }
         size_t seed_items() const { return ens_M > 0 ? (size_t)ens_M : 1; }
     } lb;

@@ -32,6 +32,7 @@ CONTROL_VARIATION = 1
 CONTROL_AREA = 2
 CONTROL_BANDWIDTH_MAX = 3
 
+ERR_STATE = -3
 ERR_SINGULAR = -4
 
 KERNEL_NAMES = ("pade_pq", "sweep", "krylov_grad", "scatter", "lu", "lindblad", "lindblad_combine")
@@ -156,6 +157,11 @@ SIGNATURES = {
                                                   _c_double_p]),
     "qocx_lindblad_ensemble_download_members": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_lindblad_set_ensemble_rates": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
+    "qocx_lindblad_set_sweep": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p,
+                                               _c_double_p]),
+    "qocx_lindblad_sweep_want_rate_sensitivities": (ctypes.c_int, [_VP, _I32]),
+    "qocx_lindblad_sweep_download_sensitivities": (ctypes.c_int, [_VP, _c_double_p, _c_double_p,
+                                                                  _c_double_p]),
     "qocx_set_timing": (ctypes.c_int, [_VP, _I32]),
     "qocx_get_timing": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(_I64), _c_double_p]),
     "qocx_reset_timing": (ctypes.c_int, [_VP]),
@@ -286,6 +292,7 @@ class Engine(object):
         self._ensemble = None
         self._sweep = None
         self._lindblad_ensemble = None
+        self._lindblad_sweep = None
         self._quadratic_count = 0
         self._keepalive = []
         self.batch = 0
@@ -619,10 +626,11 @@ class Engine(object):
                 p.diss_stages, p.op_stages = _dp(ds), _dp(os_)
         self._check(self._lib.qocx_set_lindblad_problem(self._ctx, ctypes.byref(p)))
         self._lindblad = dict(n=n, S=S, K=K, Nc=int(control_eval_count),
-                              N=int(system_eval_count))
+                              N=int(system_eval_count), L=L)
         self._lindblad_batch = 0
         self._lindblad_resident_batch = 0
         self._lindblad_ensemble = None
+        self._lindblad_sweep = None
         self._lindblad_seeds = 0
 
     def set_lindblad_ensemble(self, scales, offsets, weights):
@@ -675,9 +683,78 @@ class Engine(object):
         return () if self._lindblad_ensemble is None else (self._lindblad_ensemble["M"],)
 
     def _lindblad_seed_channels(self):
-        """Control channels of a Lindblad seed: the problem's K, or K - J with an ensemble set."""
-        ens = self._lindblad_ensemble
+        """Control channels of a Lindblad seed: the problem's K, or K - J with an ensemble or a sweep
+        set."""
+        ens = self._lindblad_ensemble if self._lindblad_sweep is None else self._lindblad_sweep
         return self._lindblad["K"] if ens is None else ens["Kr"]
+
+    def set_lindblad_sweep(self, scales, offsets, rate_scales=None):
+        """A sweep of B seeds on the current Lindblad problem (qocx_lindblad_set_sweep): seed b is an
+        open system of its own, the problem on the controls [scales[b] * u_b, offsets[b]] with the
+        rates rate_scales[b] * dissipators; the problem's last J control channels are the fixed
+        matrices D_j. scales :: (B, K - J) or None (all 1), offsets :: (B, J) or None (J = 0),
+        rate_scales :: (B, L) finite and >= 0 or None (the problem's rates); one of them is needed
+        (B is read from it). From here on evaluate_lindblad and the lindblad_* calls take and return
+        the seeds' K - J channels, the batch is exactly B and final densities are (B, S, n, n)."""
+        if scales is None and offsets is None and rate_scales is None:
+            raise ValueError("a sweep needs scales, offsets or rate_scales (the seed count is read "
+                             "from them)")
+        none = ctypes.cast(None, _c_double_p)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.float64)
+        if off is not None and off.ndim != 2:
+            raise ValueError("offsets must be (B, J), got shape {}".format(off.shape))
+        J = 0 if off is None else off.shape[1]
+        kr = self._lindblad["K"] - J
+        sc = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64)
+        rates = None if rate_scales is None else np.ascontiguousarray(rate_scales, dtype=np.float64)
+        if rates is not None and (rates.ndim != 2 or rates.shape[1] != self._lindblad["L"]):
+            raise ValueError("rate_scales must be (B, L) with L = {} operators, got shape {}".format(
+                self._lindblad["L"], rates.shape))
+        B = next(a.shape[0] for a in (sc, off, rates) if a is not None)
+        if sc is not None and sc.shape != (B, kr):
+            raise ValueError("scales must be (B, K - J) = ({}, {}), got shape {}".format(B, kr, sc.shape))
+        if any(a is not None and a.shape[0] != B for a in (off, rates)):
+            raise ValueError("scales, offsets and rate_scales disagree on the seed count")
+        if J == 0:
+            off = None
+        if rates is not None and rates.size == 0:  # (L = 0: nothing to scale)
+            rates = None
+        self._check(self._lib.qocx_lindblad_set_sweep(
+            self._ctx, B, J, none if sc is None else _dp(sc), none if off is None else _dp(off),
+            none if rates is None else _dp(rates)))
+        self._lindblad_ensemble = None
+        self._lindblad_sweep = dict(B=B, J=J, Kr=kr, L=self._lindblad["L"])
+        self._lindblad_batch = self._lindblad_seeds = 0
+        self._lindblad_resident_batch = 0
+
+    def lindblad_sweep_want_rate_sensitivities(self, on):
+        """Ask the evaluations from here on for the rate sensitivities of the sweep
+        (qocx_lindblad_sweep_want_rate_sensitivities): one more kernel launch per piece."""
+        self._check(self._lib.qocx_lindblad_sweep_want_rate_sensitivities(self._ctx, int(bool(on))))
+
+    def lindblad_sweep_sensitivities(self, want_rates=True):
+        """(dE_b / d scales [B, K - J], dE_b / d offsets [B, J], dE_b / d rate_scales [B, L] or None)
+        of the last evaluation with gradients (qocx_lindblad_sweep_download_sensitivities). The
+        rate entry is None unless the evaluation was asked for it and every piece of it ran
+        two-sided (the engine then answers QOCX_ERR_STATE for that output alone)."""
+        sw = self._lindblad_sweep
+        if sw is None:
+            raise ValueError("no sweep set (set_lindblad_sweep)")
+        none = ctypes.cast(None, _c_double_p)
+        scales = np.empty((sw["B"], sw["Kr"]), dtype=np.float64)
+        offsets = np.empty((sw["B"], sw["J"]), dtype=np.float64)
+        self._check(self._lib.qocx_lindblad_sweep_download_sensitivities(
+            self._ctx, _dp(scales), _dp(offsets), none))
+        rates = None
+        if want_rates and sw["L"] > 0:
+            rates = np.empty((sw["B"], sw["L"]), dtype=np.float64)
+            code = self._lib.qocx_lindblad_sweep_download_sensitivities(
+                self._ctx, none, none, _dp(rates))
+            if code == ERR_STATE:
+                rates = None
+            else:
+                self._check(code)
+        return scales, offsets, rates
 
     def evaluate_lindblad(self, controls, want_grad=True, want_final=True):
         """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n]) for controls[B,Nc,K]; with an

@@ -9,7 +9,8 @@ from .costs import (ControlArea, ControlBandwidthMax, ControlNorm, ControlVariat
                     TargetStateInfidelityTime)
 from .functions import (column_vector_list_to_matrix, commutator, conjugate_transpose, expm,
                         krons, matmuls, matrix_to_column_vector_list, rms_norm)
-from .hamiltonians import HamiltonianEnsemble, HamiltonianSweep, QuadraticHamiltonian
+from .hamiltonians import (HamiltonianEnsemble, HamiltonianSweep, LindbladSweep,
+                           QuadraticHamiltonian)
 from .optimizers import LBFGS, LBFGSB, SGD, Adam
 from .utils import CustomJSONEncoder, generate_save_file_path
 
@@ -22,6 +23,7 @@ __all__ = [
     "commutator", "conjugate_transpose", "expm", "krons", "rms_norm", "matmuls",
     "column_vector_list_to_matrix", "matrix_to_column_vector_list",
     "Adam", "LBFGS", "LBFGSB", "SGD",
-    "HamiltonianEnsemble", "HamiltonianSweep", "QuadraticHamiltonian", "ControlBasis",
+    "HamiltonianEnsemble", "HamiltonianSweep", "LindbladSweep", "QuadraticHamiltonian",
+    "ControlBasis",
     "generate_save_file_path", "CustomJSONEncoder",
 ]

@@ -24,6 +24,9 @@ HamiltonianSweep is not a callable either: it is B systems, each with controls o
 controls and fixed terms per SEED (a gate-time sweep, a calibration family). The Schroedinger
 evaluator sets it up as the ensemble's structured problem and the engine expands seed b into item b
 on the device (qocx_set_sweep).
+
+LindbladSweep is the sweep of the Lindblad entry points: seed b also has dissipation rates of its own
+(rate_scales), and its durations scale the rates with the Hamiltonian (qocx_lindblad_set_sweep).
 """
 
 import numbers
@@ -364,10 +367,11 @@ class HamiltonianSweep(object):
     evolution_times = None
     reference_time = None
 
-    def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None):
+    def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
+                 _more_counts=None):
         if not callable(hamiltonian):
             raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
-        counts = {}
+        counts = dict(_more_counts or {})  # (a subclass's own tables: LindbladSweep's rate_scales)
         if perturbations is not None:
             perturbations = np.array(perturbations, dtype=np.complex128)
             if perturbations.ndim != 3 or perturbations.shape[1] != perturbations.shape[2]:
@@ -391,8 +395,9 @@ class HamiltonianSweep(object):
         if not counts:
             raise ValueError("a sweep needs offsets or control_scales (B is read from them)")
         if len(set(counts.values())) > 1:
-            raise ValueError("offsets and control_scales disagree on the seed count: {}"
-                             "".format(", ".join("{} {}".format(k, v) for k, v in counts.items())))
+            raise ValueError("{} disagree on the seed count: {}".format(
+                " and ".join(sorted(counts)) if _more_counts else "offsets and control_scales",
+                ", ".join("{} {}".format(k, v) for k, v in counts.items())))
         B = next(iter(counts.values()))
         if B == 0:
             raise ValueError("a sweep needs at least one seed (B = 0 in {})"
@@ -609,3 +614,154 @@ class HamiltonianSweep(object):
         return "HamiltonianSweep({!r}, {} seeds, {} fixed matrices{})".format(
             self._source if self._source is not None else self.hamiltonian, self.seed_count,
             self.perturbation_count, ", durations" if self.time_scaled else "")
+
+
+class LindbladSweep(HamiltonianSweep):
+    """
+    W = LindbladSweep(hamiltonian, perturbations=None, offsets=None, control_scales=None,
+                      rate_scales=None)
+
+    A HamiltonianSweep for the Lindblad entry points: B open systems, each driven by controls of
+    its own. Seed b is the Lindblad problem with
+
+        H_b(u, t) = hamiltonian(s_b * u, t) + sum_j offsets[b, j] D_j
+
+    and the dissipation rates rate_scales[b] * dissipators of the problem's lindblad_data; the
+    operators, the initial densities and the costs are shared. A type of its own because its
+    durations scale the rates as well - a plain HamiltonianSweep stays refused on the Lindblad path.
+
+    hamiltonian, perturbations, offsets, control_scales: as for a HamiltonianSweep.
+    rate_scales :: (B, L) real, finite and >= 0 - c_bl, seed b's factor of the l-th dissipation rate,
+        L the number of Lindblad operators. Default: every seed takes the rates as given. With them
+        the system must be time independent (hamiltonian, drives and lindblad_data): the engine
+        holds a time-dependent control-free generator in per-stage tables, one set, not B.
+
+    B is read from whichever of offsets, control_scales and rate_scales is given; they must agree.
+    Passed as the `hamiltonian` of grape_lindblad_discrete_batch (B = initial_controls.shape[0]) or of
+    LindbladEvaluator (evaluate_batch with a batch of B); the engine expands the seeds on the device
+    (qocx_lindblad_set_sweep). The result's sweep_sensitivities holds control_scales
+    (B x control_count), offsets (B x J) and rate_scales (B x L) = d error_b / d c_bl, and for a
+    duration sweep evolution_time_gradients (B). The last two exist only where the engine's
+    sensitivity evaluation ran two-sided, and are None elsewhere: that takes ONE cost, a final
+    TargetDensityInfidelity (no step cost, no second cost), 1 to 4 Lindblad operators, a
+    time-independent system, and stage values that fit the device memory.
+    member(b) and member_lindblad_data(b, lindblad_data) are seed b's system as plain callables,
+    slice(lo, hi) the sweep of a contiguous block of seeds.
+
+    LindbladSweep.durations(...) builds the sweep in which seed b runs for its own evolution time.
+    """
+
+    def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
+                 rate_scales=None):
+        more = None
+        if rate_scales is not None:
+            rate_scales = _rate_scales_array(rate_scales)
+            more = {"rate_scales": rate_scales.shape[0]}
+        HamiltonianSweep.__init__(self, hamiltonian, perturbations, offsets, control_scales,
+                                  _more_counts=more)
+        self.rate_scales = rate_scales
+        self._user_rates = rate_scales   # c0 of time_gradients: the values before tau
+
+    @classmethod
+    def durations(cls, hamiltonian, evolution_times, reference_time, control_scales=None,
+                  perturbations=None, offsets=None, rate_scales=None):
+        """
+        The sweep in which seed b runs for evolution_times[b]: what HamiltonianSweep.durations
+        builds, with rate_scales additionally multiplied by tau_b = T_b / reference_time -
+
+            tau_b * (the whole Lindbladian)  on  [0, reference_time]
+
+        is the open system on [0, T_b], exact for a time-independent system (scaling the
+        Lindbladian is scaling time). The caller passes evolution_time = reference_time.
+        rate_scales :: (B, L) or None (all 1), before the factor tau_b. Every seed has rates of its
+        own here, so the system must be time independent - lindblad_data included.
+        """
+        self = super(LindbladSweep, cls).durations(hamiltonian, evolution_times, reference_time,
+                                                   control_scales, perturbations, offsets)
+        user_rates = None
+        if rate_scales is not None:
+            user_rates = _rate_scales_array(rate_scales)
+            if user_rates.shape[0] != self.seed_count:
+                raise ValueError("rate_scales are for {} seeds, evolution_times for {}"
+                                 "".format(user_rates.shape[0], self.seed_count))
+        self._user_rates = user_rates
+        # (rates of all 1 are kept implicit until the operator count is known: resolved_rate_scales)
+        self.rate_scales = None if user_rates is None else self._tau[:, None] * user_rates
+        return self
+
+    @property
+    def has_rates(self):
+        """Seed b decays with rates of its own (rate_scales given, or a duration sweep)."""
+        return self.rate_scales is not None or self.time_scaled
+
+    def resolved_rate_scales(self, operator_count):
+        """c_bl for a problem with this many Lindblad operators, (B, L); None where every seed takes
+        the rates as given. A duration sweep without rate_scales has c_bl = tau_b."""
+        L = int(operator_count)
+        rates = self.rate_scales
+        if rates is None:
+            if not self.time_scaled:
+                return None
+            rates = np.repeat(self._tau[:, None], L, axis=1)
+        if rates.shape[1] != L:
+            raise ValueError("rate_scales must be (B, L) with L = {} Lindblad operators of "
+                             "lindblad_data, got shape {}".format(L, rates.shape))
+        return rates
+
+    def member_lindblad_data(self, b, lindblad_data):
+        """Seed b's lindblad_data as a plain callable time -> (c_b * dissipators, operators): the
+        problem's own where the sweep has no rates of its own."""
+        b = int(b)
+        if not 0 <= b < self.seed_count:
+            raise IndexError("seed {} out of range for {} seeds".format(b, self.seed_count))
+        if not callable(lindblad_data):
+            raise ValueError("lindblad_data must be a callable time -> (dissipators, operators)")
+        if not self.has_rates:
+            return lindblad_data
+
+        def member_data(time):
+            dissipators, operators = lindblad_data(time)
+            dissipators = np.asarray(dissipators)
+            factors = self.resolved_rate_scales(dissipators.shape[0] if dissipators.ndim else 0)
+            return factors[b] * dissipators, operators
+        return member_data
+
+    def slice(self, lo, hi):
+        """The sweep of seeds lo .. hi - 1, rates included (what a rank of a communicator
+        evaluates)."""
+        out = HamiltonianSweep.slice(self, lo, hi)
+        lo, hi = int(lo), int(hi)
+        for name in ("rate_scales", "_user_rates"):
+            value = getattr(self, name, None)
+            if value is not None:
+                setattr(out, name, value[lo:hi].copy())
+        return out
+
+    def time_gradients(self, scale_sens, offset_sens, rate_sens=None):
+        """d error_b / d T_b (B,) of a duration sweep: HamiltonianSweep.time_gradients plus the rate
+        part sum_l dE/dc_bl c0_bl / reference_time with c0 the rate factors before tau_b (all 1
+        without rate_scales) - c_bl = tau_b c0_bl, so this is sum_l c_bl dE/dc_bl / tau_b /
+        reference_time. rate_sens :: (B, L); None or L = 0: no rates, the Hamiltonian part alone."""
+        out = HamiltonianSweep.time_gradients(self, scale_sens, offset_sens)
+        if rate_sens is None:
+            return out
+        rate_sens = np.asarray(rate_sens, dtype=np.float64)
+        c0 = np.ones_like(rate_sens) if self._user_rates is None else self._user_rates
+        if rate_sens.shape != c0.shape:
+            raise ValueError("rate sensitivities must be (B, L) = {}, got {}".format(
+                c0.shape, rate_sens.shape))
+        return out + np.sum(rate_sens * c0, axis=1) / self.reference_time
+
+    def __repr__(self):
+        rates = "" if self.rate_scales is None else ", rate_scales {}".format(
+            "x".join(str(d) for d in self.rate_scales.shape))
+        return "LindbladSweep({!r}, {} seeds, {} fixed matrices{}{})".format(
+            self._source if self._source is not None else self.hamiltonian, self.seed_count,
+            self.perturbation_count, rates, ", durations" if self.time_scaled else "")
+
+
+def _rate_scales_array(rate_scales):
+    rate_scales = _real_array(rate_scales, "rate_scales", 2)
+    if np.any(rate_scales < 0):
+        raise ValueError("rate_scales must be >= 0 (they multiply dissipation rates)")
+    return rate_scales
