@@ -9,7 +9,10 @@ upload differ in Pade order, squaring count and pivoting regime. With drive=True
 depend on time as well, G_k(t) = cos(w_k t + k) G_k + sin(w_k t) G'_k with w_k dt in 0.5 .. 1.0 (the
 rotating drives of tests/time_dependent_drive.py), and every draw is time dependent; what that adds is
 drawn from a generator of its own, seeded by `index`, so the draws of the shared stream - and with
-them every problem of the tests that leave drive at False - stay what they are.
+them every problem of the tests that leave drive at False - stay what they are. With costs=True the fixed
+cost triple gives way to 1 to 4 random descriptors (kinds, step or final, ragged forbid counts from 1 to
+4; tests/state_costs.py: DescriptorCost on the oracle's side), drawn the same way from a generator of
+their own.
 
     python -m tests.fuzz_parity [count] [seed] [nmin] [nmax] [smin] [smax]
 """
@@ -30,7 +33,22 @@ NODES = {"M2": (0.5,), "M4": (0.5 - 3 ** 0.5 / 6, 0.5 + 3 ** 0.5 / 6),
          "M6": (0.5 - 15 ** 0.5 / 10, 0.5, 0.5 + 15 ** 0.5 / 10)}
 
 
-def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shapes=False, drive=False):
+def random_descriptors(own, n, S):
+    """1 to 4 random cost descriptors (tests/state_costs.py: DescriptorCost): kind, step or final,
+    scale, vectors of their own and - FORBID - ragged counts from 1 to 4."""
+    from tests.state_costs import DescriptorCost
+    out = []
+    for _ in range(int(own.integers(1, 5))):
+        kind = int(own.integers(0, 3))
+        counts = [int(c) for c in own.integers(1, 5, S)] if kind == COST_FORBID else None
+        vec = own.standard_normal((sum(counts) if counts else S, n, 2)) @ np.array([1.0, 1.0j])
+        vec /= np.linalg.norm(vec, axis=1, keepdims=True)
+        out.append(DescriptorCost(kind, int(own.integers(0, 2)), float(own.uniform(0.3, 1.5)), vec, counts))
+    return out
+
+
+def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shapes=False, drive=False,
+        costs=False):
     n = int(rng.integers(nmin, nmax + 1))
     N = int(rng.integers(2, 14))
     K = int(rng.integers(1, 4))
@@ -84,6 +102,9 @@ def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shape
                                                  cost_eval_step=ces, cost_multiplier=1.3),
                    onp.ForbidStates(forb[:, :, :, None], N, cost_eval_step=ces,
                                     cost_multiplier=0.9)]
+    if costs:
+        ocosts = random_descriptors(np.random.default_rng([index, 0x636F737473]), n, S)
+        descs = [c.descriptor() for c in ocosts]
     if time_dep:
         times = [j * dt + c * dt for j in range(N - 1) for c in NODES[policy]]
         h0s = np.stack([h0 * (1 + 0.3 * np.cos(omega * t)) for t in times])
@@ -96,6 +117,9 @@ def one(engine, rng, index, nmin=1, nmax=32, smin=1, smax=4, results=None, shape
         n, N, Nc, K, S, ces, policy, hermitian, time_dep, dt, scale)
     if drive:
         tag += " drive w dt=" + ",".join("{:.2f}".format(w * dt) for w in g_omega)
+    if costs:
+        tag += " costs " + ",".join("{}{}{}".format("CIF"[c.kind], "s" if c.step_cost else "f", c.counts or "")
+                                    for c in ocosts)
     if shapes:
         # (peak amplitude three times the Gaussian scale of the default draw: its 3 sigma)
         picks = [(FAMILIES[int(rng.integers(0, len(FAMILIES)))], 3 * float(10 ** rng.uniform(-1, 0.5)))
