@@ -309,6 +309,38 @@ int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t c
 int qocx_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* scales, const double* offsets);
 int qocx_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out);
 
+/*
+ * Duration search of a sweep (minimum-time GRAPE): tau_b = T_b / T, seed b's duration in units of the
+ * problem's evolution time, becomes one more optimised parameter of the seed. Call after qocx_set_sweep
+ * (QOCX_ERR_STATE without a sweep) of a problem whose first fixed channel is the drift (J >= 1).
+ *   tau          [B]      the starting durations; clipped to [tau_min, tau_max] on the device
+ *   base_scales  [B][K_r] s0, the control scales before the factor tau (NULL: all 1)
+ *   base_offsets [B][J]   delta0, the offsets before the factor tau; column 0, the drift, is 1
+ *   0 < tau_min <= tau_max finite; time_weight >= 0 finite (QOCX_ERR_ARG otherwise, or for a
+ *   non-finite entry)
+ * The engine keeps tau, s0 and delta0 on the device and derives the sweep's tables there,
+ *     scales_bk = tau_b s0_bk      offsets_bj = tau_b delta0_bj     (one product, one rounding each)
+ * replacing those of qocx_set_sweep; the bounds qocx_opt_clip commits are those of tau_max, so they hold
+ * for every tau the optimizer can reach. A new problem or a new qocx_set_sweep clears the search.
+ * Controls must be uploaded afterwards.
+ * With durations set:
+ *   every evaluation adds time_weight tau_b to the cost of seed b, after the costs of the controls
+ *     (one product, one sum); one with gradients also produces dE_b/dtau_b + time_weight, the chain
+ *     rule through the tables in the fixed order stated in qocx_duration.hip
+ *   qocx_opt_begin* allocates the optimizer state of tau (moments, best tau)
+ *   qocx_opt_clip clips tau in place to the box and rewrites the tables before the seeds are expanded
+ *   qocx_opt_step keeps tau of the improved seeds as their best and steps tau of the flagged seeds
+ *     with the rule and learning rate of the controls (Adam / SGD are element-wise)
+ *   qocx_opt_lbfgs_begin returns QOCX_ERR_STATE (the resident L-BFGS vectors do not hold tau)
+ * qocx_sweep_download_durations: tau_out [B] the current (clipped) durations, tau_grad_out [B] the
+ *   gradient of the last evaluation with gradients (QOCX_ERR_STATE without one); either may be NULL.
+ * qocx_opt_download_best_durations: tau_out [B], tau at every seed's best evaluation so far.
+ */
+int qocx_sweep_set_durations(qocx_ctx* ctx, const double* tau, const double* base_scales,
+                             const double* base_offsets, double tau_min, double tau_max, double time_weight);
+int qocx_sweep_download_durations(qocx_ctx* ctx, double* tau_out, double* tau_grad_out);
+int qocx_opt_download_best_durations(qocx_ctx* ctx, double* tau_out);
+
 /* Optional: all system-step states of the last evaluation, [B][N][S][n] complex
  * (what save_intermediate_states persists, schroedingerdiscrete.py:395-402). */
 int qocx_set_keep_step_states(qocx_ctx* ctx, int32_t keep); /* before the evaluation */

@@ -47,6 +47,9 @@ class BatchResult(object):
         # rate_scales (B x L), which - with evolution_time_gradients - is None where the
         # sensitivity evaluation did not run two-sided
         self.sweep_sensitivities = None
+        # with a duration search (HamiltonianSweep.durations(time_bounds=...)): T_b at every seed's
+        # best iteration, (B,); NaN for a seed without one
+        self.best_evolution_times = None
 
     @property
     def best(self):
@@ -368,6 +371,10 @@ def sweep_sensitivities(evaluator, result):
     template = result.best_controls[int(np.nonzero(have)[0][0])]
     controls = np.stack([c if c is not None else np.zeros_like(template)
                          for c in result.best_controls])
+    # (a duration search: at every seed's best duration too; a seed without one keeps its start)
+    best_tau = getattr(result, "_best_tau", None)
+    if best_tau is not None:
+        evaluator.set_durations(np.where(have, best_tau, evaluator.durations()))
     # (the Lindblad path: rate sensitivities are asked for in this one evaluation only)
     want_rates = getattr(evaluator, "want_rate_sensitivities", None)
     if want_rates is not None:
@@ -391,6 +398,10 @@ def resident_route(stepper, optimizer, pstate, evaluator, batch):
     the backend's L-BFGS calls: a stand-in backend without them takes the host loop."""
     if type(optimizer) is LBFGS and not (hasattr(evaluator, "resident_lbfgs_capable")
                                          and evaluator.resident_lbfgs_capable()):
+        return False
+    # (a duration search: the two-loop recursion needs tau inside the resident vector, which is
+    # not laid out that way - LBFGS takes the host loop, where tau is the vector's last entry)
+    if type(optimizer) is LBFGS and getattr(pstate, "duration_search", None) is not None:
         return False
     # (a ControlBasis needs the backend's basis calls in the same way)
     if getattr(pstate, "control_basis", None) is not None and not (
@@ -444,6 +455,9 @@ class ResidentOps(object):
         # a ControlBasis (None on a backend without the calls)
         self._opt_begin_basis = getattr(engine, prefix + "opt_begin_basis", None)
         self._opt_download_best_params = getattr(engine, prefix + "opt_download_best_params", None)
+        # a duration search (None on a backend, or a path, without the call)
+        self.opt_download_best_durations = getattr(engine, prefix + "opt_download_best_durations",
+                                                   None)
 
     def upload_controls(self, controls):
         if self.control_costs:
@@ -480,12 +494,20 @@ def run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iter
     opt_begin_basis in the place of opt_begin and opt_download_best_params); controls go in and
     come back in the cost-function format (complex arrays for complex controls: ops holds them as
     two real channels each and keeps the optimizer's parameters unclipped, as _cost_format_batch
-    does on the host). ops.finish(), if there is one, runs when the loop ends, however it ends."""
+    does on the host). ops.finish(), if there is one, runs when the loop ends, however it ends.
+    A duration search (pstate.duration_search, its evaluator): tau_b lives on the device beside the
+    controls - ops.opt_clip clips it and rewrites the tables, ops.opt_step steps it - and the loop
+    itself does nothing more per iteration; the device adds the price of time while it runs."""
+    search = getattr(pstate, "duration_search", None)
     try:
+        if search is not None:
+            search.time_term_resident(True)
         return _run_batch_resident(ops, optimizer, params, pstate, iteration_count,
                                    log_iteration_step, min_error, comm, result)
     finally:
         getattr(ops, "finish", lambda: None)()
+        if search is not None:
+            search.time_term_resident(False)
 
 
 def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_iteration_step,
@@ -554,6 +576,9 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
             break
     best_controls, best_finals = ops.opt_download_best()
     best_coefficients = ops.opt_download_best_params() if basis is not None else None
+    search = getattr(pstate, "duration_search", None)
+    if search is not None:
+        _keep_best_durations(result, search, ops.opt_download_best_durations())
     finals = getattr(result, result.final_field)
     for b in range(B):
         if result.best_iteration[b] >= 0:
@@ -564,24 +589,47 @@ def _run_batch_resident(ops, optimizer, params, pstate, iteration_count, log_ite
     return _finish(result, comm)
 
 
+def _keep_best_durations(result, evaluator, best_tau):
+    """result.best_evolution_times (and the tau behind them) of a duration search."""
+    have = result.best_iteration >= 0
+    result._best_tau = np.where(have, best_tau, np.nan)
+    result.best_evolution_times = result._best_tau * evaluator.sweep.reference_time
+
+
 def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_count,
                    log_iteration_step, min_error, comm, result):
     """The loop on the host: evaluator.evaluate_batch once per iteration, the [B, P] stepper of the
-    built-in optimizers or one deep copy of any other step-wise plugin per seed."""
+    built-in optimizers or one deep copy of any other step-wise plugin per seed.
+    A duration search (pstate.duration_search, its evaluator): tau_b is the LAST entry of seed b's
+    flat parameter vector - after the coefficients of a basis, after [Re..., Im...] of complex
+    controls -, clipped in place to its box before every evaluation and stepped by the optimizer
+    with the gradient the engine returns for it."""
     B = params.shape[0]
     shape = tuple(pstate.controls_shape)
+    search = getattr(pstate, "duration_search", None) if B > 0 else None
+    if search is not None:
+        params = np.ascontiguousarray(np.hstack([params, search.durations()[:, None]]))
+        tau_lo, tau_hi = search.sweep.tau_bounds
+        best_tau = np.zeros(B)
+        if stepper is not None:  # (its state is shaped like the parameters)
+            stepper = batched_stepper(optimizer, params)
+    own = params if search is None else params[:, :-1]  # the controls' own parameters (a view)
     optimizers = None if stepper is not None else [_optimizer_clone(optimizer, p) for p in params]
     needs_error = bool(getattr(stepper if stepper is not None else optimizer, "needs_error", False))
     _log_header(log_iteration_step, comm)
     active = np.ones(B, dtype=bool)
     best_controls = best_finals = None
     basis = getattr(pstate, "control_basis", None)
-    best_params = np.zeros_like(params) if basis is not None else None
+    best_params = np.zeros_like(own) if basis is not None else None
     should_log = log_iteration_step != 0
     for iteration in range(iteration_count):
         # cost-function format of every seed (clipping acts in place on the optimizer's params
         # for real controls, exactly as in the single-seed driver)
-        controls = _cost_format_batch(params, pstate)
+        if search is not None:
+            tau = params[:, -1]
+            np.minimum(np.maximum(tau, tau_lo, out=tau), tau_hi, out=tau)
+            search.set_durations(tau)
+        controls = _cost_format_batch(own, pstate)
         if B > 0:
             errors, grads, finals, _ = evaluator.evaluate_batch(controls, want_grad=True)
         else:
@@ -596,7 +644,9 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
             best_controls[improved] = controls[improved]
             best_finals[improved] = finals[improved]
             if basis is not None:
-                best_params[improved] = params[improved]
+                best_params[improved] = own[improved]
+            if search is not None:
+                best_tau[improved] = params[improved, -1]
             result.best_error[improved] = errors[improved]
             result.best_iteration[improved] = iteration
         if should_log and (iteration % log_iteration_step == 0 or iteration == iteration_count - 1):
@@ -615,6 +665,9 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
             if basis is not None:  # d error / d coefficients (the derivative of the clip is ignored)
                 grads = basis.project(grads)
             flat_grads = _strip_batch(pstate.complex_controls, grads)
+            if search is not None:
+                flat_grads = np.ascontiguousarray(
+                    np.hstack([flat_grads, search.duration_gradients()[:, None]]))
             if stepper is not None and needs_error:
                 stepper.update(flat_grads, params, rows, errors)
                 active &= ~stepper.finished
@@ -630,6 +683,8 @@ def run_batch_host(evaluator, stepper, optimizer, params, pstate, iteration_coun
         still = comm.allreduce_sum(np.array([float(np.sum(active))]))[0]
         if still == 0:
             break
+    if search is not None:
+        _keep_best_durations(result, search, best_tau)
     finals = getattr(result, result.final_field)
     for b in range(B):
         if result.best_iteration[b] >= 0:

@@ -232,6 +232,10 @@ class _Evaluator(object):
         if not hasattr(backend, self.sweep_setter):
             raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian sweeps "
                                       "(no {})".format(backend, self.sweep_setter))
+        if sweep.searches_duration and not hasattr(backend, "sweep_set_durations"):
+            raise NotImplementedError(
+                "the backend {!r} does not search the durations of a sweep (no "
+                "sweep_set_durations): drop time_bounds, or use the engine".format(backend))
         matrices = sweep.resolve(control_count, complex_controls, self.hilbert_size, times)
         if matrices is not None and matrices.shape[1] != self.hilbert_size:
             raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
@@ -240,6 +244,12 @@ class _Evaluator(object):
         self._sweep_matrices = matrices
         self._sweep_args = (sweep.real_channel_scales(control_count, complex_controls),
                             sweep.offsets)
+        if sweep.searches_duration:
+            # tau_b is a parameter of seed b on the device (qocx_sweep_set_durations): the tables
+            # before the factor tau, and the durations the next evaluation runs at
+            self._duration_tables = sweep.base_tables(control_count, complex_controls)
+            self._tau = np.array(sweep._tau, dtype=np.float64)
+            self._tau_grad = None
         return base
 
     def _reject_sweep_costs(self):
@@ -621,13 +631,105 @@ class SchroedingerEvaluator(_Evaluator):
                 self.backend.set_ensemble_quadratic_scales(self.ensemble.quadratic_scales)
         if self.sweep is not None:
             self.backend.set_sweep(*self._sweep_args)
+            if self.sweep.searches_duration:
+                self._set_durations()
+
+    # -- duration search of a sweep (HamiltonianSweep.durations(time_bounds=...)) -----------------
+    _time_term_resident = False
+
+    def _device_time_weight(self):
+        """The price of time joins the error LAST, after the costs of the controls alone. Where the
+        host adds those (evaluate_batch) it adds the time term after them, the same product and the
+        same sum, and the device is given a weight of zero; where the device adds them (the resident
+        loop, time_term_resident) or there are none, the device adds the time term."""
+        if self.host_costs and not self._time_term_resident:
+            return 0.0
+        return self.sweep.time_weight
+
+    def _set_durations(self):
+        s0, d0 = self._duration_tables
+        lo, hi = self.sweep.tau_bounds
+        self.backend.sweep_set_durations(self._tau, s0, d0, lo, hi, self._device_time_weight())
+        self._tau = np.array(self.backend.sweep_download_durations(want_grad=False)[0])
+        self._tau_grad = None
+
+    def _require_search(self):
+        if self.sweep is None or not self.sweep.searches_duration:
+            raise ValueError("durations are set and read on a duration search "
+                             "(HamiltonianSweep.durations(time_bounds=...))")
+
+    def time_term_resident(self, on):
+        """The resident loop adds the costs of the controls on the device, so the price of time
+        must be added there too (run_batch_resident brackets its loop with this)."""
+        self._require_search()
+        if bool(on) != self._time_term_resident:
+            self._time_term_resident = bool(on)
+            if self.host_costs:
+                self._set_durations()
+
+    def set_durations(self, tau):
+        """tau_b = T_b / reference_time of every seed for the evaluations from here on (B,); the
+        engine clips them to the box."""
+        self._require_search()
+        tau = np.array(tau, dtype=np.float64).reshape(-1)
+        if tau.shape[0] != self.sweep.seed_count:
+            raise ValueError("a sweep of {} seeds takes that many durations, got {}".format(
+                self.sweep.seed_count, tau.shape[0]))
+        if not np.all(np.isfinite(tau)):
+            raise ValueError("durations are not finite")
+        self._tau = tau
+        self._set_durations()
+
+    def set_evolution_times(self, times):
+        """T_b of every seed for the evaluations from here on (B,), clipped to time_bounds."""
+        self._require_search()
+        self.set_durations(np.asarray(times, dtype=np.float64) / self.sweep.reference_time)
+
+    def durations(self):
+        """tau_b (B,) the evaluations run at (the last evaluation's, once there is one)."""
+        self._require_search()
+        return self._tau.copy()
+
+    def evolution_times(self):
+        """T_b = tau_b * reference_time (B,) the evaluations run at."""
+        return self.durations() * self.sweep.reference_time
+
+    def duration_gradients(self):
+        """d (error_b + time_weight * tau_b) / d tau_b (B,) of the last evaluation with gradients:
+        the engine's chain rule through the tables (qocx_duration.hip) plus time_weight."""
+        self._require_search()
+        if self._tau_grad is None:
+            raise ValueError("duration gradients need an evaluation with gradients")
+        return self._tau_grad.copy()
+
+    def evolution_time_gradients(self):
+        """d (error_b + time_weight * tau_b) / d T_b (B,): duration_gradients() / reference_time."""
+        return self.duration_gradients() / self.sweep.reference_time
+
+    def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
+        """_Evaluator.evaluate_batch; a duration search evaluates at the current durations and its
+        errors include the price of time, time_weight * tau_b, added last."""
+        out = _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_states)
+        if self.sweep is None or not self.sweep.searches_duration:
+            return out
+        errors, grads, final, steps = out
+        tau, tau_grad = self.backend.sweep_download_durations(want_grad=bool(want_grad))
+        weight = self.sweep.time_weight
+        if weight != 0.0 and self._device_time_weight() == 0.0:
+            errors = errors + weight * tau
+            if tau_grad is not None:
+                tau_grad = tau_grad + weight
+        self._tau = np.array(tau)
+        self._tau_grad = None if tau_grad is None else np.array(tau_grad)
+        return errors, grads, final, steps
 
     # -- Hamiltonian sweeps -----------------------------------------------------------------------
     def sweep_sensitivities(self):
         """Of the last evaluation with gradients: dict(control_scales = d error_b / d s_bk
         (B x control_count; a complex control's two channels added), offsets = d error_b /
         d delta_bj (B x J)), and for a duration sweep evolution_time_gradients = d error_b / d T_b
-        (B). Costs of the controls alone do not depend on the tables and do not enter."""
+        (B). Costs of the controls alone do not depend on the tables and do not enter, and neither
+        does the price of time of a duration search (evolution_time_gradients() has it)."""
         scales, offsets = self.backend.sweep_sensitivities()
         scales, offsets = np.asarray(scales), np.asarray(offsets)
         if self.complex_controls:

@@ -238,6 +238,14 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     (B x J) at the seeds' best controls (one evaluation with gradients after the loop), and for a
     duration sweep evolution_time_gradients (B). User costs without a device descriptor, and
     ControlBandwidthMax with a duration sweep, are refused.
+    With a duration search (HamiltonianSweep.durations(time_bounds=..., time_weight=...)) the
+    duration of every seed is optimised with its controls: tau_b = T_b / evolution_time is one more
+    parameter of seed b (the last entry of its flat vector on the host loop; beside the controls
+    on the device), clipped in place to the box every iteration and stepped with the controls'
+    rule and learning rate. best_error includes the price of time, best_evolution_times (B) is T_b
+    at every seed's best iteration, and sweep_sensitivities is evaluated at the best controls and
+    best durations. Adam and SGD keep tau_b resident; LBFGS and plugin optimizers take the host
+    loop.
     Returns GrapeSchroedingerBatchResult.
     """
     reject_lindblad_sweep(hamiltonian)
@@ -258,6 +266,8 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
         interpolation_policy=interpolation_policy, magnus_policy=magnus_policy,
         need_gradients=True, latency_mode=items <= 128)
     stepper = batch.batched_stepper(optimizer, params)
+    if getattr(evaluator, "sweep", None) is not None and evaluator.sweep.searches_duration:
+        pstate.duration_search = evaluator  # (both loops carry tau_b beside the controls)
     result = GrapeSchroedingerBatchResult(B)
     run = (iteration_count, log_iteration_step, min_error, comm, result)
     # Device-resident form: controls, gradients, Adam moments and the best

@@ -574,6 +574,7 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     ctx->ens_M = 0;                           // ... and the ensemble
     ctx->ens_qscales_set = false;
     ctx->swp_B = 0;                           // ... and the sweep
+    ctx->dur_set = ctx->dur_mirror_stale = false;  // ... with its duration search
 
     set_hermitian_flags(ctx, p);
     if (int rc = upload_operators(ctx, p)) return rc;
@@ -765,6 +766,7 @@ int qocx_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* sc
     ctx->swp_scales_h = sc;
     ctx->swp_offsets_h = off;
     ctx->swp_B = B;
+    ctx->dur_set = ctx->dur_mirror_stale = ctx->dur_have_grad = false;  // (a new sweep: no duration search)
     // the seed-level view: one item per seed (qocx_host.h)
     ctx->ens_scale_max = smax;
     ctx->ens_offset_max = omax;
@@ -1001,7 +1003,59 @@ int ensemble_upload(qocx_ctx* ctx, int batch, const double* stage) {
     return ensemble_expand(ctx, batch);
 }
 
+// A duration search's tables as the device holds them, into swp_scales_h / swp_offsets_h
+int sweep_mirror_tables(qocx_ctx* ctx) {
+    const size_t ns = (size_t)ctx->swp_B * ctx->ens_Kr, no = (size_t)ctx->swp_B * ctx->ens_J;
+    ctx->swp_scales_h.resize(ns);
+    ctx->swp_offsets_h.resize(no);
+    HIP_TRY(hipMemcpyAsync(ctx->swp_scales_h.data(), ctx->swp_scales.p, ns * sizeof(double), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    if (no > 0)
+        HIP_TRY(hipMemcpyAsync(ctx->swp_offsets_h.data(), ctx->swp_offsets.p, no * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->dur_mirror_stale = false;
+    return 0;
+}
+
+// The tail of an evaluation of a duration search: dE_b/dtau_b + time_weight from the sensitivities
+// (with gradients), and time_weight tau_b onto the seed costs - after every other term of the cost
+int duration_finish(qocx_ctx* ctx) {
+    if (!ctx->dur_set) return 0;
+    const int B = ctx->swp_B;
+    const size_t ns = (size_t)B * ctx->ens_Kr, no = (size_t)B * ctx->ens_J;
+    if (ctx->dur_grad.ensure((size_t)B) || ctx->swp_scale_sens.ensure(ns) || ctx->swp_offset_sens.ensure(no))
+        return QOCX_ERR_HIP;
+    if (ctx->have_grads) qocx::launch_sweep_sensitivity(sweep_args(ctx), ctx->stream);
+    qocx::DurationArgs a = qocx::host::duration_args(ctx);
+    if (!ctx->have_grads) a.tau_grad = nullptr;
+    qocx::launch_duration_gradient(a, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->dur_have_grad = ctx->have_grads;
+    return 0;
+}
+
 }  // namespace
+
+namespace qocx::host {
+
+qocx::DurationArgs duration_args(qocx_ctx* ctx) {
+    qocx::DurationArgs a;
+    a.tau = ctx->dur_tau.p;
+    a.base_scales = ctx->dur_base_scales.p;
+    a.base_offsets = ctx->ens_J > 0 ? ctx->dur_base_offsets.p : nullptr;
+    a.scales = ctx->swp_scales.p;
+    a.offsets = ctx->ens_J > 0 ? ctx->swp_offsets.p : nullptr;
+    a.scale_sens = ctx->swp_scale_sens.p; a.offset_sens = ctx->swp_offset_sens.p;
+    a.tau_grad = ctx->dur_grad.p;
+    a.cost = ctx->ens_cost.p;
+    a.tau_min = ctx->dur_tau_min; a.tau_max = ctx->dur_tau_max; a.time_weight = ctx->dur_weight;
+    a.B = ctx->swp_B; a.Kr = ctx->ens_Kr; a.J = ctx->ens_J;
+    return a;
+}
+
+}  // namespace qocx::host
 
 extern "C" {
 
@@ -1040,6 +1094,8 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // per-step bound (launch_step_table) - tighter than sum_k max_t |u_k(t)| ||G_k||_1
         double smax = 0.0, smid = 0.0, sprev = 0.0;
         double* stage = ctx->pin_controls;
+        if (ctx->dur_mirror_stale)  // (a duration search whose tables qocx_opt_clip has rewritten since)
+            if (int rc = sweep_mirror_tables(ctx)) return rc;
         if (ctx->swp_B > 0) sweep_stage(ctx, controls, stage, smax, smid);
         else if (ens) ensemble_stage(ctx, batch, controls, stage, smax, smid);
         for (size_t row = 0; !ens && row < (size_t)batch * ctx->nc; ++row) {
@@ -1231,7 +1287,7 @@ int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (int rc = eval_seeds(ctx, want_grad)) return rc;
     ControlCosts& cc = ctx->control_costs;
-    if (cc.count == 0) return 0;
+    if (cc.count == 0) return duration_finish(ctx);
     // the costs of the controls, once per seed on the controls that were evaluated (ensemble: the
     // seed's own, unscaled), added to the seed's cost and gradient
     const int seeds = seed_count(ctx);
@@ -1241,7 +1297,7 @@ int qocx_eval_resident(qocx_ctx* ctx, int32_t want_grad) {
                                    cc.grad.p, seeds, (size_t)ctx->nc * seed_channels(ctx), ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return duration_finish(ctx);  // (the price of time comes after the costs of the controls)
 }
 
 int qocx_download_results(qocx_ctx* ctx, double* cost_out, double* grad_out, double* final_out) {
@@ -1298,6 +1354,7 @@ int qocx_eval_schroedinger(qocx_ctx* ctx, int32_t batch, const double* controls,
     if (rc) return rc;
     rc = eval_seeds(ctx, want_grad);  // (host buffers in and out: without qocx_set_control_costs' terms)
     if (rc) return rc;
+    if ((rc = duration_finish(ctx))) return rc;
     return qocx_download_results(ctx, cost_out, (want_grad && ctx->K > 0) ? grad_out : nullptr,
                                  final_out);
 }
@@ -1465,6 +1522,65 @@ int qocx_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double*
     if (offsets_out && no > 0)
         HIP_TRY(hipMemcpyAsync(offsets_out, ctx->swp_offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int qocx_sweep_set_durations(qocx_ctx* ctx, const double* tau, const double* base_scales,
+                             const double* base_offsets, double tau_min, double tau_max, double time_weight) {
+    if (!ctx || !tau) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (ctx->swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_set_sweep before qocx_sweep_set_durations)");
+    const int B = ctx->swp_B, Kr = ctx->ens_Kr, J = ctx->ens_J;
+    if (J < 1 || !base_offsets)
+        return fail(QOCX_ERR_ARG, "a duration search needs the drift as the first fixed channel (base_offsets [B][J], J >= 1)");
+    if (!std::isfinite(tau_min) || !std::isfinite(tau_max) || !(tau_min > 0) || !(tau_min <= tau_max))
+        return fail(QOCX_ERR_ARG, "the duration box needs finite 0 < tau_min <= tau_max");
+    if (!std::isfinite(time_weight) || time_weight < 0)
+        return fail(QOCX_ERR_ARG, "time_weight must be finite and >= 0");
+    std::vector<double> t(tau, tau + B), s0((size_t)B * Kr, 1.0), d0(base_offsets, base_offsets + (size_t)B * J);
+    if (base_scales) s0.assign(base_scales, base_scales + s0.size());
+    for (double v : t)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite duration");
+    for (double v : s0)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base control scale");
+    for (double v : d0)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base offset");
+    // the bound qocx_opt_clip commits must hold for every tau the optimizer can reach: tau_max
+    std::vector<double> smax(Kr, 0.0), omax(J, 0.0);
+    for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < Kr; ++k) smax[k] = std::max(smax[k], fabs(tau_max * s0[(size_t)b * Kr + k]));
+        for (int j = 0; j < J; ++j) omax[j] = std::max(omax[j], fabs(tau_max * d0[(size_t)b * J + j]));
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->dur_tau.upload(t, ctx->stream) || ctx->dur_base_scales.upload(s0, ctx->stream) ||
+        ctx->dur_base_offsets.upload(d0, ctx->stream) || ctx->swp_scales.ensure(s0.size()) ||
+        ctx->swp_offsets.ensure(d0.size()))
+        return QOCX_ERR_HIP;
+    ctx->dur_tau_min = tau_min; ctx->dur_tau_max = tau_max; ctx->dur_weight = time_weight;
+    qocx::launch_duration_tables(duration_args(ctx), ctx->stream);
+    HIP_TRY(hipGetLastError());
+    if (int rc = sweep_mirror_tables(ctx)) return rc;  // (synchronises: t, s0, d0 are local)
+    ctx->ens_scale_max = smax;
+    ctx->ens_offset_max = omax;
+    ctx->dur_set = true;
+    ctx->dur_have_grad = false;
+    ctx->have_results = false;
+    ctx->B = 0;  // controls must be uploaded again: their staging takes the new tables
+    ctx->ens_B = 0;
+    ctx->ms.batch = 0;
+    return 0;
+}
+
+int qocx_sweep_download_durations(qocx_ctx* ctx, double* tau_out, double* tau_grad_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_sweep_set_durations)");
+    if (tau_grad_out && (!ctx->have_results || !ctx->have_grads || ctx->ens_stale || !ctx->dur_have_grad))
+        return fail(QOCX_ERR_STATE, "duration gradients need an evaluation with gradients");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)ctx->swp_B * sizeof(double);
+    if (tau_out) HIP_TRY(hipMemcpyAsync(tau_out, ctx->dur_tau.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (tau_grad_out)
+        HIP_TRY(hipMemcpyAsync(tau_grad_out, ctx->dur_grad.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

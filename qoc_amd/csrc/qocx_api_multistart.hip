@@ -272,9 +272,11 @@ int multistart_keep_best(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const
     return 0;
 }
 
-// keeps the controls and final states of the improved seeds, then steps the seeds flagged in `update`
+// keeps the controls and final states of the improved seeds, then steps the seeds flagged in `update`;
+// `durations` (a duration search: tau, its gradient, moments and best): the same for the seeds' tau
 int multistart_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const StepRule& rule,
-                    const uint8_t* improved, const uint8_t* update) {
+                    const uint8_t* improved, const uint8_t* update,
+                    const qocx::DurationStepArgs* durations = nullptr) {
     const int B = v.seeds;
     ParamView pv;
     if (int rc = multistart_keep_best(ctx, ms, v, improved, update, pv)) return rc;
@@ -289,6 +291,17 @@ int multistart_step(qocx_ctx* ctx, MultiStart& ms, const SeedView& v, const Step
     a.epsilon = rule.epsilon; a.corr_1 = rule.corr_1; a.corr_2 = rule.corr_2;
     a.clip = rule.clip_grads; a.apply_clip = rule.apply_clip_grads ? 1 : 0;
     qocx::launch_optimizer_update(a, B, ctx->stream);
+    if (durations) {  // one more element per seed, the same rule: one thread each (qocx_duration.hip)
+        qocx::DurationStepArgs d = *durations;
+        const qocx::OptimArgs tau = d.rule;
+        d.rule = a;
+        d.rule.params = tau.params; d.rule.grads = tau.grads;
+        d.rule.moment = tau.moment; d.rule.square_moment = tau.square_moment;
+        d.rule.per_seed = 1;
+        d.improved = ms.opt_flags.p;
+        d.B = B;
+        qocx::launch_duration_step(d, ctx->stream);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the flag arrays are the caller's memory
     return 0;
@@ -388,7 +401,17 @@ int schroedinger_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStar
         return fail(QOCX_ERR_STATE, "qocx_opt_begin needs uploaded controls of a structured problem");
     HIP_TRY(hipSetDevice(ctx->device));
     // (the seeds' optimizer states; the best final states of every item)
-    return multistart_begin(ctx, ctx->ms, schroedinger_seeds(ctx), ctx->B, complex_controls, basis);
+    if (int rc = multistart_begin(ctx, ctx->ms, schroedinger_seeds(ctx), ctx->B, complex_controls, basis)) return rc;
+    if (!ctx->dur_set) return 0;
+    // a duration search: the optimizer state of the seeds' tau - moments and best, zeroed
+    const size_t B = (size_t)ctx->swp_B;
+    if (ctx->dur_m.ensure(B) || ctx->dur_v.ensure(B) || ctx->dur_best.ensure(B)) {
+        ctx->ms.batch = 0;
+        return QOCX_ERR_HIP;
+    }
+    for (DevBuf<double>* buf : {&ctx->dur_m, &ctx->dur_v, &ctx->dur_best})
+        HIP_TRY(hipMemsetAsync(buf->p, 0, B * sizeof(double), ctx->stream));
+    return 0;
 }
 
 int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& basis = BasisStart()) {
@@ -463,6 +486,13 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     // no check of the first: to be revisited)
     if ((v.total() + 255) / 256 > 0x7fffffffu || v.per_seed() > 65535u * 256u)
         return fail(QOCX_ERR_ARG, "control arrays too large for the optimizer kernels' grids");
+    if (ctx->dur_set) {
+        // a duration search: tau clipped in place to its box and the sweep's tables rewritten from it,
+        // before the next evaluation expands the seeds (ens_scale_max / ens_offset_max above are those
+        // of tau_max: the bound holds wherever the step has taken tau)
+        qocx::launch_duration_tables(duration_args(ctx), ctx->stream);
+        ctx->dur_mirror_stale = true;
+    }
     if (int rc = multistart_clip(ctx, ctx->ms, v, max_norms)) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
@@ -480,7 +510,17 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
     if (!ctx->have_results || !ctx->have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
     HIP_TRY(hipSetDevice(ctx->device));
     const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
-    if (int rc = multistart_step(ctx, ctx->ms, schroedinger_seeds(ctx), rule, improved, update)) return rc;
+    qocx::DurationStepArgs durations;
+    if (ctx->dur_set) {
+        if (!ctx->dur_have_grad) return fail(QOCX_ERR_STATE, "no duration gradients to step with");
+        durations.rule.params = ctx->dur_tau.p; durations.rule.grads = ctx->dur_grad.p;
+        durations.rule.moment = ctx->dur_m.p; durations.rule.square_moment = ctx->dur_v.p;
+        durations.best_tau = ctx->dur_best.p;
+    }
+    if (int rc = multistart_step(ctx, ctx->ms, schroedinger_seeds(ctx), rule, improved, update,
+                                 ctx->dur_set ? &durations : nullptr))
+        return rc;
+    ctx->dur_have_grad = false;
     ctx->have_results = false;  // the resident controls are no longer those of the last evaluation
     ctx->ens_stale = ctx->ens_M > 0;
     return 0;
@@ -489,6 +529,9 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
 int qocx_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    if (ctx->dur_set)
+        return fail(QOCX_ERR_STATE, "a duration search (qocx_sweep_set_durations) steps with Adam or SGD: the "
+                                    "resident L-BFGS vectors do not hold tau");
     HIP_TRY(hipSetDevice(ctx->device));
     return multistart_lbfgs_begin(ctx, ctx->ms, schroedinger_seeds(ctx), history);
 }
@@ -523,6 +566,17 @@ int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_ou
                 final_out[2 * (v * n + i)] = fin[v * np + i].x;
                 final_out[2 * (v * n + i) + 1] = fin[v * np + i].y;
             }
+    return 0;
+}
+
+int qocx_opt_download_best_durations(qocx_ctx* ctx, double* tau_out) {
+    if (!ctx || !tau_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
+    if (!ctx->dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_sweep_set_durations)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(tau_out, ctx->dur_best.p, (size_t)ctx->swp_B * sizeof(double), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

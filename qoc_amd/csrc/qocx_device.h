@@ -466,6 +466,53 @@ struct OptimArgs {
     double learning_rate, beta_1, beta_2, one_m_b1, one_m_b2, epsilon, corr_1, corr_2, clip;
     int apply_clip;
 };
+// One element of Adam.update / SGD.update (adam.py:110-165, sgd.py): the arithmetic of
+// optimizer_update_kernel and of duration_step_kernel, one definition. Every product and sum is
+// rounded on its own; division and square root are the IEEE ones.
+__device__ __forceinline__ void optimizer_update_element(const OptimArgs& a, size_t e) {
+#pragma clang fp contract(off)
+    double g = a.grads[e];
+    if (a.kind == 0) {  // SGD: params - learning_rate * grads
+        const double s = a.learning_rate * g;
+        a.params[e] = a.params[e] - s;
+        return;
+    }
+    if (a.apply_clip) g = g < -a.clip ? -a.clip : (g > a.clip ? a.clip : g);
+    const double m0 = a.beta_1 * a.moment[e], m1 = a.one_m_b1 * g;
+    const double m = m0 + m1;
+    const double sq = g * g;
+    const double v0 = a.beta_2 * a.square_moment[e], v1 = a.one_m_b2 * sq;
+    const double v = v0 + v1;
+    a.moment[e] = m;
+    a.square_moment[e] = v;
+    const double mh = m / a.corr_1, vh = v / a.corr_2;
+    const double den = sqrt(vh) + a.epsilon;
+    const double q = mh / den;
+    const double s = a.learning_rate * q;
+    a.params[e] = a.params[e] - s;
+}
+// Duration search of a sweep (qocx_duration.hip, qocx_sweep_set_durations): tau_b = T_b / T is one
+// more parameter of seed b; the sweep's tables are tau_b times the base tables s0, delta0
+struct DurationArgs {
+    double* tau;                  // [B]: read, clipped to [tau_min, tau_max], written back
+    const double* base_scales;    // s0 [B][Kr]
+    const double* base_offsets;   // delta0 [B][J] (column 0, the drift, is 1)
+    double* scales;               // tables out: [B][Kr] = tau_b s0_bk
+    double* offsets;              // tables out: [B][J] = tau_b delta0_bj
+    const double* scale_sens;     // gradient in: [B][Kr] (sweep_sensitivity_kernel)
+    const double* offset_sens;    // gradient in: [B][J]
+    double* tau_grad;             // gradient out: [B] dE_b/dtau_b + time_weight, or nullptr (none wanted)
+    double* cost;                 // [B] seed costs: cost_b + time_weight tau_b
+    double tau_min, tau_max, time_weight;
+    int B, Kr, J;
+};
+struct DurationStepArgs {
+    OptimArgs rule;               // params = tau, grads = tau_grad, the moments [B]; per_seed = 1
+    double* best_tau;             // [B]
+    const unsigned char* improved;  // [B]: seeds whose tau is kept as the best so far
+    int B;
+};
+
 void launch_clip_controls(double* controls, size_t total, int k, const double* max_norms, hipStream_t st);
 void launch_keep_best(const double* controls, double* best_controls, size_t per_seed,
                       const double2* final_states, double2* best_final, size_t final_per_seed,
@@ -631,6 +678,9 @@ void launch_ensemble_reduce(const EnsembleArgs& a, hipStream_t st);
 void launch_sweep_expand(const SystemSweepArgs& a, hipStream_t st);
 void launch_sweep_reduce(const SystemSweepArgs& a, hipStream_t st);
 void launch_sweep_sensitivity(const SystemSweepArgs& a, hipStream_t st);
+void launch_duration_tables(const DurationArgs& a, hipStream_t st);
+void launch_duration_gradient(const DurationArgs& a, hipStream_t st);
+void launch_duration_step(const DurationStepArgs& a, hipStream_t st);
 void launch_selftest(double* out, hipStream_t st);
 
 }  // namespace qocx

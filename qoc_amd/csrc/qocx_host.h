@@ -257,6 +257,15 @@ struct qocx_ctx {
     std::vector<double> swp_scales_h, swp_offsets_h;    // [B][Kr], [B][J]
     DevBuf<double> swp_scales, swp_offsets;
     DevBuf<double> swp_scale_sens, swp_offset_sens;     // [B][Kr], [B][J] (qocx_sweep_download_sensitivities)
+    // Duration search of the sweep (qocx_sweep_set_durations, qocx_duration.hip): tau_b is a parameter of
+    // seed b on the device and swp_scales / swp_offsets are derived there, tau_b times the base tables.
+    // qocx_opt_clip rewrites them without telling the host: dur_mirror_stale until sweep_mirror_tables()
+    // has fetched swp_scales_h / swp_offsets_h again (qocx_upload_controls reads them).
+    bool dur_set = false, dur_mirror_stale = false;
+    bool dur_have_grad = false;                         // dur_grad is that of the standing evaluation
+    double dur_tau_min = 0, dur_tau_max = 0, dur_weight = 0;
+    DevBuf<double> dur_tau, dur_base_scales, dur_base_offsets, dur_grad;  // [B], [B][Kr], [B][J], [B]
+    DevBuf<double> dur_m, dur_v, dur_best;              // [B] each: Adam moments of tau, best tau (qocx_opt_begin*)
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;
@@ -408,6 +417,8 @@ int seed_channels(const qocx_ctx* ctx);
 double* seed_controls(qocx_ctx* ctx);
 double* seed_costs(qocx_ctx* ctx);
 double* seed_grads(qocx_ctx* ctx);
+// ---- qocx_api.hip: duration search of a sweep (qocx_sweep_set_durations) ----
+qocx::DurationArgs duration_args(qocx_ctx* ctx);  // of the sweep's tables, sensitivities and seed costs
 
 // ---- qocx_host_resident.hip ----
 int eval_items(qocx_ctx* ctx, int32_t want_grad);

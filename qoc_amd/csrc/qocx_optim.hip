@@ -53,26 +53,7 @@ __global__ void optimizer_update_kernel(OptimArgs a) {
     if (!a.update[b]) return;
     const size_t idx = (size_t)blockIdx.y * blockDim.x + threadIdx.x;
     if (idx >= a.per_seed) return;
-    const size_t e = b * a.per_seed + idx;
-    double g = a.grads[e];
-    if (a.kind == 0) {  // SGD: params - learning_rate * grads
-        const double s = a.learning_rate * g;
-        a.params[e] = a.params[e] - s;
-        return;
-    }
-    if (a.apply_clip) g = g < -a.clip ? -a.clip : (g > a.clip ? a.clip : g);
-    const double m0 = a.beta_1 * a.moment[e], m1 = a.one_m_b1 * g;
-    const double m = m0 + m1;
-    const double sq = g * g;
-    const double v0 = a.beta_2 * a.square_moment[e], v1 = a.one_m_b2 * sq;
-    const double v = v0 + v1;
-    a.moment[e] = m;
-    a.square_moment[e] = v;
-    const double mh = m / a.corr_1, vh = v / a.corr_2;
-    const double den = sqrt(vh) + a.epsilon;
-    const double q = mh / den;
-    const double s = a.learning_rate * q;
-    a.params[e] = a.params[e] - s;
+    optimizer_update_element(a, b * a.per_seed + idx);  // (qocx_device.h: shared with qocx_duration.hip)
 }
 
 // ---- the Lindblad multi-start driver (qocx_lindblad_*): resident controls and results in seed

@@ -142,6 +142,10 @@ SIGNATURES = {
     "qocx_set_ensemble_quadratic_scales": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_set_sweep": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p, _c_double_p]),
     "qocx_sweep_download_sensitivities": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
+    "qocx_sweep_set_durations": (ctypes.c_int, [_VP, _c_double_p, _c_double_p, _c_double_p,
+                                                ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "qocx_sweep_download_durations": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
+    "qocx_opt_download_best_durations": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_keep_step_states": (ctypes.c_int, [_VP, _I32]),
     "qocx_download_step_states": (ctypes.c_int, [_VP, _c_double_p]),
     "qocx_set_lindblad_problem": (ctypes.c_int, [_VP, ctypes.POINTER(_LindbladProblem)]),
@@ -479,6 +483,54 @@ class Engine(object):
         offsets = np.empty((sw["B"], sw["J"]), dtype=np.float64)
         self._check(self._lib.qocx_sweep_download_sensitivities(self._ctx, _dp(scales), _dp(offsets)))
         return scales, offsets
+
+    def sweep_set_durations(self, tau, base_scales, base_offsets, tau_min, tau_max,
+                            time_weight=0.0):
+        """The current sweep as a duration search (qocx_sweep_set_durations): tau :: (B,) the seeds'
+        durations in units of the evolution time, clipped to [tau_min, tau_max] on the device;
+        base_scales :: (B, K - J) or None (all 1) and base_offsets :: (B, J) the tables before the
+        factor tau (the drift column of base_offsets is 1). The engine derives the sweep's tables
+        from them; controls must be uploaded again afterwards."""
+        sw = self._sweep
+        if sw is None:  # (the engine's own refusal: QOCX_ERR_STATE)
+            B, kr, J = len(np.atleast_1d(tau)), 0, 0
+        else:
+            B, kr, J = sw["B"], sw["Kr"], sw["J"]
+        tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(-1)
+        if tau.shape[0] != B:
+            raise ValueError("tau must be (B,) = ({},), got shape {}".format(B, tau.shape))
+        none = ctypes.cast(None, _c_double_p)
+        s0 = None if base_scales is None else np.ascontiguousarray(base_scales, dtype=np.float64)
+        d0 = None if base_offsets is None else np.ascontiguousarray(base_offsets, dtype=np.float64)
+        if sw is not None and s0 is not None and s0.shape != (B, kr):
+            raise ValueError("base_scales must be (B, K - J) = ({}, {}), got shape {}".format(
+                B, kr, s0.shape))
+        if sw is not None and d0 is not None and d0.shape != (B, J):
+            raise ValueError("base_offsets must be (B, J) = ({}, {}), got shape {}".format(
+                B, J, d0.shape))
+        self._check(self._lib.qocx_sweep_set_durations(
+            self._ctx, _dp(tau), none if s0 is None else _dp(s0), none if d0 is None else _dp(d0),
+            float(tau_min), float(tau_max), float(time_weight)))
+        self.batch = 0
+
+    def sweep_download_durations(self, want_grad=True):
+        """(tau [B], d error_b / d tau_b + time_weight [B] or None) of a duration search
+        (qocx_sweep_download_durations); the gradient is that of the last evaluation with
+        gradients."""
+        B = self._sweep["B"] if self._sweep is not None else 1
+        tau = np.empty(B, dtype=np.float64)
+        grad = np.empty(B, dtype=np.float64) if want_grad else None
+        self._check(self._lib.qocx_sweep_download_durations(
+            self._ctx, _dp(tau), _dp(grad) if want_grad else ctypes.cast(None, _c_double_p)))
+        return tau, grad
+
+    def opt_download_best_durations(self):
+        """tau [B] at every seed's best evaluation of the resident driver
+        (qocx_opt_download_best_durations)."""
+        B = self._sweep["B"] if self._sweep is not None else 1
+        tau = np.empty(B, dtype=np.float64)
+        self._check(self._lib.qocx_opt_download_best_durations(self._ctx, _dp(tau)))
+        return tau
 
     def _seed_channels(self):
         """Control channels of a seed: the problem's K, or K - J with an ensemble or a sweep set."""

@@ -366,6 +366,9 @@ class HamiltonianSweep(object):
     time_scaled = False
     evolution_times = None
     reference_time = None
+    searches_duration = False   # durations(time_bounds=...): tau_b is optimised as well
+    time_bounds = None
+    time_weight = 0.0
 
     def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
                  _more_counts=None):
@@ -415,7 +418,7 @@ class HamiltonianSweep(object):
 
     @classmethod
     def durations(cls, hamiltonian, evolution_times, reference_time, control_scales=None,
-                  perturbations=None, offsets=None):
+                  perturbations=None, offsets=None, time_bounds=None, time_weight=0.0):
         """
         The sweep in which seed b runs for evolution_times[b]: with tau_b = T_b / reference_time,
 
@@ -433,7 +436,37 @@ class HamiltonianSweep(object):
         count, else when the sweep meets its problem (the probe of qoc_amd.core.structure).
         The sweep carries evolution_times, reference_time and time_scaled = True;
         time_gradients() turns its sensitivities into d error_b / d T_b.
+
+        time_bounds = (T_min, T_max), finite with 0 < T_min <= T_max, turns the sweep into a duration
+        search (minimum-time GRAPE): evolution_times are the STARTING durations (inside the box, else
+        ValueError) and tau_b becomes one more optimised parameter of seed b in
+        grape_schroedinger_discrete_batch - the last entry of its flat parameter vector, stepped by
+        the optimizer with the controls' rule and learning rate. Each iteration tau_b is clipped IN
+        PLACE to [T_min, T_max] / reference_time before the controls are expanded: the optimizer's
+        own parameter is clipped, exactly as real controls are clipped by max_control_norms (and so
+        it is with complex controls and a ControlBasis too, whose controls are clipped as copies).
+        time_weight = lambda >= 0, finite (needs time_bounds), prices time linearly: the error of seed b
+        is E_b(u_b, tau_b) + lambda * tau_b, the time term one product and one rounding, added last -
+        after the state costs and the costs of the controls. The sweep then carries
+        searches_duration = True, time_bounds and time_weight; member(b) stays the system at the
+        STARTING duration. Without time_bounds the sweep is what it is without these two arguments.
         """
+        time_weight = float(time_weight)
+        if time_bounds is None:
+            if time_weight != 0.0:  # (NaN included)
+                raise ValueError("time_weight needs time_bounds (the box of a duration search)")
+        else:
+            try:
+                t_min, t_max = (float(v) for v in time_bounds)
+            except (TypeError, ValueError):
+                raise ValueError("time_bounds must be (T_min, T_max)")
+            if not (np.isfinite(t_min) and np.isfinite(t_max)):
+                raise ValueError("time_bounds must be finite")
+            if not 0 < t_min <= t_max:
+                raise ValueError("time_bounds must be ordered: 0 < T_min <= T_max")
+            if not np.isfinite(time_weight) or time_weight < 0:
+                raise ValueError("time_weight must be finite and >= 0")
+            time_bounds = (t_min, t_max)
         if not callable(hamiltonian):
             raise ValueError("hamiltonian must be a callable (controls, time) -> matrix")
         if isinstance(hamiltonian, (QuadraticHamiltonian, HamiltonianEnsemble, HamiltonianSweep)):
@@ -489,6 +522,13 @@ class HamiltonianSweep(object):
         self.time_scaled = True
         self.evolution_times = times
         self.reference_time = reference_time
+        if time_bounds is not None:
+            if np.any(times < time_bounds[0]) or np.any(times > time_bounds[1]):
+                raise ValueError("evolution_times (the starting durations) must lie inside "
+                                 "time_bounds = {}".format(time_bounds))
+            self.searches_duration = True
+            self.time_bounds = time_bounds
+            self.time_weight = time_weight
         if user_scales is not None:
             self.resolve(user_scales.shape[1], False, None,
                          [0.0, reference_time / 3.0, reference_time])
@@ -550,9 +590,28 @@ class HamiltonianSweep(object):
             return np.repeat(scales, 2, axis=1)
         return scales.copy()
 
+    @property
+    def tau_bounds(self):
+        """The box of a duration search in units of reference_time: (T_min, T_max) / reference_time."""
+        return (self.time_bounds[0] / self.reference_time,
+                self.time_bounds[1] / self.reference_time)
+
+    def base_tables(self, control_count, complex_controls):
+        """(s0 (B, K_r) or None for all 1, delta0 (B, J)) of a duration sweep: its tables before the
+        factor tau_b, per real control channel (the drift column of delta0 is 1)."""
+        if not self.time_scaled:
+            raise ValueError("base_tables belong to a duration sweep (HamiltonianSweep.durations)")
+        scales = self._user_scales
+        if scales is not None:
+            if scales.shape[1] != control_count:
+                raise ValueError("control_scales must be (B, control_count) = ({}, {}), got shape "
+                                 "{}".format(self.seed_count, control_count, scales.shape))
+            scales = np.repeat(scales, 2, axis=1) if complex_controls else scales.copy()
+        return scales, self._user_offsets.copy()
+
     def member(self, b):
         """Seed b's system as a plain callable (controls, time) -> (n x n). For a duration sweep
-        that is tau_b * hamiltonian(u, t)."""
+        that is tau_b * hamiltonian(u, t) (a duration search: at the starting duration)."""
         b = int(b)
         if not 0 <= b < self.seed_count:
             raise IndexError("seed {} out of range for {} seeds".format(b, self.seed_count))
@@ -664,7 +723,8 @@ class LindbladSweep(HamiltonianSweep):
 
     @classmethod
     def durations(cls, hamiltonian, evolution_times, reference_time, control_scales=None,
-                  perturbations=None, offsets=None, rate_scales=None):
+                  perturbations=None, offsets=None, rate_scales=None, time_bounds=None,
+                  time_weight=0.0):
         """
         The sweep in which seed b runs for evolution_times[b]: what HamiltonianSweep.durations
         builds, with rate_scales additionally multiplied by tau_b = T_b / reference_time -
@@ -675,7 +735,14 @@ class LindbladSweep(HamiltonianSweep):
         Lindbladian is scaling time). The caller passes evolution_time = reference_time.
         rate_scales :: (B, L) or None (all 1), before the factor tau_b. Every seed has rates of its
         own here, so the system must be time independent - lindblad_data included.
+        time_bounds (a duration search, HamiltonianSweep.durations) is a NotImplementedError here.
         """
+        if time_bounds is not None or time_weight != 0.0:
+            raise NotImplementedError(
+                "a duration search (time_bounds) is not built for a LindbladSweep: its per-seed "
+                "generators and sub-division counts are built on the host from tau_b = T_b / "
+                "reference_time, so tau_b cannot move on the device (HamiltonianSweep.durations "
+                "searches the duration on the Schroedinger path)")
         self = super(LindbladSweep, cls).durations(hamiltonian, evolution_times, reference_time,
                                                    control_scales, perturbations, offsets)
         user_rates = None
