@@ -52,7 +52,7 @@ DURATIONS = np.linspace(6.0, 98.0, 24)
 def main(iteration_count=150):
     sweep = LindbladSweep.durations(hamiltonian, DURATIONS, REFERENCE_TIME)
     rng = np.random.default_rng(0)
-    start = 0.02 * rng.standard_normal((len(DURATIONS), CONTROL_EVAL_COUNT, 2))
+    start = np.clip(0.02 * rng.standard_normal((len(DURATIONS), CONTROL_EVAL_COUNT, 2)), -0.06, 0.06)
     result = grape_lindblad_discrete_batch(
         2, CONTROL_EVAL_COUNT, [TargetDensityInfidelity(TARGET)], REFERENCE_TIME, INITIAL,
         SYSTEM_EVAL_COUNT, start, hamiltonian=sweep, lindblad_data=lindblad_data,

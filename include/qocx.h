@@ -483,6 +483,51 @@ int qocx_lindblad_sweep_want_rate_sensitivities(qocx_ctx* ctx, int32_t on);
 int qocx_lindblad_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out,
                                                double* rates_out);
 
+/*
+ * Duration search of a Lindblad sweep (minimum-time GRAPE under T1 / T2): tau_b = T_b / T becomes one
+ * more optimised parameter of seed b, and seed b is tau_b times the WHOLE Lindbladian - Hamiltonian,
+ * fixed channels and rates. Call after qocx_lindblad_set_sweep with per-seed rates. QOCX_ERR_STATE:
+ * no sweep, no rates tables, a problem with stage tables (fixed_subdivision > 0), or a problem whose
+ * own h0 is not zero - in a duration sweep the drift is the first fixed channel, so the control-free
+ * part is the dissipator alone and scales with tau as a whole.
+ *   tau              [B]      the starting durations; clipped to [tau_min, tau_max] on the device
+ *   base_scales      [B][K_r] s0, the control scales before the factor tau (NULL: all 1)
+ *   base_offsets     [B][J]   delta0, the offsets before the factor tau; column 0, the drift, is 1
+ *   base_rate_scales [B][L]   c0, the rate factors before the factor tau (NULL: all 1); finite, >= 0
+ *   0 < tau_min <= tau_max finite; time_weight >= 0 finite; J >= 1; L in 1 .. 4 (QOCX_ERR_ARG
+ *   otherwise, or for a non-finite entry)
+ * Once, on the host, the engine builds every seed's control-free generators, rates and norm bound at
+ * tau = 1 (rates c0_bl gamma_l) as the plain setter builds its own, and keeps them on the device
+ * beside tau, s0, delta0 and c0. From them it derives on the device
+ *     scales_bk = tau_b s0_bk    offsets_bj = tau_b delta0_bj
+ *     A0_b = tau_b A0_b(tau = 1)  gamma_bl = tau_b (c0_bl gamma_l)       (one product, one rounding each)
+ * and on the host, from the tau that comes back with the control maxima, the same scales and offsets
+ * and the bound tau_b ||L0_b(tau = 1)|| from which seed b's sub-division count follows. Against a
+ * fixed-duration sweep at the same tau the search agrees to rounding, not bit for bit: there the rates
+ * are (tau_b c0_bl) gamma_l and the generators are summed from them.
+ * A new problem or a new qocx_lindblad_set_sweep clears the search; controls must be uploaded afterwards.
+ * With durations set:
+ *   every evaluation adds time_weight tau_b to the cost of seed b, after the costs of the controls
+ *     (one product, one sum); one with gradients runs the rate sensitivities as well and produces
+ *     dE_b/dtau_b + time_weight, the chain rule through scales, offsets and rate factors in the fixed
+ *     order stated in qocx_lindblad_duration.hip. Where a piece of it cannot run two-sided (more
+ *     than one cost, a step cost, stage values that do not fit) the evaluation fails with
+ *     QOCX_ERR_STATE and leaves no gradient
+ *   qocx_lindblad_opt_begin* allocates the optimizer state of tau (moments, best tau)
+ *   qocx_lindblad_opt_clip clips tau in place to the box and rewrites the tables
+ *   qocx_lindblad_opt_step keeps tau of the improved seeds as their best and steps tau of the flagged
+ *     seeds with the rule and learning rate of the controls
+ *   qocx_lindblad_opt_lbfgs_begin returns QOCX_ERR_STATE (the resident L-BFGS vectors do not hold tau)
+ * qocx_lindblad_sweep_download_durations: tau_out [B] the current durations, tau_grad_out [B] the
+ *   gradient of the last evaluation with gradients (QOCX_ERR_STATE without one); either may be NULL.
+ * qocx_lindblad_opt_download_best_durations: tau_out [B], tau at every seed's best evaluation so far.
+ */
+int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const double* base_scales,
+                                      const double* base_offsets, const double* base_rate_scales,
+                                      double tau_min, double tau_max, double time_weight);
+int qocx_lindblad_sweep_download_durations(qocx_ctx* ctx, double* tau_out, double* tau_grad_out);
+int qocx_lindblad_opt_download_best_durations(qocx_ctx* ctx, double* tau_out);
+
 /* Per-kernel timing, measured with HIP events on the launch streams.
  * enable: 0 off, 1 every launch, 2 + k the launches of kernel k only (two events per timed launch
  * cost the evaluation 2-3 % when all ~45 launches of it carry them; bench.py times its roofline

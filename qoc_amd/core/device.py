@@ -232,10 +232,10 @@ class _Evaluator(object):
         if not hasattr(backend, self.sweep_setter):
             raise NotImplementedError("the backend {!r} does not evaluate Hamiltonian sweeps "
                                       "(no {})".format(backend, self.sweep_setter))
-        if sweep.searches_duration and not hasattr(backend, "sweep_set_durations"):
+        if sweep.searches_duration and not hasattr(backend, self.durations_setter):
             raise NotImplementedError(
                 "the backend {!r} does not search the durations of a sweep (no "
-                "sweep_set_durations): drop time_bounds, or use the engine".format(backend))
+                "{}): drop time_bounds, or use the engine".format(backend, self.durations_setter))
         matrices = sweep.resolve(control_count, complex_controls, self.hilbert_size, times)
         if matrices is not None and matrices.shape[1] != self.hilbert_size:
             raise ValueError("perturbations are {0} x {0}, the system is {1} x {1}".format(
@@ -265,6 +265,104 @@ class _Evaluator(object):
                     raise NotImplementedError(
                         "ControlBandwidthMax with a duration sweep: its frequency bins depend on "
                         "the evolution time, which differs from seed to seed")
+
+    # -- duration search of a sweep (HamiltonianSweep.durations(time_bounds=...)) -----------------
+    _time_term_resident = False
+    durations_setter = "sweep_set_durations"         # the backend's entry points for the search
+    durations_getter = "sweep_download_durations"
+
+    def _duration_rate_tables(self):
+        """What the backend's setter takes between the base offsets and the box (the Lindblad path:
+        the base rate factors)."""
+        return ()
+
+    def _device_time_weight(self):
+        """The price of time joins the error LAST, after the costs of the controls alone. Where the
+        host adds those (evaluate_batch) it adds the time term after them, the same product and the
+        same sum, and the device is given a weight of zero; where the device adds them (the resident
+        loop, time_term_resident) or there are none, the device adds the time term."""
+        if self.host_costs and not self._time_term_resident:
+            return 0.0
+        return self.sweep.time_weight
+
+    def _set_durations(self):
+        s0, d0 = self._duration_tables
+        lo, hi = self.sweep.tau_bounds
+        getattr(self.backend, self.durations_setter)(
+            self._tau, s0, d0, *self._duration_rate_tables(), lo, hi, self._device_time_weight())
+        self._tau = np.array(getattr(self.backend, self.durations_getter)(want_grad=False)[0])
+        self._tau_grad = None
+
+    def _require_search(self):
+        if self.sweep is None or not self.sweep.searches_duration:
+            raise ValueError("durations are set and read on a duration search "
+                             "(HamiltonianSweep.durations(time_bounds=...), "
+                             "LindbladSweep.duration_search)")
+
+    def time_term_resident(self, on):
+        """The resident loop adds the costs of the controls on the device, so the price of time
+        must be added there too (run_batch_resident brackets its loop with this)."""
+        self._require_search()
+        if bool(on) != self._time_term_resident:
+            self._time_term_resident = bool(on)
+            if self.host_costs:
+                self._set_durations()
+
+    def set_durations(self, tau):
+        """tau_b = T_b / reference_time of every seed for the evaluations from here on (B,); the
+        engine clips them to the box."""
+        self._require_search()
+        tau = np.array(tau, dtype=np.float64).reshape(-1)
+        if tau.shape[0] != self.sweep.seed_count:
+            raise ValueError("a sweep of {} seeds takes that many durations, got {}".format(
+                self.sweep.seed_count, tau.shape[0]))
+        if not np.all(np.isfinite(tau)):
+            raise ValueError("durations are not finite")
+        self._tau = tau
+        self._set_durations()
+
+    def set_evolution_times(self, times):
+        """T_b of every seed for the evaluations from here on (B,), clipped to time_bounds."""
+        self._require_search()
+        self.set_durations(np.asarray(times, dtype=np.float64) / self.sweep.reference_time)
+
+    def durations(self):
+        """tau_b (B,) the evaluations run at (the last evaluation's, once there is one)."""
+        self._require_search()
+        return self._tau.copy()
+
+    def evolution_times(self):
+        """T_b = tau_b * reference_time (B,) the evaluations run at."""
+        return self.durations() * self.sweep.reference_time
+
+    def duration_gradients(self):
+        """d (error_b + time_weight * tau_b) / d tau_b (B,) of the last evaluation with gradients:
+        the engine's chain rule through the tables (qocx_duration.hip, on the Lindblad path
+        qocx_lindblad_duration.hip) plus time_weight."""
+        self._require_search()
+        if self._tau_grad is None:
+            raise ValueError("duration gradients need an evaluation with gradients")
+        return self._tau_grad.copy()
+
+    def evolution_time_gradients(self):
+        """d (error_b + time_weight * tau_b) / d T_b (B,): duration_gradients() / reference_time."""
+        return self.duration_gradients() / self.sweep.reference_time
+
+    def _finish_search(self, out, want_grad):
+        """The tail of evaluate_batch with a duration search: the durations the evaluation ran at,
+        their gradient, and the price of time where the host adds it (_device_time_weight)."""
+        if self.sweep is None or not self.sweep.searches_duration:
+            return out
+        errors, grads, final, steps = out
+        tau, tau_grad = getattr(self.backend, self.durations_getter)(want_grad=bool(want_grad))
+        weight = self.sweep.time_weight
+        if weight != 0.0 and self._device_time_weight() == 0.0:
+            errors = errors + weight * tau
+            if tau_grad is not None:
+                tau_grad = tau_grad + weight
+        self._tau = np.array(tau)
+        self._tau_grad = None if tau_grad is None else np.array(tau_grad)
+        return errors, grads, final, steps
 
     def _triage_costs(self, item_count):
         """Splits self.costs into device_costs (they have a device_descriptor(); returns those
@@ -398,11 +496,16 @@ class _Evaluator(object):
         # steps. The two paths round differently and each keeps its order: with subtotal_costs the
         # host costs are summed from 0.0 and each user cost over its steps from 0.0 before they
         # join errors[b] / grads[b]; without, every term is added to errors[b] / grads[b] in turn.
+        device_share = self._device_control_costs(device_controls, want_grad)
         for b in range(batch):
             controls = None if self.control_count == 0 else controls_batch[b]
             if self._cost_controls is not None:
                 controls = self._cost_controls
-            if self.subtotal_costs:
+            if device_share is not None:  # (the costs of the controls as the resident route adds them)
+                errors[b] = errors[b] + device_share[0][b]
+                if want_grad:
+                    grads[b] = grads[b] + device_share[1][b]
+            elif self.subtotal_costs:
                 value, host_grad = self._add_host_costs(0.0, None, controls, want_grad)
                 errors[b] += value
                 if host_grad is not None:
@@ -417,6 +520,12 @@ class _Evaluator(object):
                 for cost in self.opaque_costs:
                     errors[b] = self._add_user_cost(errors[b], cost, controls, step_states[b])
         return errors, grads, final, step_states
+
+    def _device_control_costs(self, device_controls, want_grad):
+        """(costs (B,), gradients in the cost-function format or None) of the costs of the controls
+        alone where evaluate_batch takes them from the device instead of the host; None: the host
+        adds them (_add_host_costs)."""
+        return None
 
     def _add_host_costs(self, value, grad, controls, want_grad):
         """(value + c_1 + c_2 + ..., grad + bar_1 + bar_2 + ...) over the costs of the controls
@@ -634,94 +743,11 @@ class SchroedingerEvaluator(_Evaluator):
             if self.sweep.searches_duration:
                 self._set_durations()
 
-    # -- duration search of a sweep (HamiltonianSweep.durations(time_bounds=...)) -----------------
-    _time_term_resident = False
-
-    def _device_time_weight(self):
-        """The price of time joins the error LAST, after the costs of the controls alone. Where the
-        host adds those (evaluate_batch) it adds the time term after them, the same product and the
-        same sum, and the device is given a weight of zero; where the device adds them (the resident
-        loop, time_term_resident) or there are none, the device adds the time term."""
-        if self.host_costs and not self._time_term_resident:
-            return 0.0
-        return self.sweep.time_weight
-
-    def _set_durations(self):
-        s0, d0 = self._duration_tables
-        lo, hi = self.sweep.tau_bounds
-        self.backend.sweep_set_durations(self._tau, s0, d0, lo, hi, self._device_time_weight())
-        self._tau = np.array(self.backend.sweep_download_durations(want_grad=False)[0])
-        self._tau_grad = None
-
-    def _require_search(self):
-        if self.sweep is None or not self.sweep.searches_duration:
-            raise ValueError("durations are set and read on a duration search "
-                             "(HamiltonianSweep.durations(time_bounds=...))")
-
-    def time_term_resident(self, on):
-        """The resident loop adds the costs of the controls on the device, so the price of time
-        must be added there too (run_batch_resident brackets its loop with this)."""
-        self._require_search()
-        if bool(on) != self._time_term_resident:
-            self._time_term_resident = bool(on)
-            if self.host_costs:
-                self._set_durations()
-
-    def set_durations(self, tau):
-        """tau_b = T_b / reference_time of every seed for the evaluations from here on (B,); the
-        engine clips them to the box."""
-        self._require_search()
-        tau = np.array(tau, dtype=np.float64).reshape(-1)
-        if tau.shape[0] != self.sweep.seed_count:
-            raise ValueError("a sweep of {} seeds takes that many durations, got {}".format(
-                self.sweep.seed_count, tau.shape[0]))
-        if not np.all(np.isfinite(tau)):
-            raise ValueError("durations are not finite")
-        self._tau = tau
-        self._set_durations()
-
-    def set_evolution_times(self, times):
-        """T_b of every seed for the evaluations from here on (B,), clipped to time_bounds."""
-        self._require_search()
-        self.set_durations(np.asarray(times, dtype=np.float64) / self.sweep.reference_time)
-
-    def durations(self):
-        """tau_b (B,) the evaluations run at (the last evaluation's, once there is one)."""
-        self._require_search()
-        return self._tau.copy()
-
-    def evolution_times(self):
-        """T_b = tau_b * reference_time (B,) the evaluations run at."""
-        return self.durations() * self.sweep.reference_time
-
-    def duration_gradients(self):
-        """d (error_b + time_weight * tau_b) / d tau_b (B,) of the last evaluation with gradients:
-        the engine's chain rule through the tables (qocx_duration.hip) plus time_weight."""
-        self._require_search()
-        if self._tau_grad is None:
-            raise ValueError("duration gradients need an evaluation with gradients")
-        return self._tau_grad.copy()
-
-    def evolution_time_gradients(self):
-        """d (error_b + time_weight * tau_b) / d T_b (B,): duration_gradients() / reference_time."""
-        return self.duration_gradients() / self.sweep.reference_time
-
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_states=False):
         """_Evaluator.evaluate_batch; a duration search evaluates at the current durations and its
         errors include the price of time, time_weight * tau_b, added last."""
-        out = _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_states)
-        if self.sweep is None or not self.sweep.searches_duration:
-            return out
-        errors, grads, final, steps = out
-        tau, tau_grad = self.backend.sweep_download_durations(want_grad=bool(want_grad))
-        weight = self.sweep.time_weight
-        if weight != 0.0 and self._device_time_weight() == 0.0:
-            errors = errors + weight * tau
-            if tau_grad is not None:
-                tau_grad = tau_grad + weight
-        self._tau = np.array(tau)
-        self._tau_grad = None if tau_grad is None else np.array(tau_grad)
-        return errors, grads, final, steps
+        return self._finish_search(
+            _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_states), want_grad)
 
     # -- Hamiltonian sweeps -----------------------------------------------------------------------
     def sweep_sensitivities(self):
@@ -824,6 +850,8 @@ class LindbladEvaluator(_Evaluator):
     ensemble_member_costs = "lindblad_ensemble_member_costs"
     ensemble_rates_setter = "set_lindblad_ensemble_rates"
     sweep_setter = "set_lindblad_sweep"
+    durations_setter = "lindblad_sweep_set_durations"
+    durations_getter = "lindblad_sweep_download_durations"
     _ensemble_base_message = (
         "a HamiltonianEnsemble on the Lindblad path needs a base hamiltonian linear in the "
         "controls (the tangent and frozen-controls routes evaluate one control array at a "
@@ -997,6 +1025,9 @@ class LindbladEvaluator(_Evaluator):
             g = self._append_perturbations(np.asarray(g)[None])[0]
         if self.sweep is not None:
             self._reject_sweep_costs()
+            if self.sweep.searches_duration:
+                self._reject_one_sided_search(dissipators)
+                self._base_rates = self.sweep.base_rates(len(dissipators))
             g = self._append_perturbations(np.asarray(g)[None])[0]
         self._problem_args = (self.hilbert_size, self.density_count, self.device_k,
                               control_eval_count, system_eval_count, evolution_time, h0, g,
@@ -1023,10 +1054,66 @@ class LindbladEvaluator(_Evaluator):
         self.backend.set_lindblad_problem(*self._problem_args, **tables, **self._problem_kw)
         if self.sweep is not None:
             getattr(self.backend, self.sweep_setter)(*self._sweep_args)
+            if self.sweep.searches_duration:
+                self._set_durations()
         if self.ensemble is not None:
             self.backend.set_lindblad_ensemble(*self._ensemble_args)
             if self.ensemble.rate_scales is not None:
                 getattr(self.backend, self.ensemble_rates_setter)(self.ensemble.rate_scales)
+
+    def _duration_rate_tables(self):
+        return (self._base_rates,)
+
+    def _device_control_costs(self, device_controls, want_grad):
+        """A duration search keeps its two loops on the same numbers: where the resident route
+        could run (every cost of the controls has a control_descriptor() and the backend takes
+        them), evaluate_batch adds the costs of the controls as that route does - the engine's
+        kernel on the seeds' controls, one sum onto the error and one onto every gradient entry -
+        and not NumPy's cost(), which rounds the same value differently. The engine keeps the
+        descriptors only for the call: its resident evaluations add what is set."""
+        if (self.sweep is None or not self.sweep.searches_duration or not self.host_costs
+                or not hasattr(self.backend, "eval_control_costs")
+                or not controls_stay_resident(self.backend, self.control_cost_descriptors,
+                                              self.complex_controls,
+                                              self.opt_prefix + "opt_begin_complex")):
+            return None
+        from qoc_amd.engine import PATH_LINDBLAD
+        self.backend.set_control_costs(PATH_LINDBLAD, self.complex_controls,
+                                       self.control_cost_descriptors)
+        try:
+            cost, grads = self.backend.eval_control_costs(PATH_LINDBLAD, device_controls,
+                                                          want_grad=bool(want_grad))
+        finally:
+            self.backend.set_control_costs(PATH_LINDBLAD, self.complex_controls, [])
+        if grads is not None:
+            grads = structure.from_real_gradients(grads, self.complex_controls)
+        return cost, grads
+
+    def _reject_one_sided_search(self, dissipators):
+        """A duration search (LindbladSweep.duration_search) needs dE/dtau_b with its rate part,
+        which exists only where the engine's evaluation runs two-sided; what can be known here is
+        refused by name before the backend sees a problem."""
+        from qoc_amd.standard.costs import TargetDensityInfidelity
+        L = 0 if dissipators is None else len(dissipators)
+        if L == 0:
+            raise NotImplementedError(
+                "a duration search on the Lindblad path needs 1 to 4 Lindblad operators, "
+                "lindblad_data has none: without dissipation this is a closed system - use the "
+                "Schroedinger search (HamiltonianSweep.duration_search with "
+                "grape_schroedinger_discrete_batch)")
+        if L > 4:
+            raise NotImplementedError(
+                "a duration search on the Lindblad path takes 1 to 4 Lindblad operators (the "
+                "rate sensitivities behind dE/dT exist for those), lindblad_data has {}".format(L))
+        ok = (len(self.device_costs) == 1
+              and isinstance(self.device_costs[0], TargetDensityInfidelity)
+              and not self.device_costs[0].requires_step_evaluation)
+        if not ok:
+            raise NotImplementedError(
+                "a duration search on the Lindblad path takes exactly one cost of the densities, a "
+                "final TargetDensityInfidelity (costs of the controls alone may join it): the rate "
+                "part of dE/dT exists only on the engine's two-sided route, which evaluates that "
+                "cost alone; got {}".format(self.device_costs))
 
     def _check_rate_scales(self, rates, dissipators, data_dependent, shape, each):
         """rate_scales (an ensemble's (M, L), a sweep's (B, L)) against the probed lindblad_data,
@@ -1164,8 +1251,12 @@ class LindbladEvaluator(_Evaluator):
 
     def evaluate_batch(self, controls_batch, want_grad=True, want_step_densities=False):
         """_Evaluator.evaluate_batch; the step states are densities [B x N x S x n x n] (with an
-        ensemble a member axis M follows B, in the final densities too)."""
-        return _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_densities)
+        ensemble a member axis M follows B, in the final densities too). A duration search
+        (LindbladSweep.duration_search) evaluates at the current durations and its errors include
+        the price of time, time_weight * tau_b, added last."""
+        return self._finish_search(
+            _Evaluator.evaluate_batch(self, controls_batch, want_grad, want_step_densities),
+            want_grad)
 
     # -- Lindblad sweeps ------------------------------------------------------------------------
     def want_rate_sensitivities(self, on):

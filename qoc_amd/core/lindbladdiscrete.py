@@ -273,6 +273,16 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     without a device descriptor, ControlBandwidthMax with a duration sweep, a QuadraticHamiltonian,
     ensemble, sweep or non-linear base, K_r + J > 8, and - with rates of its own, so for every
     duration sweep - a time-dependent hamiltonian or lindblad_data.
+    With a duration search (LindbladSweep.duration_search) the duration of every seed is optimised
+    with its controls (minimum-time GRAPE under T1 / T2): tau_b = T_b / evolution_time is one more
+    parameter of seed b (the last entry of its flat vector on the host loop; beside the controls on
+    the device), clipped in place to the box every iteration and stepped with the controls' rule
+    and learning rate. best_error includes the price of time, best_evolution_times (B) is T_b at
+    every seed's best iteration, and sweep_sensitivities is evaluated at the best controls and best
+    durations. Adam and SGD keep tau_b resident; LBFGS and plugin optimizers take the host loop.
+    The search needs the two-sided evaluation: exactly one cost of the densities, a final
+    TargetDensityInfidelity (costs of the controls alone may join it), and 1 to 4 Lindblad
+    operators; anything else is refused by name.
     Returns GrapeLindbladBatchResult.
     """
     _check_ensemble(hamiltonian, costs)
@@ -291,6 +301,8 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
         cost_eval_step=cost_eval_step, interpolation_policy=interpolation_policy,
         need_gradients=True, control_bounds=pstate.max_control_norms)
     stepper = batch.batched_stepper(optimizer, params)
+    if evaluator.sweep is not None and evaluator.sweep.searches_duration:
+        pstate.duration_search = evaluator  # (both loops carry tau_b beside the controls)
     result = GrapeLindbladBatchResult(B)
     run = (iteration_count, log_iteration_step, min_error, comm, result)
     if batch.resident_route(stepper, optimizer, pstate, evaluator, B):

@@ -506,6 +506,7 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.ens_rates = false;
     lb.swp_B = 0;  // ... and the sweep
     lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
+    lb.dur_set = lb.dur_mirror_stale = lb.dur_have_grad = false;  // ... with its duration search
     return 0;
 }
 
@@ -561,13 +562,14 @@ namespace {
 // The rates tables of `count` members (an ensemble's members, a sweep's seeds) from rate_scales [count][L]:
 // member m is the control-free part of the plain problem with gamma_mi = c_mi * gamma_i (one product, one
 // rounding); [count][4] dumps A0L, A0R, A0L^H, A0R^H and [count][L'] rates, L' with the zero operator of pad_op
-int build_rate_tables(qocx_ctx* ctx, int count, const double* rate_scales) {
-    auto& lb = ctx->lb;
+// (the host part: the tables themselves, which a duration search keeps at tau = 1 as its base tables)
+void rate_tables_host(const qocx_ctx::Lindblad& lb, int count, const double* rate_scales, std::vector<double2>& img,
+                      std::vector<double>& gam, std::vector<double>& l0_norm) {
     const int M = count, L = lb.nops, n = lb.n;
     const size_t md = dump_elems(n), Lp = lb.gammas_h.size();
-    std::vector<double2> img((size_t)M * 4 * md);
-    std::vector<double> gam((size_t)M * std::max<size_t>(Lp, 1), 0.0);
-    lb.rate_l0_norm.assign(M, 0.0);
+    img.assign((size_t)M * 4 * md, make_double2(0.0, 0.0));
+    gam.assign((size_t)M * std::max<size_t>(Lp, 1), 0.0);
+    l0_norm.assign(M, 0.0);
     for (int m = 0; m < M; ++m) {
         std::vector<double> gm(lb.gammas_h);
         for (int i = 0; i < L; ++i) gm[i] = rate_scales[(size_t)m * L + i] * lb.gammas_h[i];
@@ -577,8 +579,15 @@ int build_rate_tables(qocx_ctx* ctx, int count, const double* rate_scales) {
         c_dump(cm_adjoint(cf.a0l, n), n, img.data() + ((size_t)m * 4 + 2) * md);
         c_dump(cm_adjoint(cf.a0r, n), n, img.data() + ((size_t)m * 4 + 3) * md);
         for (size_t i = 0; i < Lp; ++i) gam[(size_t)m * Lp + i] = gm[i];
-        lb.rate_l0_norm[m] = cf.l0_norm;
+        l0_norm[m] = cf.l0_norm;
     }
+}
+
+int build_rate_tables(qocx_ctx* ctx, int count, const double* rate_scales) {
+    auto& lb = ctx->lb;
+    std::vector<double2> img;
+    std::vector<double> gam;
+    rate_tables_host(lb, count, rate_scales, img, gam, lb.rate_l0_norm);
     if (lb.rate_a0.upload(img, ctx->stream) || lb.rate_gammas.upload(gam, ctx->stream)) return QOCX_ERR_HIP;
     return 0;
 }
@@ -668,6 +677,7 @@ int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const d
     lb.swp_offsets_h = off;
     lb.swp_B = B;
     lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
+    lb.dur_set = lb.dur_mirror_stale = lb.dur_have_grad = false;  // (a new sweep: no duration search)
     lb.swp_seed_controls = nullptr;
     // the seed-level view: one item per seed (qocx_host.h)
     lb.ens_M = 1;
@@ -990,7 +1000,8 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
     // qocx_lindblad_ratesens.hip behind every piece's combine launch; a piece that does not run two-sided
     // (or a problem with more than four operators) leaves the evaluation without them.
     const int rate_ops = lb.nops;
-    const bool want_rates = lb.swp_B > 0 && lb.swp_want_rates && want_grad;
+    // (a duration search asks for them in every evaluation with gradients: dE/dtau needs its rate part)
+    const bool want_rates = lb.swp_B > 0 && (lb.swp_want_rates || lb.dur_set) && want_grad;
     lb.swp_rates_ok = want_rates && rate_ops >= 1 && rate_ops <= 4;
     if (lb.swp_rates_ok && (lb.swp_rate_partials.ensure((size_t)lb.last_subintervals * rate_ops) ||
                             lb.swp_rate_sens.ensure((size_t)B * rate_ops)))
@@ -1199,6 +1210,87 @@ qocx::EnsembleArgs lindblad_ensemble_args(qocx_ctx* ctx, int seeds, const double
     return a;
 }
 
+// ---- duration search of a sweep (qocx_lindblad_sweep_set_durations, qocx_lindblad_duration.hip) -------
+
+// the kernels of qocx_duration.hip on the Lindblad sweep's buffers (the clip of tau and the tables)
+qocx::DurationArgs lindblad_duration_args(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    qocx::DurationArgs a;
+    a.tau = lb.dur_tau.p;
+    a.base_scales = lb.dur_base_scales.p;
+    a.base_offsets = lb.dur_base_offsets.p;
+    a.scales = lb.swp_scales.p;
+    a.offsets = lb.swp_offsets.p;
+    a.scale_sens = lb.swp_scale_sens.p; a.offset_sens = lb.swp_offset_sens.p;
+    a.tau_grad = nullptr;
+    a.cost = nullptr;
+    a.tau_min = lb.dur_tau_min; a.tau_max = lb.dur_tau_max; a.time_weight = lb.dur_weight;
+    a.B = lb.swp_B; a.Kr = lb.ens_Kr; a.J = lb.ens_J;
+    return a;
+}
+
+qocx::LindbladDurationArgs lindblad_generator_args(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    qocx::LindbladDurationArgs a;
+    a.tau = lb.dur_tau.p;
+    a.base_a0 = lb.dur_base_a0.p; a.a0 = lb.rate_a0.p;
+    a.base_gammas = lb.dur_base_gammas.p; a.gammas = lb.rate_gammas.p;
+    a.base_scales = lb.dur_base_scales.p; a.base_offsets = lb.dur_base_offsets.p;
+    a.base_rates = lb.dur_base_rates.p;
+    a.scale_sens = lb.swp_scale_sens.p; a.offset_sens = lb.swp_offset_sens.p;
+    a.rate_sens = lb.swp_rate_sens.p;
+    a.order = lb.order_dev.p;
+    a.tau_grad = nullptr;
+    a.cost = nullptr;
+    a.time_weight = lb.dur_weight;
+    a.a0_per_seed = 4 * (size_t)dump_elems(lb.n);
+    a.B = lb.swp_B; a.Kr = lb.ens_Kr; a.J = lb.ens_J; a.L = lb.nops; a.Lp = (int)lb.gammas_h.size();
+    return a;
+}
+
+// Before an evaluation of a duration search: if tau has moved on the device since the tables were
+// written (a step without the clip behind it), they are rewritten and the host mirrors re-formed
+int lindblad_duration_refresh(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    if (!lb.dur_set || !lb.dur_mirror_stale) return 0;
+    lindblad_duration_tables(ctx);
+    HIP_TRY(hipGetLastError());
+    if (int rc = lindblad_duration_fetch(ctx)) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    lindblad_duration_mirror(ctx);
+    return 0;
+}
+
+// The tail of an evaluation of a duration search, on the seeds' costs `cost` [B] once every other term
+// has joined them: dE_b/dtau_b + time_weight by the chain rule through the three tables (with
+// gradients), and time_weight tau_b onto the costs. An evaluation with gradients whose rate
+// sensitivities did not come about fails by name: it must not return a gradient without its rate part.
+int lindblad_duration_finish(qocx_ctx* ctx, int want_grad, double* cost) {
+    auto& lb = ctx->lb;
+    if (!lb.dur_set) return 0;
+    lb.dur_have_grad = false;
+    if (want_grad && !lb.swp_rates_ok) {
+        lb.have_results = lb.res_have_results = lb.swp_have_grads = false;
+        return fail(QOCX_ERR_STATE,
+                    "a duration search (qocx_lindblad_sweep_set_durations) needs the rate sensitivities in every "
+                    "evaluation with gradients, and a piece of this one did not run two-sided: that takes ONE "
+                    "cost, a final target-density infidelity, 1 .. 4 operators, the two-sided kernels and stage "
+                    "values that fit the device memory");
+    }
+    const size_t ns = (size_t)lb.swp_B * lb.ens_Kr, no = (size_t)lb.swp_B * lb.ens_J;
+    if (lb.dur_grad.ensure((size_t)lb.swp_B) || lb.swp_scale_sens.ensure(ns) || lb.swp_offset_sens.ensure(no))
+        return QOCX_ERR_HIP;
+    if (want_grad)
+        qocx::launch_sweep_sensitivity(lindblad_sweep_args(ctx, lb.swp_seed_controls, nullptr, nullptr), ctx->stream);
+    qocx::LindbladDurationArgs a = lindblad_generator_args(ctx);
+    a.tau_grad = want_grad ? lb.dur_grad.p : nullptr;
+    a.cost = cost;
+    qocx::launch_lindblad_duration_gradient(a, ctx->stream);
+    HIP_TRY(hipGetLastError());
+    lb.dur_have_grad = want_grad != 0;
+    return 0;
+}
+
 // The seeds' controls [seeds][nc][K_r] on the device expanded into their items, each item's own
 // sub-division count, the plan, the items gathered into group order and the launches of any batch:
 // results in lb.cost_out / grads / final_out in group order, lb.order / order_dev of the items.
@@ -1275,6 +1367,7 @@ int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int wan
     if ((int64_t)B * M > 0x7fffffff) return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
     const size_t items = (size_t)B * M;
     lb.have_results = false;
+    if (int rc0 = lindblad_duration_refresh(ctx)) return rc0;
     std::vector<double> umax((size_t)B * Kr);
     lindblad_control_maxima(controls, B, nc, Kr, umax.data());
     if (lb.ens_seed_controls.ensure((size_t)B * csz) || lb.ens_seed_cost.ensure(B) ||
@@ -1286,6 +1379,7 @@ int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int wan
                            hipMemcpyHostToDevice, ctx->stream));
     int rc = lindblad_ensemble_launch(ctx, B, lb.ens_seed_controls.p, umax.data(), want_grad);
     if (!rc) rc = lindblad_ensemble_reduce(ctx, B, want_grad, lb.ens_seed_cost.p, lb.ens_seed_grads.p, lb.ens_final.p);
+    if (!rc) rc = lindblad_duration_finish(ctx, want_grad, lb.ens_seed_cost.p);
     if (rc) return rc;
     std::vector<double2> fin(final_out ? items * S * md : 0);
     if (cost_out)
@@ -1308,7 +1402,133 @@ int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int wan
 }
 
 }  // namespace
+
+namespace qocx::host {
+
+void lindblad_duration_tables(qocx_ctx* ctx) {
+    qocx::launch_duration_tables(lindblad_duration_args(ctx), ctx->stream);
+    qocx::launch_lindblad_duration_generators(lindblad_generator_args(ctx), ctx->stream);
+}
+
+int lindblad_duration_fetch(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    lb.dur_tau_h.resize((size_t)lb.swp_B);
+    HIP_TRY(hipMemcpyAsync(lb.dur_tau_h.data(), lb.dur_tau.p, (size_t)lb.swp_B * sizeof(double), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    return 0;
+}
+
+// swp_scales_h, swp_offsets_h and rate_l0_norm as the device holds the tables: the same single products
+// of the clipped tau (a product alone is rounded once on either side)
+void lindblad_duration_mirror(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    const int B = lb.swp_B, Kr = lb.ens_Kr, J = lb.ens_J;
+    lb.swp_scales_h.resize((size_t)B * Kr);
+    lb.swp_offsets_h.resize((size_t)B * J);
+    lb.rate_l0_norm.resize((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        const double tau = lb.dur_tau_h[b];
+        for (int k = 0; k < Kr; ++k)
+            lb.swp_scales_h[(size_t)b * Kr + k] = tau * lb.dur_base_scales_h[(size_t)b * Kr + k];
+        for (int j = 0; j < J; ++j)
+            lb.swp_offsets_h[(size_t)b * J + j] = tau * lb.dur_base_offsets_h[(size_t)b * J + j];
+        lb.rate_l0_norm[b] = tau * lb.dur_l0_norm0[b];
+    }
+    lb.dur_mirror_stale = false;
+}
+
+}  // namespace qocx::host
 }  // extern "C++"
+
+int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const double* base_scales,
+                                      const double* base_offsets, const double* base_rate_scales, double tau_min,
+                                      double tau_max, double time_weight) {
+    if (!ctx || !tau) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (!lb.has_problem || lb.swp_B == 0)
+        return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep before qocx_lindblad_sweep_set_durations)");
+    if (lb.fixed_ksub > 0)
+        return fail(QOCX_ERR_STATE, "a duration search needs a static problem: this one was set with stage tables "
+                                    "(fixed_subdivision > 0), which hold one control-free generator per stage");
+    if (!lb.ens_rates)
+        return fail(QOCX_ERR_STATE, "a duration search needs per-seed rates (rate_scales of qocx_lindblad_set_sweep): "
+                                    "tau_b scales the rates of seed b with its Hamiltonian");
+    for (double v : lb.h0_h)
+        if (v != 0.0)
+            return fail(QOCX_ERR_STATE, "a duration search needs a problem whose own h0 is zero (the drift is the "
+                                        "first fixed channel): the control-free part is then the dissipator alone "
+                                        "and scales with tau as a whole");
+    const int B = lb.swp_B, Kr = lb.ens_Kr, J = lb.ens_J, L = lb.nops;
+    if (J < 1 || !base_offsets)
+        return fail(QOCX_ERR_ARG, "a duration search needs the drift as the first fixed channel (base_offsets [B][J], J >= 1)");
+    if (L < 1 || L > 4)
+        return fail(QOCX_ERR_ARG, "a duration search takes 1 .. 4 Lindblad operators (the rate sensitivities exist for those)");
+    if (!std::isfinite(tau_min) || !std::isfinite(tau_max) || !(tau_min > 0) || !(tau_min <= tau_max))
+        return fail(QOCX_ERR_ARG, "the duration box needs finite 0 < tau_min <= tau_max");
+    if (!std::isfinite(time_weight) || time_weight < 0)
+        return fail(QOCX_ERR_ARG, "time_weight must be finite and >= 0");
+    std::vector<double> t(tau, tau + B), s0((size_t)B * Kr, 1.0), d0(base_offsets, base_offsets + (size_t)B * J);
+    std::vector<double> c0((size_t)B * L, 1.0);
+    if (base_scales) s0.assign(base_scales, base_scales + s0.size());
+    if (base_rate_scales) c0.assign(base_rate_scales, base_rate_scales + c0.size());
+    for (double v : t)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite duration");
+    for (double v : s0)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base control scale");
+    for (double v : d0)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base offset");
+    for (double v : c0)
+        if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "base_rate_scales must be finite and >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the base tables, once: every seed's control-free generators, rates and norm bound at tau = 1, built
+    // as the plain setter builds its own (a later call of the same search with the same c0 - the host loop
+    // sets tau every iteration - keeps them)
+    if (!lb.dur_set || lb.dur_base_rates_h != c0) {
+        std::vector<double2> img;
+        std::vector<double> gam;
+        lb.dur_set = false;
+        rate_tables_host(lb, B, c0.data(), img, gam, lb.dur_l0_norm0);
+        if (lb.dur_base_a0.upload(img, ctx->stream) || lb.dur_base_gammas.upload(gam, ctx->stream) ||
+            lb.rate_a0.ensure(img.size()) || lb.rate_gammas.ensure(gam.size()) ||
+            lb.dur_base_rates.upload(c0, ctx->stream))
+            return QOCX_ERR_HIP;
+        lb.dur_base_rates_h = c0;
+    }
+    if (lb.dur_tau.upload(t, ctx->stream) || lb.dur_base_scales.upload(s0, ctx->stream) ||
+        lb.dur_base_offsets.upload(d0, ctx->stream) || lb.swp_scales.ensure(s0.size()) ||
+        lb.swp_offsets.ensure(d0.size()))
+        return QOCX_ERR_HIP;
+    lb.dur_base_scales_h = s0;
+    lb.dur_base_offsets_h = d0;
+    lb.dur_tau_min = tau_min; lb.dur_tau_max = tau_max; lb.dur_weight = time_weight;
+    lindblad_duration_tables(ctx);
+    HIP_TRY(hipGetLastError());
+    if (int rc = lindblad_duration_fetch(ctx)) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    lindblad_duration_mirror(ctx);
+    lb.dur_set = true;
+    lb.dur_have_grad = false;
+    lb.have_results = false;
+    lb.swp_have_grads = false;
+    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again, and the driver begun again
+    lb.res_have_results = false;
+    return 0;
+}
+
+int qocx_lindblad_sweep_download_durations(qocx_ctx* ctx, double* tau_out, double* tau_grad_out) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    auto& lb = ctx->lb;
+    if (!lb.dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_lindblad_sweep_set_durations)");
+    if (tau_grad_out && (!lb.have_results || !lb.swp_have_grads || !lb.dur_have_grad))
+        return fail(QOCX_ERR_STATE, "duration gradients need an evaluation with gradients");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)lb.swp_B * sizeof(double);
+    if (tau_out) HIP_TRY(hipMemcpyAsync(tau_out, lb.dur_tau.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (tau_grad_out)
+        HIP_TRY(hipMemcpyAsync(tau_grad_out, lb.dur_grad.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
 
 int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int32_t want_grad,
                        double* cost_out, double* grad_out, double* final_out) {
@@ -1473,6 +1693,13 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
     const bool ens = lb.ens_M > 0;
     want_grad = want_grad ? 1 : 0;
     lb.res_have_results = false;
+    // (a duration search whose tau has moved since the clip: tau comes back with the maxima below)
+    const bool refresh = lb.dur_set && lb.dur_mirror_stale;
+    if (refresh) {
+        lindblad_duration_tables(ctx);
+        HIP_TRY(hipGetLastError());
+        if (int rc0 = lindblad_duration_fetch(ctx)) return rc0;
+    }
     // the sub-division decision needs the control maxima on the host, except on a fixed grid
     if (lb.fixed_ksub == 0 && !lb.umax_valid) {
         if (lb.umax.ensure((size_t)B * K)) return QOCX_ERR_HIP;
@@ -1483,7 +1710,10 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
                                hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         lb.umax_valid = true;
+    } else if (refresh) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
+    if (refresh) lindblad_duration_mirror(ctx);
     const double* umax = lb.fixed_ksub == 0 ? lb.umax_host.data() : nullptr;
     if (lb.res_cost.ensure(B) || lb.res_grads.ensure((size_t)B * csz) ||
         lb.res_final.ensure((size_t)B * items * S * md))
@@ -1517,6 +1747,8 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
                                        B, csz, ctx->stream);
         HIP_TRY(hipGetLastError());
     }
+    // (a duration search: the price of time comes after the costs of the controls)
+    if (int rc3 = lindblad_duration_finish(ctx, want_grad, lb.res_cost.p)) return rc3;
     if (ctx->timing) {  // (the events of the launches are read once they have run)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         time_collect(ctx);

@@ -420,7 +420,17 @@ int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& b
     if (!lb.has_problem || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin needs resident Lindblad controls");
     HIP_TRY(hipSetDevice(ctx->device));
-    return multistart_begin(ctx, lb.ms, lindblad_seeds(ctx), lb.res_B, complex_controls, basis);
+    if (int rc = multistart_begin(ctx, lb.ms, lindblad_seeds(ctx), lb.res_B, complex_controls, basis)) return rc;
+    if (!lb.dur_set) return 0;
+    // a duration search: the optimizer state of the seeds' tau - moments and best, zeroed
+    const size_t B = (size_t)lb.swp_B;
+    if (lb.dur_m.ensure(B) || lb.dur_v.ensure(B) || lb.dur_best.ensure(B)) {
+        lb.ms.batch = 0;
+        return QOCX_ERR_HIP;
+    }
+    for (DevBuf<double>* buf : {&lb.dur_m, &lb.dur_v, &lb.dur_best})
+        HIP_TRY(hipMemsetAsync(buf->p, 0, B * sizeof(double), ctx->stream));
+    return 0;
 }
 
 // the arguments of *_opt_begin_basis, checked
@@ -613,6 +623,14 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     for (int k = 0; k < Kn; ++k)
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
     HIP_TRY(hipSetDevice(ctx->device));
+    if (lb.dur_set) {
+        // a duration search: tau clipped in place to its box, the sweep's tables and the seeds' generator
+        // tables rewritten from it before the next evaluation expands the seeds; tau comes back to the
+        // host in the synchronisation below, for the mirrors the sub-division decision reads
+        lindblad_duration_tables(ctx);
+        lb.dur_mirror_stale = true;
+        if (int rc = lindblad_duration_fetch(ctx)) return rc;
+    }
     if (int rc = multistart_clip(ctx, lb.ms, lindblad_seeds(ctx), max_norms)) return rc;
     // the maxima of the clipped controls decide the next evaluation's sub-divisions: they come back
     // with the synchronisation the clip needs anyway (none on a fixed grid)
@@ -628,6 +646,7 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
     lb.umax_valid = maxima;
     lb.res_have_results = false;
+    if (lb.dur_set) lindblad_duration_mirror(ctx);
     return 0;
 }
 
@@ -642,7 +661,18 @@ int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
     if (!lb.res_have_results || !lb.res_have_grads) return fail(QOCX_ERR_STATE, "no gradients to step with");
     HIP_TRY(hipSetDevice(ctx->device));
     const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
-    if (int rc = multistart_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update)) return rc;
+    qocx::DurationStepArgs durations;
+    if (lb.dur_set) {
+        if (!lb.dur_have_grad) return fail(QOCX_ERR_STATE, "no duration gradients to step with");
+        durations.rule.params = lb.dur_tau.p; durations.rule.grads = lb.dur_grad.p;
+        durations.rule.moment = lb.dur_m.p; durations.rule.square_moment = lb.dur_v.p;
+        durations.best_tau = lb.dur_best.p;
+    }
+    if (int rc = multistart_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update,
+                                 lb.dur_set ? &durations : nullptr))
+        return rc;
+    lb.dur_have_grad = false;
+    lb.dur_mirror_stale = lb.dur_set;  // (tau has moved: the tables are rewritten by the clip, or before the next evaluation)
     lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
     lb.umax_valid = false;
     return 0;
@@ -653,6 +683,9 @@ int qocx_lindblad_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history) {
     auto& lb = ctx->lb;
     if (lb.ms.batch != lb.res_B || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    if (lb.dur_set)
+        return fail(QOCX_ERR_STATE, "a duration search (qocx_lindblad_sweep_set_durations) steps with Adam or SGD: "
+                                    "the resident L-BFGS vectors do not hold tau");
     HIP_TRY(hipSetDevice(ctx->device));
     return multistart_lbfgs_begin(ctx, lb.ms, lindblad_seeds(ctx), history);
 }
@@ -690,6 +723,19 @@ int qocx_lindblad_opt_download_best(qocx_ctx* ctx, double* controls_out, double*
         return rc;
     if (final_out)
         for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
+    return 0;
+}
+
+int qocx_lindblad_opt_download_best_durations(qocx_ctx* ctx, double* tau_out) {
+    if (!ctx || !tau_out) return fail(QOCX_ERR_ARG, "NULL argument");
+    auto& lb = ctx->lb;
+    if (lb.ms.batch != lb.res_B || lb.res_B < 1)
+        return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
+    if (!lb.dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_lindblad_sweep_set_durations)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(tau_out, lb.dur_best.p, (size_t)lb.swp_B * sizeof(double), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

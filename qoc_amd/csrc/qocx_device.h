@@ -512,6 +512,28 @@ struct DurationStepArgs {
     const unsigned char* improved;  // [B]: seeds whose tau is kept as the best so far
     int B;
 };
+// Duration search of a Lindblad sweep (qocx_lindblad_duration.hip, qocx_lindblad_sweep_set_durations):
+// the per-seed control-free generators and rates are tau_b times base tables built at tau = 1, and the
+// chain rule runs through the scales, the offsets and the rate factors c_bl = tau_b c0_bl
+struct LindbladDurationArgs {
+    const double* tau;            // [B], clipped by duration_tables_kernel
+    const double2* base_a0;       // [B][4] dumps A0L, A0R, A0L^H, A0R^H of the rates c0_b gamma
+    double2* a0;                  // tables out: [B][4] dumps = tau_b base_a0
+    const double* base_gammas;    // [B][Lp]: c0_bl gamma_l
+    double* gammas;               // tables out: [B][Lp] = tau_b base_gammas
+    const double* base_scales;    // s0 [B][Kr]
+    const double* base_offsets;   // delta0 [B][J]
+    const double* base_rates;     // c0 [B][L]
+    const double* scale_sens;     // gradient in: [B][Kr], seed order (sweep_sensitivity_kernel)
+    const double* offset_sens;    // gradient in: [B][J], seed order
+    const double* rate_sens;      // gradient in: [B][L], LAUNCH order (qocx_lindblad_ratesens.hip)
+    const int* order;             // [B]: the seed launched at position p
+    double* tau_grad;             // gradient out: [B] dE_b/dtau_b + time_weight, or nullptr (none wanted)
+    double* cost;                 // [B] seed costs: cost_b + time_weight tau_b
+    double time_weight;
+    size_t a0_per_seed;           // 4 md double2
+    int B, Kr, J, L, Lp;
+};
 
 void launch_clip_controls(double* controls, size_t total, int k, const double* max_norms, hipStream_t st);
 void launch_keep_best(const double* controls, double* best_controls, size_t per_seed,
@@ -681,6 +703,8 @@ void launch_sweep_sensitivity(const SystemSweepArgs& a, hipStream_t st);
 void launch_duration_tables(const DurationArgs& a, hipStream_t st);
 void launch_duration_gradient(const DurationArgs& a, hipStream_t st);
 void launch_duration_step(const DurationStepArgs& a, hipStream_t st);
+void launch_lindblad_duration_generators(const LindbladDurationArgs& a, hipStream_t st);
+void launch_lindblad_duration_gradient(const LindbladDurationArgs& a, hipStream_t st);
 void launch_selftest(double* out, hipStream_t st);
 
 }  // namespace qocx

@@ -372,6 +372,21 @@ struct qocx_ctx {
         bool swp_want_rates = false, swp_rates_ok = false;
         DevBuf<double2> swp_ldl;                            // [L] dumps of L_l^H L_l
         DevBuf<double> swp_rate_partials, swp_rate_sens;    // [sub-intervals of the evaluation][L]; [B][L], launch order
+        // Duration search of the sweep (qocx_lindblad_sweep_set_durations, qocx_lindblad_duration.hip): tau_b is a
+        // parameter of seed b on the device; swp_scales / swp_offsets and the rates tables (rate_a0,
+        // rate_gammas) are derived there, tau_b times the base tables below. The host mirrors - swp_scales_h,
+        // swp_offsets_h and rate_l0_norm, which decide the sub-division counts - are re-formed from tau by
+        // the same single products once it has come back (lindblad_duration_mirror); dur_mirror_stale: tau
+        // has moved on the device since the tables were last written.
+        bool dur_set = false, dur_mirror_stale = false;
+        bool dur_have_grad = false;                         // dur_grad is that of the standing evaluation
+        double dur_tau_min = 0, dur_tau_max = 0, dur_weight = 0;
+        DevBuf<double> dur_tau, dur_base_scales, dur_base_offsets, dur_base_rates, dur_grad;  // [B], [B][Kr], [B][J], [B][L], [B]
+        DevBuf<double2> dur_base_a0;                        // [B][4] dumps at tau = 1 (rates c0_b gamma)
+        DevBuf<double> dur_base_gammas;                     // [B][L'] at tau = 1
+        std::vector<double> dur_tau_h, dur_base_scales_h, dur_base_offsets_h, dur_base_rates_h;  // host copies
+        std::vector<double> dur_l0_norm0;                   // [B]: the seeds' l0_norm at tau = 1
+        DevBuf<double> dur_m, dur_v, dur_best;              // [B] each: Adam moments of tau, best tau
         int seed_channels() const { return ens_M > 0 ? ens_Kr : K; }
         size_t seed_items() const { return ens_M > 0 ? (size_t)ens_M : 1; }
     } lb;
@@ -419,6 +434,14 @@ double* seed_costs(qocx_ctx* ctx);
 double* seed_grads(qocx_ctx* ctx);
 // ---- qocx_api.hip: duration search of a sweep (qocx_sweep_set_durations) ----
 qocx::DurationArgs duration_args(qocx_ctx* ctx);  // of the sweep's tables, sensitivities and seed costs
+
+// ---- qocx_api_lindblad.hip: duration search of a Lindblad sweep (qocx_lindblad_sweep_set_durations) ----
+// clips tau and rewrites the sweep's tables and the seeds' generator tables from it (enqueued)
+void lindblad_duration_tables(qocx_ctx* ctx);
+// enqueues the copy of tau to the host; after the caller's synchronisation lindblad_duration_mirror()
+// re-forms the host mirrors from it
+int lindblad_duration_fetch(qocx_ctx* ctx);
+void lindblad_duration_mirror(qocx_ctx* ctx);
 
 // ---- qocx_host_resident.hip ----
 int eval_items(qocx_ctx* ctx, int32_t want_grad);

@@ -166,7 +166,12 @@ SIGNATURES = {
     "qocx_lindblad_sweep_want_rate_sensitivities": (ctypes.c_int, [_VP, _I32]),
     "qocx_lindblad_sweep_download_sensitivities": (ctypes.c_int, [_VP, _c_double_p, _c_double_p,
                                                                   _c_double_p]),
-    "qocx_set_timing": (ctypes.c_int, [_VP, _I32]),
+    "qocx_lindblad_sweep_set_durations": (ctypes.c_int, [_VP, _c_double_p, _c_double_p, _c_double_p,
+                                                         _c_double_p, ctypes.c_double,
+                                                         ctypes.c_double, ctypes.c_double]),
+    "qocx_lindblad_sweep_download_durations": (ctypes.c_int, [_VP, _c_double_p, _c_double_p]),
+    "qocx_lindblad_opt_download_best_durations": (ctypes.c_int, [_VP, _c_double_p]),
+    "qocx_set_timing":(ctypes.c_int, [_VP, _I32]),
     "qocx_get_timing": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(_I64), _c_double_p]),
     "qocx_reset_timing": (ctypes.c_int, [_VP]),
     "qocx_set_chunk": (ctypes.c_int, [_VP, _I32]),
@@ -807,6 +812,55 @@ class Engine(object):
             else:
                 self._check(code)
         return scales, offsets, rates
+
+    def lindblad_sweep_set_durations(self, tau, base_scales, base_offsets, base_rate_scales,
+                                     tau_min, tau_max, time_weight=0.0):
+        """The current Lindblad sweep as a duration search (qocx_lindblad_sweep_set_durations):
+        tau :: (B,) the seeds' durations in units of the evolution time, clipped to
+        [tau_min, tau_max] on the device; base_scales :: (B, K - J) or None (all 1), base_offsets ::
+        (B, J) and base_rate_scales :: (B, L) or None (all 1) the tables before the factor tau (the
+        drift column of base_offsets is 1). The engine derives the sweep's tables and the seeds'
+        control-free generators from them; controls must be uploaded again afterwards."""
+        sw = self._lindblad_sweep
+        tau = np.ascontiguousarray(tau, dtype=np.float64).reshape(-1)
+        none = ctypes.cast(None, _c_double_p)
+        s0 = None if base_scales is None else np.ascontiguousarray(base_scales, dtype=np.float64)
+        d0 = None if base_offsets is None else np.ascontiguousarray(base_offsets, dtype=np.float64)
+        c0 = (None if base_rate_scales is None
+              else np.ascontiguousarray(base_rate_scales, dtype=np.float64))
+        if sw is not None:  # (without a sweep the engine refuses by itself: QOCX_ERR_STATE)
+            B = sw["B"]
+            if tau.shape[0] != B:
+                raise ValueError("tau must be (B,) = ({},), got shape {}".format(B, tau.shape))
+            for name, table, width in (("base_scales", s0, sw["Kr"]), ("base_offsets", d0, sw["J"]),
+                                       ("base_rate_scales", c0, sw["L"])):
+                if table is not None and table.shape != (B, width):
+                    raise ValueError("{} must be ({}, {}), got shape {}".format(
+                        name, B, width, table.shape))
+        self._check(self._lib.qocx_lindblad_sweep_set_durations(
+            self._ctx, _dp(tau), none if s0 is None else _dp(s0), none if d0 is None else _dp(d0),
+            none if c0 is None else _dp(c0), float(tau_min), float(tau_max), float(time_weight)))
+        self._lindblad_batch = self._lindblad_seeds = 0
+        self._lindblad_resident_batch = 0
+
+    def lindblad_sweep_download_durations(self, want_grad=True):
+        """(tau [B], d error_b / d tau_b + time_weight [B] or None) of a duration search
+        (qocx_lindblad_sweep_download_durations); the gradient is that of the last evaluation with
+        gradients."""
+        B = self._lindblad_sweep["B"] if self._lindblad_sweep is not None else 1
+        tau = np.empty(B, dtype=np.float64)
+        grad = np.empty(B, dtype=np.float64) if want_grad else None
+        self._check(self._lib.qocx_lindblad_sweep_download_durations(
+            self._ctx, _dp(tau), _dp(grad) if want_grad else ctypes.cast(None, _c_double_p)))
+        return tau, grad
+
+    def lindblad_opt_download_best_durations(self):
+        """tau [B] at every seed's best evaluation of the resident driver
+        (qocx_lindblad_opt_download_best_durations)."""
+        B = self._lindblad_sweep["B"] if self._lindblad_sweep is not None else 1
+        tau = np.empty(B, dtype=np.float64)
+        self._check(self._lib.qocx_lindblad_opt_download_best_durations(self._ctx, _dp(tau)))
+        return tau
 
     def evaluate_lindblad(self, controls, want_grad=True, want_final=True):
         """(cost[B], grads[B,Nc,K] or None, final_densities[B,S,n,n]) for controls[B,Nc,K]; with an

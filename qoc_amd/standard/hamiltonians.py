@@ -534,6 +534,17 @@ class HamiltonianSweep(object):
                          [0.0, reference_time / 3.0, reference_time])
         return self
 
+    @classmethod
+    def duration_search(cls, hamiltonian, evolution_times, reference_time, time_bounds,
+                        time_weight=0.0, control_scales=None, perturbations=None, offsets=None):
+        """The duration search under a name of its own: exactly what durations(..., time_bounds=,
+        time_weight=) builds (see there). time_bounds is required."""
+        if time_bounds is None:
+            raise ValueError("time_bounds must be (T_min, T_max)")
+        return cls.durations(hamiltonian, evolution_times, reference_time,
+                             control_scales=control_scales, perturbations=perturbations,
+                             offsets=offsets, time_bounds=time_bounds, time_weight=time_weight)
+
     @property
     def perturbation_count(self):
         """J, the number of fixed matrices (a duration sweep: the drift D_0 among them)."""
@@ -707,7 +718,8 @@ class LindbladSweep(HamiltonianSweep):
     member(b) and member_lindblad_data(b, lindblad_data) are seed b's system as plain callables,
     slice(lo, hi) the sweep of a contiguous block of seeds.
 
-    LindbladSweep.durations(...) builds the sweep in which seed b runs for its own evolution time.
+    LindbladSweep.durations(...) builds the sweep in which seed b runs for its own evolution time,
+    LindbladSweep.duration_search(...) the one in which that time is optimised with the pulse.
     """
 
     def __init__(self, hamiltonian, perturbations=None, offsets=None, control_scales=None,
@@ -735,16 +747,58 @@ class LindbladSweep(HamiltonianSweep):
         Lindbladian is scaling time). The caller passes evolution_time = reference_time.
         rate_scales :: (B, L) or None (all 1), before the factor tau_b. Every seed has rates of its
         own here, so the system must be time independent - lindblad_data included.
-        time_bounds (a duration search, HamiltonianSweep.durations) is a NotImplementedError here.
+        time_bounds is a NotImplementedError here: the sweep this constructor builds has its
+        per-seed generators fixed by the host. LindbladSweep.duration_search builds the search.
         """
         if time_bounds is not None or time_weight != 0.0:
             raise NotImplementedError(
-                "a duration search (time_bounds) is not built for a LindbladSweep: its per-seed "
-                "generators and sub-division counts are built on the host from tau_b = T_b / "
-                "reference_time, so tau_b cannot move on the device (HamiltonianSweep.durations "
-                "searches the duration on the Schroedinger path)")
+                "LindbladSweep.durations builds fixed durations: its per-seed generators and "
+                "sub-division counts are built on the host from tau_b = T_b / reference_time. "
+                "LindbladSweep.duration_search(..., time_bounds, time_weight) builds the search, "
+                "whose generators follow tau_b on the device")
+        return cls._durations(hamiltonian, evolution_times, reference_time, control_scales,
+                              perturbations, offsets, rate_scales, None, 0.0)
+
+    @classmethod
+    def duration_search(cls, hamiltonian, evolution_times, reference_time, time_bounds,
+                        time_weight=0.0, control_scales=None, perturbations=None, offsets=None,
+                        rate_scales=None):
+        """
+        The duration search of open systems (minimum-time GRAPE under T1 / T2): seed b is
+
+            tau_b * (the whole Lindbladian)  on  [0, reference_time],   tau_b = T_b / reference_time,
+
+        as in LindbladSweep.durations, and tau_b is one more optimised parameter of seed b in
+        grape_lindblad_discrete_batch - the last entry of its flat parameter vector on the host
+        loop, beside the controls on the device -, clipped in place to time_bounds /
+        reference_time every iteration and stepped with the controls' rule and learning rate.
+        The error of seed b is E_b(u_b, tau_b) + time_weight * tau_b, the time term one product and
+        one sum, added last. Under dissipation E_b has a minimum in T_b of its own, so
+        time_weight = 0 already has something to find.
+
+        evolution_times are the STARTING durations; time_bounds = (T_min, T_max) and time_weight as
+        in HamiltonianSweep.durations, with the same ValueErrors; control_scales, perturbations,
+        offsets and rate_scales are the values before the factor tau_b. member(b) and
+        member_lindblad_data(b, .) stay the system at the starting duration.
+
+        The gradient with respect to tau_b needs the rate sensitivities, which exist where the
+        evaluation runs two-sided: ONE state cost, a final TargetDensityInfidelity (costs of the
+        controls alone may join it), 1 to 4 Lindblad operators, a time-independent system.
+        LindbladEvaluator refuses anything else by name. Against LindbladSweep.durations at the
+        same durations the search agrees to rounding, not bit for bit: tau * sum (c0 gamma) L^H L
+        and sum (tau c0 gamma) L^H L round differently.
+        """
+        if time_bounds is None:
+            raise ValueError("time_bounds must be (T_min, T_max)")
+        return cls._durations(hamiltonian, evolution_times, reference_time, control_scales,
+                              perturbations, offsets, rate_scales, time_bounds, time_weight)
+
+    @classmethod
+    def _durations(cls, hamiltonian, evolution_times, reference_time, control_scales,
+                   perturbations, offsets, rate_scales, time_bounds, time_weight):
         self = super(LindbladSweep, cls).durations(hamiltonian, evolution_times, reference_time,
-                                                   control_scales, perturbations, offsets)
+                                                   control_scales, perturbations, offsets,
+                                                   time_bounds, time_weight)
         user_rates = None
         if rate_scales is not None:
             user_rates = _rate_scales_array(rate_scales)
@@ -774,6 +828,16 @@ class LindbladSweep(HamiltonianSweep):
             raise ValueError("rate_scales must be (B, L) with L = {} Lindblad operators of "
                              "lindblad_data, got shape {}".format(L, rates.shape))
         return rates
+
+    def base_rates(self, operator_count):
+        """c0 (B, L) of a duration sweep, its rate factors before the factor tau_b; None for all 1."""
+        if not self.time_scaled:
+            raise ValueError("base_rates belong to a duration sweep (LindbladSweep.durations)")
+        rates = self._user_rates
+        if rates is not None and rates.shape[1] != int(operator_count):
+            raise ValueError("rate_scales must be (B, L) with L = {} Lindblad operators of "
+                             "lindblad_data, got shape {}".format(int(operator_count), rates.shape))
+        return None if rates is None else rates.copy()
 
     def member_lindblad_data(self, b, lindblad_data):
         """Seed b's lindblad_data as a plain callable time -> (c_b * dissipators, operators): the
