@@ -2,10 +2,12 @@
 lindblad_model.py - TEST INFRASTRUCTURE: NumPy model of the device algorithm for the Lindblad
 path: the matrix-form master equation
 
-    d rho / dt = A(t) rho + rho A(t)^H + sum_i gamma_i L_i rho L_i^H,
-    A(t) = -i (H0 + sum_k u_k(t) G_k) - 1/2 sum_i gamma_i L_i^H L_i
+    d rho / dt = A(t) rho + rho B(t) + sum_i gamma_i L_i rho L_i^H,
+    A(t) = -i H(t) - D / 2,  B(t) = +i H(t) - D / 2,  H(t) = H0 + sum_k u_k(t) G_k,
+    D = sum_i gamma_i L_i^H L_i
 
-integrated with a FIXED-step explicit Runge-Kutta scheme (Dormand-Prince 8(5,3), 12 stages,
+(B = A^H for a Hermitian H; a Hamiltonian that is not Hermitian enters as the plain commutator
+-i [H, rho], as in the reference's get_lindbladian and in the engine's a0l / a0r) integrated with a FIXED-step explicit Runge-Kutta scheme (Dormand-Prince 8(5,3), 12 stages,
 coefficients from scipy) on sub-intervals that never straddle a control knot, and its exact
 discrete adjoint with per-substep recomputation. The reference integrates the same equation
 with an adaptive RK5(4) whose own accuracy is ~1e-10 (tests/test_lindblad_oracle.py), which
@@ -76,26 +78,27 @@ class StructuredLindblad(object):
         return self.g if self.g_of_t is None else self.g_of_t(t)
 
     def generator(self, u, t=None):
-        """(A, gammas, ops) of one stage: A = -i H(u, t) - 1/2 sum gamma_i L_i^H L_i."""
+        """(A, gammas, ops, B) of one stage: A = -i H(u, t) - D / 2 on the left of rho and
+        B = +i H(u, t) - D / 2 on its right, D = sum gamma_i L_i^H L_i."""
         h0 = self.h0 if self.h0_of_t is None else self.h0_of_t(t)
         ham = h0 + sum((uk * gk for uk, gk in zip(u, self.g_at(t))), np.zeros_like(self.h0))
         if self.data_of_t is None:
-            return -1j * ham - 0.5 * self.decay, self.gammas, self.ops
+            return -1j * ham - 0.5 * self.decay, self.gammas, self.ops, 1j * ham - 0.5 * self.decay
         gammas, ops = self.data_of_t(t)
         decay = sum((gm * (h(op) @ op) for gm, op in zip(gammas, ops)), np.zeros_like(self.h0))
-        return -1j * ham - 0.5 * decay, gammas, ops
+        return -1j * ham - 0.5 * decay, gammas, ops, 1j * ham - 0.5 * decay
 
     def rhs(self, gen, rho):
-        a, gammas, ops = gen
-        out = a @ rho + rho @ h(a)
+        a, gammas, ops, b = gen
+        out = a @ rho + rho @ b
         for gm, op in zip(gammas, ops):
             out = out + gm * (op @ rho @ h(op))
         return out
 
     def rhs_adjoint(self, gen, x):
         """adjoint of rho -> rhs(gen, rho) w.r.t. Re tr(X^H Y)."""
-        a, gammas, ops = gen
-        out = h(a) @ x + x @ a
+        a, gammas, ops, b = gen
+        out = h(a) @ x + x @ h(b)
         for gm, op in zip(gammas, ops):
             out = out + gm * (h(op) @ x @ op)
         return out
@@ -123,26 +126,36 @@ class StructuredLindblad(object):
 
 def evaluate_with_grad(system, controls, initial_densities, evolution_time, system_eval_count,
                        costs, cost_eval_step=1, want_grad=True, stop_step=None,
-                       subdivision=None):
+                       subdivision=None, piecewise_constant=False):
     """
     controls :: (Nc x K) real. costs :: oracle cost objects (cost / states_bar on
     (S x n x n) densities). Returns (error, grads (Nc x K), final_densities).
+    piecewise_constant: controls[j] is the value on slice j of Nc equal slices, as the engine runs
+    InterpolationPolicy.PIECEWISE_CONSTANT (build_lindblad_grid): the sub-intervals are cut at the
+    slice edges, the knots of Nc + 1, both ends of a sub-interval read the slice that contains it,
+    and its whole control cotangent goes to that slice.
     """
     controls = np.asarray(controls, dtype=np.float64)
     nc, k = controls.shape
     xs = np.linspace(0, evolution_time, nc)
     n_steps = system_eval_count - 1
     umax = np.max(np.abs(controls), axis=0) if k else []
-    grid = substep_grid(evolution_time, system_eval_count, nc, system.norm_bound(umax),
-                        subdivision=subdivision)
+    grid = substep_grid(evolution_time, system_eval_count, nc + 1 if piecewise_constant else nc,
+                        system.norm_bound(umax), subdivision=subdivision)
     step_costs = [c for c in costs if c.requires_step_evaluation]
+
+    def slice_of(ta, tb):
+        return min(max(int(np.floor(0.5 * (ta + tb) * nc / evolution_time)), 0), nc - 1)
 
     def control(t):
         return onp.interpolate_linear_set(t, xs, controls)
 
     def run_substep(rho, ta, tb, keep=False):
         hh = tb - ta
-        ua, ub = control(ta), control(tb)
+        if piecewise_constant:
+            ua = ub = controls[slice_of(ta, tb)]
+        else:
+            ua, ub = control(ta), control(tb)
         ks, ys, gens = [], [], []
         for i in range(STAGES):
             u = (1 - RK_C[i]) * ua + RK_C[i] * ub  # linear inside a sub-interval
@@ -184,8 +197,12 @@ def evaluate_with_grad(system, controls, initial_densities, evolution_time, syst
     for step, ta, tb, rho0 in reversed(checkpoints):
         hh = tb - ta
         _, ys, gens = run_substep(rho0, ta, tb, keep=True)
-        ia1, wa1, ia2, wa2 = onp.interpolation_weights(ta, xs)
-        ib1, wb1, ib2, wb2 = onp.interpolation_weights(tb, xs)
+        if piecewise_constant:
+            ia1 = ia2 = ib1 = ib2 = slice_of(ta, tb)
+            wa1, wa2, wb1, wb2 = 1.0, 0.0, 1.0, 0.0
+        else:
+            ia1, wa1, ia2, wa2 = onp.interpolation_weights(ta, xs)
+            ib1, wb1, ib2, wb2 = onp.interpolation_weights(tb, xs)
         ybar_stage = [None] * STAGES
         lam_new = lam.copy()
         for i in range(STAGES - 1, -1, -1):

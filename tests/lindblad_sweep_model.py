@@ -27,11 +27,13 @@ def scaled_system(system, factors):
 
 
 def rate_sensitivities(system, controls, initial_densities, evolution_time, system_eval_count,
-                       costs, cost_eval_step=1, subdivision=None, factors=None):
+                       costs, cost_eval_step=1, subdivision=None, factors=None,
+                       piecewise_constant=False):
     """
     (error, dE/dc (L,)) of `system` with the rates factors * system.gammas (default 1): the adjoint
     recursion of lindblad_model.evaluate_with_grad with the formula above accumulated in its stage
     loop. The derivative is with respect to the FACTORS: gamma_l below is system.gammas[l].
+    piecewise_constant: as in lindblad_model.evaluate_with_grad.
     """
     L = len(system.gammas)
     factors = np.ones(L) if factors is None else np.asarray(factors, dtype=np.float64)
@@ -41,7 +43,8 @@ def rate_sensitivities(system, controls, initial_densities, evolution_time, syst
     xs = np.linspace(0, evolution_time, nc)
     n_steps = system_eval_count - 1
     umax = np.max(np.abs(controls), axis=0) if k else []
-    grid = lm.substep_grid(evolution_time, system_eval_count, nc, run.norm_bound(umax),
+    grid = lm.substep_grid(evolution_time, system_eval_count,
+                           nc + 1 if piecewise_constant else nc, run.norm_bound(umax),
                            subdivision=subdivision)
     from oracle import qoc_numpy as onp
 
@@ -51,6 +54,9 @@ def rate_sensitivities(system, controls, initial_densities, evolution_time, syst
     def run_substep(rho, ta, tb):
         hh = tb - ta
         ua, ub = control(ta), control(tb)
+        if piecewise_constant:
+            j = int(np.floor(0.5 * (ta + tb) * nc / evolution_time))
+            ua = ub = controls[min(max(j, 0), nc - 1)]
         ks, ys, gens = [], [], []
         for i in range(lm.STAGES):
             u = (1 - lm.RK_C[i]) * ua + lm.RK_C[i] * ub

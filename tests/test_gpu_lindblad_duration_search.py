@@ -256,6 +256,20 @@ def test_the_duration_gradient_agrees_with_central_differences_of_the_model():
     print("dE/dtau", got, "central differences", want, "difference", got - want)
     assert np.min(np.abs(want)) > 1e-4
     assert helpers.lindblad_grad_close(got, want, case)
+    # ... and beside the differences the exact sensitivity (tests/lindblad_exact.py: the forward
+    # sensitivity equation of the factor tau on the whole Lindbladian, two integrators), at its gate
+    from tests import lindblad_exact as ex
+    fixed = LindbladSweep.durations(case.hamiltonian(), case.T * taus, case.T, **tab)
+    exact = np.zeros(B)
+    for b in range(B):
+        s = structured(fixed, b)
+        r = ex.linear(s.h0, s.g, s.ops, s.gammas, u[b], case.T, case.N, case.initial_densities, costs,
+                      directions=[None])
+        assert 10 * r.disagreement["derivative"] <= ex.GATE_LINEAR_DERIVATIVE
+        exact[b] = r.derivative[0] / taus[b]
+    print("exact", exact, "difference", got - exact, "over its gate",
+          np.max(np.abs(got - exact)) / np.max(np.abs(exact)) / ex.GATE_LINEAR_DERIVATIVE)
+    assert np.max(np.abs(got - exact)) <= ex.GATE_LINEAR_DERIVATIVE * np.max(np.abs(exact))
 
 
 # ---- 5. a known answer with an interior minimum -------------------------------------------------------

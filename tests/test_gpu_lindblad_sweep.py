@@ -441,6 +441,21 @@ def test_t1_decay_per_seed_and_its_time_gradient(engine):
     assert np.max(np.abs(got - want)) < 1e-8 * np.max(np.abs(want))
     # (c_b = tau_b: E_b = 1 - exp(-gamma c_b reference_time) / 2)
     assert np.max(np.abs(sens["rate_scales"][:, 0] - ref * want)) < 1e-8 * np.max(ref * want)
+    # ... and the exact sensitivities (tests/lindblad_exact.py: Frechet derivatives of the superoperator
+    # exponentials of seed b, tau_b times the whole Lindbladian) at their gate, far below 1e-8
+    from tests import lindblad_exact as ex
+    exact = []
+    for tau in times / ref:
+        r = ex.piecewise_constant(tau * 0.3 * sz, [tau * sz], sm_op[None], [tau * gamma],
+                                  np.zeros((4, 1)), ref, 7, rho0, [ol.TargetDensityInfidelity(rho0)])
+        exact.append((r.error, r.tau_sens / tau / ref, r.rate_sens[0] / tau))
+    exact = np.array(exact)
+    print("over the gates: cost", np.max(np.abs(errors - exact[:, 0])) / ex.GATE_COST, "dE/dT",
+          np.max(np.abs(got - exact[:, 1])) / np.max(exact[:, 1]) / ex.GATE_SENSITIVITIES)
+    assert np.max(np.abs(errors - exact[:, 0])) <= ex.GATE_COST
+    assert np.max(np.abs(got - exact[:, 1])) <= ex.GATE_SENSITIVITIES * np.max(np.abs(exact[:, 1]))
+    assert (np.max(np.abs(sens["rate_scales"][:, 0] - exact[:, 2]))
+            <= ex.GATE_SENSITIVITIES * np.max(np.abs(exact[:, 2])))
 
 
 # ---- 5. the resident route against the host loop --------------------------------------------------------
