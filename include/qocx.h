@@ -589,6 +589,9 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   one-state form of the column-chain sweep).
  *   "pade_order"    0 (default): Pade order 3 / 5 / 7 / 9 / 13 by the 1-norm of the step generator;
  *                   13: always [13/13], as the reference executes it (qocx_pade_orders).
+ *   "action"        1 (default): one state, Hermitian H, 17 <= n <= 32, one final TargetStateInfidelity,
+ *                   "pade_order" 0: matrix-free sweeps - exp(a) psi by the truncated Taylor series, no
+ *                   factorisation (qocx_action.hip, qocx_action_degrees); 0: the Pade route.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;
@@ -641,8 +644,21 @@ int qocx_debug_read_stamps(qocx_ctx* ctx, uint64_t* out, int64_t count);
  * takes the order from the 1-norm of the step generator by the thresholds of Higham 2005,
  * Algorithm 2.3 - the table /root/reference/qoc/standard/functions/expm.py:194-209 carries; the
  * reference itself always evaluates [13/13] (expm.py:230-233: its selection loop has no break),
- * which the knob "pade_order" = 13 reproduces. Same matrix and same derivative to rounding. */
+ * which the knob "pade_order" = 13 reproduces. Same matrix and same derivative to rounding.
+ * These are bits 8..15 of the step table's entries: the table's classification of the steps, and
+ * what the Pade route executes. An evaluation on the matrix-free route (qocx_action_degrees) forms
+ * no approximant; the counts then say what the Pade route would have taken. */
 int qocx_pade_orders(qocx_ctx* ctx, int64_t* counts);
+/* Taylor degrees the last Schroedinger evaluation executed on the matrix-free route (one state,
+ * Hermitian H, 17 <= n <= 32, one final TargetStateInfidelity; knob "action"; qoc_amd/csrc/
+ * qocx_action.hip): counts[m], m = 1 .. 18, = propagator steps whose exp(a) psi was the degree-m
+ * truncated Taylor series (Al-Mohy & Higham 2011; the least m with ||a||_1 <= theta_m), summed over
+ * every seed of the evaluation. All 19 entries are zero when the evaluation took the Pade route. */
+int qocx_action_degrees(qocx_ctx* ctx, int64_t* counts);
+/* Evaluations of this context the matrix-free route handed back to the Pade route because a step's
+ * degree, decided on the device, was beyond the buffers the host had sized from its norm bound
+ * (stale after qocx_opt_step). The results are those of the Pade route. */
+int qocx_action_reruns(qocx_ctx* ctx, int64_t* count);
 /* Matrices of the last Schroedinger evaluation (or qocx_debug_pade_factor call) whose LU factorisation
  * left the diagonal-pivot form with MFMA Schur updates (knob "lu_mfma"; qoc_amd/csrc/qocx_lu4.h,
  * qocx_lu4m.hip) for the general partial-pivoting elimination: LAPACK's pivot rule asked for a row

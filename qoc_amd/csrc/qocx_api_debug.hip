@@ -242,6 +242,24 @@ int qocx_pade_orders(qocx_ctx* ctx, int64_t* counts) {
     return 0;
 }
 
+int qocx_action_degrees(qocx_ctx* ctx, int64_t* counts) {
+    if (!ctx || !counts) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
+    for (int i = 0; i < 19; ++i) counts[i] = 0;
+    if (ctx->action_counts.p == nullptr) return 0;  // (no evaluation has reached the resident pipeline)
+    HIP_TRY(hipSetDevice(ctx->device));
+    int v[19];
+    HIP_TRY(hipMemcpy(v, ctx->action_counts.p, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 19; ++i) counts[i] = v[i];
+    return 0;
+}
+
+int qocx_action_reruns(qocx_ctx* ctx, int64_t* count) {
+    if (!ctx || !count) return fail(QOCX_ERR_ARG, "NULL argument");
+    *count = ctx->action_reruns;
+    return 0;
+}
+
 int qocx_debug_timeline(qocx_ctx* ctx, double* out, int64_t capacity, int64_t* count) {
     if (!ctx || !count) return fail(QOCX_ERR_ARG, "NULL argument");
     const int64_t n = (int64_t)(ctx->timeline.size() / 3);

@@ -88,6 +88,7 @@ struct StepTableArgs {
     int pade_policy;           // 0: order by norm, 13: always [13/13]
     int sq_max = 30;           // the squaring count the host sized the sub-step slots for
     int order_max = 13;        // 5: the three-wave K1a of qocx_pade3.hip runs the evaluation (host bound below theta_5)
+    int action = 0;            // the entries also carry the Taylor degree of the step (qocx_action.h)
     double* ustep;             // out: [B][nsteps][K]
     int* s_arr;                // out: [B][nsteps]
     int* status;               // bit 1: non-finite controls
@@ -196,6 +197,34 @@ struct KrylovArgs {
     const double2* m_rm;
     double2* mbar_rm;
 };
+
+// Matrix-free route of one-state Hermitian problems at 17 <= n <= 32 (qocx_action.hip): the sweeps
+// apply exp(a_j) to their vector by the truncated Taylor series and leave its terms behind
+struct ActionArgs {
+    SweepArgs sw;              // phase, j_begin / j_end, psi0, costs, cost_out, final_out, lam_scale, lam_buf, s_arr, status
+    const double* ustep;       // [B][nsteps][K] the step table's u_k(t_mid)
+    const double2* h0_rimg;    // column-major H0
+    const double2* g_rimg;     // [K] column-major G_k
+    int K, m_max;              // controls; Taylor terms a step of the Krylov buffers holds
+    double dt;
+    double2* kv_f;             // [B][nsteps][m_max][NP] v_0 .. v_(m-1) of every step, or nullptr (no gradient wanted)
+    double2* kv_b;             // [B][nsteps][m_max][NP] w_0 .. w_(m-1)
+    double2* carry_f;          // [B][NP] the state between two forward launches
+    int* degree_counts;        // [QOCX_ACTION_MAX_DEGREE + 1] steps of the forward sweep per degree
+};
+struct ActionGradArgs {
+    const double2* kv_f;
+    const double2* kv_b;
+    const int* s_arr;
+    const double2* g_rimg;
+    int K, m_max, nsteps;
+    int step0;                 // grid.x covers steps [step0, step0 + gridDim.x), grid.y the seeds
+    double dt;
+    double* gstep;             // [B][nsteps][K][2]: gamma_k as KrylovArgs::gstep under the unit adjoint
+};
+void launch_action_sweep(const ActionArgs& a, int batch, hipStream_t st);
+void launch_action_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
+int action_grad_lds_bytes(int m_max);
 
 // Magnus M4 / M6 generator kernels (qocx_magnus.hip)
 struct MagnusArgs {

@@ -216,6 +216,12 @@ struct qocx_ctx {
     DevBuf<int> perm, iperm, s_arr, offs, status;
     DevBuf<int> lu_fallbacks;  // [1] matrices that left the diagonal-pivot MFMA factorisation (qocx_lu_fallbacks)
     DevBuf<int> lu_redo;  // 33 <= n <= 64: matrices the MFMA factorisation hands to the general one (LuArgs::redo)
+    // matrix-free route (qocx_action.hip): the Taylor terms of every step of a chunk, the forward sweep's
+    // state between launches, the degrees the last evaluation executed (qocx_action_degrees) and the
+    // evaluations run again on the Pade route because a step's degree was beyond the buffers (qocx_action_reruns)
+    DevBuf<double2> kry_f, kry_b, action_carry;
+    DevBuf<int> action_counts;
+    int64_t action_reruns = 0;
     // ---- Lindblad problem / evaluation state ----
     // ---- Magnus M4/M6 ----
     int nodes = 1;

@@ -2,6 +2,7 @@
 // (eval_items, behind qocx_eval_resident): the general path for Hilbert sizes above 64 and the
 // resident pipeline of the wavefront kernels - route, buffers, chunks, schedules.
 #include "qocx_host.h"
+#include "qocx_action.h"
 
 // Evaluation for Hilbert sizes above 64 (qocx_general.hip): classic order, one stream - factor every step,
 // forward sweep, adjoint sweep, K3, scatter - per memory chunk of seeds.
@@ -10,12 +11,15 @@ size_t general_krylov_scratch(int np, int S);
 void launch_general_magnus(const MagnusArgs& a, bool vjp, int blocks, hipStream_t st);
 }
 // the end of an evaluation of the uploaded items: waits for it and reads the kernels' status word
+// (finish_items: a step of the matrix-free route asked for a degree beyond its buffers)
+static constexpr int kActionRefused = -0x7a11;
 static int finish_items(qocx_ctx* ctx, int want_grad) {
     HIP_TRY(hipGetLastError());
     int status = 0;
     HIP_TRY(hipMemcpyAsync(&status, ctx->status.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     time_collect(ctx);
+    if (status & 8) return kActionRefused;  // eval_items runs the evaluation again on the Pade route
     if (status & 2) return fail(QOCX_ERR_ARG, "non-finite generator norm");
     if (status & 1) return fail(QOCX_ERR_SINGULAR, "Singular matrix");
     if (status & 4) return fail(QOCX_ERR_CAPACITY, "squaring sub-step capacity exceeded");
@@ -277,9 +281,11 @@ struct ResidentRoute {
     bool all_dominant;   // every Pade denominator diagonally dominant
     bool pack8;          // n <= 8: two steps per 16 x 16 tile through K1a and K1b
     bool umode;          // the propagator itself in the Q image, one product per sweep sub-step
+    bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip)
+    int m_max;           // ... and the Taylor terms per step its buffers hold
 };
 
-ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
+ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_action) {
     ResidentRoute r;
     const int nb = ctx->nb, S = ctx->S;
     const bool explicit_gen = ctx->explicit_mode;
@@ -335,6 +341,21 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
     // itself in the Q image; the sweeps apply ONE matrix per sub-step, the adjoint sweep hands lambda'
     // to K3, which forms x = P^-H lambda' from the P^-1 image (knob "sweep_umode").
     r.umode = r.latency && r.inverse_sweep && !r.dense && nb <= 2 && ctx->knob("sweep_umode", 1) != 0;
+    // One state, Hermitian H, 17 <= n <= 32, structured M2, one final TargetStateInfidelity: the evaluation
+    // needs exp(a_j) psi and exp(a_j)^H lambda, never the matrix - the sweeps apply the truncated Taylor
+    // series (degree per step from the step table) and leave its terms to the gradient kernel; no K1a, no
+    // LU, no stored factors. Independent of want_grad (a forward-only evaluation returns the same costs
+    // bit for bit), of the batch size, chunking and segmentation. "pade_order" = 13 keeps executing
+    // [13/13]. The degree is decided on the device; the host's bound sizes the buffers (m_max) and a
+    // step beyond them sends the evaluation back to the Pade route (eval_items).
+    const double host_bound = std::min(ctx->norm_bound, ctx->norm_bound_mid);
+    r.action = allow_action && nb == 2 && S == 1 && r.step_table && ctx->nt == 1 && ctx->hermitian &&
+               ctx->unit_ok && ctx->inj_count == 0 && !ctx->has_step_costs && !r.latency &&
+               !r.inverse_sweep && !ctx->keep_step_states && ctx->knob("pade_order", 0) == 0 &&
+               ctx->knob("unit_adjoint", 1) != 0 && ctx->knob("action", 1) != 0 &&
+               host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
+    // (the device's bound of a step is the host's up to the rounding of the interpolation)
+    r.m_max = r.action ? std::min(QOCX_ACTION_MAX_DEGREE, qocx::action_degree_for(host_bound * (1 + 1e-9))) : 0;
     return r;
 }
 
@@ -342,6 +363,30 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad) {
 int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& chunk) {
     const int B = ctx->B, np = ctx->np, mat = np * np, S = ctx->S, K = ctx->K, nsteps = ctx->nsteps;
     if (r.unit && ctx->lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
+    if (ctx->action_counts.ensure(QOCX_ACTION_MAX_DEGREE + 1)) return QOCX_ERR_HIP;
+    if (r.action) {
+        // no Q / LU images, 1 / U_kk, permutations or sub-step slots: the Taylor terms of both sweeps
+        // (gradient wanted), the step table and the step cotangents
+        const size_t terms = want_grad ? (size_t)r.m_max * np : 0;
+        const size_t seed_bytes = (size_t)nsteps * (2 * terms * 16 + 4 + (size_t)K * 8 + (size_t)K * 16) + (size_t)np * 64;
+        chunk = ctx->chunk_user;
+        if (chunk <= 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            const size_t have = (ctx->kry_f.count + ctx->kry_b.count) * 16;
+            const size_t budget = (size_t)((double)(free_b + have) * 0.6);
+            chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, budget / seed_bytes));
+        }
+        chunk = std::min(chunk, B);
+        const size_t cm = (size_t)chunk * nsteps;
+        if (ctx->s_arr.ensure(cm) || ctx->kry_f.ensure(std::max<size_t>(1, cm * terms)) ||
+            ctx->kry_b.ensure(std::max<size_t>(1, cm * terms)) || ctx->action_carry.ensure((size_t)chunk * np) ||
+            ctx->gstep.ensure(cm * std::max(K, 1) * 2) || ctx->cost_out.ensure(B) ||
+            ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) || ctx->final_out.ensure((size_t)B * S * np) ||
+            ctx->lam_buf.ensure((size_t)chunk * S * np) || ctx->lu_fallbacks.ensure(1))
+            return QOCX_ERR_HIP;
+        return 0;
+    }
     const size_t per_seed = (size_t)nsteps * ((size_t)mat * 32 + (size_t)np * 20 + 4) +
                             ctx->slot_cap * S * np * 32 + (size_t)(nsteps + 1) * 4 +
                             (size_t)nsteps * ctx->nodes * std::max(r.Kk, 1) * 24 +
@@ -425,6 +470,8 @@ struct ResidentChunk {
     qocx::MagnusArgs ma;
     qocx::SweepArgs sa;
     qocx::KrylovArgs ka;
+    qocx::ActionArgs aa;       // the matrix-free route (r.action)
+    qocx::ActionGradArgs ga;
 
     ResidentChunk(qocx_ctx* c, const ResidentRoute& route, int grad, int first, int count)
         : ctx(c), r(route), want_grad(grad), b0(first), bc(count), cs(c->stream) {
@@ -492,6 +539,7 @@ struct ResidentChunk {
             ta.controls = fa.controls; ta.interp = fa.interp; ta.K = K; ta.nc = ctx->nc;
             ta.nsteps = nsteps; ta.batch = bc; ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max;
             ta.g_norm = ctx->g_norm_dev.p; ta.pade_policy = fa.pade_policy;
+            ta.action = r.action ? 1 : 0;
             ta.sq_max = std::min(30, ctx->sbound);
             // only the three-wave K1a (orders 3 and 5) will be launched: no step above order 5
             qocx::FactorArgs probe = fa;
@@ -606,6 +654,16 @@ struct ResidentChunk {
             ka.mbar_rm = want_grad ? ctx->genbar_rm.p + (size_t)b0 * nsteps * mat : nullptr;
         }
         ka.skew = explicit_gen ? ctx->explicit_hermitian : ctx->hermitian;
+        if (r.action) {
+            aa.ustep = ctx->ustep.p; aa.h0_rimg = ctx->h0.r.p; aa.g_rimg = ctx->g.r.p;
+            aa.K = ctx->K; aa.m_max = r.m_max; aa.dt = ctx->dt;
+            aa.kv_f = want_grad ? ctx->kry_f.p : nullptr;
+            aa.kv_b = want_grad ? ctx->kry_b.p : nullptr;
+            aa.carry_f = ctx->action_carry.p;
+            aa.degree_counts = ctx->action_counts.p;
+            ga.kv_f = ctx->kry_f.p; ga.kv_b = ctx->kry_b.p; ga.s_arr = ctx->s_arr.p; ga.g_rimg = ctx->g.r.p;
+            ga.K = ctx->K; ga.m_max = r.m_max; ga.nsteps = nsteps; ga.dt = ctx->dt; ga.gstep = ctx->gstep.p;
+        }
         return 0;
     }
 
@@ -616,6 +674,10 @@ struct ResidentChunk {
         // that K1b might find P in the last-level cache: 13.1 / 13.8 / 15.5 ms against 12.7 -
         // the launch tails cost more than any cache hit returns.)
         const int nb = ctx->nb, np = ctx->np, plo = lo[i], len = lo[i + 1] - lo[i];
+        if (r.action) {  // nothing to factor: the sweeps wait for the step table only
+            if (nseg > 1) HIP_TRY(hipEventRecord(ctx->ev_factored[i], cs));
+            return 0;
+        }
         fa.step0 = plo; fa.seg_len = len;
         time_begin(ctx, 0, cs);
         if (ctx->explicit_mode) {
@@ -675,7 +737,10 @@ struct ResidentChunk {
         sa.j_begin = jb; sa.j_end = je; sa.phase = phase;
         time_begin(ctx, 1, st);
         if (!((dbg_skip & 1) && (phase & 1)) && !((dbg_skip & 2) && (phase & 2))) {
-            if (r.dense) qocx::launch_sweepd(sa, bc, st);
+            if (r.action) {
+                aa.sw = sa;
+                qocx::launch_action_sweep(aa, bc, st);
+            } else if (r.dense) qocx::launch_sweepd(sa, bc, st);
             else if (r.inverse_sweep) qocx::launch_sweepi(ctx->nb, sa, bc, st);
             else if (r.sweep3) qocx::launch_sweep3(ctx->nb, sa, bc, st);
             else qocx::launch_sweep(ctx->nb, sa, bc, st);
@@ -688,7 +753,10 @@ struct ResidentChunk {
         const int len = je - jb;
         ka.step0 = jb;
         time_begin(ctx, 2, cs);
-        if (!(dbg_skip & 4)) qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
+        if (r.action) {
+            ga.step0 = jb;
+            if (!(dbg_skip & 4)) qocx::launch_action_grad(ga, len, bc, cs);
+        } else if (!(dbg_skip & 4)) qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
         if (r.nodes > 1) {
             ma.step0 = jb; ma.seg_len = len; ma.total = (size_t)bc * len;
             ma.m_rm = nullptr; ma.mbar_rm = ka.mbar_rm; ma.gstep = ka.gstep;
@@ -805,6 +873,8 @@ int run_two_sided(ResidentChunk& c) {
 
 namespace qocx::host {
 
+static int eval_resident(qocx_ctx* ctx, int32_t want_grad, bool allow_action);
+
 // The evaluation of the ctx->B items of the uploaded controls (qocx_eval_resident)
 int eval_items(qocx_ctx* ctx, int32_t want_grad) {
     if (!ctx->has_problem || ctx->B < 1) return fail(QOCX_ERR_STATE, "no problem / controls");
@@ -816,12 +886,28 @@ int eval_items(qocx_ctx* ctx, int32_t want_grad) {
         if (ctx->genbar_rm.ensure((size_t)B * ctx->nsteps * ctx->np * ctx->np)) return QOCX_ERR_HIP;
     if (ctx->inj_count > 0 && ctx->inj_batch != B)
         return fail(QOCX_ERR_STATE, "state cotangents were set for a different batch size");
+    // (the degrees of the matrix-free route: none executed unless its forward sweep says so)
+    if (ctx->action_counts.p != nullptr)
+        HIP_TRY(hipMemsetAsync(ctx->action_counts.p, 0, ctx->action_counts.count * sizeof(int), ctx->stream));
     if (ctx->general_path) return eval_general(ctx, want_grad);  // n > 64, or more states than the sweep's LDS (qocx_general.hip)
+    int rc = eval_resident(ctx, want_grad, true);
+    if (rc == kActionRefused) {
+        // The host's bound was stale (qocx_opt_step moves the controls on the device): a step
+        // asked for a Taylor degree beyond the buffers. Never clamped - the Pade route evaluates instead.
+        ctx->action_reruns += 1;
+        rc = eval_resident(ctx, want_grad, false);
+    }
+    return rc;
+}
 
-    const ResidentRoute route = resident_route(ctx, want_grad);
+// ... on the resident pipeline, with or without the matrix-free route
+int eval_resident(qocx_ctx* ctx, int32_t want_grad, bool allow_action) {
+    const int B = ctx->B;
+    const ResidentRoute route = resident_route(ctx, want_grad, allow_action);
     int chunk = 0;
     if (int rc = reserve_resident(ctx, route, want_grad, chunk)) return rc;
     HIP_TRY(hipMemsetAsync(ctx->status.p, 0, sizeof(int), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->action_counts.p, 0, ctx->action_counts.count * sizeof(int), ctx->stream));
     for (int b0 = 0; b0 < B; b0 += chunk) {
         ResidentChunk c(ctx, route, want_grad, b0, std::min(chunk, B - b0));
         ctx->last_chunk = c.bc;

@@ -34,6 +34,7 @@
 #include "qocx_sweep_common.h"
 #include "qocx_lu.h"
 #include "qocx_lu5.h"
+#include "qocx_action.h"
 
 namespace qocx {
 
@@ -1573,7 +1574,9 @@ __global__ __launch_bounds__(256) void step_table_kernel(StepTableArgs args) {
         }
         dominant = pade_denominator_dominant(order, ldexp(bound, -sq));
     }
-    args.s_arr[idx] = step_entry(sq, order) | (dominant ? QOCX_STEP_DOMINANT : 0);
+    // (matrix-free route, qocx_action.hip: the Taylor degree from the same bound; NaN: beyond every degree)
+    const int degree = args.action ? (action_degree_for(bound) << QOCX_STEP_DEGREE_SHIFT) : 0;
+    args.s_arr[idx] = step_entry(sq, order) | (dominant ? QOCX_STEP_DOMINANT : 0) | degree;
 }
 void launch_step_table(const StepTableArgs& a, hipStream_t st) {
     const size_t total = (size_t)a.batch * a.nsteps;

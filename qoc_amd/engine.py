@@ -194,6 +194,8 @@ SIGNATURES = {
     "qocx_debug_timeline": (ctypes.c_int, [_VP, _c_double_p, _I64, ctypes.POINTER(_I64)]),
     "qocx_pade_orders": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "qocx_lu_fallbacks": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
+    "qocx_action_degrees": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
+    "qocx_action_reruns": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "qocx_debug_mfma_peak": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_opt_begin": (ctypes.c_int, [_VP]),
     "qocx_opt_clip": (ctypes.c_int, [_VP, _c_double_p]),
@@ -939,6 +941,19 @@ class Engine(object):
         diagonal-pivot MFMA form for the general elimination (include/qocx.h: qocx_lu_fallbacks)."""
         count = _I64(0)
         self._check(self._lib.qocx_lu_fallbacks(self._ctx, ctypes.byref(count)))
+        return int(count.value)
+
+    def action_degrees(self):
+        """{degree: propagator steps} the last evaluation executed on the matrix-free route, degrees
+        1 .. 18; every count is zero when it took the Pade route (include/qocx.h: qocx_action_degrees)."""
+        counts = (_I64 * 19)()
+        self._check(self._lib.qocx_action_degrees(self._ctx, counts))
+        return {m: int(counts[m]) for m in range(1, 19)}
+
+    def action_reruns(self):
+        """Evaluations the matrix-free route handed back to the Pade route (qocx_action_reruns)."""
+        count = _I64(0)
+        self._check(self._lib.qocx_action_reruns(self._ctx, ctypes.byref(count)))
         return int(count.value)
 
     def timeline(self, capacity=4096):
