@@ -591,7 +591,10 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   13: always [13/13], as the reference executes it (qocx_pade_orders).
  *   "action"        1 (default): one state, Hermitian H, 17 <= n <= 32, one final TargetStateInfidelity,
  *                   "pade_order" 0: matrix-free sweeps - exp(a) psi by the truncated Taylor series, no
- *                   factorisation (qocx_action.hip, qocx_action_degrees); 0: the Pade route.
+ *                   factorisation (qocx_action.hip, qocx_action_degrees); 0: the Pade route;
+ *                   2: as 1, and the same problems at 33 <= n <= 64 too (qocx_action4.hip: workgroups
+ *                   of three / four waves). Opt-in: above n = 32 the values 0 and 1 launch exactly
+ *                   what they always launched.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;
@@ -650,8 +653,8 @@ int qocx_debug_read_stamps(qocx_ctx* ctx, uint64_t* out, int64_t count);
  * no approximant; the counts then say what the Pade route would have taken. */
 int qocx_pade_orders(qocx_ctx* ctx, int64_t* counts);
 /* Taylor degrees the last Schroedinger evaluation executed on the matrix-free route (one state,
- * Hermitian H, 17 <= n <= 32, one final TargetStateInfidelity; knob "action"; qoc_amd/csrc/
- * qocx_action.hip): counts[m], m = 1 .. 18, = propagator steps whose exp(a) psi was the degree-m
+ * Hermitian H, 17 <= n <= 32 - with knob "action" = 2 up to n = 64 -, one final TargetStateInfidelity;
+ * qoc_amd/csrc/qocx_action.hip, qocx_action4.hip): counts[m], m = 1 .. 18, = propagator steps whose exp(a) psi was the degree-m
  * truncated Taylor series (Al-Mohy & Higham 2011; the least m with ||a||_1 <= theta_m), summed over
  * every seed of the evaluation. All 19 entries are zero when the evaluation took the Pade route. */
 int qocx_action_degrees(qocx_ctx* ctx, int64_t* counts);

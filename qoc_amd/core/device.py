@@ -582,8 +582,13 @@ class SchroedingerEvaluator(_Evaluator):
                  control_count=0, control_eval_count=0, complex_controls=False, costs=(),
                  cost_eval_step=1, interpolation_policy=InterpolationPolicy.LINEAR,
                  magnus_policy=MagnusPolicy.M2, need_gradients=True, backend=None,
-                 latency_mode=False):
+                 latency_mode=False, matrix_free="default"):
         """
+        matrix_free: "default" leaves the engine's route decision as it is (matrix-free Taylor
+        sweeps for one-state Hermitian problems at 17 <= n <= 32, knob "action" untouched); "wide"
+        also takes them at 33 <= n <= 64 (knob "action" = 2 on a backend with set_knob; opt-in
+        because the default route there is what existing callers measure and assert on). A backend
+        without knobs ignores it; any other value is a ValueError.
         latency_mode: the evaluator will be asked for ONE control array at a time (the
         reference's evolve_* / grape_* entry points). Where the cost is a single final
         TargetStateInfidelity the engine then runs its two-sided pipeline (round 3: forward and
@@ -601,6 +606,10 @@ class SchroedingerEvaluator(_Evaluator):
         self.interpolation_policy = interpolation_policy
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
+        if not (isinstance(matrix_free, str) and matrix_free in ("default", "wide")):
+            raise ValueError("matrix_free must be \"default\" or \"wide\", not {!r}."
+                             .format(matrix_free))
+        self.matrix_free = matrix_free
         initial_states = np.asarray(initial_states)
         self.state_count = initial_states.shape[0]
         self.hilbert_size = initial_states.shape[1]
@@ -711,6 +720,8 @@ class SchroedingerEvaluator(_Evaluator):
             self.backend.set_knob(
                 "sweep_impl", 3 if (latency_mode and 16 < self.hilbert_size <= 32) else 1)
             self.backend.set_knob("latency", 1 if latency_mode else 0)
+            if matrix_free == "wide":
+                self.backend.set_knob("action", 2)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:

@@ -37,7 +37,7 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
                                  controls=None, cost_eval_step=1, costs=list(),
                                  interpolation_policy=InterpolationPolicy.LINEAR,
                                  magnus_policy=MagnusPolicy.M2, save_file_path=None,
-                                 save_intermediate_states=False):
+                                 save_intermediate_states=False, matrix_free="default"):
     """
     Evolve state vectors under the Schroedinger equation and compute the optimization error.
 
@@ -49,6 +49,7 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
     (qoc_amd.standard) the error is the weighted sum over its members, final_states gains a
     member axis (M x state_count x n x 1) and the result's member_errors holds each member's
     unweighted device cost.
+    matrix_free: SchroedingerEvaluator's keyword ("default" or "wide").
     """
     reject_lindblad_sweep(hamiltonian)
     reject_sweep(hamiltonian, "evolve_schroedinger_discrete", _SWEEP_HINT)
@@ -68,7 +69,8 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
         control_count=control_count, control_eval_count=control_eval_count,
         complex_controls=controls is not None and np.iscomplexobj(controls), costs=costs,
         cost_eval_step=cost_eval_step, interpolation_policy=interpolation_policy,
-        magnus_policy=magnus_policy, need_gradients=False, latency_mode=True)
+        magnus_policy=magnus_policy, need_gradients=False, latency_mode=True,
+        matrix_free=matrix_free)
     error, _, final_states, step_states = evaluator.evaluate(
         controls, want_grad=False, want_step_states=pstate.save_intermediate_states_)
     if pstate.save_intermediate_states_:
@@ -89,7 +91,7 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
                                 magnus_policy=MagnusPolicy.M2, max_control_norms=None,
                                 min_error=0, optimizer=Adam(), save_file_path=None,
                                 save_intermediate_states=False, save_iteration_step=0,
-                                control_basis=None):
+                                control_basis=None, matrix_free="default"):
     """
     Optimize time-discrete controls for the evolution of a set of states (GRAPE).
     Arguments as in the reference (schroedingerdiscrete.py:106-212).
@@ -103,6 +105,7 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     With a HamiltonianEnsemble the error is the weighted sum over its members, best_final_states
     has a member axis, and member_errors holds each member's unweighted device cost at
     best_controls (one forward evaluation after the loop).
+    matrix_free: SchroedingerEvaluator's keyword ("default" or "wide").
     """
     reject_lindblad_sweep(hamiltonian)
     reject_sweep(hamiltonian, "grape_schroedinger_discrete", _SWEEP_HINT)
@@ -131,7 +134,7 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
         control_count=control_count, control_eval_count=control_eval_count,
         complex_controls=complex_controls, costs=costs, cost_eval_step=cost_eval_step,
         interpolation_policy=interpolation_policy, magnus_policy=magnus_policy,
-        need_gradients=True, latency_mode=True)
+        need_gradients=True, latency_mode=True, matrix_free=matrix_free)
     pstate.log_and_save_initial()
     reporter = Dummy()
     reporter.iteration = 0
@@ -203,7 +206,7 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
                                       iteration_count=1000, log_iteration_step=10,
                                       magnus_policy=MagnusPolicy.M2, max_control_norms=None,
                                       min_error=0, optimizer=Adam(), comm=None,
-                                      control_basis=None):
+                                      control_basis=None, matrix_free="default"):
     """
     Multi-start GRAPE: B = len(initial_controls) independent optimisations of the same problem,
     one batched device evaluation per iteration (the engine's batch axis; the reference runs one
@@ -246,6 +249,9 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     at every seed's best iteration, and sweep_sensitivities is evaluated at the best controls and
     best durations. Adam and SGD keep tau_b resident; LBFGS and plugin optimizers take the host
     loop.
+    matrix_free: SchroedingerEvaluator's keyword - "wide" opts one-state Hermitian problems at
+    33 <= n <= 64 into the matrix-free Taylor sweeps (more than 128 evaluated items: the route
+    yields to the latency mode of smaller batches).
     Returns GrapeSchroedingerBatchResult.
     """
     reject_lindblad_sweep(hamiltonian)
@@ -264,7 +270,7 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
         control_count=control_count, control_eval_count=control_eval_count,
         complex_controls=complex_controls, costs=costs, cost_eval_step=cost_eval_step,
         interpolation_policy=interpolation_policy, magnus_policy=magnus_policy,
-        need_gradients=True, latency_mode=items <= 128)
+        need_gradients=True, latency_mode=items <= 128, matrix_free=matrix_free)
     stepper = batch.batched_stepper(optimizer, params)
     if getattr(evaluator, "sweep", None) is not None and evaluator.sweep.searches_duration:
         pstate.duration_search = evaluator  # (both loops carry tau_b beside the controls)

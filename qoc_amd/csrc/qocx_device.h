@@ -198,7 +198,8 @@ struct KrylovArgs {
     double2* mbar_rm;
 };
 
-// Matrix-free route of one-state Hermitian problems at 17 <= n <= 32 (qocx_action.hip): the sweeps
+// Matrix-free route of one-state Hermitian problems at 17 <= n <= 32 (qocx_action.hip; 33 <= n <= 64:
+// qocx_action4.hip, NP = 64 in the buffer shapes below): the sweeps
 // apply exp(a_j) to their vector by the truncated Taylor series and leave its terms behind
 struct ActionArgs {
     SweepArgs sw;              // phase, j_begin / j_end, psi0, costs, cost_out, final_out, lam_scale, lam_buf, s_arr, status
@@ -225,6 +226,12 @@ struct ActionGradArgs {
 void launch_action_sweep(const ActionArgs& a, int batch, hipStream_t st);
 void launch_action_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
 int action_grad_lds_bytes(int m_max);
+// ... at 33 <= n <= 64 (qocx_action4.hip, knob "action" = 2; images and vectors padded to 64): workgroups
+// of three (n <= 48) or four waves, each wave 16 columns of the generator; the same arguments, buffers
+// and contract
+void launch_action4_sweep(int n, const ActionArgs& a, int batch, hipStream_t st);
+void launch_action4_grad(int n, const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
+int action4_grad_lds_bytes(int n, int m_max, int K);
 
 // Magnus M4 / M6 generator kernels (qocx_magnus.hip)
 struct MagnusArgs {

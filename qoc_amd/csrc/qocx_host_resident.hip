@@ -281,7 +281,8 @@ struct ResidentRoute {
     bool all_dominant;   // every Pade denominator diagonally dominant
     bool pack8;          // n <= 8: two steps per 16 x 16 tile through K1a and K1b
     bool umode;          // the propagator itself in the Q image, one product per sweep sub-step
-    bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip)
+    bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip, qocx_action4.hip)
+    bool action_table;   // ... at 33 <= n <= 64: launch_step_table for the sweeps alone (no K1a reads it)
     int m_max;           // ... and the Taylor terms per step its buffers hold
 };
 
@@ -348,12 +349,22 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // bit for bit), of the batch size, chunking and segmentation. "pade_order" = 13 keeps executing
     // [13/13]. The degree is decided on the device; the host's bound sizes the buffers (m_max) and a
     // step beyond them sends the evaluation back to the Pade route (eval_items).
+    // Knob "action": 0 never, 1 (default) at 17 <= n <= 32, 2 also at 33 <= n <= 64 (qocx_action4.hip:
+    // workgroups of three waves up to n = 48, of four above). There the step table - which at nb = 2 also
+    // serves K1a - is launched for the sweeps alone; the Pade route above n = 32 knows no step table and
+    // stays as it is.
     const double host_bound = std::min(ctx->norm_bound, ctx->norm_bound_mid);
-    r.action = allow_action && nb == 2 && S == 1 && r.step_table && ctx->nt == 1 && ctx->hermitian &&
+    const int64_t action_knob = ctx->knob("action", 1);
+    const bool table_ok = !explicit_gen && r.nodes == 1 && !r.eff && !r.dense && ctx->K > 0 &&
+                          ctx->g_norm_dev.p != nullptr;
+    const bool sized = nb == 2 ? (action_knob != 0 && r.step_table)
+                               : (nb == 4 && action_knob == 2 && table_ok);  // (33 <= n <= 64: padded to 64)
+    r.action = allow_action && sized && S == 1 && ctx->nt == 1 && ctx->hermitian &&
                ctx->unit_ok && ctx->inj_count == 0 && !ctx->has_step_costs && !r.latency &&
                !r.inverse_sweep && !ctx->keep_step_states && ctx->knob("pade_order", 0) == 0 &&
-               ctx->knob("unit_adjoint", 1) != 0 && ctx->knob("action", 1) != 0 &&
+               ctx->knob("unit_adjoint", 1) != 0 &&
                host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
+    r.action_table = r.action && nb != 2;
     // (the device's bound of a step is the host's up to the rounding of the interpolation)
     r.m_max = r.action ? std::min(QOCX_ACTION_MAX_DEGREE, qocx::action_degree_for(host_bound * (1 + 1e-9))) : 0;
     return r;
@@ -533,7 +544,7 @@ struct ResidentChunk {
         fa.s_arr = ctx->s_arr.p; fa.status = ctx->status.p;
         fa.fuse_lu = r.fused_lu ? 1 : 0;
         fa.dinv = ctx->dinv.p; fa.perm = ctx->perm.p; fa.iperm = ctx->iperm.p;
-        if (r.step_table) {
+        if (r.step_table || r.action_table) {
             if (ctx->ustep.ensure((size_t)bc * nsteps * K)) return QOCX_ERR_HIP;
             qocx::StepTableArgs ta;
             ta.controls = fa.controls; ta.interp = fa.interp; ta.K = K; ta.nc = ctx->nc;
@@ -739,7 +750,8 @@ struct ResidentChunk {
         if (!((dbg_skip & 1) && (phase & 1)) && !((dbg_skip & 2) && (phase & 2))) {
             if (r.action) {
                 aa.sw = sa;
-                qocx::launch_action_sweep(aa, bc, st);
+                if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
+                else qocx::launch_action4_sweep(ctx->n, aa, bc, st);
             } else if (r.dense) qocx::launch_sweepd(sa, bc, st);
             else if (r.inverse_sweep) qocx::launch_sweepi(ctx->nb, sa, bc, st);
             else if (r.sweep3) qocx::launch_sweep3(ctx->nb, sa, bc, st);
@@ -755,7 +767,9 @@ struct ResidentChunk {
         time_begin(ctx, 2, cs);
         if (r.action) {
             ga.step0 = jb;
-            if (!(dbg_skip & 4)) qocx::launch_action_grad(ga, len, bc, cs);
+            if (dbg_skip & 4) {
+            } else if (ctx->nb == 2) qocx::launch_action_grad(ga, len, bc, cs);
+            else qocx::launch_action4_grad(ctx->n, ga, len, bc, cs);
         } else if (!(dbg_skip & 4)) qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
         if (r.nodes > 1) {
             ma.step0 = jb; ma.seg_len = len; ma.total = (size_t)bc * len;
