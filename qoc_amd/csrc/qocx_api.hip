@@ -571,10 +571,8 @@ int qocx_set_schroedinger_problem(qocx_ctx* ctx, const qocx_schroedinger_problem
     ctx->T = p->evolution_time;
     ctx->dt = p->evolution_time / (N - 1);  // programstate.py:44
     ctx->eff.kind = EffectiveControls::NONE;  // a new problem clears the quadratic terms
-    ctx->ens_M = 0;                           // ... and the ensemble
+    ctx->seeds.clear();                       // ... the ensemble or the sweep, with its duration search
     ctx->ens_qscales_set = false;
-    ctx->swp_B = 0;                           // ... and the sweep
-    ctx->dur_set = ctx->dur_mirror_stale = false;  // ... with its duration search
 
     set_hermitian_flags(ctx, p);
     if (int rc = upload_operators(ctx, p)) return rc;
@@ -615,7 +613,7 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
         return 0;
     }
     if (!pairs || !matrices) return fail(QOCX_ERR_ARG, "pairs / matrices missing");
-    if (ctx->swp_B > 0)
+    if (ctx->seeds.sweep())
         return fail(QOCX_ERR_STATE, "a sweep is set (qocx_set_sweep): it does not take quadratic terms");
     if (ctx->nodes != 1)
         return fail(QOCX_ERR_ARG, "quadratic terms need magnus_policy M2 (M4 / M6 take the callable's tangent)");
@@ -628,9 +626,9 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     for (int q = 0; q < count; ++q)
         if (pairs[2 * q] < 0 || pairs[2 * q] > pairs[2 * q + 1] || pairs[2 * q + 1] >= K)
             return fail(QOCX_ERR_ARG, "quadratic term pairs must satisfy 0 <= k <= l < control_count");
-    if (ctx->ens_M > 0)
+    if (ctx->seeds.M > 0)
         for (int q = 0; q < count; ++q)
-            if (pairs[2 * q + 1] >= ctx->ens_Kr)
+            if (pairs[2 * q + 1] >= ctx->seeds.Kr)
                 return fail(QOCX_ERR_ARG, "quadratic term pairs must index the ensemble's seed channels "
                                           "(l < control_count - fixed)");
     const size_t nn = (size_t)n * n, mat = (size_t)np * np;
@@ -678,118 +676,68 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
     return 0;
 }
 
-int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
-                      const double* offsets, const double* weights) {
-    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
-    if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
-    if (ctx->swp_B > 0)
-        return fail(QOCX_ERR_STATE, "a sweep is set (qocx_set_sweep): a problem takes a sweep or an ensemble");
-    if (members < 1 || members > 1024) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
-    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
-    if (fixed >= ctx->K)
-        return fail(QOCX_ERR_ARG, "an ensemble needs fixed < control_count (at least one seed control)");
-    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed perturbation channels need offsets");
-    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 perturbation channels");
-    if (!weights) return fail(QOCX_ERR_ARG, "weights missing");
-    const int M = members, J = fixed, Kr = ctx->K - fixed;
-    // quadratic terms are products of the seeds' channels (qocx_set_quadratic_terms checks the same
-    // when it comes second)
-    for (int q = 0; q < ctx->eff.quad_count(); ++q)
-        if (ctx->eff.pairs[2 * q + 1] >= Kr)
-            return fail(QOCX_ERR_ARG, "quadratic term pairs must index the ensemble's seed channels "
-                                      "(l < control_count - fixed)");
-    std::vector<double> sc((size_t)M * Kr, 1.0), off((size_t)M * J), w(weights, weights + M);
-    if (scales) sc.assign(scales, scales + sc.size());
-    if (J > 0) off.assign(offsets, offsets + off.size());
-    for (double v : sc)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble control scale");
-    for (double v : off)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble offset");
-    for (double v : w)
-        if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "ensemble weights must be finite and >= 0");
-    std::vector<double> smax(Kr, 0.0), omax(J, 0.0);
-    for (int m = 0; m < M; ++m) {
-        for (int k = 0; k < Kr; ++k) smax[k] = std::max(smax[k], fabs(sc[(size_t)m * Kr + k]));
-        for (int j = 0; j < J; ++j) omax[j] = std::max(omax[j], fabs(off[(size_t)m * J + j]));
+// What this path keeps beside seed tables just set: max_r |factor s_rk| and max_r |factor delta_rj| over
+// their rows, for the bound qocx_opt_clip commits; and nothing of earlier uploads stands
+static void seed_tables_were_set(qocx_ctx* ctx, const std::vector<double>& sc, const std::vector<double>& off,
+                                 double factor) {
+    const int rows = ctx->seeds.rows(), Kr = ctx->seeds.Kr, J = ctx->seeds.J;
+    ctx->ens_scale_max.assign(Kr, 0.0);
+    ctx->ens_offset_max.assign(J, 0.0);
+    for (int r = 0; r < rows; ++r) {
+        for (int k = 0; k < Kr; ++k)
+            ctx->ens_scale_max[k] = std::max(ctx->ens_scale_max[k], fabs(factor * sc[(size_t)r * Kr + k]));
+        for (int j = 0; j < J; ++j)
+            ctx->ens_offset_max[j] = std::max(ctx->ens_offset_max[j], fabs(factor * off[(size_t)r * J + j]));
     }
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->ens_scales.upload(sc, ctx->stream) || ctx->ens_weights.upload(w, ctx->stream) ||
-        (J > 0 && ctx->ens_offsets.upload(off, ctx->stream)))
-        return QOCX_ERR_HIP;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->ens_scales_h = sc;
-    ctx->ens_offsets_h = off;
-    ctx->ens_scale_max = smax;
-    ctx->ens_offset_max = omax;
-    ctx->ens_M = M;
-    ctx->ens_J = J;
-    ctx->ens_Kr = Kr;
     ctx->ens_B = 0;
     ctx->ens_stale = false;
     ctx->ens_qscales_set = false;  // (scales of the previous ensemble's members)
     ctx->have_results = false;
-    ctx->B = 0;  // controls must be uploaded again (as seed controls)
+    ctx->B = 0;  // controls must be uploaded again (as seed controls: their staging takes the new tables)
     ctx->ms.batch = 0;
+}
+
+int qocx_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, const double* scales,
+                      const double* offsets, const double* weights) {
+    if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
+    if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
+    if (ctx->seeds.sweep())
+        return fail(QOCX_ERR_STATE, "a sweep is set (qocx_set_sweep): a problem takes a sweep or an ensemble");
+    // quadratic terms are products of the seeds' channels (qocx_set_quadratic_terms checks the same
+    // when it comes second)
+    for (int q = 0; q < ctx->eff.quad_count(); ++q)
+        if (ctx->eff.pairs[2 * q + 1] >= ctx->K - fixed)
+            return fail(QOCX_ERR_ARG, "quadratic term pairs must index the ensemble's seed channels "
+                                      "(l < control_count - fixed)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = set_seed_tables(ctx->seeds, false, ctx->K, members, fixed, scales, offsets, weights, ctx->stream))
+        return rc;
+    seed_tables_were_set(ctx, ctx->seeds.scales_h, ctx->seeds.offsets_h, 1.0);
     return 0;
 }
 
 int qocx_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const double* scales, const double* offsets) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
-    if (ctx->ens_M > 0 && ctx->swp_B == 0)
+    if (ctx->seeds.M > 0 && !ctx->seeds.sweep())
         return fail(QOCX_ERR_STATE, "an ensemble is set (qocx_set_ensemble): a problem takes a sweep or an ensemble");
     if (ctx->eff.quad_count() > 0)
         return fail(QOCX_ERR_STATE, "quadratic terms are set (qocx_set_quadratic_terms): a sweep does not take them");
-    if (seeds < 1) return fail(QOCX_ERR_ARG, "sweep seeds must be >= 1");
-    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
-    if (fixed >= ctx->K)
-        return fail(QOCX_ERR_ARG, "a sweep needs fixed < control_count (at least one seed control)");
-    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed channels need offsets");
-    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 channels");
-    const int B = seeds, J = fixed, Kr = ctx->K - fixed;
-    std::vector<double> sc((size_t)B * Kr, 1.0), off((size_t)B * J);
-    if (scales) sc.assign(scales, scales + sc.size());
-    if (J > 0) off.assign(offsets, offsets + off.size());
-    for (double v : sc)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep control scale");
-    for (double v : off)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep offset");
-    std::vector<double> smax(Kr, 0.0), omax(J, 0.0);
-    for (int b = 0; b < B; ++b) {
-        for (int k = 0; k < Kr; ++k) smax[k] = std::max(smax[k], fabs(sc[(size_t)b * Kr + k]));
-        for (int j = 0; j < J; ++j) omax[j] = std::max(omax[j], fabs(off[(size_t)b * J + j]));
-    }
     HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->swp_scales.upload(sc, ctx->stream) || (J > 0 && ctx->swp_offsets.upload(off, ctx->stream)))
-        return QOCX_ERR_HIP;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->swp_scales_h = sc;
-    ctx->swp_offsets_h = off;
-    ctx->swp_B = B;
-    ctx->dur_set = ctx->dur_mirror_stale = ctx->dur_have_grad = false;  // (a new sweep: no duration search)
-    // the seed-level view: one item per seed (qocx_host.h)
-    ctx->ens_scale_max = smax;
-    ctx->ens_offset_max = omax;
-    ctx->ens_M = 1;
-    ctx->ens_J = J;
-    ctx->ens_Kr = Kr;
-    ctx->ens_B = 0;
-    ctx->ens_stale = false;
-    ctx->ens_qscales_set = false;
-    ctx->have_results = false;
-    ctx->B = 0;  // controls must be uploaded again (as seed controls)
-    ctx->ms.batch = 0;
+    if (int rc = set_seed_tables(ctx->seeds, true, ctx->K, seeds, fixed, scales, offsets, nullptr, ctx->stream))
+        return rc;
+    seed_tables_were_set(ctx, ctx->seeds.scales_h, ctx->seeds.offsets_h, 1.0);
     return 0;
 }
 
 int qocx_set_ensemble_quadratic_scales(qocx_ctx* ctx, int32_t members, int32_t count, const double* scales) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set (qocx_set_schroedinger_problem first)");
-    if (ctx->ens_M == 0 || ctx->swp_B > 0)
+    if (ctx->seeds.M == 0 || ctx->seeds.swp_B > 0)
         return fail(QOCX_ERR_ARG, "quadratic term scales need an ensemble (qocx_set_ensemble)");
     if (ctx->eff.quad_count() == 0)
         return fail(QOCX_ERR_ARG, "quadratic term scales need quadratic terms (qocx_set_quadratic_terms)");
-    if (members != ctx->ens_M) return fail(QOCX_ERR_ARG, "members does not match the ensemble's");
+    if (members != ctx->seeds.M) return fail(QOCX_ERR_ARG, "members does not match the ensemble's");
     if (count != ctx->eff.quad_count()) return fail(QOCX_ERR_ARG, "count does not match the quadratic terms'");
     if (!scales) {
         ctx->ens_qscales_set = false;
@@ -865,7 +813,7 @@ double quad_bound(const qocx_ctx* ctx, const double* umax) {
     double b = 0.0;
     if (ctx->effctl_kind(false) != EffectiveControls::QUADRATIC) return b;
     const EffectiveControls& eff = ctx->eff;
-    const bool ens = ctx->ens_M > 0;
+    const bool ens = ctx->seeds.M > 0;
     for (int q = 0; q < eff.quad_count(); ++q) {
         const int k = eff.pairs[2 * q], l = eff.pairs[2 * q + 1];
         if (!ens) {
@@ -880,11 +828,11 @@ double quad_bound(const qocx_ctx* ctx, const double* umax) {
 
 // The seed-level view: with an ensemble the entry points of the host's optimizer loop (costs,
 // gradients, qocx_opt_*) act on the seeds and their K_r channels, else on the items themselves.
-int seed_count(const qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_B : ctx->B; }
-int seed_channels(const qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_Kr : ctx->K; }
-double* seed_controls(qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_controls.p : ctx->controls.p; }
-double* seed_costs(qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_cost.p : ctx->cost_out.p; }
-double* seed_grads(qocx_ctx* ctx) { return ctx->ens_M > 0 ? ctx->ens_grads.p : ctx->grads.p; }
+int seed_count(const qocx_ctx* ctx) { return ctx->seeds.M > 0 ? ctx->ens_B : ctx->B; }
+int seed_channels(const qocx_ctx* ctx) { return ctx->seeds.M > 0 ? ctx->seeds.Kr : ctx->K; }
+double* seed_controls(qocx_ctx* ctx) { return ctx->seeds.M > 0 ? ctx->ens_controls.p : ctx->controls.p; }
+double* seed_costs(qocx_ctx* ctx) { return ctx->seeds.M > 0 ? ctx->ens_cost.p : ctx->cost_out.p; }
+double* seed_grads(qocx_ctx* ctx) { return ctx->seeds.M > 0 ? ctx->ens_grads.p : ctx->grads.p; }
 
 }  // namespace qocx::host
 
@@ -901,33 +849,149 @@ std::vector<double> quad_control_max(const double* rows_p, size_t rows, int K) {
     return m;
 }
 
-// ---- Hamiltonian ensembles (qocx_set_ensemble) ----------------------------------------------------
+}  // namespace
 
-qocx::EnsembleArgs ensemble_args(qocx_ctx* ctx, int seeds) {
+// ---- Hamiltonian ensembles and sweeps: what both paths do with a SeedTables (qocx_host.h) -----------
+
+namespace qocx::host {
+
+int set_seed_tables(SeedTables& s, bool sweep, int K, int rows, int fixed, const double* scales,
+                    const double* offsets, const double* weights, hipStream_t st) {
+    const std::string kind = sweep ? "sweep" : "ensemble";
+    if (sweep && rows < 1) return fail(QOCX_ERR_ARG, "sweep seeds must be >= 1");
+    if (!sweep && (rows < 1 || rows > 1024)) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
+    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
+    if (fixed >= K)
+        return fail(QOCX_ERR_ARG,
+                    (sweep ? "a " : "an ") + kind + " needs fixed < control_count (at least one seed control)");
+    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed channels need offsets");
+    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 channels");
+    if (!sweep && !weights) return fail(QOCX_ERR_ARG, "weights missing");
+    const int J = fixed, Kr = K - fixed;
+    std::vector<double> sc((size_t)rows * Kr, 1.0), off((size_t)rows * J), w;
+    if (scales) sc.assign(scales, scales + sc.size());
+    if (J > 0) off.assign(offsets, offsets + off.size());
+    if (!sweep) w.assign(weights, weights + rows);
+    for (double v : sc)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite " + kind + " control scale");
+    for (double v : off)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite " + kind + " offset");
+    for (double v : w)
+        if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "ensemble weights must be finite and >= 0");
+    if (s.scales.upload(sc, st) || (!sweep && s.weights.upload(w, st)) || (J > 0 && s.offsets.upload(off, st)))
+        return QOCX_ERR_HIP;
+    HIP_TRY(hipStreamSynchronize(st));  // sc, off, w are local
+    s.scales_h.swap(sc);
+    s.offsets_h.swap(off);
+    s.M = sweep ? 1 : rows;
+    s.J = J;
+    s.Kr = Kr;
+    s.swp_B = sweep ? rows : 0;
+    s.dur.clear();  // (a new sweep: no duration search)
+    return 0;
+}
+
+int set_seed_durations(SeedTables& s, const double* tau, const double* base_scales, const double* base_offsets,
+                       double tau_min, double tau_max, double time_weight, hipStream_t st, std::vector<double>& s0,
+                       std::vector<double>& d0) {
+    const int B = s.swp_B, Kr = s.Kr, J = s.J;
+    if (J < 1 || !base_offsets)
+        return fail(QOCX_ERR_ARG, "a duration search needs the drift as the first fixed channel (base_offsets [B][J], J >= 1)");
+    if (!std::isfinite(tau_min) || !std::isfinite(tau_max) || !(tau_min > 0) || !(tau_min <= tau_max))
+        return fail(QOCX_ERR_ARG, "the duration box needs finite 0 < tau_min <= tau_max");
+    if (!std::isfinite(time_weight) || time_weight < 0)
+        return fail(QOCX_ERR_ARG, "time_weight must be finite and >= 0");
+    std::vector<double> t(tau, tau + B);
+    s0.assign((size_t)B * Kr, 1.0);
+    d0.assign(base_offsets, base_offsets + (size_t)B * J);
+    if (base_scales) s0.assign(base_scales, base_scales + s0.size());
+    for (double v : t)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite duration");
+    for (double v : s0)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base control scale");
+    for (double v : d0)
+        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base offset");
+    if (s.dur.tau.upload(t, st) || s.dur.base_scales.upload(s0, st) || s.dur.base_offsets.upload(d0, st) ||
+        s.scales.ensure(s0.size()) || s.offsets.ensure(d0.size()))
+        return QOCX_ERR_HIP;
+    s.dur.tau_min = tau_min; s.dur.tau_max = tau_max; s.dur.weight = time_weight;
+    return 0;
+}
+
+int download_seed_durations(const SeedTables& s, hipStream_t st, bool gradient_stands, double* tau_out,
+                            double* tau_grad_out) {
+    if (tau_grad_out && !gradient_stands)
+        return fail(QOCX_ERR_STATE, "duration gradients need an evaluation with gradients");
+    const size_t bytes = (size_t)s.swp_B * sizeof(double);
+    if (tau_out) HIP_TRY(hipMemcpyAsync(tau_out, s.dur.tau.p, bytes, hipMemcpyDeviceToHost, st));
+    if (tau_grad_out) HIP_TRY(hipMemcpyAsync(tau_grad_out, s.dur.grad.p, bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+qocx::EnsembleArgs ensemble_args(const SeedTables& s, int seeds, int nc, const SeedBuffers& b) {
     qocx::EnsembleArgs a;
-    a.seed_controls = ctx->ens_controls.p; a.scales = ctx->ens_scales.p;
-    a.offsets = ctx->ens_J > 0 ? ctx->ens_offsets.p : nullptr; a.weights = ctx->ens_weights.p;
-    a.controls = ctx->controls.p;
-    a.member_cost = ctx->cost_out.p; a.member_grads = ctx->grads.p;
-    a.cost = ctx->ens_cost.p; a.grads = ctx->ens_grads.p;
-    a.B = seeds; a.M = ctx->ens_M; a.nc = ctx->nc; a.K = ctx->K; a.Kr = ctx->ens_Kr; a.J = ctx->ens_J;
+    a.seed_controls = b.seed_controls; a.scales = s.scales.p;
+    a.offsets = s.J > 0 ? s.offsets.p : nullptr; a.weights = s.weights.p;
+    a.controls = b.items;
+    a.member_cost = b.item_cost; a.member_grads = b.item_grads;
+    a.cost = b.cost; a.grads = b.grads;
+    a.B = seeds; a.M = s.M; a.nc = nc; a.K = s.Kr + s.J; a.Kr = s.Kr; a.J = s.J;
     return a;
+}
+
+qocx::SystemSweepArgs sweep_args(const SeedTables& s, int nc, const SeedBuffers& b) {
+    qocx::SystemSweepArgs a;
+    a.seed_controls = b.seed_controls; a.scales = s.scales.p;
+    a.offsets = s.J > 0 ? s.offsets.p : nullptr;
+    a.controls = b.items;
+    a.item_cost = b.item_cost; a.item_grads = b.item_grads;
+    a.cost = b.cost; a.grads = b.grads;
+    a.scale_sens = s.scale_sens.p; a.offset_sens = s.offset_sens.p;
+    a.B = s.swp_B; a.nc = nc; a.K = s.Kr + s.J; a.Kr = s.Kr; a.J = s.J;
+    return a;
+}
+
+qocx::DurationArgs duration_args(const SeedTables& s, double* tau_grad, double* cost) {
+    qocx::DurationArgs a;
+    a.tau = s.dur.tau.p;
+    a.base_scales = s.dur.base_scales.p; a.base_offsets = s.dur.base_offsets.p;  // (J >= 1)
+    a.scales = s.scales.p; a.offsets = s.offsets.p;
+    a.scale_sens = s.scale_sens.p; a.offset_sens = s.offset_sens.p;
+    a.tau_grad = tau_grad;
+    a.cost = cost;
+    a.tau_min = s.dur.tau_min; a.tau_max = s.dur.tau_max; a.time_weight = s.dur.weight;
+    a.B = s.swp_B; a.Kr = s.Kr; a.J = s.J;
+    return a;
+}
+
+}  // namespace qocx::host
+
+namespace {
+
+SeedBuffers seed_buffers(qocx_ctx* ctx) {
+    return {ctx->ens_controls.p, ctx->controls.p, ctx->cost_out.p, ctx->grads.p, ctx->ens_cost.p, ctx->ens_grads.p};
+}
+qocx::SystemSweepArgs sweep_args(qocx_ctx* ctx) {
+    return qocx::host::sweep_args(ctx->seeds, ctx->nc, seed_buffers(ctx));
 }
 
 // The seeds' controls into the pinned staging buffer, and the bounds qocx_upload_controls takes from
 // a control array: here those of the expanded [B][M][nc][K] array - the same per-row sum in the same
-// order over the member rows (s_mk u_bjk for k < K_r, delta_mj beyond), so they equal bit for bit
-// what an upload of the expanded array gives.
-void ensemble_stage(const qocx_ctx* ctx, int batch, const double* controls, double* stage, double& smax,
-                    double& smid) {
-    const int M = ctx->ens_M, Kr = ctx->ens_Kr, J = ctx->ens_J, nc = ctx->nc;
+// order over the items' rows (s_rk u_bjk for k < K_r, delta_rj beyond; r = m of an ensemble, b of a
+// sweep), so they equal bit for bit what an upload of the expanded array gives, and a sweep's item b
+// takes the Pade orders, squarings and kernel variants of the plain problem.
+void seeds_stage(const qocx_ctx* ctx, int batch, const double* controls, double* stage, double& smax, double& smid) {
+    const SeedTables& t = ctx->seeds;
+    const int M = t.M, Kr = t.Kr, J = t.J, nc = ctx->nc;
     const double* gn = ctx->g_norm_max.data();
     memcpy(stage, controls, (size_t)batch * nc * Kr * sizeof(double));
     double sprev = 0.0;
     for (int b = 0; b < batch; ++b)
         for (int m = 0; m < M; ++m) {
-            const double* s = ctx->ens_scales_h.data() + (size_t)m * Kr;
-            const double* d = ctx->ens_offsets_h.data() + (size_t)m * J;
+            const size_t r = t.sweep() ? b : m;
+            const double* s = t.scales_h.data() + r * Kr;
+            const double* d = t.offsets_h.data() + r * J;
             for (int j = 0; j < nc; ++j) {
                 const double* u = controls + ((size_t)b * nc + j) * Kr;
                 double srow = 0.0;
@@ -943,50 +1007,10 @@ void ensemble_stage(const qocx_ctx* ctx, int batch, const double* controls, doub
         }
 }
 
-// ---- Hamiltonian sweeps (qocx_set_sweep) ------------------------------------------------------------
-
-qocx::SystemSweepArgs sweep_args(qocx_ctx* ctx) {
-    qocx::SystemSweepArgs a;
-    a.seed_controls = ctx->ens_controls.p; a.scales = ctx->swp_scales.p;
-    a.offsets = ctx->ens_J > 0 ? ctx->swp_offsets.p : nullptr;
-    a.controls = ctx->controls.p;
-    a.item_cost = ctx->cost_out.p; a.item_grads = ctx->grads.p;
-    a.cost = ctx->ens_cost.p; a.grads = ctx->ens_grads.p;
-    a.scale_sens = ctx->swp_scale_sens.p; a.offset_sens = ctx->swp_offset_sens.p;
-    a.B = ctx->swp_B; a.nc = ctx->nc; a.K = ctx->K; a.Kr = ctx->ens_Kr; a.J = ctx->ens_J;
-    return a;
-}
-
-// ensemble_stage for a sweep: the bounds of the expanded [B][nc][K] array, row by row in the order of
-// the plain upload (s_bk u_bjk for k < K_r, delta_bj beyond) - bit for bit those of an upload of the
-// expanded array, so item b takes the Pade orders, squarings and kernel variants of the plain problem.
-void sweep_stage(const qocx_ctx* ctx, const double* controls, double* stage, double& smax, double& smid) {
-    const int B = ctx->swp_B, Kr = ctx->ens_Kr, J = ctx->ens_J, nc = ctx->nc;
-    const double* gn = ctx->g_norm_max.data();
-    memcpy(stage, controls, (size_t)B * nc * Kr * sizeof(double));
-    double sprev = 0.0;
-    for (int b = 0; b < B; ++b) {
-        const double* s = ctx->swp_scales_h.data() + (size_t)b * Kr;
-        const double* d = ctx->swp_offsets_h.data() + (size_t)b * J;
-        for (int j = 0; j < nc; ++j) {
-            const double* u = controls + ((size_t)b * nc + j) * Kr;
-            double srow = 0.0;
-            for (int k = 0; k < Kr; ++k) srow += fabs(s[k] * u[k]) * gn[k];
-            for (int k = 0; k < J; ++k) srow += fabs(d[k]) * gn[Kr + k];
-            if (!(srow <= smax)) smax = srow;  // also catches NaN
-            if (j != 0) {
-                const double mid = 0.5 * (sprev + srow);
-                if (!(mid <= smid)) smid = mid;
-            }
-            sprev = srow;
-        }
-    }
-}
-
 // expand the seeds' controls into the member items of ctx->controls (a sweep: into its B items)
 int ensemble_expand(qocx_ctx* ctx, int seeds) {
-    if (ctx->swp_B > 0) qocx::launch_sweep_expand(sweep_args(ctx), ctx->stream);
-    else qocx::launch_ensemble_expand(ensemble_args(ctx, seeds), ctx->stream);
+    if (ctx->seeds.sweep()) qocx::launch_sweep_expand(sweep_args(ctx), ctx->stream);
+    else qocx::launch_ensemble_expand(ensemble_args(ctx->seeds, seeds, ctx->nc, seed_buffers(ctx)), ctx->stream);
     HIP_TRY(hipGetLastError());
     ctx->ens_stale = false;
     return 0;
@@ -994,8 +1018,8 @@ int ensemble_expand(qocx_ctx* ctx, int seeds) {
 
 // the staged seed controls to the device, expanded there
 int ensemble_upload(qocx_ctx* ctx, int batch, const double* stage) {
-    const size_t seeds = (size_t)batch * ctx->nc * ctx->ens_Kr;
-    const size_t items = (size_t)batch * ctx->ens_M * ctx->nc * ctx->K;
+    const size_t seeds = (size_t)batch * ctx->nc * ctx->seeds.Kr;
+    const size_t items = (size_t)batch * ctx->seeds.M * ctx->nc * ctx->K;
     if ((items + 255) / 256 > 0x7fffffffu) return fail(QOCX_ERR_ARG, "ensemble control arrays too large");
     if (ctx->ens_controls.ensure(seeds) || ctx->controls.ensure(items)) return QOCX_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(ctx->ens_controls.p, stage, seeds * sizeof(double), hipMemcpyHostToDevice,
@@ -1003,59 +1027,38 @@ int ensemble_upload(qocx_ctx* ctx, int batch, const double* stage) {
     return ensemble_expand(ctx, batch);
 }
 
-// A duration search's tables as the device holds them, into swp_scales_h / swp_offsets_h
+// A duration search's tables as the device holds them, into seeds.scales_h / seeds.offsets_h
 int sweep_mirror_tables(qocx_ctx* ctx) {
-    const size_t ns = (size_t)ctx->swp_B * ctx->ens_Kr, no = (size_t)ctx->swp_B * ctx->ens_J;
-    ctx->swp_scales_h.resize(ns);
-    ctx->swp_offsets_h.resize(no);
-    HIP_TRY(hipMemcpyAsync(ctx->swp_scales_h.data(), ctx->swp_scales.p, ns * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream));
+    SeedTables& t = ctx->seeds;
+    const size_t ns = (size_t)t.swp_B * t.Kr, no = (size_t)t.swp_B * t.J;
+    t.scales_h.resize(ns);
+    t.offsets_h.resize(no);
+    HIP_TRY(hipMemcpyAsync(t.scales_h.data(), t.scales.p, ns * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (no > 0)
-        HIP_TRY(hipMemcpyAsync(ctx->swp_offsets_h.data(), ctx->swp_offsets.p, no * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(t.offsets_h.data(), t.offsets.p, no * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->dur_mirror_stale = false;
+    t.dur.mirror_stale = false;
     return 0;
 }
 
 // The tail of an evaluation of a duration search: dE_b/dtau_b + time_weight from the sensitivities
 // (with gradients), and time_weight tau_b onto the seed costs - after every other term of the cost
 int duration_finish(qocx_ctx* ctx) {
-    if (!ctx->dur_set) return 0;
-    const int B = ctx->swp_B;
-    const size_t ns = (size_t)B * ctx->ens_Kr, no = (size_t)B * ctx->ens_J;
-    if (ctx->dur_grad.ensure((size_t)B) || ctx->swp_scale_sens.ensure(ns) || ctx->swp_offset_sens.ensure(no))
-        return QOCX_ERR_HIP;
+    SeedTables& t = ctx->seeds;
+    if (!t.dur.set) return 0;
+    const size_t B = (size_t)t.swp_B;
+    if (t.dur.grad.ensure(B) || t.scale_sens.ensure(B * t.Kr) || t.offset_sens.ensure(B * t.J)) return QOCX_ERR_HIP;
     if (ctx->have_grads) qocx::launch_sweep_sensitivity(sweep_args(ctx), ctx->stream);
-    qocx::DurationArgs a = qocx::host::duration_args(ctx);
-    if (!ctx->have_grads) a.tau_grad = nullptr;
-    qocx::launch_duration_gradient(a, ctx->stream);
+    qocx::launch_duration_gradient(duration_args(t, ctx->have_grads ? t.dur.grad.p : nullptr, ctx->ens_cost.p),
+                                   ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->dur_have_grad = ctx->have_grads;
+    t.dur.have_grad = ctx->have_grads;
     return 0;
 }
 
 }  // namespace
-
-namespace qocx::host {
-
-qocx::DurationArgs duration_args(qocx_ctx* ctx) {
-    qocx::DurationArgs a;
-    a.tau = ctx->dur_tau.p;
-    a.base_scales = ctx->dur_base_scales.p;
-    a.base_offsets = ctx->ens_J > 0 ? ctx->dur_base_offsets.p : nullptr;
-    a.scales = ctx->swp_scales.p;
-    a.offsets = ctx->ens_J > 0 ? ctx->swp_offsets.p : nullptr;
-    a.scale_sens = ctx->swp_scale_sens.p; a.offset_sens = ctx->swp_offset_sens.p;
-    a.tau_grad = ctx->dur_grad.p;
-    a.cost = ctx->ens_cost.p;
-    a.tau_min = ctx->dur_tau_min; a.tau_max = ctx->dur_tau_max; a.time_weight = ctx->dur_weight;
-    a.B = ctx->swp_B; a.Kr = ctx->ens_Kr; a.J = ctx->ens_J;
-    return a;
-}
-
-}  // namespace qocx::host
 
 extern "C" {
 
@@ -1064,13 +1067,13 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     if (!ctx->has_problem) return fail(QOCX_ERR_STATE, "no problem set");
     if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool ens = ctx->ens_M > 0;
-    if (ctx->swp_B > 0 && batch != ctx->swp_B)
+    const bool ens = ctx->seeds.M > 0;
+    if (ctx->seeds.swp_B > 0 && batch != ctx->seeds.swp_B)
         return fail(QOCX_ERR_ARG, "a sweep takes exactly its own seed count as the batch (qocx_set_sweep)");
-    if (ens && (int64_t)batch * ctx->ens_M > 0x7fffffff)
+    if (ens && (int64_t)batch * ctx->seeds.M > 0x7fffffff)
         return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
     // (with an ensemble the caller's array holds the seeds' K_r channels)
-    const size_t per = (size_t)ctx->nc * (ens ? ctx->ens_Kr : ctx->K);
+    const size_t per = (size_t)ctx->nc * (ens ? ctx->seeds.Kr : ctx->K);
     double bound = ctx->h0_norm_max;
     if (ctx->K > 0) {
         if (!controls) return fail(QOCX_ERR_ARG, "controls is NULL");
@@ -1094,10 +1097,9 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // per-step bound (launch_step_table) - tighter than sum_k max_t |u_k(t)| ||G_k||_1
         double smax = 0.0, smid = 0.0, sprev = 0.0;
         double* stage = ctx->pin_controls;
-        if (ctx->dur_mirror_stale)  // (a duration search whose tables qocx_opt_clip has rewritten since)
+        if (ctx->seeds.dur.mirror_stale)  // (a duration search whose tables qocx_opt_clip has rewritten since)
             if (int rc = sweep_mirror_tables(ctx)) return rc;
-        if (ctx->swp_B > 0) sweep_stage(ctx, controls, stage, smax, smid);
-        else if (ens) ensemble_stage(ctx, batch, controls, stage, smax, smid);
+        if (ens) seeds_stage(ctx, batch, controls, stage, smax, smid);
         for (size_t row = 0; !ens && row < (size_t)batch * ctx->nc; ++row) {
             const double* src = controls + row * K;
             double* dst = stage + row * K;
@@ -1128,7 +1130,7 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // (with an ensemble the staging buffer holds the seeds' K_r channels, unscaled: quad_bound
         // applies the members' scales)
         if (ctx->eff.quad_count() > 0)
-            bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, ens ? ctx->ens_Kr : K).data());
+            bound += quad_bound(ctx, quad_control_max(stage, (size_t)batch * ctx->nc, ens ? ctx->seeds.Kr : K).data());
         if (ens) {
             if (int rc = ensemble_upload(ctx, batch, stage)) return rc;
         } else {
@@ -1140,7 +1142,7 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or Hamiltonian");
     if (int rc = commit_step_bound(ctx, bound, false, "bound needs")) return rc;
-    ctx->B = ens ? batch * ctx->ens_M : batch;
+    ctx->B = ens ? batch * ctx->seeds.M : batch;
     ctx->ens_B = ens ? batch : 0;
     ctx->have_results = false;
     ctx->explicit_mode = false;
@@ -1257,7 +1259,7 @@ int qocx_set_keep_step_states(qocx_ctx* ctx, int32_t keep) {
 
 // The evaluation of the seeds of the uploaded controls, without the costs of the controls alone
 static int eval_seeds(qocx_ctx* ctx, int32_t want_grad) {
-    if (ctx->ens_M == 0) return eval_items(ctx, want_grad);
+    if (ctx->seeds.M == 0) return eval_items(ctx, want_grad);
     // ensemble: the member items of the seeds' current controls, evaluated as any batch, then
     // reduced to seed costs and gradients
     if (!ctx->has_problem || ctx->B < 1) return fail(QOCX_ERR_STATE, "no problem / controls");
@@ -1267,17 +1269,12 @@ static int eval_seeds(qocx_ctx* ctx, int32_t want_grad) {
         if (int rc = ensemble_expand(ctx, seeds)) return rc;
     if (int rc = eval_items(ctx, want_grad)) return rc;
     if (ctx->ens_cost.ensure((size_t)seeds) ||
-        (ctx->have_grads && ctx->ens_grads.ensure((size_t)seeds * ctx->nc * ctx->ens_Kr)))
+        (ctx->have_grads && ctx->ens_grads.ensure((size_t)seeds * ctx->nc * ctx->seeds.Kr)))
         return QOCX_ERR_HIP;
-    if (ctx->swp_B > 0) {
-        qocx::SystemSweepArgs a = sweep_args(ctx);
-        if (!ctx->have_grads) a.grads = nullptr;
-        qocx::launch_sweep_reduce(a, ctx->stream);
-    } else {
-        qocx::EnsembleArgs a = ensemble_args(ctx, seeds);
-        if (!ctx->have_grads) a.grads = nullptr;
-        qocx::launch_ensemble_reduce(a, ctx->stream);
-    }
+    SeedBuffers buf = seed_buffers(ctx);
+    if (!ctx->have_grads) buf.grads = nullptr;
+    if (ctx->seeds.sweep()) qocx::launch_sweep_reduce(sweep_args(ctx->seeds, ctx->nc, buf), ctx->stream);
+    else qocx::launch_ensemble_reduce(ensemble_args(ctx->seeds, seeds, ctx->nc, buf), ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -1495,7 +1492,7 @@ int qocx_download_costs(qocx_ctx* ctx, double* cost_out) {
 
 int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
     if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
-    if (ctx->ens_M == 0 || ctx->swp_B > 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_set_ensemble)");
+    if (ctx->seeds.M == 0 || ctx->seeds.swp_B > 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_set_ensemble)");
     if (!ctx->have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(cost_out, ctx->cost_out.p, (size_t)ctx->B * sizeof(double),
@@ -1506,21 +1503,21 @@ int qocx_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
 
 int qocx_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double* offsets_out) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
-    if (ctx->swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_set_sweep)");
+    if (ctx->seeds.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_set_sweep)");
     // (the seed controls on the device are those of the evaluation exactly while its results stand:
     // qocx_opt_clip / _step and an upload clear have_results)
     if (!ctx->have_results || !ctx->have_grads || ctx->ens_stale)
         return fail(QOCX_ERR_STATE, "sweep sensitivities need an evaluation with gradients");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t ns = (size_t)ctx->swp_B * ctx->ens_Kr, no = (size_t)ctx->swp_B * ctx->ens_J;
-    if (ctx->swp_scale_sens.ensure(ns) || ctx->swp_offset_sens.ensure(no)) return QOCX_ERR_HIP;
+    const size_t ns = (size_t)ctx->seeds.swp_B * ctx->seeds.Kr, no = (size_t)ctx->seeds.swp_B * ctx->seeds.J;
+    if (ctx->seeds.scale_sens.ensure(ns) || ctx->seeds.offset_sens.ensure(no)) return QOCX_ERR_HIP;
     qocx::launch_sweep_sensitivity(sweep_args(ctx), ctx->stream);
     HIP_TRY(hipGetLastError());
     if (scales_out)
-        HIP_TRY(hipMemcpyAsync(scales_out, ctx->swp_scale_sens.p, ns * sizeof(double), hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(scales_out, ctx->seeds.scale_sens.p, ns * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
     if (offsets_out && no > 0)
-        HIP_TRY(hipMemcpyAsync(offsets_out, ctx->swp_offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(offsets_out, ctx->seeds.offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -1529,60 +1526,28 @@ int qocx_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out, double*
 int qocx_sweep_set_durations(qocx_ctx* ctx, const double* tau, const double* base_scales,
                              const double* base_offsets, double tau_min, double tau_max, double time_weight) {
     if (!ctx || !tau) return fail(QOCX_ERR_ARG, "NULL argument");
-    if (ctx->swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_set_sweep before qocx_sweep_set_durations)");
-    const int B = ctx->swp_B, Kr = ctx->ens_Kr, J = ctx->ens_J;
-    if (J < 1 || !base_offsets)
-        return fail(QOCX_ERR_ARG, "a duration search needs the drift as the first fixed channel (base_offsets [B][J], J >= 1)");
-    if (!std::isfinite(tau_min) || !std::isfinite(tau_max) || !(tau_min > 0) || !(tau_min <= tau_max))
-        return fail(QOCX_ERR_ARG, "the duration box needs finite 0 < tau_min <= tau_max");
-    if (!std::isfinite(time_weight) || time_weight < 0)
-        return fail(QOCX_ERR_ARG, "time_weight must be finite and >= 0");
-    std::vector<double> t(tau, tau + B), s0((size_t)B * Kr, 1.0), d0(base_offsets, base_offsets + (size_t)B * J);
-    if (base_scales) s0.assign(base_scales, base_scales + s0.size());
-    for (double v : t)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite duration");
-    for (double v : s0)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base control scale");
-    for (double v : d0)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base offset");
-    // the bound qocx_opt_clip commits must hold for every tau the optimizer can reach: tau_max
-    std::vector<double> smax(Kr, 0.0), omax(J, 0.0);
-    for (int b = 0; b < B; ++b) {
-        for (int k = 0; k < Kr; ++k) smax[k] = std::max(smax[k], fabs(tau_max * s0[(size_t)b * Kr + k]));
-        for (int j = 0; j < J; ++j) omax[j] = std::max(omax[j], fabs(tau_max * d0[(size_t)b * J + j]));
-    }
+    if (!ctx->seeds.sweep()) return fail(QOCX_ERR_STATE, "no sweep set (qocx_set_sweep before qocx_sweep_set_durations)");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->dur_tau.upload(t, ctx->stream) || ctx->dur_base_scales.upload(s0, ctx->stream) ||
-        ctx->dur_base_offsets.upload(d0, ctx->stream) || ctx->swp_scales.ensure(s0.size()) ||
-        ctx->swp_offsets.ensure(d0.size()))
-        return QOCX_ERR_HIP;
-    ctx->dur_tau_min = tau_min; ctx->dur_tau_max = tau_max; ctx->dur_weight = time_weight;
-    qocx::launch_duration_tables(duration_args(ctx), ctx->stream);
+    std::vector<double> s0, d0;
+    if (int rc = set_seed_durations(ctx->seeds, tau, base_scales, base_offsets, tau_min, tau_max, time_weight,
+                                    ctx->stream, s0, d0))
+        return rc;
+    qocx::launch_duration_tables(duration_args(ctx->seeds, nullptr, nullptr), ctx->stream);
     HIP_TRY(hipGetLastError());
-    if (int rc = sweep_mirror_tables(ctx)) return rc;  // (synchronises: t, s0, d0 are local)
-    ctx->ens_scale_max = smax;
-    ctx->ens_offset_max = omax;
-    ctx->dur_set = true;
-    ctx->dur_have_grad = false;
-    ctx->have_results = false;
-    ctx->B = 0;  // controls must be uploaded again: their staging takes the new tables
-    ctx->ens_B = 0;
-    ctx->ms.batch = 0;
+    if (int rc = sweep_mirror_tables(ctx)) return rc;
+    // the bound qocx_opt_clip commits must hold for every tau the optimizer can reach: tau_max
+    seed_tables_were_set(ctx, s0, d0, tau_max);
+    ctx->seeds.dur.set = true;
+    ctx->seeds.dur.have_grad = false;
     return 0;
 }
 
 int qocx_sweep_download_durations(qocx_ctx* ctx, double* tau_out, double* tau_grad_out) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
-    if (!ctx->dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_sweep_set_durations)");
-    if (tau_grad_out && (!ctx->have_results || !ctx->have_grads || ctx->ens_stale || !ctx->dur_have_grad))
-        return fail(QOCX_ERR_STATE, "duration gradients need an evaluation with gradients");
+    if (!ctx->seeds.dur.set) return fail(QOCX_ERR_STATE, "no durations set (qocx_sweep_set_durations)");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)ctx->swp_B * sizeof(double);
-    if (tau_out) HIP_TRY(hipMemcpyAsync(tau_out, ctx->dur_tau.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (tau_grad_out)
-        HIP_TRY(hipMemcpyAsync(tau_grad_out, ctx->dur_grad.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    const bool stands = ctx->have_results && ctx->have_grads && !ctx->ens_stale && ctx->seeds.dur.have_grad;
+    return download_seed_durations(ctx->seeds, ctx->stream, stands, tau_out, tau_grad_out);
 }
 
 int qocx_reduce_results(qocx_ctx* ctx, int32_t allreduce, double* out, int64_t count) {

@@ -501,12 +501,10 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     lb.res_B = lb.ms.batch = 0;  // resident controls and optimizer states belong to the old problem
     lb.res_have_results = false;
     lb.inj_count = 0;
-    lb.ens_M = lb.ens_J = lb.ens_Kr = 0;  // ... and so does the ensemble, with its rates
+    lb.seeds.clear();  // ... and so do the ensemble with its rates, or the sweep with its duration search
     lb.ens_members_B = 0;
     lb.ens_rates = false;
-    lb.swp_B = 0;  // ... and the sweep
     lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
-    lb.dur_set = lb.dur_mirror_stale = lb.dur_have_grad = false;  // ... with its duration search
     return 0;
 }
 
@@ -515,38 +513,15 @@ int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, co
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
     if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set (qocx_set_lindblad_problem first)");
-    if (lb.swp_B > 0)
+    if (lb.seeds.sweep())
         return fail(QOCX_ERR_STATE, "a sweep is set (qocx_lindblad_set_sweep): a problem takes a sweep or an ensemble");
-    if (members < 1 || members > 1024) return fail(QOCX_ERR_ARG, "ensemble members must be 1 .. 1024");
-    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
-    // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
-    if (fixed >= lb.K)
-        return fail(QOCX_ERR_ARG, "an ensemble needs fixed < control_count (at least one seed control)");
-    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed perturbation channels need offsets");
-    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 perturbation channels");
-    if (!weights) return fail(QOCX_ERR_ARG, "weights missing");
     if (lb.inj_count > 0)
         return fail(QOCX_ERR_STATE, "density cotangents are set (qocx_set_density_cotangents): an ensemble "
                                     "takes none");
-    const int M = members, J = fixed, Kr = lb.K - fixed;
-    std::vector<double> sc((size_t)M * Kr, 1.0), off((size_t)M * J), w(weights, weights + M);
-    if (scales) sc.assign(scales, scales + sc.size());
-    if (J > 0) off.assign(offsets, offsets + off.size());
-    for (double v : sc)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble control scale");
-    for (double v : off)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite ensemble offset");
-    for (double v : w)
-        if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "ensemble weights must be finite and >= 0");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (lb.ens_scales.upload(sc, ctx->stream) || lb.ens_weights.upload(w, ctx->stream) ||
-        (J > 0 && lb.ens_offsets.upload(off, ctx->stream)))
-        return QOCX_ERR_HIP;
-    lb.ens_scales_h = sc;
-    lb.ens_offsets_h = off;
-    lb.ens_M = M;
-    lb.ens_J = J;
-    lb.ens_Kr = Kr;
+    // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
+    if (int rc = set_seed_tables(lb.seeds, false, lb.K, members, fixed, scales, offsets, weights, ctx->stream))
+        return rc;
     lb.ens_members_B = 0;
     lb.ens_rates = false;        // (qocx_lindblad_set_ensemble_rates comes after, as the quadratic scales do)
     lb.have_results = false;
@@ -598,7 +573,7 @@ int build_rate_tables(qocx_ctx* ctx, int count, const double* rate_scales) {
 int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t operators, const double* rate_scales) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
-    if (!lb.has_problem || lb.ens_M == 0 || lb.swp_B > 0)
+    if (!lb.has_problem || lb.seeds.M == 0 || lb.seeds.swp_B > 0)
         return fail(QOCX_ERR_STATE, "no Lindblad ensemble set (qocx_lindblad_set_ensemble first)");
     if (lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "per-member rates need a static problem: this one was set with stage tables "
@@ -614,7 +589,7 @@ int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t ope
         invalidate();
         return 0;
     }
-    const int M = lb.ens_M, L = lb.nops;
+    const int M = lb.seeds.M, L = lb.nops;
     if (members != M) return fail(QOCX_ERR_ARG, "rate_scales: members differs from the ensemble's");
     if (operators != L) return fail(QOCX_ERR_ARG, "rate_scales: operators differs from the problem's operator_count");
     for (size_t e = 0; e < (size_t)M * L; ++e)
@@ -632,40 +607,36 @@ int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const d
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
     if (!lb.has_problem) return fail(QOCX_ERR_STATE, "no Lindblad problem set (qocx_set_lindblad_problem first)");
-    if (lb.ens_M > 0 && lb.swp_B == 0)
+    if (lb.seeds.M > 0 && !lb.seeds.sweep())
         return fail(QOCX_ERR_STATE, "an ensemble is set (qocx_lindblad_set_ensemble): a problem takes a sweep or an "
                                     "ensemble");
     if (lb.inj_count > 0)
         return fail(QOCX_ERR_STATE, "density cotangents are set (qocx_set_density_cotangents): a sweep takes none");
     // (the rates tables hold at most this many members)
     if (seeds < 1 || seeds > 1024) return fail(QOCX_ERR_ARG, "sweep seeds must be 1 .. 1024");
-    if (fixed < 0) return fail(QOCX_ERR_ARG, "fixed channel count must be >= 0");
-    // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
-    if (fixed >= lb.K) return fail(QOCX_ERR_ARG, "a sweep needs fixed < control_count (at least one seed control)");
-    if (fixed > 0 && !offsets) return fail(QOCX_ERR_ARG, "fixed channels need offsets");
-    if (fixed == 0 && offsets) return fail(QOCX_ERR_ARG, "offsets need fixed >= 1 channels");
-    const bool rates = rate_scales != nullptr && lb.nops > 0;
+    const int L = lb.nops, n = lb.n;
+    const bool rates = rate_scales != nullptr && L > 0;
     if (rates && lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "per-seed rates need a static problem: this one was set with stage tables "
                                     "(fixed_subdivision > 0), which hold one control-free generator per stage");
-    const int B = seeds, J = fixed, Kr = lb.K - fixed, L = lb.nops, n = lb.n;
-    std::vector<double> sc((size_t)B * Kr, 1.0), off((size_t)B * J);
-    if (scales) sc.assign(scales, scales + sc.size());
-    if (J > 0) off.assign(offsets, offsets + off.size());
-    for (double v : sc)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep control scale");
-    for (double v : off)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite sweep offset");
-    for (size_t e = 0; rates && e < (size_t)B * L; ++e)
+    for (size_t e = 0; rates && e < (size_t)seeds * L; ++e)
         if (!std::isfinite(rate_scales[e]) || !(rate_scales[e] >= 0))
             return fail(QOCX_ERR_ARG, "rate_scales must be finite and >= 0");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (lb.swp_scales.upload(sc, ctx->stream) || (J > 0 && lb.swp_offsets.upload(off, ctx->stream)))
-        return QOCX_ERR_HIP;
+    // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
+    if (int rc = set_seed_tables(lb.seeds, true, lb.K, seeds, fixed, scales, offsets, nullptr, ctx->stream)) return rc;
+    lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
+    lb.swp_seed_controls = nullptr;
+    lb.ens_members_B = 0;
+    lb.ens_rates = false;        // (until the rates tables below stand)
+    lb.have_results = false;
+    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
+    lb.res_have_results = false;
+    lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
     // seed b: the control-free part of the plain problem with the rates c_b * gamma, built as the plain
     // setter builds its own (build_rate_tables)
     if (rates)
-        if (int rc = build_rate_tables(ctx, B, rate_scales)) return rc;
+        if (int rc = build_rate_tables(ctx, seeds, rate_scales)) return rc;
     // M_l = L_l^H L_l of the problem's own operators, for the rate sensitivities
     if (L > 0) {
         std::vector<cmat> ldl;
@@ -673,28 +644,13 @@ int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const d
         if (upload_dumps(lb.swp_ldl, ldl, n, ctx->stream)) return QOCX_ERR_HIP;
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    lb.swp_scales_h = sc;
-    lb.swp_offsets_h = off;
-    lb.swp_B = B;
-    lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
-    lb.dur_set = lb.dur_mirror_stale = lb.dur_have_grad = false;  // (a new sweep: no duration search)
-    lb.swp_seed_controls = nullptr;
-    // the seed-level view: one item per seed (qocx_host.h)
-    lb.ens_M = 1;
-    lb.ens_J = J;
-    lb.ens_Kr = Kr;
-    lb.ens_members_B = 0;
     lb.ens_rates = rates;
-    lb.have_results = false;
-    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
-    lb.res_have_results = false;
-    lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
     return 0;
 }
 
 int qocx_lindblad_sweep_want_rate_sensitivities(qocx_ctx* ctx, int32_t on) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
-    if (ctx->lb.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
+    if (ctx->lb.seeds.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
     ctx->lb.swp_want_rates = on != 0;
     return 0;
 }
@@ -873,7 +829,7 @@ int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<
         // (per-member rates: B counts items b * M + m, and item (b, m) takes member m's bound - the
         // sub-division count the plain problem with that member's rates would pick; a sweep: item b is seed b)
         const double base = lb.fixed_ksub > 0 ? 2 * lb.h0_norm + 2 * lb.diss_norm
-                            : lb.ens_rates    ? lb.rate_l0_norm[lb.swp_B > 0 ? b : b % lb.ens_M]
+                            : lb.ens_rates    ? lb.rate_l0_norm[lb.seeds.swp_B > 0 ? b : b % lb.seeds.M]
                                               : lb.l0_norm;
         const double bound = base + 2 * ctl;
         if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or operators");
@@ -1001,7 +957,7 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
     // (or a problem with more than four operators) leaves the evaluation without them.
     const int rate_ops = lb.nops;
     // (a duration search asks for them in every evaluation with gradients: dE/dtau needs its rate part)
-    const bool want_rates = lb.swp_B > 0 && (lb.swp_want_rates || lb.dur_set) && want_grad;
+    const bool want_rates = lb.seeds.swp_B > 0 && (lb.swp_want_rates || lb.seeds.dur.set) && want_grad;
     lb.swp_rates_ok = want_rates && rate_ops >= 1 && rate_ops <= 4;
     if (lb.swp_rates_ok && (lb.swp_rate_partials.ensure((size_t)lb.last_subintervals * rate_ops) ||
                             lb.swp_rate_sens.ensure((size_t)B * rate_ops)))
@@ -1166,15 +1122,13 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
 // beyond. |s u| = |s| |u| exactly and rounding is monotone, so these are the maxima of the expanded
 // array, bit for bit (a NaN of umax is carried).
 std::vector<double> lindblad_item_maxima(const qocx_ctx::Lindblad& lb, int seeds, const double* umax) {
-    const int M = lb.ens_M, Kr = lb.ens_Kr, J = lb.ens_J, K = lb.K;
+    const int M = lb.seeds.M, Kr = lb.seeds.Kr, J = lb.seeds.J, K = lb.K;
     std::vector<double> out((size_t)seeds * M * K);
-    // (a sweep: M = 1 and the tables are the seed's own rows)
-    const bool swp = lb.swp_B > 0;
-    const double* scales = swp ? lb.swp_scales_h.data() : lb.ens_scales_h.data();
-    const double* offsets = swp ? lb.swp_offsets_h.data() : lb.ens_offsets_h.data();
+    const double* scales = lb.seeds.scales_h.data();
+    const double* offsets = lb.seeds.offsets_h.data();
     for (int b = 0; b < seeds; ++b)
         for (int m = 0; m < M; ++m) {
-            const size_t row = swp ? (size_t)b : (size_t)m;
+            const size_t row = lb.seeds.sweep() ? b : m;  // (a sweep: M = 1 and the seed's own row)
             double* o = out.data() + ((size_t)b * M + m) * K;
             for (int k = 0; k < Kr; ++k) o[k] = fabs(scales[row * Kr + k]) * umax[(size_t)b * Kr + k];
             for (int j = 0; j < J; ++j) o[Kr + j] = fabs(offsets[row * J + j]);
@@ -1182,69 +1136,30 @@ std::vector<double> lindblad_item_maxima(const qocx_ctx::Lindblad& lb, int seeds
     return out;
 }
 
-// the kernels of qocx_sweep.hip on the Lindblad buffers: seed controls -> items (expand), the items'
-// results in item order -> the seeds' (reduce), and the channel sensitivities
-qocx::SystemSweepArgs lindblad_sweep_args(qocx_ctx* ctx, const double* seed_controls, double* cost, double* grads) {
-    auto& lb = ctx->lb;
-    qocx::SystemSweepArgs a;
-    a.seed_controls = seed_controls; a.scales = lb.swp_scales.p;
-    a.offsets = lb.ens_J > 0 ? lb.swp_offsets.p : nullptr;
-    a.controls = lb.ens_items.p;
-    a.item_cost = lb.ens_cost.p; a.item_grads = lb.ens_grads.p;
-    a.cost = cost; a.grads = grads;
-    a.scale_sens = lb.swp_scale_sens.p; a.offset_sens = lb.swp_offset_sens.p;
-    a.B = lb.swp_B; a.nc = lb.nc; a.K = lb.K; a.Kr = lb.ens_Kr; a.J = lb.ens_J;
-    return a;
-}
-
-qocx::EnsembleArgs lindblad_ensemble_args(qocx_ctx* ctx, int seeds, const double* seed_controls, double* cost,
-                                          double* grads) {
-    auto& lb = ctx->lb;
-    qocx::EnsembleArgs a;
-    a.seed_controls = seed_controls; a.scales = lb.ens_scales.p;
-    a.offsets = lb.ens_J > 0 ? lb.ens_offsets.p : nullptr; a.weights = lb.ens_weights.p;
-    a.controls = lb.ens_items.p;
-    a.member_cost = lb.ens_cost.p; a.member_grads = lb.ens_grads.p;
-    a.cost = cost; a.grads = grads;
-    a.B = seeds; a.M = lb.ens_M; a.nc = lb.nc; a.K = lb.K; a.Kr = lb.ens_Kr; a.J = lb.ens_J;
-    return a;
+// the Lindblad buffers the kernels of qocx_ensemble.hip / qocx_sweep.hip run on: seed controls -> items
+// (expand), the items' results in item order -> the seeds' (reduce), and the channel sensitivities
+SeedBuffers lindblad_buffers(qocx_ctx::Lindblad& lb, const double* seed_controls, double* cost, double* grads) {
+    return {seed_controls, lb.ens_items.p, lb.ens_cost.p, lb.ens_grads.p, cost, grads};
 }
 
 // ---- duration search of a sweep (qocx_lindblad_sweep_set_durations, qocx_lindblad_duration.hip) -------
 
-// the kernels of qocx_duration.hip on the Lindblad sweep's buffers (the clip of tau and the tables)
-qocx::DurationArgs lindblad_duration_args(qocx_ctx* ctx) {
-    auto& lb = ctx->lb;
-    qocx::DurationArgs a;
-    a.tau = lb.dur_tau.p;
-    a.base_scales = lb.dur_base_scales.p;
-    a.base_offsets = lb.dur_base_offsets.p;
-    a.scales = lb.swp_scales.p;
-    a.offsets = lb.swp_offsets.p;
-    a.scale_sens = lb.swp_scale_sens.p; a.offset_sens = lb.swp_offset_sens.p;
-    a.tau_grad = nullptr;
-    a.cost = nullptr;
-    a.tau_min = lb.dur_tau_min; a.tau_max = lb.dur_tau_max; a.time_weight = lb.dur_weight;
-    a.B = lb.swp_B; a.Kr = lb.ens_Kr; a.J = lb.ens_J;
-    return a;
-}
-
 qocx::LindbladDurationArgs lindblad_generator_args(qocx_ctx* ctx) {
     auto& lb = ctx->lb;
     qocx::LindbladDurationArgs a;
-    a.tau = lb.dur_tau.p;
+    a.tau = lb.seeds.dur.tau.p;
     a.base_a0 = lb.dur_base_a0.p; a.a0 = lb.rate_a0.p;
     a.base_gammas = lb.dur_base_gammas.p; a.gammas = lb.rate_gammas.p;
-    a.base_scales = lb.dur_base_scales.p; a.base_offsets = lb.dur_base_offsets.p;
+    a.base_scales = lb.seeds.dur.base_scales.p; a.base_offsets = lb.seeds.dur.base_offsets.p;
     a.base_rates = lb.dur_base_rates.p;
-    a.scale_sens = lb.swp_scale_sens.p; a.offset_sens = lb.swp_offset_sens.p;
+    a.scale_sens = lb.seeds.scale_sens.p; a.offset_sens = lb.seeds.offset_sens.p;
     a.rate_sens = lb.swp_rate_sens.p;
     a.order = lb.order_dev.p;
     a.tau_grad = nullptr;
     a.cost = nullptr;
-    a.time_weight = lb.dur_weight;
+    a.time_weight = lb.seeds.dur.weight;
     a.a0_per_seed = 4 * (size_t)dump_elems(lb.n);
-    a.B = lb.swp_B; a.Kr = lb.ens_Kr; a.J = lb.ens_J; a.L = lb.nops; a.Lp = (int)lb.gammas_h.size();
+    a.B = lb.seeds.swp_B; a.Kr = lb.seeds.Kr; a.J = lb.seeds.J; a.L = lb.nops; a.Lp = (int)lb.gammas_h.size();
     return a;
 }
 
@@ -1252,7 +1167,7 @@ qocx::LindbladDurationArgs lindblad_generator_args(qocx_ctx* ctx) {
 // written (a step without the clip behind it), they are rewritten and the host mirrors re-formed
 int lindblad_duration_refresh(qocx_ctx* ctx) {
     auto& lb = ctx->lb;
-    if (!lb.dur_set || !lb.dur_mirror_stale) return 0;
+    if (!lb.seeds.dur.set || !lb.seeds.dur.mirror_stale) return 0;
     lindblad_duration_tables(ctx);
     HIP_TRY(hipGetLastError());
     if (int rc = lindblad_duration_fetch(ctx)) return rc;
@@ -1267,8 +1182,8 @@ int lindblad_duration_refresh(qocx_ctx* ctx) {
 // sensitivities did not come about fails by name: it must not return a gradient without its rate part.
 int lindblad_duration_finish(qocx_ctx* ctx, int want_grad, double* cost) {
     auto& lb = ctx->lb;
-    if (!lb.dur_set) return 0;
-    lb.dur_have_grad = false;
+    if (!lb.seeds.dur.set) return 0;
+    lb.seeds.dur.have_grad = false;
     if (want_grad && !lb.swp_rates_ok) {
         lb.have_results = lb.res_have_results = lb.swp_have_grads = false;
         return fail(QOCX_ERR_STATE,
@@ -1277,17 +1192,18 @@ int lindblad_duration_finish(qocx_ctx* ctx, int want_grad, double* cost) {
                     "cost, a final target-density infidelity, 1 .. 4 operators, the two-sided kernels and stage "
                     "values that fit the device memory");
     }
-    const size_t ns = (size_t)lb.swp_B * lb.ens_Kr, no = (size_t)lb.swp_B * lb.ens_J;
-    if (lb.dur_grad.ensure((size_t)lb.swp_B) || lb.swp_scale_sens.ensure(ns) || lb.swp_offset_sens.ensure(no))
+    const size_t ns = (size_t)lb.seeds.swp_B * lb.seeds.Kr, no = (size_t)lb.seeds.swp_B * lb.seeds.J;
+    if (lb.seeds.dur.grad.ensure((size_t)lb.seeds.swp_B) || lb.seeds.scale_sens.ensure(ns) ||
+        lb.seeds.offset_sens.ensure(no))
         return QOCX_ERR_HIP;
-    if (want_grad)
-        qocx::launch_sweep_sensitivity(lindblad_sweep_args(ctx, lb.swp_seed_controls, nullptr, nullptr), ctx->stream);
+    const SeedBuffers buf = lindblad_buffers(lb, lb.swp_seed_controls, nullptr, nullptr);
+    if (want_grad) qocx::launch_sweep_sensitivity(sweep_args(lb.seeds, lb.nc, buf), ctx->stream);
     qocx::LindbladDurationArgs a = lindblad_generator_args(ctx);
-    a.tau_grad = want_grad ? lb.dur_grad.p : nullptr;
+    a.tau_grad = want_grad ? lb.seeds.dur.grad.p : nullptr;
     a.cost = cost;
     qocx::launch_lindblad_duration_gradient(a, ctx->stream);
     HIP_TRY(hipGetLastError());
-    lb.dur_have_grad = want_grad != 0;
+    lb.seeds.dur.have_grad = want_grad != 0;
     return 0;
 }
 
@@ -1298,18 +1214,19 @@ int lindblad_duration_finish(qocx_ctx* ctx, int want_grad, double* cost) {
 int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_controls, const double* umax,
                              int want_grad) {
     auto& lb = ctx->lb;
-    if ((int64_t)seeds * lb.ens_M > 0x7fffffff)
+    if ((int64_t)seeds * lb.seeds.M > 0x7fffffff)
         return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
-    const int items = seeds * lb.ens_M;
+    const int items = seeds * lb.seeds.M;
     const size_t csz = (size_t)lb.nc * lb.K, total = (size_t)items * csz;
     if ((total + 255) / 256 > 0x7fffffffu) return fail(QOCX_ERR_ARG, "ensemble control arrays too large");
     if (csz > 65535u * 256u) return fail(QOCX_ERR_ARG, "control arrays too large for the driver kernels' grids");
     if (lb.ens_items.ensure(total)) return QOCX_ERR_HIP;
-    const bool swp = lb.swp_B > 0;
-    if (swp && seeds != lb.swp_B)
+    const bool swp = lb.seeds.swp_B > 0;
+    if (swp && seeds != lb.seeds.swp_B)
         return fail(QOCX_ERR_ARG, "a sweep takes exactly its own seed count as the batch (qocx_lindblad_set_sweep)");
-    if (swp) qocx::launch_sweep_expand(lindblad_sweep_args(ctx, seed_controls, nullptr, nullptr), ctx->stream);
-    else qocx::launch_ensemble_expand(lindblad_ensemble_args(ctx, seeds, seed_controls, nullptr, nullptr), ctx->stream);
+    const SeedBuffers buf = lindblad_buffers(lb, seed_controls, nullptr, nullptr);
+    if (swp) qocx::launch_sweep_expand(sweep_args(lb.seeds, lb.nc, buf), ctx->stream);
+    else qocx::launch_ensemble_expand(ensemble_args(lb.seeds, seeds, lb.nc, buf), ctx->stream);
     HIP_TRY(hipGetLastError());
     lb.swp_seed_controls = swp ? seed_controls : nullptr;
     lb.swp_have_grads = false;
@@ -1324,7 +1241,7 @@ int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_contro
         // behind the order: the member of every launched item, in launch order (LindbladMembers::item_member)
         std::vector<int> both(lb.order);
         // (a sweep: the launched seed's own index)
-        for (int i = 0; i < items; ++i) both.push_back(swp ? lb.order[i] : lb.order[i] % lb.ens_M);
+        for (int i = 0; i < items; ++i) both.push_back(swp ? lb.order[i] : lb.order[i] % lb.seeds.M);
         if (lb.order_dev.upload(both, ctx->stream)) return QOCX_ERR_HIP;
     } else if (lb.order_dev.upload(lb.order, ctx->stream)) {
         return QOCX_ERR_HIP;
@@ -1340,17 +1257,15 @@ int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_contro
 int lindblad_ensemble_reduce(qocx_ctx* ctx, int seeds, int want_grad, double* cost, double* grads,
                              double2* final_items) {
     auto& lb = ctx->lb;
-    const int items = seeds * lb.ens_M;
+    const int items = seeds * lb.seeds.M;
     const size_t csz = (size_t)lb.nc * lb.K, md = dump_elems(lb.n);
     if (lb.ens_cost.ensure(items) || (want_grad && lb.ens_grads.ensure((size_t)items * csz))) return QOCX_ERR_HIP;
     qocx::launch_scatter_seeds(lb.cost_out.p, lb.ens_cost.p, want_grad ? lb.grads.p : nullptr, lb.ens_grads.p,
                                csz, lb.final_out.p, final_items, (size_t)lb.S * md, lb.order_dev.p, items,
                                ctx->stream);
-    if (lb.swp_B > 0)
-        qocx::launch_sweep_reduce(lindblad_sweep_args(ctx, nullptr, cost, want_grad ? grads : nullptr), ctx->stream);
-    else
-        qocx::launch_ensemble_reduce(lindblad_ensemble_args(ctx, seeds, nullptr, cost, want_grad ? grads : nullptr),
-                                     ctx->stream);
+    const SeedBuffers buf = lindblad_buffers(lb, nullptr, cost, want_grad ? grads : nullptr);
+    if (lb.seeds.sweep()) qocx::launch_sweep_reduce(sweep_args(lb.seeds, lb.nc, buf), ctx->stream);
+    else qocx::launch_ensemble_reduce(ensemble_args(lb.seeds, seeds, lb.nc, buf), ctx->stream);
     HIP_TRY(hipGetLastError());
     lb.ens_members_B = seeds;
     return 0;
@@ -1361,7 +1276,7 @@ int lindblad_ensemble_reduce(qocx_ctx* ctx, int seeds, int want_grad, double* co
 int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int want_grad, double* cost_out,
                            double* grad_out, double* final_out) {
     auto& lb = ctx->lb;
-    const int n = lb.n, S = lb.S, Kr = lb.ens_Kr, nc = lb.nc, M = lb.ens_M;
+    const int n = lb.n, S = lb.S, Kr = lb.seeds.Kr, nc = lb.nc, M = lb.seeds.M;
     const size_t csz = (size_t)nc * Kr, md = dump_elems(n);
     if (!controls) return fail(QOCX_ERR_ARG, "controls is NULL");
     if ((int64_t)B * M > 0x7fffffff) return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
@@ -1406,35 +1321,35 @@ int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int wan
 namespace qocx::host {
 
 void lindblad_duration_tables(qocx_ctx* ctx) {
-    qocx::launch_duration_tables(lindblad_duration_args(ctx), ctx->stream);
+    qocx::launch_duration_tables(duration_args(ctx->lb.seeds, nullptr, nullptr), ctx->stream);
     qocx::launch_lindblad_duration_generators(lindblad_generator_args(ctx), ctx->stream);
 }
 
 int lindblad_duration_fetch(qocx_ctx* ctx) {
     auto& lb = ctx->lb;
-    lb.dur_tau_h.resize((size_t)lb.swp_B);
-    HIP_TRY(hipMemcpyAsync(lb.dur_tau_h.data(), lb.dur_tau.p, (size_t)lb.swp_B * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream));
+    lb.dur_tau_h.resize((size_t)lb.seeds.swp_B);
+    HIP_TRY(hipMemcpyAsync(lb.dur_tau_h.data(), lb.seeds.dur.tau.p, (size_t)lb.seeds.swp_B * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx->stream));
     return 0;
 }
 
-// swp_scales_h, swp_offsets_h and rate_l0_norm as the device holds the tables: the same single products
+// seeds.scales_h, seeds.offsets_h and rate_l0_norm as the device holds the tables: the same single products
 // of the clipped tau (a product alone is rounded once on either side)
 void lindblad_duration_mirror(qocx_ctx* ctx) {
     auto& lb = ctx->lb;
-    const int B = lb.swp_B, Kr = lb.ens_Kr, J = lb.ens_J;
-    lb.swp_scales_h.resize((size_t)B * Kr);
-    lb.swp_offsets_h.resize((size_t)B * J);
+    const int B = lb.seeds.swp_B, Kr = lb.seeds.Kr, J = lb.seeds.J;
+    lb.seeds.scales_h.resize((size_t)B * Kr);
+    lb.seeds.offsets_h.resize((size_t)B * J);
     lb.rate_l0_norm.resize((size_t)B);
     for (int b = 0; b < B; ++b) {
         const double tau = lb.dur_tau_h[b];
         for (int k = 0; k < Kr; ++k)
-            lb.swp_scales_h[(size_t)b * Kr + k] = tau * lb.dur_base_scales_h[(size_t)b * Kr + k];
+            lb.seeds.scales_h[(size_t)b * Kr + k] = tau * lb.dur_base_scales_h[(size_t)b * Kr + k];
         for (int j = 0; j < J; ++j)
-            lb.swp_offsets_h[(size_t)b * J + j] = tau * lb.dur_base_offsets_h[(size_t)b * J + j];
+            lb.seeds.offsets_h[(size_t)b * J + j] = tau * lb.dur_base_offsets_h[(size_t)b * J + j];
         lb.rate_l0_norm[b] = tau * lb.dur_l0_norm0[b];
     }
-    lb.dur_mirror_stale = false;
+    lb.seeds.dur.mirror_stale = false;
 }
 
 }  // namespace qocx::host
@@ -1445,7 +1360,7 @@ int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const do
                                       double tau_max, double time_weight) {
     if (!ctx || !tau) return fail(QOCX_ERR_ARG, "NULL argument");
     auto& lb = ctx->lb;
-    if (!lb.has_problem || lb.swp_B == 0)
+    if (!lb.has_problem || lb.seeds.swp_B == 0)
         return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep before qocx_lindblad_sweep_set_durations)");
     if (lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "a duration search needs a static problem: this one was set with stage tables "
@@ -1458,35 +1373,27 @@ int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const do
             return fail(QOCX_ERR_STATE, "a duration search needs a problem whose own h0 is zero (the drift is the "
                                         "first fixed channel): the control-free part is then the dissipator alone "
                                         "and scales with tau as a whole");
-    const int B = lb.swp_B, Kr = lb.ens_Kr, J = lb.ens_J, L = lb.nops;
-    if (J < 1 || !base_offsets)
-        return fail(QOCX_ERR_ARG, "a duration search needs the drift as the first fixed channel (base_offsets [B][J], J >= 1)");
+    const int B = lb.seeds.swp_B, L = lb.nops;
     if (L < 1 || L > 4)
         return fail(QOCX_ERR_ARG, "a duration search takes 1 .. 4 Lindblad operators (the rate sensitivities exist for those)");
-    if (!std::isfinite(tau_min) || !std::isfinite(tau_max) || !(tau_min > 0) || !(tau_min <= tau_max))
-        return fail(QOCX_ERR_ARG, "the duration box needs finite 0 < tau_min <= tau_max");
-    if (!std::isfinite(time_weight) || time_weight < 0)
-        return fail(QOCX_ERR_ARG, "time_weight must be finite and >= 0");
-    std::vector<double> t(tau, tau + B), s0((size_t)B * Kr, 1.0), d0(base_offsets, base_offsets + (size_t)B * J);
     std::vector<double> c0((size_t)B * L, 1.0);
-    if (base_scales) s0.assign(base_scales, base_scales + s0.size());
     if (base_rate_scales) c0.assign(base_rate_scales, base_rate_scales + c0.size());
-    for (double v : t)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite duration");
-    for (double v : s0)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base control scale");
-    for (double v : d0)
-        if (!std::isfinite(v)) return fail(QOCX_ERR_ARG, "non-finite base offset");
     for (double v : c0)
         if (!std::isfinite(v) || !(v >= 0)) return fail(QOCX_ERR_ARG, "base_rate_scales must be finite and >= 0");
     HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<double> s0, d0;
+    if (int rc = set_seed_durations(lb.seeds, tau, base_scales, base_offsets, tau_min, tau_max, time_weight, ctx->stream,
+                                    s0, d0))
+        return rc;
+    lb.dur_base_scales_h.swap(s0);
+    lb.dur_base_offsets_h.swap(d0);
     // the base tables, once: every seed's control-free generators, rates and norm bound at tau = 1, built
     // as the plain setter builds its own (a later call of the same search with the same c0 - the host loop
     // sets tau every iteration - keeps them)
-    if (!lb.dur_set || lb.dur_base_rates_h != c0) {
+    if (!lb.seeds.dur.set || lb.dur_base_rates_h != c0) {
         std::vector<double2> img;
         std::vector<double> gam;
-        lb.dur_set = false;
+        lb.seeds.dur.set = false;
         rate_tables_host(lb, B, c0.data(), img, gam, lb.dur_l0_norm0);
         if (lb.dur_base_a0.upload(img, ctx->stream) || lb.dur_base_gammas.upload(gam, ctx->stream) ||
             lb.rate_a0.ensure(img.size()) || lb.rate_gammas.ensure(gam.size()) ||
@@ -1494,20 +1401,13 @@ int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const do
             return QOCX_ERR_HIP;
         lb.dur_base_rates_h = c0;
     }
-    if (lb.dur_tau.upload(t, ctx->stream) || lb.dur_base_scales.upload(s0, ctx->stream) ||
-        lb.dur_base_offsets.upload(d0, ctx->stream) || lb.swp_scales.ensure(s0.size()) ||
-        lb.swp_offsets.ensure(d0.size()))
-        return QOCX_ERR_HIP;
-    lb.dur_base_scales_h = s0;
-    lb.dur_base_offsets_h = d0;
-    lb.dur_tau_min = tau_min; lb.dur_tau_max = tau_max; lb.dur_weight = time_weight;
     lindblad_duration_tables(ctx);
     HIP_TRY(hipGetLastError());
     if (int rc = lindblad_duration_fetch(ctx)) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     lindblad_duration_mirror(ctx);
-    lb.dur_set = true;
-    lb.dur_have_grad = false;
+    lb.seeds.dur.set = true;
+    lb.seeds.dur.have_grad = false;
     lb.have_results = false;
     lb.swp_have_grads = false;
     lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again, and the driver begun again
@@ -1518,16 +1418,10 @@ int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const do
 int qocx_lindblad_sweep_download_durations(qocx_ctx* ctx, double* tau_out, double* tau_grad_out) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
-    if (!lb.dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_lindblad_sweep_set_durations)");
-    if (tau_grad_out && (!lb.have_results || !lb.swp_have_grads || !lb.dur_have_grad))
-        return fail(QOCX_ERR_STATE, "duration gradients need an evaluation with gradients");
+    if (!lb.seeds.dur.set) return fail(QOCX_ERR_STATE, "no durations set (qocx_lindblad_sweep_set_durations)");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)lb.swp_B * sizeof(double);
-    if (tau_out) HIP_TRY(hipMemcpyAsync(tau_out, lb.dur_tau.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (tau_grad_out)
-        HIP_TRY(hipMemcpyAsync(tau_grad_out, lb.dur_grad.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return download_seed_durations(lb.seeds, ctx->stream, lb.have_results && lb.swp_have_grads && lb.seeds.dur.have_grad,
+                                   tau_out, tau_grad_out);
 }
 
 int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int32_t want_grad,
@@ -1540,7 +1434,7 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
     const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, B = batch;
     const size_t md = dump_elems(n);
     want_grad = (want_grad && K > 0) ? 1 : 0;
-    if (lb.ens_M > 0) return eval_lindblad_ensemble(ctx, B, controls, want_grad, cost_out, grad_out, final_out);
+    if (lb.seeds.M > 0) return eval_lindblad_ensemble(ctx, B, controls, want_grad, cost_out, grad_out, final_out);
     if (K > 0 && !controls) return fail(QOCX_ERR_ARG, "controls is NULL");
     const bool trace_host = qocx::diag_getenv("QOCX_TRACE_HOST") != nullptr;
     auto now_ms = [] {
@@ -1615,8 +1509,8 @@ int qocx_set_density_cotangents(qocx_ctx* ctx, int32_t batch, int32_t count, con
         return 0;
     }
     if (batch < 1 || !steps || !bars) return fail(QOCX_ERR_ARG, "bad argument");
-    if (lb.ens_M > 0)
-        return fail(QOCX_ERR_STATE, lb.swp_B > 0
+    if (lb.seeds.M > 0)
+        return fail(QOCX_ERR_STATE, lb.seeds.swp_B > 0
                                         ? "density cotangents are not taken with a sweep (qocx_lindblad_set_sweep)"
                                         : "density cotangents are not taken with an ensemble (qocx_lindblad_set_ensemble)");
     std::vector<bool> seen(lb.nsteps + 1, false);
@@ -1658,7 +1552,7 @@ int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* co
     if (!lb.has_problem || lb.K < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_upload_controls needs a Lindblad problem with controls");
     if (batch < 1) return fail(QOCX_ERR_ARG, "batch must be >= 1");
-    if (lb.swp_B > 0 && batch != lb.swp_B)
+    if (lb.seeds.swp_B > 0 && batch != lb.seeds.swp_B)
         return fail(QOCX_ERR_ARG, "a sweep takes exactly its own seed count as the batch (qocx_lindblad_set_sweep)");
     // (with an ensemble the caller's array holds the seeds' K_r channels)
     const int Ks = lb.seed_channels();
@@ -1690,11 +1584,11 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
     // (K: the seeds' channels - with an ensemble K_r, and `items` evaluated items per seed)
     const int B = lb.res_B, K = lb.seed_channels(), S = lb.S;
     const size_t csz = (size_t)lb.nc * K, md = dump_elems(lb.n), items = lb.seed_items();
-    const bool ens = lb.ens_M > 0;
+    const bool ens = lb.seeds.M > 0;
     want_grad = want_grad ? 1 : 0;
     lb.res_have_results = false;
     // (a duration search whose tau has moved since the clip: tau comes back with the maxima below)
-    const bool refresh = lb.dur_set && lb.dur_mirror_stale;
+    const bool refresh = lb.seeds.dur.set && lb.seeds.dur.mirror_stale;
     if (refresh) {
         lindblad_duration_tables(ctx);
         HIP_TRY(hipGetLastError());
@@ -1794,10 +1688,10 @@ int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out) {
 int qocx_lindblad_ensemble_download_members(qocx_ctx* ctx, double* cost_out) {
     if (!ctx || !cost_out) return fail(QOCX_ERR_ARG, "NULL argument");
     auto& lb = ctx->lb;
-    if (lb.ens_M == 0 || lb.swp_B > 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_lindblad_set_ensemble)");
+    if (lb.seeds.M == 0 || lb.seeds.swp_B > 0) return fail(QOCX_ERR_STATE, "no ensemble set (qocx_lindblad_set_ensemble)");
     if (lb.ens_members_B < 1 || !lb.have_results) return fail(QOCX_ERR_STATE, "no evaluation results");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(cost_out, lb.ens_cost.p, (size_t)lb.ens_members_B * lb.ens_M * sizeof(double),
+    HIP_TRY(hipMemcpyAsync(cost_out, lb.ens_cost.p, (size_t)lb.ens_members_B * lb.seeds.M * sizeof(double),
                            hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -1807,7 +1701,7 @@ int qocx_lindblad_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out
                                                double* rates_out) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     auto& lb = ctx->lb;
-    if (lb.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
+    if (lb.seeds.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
     // (the seed controls on the device are those of the evaluation exactly while its results stand: the
     // resident ones move with qocx_lindblad_opt_clip / _step, which clear res_have_results)
     const bool resident = lb.swp_seed_controls != nullptr && lb.swp_seed_controls == lb.res_controls.p;
@@ -1819,17 +1713,18 @@ int qocx_lindblad_sweep_download_sensitivities(qocx_ctx* ctx, double* scales_out
                                     "(qocx_lindblad_sweep_want_rate_sensitivities), or a piece of it did not run "
                                     "two-sided with 1 .. 4 operators");
     HIP_TRY(hipSetDevice(ctx->device));
-    const int B = lb.swp_B, L = lb.nops;
-    const size_t ns = (size_t)B * lb.ens_Kr, no = (size_t)B * lb.ens_J;
-    if (lb.swp_scale_sens.ensure(ns) || lb.swp_offset_sens.ensure(no)) return QOCX_ERR_HIP;
+    const int B = lb.seeds.swp_B, L = lb.nops;
+    const size_t ns = (size_t)B * lb.seeds.Kr, no = (size_t)B * lb.seeds.J;
+    if (lb.seeds.scale_sens.ensure(ns) || lb.seeds.offset_sens.ensure(no)) return QOCX_ERR_HIP;
     // (the items' gradients in item order are the reduce launch's input, ens_grads)
-    qocx::launch_sweep_sensitivity(lindblad_sweep_args(ctx, lb.swp_seed_controls, nullptr, nullptr), ctx->stream);
+    const SeedBuffers buf = lindblad_buffers(lb, lb.swp_seed_controls, nullptr, nullptr);
+    qocx::launch_sweep_sensitivity(sweep_args(lb.seeds, lb.nc, buf), ctx->stream);
     HIP_TRY(hipGetLastError());
     if (scales_out)
-        HIP_TRY(hipMemcpyAsync(scales_out, lb.swp_scale_sens.p, ns * sizeof(double), hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(scales_out, lb.seeds.scale_sens.p, ns * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
     if (offsets_out && no > 0)
-        HIP_TRY(hipMemcpyAsync(offsets_out, lb.swp_offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(offsets_out, lb.seeds.offset_sens.p, no * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
     std::vector<double> launched(rates_out ? (size_t)B * L : 0);
     if (rates_out)

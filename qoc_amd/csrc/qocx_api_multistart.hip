@@ -118,7 +118,7 @@ struct SeedView {
 
 // (ensemble: a seed's K_r channels, and the final states of its M items)
 SeedView schroedinger_seeds(qocx_ctx* ctx) {
-    const size_t items = ctx->ens_M > 0 ? (size_t)ctx->ens_M : 1;
+    const size_t items = ctx->seeds.M > 0 ? (size_t)ctx->seeds.M : 1;
     return SeedView{seed_count(ctx), seed_channels(ctx), ctx->nc, seed_controls(ctx), seed_grads(ctx),
                     seed_costs(ctx), ctx->final_out.p, items * ctx->S * ctx->np};
 }
@@ -395,6 +395,36 @@ int multistart_download_best_params(qocx_ctx* ctx, MultiStart& ms, const SeedVie
     return 0;
 }
 
+// a duration search: the optimizer state of the seeds' tau - moments and best, zeroed
+int durations_begin(qocx_ctx* ctx, SeedTables::Durations& dur, size_t B, MultiStart& ms) {
+    if (!dur.set) return 0;
+    if (dur.m.ensure(B) || dur.v.ensure(B) || dur.best.ensure(B)) {
+        ms.batch = 0;
+        return QOCX_ERR_HIP;
+    }
+    for (DevBuf<double>* buf : {&dur.m, &dur.v, &dur.best})
+        HIP_TRY(hipMemsetAsync(buf->p, 0, B * sizeof(double), ctx->stream));
+    return 0;
+}
+
+// ... its part of an optimizer step: tau, its gradient (which must stand), the moments and the best
+int durations_rule(SeedTables::Durations& dur, qocx::DurationStepArgs& step) {
+    if (!dur.have_grad) return fail(QOCX_ERR_STATE, "no duration gradients to step with");
+    step.rule.params = dur.tau.p; step.rule.grads = dur.grad.p;
+    step.rule.moment = dur.m.p; step.rule.square_moment = dur.v.p;
+    step.best_tau = dur.best.p;
+    return 0;
+}
+
+// ... and the tau of the best so far [B]; `set_by`: the path's setter, for the message
+int durations_download_best(qocx_ctx* ctx, SeedTables::Durations& dur, size_t B, const char* set_by, double* tau_out) {
+    if (!dur.set) return fail(QOCX_ERR_STATE, std::string("no durations set (") + set_by + ")");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(tau_out, dur.best.p, B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 int schroedinger_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& basis = BasisStart()) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (!ctx->has_problem || ctx->B < 1 || ctx->K < 1 || ctx->explicit_mode)
@@ -402,16 +432,7 @@ int schroedinger_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStar
     HIP_TRY(hipSetDevice(ctx->device));
     // (the seeds' optimizer states; the best final states of every item)
     if (int rc = multistart_begin(ctx, ctx->ms, schroedinger_seeds(ctx), ctx->B, complex_controls, basis)) return rc;
-    if (!ctx->dur_set) return 0;
-    // a duration search: the optimizer state of the seeds' tau - moments and best, zeroed
-    const size_t B = (size_t)ctx->swp_B;
-    if (ctx->dur_m.ensure(B) || ctx->dur_v.ensure(B) || ctx->dur_best.ensure(B)) {
-        ctx->ms.batch = 0;
-        return QOCX_ERR_HIP;
-    }
-    for (DevBuf<double>* buf : {&ctx->dur_m, &ctx->dur_v, &ctx->dur_best})
-        HIP_TRY(hipMemsetAsync(buf->p, 0, B * sizeof(double), ctx->stream));
-    return 0;
+    return durations_begin(ctx, ctx->seeds.dur, (size_t)ctx->seeds.swp_B, ctx->ms);
 }
 
 int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& basis = BasisStart()) {
@@ -421,16 +442,7 @@ int lindblad_opt_begin(qocx_ctx* ctx, bool complex_controls, const BasisStart& b
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin needs resident Lindblad controls");
     HIP_TRY(hipSetDevice(ctx->device));
     if (int rc = multistart_begin(ctx, lb.ms, lindblad_seeds(ctx), lb.res_B, complex_controls, basis)) return rc;
-    if (!lb.dur_set) return 0;
-    // a duration search: the optimizer state of the seeds' tau - moments and best, zeroed
-    const size_t B = (size_t)lb.swp_B;
-    if (lb.dur_m.ensure(B) || lb.dur_v.ensure(B) || lb.dur_best.ensure(B)) {
-        lb.ms.batch = 0;
-        return QOCX_ERR_HIP;
-    }
-    for (DevBuf<double>* buf : {&lb.dur_m, &lb.dur_v, &lb.dur_best})
-        HIP_TRY(hipMemsetAsync(buf->p, 0, B * sizeof(double), ctx->stream));
-    return 0;
+    return durations_begin(ctx, lb.seeds.dur, (size_t)lb.seeds.swp_B, lb.ms);
 }
 
 // the arguments of *_opt_begin_basis, checked
@@ -474,7 +486,7 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     // after the clip |u_k| <= max_norms[k]: the squaring capacity follows from that bound
     // (ensemble: |s_mk u_k| <= max_norms[k] max_m |s_mk| on the K_r seed channels, |delta_mj| beyond;
     // a sweep keeps max_b |s_bk| and max_b |delta_bj| in the same two vectors)
-    const bool ens = ctx->ens_M > 0;
+    const bool ens = ctx->seeds.M > 0;
     const SeedView v = schroedinger_seeds(ctx);
     const int Ks = v.channels;
     // (complex controls: max_norms [Ks / 2] bound the moduli, hence both channels of a control)
@@ -485,7 +497,7 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
         if (!(channel_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
         bound += (ens ? channel_norms[k] * ctx->ens_scale_max[k] : channel_norms[k]) * ctx->g_norm_max[k];
     }
-    for (int j = 0; ens && j < ctx->ens_J; ++j) bound += ctx->ens_offset_max[j] * ctx->g_norm_max[Ks + j];
+    for (int j = 0; ens && j < ctx->seeds.J; ++j) bound += ctx->ens_offset_max[j] * ctx->g_norm_max[Ks + j];
     // (quadratic terms: ||Q_q||_1 max_norms_k max_norms_l, with an ensemble times its members' largest
     // scales as in qocx_upload_controls)
     bound += quad_bound(ctx, channel_norms.data());
@@ -496,12 +508,12 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     // no check of the first: to be revisited)
     if ((v.total() + 255) / 256 > 0x7fffffffu || v.per_seed() > 65535u * 256u)
         return fail(QOCX_ERR_ARG, "control arrays too large for the optimizer kernels' grids");
-    if (ctx->dur_set) {
+    if (ctx->seeds.dur.set) {
         // a duration search: tau clipped in place to its box and the sweep's tables rewritten from it,
         // before the next evaluation expands the seeds (ens_scale_max / ens_offset_max above are those
         // of tau_max: the bound holds wherever the step has taken tau)
-        qocx::launch_duration_tables(duration_args(ctx), ctx->stream);
-        ctx->dur_mirror_stale = true;
+        qocx::launch_duration_tables(duration_args(ctx->seeds, nullptr, nullptr), ctx->stream);
+        ctx->seeds.dur.mirror_stale = true;
     }
     if (int rc = multistart_clip(ctx, ctx->ms, v, max_norms)) return rc;
     HIP_TRY(hipGetLastError());
@@ -521,25 +533,21 @@ int qocx_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved, const ui
     HIP_TRY(hipSetDevice(ctx->device));
     const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
     qocx::DurationStepArgs durations;
-    if (ctx->dur_set) {
-        if (!ctx->dur_have_grad) return fail(QOCX_ERR_STATE, "no duration gradients to step with");
-        durations.rule.params = ctx->dur_tau.p; durations.rule.grads = ctx->dur_grad.p;
-        durations.rule.moment = ctx->dur_m.p; durations.rule.square_moment = ctx->dur_v.p;
-        durations.best_tau = ctx->dur_best.p;
-    }
+    if (ctx->seeds.dur.set)
+        if (int rc = durations_rule(ctx->seeds.dur, durations)) return rc;
     if (int rc = multistart_step(ctx, ctx->ms, schroedinger_seeds(ctx), rule, improved, update,
-                                 ctx->dur_set ? &durations : nullptr))
+                                 ctx->seeds.dur.set ? &durations : nullptr))
         return rc;
-    ctx->dur_have_grad = false;
+    ctx->seeds.dur.have_grad = false;
     ctx->have_results = false;  // the resident controls are no longer those of the last evaluation
-    ctx->ens_stale = ctx->ens_M > 0;
+    ctx->ens_stale = ctx->seeds.M > 0;
     return 0;
 }
 
 int qocx_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
-    if (ctx->dur_set)
+    if (ctx->seeds.dur.set)
         return fail(QOCX_ERR_STATE, "a duration search (qocx_sweep_set_durations) steps with Adam or SGD: the "
                                     "resident L-BFGS vectors do not hold tau");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -557,7 +565,7 @@ int qocx_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const uint8_t* u
     if (int rc = multistart_lbfgs_step(ctx, ctx->ms, schroedinger_seeds(ctx), rule, improved, update, finished_out))
         return rc;
     ctx->have_results = false;  // the resident controls are no longer those of the last evaluation
-    ctx->ens_stale = ctx->ens_M > 0;
+    ctx->ens_stale = ctx->seeds.M > 0;
     return 0;
 }
 
@@ -582,12 +590,7 @@ int qocx_opt_download_best(qocx_ctx* ctx, double* controls_out, double* final_ou
 int qocx_opt_download_best_durations(qocx_ctx* ctx, double* tau_out) {
     if (!ctx || !tau_out) return fail(QOCX_ERR_ARG, "NULL argument");
     if (ctx->ms.batch != ctx->B || ctx->B < 1) return fail(QOCX_ERR_STATE, "qocx_opt_begin has not run for this batch");
-    if (!ctx->dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_sweep_set_durations)");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(tau_out, ctx->dur_best.p, (size_t)ctx->swp_B * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return durations_download_best(ctx, ctx->seeds.dur, (size_t)ctx->seeds.swp_B, "qocx_sweep_set_durations", tau_out);
 }
 
 // ---- the Lindblad path: the seeds of qocx_lindblad_upload_controls ----------------------------------
@@ -623,12 +626,12 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     for (int k = 0; k < Kn; ++k)
         if (!(max_norms[k] >= 0)) return fail(QOCX_ERR_ARG, "max_norms must be non-negative");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (lb.dur_set) {
+    if (lb.seeds.dur.set) {
         // a duration search: tau clipped in place to its box, the sweep's tables and the seeds' generator
         // tables rewritten from it before the next evaluation expands the seeds; tau comes back to the
         // host in the synchronisation below, for the mirrors the sub-division decision reads
         lindblad_duration_tables(ctx);
-        lb.dur_mirror_stale = true;
+        lb.seeds.dur.mirror_stale = true;
         if (int rc = lindblad_duration_fetch(ctx)) return rc;
     }
     if (int rc = multistart_clip(ctx, lb.ms, lindblad_seeds(ctx), max_norms)) return rc;
@@ -646,7 +649,7 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
     lb.umax_valid = maxima;
     lb.res_have_results = false;
-    if (lb.dur_set) lindblad_duration_mirror(ctx);
+    if (lb.seeds.dur.set) lindblad_duration_mirror(ctx);
     return 0;
 }
 
@@ -662,17 +665,14 @@ int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
     HIP_TRY(hipSetDevice(ctx->device));
     const StepRule rule{kind, learning_rate, beta_1, beta_2, epsilon, corr_1, corr_2, apply_clip_grads, clip_grads};
     qocx::DurationStepArgs durations;
-    if (lb.dur_set) {
-        if (!lb.dur_have_grad) return fail(QOCX_ERR_STATE, "no duration gradients to step with");
-        durations.rule.params = lb.dur_tau.p; durations.rule.grads = lb.dur_grad.p;
-        durations.rule.moment = lb.dur_m.p; durations.rule.square_moment = lb.dur_v.p;
-        durations.best_tau = lb.dur_best.p;
-    }
+    if (lb.seeds.dur.set)
+        if (int rc = durations_rule(lb.seeds.dur, durations)) return rc;
     if (int rc = multistart_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update,
-                                 lb.dur_set ? &durations : nullptr))
+                                 lb.seeds.dur.set ? &durations : nullptr))
         return rc;
-    lb.dur_have_grad = false;
-    lb.dur_mirror_stale = lb.dur_set;  // (tau has moved: the tables are rewritten by the clip, or before the next evaluation)
+    lb.seeds.dur.have_grad = false;
+    // (tau has moved: the tables are rewritten by the clip, or before the next evaluation)
+    lb.seeds.dur.mirror_stale = lb.seeds.dur.set;
     lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
     lb.umax_valid = false;
     return 0;
@@ -683,7 +683,7 @@ int qocx_lindblad_opt_lbfgs_begin(qocx_ctx* ctx, int32_t history) {
     auto& lb = ctx->lb;
     if (lb.ms.batch != lb.res_B || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
-    if (lb.dur_set)
+    if (lb.seeds.dur.set)
         return fail(QOCX_ERR_STATE, "a duration search (qocx_lindblad_sweep_set_durations) steps with Adam or SGD: "
                                     "the resident L-BFGS vectors do not hold tau");
     HIP_TRY(hipSetDevice(ctx->device));
@@ -731,12 +731,7 @@ int qocx_lindblad_opt_download_best_durations(qocx_ctx* ctx, double* tau_out) {
     auto& lb = ctx->lb;
     if (lb.ms.batch != lb.res_B || lb.res_B < 1)
         return fail(QOCX_ERR_STATE, "qocx_lindblad_opt_begin has not run for this batch");
-    if (!lb.dur_set) return fail(QOCX_ERR_STATE, "no durations set (qocx_lindblad_sweep_set_durations)");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(tau_out, lb.dur_best.p, (size_t)lb.swp_B * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
+    return durations_download_best(ctx, lb.seeds.dur, (size_t)lb.seeds.swp_B, "qocx_lindblad_sweep_set_durations", tau_out);
 }
 
 // ---- costs of the controls alone; complex controls in the resident drivers -------------------------
@@ -744,7 +739,7 @@ int qocx_lindblad_opt_download_best_durations(qocx_ctx* ctx, double* tau_out) {
 static ControlCosts* control_costs_of(qocx_ctx* ctx, int32_t path, int& nc, int& Kr) {
     if (path == QOCX_PATH_SCHROEDINGER && ctx->has_problem) {
         nc = ctx->nc;
-        Kr = ctx->ens_M > 0 ? ctx->ens_Kr : ctx->K;
+        Kr = ctx->seeds.M > 0 ? ctx->seeds.Kr : ctx->K;
         return &ctx->control_costs;
     }
     if (path == QOCX_PATH_LINDBLAD && ctx->lb.has_problem) {

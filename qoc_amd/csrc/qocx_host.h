@@ -161,6 +161,47 @@ struct EffectiveControls {
     int quad_count() const { return kind == QUADRATIC ? (int)pairs.size() / 2 : 0; }
 };
 
+// Per-seed or per-member tables of the controls' channels, held by value by both paths (ctx->seeds,
+// ctx->lb.seeds): the last J of the problem's K channels are fixed channels, the first Kr = K - J
+// those of the seeds, and row r of the tables scales the seed channels (s_rk u_k) and sets the fixed
+// ones (delta_rj).
+//  - Hamiltonian ensemble (qocx_set_ensemble / qocx_lindblad_set_ensemble, EnsembleArgs): M member
+//    rows; every seed is evaluated as its M member items, item b * M + m, whose results are folded
+//    with `weights` into the seed's. The seed-level calls take and return the seeds' Kr channels.
+//  - Hamiltonian sweep (qocx_set_sweep / qocx_lindblad_set_sweep, SystemSweepArgs): seed b is a
+//    system of its own, item b, with row b: swp_B rows and M = 1, ONE item per seed, so every
+//    seed-level call (the optimizer drivers, control costs, downloads) serves it as it serves an
+//    ensemble; swp_B is also the only batch size the sweep takes.
+// A problem takes one or the other (the setters refuse the second kind, and a new problem clears
+// both), so the tables in these buffers are those of the last setter that succeeded and no launch
+// reads another kind's: rows() of them stand.
+struct SeedTables {
+    int M = 0;           // 0: neither; items per seed
+    int J = 0, Kr = 0;   // fixed channels, seed channels (K = Kr + J)
+    int swp_B = 0;       // 0: no sweep
+    std::vector<double> scales_h, offsets_h;  // [rows][Kr], [rows][J]: what the staging bounds read
+    DevBuf<double> scales, offsets, weights;  // ... on the device; [M] (an ensemble's only)
+    DevBuf<double> scale_sens, offset_sens;   // a sweep: dE_b/ds_bk [B][Kr], dE_b/ddelta_bj [B][J]
+    // Duration search of a sweep (qocx_sweep_set_durations / qocx_lindblad_sweep_set_durations): tau_b
+    // is a parameter of seed b on the device and the sweep's tables are derived there, tau_b times the
+    // base tables. The optimizer's clip and step move tau without telling the host: mirror_stale
+    // until the path has re-formed scales_h / offsets_h (which the next upload or sub-division reads).
+    struct Durations {
+        bool set = false, mirror_stale = false;
+        bool have_grad = false;  // `grad` is that of the standing evaluation
+        double tau_min = 0, tau_max = 0, weight = 0;
+        DevBuf<double> tau, base_scales, base_offsets, grad;  // [B], [B][Kr], [B][J], [B]
+        DevBuf<double> m, v, best;  // [B] each: Adam moments of tau, best tau (the drivers' *_opt_begin)
+        void clear() { set = mirror_stale = have_grad = false; }
+    } dur;
+    bool sweep() const { return swp_B > 0; }
+    int rows() const { return swp_B > 0 ? swp_B : M; }
+    void clear() {  // a new problem
+        M = J = Kr = swp_B = 0;
+        dur.clear();
+    }
+};
+
 }  // namespace qocx::host
 
 // (the host files name the shared helpers as the single file they were cut from did)
@@ -222,7 +263,6 @@ struct qocx_ctx {
     DevBuf<double2> kry_f, kry_b, action_carry;
     DevBuf<int> action_counts;
     int64_t action_reruns = 0;
-    // ---- Lindblad problem / evaluation state ----
     // ---- Magnus M4/M6 ----
     int nodes = 1;
     int cu_count = 256;
@@ -239,39 +279,19 @@ struct qocx_ctx {
         return eff.kind == E::QUADRATIC && nodes == 1 ? E::QUADRATIC : E::NONE;
     }
     int hermitian_linear = 0;  // `hermitian` of H0 / G_k alone (qocx_set_quadratic_terms folds in the Q_q)
-    // Hamiltonian ensemble (qocx_set_ensemble, EnsembleArgs): the last ens_J of the problem's K channels
-    // are fixed perturbation channels; controls, costs and gradients of the seeds live in ens_* and the
-    // evaluation buffers (controls, cost_out, grads, final_out) hold the B x M member items
-    int ens_M = 0;                       // 0: no ensemble
-    int ens_J = 0, ens_Kr = 0;           // fixed channels, seed channels (K = ens_Kr + ens_J)
-    int ens_B = 0;                       // seeds of the last upload (ctx->B = ens_B * ens_M)
+    // Hamiltonian ensemble or sweep (SeedTables). The seeds' controls, costs and gradients live in ens_*
+    // and the evaluation buffers (controls, cost_out, grads, final_out) hold the items; a sweep keeps
+    // the maxima over its seeds in ens_scale_max / ens_offset_max, and its expansion, reduction and
+    // staging are its own.
+    SeedTables seeds;
+    int ens_B = 0;                       // seeds of the last upload (ctx->B = ens_B * seeds.M)
     bool ens_stale = false;              // ens_controls moved (qocx_opt_clip / _step) since the expansion
-    std::vector<double> ens_scales_h, ens_offsets_h;    // [M][Kr], [M][J]
-    std::vector<double> ens_scale_max, ens_offset_max;  // max_m |s_mk|, max_m |delta_mj|
-    DevBuf<double> ens_scales, ens_offsets, ens_weights;
+    std::vector<double> ens_scale_max, ens_offset_max;  // max_r |s_rk|, max_r |delta_rj| (a duration search: at tau_max)
     DevBuf<double> ens_controls, ens_cost, ens_grads;   // [B][nc][Kr], [B], [B][nc][Kr]
     // ... with quadratic terms: the members' scales c_mq of the terms (qocx_set_ensemble_quadratic_scales)
     bool ens_qscales_set = false;
     std::vector<double> ens_qscale_max;                 // max_m |c_mq|
     DevBuf<double> ens_qscales;                         // [M][count]
-    // Hamiltonian sweep (qocx_set_sweep, SystemSweepArgs): seed b is a system of its own, item b. It is the
-    // ensemble's seed-level state above with ONE item per seed (ens_M = 1: ens_Kr, ens_J, ens_B,
-    // ens_stale, ens_controls / _cost / _grads, and ens_scale_max / ens_offset_max as maxima over the
-    // seeds), so every seed-level call (qocx_opt_*, control costs, downloads) serves it unchanged;
-    // its tables are per SEED and live here, and its expansion, reduction and staging are its own.
-    int swp_B = 0;                                      // 0: no sweep; else the only batch size it takes
-    std::vector<double> swp_scales_h, swp_offsets_h;    // [B][Kr], [B][J]
-    DevBuf<double> swp_scales, swp_offsets;
-    DevBuf<double> swp_scale_sens, swp_offset_sens;     // [B][Kr], [B][J] (qocx_sweep_download_sensitivities)
-    // Duration search of the sweep (qocx_sweep_set_durations, qocx_duration.hip): tau_b is a parameter of
-    // seed b on the device and swp_scales / swp_offsets are derived there, tau_b times the base tables.
-    // qocx_opt_clip rewrites them without telling the host: dur_mirror_stale until sweep_mirror_tables()
-    // has fetched swp_scales_h / swp_offsets_h again (qocx_upload_controls reads them).
-    bool dur_set = false, dur_mirror_stale = false;
-    bool dur_have_grad = false;                         // dur_grad is that of the standing evaluation
-    double dur_tau_min = 0, dur_tau_max = 0, dur_weight = 0;
-    DevBuf<double> dur_tau, dur_base_scales, dur_base_offsets, dur_grad;  // [B], [B][Kr], [B][J], [B]
-    DevBuf<double> dur_m, dur_v, dur_best;              // [B] each: Adam moments of tau, best tau (qocx_opt_begin*)
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;
@@ -337,15 +357,10 @@ struct qocx_ctx {
         DevBuf<int> order_dev;            // lb.order on the device
         MultiStart ms;                    // qocx_lindblad_opt_*
         ControlCosts control_costs;       // qocx_set_control_costs(QOCX_PATH_LINDBLAD)
-        // Hamiltonian ensemble (qocx_lindblad_set_ensemble, EnsembleArgs): the last ens_J of the problem's
-        // K channels are fixed perturbation channels. The seed-level calls take and return the seeds'
-        // K_r channels; an evaluation runs on the B x M member items (item b * M + m), each with its own
-        // sub-division count, and the buffers above (controls, cost_out, grads, final_out, order, B)
-        // are then those of the items.
-        int ens_M = 0;                    // 0: no ensemble
-        int ens_J = 0, ens_Kr = 0;        // fixed channels, seed channels (K = ens_Kr + ens_J)
-        std::vector<double> ens_scales_h, ens_offsets_h;  // [M][Kr], [M][J]
-        DevBuf<double> ens_scales, ens_offsets, ens_weights;
+        // Hamiltonian ensemble or sweep (SeedTables). An evaluation runs on the items, each with its own
+        // sub-division count, and the buffers above (controls, cost_out, grads, final_out, order, B) are
+        // then those of the items.
+        SeedTables seeds;
         DevBuf<double> ens_seed_controls;  // [B][nc][Kr]: the seeds of qocx_eval_lindblad
         DevBuf<double> ens_seed_cost, ens_seed_grads;  // ... and their reduced results
         DevBuf<double> ens_items;          // [B][M][nc][K]: the expanded controls, item order
@@ -361,16 +376,9 @@ struct qocx_ctx {
         std::vector<double> rate_l0_norm;                // [M]: l0_norm of the members
         DevBuf<double2> rate_a0;                         // [M][4] dumps A0L, A0R, A0L^H, A0R^H
         DevBuf<double> rate_gammas;                      // [M][L']
-        // Hamiltonian sweep (qocx_lindblad_set_sweep, SystemSweepArgs): seed b is a system of its own, item b.
-        // As on the Schroedinger path it is the ensemble's seed-level state with ONE item per seed
-        // (ens_M = 1: ens_Kr, ens_J, the seed / item buffers above), its tables per SEED live here, and its
-        // expansion, reduction and channel sensitivities are the kernels of qocx_sweep.hip. With rate
-        // factors the rates tables above hold one entry per seed (ens_rates, rate_a0, rate_gammas,
+        // A sweep's expansion, reduction and channel sensitivities are the kernels of qocx_sweep.hip. With
+        // rate factors the rates tables above hold one entry per seed (ens_rates, rate_a0, rate_gammas,
         // rate_l0_norm [B]) and item_member is the launched seed's own index.
-        int swp_B = 0;                                      // 0: no sweep; else the only batch size it takes
-        std::vector<double> swp_scales_h, swp_offsets_h;    // [B][Kr], [B][J]
-        DevBuf<double> swp_scales, swp_offsets;
-        DevBuf<double> swp_scale_sens, swp_offset_sens;     // [B][Kr], [B][J]
         const double* swp_seed_controls = nullptr;          // the seed controls of the last evaluation (device)
         bool swp_have_grads = false;                        // ... which had gradients, and whose results stand
         // rate sensitivities (qocx_lindblad_ratesens.hip): asked for, and whether every piece of the last
@@ -378,23 +386,17 @@ struct qocx_ctx {
         bool swp_want_rates = false, swp_rates_ok = false;
         DevBuf<double2> swp_ldl;                            // [L] dumps of L_l^H L_l
         DevBuf<double> swp_rate_partials, swp_rate_sens;    // [sub-intervals of the evaluation][L]; [B][L], launch order
-        // Duration search of the sweep (qocx_lindblad_sweep_set_durations, qocx_lindblad_duration.hip): tau_b is a
-        // parameter of seed b on the device; swp_scales / swp_offsets and the rates tables (rate_a0,
-        // rate_gammas) are derived there, tau_b times the base tables below. The host mirrors - swp_scales_h,
-        // swp_offsets_h and rate_l0_norm, which decide the sub-division counts - are re-formed from tau by
-        // the same single products once it has come back (lindblad_duration_mirror); dur_mirror_stale: tau
-        // has moved on the device since the tables were last written.
-        bool dur_set = false, dur_mirror_stale = false;
-        bool dur_have_grad = false;                         // dur_grad is that of the standing evaluation
-        double dur_tau_min = 0, dur_tau_max = 0, dur_weight = 0;
-        DevBuf<double> dur_tau, dur_base_scales, dur_base_offsets, dur_base_rates, dur_grad;  // [B], [B][Kr], [B][J], [B][L], [B]
+        // A duration search (qocx_lindblad_duration.hip) also derives the rates tables (rate_a0, rate_gammas)
+        // on the device, tau_b times the base tables below. The host mirrors - seeds.scales_h, seeds.offsets_h
+        // and rate_l0_norm, which decide the sub-division counts - are re-formed from tau by the same single
+        // products once it has come back (lindblad_duration_mirror).
+        DevBuf<double> dur_base_rates;                      // [B][L]
         DevBuf<double2> dur_base_a0;                        // [B][4] dumps at tau = 1 (rates c0_b gamma)
         DevBuf<double> dur_base_gammas;                     // [B][L'] at tau = 1
         std::vector<double> dur_tau_h, dur_base_scales_h, dur_base_offsets_h, dur_base_rates_h;  // host copies
         std::vector<double> dur_l0_norm0;                   // [B]: the seeds' l0_norm at tau = 1
-        DevBuf<double> dur_m, dur_v, dur_best;              // [B] each: Adam moments of tau, best tau
-        int seed_channels() const { return ens_M > 0 ? ens_Kr : K; }
-        size_t seed_items() const { return ens_M > 0 ? (size_t)ens_M : 1; }
+        int seed_channels() const { return seeds.M > 0 ? seeds.Kr : K; }
+        size_t seed_items() const { return seeds.M > 0 ? (size_t)seeds.M : 1; }
     } lb;
     // ---- qocx_debug_set_knob: kernel-variant switches for A/B measurements and tests ----
     std::map<std::string, int64_t> knobs;
@@ -438,8 +440,30 @@ int seed_channels(const qocx_ctx* ctx);
 double* seed_controls(qocx_ctx* ctx);
 double* seed_costs(qocx_ctx* ctx);
 double* seed_grads(qocx_ctx* ctx);
-// ---- qocx_api.hip: duration search of a sweep (qocx_sweep_set_durations) ----
-qocx::DurationArgs duration_args(qocx_ctx* ctx);  // of the sweep's tables, sensitivities and seed costs
+// ---- qocx_api.hip: what both paths do with a SeedTables ----
+// The setters' shared part: checks members / seeds (`rows`), `fixed` of the problem's K channels and the
+// three pointers (weights: an ensemble's), fills the tables with the defaults (scales 1), uploads them and
+// commits the shape; synchronises. The caller has made its own state checks and set the device.
+int set_seed_tables(SeedTables& s, bool sweep, int K, int rows, int fixed, const double* scales,
+                    const double* offsets, const double* weights, hipStream_t st);
+// ... of the duration setters: the box and weight checks, tau and the base tables s0 / d0 (returned: the
+// paths take their own maxima and mirrors from them) checked and uploaded, the sweep's tables ensured
+int set_seed_durations(SeedTables& s, const double* tau, const double* base_scales, const double* base_offsets,
+                       double tau_min, double tau_max, double time_weight, hipStream_t st, std::vector<double>& s0,
+                       std::vector<double>& d0);
+// tau and, where the caller says its gradient stands, dE/dtau of a duration search
+int download_seed_durations(const SeedTables& s, hipStream_t st, bool gradient_stands, double* tau_out,
+                            double* tau_grad_out);
+// The kernels' arguments from the tables and the buffers of a path they expand and reduce on
+struct SeedBuffers {
+    const double* seed_controls;   // [B][nc][Kr]
+    double* items;                 // the expanded controls [B][M][nc][K]
+    double *item_cost, *item_grads;  // the items' results, item order
+    double *cost, *grads;          // the seeds' reduced results (grads nullptr: none)
+};
+qocx::EnsembleArgs ensemble_args(const SeedTables& s, int seeds, int nc, const SeedBuffers& b);
+qocx::SystemSweepArgs sweep_args(const SeedTables& s, int nc, const SeedBuffers& b);
+qocx::DurationArgs duration_args(const SeedTables& s, double* tau_grad, double* cost);
 
 // ---- qocx_api_lindblad.hip: duration search of a Lindblad sweep (qocx_lindblad_sweep_set_durations) ----
 // clips tau and rewrites the sweep's tables and the seeds' generator tables from it (enqueued)

@@ -67,8 +67,8 @@ struct EffCtlChunk {
             qocx::launch_m4lin_controls(m4, st);
         } else {
             qa.pairs = ctx->eff.pairs_dev.p; qa.count = ctx->eff.quad_count();
-            if (ctx->ens_M > 0 && ctx->ens_qscales_set) {
-                qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->ens_M; qa.item0 = (size_t)b0;
+            if (ctx->seeds.M > 0 && ctx->ens_qscales_set) {
+                qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->seeds.M; qa.item0 = (size_t)b0;
             }
             qocx::launch_quad_controls(qa, st);
         }

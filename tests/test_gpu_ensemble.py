@@ -306,6 +306,8 @@ def test_engine_rejections():
         assert eng._lib.qocx_set_ensemble(eng._ctx, 2, 0, None, engine_mod._dp(dummy),
                                           engine_mod._dp(w)) != 0  # offsets without channels
         assert b"offsets need fixed >= 1" in eng._lib.qocx_last_error()
+        assert eng._lib.qocx_set_ensemble(eng._ctx, 2, 0, None, None, None) != 0
+        assert b"weights missing" in eng._lib.qocx_last_error()
         with pytest.raises(engine_mod.QocxError, match="weights"):
             eng.set_ensemble(None, None, np.array([1.0, -1.0]))
         eng.set_ensemble(None, None, np.ones(1024))  # the largest M is taken
