@@ -71,6 +71,19 @@ double two_norm(const double* m, int n) {
 // (row 16 ti + 4 r + (l >> 4), col 16 tj + (l & 15)), index ((ti nb + tj) 4 + r) 64 + l
 int dump_tiles(int n) { return n <= 16 ? 1 : 2; }
 
+// f(dump index, row-major element index) for every element of the matrix; f(dump index, -1) for the padding
+template <typename F>
+void walk_c_dump(int n, F f) {
+    const int nb = dump_tiles(n);
+    for (int ti = 0; ti < nb; ++ti)
+        for (int tj = 0; tj < nb; ++tj)
+            for (int r = 0; r < 4; ++r)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int row = 16 * ti + 4 * r + (lane >> 4), col = 16 * tj + (lane & 15);
+                    f(((ti * nb + tj) * 4 + r) * 64 + lane, (row < n && col < n) ? row * n + col : -1);
+                }
+}
+
 }  // namespace
 
 namespace qocx::host {
@@ -78,18 +91,9 @@ namespace qocx::host {
 int dump_elems(int n) { return 256 * dump_tiles(n) * dump_tiles(n); }
 
 void from_c_dump(const double2* d, int n, double* out) {
-    const int nb = dump_tiles(n);
-    for (int ti = 0; ti < nb; ++ti)
-        for (int tj = 0; tj < nb; ++tj)
-            for (int r = 0; r < 4; ++r)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int row = 16 * ti + 4 * r + (lane >> 4), col = 16 * tj + (lane & 15);
-                    if (row < n && col < n) {
-                        const double2 e = d[((ti * nb + tj) * 4 + r) * 64 + lane];
-                        out[2 * ((size_t)row * n + col)] = e.x;
-                        out[2 * ((size_t)row * n + col) + 1] = e.y;
-                    }
-                }
+    walk_c_dump(n, [&](int at, int e) {
+        if (e >= 0) { out[2 * e] = d[at].x; out[2 * e + 1] = d[at].y; }
+    });
 }
 
 }  // namespace qocx::host
@@ -120,25 +124,17 @@ bool cm_is_hermitian(const cmat& a, int n) {
     return diff <= 1.5e-14 * big;
 }
 
-cmat cm_adjoint(const cmat& a, int n) {
+cmat cm_transpose(const cmat& a, int n, double imag_sign = 1.0) {
     cmat o = cm_zero(n);
     for (int r = 0; r < n; ++r)
         for (int c = 0; c < n; ++c) {
             o[2 * ((size_t)c * n + r)] = a[2 * ((size_t)r * n + c)];
-            o[2 * ((size_t)c * n + r) + 1] = -a[2 * ((size_t)r * n + c) + 1];
+            o[2 * ((size_t)c * n + r) + 1] = imag_sign * a[2 * ((size_t)r * n + c) + 1];
         }
     return o;
 }
 
-cmat cm_transpose(const cmat& a, int n) {
-    cmat o = cm_zero(n);
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) {
-            o[2 * ((size_t)c * n + r)] = a[2 * ((size_t)r * n + c)];
-            o[2 * ((size_t)c * n + r) + 1] = a[2 * ((size_t)r * n + c) + 1];
-        }
-    return o;
-}
+cmat cm_adjoint(const cmat& a, int n) { return cm_transpose(a, n, -1.0); }
 
 cmat cm_mul(const cmat& a, const cmat& b, int n) {
     cmat o = cm_zero(n);
@@ -168,32 +164,8 @@ void cm_axpy(cmat& y, double alpha, const cmat& x) {
     for (size_t e = 0; e < y.size(); ++e) y[e] += alpha * x[e];
 }
 
-
 void c_dump(const cmat& m, int n, double2* out) {
-    const int nb = dump_tiles(n);
-    for (int ti = 0; ti < nb; ++ti)
-        for (int tj = 0; tj < nb; ++tj)
-            for (int r = 0; r < 4; ++r)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int row = 16 * ti + 4 * r + (lane >> 4), col = 16 * tj + (lane & 15);
-                    double2 e = make_double2(0, 0);
-                    if (row < n && col < n) {
-                        e.x = m[2 * ((size_t)row * n + col)];
-                        e.y = m[2 * ((size_t)row * n + col) + 1];
-                    }
-                    out[((ti * nb + tj) * 4 + r) * 64 + lane] = e;
-                }
-}
-
-
-double cm_norm_inf(const cmat& m, int n) {
-    double best = 0;
-    for (int r = 0; r < n; ++r) {
-        double s = 0;
-        for (int c = 0; c < n; ++c) s += hypot(m[2 * ((size_t)r * n + c)], m[2 * ((size_t)r * n + c) + 1]);
-        best = std::max(best, s);
-    }
-    return best;
+    walk_c_dump(n, [&](int at, int e) { out[at] = e >= 0 ? make_double2(m[2 * e], m[2 * e + 1]) : make_double2(0, 0); });
 }
 
 // Spectral norm of the control-free Liouvillian X -> A_L X + X A_R + sum_i gamma_i L_i X L_i^H as
@@ -282,19 +254,12 @@ ControlFree control_free_part(const cmat& h0, double h0_norm, const std::vector<
     return cf;
 }
 
-}  // namespace
-}  // extern "C++"
-
-int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
-    if (!ctx || !p) return fail(QOCX_ERR_ARG, "NULL argument");
-    if (p->struct_size != (int32_t)sizeof(qocx_lindblad_problem))
-        return fail(QOCX_ERR_ARG, "qocx_lindblad_problem.struct_size does not match this "
-                                  "library's header (stale binding?)");
-    HIP_TRY(hipSetDevice(ctx->device));
+// qocx_set_lindblad_problem by stage. First every refusal that reads the description alone: it runs before
+// any state of the context is touched, so an argument fault leaves the previous problem in place
+int check_lindblad_problem(const qocx_lindblad_problem* p) {
     const int n = p->hilbert_size, S = p->density_count, K = p->control_count;
     const int N = p->system_eval_count, nc = p->control_eval_count, L = p->operator_count;
-    if (n < 1 || n > 32)
-        return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..32 for the Lindblad engine");
+    if (n < 1 || n > 32) return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..32 for the Lindblad engine");
     if (S < 1 || S > 64) return fail(QOCX_ERR_ARG, "density_count must be in 1..64");
     if (K < 0 || K > QOCX_LINDBLAD_MAX_K) return fail(QOCX_ERR_ARG, "control_count must be in 0..8");
     // (1..4 operators: the several-wave / tile-per-wave stage loops; 5..8: the one-wave kernels, whose stage
@@ -305,30 +270,52 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     if (p->cost_eval_step < 1) return fail(QOCX_ERR_ARG, "cost_eval_step must be >= 1");
     if (!p->initial_densities || (K > 0 && !p->g) || (L > 0 && (!p->operators || !p->dissipators)))
         return fail(QOCX_ERR_ARG, "missing problem arrays");
-    // densities, cotangents and stage derivatives live in LDS when they fit (n <= 16), else in
-    // per-seed HBM scratch
-    ctx->lb.global_scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;
-    if (qocx::lindblad_lds_size(n, S, L, ctx->lb.global_scratch, K) > 160 * 1024)
+    const int scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;  // (choose_launch_form)
+    if (qocx::lindblad_lds_size(n, S, L, scratch, K) > 160 * 1024)
         return fail(QOCX_ERR_ARG, "too many operators for the kernel's LDS");
+    if ((p->op_stages != nullptr) != (p->diss_stages != nullptr))
+        return fail(QOCX_ERR_ARG, "diss_stages and op_stages go together");
+    if (p->op_stages != nullptr && L > 0 && p->fixed_subdivision <= 0)
+        return fail(QOCX_ERR_ARG, "time-dependent lindblad_data needs fixed_subdivision > 0");
+    if (p->fixed_subdivision > 0 && !p->h0_stages) return fail(QOCX_ERR_ARG, "h0_stages missing");
+    for (int ci = 0; ci < p->cost_count; ++ci) {
+        const qocx_cost_desc& c = p->costs[ci];
+        if (!c.vectors) return fail(QOCX_ERR_ARG, "cost matrices missing");
+        if (c.kind == QOCX_COST_FORBID_DENSITY) {
+            if (!c.counts) return fail(QOCX_ERR_ARG, "forbid counts missing");
+            for (int s = 0; s < S; ++s)
+                if (c.counts[s] < 1) return fail(QOCX_ERR_ARG, "forbid count < 1");
+        } else if (c.kind != QOCX_COST_TARGET_DENSITY) {
+            return fail(QOCX_ERR_ARG, "cost kind not valid for the Lindblad path");
+        }
+    }
+    return 0;
+}
+
+// The launch form of the problem: where its densities live, and how many waves work on a seed
+void choose_launch_form(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
+    auto& lb = ctx->lb;
+    const int n = p->hilbert_size, S = p->density_count, K = p->control_count, L = p->operator_count;
+    // densities, cotangents and stage derivatives live in LDS when they fit (n <= 16), else in per-seed HBM scratch
+    lb.global_scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;
     // several waves per seed (generator terms | one per operator | control cotangents) whenever
     // that layout fits LDS: the recursion in time is serial, this shortens every stage
     // (ONE operator - the T1 problem - runs the several-wave launches as two, the second one zero: the
     // four-wave stage loops of section 14 exist for L = 2 only and are 1.5 times faster than the three-wave
     // form of L = 1 although they multiply by that zero: 17.2 -> 11.5 ms on configs[3]'s sizes)
-    ctx->lb.pad_op = (L == 1 && n <= 16 && p->op_stages == nullptr && ctx->knob("lindblad_pad_operator", 1) != 0) ? 1 : 0;
-    const int Lmw = ctx->lb.pad_op ? 2 : L;
-    ctx->lb.multi_wave = (!ctx->lb.global_scratch && L > 0 && L <= 4 &&
-                          qocx::lindblad_lds_size(n, S, Lmw, 2, K) <= 160 * 1024 &&
-                          !qocx::diag_getenv("QOCX_LINDBLAD_SINGLE_WAVE")) ? 1 : 0;
-    ctx->lb.cache_gen = (ctx->lb.multi_wave && p->fixed_subdivision <= 0 &&
-                         qocx::lindblad_lds_size(n, S, Lmw, 3, K) <= 160 * 1024) ? 1 : 0;
-    auto& lb = ctx->lb;
-    lb.has_problem = false;
-    lb.control_costs.clear();
-    lb.n = n; lb.S = S; lb.K = K; lb.nc = nc; lb.N = N; lb.nsteps = N - 1; lb.ces = p->cost_eval_step;
-    lb.nops = L; lb.T = p->evolution_time; lb.dt = p->evolution_time / (N - 1);
-    lb.pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
+    lb.pad_op = (L == 1 && n <= 16 && p->op_stages == nullptr && ctx->knob("lindblad_pad_operator", 1) != 0) ? 1 : 0;
+    const int Lmw = lb.pad_op ? 2 : L;
+    lb.multi_wave = (!lb.global_scratch && L > 0 && L <= 4 &&
+                     qocx::lindblad_lds_size(n, S, Lmw, 2, K) <= 160 * 1024 &&
+                     !qocx::diag_getenv("QOCX_LINDBLAD_SINGLE_WAVE")) ? 1 : 0;
+    lb.cache_gen = (lb.multi_wave && p->fixed_subdivision <= 0 &&
+                    qocx::lindblad_lds_size(n, S, Lmw, 3, K) <= 160 * 1024) ? 1 : 0;
+}
 
+// The control-free part (host copies, norm bounds) and the images of G_k; `decay`: sum gamma_i L_i^H L_i
+int upload_static_part(qocx_ctx* ctx, const qocx_lindblad_problem* p, cmat& decay, bool& hermitian) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, K = lb.K, L = lb.nops;
     const cmat h0 = p->h0 ? cm_from(p->h0, n) : cm_zero(n);
     std::vector<cmat> ops;
     std::vector<double> gammas(L), op_norms(L);
@@ -347,116 +334,107 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
             if (op[2 * e + 1] != 0.0) lb.ops_real = false;
     lb.h0_norm = two_norm(h0.data(), n);
     const ControlFree cf = control_free_part(h0, lb.h0_norm, ops, gammas, op_norms, L, n);
-    const cmat &a0l = cf.a0l, &a0r = cf.a0r, &decay = cf.decay;  // decay: sum gamma_i L_i^H L_i
-    lb.diss_norm = cf.diss_norm;
-    lb.l0_norm = cf.l0_norm;
-    lb.hermitian = p->h0_stages == nullptr && p->g_stages == nullptr && p->op_stages == nullptr &&
-                   cm_is_hermitian(h0, n) && cm_is_hermitian(decay, n);
+    decay = cf.decay; lb.diss_norm = cf.diss_norm; lb.l0_norm = cf.l0_norm;
+    hermitian = cm_is_hermitian(h0, n) && cm_is_hermitian(decay, n);
     // (kept for qocx_lindblad_set_ensemble_rates, which builds the members' control-free parts from them)
-    lb.h0_h = h0;
-    lb.ops_h = ops;
-    lb.gammas_h = gammas;
-    lb.op_norms_h = op_norms;
+    lb.h0_h = h0; lb.ops_h = ops; lb.gammas_h = gammas; lb.op_norms_h = op_norms;
     std::vector<cmat> gp, gpd, gpt;
     lb.g_norm.assign(K, 0.0);
     for (int k = 0; k < K; ++k) {
         const cmat gk = cm_from(p->g + (size_t)k * n * n * 2, n);
         lb.g_norm[k] = two_norm(gk.data(), n);
-        lb.hermitian = lb.hermitian && cm_is_hermitian(gk, n);
+        hermitian = hermitian && cm_is_hermitian(gk, n);
         gp.push_back(cm_scale(gk, 0.0, -1.0));  // Gp = -i G
         gpd.push_back(cm_adjoint(gp.back(), n));
         gpt.push_back(cm_transpose(gp.back(), n));
     }
-    if (upload_dumps(lb.a0l, {a0l}, n, ctx->stream) || upload_dumps(lb.a0r, {a0r}, n, ctx->stream) ||
-        upload_dumps(lb.a0ld, {cm_adjoint(a0l, n)}, n, ctx->stream) ||
-        upload_dumps(lb.a0rd, {cm_adjoint(a0r, n)}, n, ctx->stream) ||
+    if (upload_dumps(lb.a0l, {cf.a0l}, n, ctx->stream) || upload_dumps(lb.a0r, {cf.a0r}, n, ctx->stream) ||
+        upload_dumps(lb.a0ld, {cm_adjoint(cf.a0l, n)}, n, ctx->stream) ||
+        upload_dumps(lb.a0rd, {cm_adjoint(cf.a0r, n)}, n, ctx->stream) ||
         upload_dumps(lb.gp, gp, n, ctx->stream) || upload_dumps(lb.gpd, gpd, n, ctx->stream) ||
         upload_dumps(lb.gpt, gpt, n, ctx->stream) || upload_dumps(lb.ops, ops, n, ctx->stream) ||
         lb.gammas.upload(gammas, ctx->stream))
         return QOCX_ERR_HIP;
-    // Time-dependent Hamiltonian: samples at the stage times of the fixed sub-division
-    // (qocx_lindblad_stage_times), turned into per-stage generator dumps.
-    lb.fixed_ksub = 0;
-    lb.a0_tab.release();
-    lb.gp_tab.release();
-    lb.op_tab.release();
-    lb.gamma_tab.release();
-    const bool td_ops = p->op_stages != nullptr && L > 0;
-    if ((p->op_stages != nullptr) != (p->diss_stages != nullptr))
-        return fail(QOCX_ERR_ARG, "diss_stages and op_stages go together");
-    if (td_ops && p->fixed_subdivision <= 0)
-        return fail(QOCX_ERR_ARG, "time-dependent lindblad_data needs fixed_subdivision > 0");
-    if (p->fixed_subdivision > 0) {
-        if (!p->h0_stages) return fail(QOCX_ERR_ARG, "h0_stages missing");
-        int64_t count = 0;
-        // (piecewise constant: the slice edges are the cut points of nc + 1 linear knots)
-        int rc = qocx_lindblad_stage_times(p->evolution_time, N, lb.pwc ? nc + 1 : nc, K,
-                                           p->fixed_subdivision, nullptr, 0, &count);
-        if (rc) return rc;
-        const size_t md = dump_elems(n);
-        std::vector<double2> tab((size_t)count * 4 * md);
-        lb.h0_norm = 0;
-        std::vector<double2> otab(td_ops ? (size_t)count * L * md : 0);
-        std::vector<double> gtab_d(td_ops ? (size_t)count * L : 0);
-        if (td_ops) lb.diss_norm = 0;
-        for (int64_t st = 0; st < count; ++st) {
-            const cmat h = cm_from(p->h0_stages + (size_t)st * n * n * 2, n);
-            // (norms on every fourth stage sample: they vary smoothly in time, the host picked
-            // the sub-division with a 25 % margin, and a power iteration per sample is what made
-            // this loop slow)
-            const bool norm_sample = (st % 4 == 0) || st == count - 1;
-            if (norm_sample) lb.h0_norm = std::max(lb.h0_norm, two_norm(h.data(), n));
-            cmat l = cm_scale(h, 0.0, -1.0), r = cm_scale(h, 0.0, 1.0);
-            cmat decay_st = decay;
-            if (td_ops) {  // -1/2 sum_i gamma_i(t) L_i(t)^H L_i(t) of THIS stage time
-                decay_st = cm_zero(n);
-                double dn = 0;
-                for (int i = 0; i < L; ++i) {
-                    const cmat li = cm_from(p->op_stages + ((size_t)st * L + i) * n * n * 2, n);
-                    const double gi = p->diss_stages[(size_t)st * L + i];
-                    cm_axpy(decay_st, gi, cm_mul(cm_adjoint(li, n), li, n));
-                    c_dump(li, n, otab.data() + ((size_t)st * L + i) * md);
-                    gtab_d[(size_t)st * L + i] = gi;
-                    if (norm_sample) {
-                        const double opn = two_norm(li.data(), n);
-                        dn += fabs(gi) * opn * opn;
-                    }
-                }
-                lb.diss_norm = std::max(lb.diss_norm, dn);
-            }
-            cm_axpy(l, -0.5, decay_st);
-            cm_axpy(r, -0.5, decay_st);
-            c_dump(l, n, tab.data() + ((size_t)st * 4 + 0) * md);
-            c_dump(r, n, tab.data() + ((size_t)st * 4 + 1) * md);
-            c_dump(cm_adjoint(l, n), n, tab.data() + ((size_t)st * 4 + 2) * md);
-            c_dump(cm_adjoint(r, n), n, tab.data() + ((size_t)st * 4 + 3) * md);
-        }
-        if (lb.a0_tab.upload(tab, ctx->stream)) return QOCX_ERR_HIP;
-        if (td_ops && (lb.op_tab.upload(otab, ctx->stream) || lb.gamma_tab.upload(gtab_d, ctx->stream)))
-            return QOCX_ERR_HIP;
-        if (p->g_stages && K > 0) {
-            std::vector<double2> gtab((size_t)count * K * 3 * md);
-            lb.g_norm.assign(K, 0.0);
-            for (int64_t st = 0; st < count; ++st)
-                for (int k = 0; k < K; ++k) {
-                    const cmat gk = cm_from(p->g_stages + ((size_t)st * K + k) * n * n * 2, n);
-                    if (st % 4 == 0 || st == count - 1)
-                        lb.g_norm[k] = std::max(lb.g_norm[k], two_norm(gk.data(), n));
-                    const cmat gpk = cm_scale(gk, 0.0, -1.0);
-                    double2* dst = gtab.data() + (((size_t)st * K + k) * 3) * md;
-                    c_dump(gpk, n, dst);
-                    c_dump(cm_adjoint(gpk, n), n, dst + md);
-                    c_dump(cm_transpose(gpk, n), n, dst + 2 * md);
-                }
-            if (lb.gp_tab.upload(gtab, ctx->stream)) return QOCX_ERR_HIP;
-        }
-        lb.fixed_ksub = p->fixed_subdivision;
-    }
-    std::vector<cmat> rho0;
-    for (int s = 0; s < S; ++s) rho0.push_back(cm_from(p->initial_densities + (size_t)s * n * n * 2, n));
-    if (upload_dumps(lb.rho0, rho0, n, ctx->stream)) return QOCX_ERR_HIP;
-    for (const cmat& r : rho0) lb.hermitian = lb.hermitian && cm_is_hermitian(r, n);
+    return 0;
+}
 
+// Time-dependent Hamiltonian: the samples at the stage times of the fixed sub-division
+// (qocx_lindblad_stage_times) as per-stage dumps, and the norm bounds taken over the samples
+int upload_stage_tables(qocx_ctx* ctx, const qocx_lindblad_problem* p, const cmat& decay) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, K = lb.K, L = lb.nops;
+    const bool td_ops = p->op_stages != nullptr && L > 0, td_g = p->g_stages != nullptr && K > 0;
+    int64_t count = 0;
+    // (piecewise constant: the slice edges are the cut points of nc + 1 linear knots)
+    if (int rc = qocx_lindblad_stage_times(p->evolution_time, lb.N, lb.pwc ? lb.nc + 1 : lb.nc, K,
+                                           p->fixed_subdivision, nullptr, 0, &count))
+        return rc;
+    const size_t md = dump_elems(n);
+    std::vector<double2> tab((size_t)count * 4 * md), otab(td_ops ? (size_t)count * L * md : 0);
+    std::vector<double2> gtab(td_g ? (size_t)count * K * 3 * md : 0);
+    std::vector<double> gamtab(td_ops ? (size_t)count * L : 0);
+    lb.h0_norm = 0;
+    if (td_ops) lb.diss_norm = 0;
+    if (td_g) lb.g_norm.assign(K, 0.0);
+    for (int64_t st = 0; st < count; ++st) {
+        // Norms on every fourth stage sample, and on the last: they vary smoothly in time, the host picked
+        // the sub-division with a 25 % margin, and a power iteration per sample is what made this loop slow
+        const bool norm_sample = (st % 4 == 0) || st == count - 1;
+        const cmat h = cm_from(p->h0_stages + (size_t)st * n * n * 2, n);
+        if (norm_sample) lb.h0_norm = std::max(lb.h0_norm, two_norm(h.data(), n));
+        cmat l = cm_scale(h, 0.0, -1.0), r = cm_scale(h, 0.0, 1.0);
+        cmat decay_st = decay;
+        if (td_ops) {  // -1/2 sum_i gamma_i(t) L_i(t)^H L_i(t) of THIS stage time
+            decay_st = cm_zero(n);
+            double dn = 0;
+            for (int i = 0; i < L; ++i) {
+                const cmat li = cm_from(p->op_stages + ((size_t)st * L + i) * n * n * 2, n);
+                const double gi = p->diss_stages[(size_t)st * L + i];
+                cm_axpy(decay_st, gi, cm_mul(cm_adjoint(li, n), li, n));
+                c_dump(li, n, otab.data() + ((size_t)st * L + i) * md);
+                gamtab[(size_t)st * L + i] = gi;
+                if (norm_sample) {
+                    const double opn = two_norm(li.data(), n);
+                    dn += fabs(gi) * opn * opn;
+                }
+            }
+            lb.diss_norm = std::max(lb.diss_norm, dn);
+        }
+        cm_axpy(l, -0.5, decay_st);
+        cm_axpy(r, -0.5, decay_st);
+        double2* a0 = tab.data() + (size_t)st * 4 * md;
+        c_dump(l, n, a0); c_dump(r, n, a0 + md);
+        c_dump(cm_adjoint(l, n), n, a0 + 2 * md); c_dump(cm_adjoint(r, n), n, a0 + 3 * md);
+        for (int k = 0; td_g && k < K; ++k) {
+            const cmat gk = cm_from(p->g_stages + ((size_t)st * K + k) * n * n * 2, n);
+            if (norm_sample) lb.g_norm[k] = std::max(lb.g_norm[k], two_norm(gk.data(), n));
+            const cmat gpk = cm_scale(gk, 0.0, -1.0);
+            double2* dst = gtab.data() + (((size_t)st * K + k) * 3) * md;
+            c_dump(gpk, n, dst); c_dump(cm_adjoint(gpk, n), n, dst + md); c_dump(cm_transpose(gpk, n), n, dst + 2 * md);
+        }
+    }
+    if (lb.a0_tab.upload(tab, ctx->stream)) return QOCX_ERR_HIP;
+    if (td_ops && (lb.op_tab.upload(otab, ctx->stream) || lb.gamma_tab.upload(gamtab, ctx->stream)))
+        return QOCX_ERR_HIP;
+    if (td_g && lb.gp_tab.upload(gtab, ctx->stream)) return QOCX_ERR_HIP;
+    lb.fixed_ksub = p->fixed_subdivision;
+    return 0;
+}
+
+int upload_initial_densities(qocx_ctx* ctx, const qocx_lindblad_problem* p, bool& hermitian) {
+    auto& lb = ctx->lb;
+    std::vector<cmat> rho0;
+    for (int s = 0; s < lb.S; ++s) rho0.push_back(cm_from(p->initial_densities + (size_t)s * lb.n * lb.n * 2, lb.n));
+    if (upload_dumps(lb.rho0, rho0, lb.n, ctx->stream)) return QOCX_ERR_HIP;
+    hermitian = true;
+    for (const cmat& r : rho0) hermitian = hermitian && cm_is_hermitian(r, lb.n);
+    return 0;
+}
+
+// The cost descriptors (checked by check_lindblad_problem) with their pooled matrices
+int upload_lindblad_costs(qocx_ctx* ctx, const qocx_lindblad_problem* p, bool& hermitian) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, S = lb.S;
     std::vector<qocx::DevCost> dcosts;
     std::vector<cmat> pool;
     std::vector<int> counts;
@@ -464,47 +442,67 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     for (int ci = 0; ci < p->cost_count; ++ci) {
         const qocx_cost_desc& c = p->costs[ci];
         qocx::DevCost d;
-        d.step_cost = c.step_cost ? 1 : 0;
-        d.scale = c.scale;
-        d.vec_offset = (int)pool.size();
-        d.cnt_offset = (int)counts.size();
-        if (!c.vectors) return fail(QOCX_ERR_ARG, "cost matrices missing");
+        d.step_cost = c.step_cost ? 1 : 0; d.scale = c.scale;
+        d.vec_offset = (int)pool.size(); d.cnt_offset = (int)counts.size();
+        d.kind = c.kind == QOCX_COST_TARGET_DENSITY ? QOCX_DEV_COST_TARGET_DENSITY : QOCX_DEV_COST_FORBID_DENSITY;
         int nmat = S;
-        if (c.kind == QOCX_COST_TARGET_DENSITY) {
-            d.kind = QOCX_DEV_COST_TARGET_DENSITY;
-        } else if (c.kind == QOCX_COST_FORBID_DENSITY) {
-            d.kind = QOCX_DEV_COST_FORBID_DENSITY;
-            if (!c.counts) return fail(QOCX_ERR_ARG, "forbid counts missing");
+        if (c.kind == QOCX_COST_FORBID_DENSITY) {
             nmat = 0;
             for (int s = 0; s < S; ++s) {
-                if (c.counts[s] < 1) return fail(QOCX_ERR_ARG, "forbid count < 1");
                 counts.push_back(c.counts[s]);
                 nmat += c.counts[s];
             }
-        } else {
-            return fail(QOCX_ERR_ARG, "cost kind not valid for the Lindblad path");
         }
         for (int m = 0; m < nmat; ++m) pool.push_back(cm_from(c.vectors + (size_t)m * n * n * 2, n));
         if (d.step_cost) lb.has_step_costs = 1;
         dcosts.push_back(d);
     }
-    for (const cmat& m : pool) lb.hermitian = lb.hermitian && cm_is_hermitian(m, n);
+    hermitian = true;
+    for (const cmat& m : pool) hermitian = hermitian && cm_is_hermitian(m, n);
     lb.cost_count = (int)dcosts.size();
-    lb.unit_ok = dcosts.size() == 1 && !dcosts[0].step_cost &&
-                 dcosts[0].kind == QOCX_DEV_COST_TARGET_DENSITY;
+    lb.unit_ok = dcosts.size() == 1 && !dcosts[0].step_cost && dcosts[0].kind == QOCX_DEV_COST_TARGET_DENSITY;
     if (lb.costs.upload(dcosts, ctx->stream) || upload_dumps(lb.cost_matrices, pool, n, ctx->stream) ||
         lb.cost_counts.upload(counts, ctx->stream))
         return QOCX_ERR_HIP;
+    return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
+    if (!ctx || !p) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (p->struct_size != (int32_t)sizeof(qocx_lindblad_problem))
+        return fail(QOCX_ERR_ARG, "qocx_lindblad_problem.struct_size does not match this "
+                                  "library's header (stale binding?)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = check_lindblad_problem(p)) return rc;
+    auto& lb = ctx->lb;
+    lb.has_problem = false;
+    lb.control_costs.clear();
+    choose_launch_form(ctx, p);
+    lb.n = p->hilbert_size; lb.S = p->density_count; lb.K = p->control_count; lb.nc = p->control_eval_count;
+    lb.N = p->system_eval_count; lb.nsteps = lb.N - 1; lb.ces = p->cost_eval_step; lb.nops = p->operator_count;
+    lb.T = p->evolution_time; lb.dt = p->evolution_time / lb.nsteps;
+    lb.pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
+    lb.fixed_ksub = 0;
+    lb.a0_tab.release(); lb.gp_tab.release(); lb.op_tab.release(); lb.gamma_tab.release();
+    cmat decay;
+    bool h_static = false, h_rho = false, h_costs = false;
+    if (int rc = upload_static_part(ctx, p, decay, h_static)) return rc;
+    if (p->fixed_subdivision > 0)
+        if (int rc = upload_stage_tables(ctx, p, decay)) return rc;
+    if (int rc = upload_initial_densities(ctx, p, h_rho)) return rc;
+    if (int rc = upload_lindblad_costs(ctx, p, h_costs)) return rc;
+    // (stage tables: the Hermitian shortcuts read constant generators)
+    lb.hermitian = p->h0_stages == nullptr && p->g_stages == nullptr && p->op_stages == nullptr && h_static &&
+                   h_rho && h_costs;
     lb.grids.clear();  // (frees the tables of the old problem's grids)
     lb.has_problem = true;
-    lb.have_results = false;
-    lb.res_B = lb.ms.batch = 0;  // resident controls and optimizer states belong to the old problem
-    lb.res_have_results = false;
+    lb.drop_resident();  // resident controls and optimizer states belong to the old problem
     lb.inj_count = 0;
     lb.seeds.clear();  // ... and so do the ensemble with its rates, or the sweep with its duration search
-    lb.ens_members_B = 0;
-    lb.ens_rates = false;
-    lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
+    lb.ens_rates = lb.swp_want_rates = false;
     return 0;
 }
 
@@ -522,12 +520,9 @@ int qocx_lindblad_set_ensemble(qocx_ctx* ctx, int32_t members, int32_t fixed, co
     // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
     if (int rc = set_seed_tables(lb.seeds, false, lb.K, members, fixed, scales, offsets, weights, ctx->stream))
         return rc;
-    lb.ens_members_B = 0;
-    lb.ens_rates = false;        // (qocx_lindblad_set_ensemble_rates comes after, as the quadratic scales do)
-    lb.have_results = false;
-    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
-    lb.res_have_results = false;
-    lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
+    lb.ens_rates = false;      // (qocx_lindblad_set_ensemble_rates comes after, as the quadratic scales do)
+    lb.drop_resident();        // controls must be uploaded again (as seed controls)
+    lb.control_costs.clear();  // (they were set for K channels: qocx_set_control_costs comes after)
     return 0;
 }
 
@@ -578,15 +573,9 @@ int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t ope
     if (lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "per-member rates need a static problem: this one was set with stage tables "
                                     "(fixed_subdivision > 0), which hold one control-free generator per stage");
-    auto invalidate = [&] {
-        lb.ens_members_B = 0;
-        lb.have_results = false;
-        lb.res_B = lb.ms.batch = 0;
-        lb.res_have_results = false;
-    };
     if (!rate_scales) {
         lb.ens_rates = false;
-        invalidate();
+        lb.drop_resident();
         return 0;
     }
     const int M = lb.seeds.M, L = lb.nops;
@@ -598,7 +587,7 @@ int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t ope
     HIP_TRY(hipSetDevice(ctx->device));
     if (int rc = build_rate_tables(ctx, M, rate_scales)) return rc;
     lb.ens_rates = true;
-    invalidate();
+    lb.drop_resident();
     return 0;
 }
 
@@ -625,14 +614,10 @@ int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const d
     HIP_TRY(hipSetDevice(ctx->device));
     // (control_count <= QOCX_LINDBLAD_MAX_K was checked by the problem setter: K_r + J <= 8)
     if (int rc = set_seed_tables(lb.seeds, true, lb.K, seeds, fixed, scales, offsets, nullptr, ctx->stream)) return rc;
-    lb.swp_have_grads = lb.swp_rates_ok = lb.swp_want_rates = false;
-    lb.swp_seed_controls = nullptr;
-    lb.ens_members_B = 0;
-    lb.ens_rates = false;        // (until the rates tables below stand)
-    lb.have_results = false;
-    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again (as seed controls)
-    lb.res_have_results = false;
-    lb.control_costs.clear();    // (they were set for K channels: qocx_set_control_costs comes after)
+    lb.swp_want_rates = false;
+    lb.ens_rates = false;      // (until the rates tables below stand)
+    lb.drop_resident();        // controls must be uploaded again (as seed controls)
+    lb.control_costs.clear();  // (they were set for K channels: qocx_set_control_costs comes after)
     // seed b: the control-free part of the plain problem with the rates c_b * gamma, built as the plain
     // setter builds its own (build_rate_tables)
     if (rates)
@@ -848,12 +833,52 @@ int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<
     return 0;
 }
 
-// What an evaluation of these sub-division counts launches: seeds with equal counts are evaluated
-// together (`lb.order` lists the seeds group by group), the grid tables and the evaluation's
-// buffers for them.
+// One piece of an evaluation - one launch, or the three of a two-sided piece: `count` seeds of the group
+// with sub-division count `ksub`, from position `first` of the launch order (lb.order).
+struct LindbladPiece {
+    int ksub = 0, first = 0, count = 0;
+    // the forward pass keeps its stage values for the adjoint (else: recomputed); several waves per seed
+    bool keep_stages = false, multi_wave = false;
+};
+
+// What decides the schedule: the stage budget (double2 elements), the record's debug knobs, the launch form
+struct PieceRule {
+    bool want_grad = false, multi_wave = false;
+    size_t stage_budget = 0;
+    int64_t dbg_stage_seeds = 0;
+    int dbg_min_piece = 256, dbg_wave_mode = 0, cu_count = 1;
+};
+
+// THE schedule (plain C++ over integers), for one group of `Bg` seeds from position `first`, `per_seed` stage
+// elements each; its pieces are appended in launch order. The stage values of the forward pass are kept for
+// the adjoint (12 x the checkpoints of the seeds in flight); a group that does not fit goes in pieces that do,
+// and only if a piece would fall below dbg_min_piece seeds does the adjoint recompute them instead (one piece,
+// as without gradients). Several waves per seed whenever the kernel is built for the problem; batches beyond
+// the CU count then go in rounds of one seed per CU. (Round 1 switched to one wave per seed, two seeds per CU,
+// beyond 256 seeds; on configs[3] at 300 / 512 / 768 / 1024 seeds: 73.7 / 80.7 / 126.6 / 123.7 ms against 74.4 /
+// 76.6 / 82.7 / 104.8 ms in rounds.) Returns the seeds the stage buffers are sized for: the kept piece BEFORE
+// the round cap (0: none kept), which over-provisions a capped group: the footprint of old.
+size_t lindblad_group_pieces(const PieceRule& r, int ksub, int first, int Bg, size_t per_seed,
+                             std::vector<LindbladPiece>& out) {
+    int piece = Bg;
+    bool keep = false;
+    if (r.want_grad) {
+        const size_t fit = r.dbg_stage_seeds > 0 ? (size_t)r.dbg_stage_seeds
+                                                 : std::max<size_t>(1, r.stage_budget / per_seed);
+        if (fit >= (size_t)Bg) { keep = true; }
+        else if (fit >= (size_t)r.dbg_min_piece) { keep = true; piece = (int)fit; }
+    }
+    const size_t sized_for = keep ? (size_t)piece : 0;
+    const bool multi = r.multi_wave && r.dbg_wave_mode != 1;
+    if (multi && r.dbg_wave_mode != 2) piece = std::min(piece, r.cu_count);
+    for (int p0 = 0; p0 < Bg; p0 += piece) out.push_back({ksub, first + p0, std::min(piece, Bg - p0), keep, multi});
+    return sized_for;
+}
+
+// What an evaluation of these sub-division counts launches: seeds with equal counts go together (`lb.order`
+// lists the seeds group by group) in the pieces of the schedule above; the grid tables and buffers for them.
 struct LindbladPlan {
-    std::map<int, std::vector<int>> groups;
-    size_t stage_budget = 0;  // double2 elements
+    std::vector<LindbladPiece> pieces;  // launch order
     bool two_sided_ok = false, two_sided_tiles = false;
 };
 
@@ -861,27 +886,21 @@ int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of,
     auto& lb = ctx->lb;
     const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = (int)ksub_of.size();
     const size_t md = dump_elems(n);
-    auto& groups = plan.groups;
+    std::map<int, std::vector<int>> groups;
     for (int b = 0; b < B; ++b) groups[ksub_of[b]].push_back(b);
     if (lb.grids.size() > 64) lb.grids.clear();  // bounded cache of sub-interval tables
     size_t ckpt_total = 0, gsub_total = 0;
     lb.order.clear();
     lb.last_subintervals = 0;
     for (auto& kv : groups) {
-        auto it = lb.grids.find(kv.first);
-        if (it == lb.grids.end()) {
-            int rc = build_lindblad_grid(ctx, kv.first, lb.grids[kv.first]);
-            if (rc) return rc;
-            it = lb.grids.find(kv.first);
-        }
-        ckpt_total += kv.second.size() * (size_t)it->second.nsub * S * md;
-        gsub_total += kv.second.size() * (size_t)it->second.nsub * 2 * std::max(K, 1);
-        lb.last_subintervals += (int64_t)kv.second.size() * it->second.nsub;
+        if (lb.grids.find(kv.first) == lb.grids.end())
+            if (int rc = build_lindblad_grid(ctx, kv.first, lb.grids[kv.first])) return rc;
+        const size_t seed_subs = kv.second.size() * (size_t)lb.grids[kv.first].nsub;
+        ckpt_total += seed_subs * S * md;
+        gsub_total += seed_subs * 2 * std::max(K, 1);
+        lb.last_subintervals += (int64_t)seed_subs;
         for (int b : kv.second) lb.order.push_back(b);
     }
-    // The stage values of the forward pass are kept for the adjoint (12 x the checkpoints of the
-    // seeds in flight); a group of seeds that does not fit is launched in pieces that do, and
-    // only if a piece would fall below 256 seeds does the adjoint recompute the stages instead.
     // Two-sided evaluation (LindbladArgs::phase): where it applies the adjoint's stage cotangents
     // need a buffer like the forward's stage values, and gsub holds complex numbers
     // (n > 16: the tile-per-wave kernel of qocx_lindblad4t.hip in its phases, constant tables only)
@@ -890,229 +909,257 @@ int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of,
     const bool two_sided_tiles = plan.two_sided_tiles = n > 16 && ctx->knob("lindblad_4t", 1) != 0 && lb.nops <= 4;
     const bool two_sided_ok = plan.two_sided_ok = want_grad && lb.unit_ok && lb.inj_count == 0 &&
                               (two_sided_small || two_sided_tiles) && lb.fixed_ksub == 0 &&
-                              (int)ctx->sweep_streams.size() >= 1 &&
-                              ctx->knob("lindblad_two_sided", 1) != 0;
-    if (two_sided_ok)
-        if (lb.lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
-    size_t& stage_budget = plan.stage_budget;
+                              (int)ctx->sweep_streams.size() >= 1 && ctx->knob("lindblad_two_sided", 1) != 0;
+    if (two_sided_ok && lb.lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
+    PieceRule rule{want_grad != 0, lb.multi_wave != 0, 0, lb.dbg_stage_seeds, lb.dbg_min_piece, lb.dbg_wave_mode,
+                   ctx->cu_count};
     if (want_grad) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        stage_budget = (size_t)(0.45 * (double)(free_b + (lb.ystages.count + lb.kbstages.count) *
-                                                              sizeof(double2))) /
-                       sizeof(double2);
-        if (two_sided_ok) stage_budget /= 2;  // kbar_i beside Y_i
-        size_t want = 0;
-        for (auto& kv : groups) {
-            const size_t per_seed = (size_t)lb.grids[kv.first].nsub * S * md * 12;
-            const size_t fit = lb.dbg_stage_seeds > 0 ? (size_t)lb.dbg_stage_seeds
-                                                      : std::max<size_t>(1, stage_budget / per_seed);
-            const size_t piece = std::min<size_t>(kv.second.size(), fit);
-            if (piece == kv.second.size() || piece >= (size_t)lb.dbg_min_piece)
-                want = std::max(want, piece * per_seed);
-        }
-        if (want > 0 && lb.ystages.ensure(want)) return QOCX_ERR_HIP;
-        if (want > 0 && two_sided_ok && lb.kbstages.ensure(want)) return QOCX_ERR_HIP;
+        rule.stage_budget =
+            (size_t)(0.45 * (double)(free_b + (lb.ystages.count + lb.kbstages.count) * sizeof(double2))) / sizeof(double2);
+        if (two_sided_ok) rule.stage_budget /= 2;  // kbar_i beside Y_i
     }
-    if (lb.global_scratch &&
-        lb.scratch.ensure((size_t)B * qocx::lindblad_scratch_elems(n, S)))
+    size_t stage_elems = 0;  // of the largest kept piece, before its round cap (lindblad_group_pieces)
+    int first = 0;
+    for (auto& kv : groups) {
+        const int Bg = (int)kv.second.size();
+        const size_t per_seed = (size_t)lb.grids[kv.first].nsub * S * md * 12;
+        stage_elems = std::max(stage_elems, per_seed * lindblad_group_pieces(rule, kv.first, first, Bg, per_seed,
+                                                                            plan.pieces));
+        first += Bg;
+    }
+    if (stage_elems > 0 && (lb.ystages.ensure(stage_elems) || (two_sided_ok && lb.kbstages.ensure(stage_elems))))
         return QOCX_ERR_HIP;
+    if (lb.global_scratch && lb.scratch.ensure((size_t)B * qocx::lindblad_scratch_elems(n, S))) return QOCX_ERR_HIP;
     const size_t csz = (size_t)nc * K;
     if (lb.controls.ensure((size_t)B * std::max<size_t>(csz, 1)) || lb.cost_out.ensure(B) ||
         lb.grads.ensure((size_t)B * std::max<size_t>(csz, 1)) || lb.gsub.ensure(gsub_total) ||
         lb.checkpoints.ensure(ckpt_total) || lb.final_out.ensure((size_t)B * S * md))
         return QOCX_ERR_HIP;
-    if (ctx->keep_step_states)
-        if (lb.step_densities.ensure((size_t)B * (nsteps + 1) * S * md)) return QOCX_ERR_HIP;
+    if (ctx->keep_step_states && lb.step_densities.ensure((size_t)B * (nsteps + 1) * S * md)) return QOCX_ERR_HIP;
     return 0;
 }
 
-// The launches group by group, piece by piece: results in lb.cost_out / grads / final_out in group
+// Host-supplied density cotangents (qocx_set_density_cotangents): dumps in launch order, the table step -> cotangent
+int upload_density_cotangents(qocx_ctx* ctx) {
+    auto& lb = ctx->lb;
+    const int n = lb.n, B = (int)lb.order.size();
+    const size_t md = dump_elems(n);
+    if (lb.inj_batch != B) return fail(QOCX_ERR_STATE, "density cotangents were set for a different batch size");
+    std::vector<int> index(lb.nsteps + 1, -1);
+    for (int c = 0; c < lb.inj_count; ++c) index[lb.inj_steps[c]] = c;
+    const size_t per_seed = (size_t)lb.inj_count * lb.S;
+    std::vector<double2> dumps((size_t)B * per_seed * md);
+    for (int pos = 0; pos < B; ++pos)
+        for (size_t v = 0; v < per_seed; ++v) {
+            cmat m(lb.inj_host.begin() + (((size_t)lb.order[pos] * per_seed + v) * n * n * 2),
+                   lb.inj_host.begin() + (((size_t)lb.order[pos] * per_seed + v + 1) * n * n * 2));
+            c_dump(m, n, dumps.data() + ((size_t)pos * per_seed + v) * md);
+        }
+    return (lb.inj_index.upload(index, ctx->stream) || lb.inj_bars.upload(dumps, ctx->stream)) ? QOCX_ERR_HIP : 0;
+}
+
+// The launches of one evaluation: what is the same for every piece, read once (the knobs are map lookups by
+// name), and the running offsets of the pieces into the evaluation's buffers
+struct LindbladLaunch {
+    int want_grad = 0, tile4 = 0, hermitian = 0, q2 = 0, chain = 0, ops_real = 0, side_limit = 0;
+    bool two_sided = false, stamps = false;
+    qocx::LindbladMembers mem;  // per-member rates (lb.ens_rates): the strides; item_member is the piece's
+    size_t ckpt_off = 0, gsub_off = 0, rate_off = 0;
+};
+
+// The arguments of the classic launch of piece `pc`; the two-sided launches add theirs (launch_two_sided)
+qocx::LindbladArgs lindblad_piece_args(qocx_ctx* ctx, const LindbladLaunch& ev, const LindbladPiece& pc) {
+    auto& lb = ctx->lb;
+    const int S = lb.S, nsteps = lb.nsteps;
+    const size_t md = dump_elems(lb.n), csz = (size_t)lb.nc * lb.K, pos0 = pc.first;
+    const auto& gr = lb.grids[pc.ksub];
+    qocx::LindbladArgs la;
+    la.controls = lb.controls.p + pos0 * csz; la.substeps = gr.substeps.p;
+    la.a0l_cimg = lb.a0l.p; la.a0r_cimg = lb.a0r.p; la.a0ld_cimg = lb.a0ld.p; la.a0rd_cimg = lb.a0rd.p;
+    la.gp_cimg = lb.gp.p; la.gpd_cimg = lb.gpd.p; la.gpt_cimg = lb.gpt.p; la.op_cimg = lb.ops.p;
+    la.gammas = lb.gammas.p; la.rho0_cimg = lb.rho0.p;
+    if (lb.ens_rates) {  // member 0's tables; a workgroup adds its member's stride (LindbladMembers)
+        la.a0l_cimg = lb.rate_a0.p; la.a0r_cimg = lb.rate_a0.p + md;
+        la.a0ld_cimg = lb.rate_a0.p + 2 * md; la.a0rd_cimg = lb.rate_a0.p + 3 * md;
+        la.gammas = lb.rate_gammas.p;
+    }
+    la.a0_tab = lb.fixed_ksub > 0 ? lb.a0_tab.p : nullptr;
+    la.gp_tab = (lb.fixed_ksub > 0 && lb.gp_tab.p) ? lb.gp_tab.p : nullptr;
+    la.op_tab = (lb.fixed_ksub > 0 && lb.op_tab.p) ? lb.op_tab.p : nullptr;
+    la.gamma_tab = la.op_tab ? lb.gamma_tab.p : nullptr;
+    la.n = lb.n; la.S = S; la.K = lb.K; la.nc = lb.nc; la.nsub = gr.nsub; la.nsteps = nsteps;
+    la.nops = (pc.multi_wave && lb.pad_op) ? 2 : lb.nops;
+    la.cost_eval_step = lb.ces; la.want_grad = ev.want_grad; la.has_step_costs = lb.has_step_costs; la.cost_count = lb.cost_count;
+    la.costs = lb.costs.p; la.cost_matrices = lb.cost_matrices.p; la.cost_counts = lb.cost_counts.p;
+    la.checkpoints = lb.checkpoints.p + ev.ckpt_off; la.gsub = lb.gsub.p + ev.gsub_off;
+    la.ystages = pc.keep_stages ? lb.ystages.p : nullptr;     // reused piece after piece
+    la.scratch = lb.global_scratch ? lb.scratch.p : nullptr;  // likewise
+    // several waves per seed shorten a seed's serial chain by ~1.4x but hold one seed
+    // per CU instead of two: worth it while the batch leaves CUs idle
+    la.multi_wave = pc.multi_wave ? 1 : 0;
+    la.cache_gen = (la.multi_wave && lb.cache_gen) ? 1 : 0;
+    la.cost_out = lb.cost_out.p + pos0; la.final_out = lb.final_out.p + pos0 * S * md;
+    la.step_densities = ctx->keep_step_states ? lb.step_densities.p + pos0 * (nsteps + 1) * S * md : nullptr;
+    la.tile4 = ev.tile4; la.hermitian = ev.hermitian;
+    // ([B] sets of the forward pass / classic launch, then [B] of the unit adjoint)
+    la.stamps = ev.stamps ? ctx->stamps.p + pos0 * 48 : nullptr;
+    la.inj_count = lb.inj_count;
+    la.inj_index = lb.inj_count > 0 ? lb.inj_index.p : nullptr;
+    la.inj_bars = lb.inj_count > 0 ? lb.inj_bars.p + pos0 * lb.inj_count * S * md : nullptr;
+    return la;
+}
+
+// (per-member rates: kernels of their own, qocx_lindblad_rates.hip / qocx_lindblad4t_rates.hip, whose workgroup i
+// reads the tables of member item_member[i]: behind the order, in launch order)
+void launch_lindblad_piece(qocx_ctx* ctx, const LindbladLaunch& ev, const qocx::LindbladArgs& args,
+                           const LindbladPiece& pc, hipStream_t st) {
+    auto& lb = ctx->lb;
+    time_begin(ctx, 5, st);
+    if (lb.ens_rates) {
+        qocx::LindbladMembers mem = ev.mem;
+        mem.item_member = lb.order_dev.p + lb.order.size() + pc.first;
+        qocx::launch_lindblad_rates(args, mem, pc.count, st);
+    } else qocx::launch_lindblad(args, pc.count, st);
+    time_end(ctx, st);
+}
+
+// Two-sided: forward pass and unit adjoint as two launches, then the combine kernel on the whole chip.
+// While both launches find CUs of their own they run on two streams (2 Bp CUs busy instead of Bp); a
+// bigger piece runs them one after the other - the same three kernels, so a seed's result does not depend
+// on the batch it is part of. Then, for a sweep that asked, the rate sensitivities of the piece.
+int launch_two_sided(qocx_ctx* ctx, const LindbladLaunch& ev, qocx::LindbladArgs la, const LindbladPiece& pc) {
+    auto& lb = ctx->lb;
+    hipStream_t side = pc.count <= ev.side_limit ? ctx->sweep_streams[0] : ctx->stream;
+    la.kbstages = lb.kbstages.p;
+    la.lam_scale = lb.lam_scale.p + (size_t)pc.first * lb.S;
+    // everything enqueued so far (uploads, earlier pieces that reuse the stage buffers)
+    if (side != ctx->stream) {
+        HIP_TRY(hipEventRecord(ctx->ev_factored[0], ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(side, ctx->ev_factored[0], 0));
+    }
+    qocx::LindbladArgs fwd = la, adj = la;
+    fwd.phase = 1; adj.phase = 2;
+    fwd.q2 = adj.q2 = ev.q2; fwd.chain = adj.chain = ev.chain; fwd.ops_real = adj.ops_real = ev.ops_real;
+    if (la.stamps != nullptr) adj.stamps = la.stamps + lb.order.size() * 48;
+    launch_lindblad_piece(ctx, ev, fwd, pc, ctx->stream);
+    launch_lindblad_piece(ctx, ev, adj, pc, side);
+    if (side != ctx->stream) {
+        HIP_TRY(hipEventRecord(ctx->ev_swept[0], side));
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_swept[0], 0));
+    }
+    time_begin(ctx, 6, ctx->stream);
+    qocx::launch_lindblad_combine(la, pc.count, ctx->stream);
+    time_end(ctx, ctx->stream);
+    if (lb.swp_rates_ok) {
+        // on the stream of the forward launches, so before the next piece's (and, through
+        // ev_factored, before its adjoint's on the side stream): they reuse the stage buffers
+        qocx::RateSensArgs rs;
+        rs.ldl_cimg = lb.swp_ldl.p; rs.gammas = lb.gammas.p; rs.nops = lb.nops;
+        rs.partials = lb.swp_rate_partials.p + ev.rate_off;
+        rs.out = lb.swp_rate_sens.p + (size_t)pc.first * lb.nops;
+        qocx::launch_lindblad_ratesens(la, rs, pc.count, ctx->stream);
+    }
+    return 0;
+}
+
+// The launches piece by piece, as the plan lists them: results in lb.cost_out / grads / final_out in group
 // order. The controls are in lb.controls, in group order, on ctx->stream before this.
 int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& plan) {
     auto& lb = ctx->lb;
-    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, nsteps = lb.nsteps, B = (int)lb.order.size();
+    const int n = lb.n, S = lb.S, K = lb.K, nc = lb.nc, B = (int)lb.order.size();
     const size_t md = dump_elems(n), csz = (size_t)nc * K;
-    const size_t stage_budget = plan.stage_budget;
-    const bool two_sided_ok = plan.two_sided_ok;
-    const bool two_sided_tiles = plan.two_sided_tiles;
-    if (lb.inj_count > 0) {
-        if (lb.inj_batch != B)
-            return fail(QOCX_ERR_STATE, "density cotangents were set for a different batch size");
-        std::vector<int> index(nsteps + 1, -1);
-        for (int c = 0; c < lb.inj_count; ++c) index[lb.inj_steps[c]] = c;
-        const size_t per_seed = (size_t)lb.inj_count * S;
-        std::vector<double2> dumps((size_t)B * per_seed * md);
-        for (int pos = 0; pos < B; ++pos)
-            for (size_t v = 0; v < per_seed; ++v) {
-                cmat m(lb.inj_host.begin() + (((size_t)lb.order[pos] * per_seed + v) * n * n * 2),
-                       lb.inj_host.begin() + (((size_t)lb.order[pos] * per_seed + v + 1) * n * n * 2));
-                c_dump(m, n, dumps.data() + ((size_t)pos * per_seed + v) * md);
-            }
-        if (lb.inj_index.upload(index, ctx->stream) || lb.inj_bars.upload(dumps, ctx->stream))
-            return QOCX_ERR_HIP;
-    }
+    if (int rc = lb.inj_count > 0 ? upload_density_cotangents(ctx) : 0) return rc;
     // Rate sensitivities of a sweep (qocx_lindblad_sweep_want_rate_sensitivities): a launch of
     // qocx_lindblad_ratesens.hip behind every piece's combine launch; a piece that does not run two-sided
     // (or a problem with more than four operators) leaves the evaluation without them.
-    const int rate_ops = lb.nops;
     // (a duration search asks for them in every evaluation with gradients: dE/dtau needs its rate part)
     const bool want_rates = lb.seeds.swp_B > 0 && (lb.swp_want_rates || lb.seeds.dur.set) && want_grad;
-    lb.swp_rates_ok = want_rates && rate_ops >= 1 && rate_ops <= 4;
-    if (lb.swp_rates_ok && (lb.swp_rate_partials.ensure((size_t)lb.last_subintervals * rate_ops) ||
-                            lb.swp_rate_sens.ensure((size_t)B * rate_ops)))
+    lb.swp_rates_ok = want_rates && lb.nops >= 1 && lb.nops <= 4;
+    if (lb.swp_rates_ok && (lb.swp_rate_partials.ensure((size_t)lb.last_subintervals * lb.nops) ||
+                            lb.swp_rate_sens.ensure((size_t)B * lb.nops)))
         return QOCX_ERR_HIP;
-    size_t pos0 = 0, ckpt_off = 0, gsub_off = 0, rate_off = 0;
-    for (auto& kv : plan.groups) {
-        const auto& gr = lb.grids[kv.first];
-        const int Bg = (int)kv.second.size(), nsub = gr.nsub;
-        const size_t per_seed_stage = (size_t)nsub * S * md * 12;
-        int piece = Bg;
-        bool keep_stages = false;
+    LindbladLaunch ev;
+    ev.want_grad = want_grad;
+    ev.tile4 = ctx->knob("lindblad_4t", 1) != 0 ? 1 : 0;
+    ev.hermitian = (lb.hermitian && lb.inj_count == 0 && ctx->knob("lindblad_hermitian", 1) != 0) ? 1 : 0;
+    ev.q2 = ctx->knob("lindblad_q2", 1) != 0 ? 1 : 0; ev.chain = ctx->knob("lindblad_chain", 1) != 0 ? 1 : 0;
+    ev.ops_real = (lb.ops_real && ctx->knob("lindblad_real_ops", 1) != 0) ? 1 : 0;
+    ev.side_limit = (int)ctx->knob("lindblad_side_limit", ctx->cu_count / 2);
+    ev.stamps = ctx->knob("lindblad_stamps", 0) != 0;
+    ev.mem.a0_stride = 4 * md; ev.mem.gamma_stride = lb.gammas_h.size();
+    if (ev.stamps) {  // the whole buffer once: a piece's launches stamp only their own seeds' sets
+        if (ctx->stamps.ensure((size_t)B * 96)) return QOCX_ERR_HIP;
+        HIP_TRY(hipMemsetAsync(ctx->stamps.p, 0, (size_t)B * 96 * sizeof(unsigned long long), ctx->stream));
+    }
+    ev.two_sided = plan.two_sided_ok;
+    if (ev.two_sided && n > 16 && !plan.pieces.empty()) {
+        // above one tile only the tile-per-wave kernel knows the phases: ask IT whether it takes these
+        // launches (the one-wave form would run the whole evaluation twice). Its answer reads nothing that
+        // differs between the pieces that ask - those that keep their stage values, in the one buffer.
+        qocx::LindbladArgs probe = lindblad_piece_args(ctx, ev, plan.pieces[0]);
+        probe.phase = 1; probe.ystages = lb.ystages.p;
+        ev.two_sided = qocx::lindblad4t_supports(probe);
+    }
+    for (const LindbladPiece& pc : plan.pieces) {
+        const auto& gr = lb.grids[pc.ksub];
+        const qocx::LindbladArgs la = lindblad_piece_args(ctx, ev, pc);
+        if (ev.two_sided && pc.keep_stages && (pc.multi_wave || plan.two_sided_tiles)) {
+            if (int rc = launch_two_sided(ctx, ev, la, pc)) return rc;
+        } else {
+            lb.swp_rates_ok = false;
+            launch_lindblad_piece(ctx, ev, la, pc, ctx->stream);
+        }
         if (want_grad) {
-            const size_t fit = lb.dbg_stage_seeds > 0
-                                   ? (size_t)lb.dbg_stage_seeds
-                                   : std::max<size_t>(1, stage_budget / per_seed_stage);
-            if (fit >= (size_t)Bg) { keep_stages = true; }
-            else if (fit >= (size_t)lb.dbg_min_piece) { keep_stages = true; piece = (int)fit; }
+            qocx::ScatterArgs sc;
+            sc.gstep = la.gsub; sc.row_ptr = gr.row_ptr.p; sc.col_step = gr.col.p;
+            sc.weight = gr.weight.p; sc.grads = lb.grads.p + (size_t)pc.first * csz;
+            sc.B = pc.count; sc.nc = nc; sc.K = K; sc.nsteps = 2 * gr.nsub;
+            time_begin(ctx, 3, ctx->stream);
+            qocx::launch_scatter(sc, ctx->stream);
+            time_end(ctx, ctx->stream);
         }
-        // Several waves per seed (one seed per CU) whenever the kernel is built for this problem;
-        // batches beyond the CU count go in rounds of one seed per CU. (Round 1 switched to one wave
-        // per seed, two seeds per CU, beyond 256 seeds; measured on configs[3] at 300 / 512 / 768 /
-        // 1024 seeds: 73.7 / 80.7 / 126.6 / 123.7 ms against 74.4 / 76.6 / 82.7 / 104.8 ms in rounds.)
-        bool multi = lb.multi_wave != 0;
-        if (lb.dbg_wave_mode == 1) multi = false;
-        if (multi && lb.dbg_wave_mode != 2) piece = std::min(piece, ctx->cu_count);
-        for (int p0 = 0; p0 < Bg; p0 += piece) {
-            const int Bp = std::min(piece, Bg - p0);
-            qocx::LindbladArgs la;
-            la.controls = lb.controls.p + pos0 * csz; la.substeps = gr.substeps.p;
-            la.a0l_cimg = lb.a0l.p; la.a0r_cimg = lb.a0r.p; la.a0ld_cimg = lb.a0ld.p; la.a0rd_cimg = lb.a0rd.p;
-            la.gp_cimg = lb.gp.p; la.gpd_cimg = lb.gpd.p; la.gpt_cimg = lb.gpt.p; la.op_cimg = lb.ops.p;
-            la.gammas = lb.gammas.p; la.rho0_cimg = lb.rho0.p;
-            qocx::LindbladMembers mem;
-            if (lb.ens_rates) {
-                // per-member rates: workgroup i of this launch reads the tables of member item_member[i]
-                mem.item_member = lb.order_dev.p + B + pos0;
-                la.a0l_cimg = lb.rate_a0.p; la.a0r_cimg = lb.rate_a0.p + md;
-                la.a0ld_cimg = lb.rate_a0.p + 2 * md; la.a0rd_cimg = lb.rate_a0.p + 3 * md;
-                la.gammas = lb.rate_gammas.p;
-                mem.a0_stride = 4 * md;
-                mem.gamma_stride = lb.gammas_h.size();
-            }
-            // (kernels of their own behind the member table: qocx_lindblad_rates.hip, qocx_lindblad4t_rates.hip)
-            auto launch = [&](const qocx::LindbladArgs& args, hipStream_t st) {
-                if (lb.ens_rates) qocx::launch_lindblad_rates(args, mem, Bp, st);
-                else qocx::launch_lindblad(args, Bp, st);
-            };
-            la.a0_tab = lb.fixed_ksub > 0 ? lb.a0_tab.p : nullptr;
-            la.gp_tab = (lb.fixed_ksub > 0 && lb.gp_tab.p) ? lb.gp_tab.p : nullptr;
-            la.op_tab = (lb.fixed_ksub > 0 && lb.op_tab.p) ? lb.op_tab.p : nullptr;
-            la.gamma_tab = la.op_tab ? lb.gamma_tab.p : nullptr;
-            la.n = n; la.S = S; la.K = K; la.nc = nc; la.nops = (multi && lb.pad_op) ? 2 : lb.nops; la.nsub = nsub;
-            la.nsteps = nsteps;
-            la.cost_eval_step = lb.ces; la.want_grad = want_grad; la.has_step_costs = lb.has_step_costs;
-            la.cost_count = lb.cost_count; la.costs = lb.costs.p; la.cost_matrices = lb.cost_matrices.p;
-            la.cost_counts = lb.cost_counts.p;
-            la.checkpoints = lb.checkpoints.p + ckpt_off; la.gsub = lb.gsub.p + gsub_off;
-            la.ystages = keep_stages ? lb.ystages.p : nullptr;  // reused piece after piece
-            la.scratch = lb.global_scratch ? lb.scratch.p : nullptr;  // likewise
-            // several waves per seed shorten a seed's serial chain by ~1.4x but hold one seed
-            // per CU instead of two: worth it while the batch leaves CUs idle
-            la.multi_wave = multi ? 1 : 0;
-            la.cache_gen = (la.multi_wave && lb.cache_gen) ? 1 : 0;
-            la.cost_out = lb.cost_out.p + pos0;
-            la.final_out = lb.final_out.p + pos0 * S * md;
-            la.step_densities = ctx->keep_step_states
-                                    ? lb.step_densities.p + pos0 * (nsteps + 1) * S * md : nullptr;
-            la.tile4 = ctx->knob("lindblad_4t", 1) != 0 ? 1 : 0;
-            la.hermitian = (lb.hermitian && lb.inj_count == 0 && ctx->knob("lindblad_hermitian", 1) != 0) ? 1 : 0;
-            la.stamps = nullptr;
-            if (ctx->knob("lindblad_stamps", 0)) {
-                // ([B] sets of the forward pass / classic launch, then [B] of the unit adjoint)
-                if (ctx->stamps.ensure((size_t)B * 96)) return QOCX_ERR_HIP;
-                HIP_TRY(hipMemsetAsync(ctx->stamps.p, 0, (size_t)B * 96 * sizeof(unsigned long long),
-                                       ctx->stream));
-                la.stamps = ctx->stamps.p + pos0 * 48;
-            }
-            la.inj_count = lb.inj_count;
-            la.inj_index = lb.inj_count > 0 ? lb.inj_index.p : nullptr;
-            la.inj_bars = lb.inj_count > 0 ? lb.inj_bars.p + pos0 * lb.inj_count * S * md : nullptr;
-            // Two-sided: forward pass and unit adjoint as two launches, then the combine kernel on
-            // the whole chip. While both launches find CUs of their own they run on two streams
-            // (2 Bp CUs busy instead of Bp); a bigger piece runs them one after the other - the
-            // same three kernels, so a seed's result does not depend on the batch it is part of.
-            bool two_sided = two_sided_ok && keep_stages && (multi || two_sided_tiles);
-            if (two_sided && n > 16) {
-                // above one tile only the tile-per-wave kernel knows the phases: ask IT whether it
-                // takes these launches (the one-wave form would run the whole evaluation twice)
-                qocx::LindbladArgs probe = la;
-                probe.phase = 1;
-                probe.kbstages = lb.kbstages.p;
-                if (!qocx::lindblad4t_supports(probe)) two_sided = false;
-            }
-            if (two_sided) {
-                const int side_limit = (int)ctx->knob("lindblad_side_limit", ctx->cu_count / 2);
-                hipStream_t side = Bp <= side_limit ? ctx->sweep_streams[0] : ctx->stream;
-                la.kbstages = lb.kbstages.p;
-                la.lam_scale = lb.lam_scale.p + pos0 * S;
-                // everything enqueued so far (uploads, earlier pieces that reuse the stage buffers)
-                if (side != ctx->stream) {
-                    HIP_TRY(hipEventRecord(ctx->ev_factored[0], ctx->stream));
-                    HIP_TRY(hipStreamWaitEvent(side, ctx->ev_factored[0], 0));
-                }
-                qocx::LindbladArgs fwd = la, adj = la;
-                fwd.phase = 1;
-                adj.phase = 2;
-                fwd.q2 = adj.q2 = ctx->knob("lindblad_q2", 1) != 0 ? 1 : 0;
-                fwd.chain = adj.chain = ctx->knob("lindblad_chain", 1) != 0 ? 1 : 0;
-                fwd.ops_real = adj.ops_real = (lb.ops_real && ctx->knob("lindblad_real_ops", 1) != 0) ? 1 : 0;
-                if (la.stamps != nullptr) adj.stamps = la.stamps + (size_t)B * 48;
-                time_begin(ctx, 5, ctx->stream);
-                launch(fwd, ctx->stream);
-                time_end(ctx, ctx->stream);
-                time_begin(ctx, 5, side);
-                launch(adj, side);
-                time_end(ctx, side);
-                if (side != ctx->stream) {
-                    HIP_TRY(hipEventRecord(ctx->ev_swept[0], side));
-                    HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_swept[0], 0));
-                }
-                time_begin(ctx, 6, ctx->stream);
-                qocx::launch_lindblad_combine(la, Bp, ctx->stream);
-                time_end(ctx, ctx->stream);
-                if (lb.swp_rates_ok) {
-                    // on the stream of the forward launches, so before the next piece's (and, through
-                    // ev_factored, before its adjoint's on the side stream): they reuse the stage buffers
-                    qocx::RateSensArgs rs;
-                    rs.ldl_cimg = lb.swp_ldl.p; rs.gammas = lb.gammas.p; rs.nops = rate_ops;
-                    rs.partials = lb.swp_rate_partials.p + rate_off;
-                    rs.out = lb.swp_rate_sens.p + pos0 * rate_ops;
-                    qocx::launch_lindblad_ratesens(la, rs, Bp, ctx->stream);
-                }
-            } else {
-                lb.swp_rates_ok = false;
-                time_begin(ctx, 5, ctx->stream);
-                launch(la, ctx->stream);
-                time_end(ctx, ctx->stream);
-            }
-            if (want_grad) {
-                qocx::ScatterArgs sc;
-                sc.gstep = la.gsub; sc.row_ptr = gr.row_ptr.p; sc.col_step = gr.col.p;
-                sc.weight = gr.weight.p; sc.grads = lb.grads.p + pos0 * csz;
-                sc.B = Bp; sc.nc = nc; sc.K = K; sc.nsteps = 2 * nsub;
-
-                time_begin(ctx, 3, ctx->stream);
-                qocx::launch_scatter(sc, ctx->stream);
-                time_end(ctx, ctx->stream);
-            }
-            pos0 += Bp;
-            ckpt_off += (size_t)Bp * nsub * S * md;
-            gsub_off += (size_t)Bp * nsub * 2 * std::max(K, 1);
-            rate_off += (size_t)Bp * nsub * rate_ops;
-        }
+        ev.ckpt_off += (size_t)pc.count * gr.nsub * S * md;
+        ev.gsub_off += (size_t)pc.count * gr.nsub * 2 * std::max(K, 1);
+        ev.rate_off += (size_t)pc.count * gr.nsub * lb.nops;
     }
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// An evaluation of `items` control arrays [items][nc][K] on the device (umax as lindblad_subdivisions takes
+// it): the plan, the order uploaded, the controls gathered into group order (the device-side form of
+// qocx_eval_lindblad's staging copy), the launches. Results in lb.cost_out / grads / final_out in group order.
+int lindblad_launch_items(qocx_ctx* ctx, int items, const double* controls, const double* umax, int want_grad) {
+    auto& lb = ctx->lb;
+    std::vector<int> ksub_of;
+    LindbladPlan plan;
+    if (int rc = lindblad_subdivisions(ctx, items, umax, ksub_of)) return rc;
+    if (int rc = lindblad_plan(ctx, want_grad, ksub_of, plan)) return rc;
+    std::vector<int> table(lb.order);
+    // per-member rates, behind the order: every launched item's member (item_member; a sweep: the seed itself)
+    for (int i = 0; lb.ens_rates && i < items; ++i)
+        table.push_back(lb.seeds.swp_B > 0 ? lb.order[i] : lb.order[i] % lb.seeds.M);
+    if (lb.order_dev.upload(table, ctx->stream)) return QOCX_ERR_HIP;
+    qocx::launch_gather_seeds(controls, lb.controls.p, (size_t)lb.nc * lb.K, lb.order_dev.p, items, ctx->stream);
+    return lindblad_launch_groups(ctx, want_grad, plan);
+}
+
+// Cost [B], gradients [B][csz], final dumps [B][dens] of B seeds into the caller's arrays (each optional), un-dumped
+int download_seed_results(qocx_ctx* ctx, int B, size_t csz, size_t dens, const double* cost, const double* grads,
+                          const double2* finals, double* cost_out, double* grad_out, double* final_out) {
+    const size_t n = ctx->lb.n, md = dump_elems(ctx->lb.n);
+    std::vector<double2> fin(final_out ? (size_t)B * dens * md : 0);
+    if (cost_out)
+        HIP_TRY(hipMemcpyAsync(cost_out, cost, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_out)
+        HIP_TRY(hipMemcpyAsync(grad_out, grads, (size_t)B * csz * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (final_out)
+        HIP_TRY(hipMemcpyAsync(fin.data(), finals, fin.size() * sizeof(double2), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t v = 0; final_out && v < (size_t)B * dens; ++v)
+        from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
     return 0;
 }
 
@@ -1185,7 +1232,7 @@ int lindblad_duration_finish(qocx_ctx* ctx, int want_grad, double* cost) {
     if (!lb.seeds.dur.set) return 0;
     lb.seeds.dur.have_grad = false;
     if (want_grad && !lb.swp_rates_ok) {
-        lb.have_results = lb.res_have_results = lb.swp_have_grads = false;
+        lb.drop_results();
         return fail(QOCX_ERR_STATE,
                     "a duration search (qocx_lindblad_sweep_set_durations) needs the rate sensitivities in every "
                     "evaluation with gradients, and a piece of this one did not run two-sided: that takes ONE "
@@ -1232,22 +1279,8 @@ int lindblad_ensemble_launch(qocx_ctx* ctx, int seeds, const double* seed_contro
     lb.swp_have_grads = false;
     std::vector<double> item_umax;
     if (umax) item_umax = lindblad_item_maxima(lb, seeds, umax);
-    std::vector<int> ksub_of;
-    LindbladPlan plan;
-    int rc = lindblad_subdivisions(ctx, items, umax ? item_umax.data() : nullptr, ksub_of);
-    if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
-    if (rc) return rc;
-    if (lb.ens_rates) {
-        // behind the order: the member of every launched item, in launch order (LindbladMembers::item_member)
-        std::vector<int> both(lb.order);
-        // (a sweep: the launched seed's own index)
-        for (int i = 0; i < items; ++i) both.push_back(swp ? lb.order[i] : lb.order[i] % lb.seeds.M);
-        if (lb.order_dev.upload(both, ctx->stream)) return QOCX_ERR_HIP;
-    } else if (lb.order_dev.upload(lb.order, ctx->stream)) {
-        return QOCX_ERR_HIP;
-    }
-    qocx::launch_gather_seeds(lb.ens_items.p, lb.controls.p, csz, lb.order_dev.p, items, ctx->stream);
-    if (int rc2 = lindblad_launch_groups(ctx, want_grad, plan)) return rc2;
+    if (int rc = lindblad_launch_items(ctx, items, lb.ens_items.p, umax ? item_umax.data() : nullptr, want_grad))
+        return rc;
     lb.swp_have_grads = swp && want_grad;
     return 0;
 }
@@ -1276,8 +1309,8 @@ int lindblad_ensemble_reduce(qocx_ctx* ctx, int seeds, int want_grad, double* co
 int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int want_grad, double* cost_out,
                            double* grad_out, double* final_out) {
     auto& lb = ctx->lb;
-    const int n = lb.n, S = lb.S, Kr = lb.seeds.Kr, nc = lb.nc, M = lb.seeds.M;
-    const size_t csz = (size_t)nc * Kr, md = dump_elems(n);
+    const int S = lb.S, Kr = lb.seeds.Kr, nc = lb.nc, M = lb.seeds.M;
+    const size_t csz = (size_t)nc * Kr, md = dump_elems(lb.n);
     if (!controls) return fail(QOCX_ERR_ARG, "controls is NULL");
     if ((int64_t)B * M > 0x7fffffff) return fail(QOCX_ERR_ARG, "seeds x ensemble members must fit in int32");
     const size_t items = (size_t)B * M;
@@ -1296,23 +1329,11 @@ int eval_lindblad_ensemble(qocx_ctx* ctx, int B, const double* controls, int wan
     if (!rc) rc = lindblad_ensemble_reduce(ctx, B, want_grad, lb.ens_seed_cost.p, lb.ens_seed_grads.p, lb.ens_final.p);
     if (!rc) rc = lindblad_duration_finish(ctx, want_grad, lb.ens_seed_cost.p);
     if (rc) return rc;
-    std::vector<double2> fin(final_out ? items * S * md : 0);
-    if (cost_out)
-        HIP_TRY(hipMemcpyAsync(cost_out, lb.ens_seed_cost.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    if (want_grad && grad_out)
-        HIP_TRY(hipMemcpyAsync(grad_out, lb.ens_seed_grads.p, (size_t)B * csz * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    if (final_out)
-        HIP_TRY(hipMemcpyAsync(fin.data(), lb.ens_final.p, fin.size() * sizeof(double2), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (int rc3 = download_seed_results(ctx, B, csz, (size_t)M * S, lb.ens_seed_cost.p, lb.ens_seed_grads.p,
+                                        lb.ens_final.p, cost_out, want_grad ? grad_out : nullptr, final_out))
+        return rc3;
     time_collect(ctx);
-    if (final_out)
-        for (size_t v = 0; v < items * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
-    lb.B = (int)items;
-    lb.have_results = true;
-    lb.have_steps = ctx->keep_step_states != 0;
+    lb.results_stand((int)items, ctx->keep_step_states != 0);
     return 0;
 }
 
@@ -1408,10 +1429,7 @@ int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const do
     lindblad_duration_mirror(ctx);
     lb.seeds.dur.set = true;
     lb.seeds.dur.have_grad = false;
-    lb.have_results = false;
-    lb.swp_have_grads = false;
-    lb.res_B = lb.ms.batch = 0;  // controls must be uploaded again, and the driver begun again
-    lb.res_have_results = false;
+    lb.drop_resident();  // controls must be uploaded again, and the driver begun again
     return 0;
 }
 
@@ -1493,9 +1511,7 @@ int qocx_eval_lindblad(qocx_ctx* ctx, int32_t batch, const double* controls, int
                 from_c_dump(fin.data() + ((size_t)pos * S + s) * md, n,
                             final_out + ((size_t)b * S + s) * n * n * 2);
     }
-    lb.B = B;
-    lb.have_results = true;
-    lb.have_steps = ctx->keep_step_states != 0;
+    lb.results_stand(B, ctx->keep_step_states != 0);
     return 0;
 }
 
@@ -1568,9 +1584,8 @@ int qocx_lindblad_upload_controls(qocx_ctx* ctx, int32_t batch, const double* co
     // the host has these controls: their maxima cost nothing here and spare eval_resident a round trip
     lb.umax_host.assign((size_t)batch * Ks, 0.0);
     lindblad_control_maxima(controls, batch, lb.nc, Ks, lb.umax_host.data());
-    lb.umax_valid = true;
     lb.res_B = batch;
-    lb.res_have_results = false;
+    lb.resident_controls_moved(true);
     lb.swp_have_grads = false;  // (the seed controls of the last evaluation may just have been overwritten)
     return 0;
 }
@@ -1619,16 +1634,7 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
         if (!rc) rc = lindblad_ensemble_reduce(ctx, B, want_grad, lb.res_cost.p, lb.res_grads.p, lb.res_final.p);
         if (rc) return rc;
     } else {
-        std::vector<int> ksub_of;
-        LindbladPlan plan;
-        int rc = lindblad_subdivisions(ctx, B, umax, ksub_of);
-        if (!rc) rc = lindblad_plan(ctx, want_grad, ksub_of, plan);
-        if (rc) return rc;
-        if (lb.order_dev.upload(lb.order, ctx->stream)) return QOCX_ERR_HIP;
-        // seed order -> group order: the device-side form of qocx_eval_lindblad's staging copy
-        qocx::launch_gather_seeds(lb.res_controls.p, lb.controls.p, csz, lb.order_dev.p, B, ctx->stream);
-        rc = lindblad_launch_groups(ctx, want_grad, plan);
-        if (rc) return rc;
+        if (int rc = lindblad_launch_items(ctx, B, lb.res_controls.p, umax, want_grad)) return rc;
         qocx::launch_scatter_seeds(lb.cost_out.p, lb.res_cost.p, want_grad ? lb.grads.p : nullptr,
                                    lb.res_grads.p, csz, lb.final_out.p, lb.res_final.p, (size_t)S * md,
                                    lb.order_dev.p, B, ctx->stream);
@@ -1647,9 +1653,7 @@ int qocx_eval_lindblad_resident(qocx_ctx* ctx, int32_t want_grad) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         time_collect(ctx);
     }
-    lb.B = B * (int)items;
-    lb.have_results = true;
-    lb.have_steps = ctx->keep_step_states != 0;
+    lb.results_stand(B * (int)items, ctx->keep_step_states != 0);
     lb.res_have_results = true;
     lb.res_have_grads = want_grad != 0;
     return 0;
@@ -1662,22 +1666,8 @@ int qocx_lindblad_download_results(qocx_ctx* ctx, double* cost_out, double* grad
     if (grad_out && !lb.res_have_grads) return fail(QOCX_ERR_STATE, "the last evaluation had no gradients");
     HIP_TRY(hipSetDevice(ctx->device));
     // (with an ensemble: the seeds' K_r channels, the final densities of every item)
-    const int B = lb.res_B, S = lb.S * (int)lb.seed_items(), n = lb.n;
-    const size_t csz = (size_t)lb.nc * lb.seed_channels(), md = dump_elems(n);
-    if (cost_out)
-        HIP_TRY(hipMemcpyAsync(cost_out, lb.res_cost.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    if (grad_out)
-        HIP_TRY(hipMemcpyAsync(grad_out, lb.res_grads.p, (size_t)B * csz * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<double2> fin(final_out ? (size_t)B * S * md : 0);
-    if (final_out)
-        HIP_TRY(hipMemcpyAsync(fin.data(), lb.res_final.p, fin.size() * sizeof(double2), hipMemcpyDeviceToHost,
-                               ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (final_out)
-        for (size_t v = 0; v < (size_t)B * S; ++v) from_c_dump(fin.data() + v * md, n, final_out + v * n * n * 2);
-    return 0;
+    return download_seed_results(ctx, lb.res_B, (size_t)lb.nc * lb.seed_channels(), lb.S * lb.seed_items(),
+                                 lb.res_cost.p, lb.res_grads.p, lb.res_final.p, cost_out, grad_out, final_out);
 }
 
 int qocx_lindblad_download_costs(qocx_ctx* ctx, double* cost_out) {

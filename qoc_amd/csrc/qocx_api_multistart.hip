@@ -647,8 +647,7 @@ int qocx_lindblad_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // max_norms is the caller's memory
-    lb.umax_valid = maxima;
-    lb.res_have_results = false;
+    lb.resident_controls_moved(maxima);
     if (lb.seeds.dur.set) lindblad_duration_mirror(ctx);
     return 0;
 }
@@ -673,8 +672,7 @@ int qocx_lindblad_opt_step(qocx_ctx* ctx, int32_t kind, const uint8_t* improved,
     lb.seeds.dur.have_grad = false;
     // (tau has moved: the tables are rewritten by the clip, or before the next evaluation)
     lb.seeds.dur.mirror_stale = lb.seeds.dur.set;
-    lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
-    lb.umax_valid = false;
+    lb.resident_controls_moved(false);  // ... and are no longer those of the last evaluation
     return 0;
 }
 
@@ -704,8 +702,7 @@ int qocx_lindblad_opt_lbfgs_step(qocx_ctx* ctx, const uint8_t* improved, const u
     const LbfgsRule rule{first_step, armijo, shrink, max_backtracks};
     if (int rc = multistart_lbfgs_step(ctx, lb.ms, lindblad_seeds(ctx), rule, improved, update, finished_out))
         return rc;
-    lb.res_have_results = false;  // the resident controls are no longer those of the last evaluation
-    lb.umax_valid = false;
+    lb.resident_controls_moved(false);  // ... and are no longer those of the last evaluation
     return 0;
 }
 

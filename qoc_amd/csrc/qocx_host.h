@@ -302,7 +302,7 @@ struct qocx_ctx {
     DevBuf<int> inj_index;
     DevBuf<double2> inj_bars;
     struct Lindblad {
-        bool has_problem = false, have_results = false, have_grads = false, have_steps = false;
+        bool has_problem = false;
         int n = 0, S = 0, K = 0, nc = 0, N = 0, nsteps = 0, ces = 1, nops = 0;
         double T = 0, dt = 0, h0_norm = 0, diss_norm = 0, l0_norm = 0;
         bool pwc = false;  // set piecewise constant: nc slices, sub-intervals cut at j T / nc
@@ -323,6 +323,18 @@ struct qocx_ctx {
         // per evaluation
         int B = 0;
         std::vector<int> order;  // device position -> seed
+        // What stands of the last evaluation: set where a result comes about, cleared by these functions alone.
+        bool have_results = false, have_steps = false;
+        void results_stand(int items, bool kept_steps) { B = items; have_results = true; have_steps = kept_steps; }
+        // the resident controls moved (clip, step, upload): only the resident results are no longer theirs
+        void resident_controls_moved(bool maxima_known) { res_have_results = false; umax_valid = maxima_known; }
+        // a setter changed what an evaluation means: nothing of the last one stands
+        void drop_results() {
+            have_results = have_steps = res_have_results = res_have_grads = swp_have_grads = swp_rates_ok = false;
+            swp_seed_controls = nullptr; ens_members_B = 0;
+        }
+        // ... nor does the resident batch: controls must be uploaded again, and the driver begun again
+        void drop_resident() { drop_results(); res_B = ms.batch = 0; umax_valid = false; }
         // host-supplied density cotangents
         int inj_count = 0, inj_batch = 0;
         std::vector<int> inj_steps;
