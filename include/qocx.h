@@ -595,6 +595,13 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   2: as 1, and the same problems at 33 <= n <= 64 too (qocx_action4.hip: workgroups
  *                   of three / four waves). Opt-in: above n = 32 the values 0 and 1 launch exactly
  *                   what they always launched.
+ *   "action_states" 0 (default): the matrix-free route takes one state per seed only. 2 .. 4
+ *                   (QOCX_ACTION_MAX_STATES): the most states per seed that take it at 17 <= n <= 32,
+ *                   where "action" admits the problem and the one cost is a COHERENT final
+ *                   TargetStateInfidelity (one scalar for every state): a wave per state, the states'
+ *                   generator cotangents summed before one contraction (qocx_action_states.hip). Any
+ *                   other value is QOCX_ERR_ARG. Opt-in: at 0 every problem launches what it always
+ *                   launched. n <= 16 and the wide route of "action" = 2 stay one-state.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;

@@ -23,6 +23,14 @@ def make_backend(device=-1):
 
 _FD_STEP = 1e-6
 
+# matrix_free="states" / "all": the most states per seed that take the matrix-free route (the engine's
+# knob "action_states"). The engine accepts up to 4; this is the largest count at which the route's median
+# evaluation was below the Pade route's fastest one in every run (n = 32, 256 seeds x 1000 steps: 10.9 ms
+# against 11.3 at two states, 18.4 against 13.5 at three - tools/bench_action_states.py,
+# profiles/action_states.jsonl).
+ACTION_STATES_DEFAULT = 2
+MATRIX_FREE_VALUES = ("default", "wide", "states", "all")
+
 
 def interpolation_keywords(backend, setter, interpolation_policy):
     """The keyword a backend's problem setter takes for `interpolation_policy`: none for LINEAR
@@ -587,8 +595,12 @@ class SchroedingerEvaluator(_Evaluator):
         matrix_free: "default" leaves the engine's route decision as it is (matrix-free Taylor
         sweeps for one-state Hermitian problems at 17 <= n <= 32, knob "action" untouched); "wide"
         also takes them at 33 <= n <= 64 (knob "action" = 2 on a backend with set_knob; opt-in
-        because the default route there is what existing callers measure and assert on). A backend
-        without knobs ignores it; any other value is a ValueError.
+        because the default route there is what existing callers measure and assert on); "states"
+        also takes them for 2 .. ACTION_STATES_DEFAULT states per seed at 17 <= n <= 32 under one
+        coherent final TargetStateInfidelity (knob "action_states"; a wave per state, opt-in for the
+        same reason); "all" asks for both. A problem of that many states asked for with "states" or
+        "all" is not put into latency mode, which the route yields to. A backend without knobs
+        ignores it; any other value is a ValueError.
         latency_mode: the evaluator will be asked for ONE control array at a time (the
         reference's evolve_* / grape_* entry points). Where the cost is a single final
         TargetStateInfidelity the engine then runs its two-sided pipeline (round 3: forward and
@@ -606,8 +618,8 @@ class SchroedingerEvaluator(_Evaluator):
         self.interpolation_policy = interpolation_policy
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
-        if not (isinstance(matrix_free, str) and matrix_free in ("default", "wide")):
-            raise ValueError("matrix_free must be \"default\" or \"wide\", not {!r}."
+        if not (isinstance(matrix_free, str) and matrix_free in MATRIX_FREE_VALUES):
+            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\" or \"all\", not {!r}."
                              .format(matrix_free))
         self.matrix_free = matrix_free
         initial_states = np.asarray(initial_states)
@@ -717,11 +729,16 @@ class SchroedingerEvaluator(_Evaluator):
             g = self._append_perturbations(g)
         self.backend = backend if backend is not None else make_backend()
         if hasattr(self.backend, "set_knob"):
+            states = matrix_free in ("states", "all")
+            if states and 2 <= self.state_count <= ACTION_STATES_DEFAULT:
+                latency_mode = False  # (the route asked for yields to it)
             self.backend.set_knob(
                 "sweep_impl", 3 if (latency_mode and 16 < self.hilbert_size <= 32) else 1)
             self.backend.set_knob("latency", 1 if latency_mode else 0)
-            if matrix_free == "wide":
+            if matrix_free in ("wide", "all"):
                 self.backend.set_knob("action", 2)
+            if states:
+                self.backend.set_knob("action_states", ACTION_STATES_DEFAULT)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:

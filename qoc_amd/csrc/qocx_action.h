@@ -15,6 +15,9 @@
 namespace qocx {
 
 #define QOCX_ACTION_MAX_DEGREE 18
+// the most states per seed the matrix-free route takes (qocx_action_states.hip: a wave per state, one per
+// SIMD of a CU; knob "action_states")
+#define QOCX_ACTION_MAX_STATES 4
 // bits 24..29 of a step's entry in s_arr (qocx_wave.h: bits 0..7 squarings, 8..15 Pade order, 16
 // dominance): the Taylor degree of the step, 1 .. 18, or 19 - the bound is above theta_18
 #define QOCX_STEP_DEGREE_SHIFT 24

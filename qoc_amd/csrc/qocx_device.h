@@ -226,6 +226,16 @@ struct ActionGradArgs {
 void launch_action_sweep(const ActionArgs& a, int batch, hipStream_t st);
 void launch_action_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
 int action_grad_lds_bytes(int m_max);
+// ... with two to four states per seed at 17 <= n <= 32 (qocx_action_states.hip, knob "action_states"): a
+// workgroup of sw.S waves per (seed, direction), wave s the state s. The same arguments with the state
+// between the terms' step and degree: kv_f / kv_b [B][nsteps][S][m_max][NP], carry_f [B][S][NP]. The
+// gradient kernel adds the states' cotangents of the generator and contracts once with the G_k.
+struct ActionStatesGradArgs {
+    ActionGradArgs g;
+    int S;
+};
+void launch_action_states_sweep(const ActionArgs& a, int batch, hipStream_t st);
+void launch_action_states_grad(const ActionStatesGradArgs& a, int nsteps, int batch, hipStream_t st);
 // ... at 33 <= n <= 64 (qocx_action4.hip, knob "action" = 2; images and vectors padded to 64): workgroups
 // of three (n <= 48) or four waves, each wave 16 columns of the generator; the same arguments, buffers
 // and contract

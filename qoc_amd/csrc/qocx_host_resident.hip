@@ -353,13 +353,18 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // workgroups of three waves up to n = 48, of four above). There the step table - which at nb = 2 also
     // serves K1a - is launched for the sweeps alone; the Pade route above n = 32 knows no step table and
     // stays as it is.
+    // Knob "action_states": 0 (default) one state only; 2 .. QOCX_ACTION_MAX_STATES: the most states per
+    // seed that take the route at 17 <= n <= 32 (qocx_action_states.hip: a wave per state). unit_ok admits
+    // several states for a coherent target only - one scalar for all of them.
+    const int action_states = (int)ctx->knob("action_states", 0);
+    const bool states_ok = S == 1 || (nb == 2 && S >= 2 && S <= std::min(action_states, QOCX_ACTION_MAX_STATES));
     const double host_bound = std::min(ctx->norm_bound, ctx->norm_bound_mid);
     const int64_t action_knob = ctx->knob("action", 1);
     const bool table_ok = !explicit_gen && r.nodes == 1 && !r.eff && !r.dense && ctx->K > 0 &&
                           ctx->g_norm_dev.p != nullptr;
     const bool sized = nb == 2 ? (action_knob != 0 && r.step_table)
                                : (nb == 4 && action_knob == 2 && table_ok);  // (33 <= n <= 64: padded to 64)
-    r.action = allow_action && sized && S == 1 && ctx->nt == 1 && ctx->hermitian &&
+    r.action = allow_action && sized && states_ok && ctx->nt == 1 && ctx->hermitian &&
                ctx->unit_ok && ctx->inj_count == 0 && !ctx->has_step_costs && !r.latency &&
                !r.inverse_sweep && !ctx->keep_step_states && ctx->knob("pade_order", 0) == 0 &&
                ctx->knob("unit_adjoint", 1) != 0 &&
@@ -377,9 +382,9 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
     if (ctx->action_counts.ensure(QOCX_ACTION_MAX_DEGREE + 1)) return QOCX_ERR_HIP;
     if (r.action) {
         // no Q / LU images, 1 / U_kk, permutations or sub-step slots: the Taylor terms of both sweeps
-        // (gradient wanted), the step table and the step cotangents
-        const size_t terms = want_grad ? (size_t)r.m_max * np : 0;
-        const size_t seed_bytes = (size_t)nsteps * (2 * terms * 16 + 4 + (size_t)K * 8 + (size_t)K * 16) + (size_t)np * 64;
+        // (gradient wanted) of every state, the step table and the step cotangents
+        const size_t terms = want_grad ? (size_t)S * r.m_max * np : 0;
+        const size_t seed_bytes = (size_t)nsteps * (2 * terms * 16 + 4 + (size_t)K * 8 + (size_t)K * 16) + (size_t)S * np * 64;
         chunk = ctx->chunk_user;
         if (chunk <= 0) {
             size_t free_b = 0, total_b = 0;
@@ -391,7 +396,7 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
         chunk = std::min(chunk, B);
         const size_t cm = (size_t)chunk * nsteps;
         if (ctx->s_arr.ensure(cm) || ctx->kry_f.ensure(std::max<size_t>(1, cm * terms)) ||
-            ctx->kry_b.ensure(std::max<size_t>(1, cm * terms)) || ctx->action_carry.ensure((size_t)chunk * np) ||
+            ctx->kry_b.ensure(std::max<size_t>(1, cm * terms)) || ctx->action_carry.ensure((size_t)chunk * S * np) ||
             ctx->gstep.ensure(cm * std::max(K, 1) * 2) || ctx->cost_out.ensure(B) ||
             ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) || ctx->final_out.ensure((size_t)B * S * np) ||
             ctx->lam_buf.ensure((size_t)chunk * S * np) || ctx->lu_fallbacks.ensure(1))
@@ -483,6 +488,7 @@ struct ResidentChunk {
     qocx::KrylovArgs ka;
     qocx::ActionArgs aa;       // the matrix-free route (r.action)
     qocx::ActionGradArgs ga;
+    qocx::ActionStatesGradArgs sga;  // ... with several states per seed (qocx_action_states.hip)
 
     ResidentChunk(qocx_ctx* c, const ResidentRoute& route, int grad, int first, int count)
         : ctx(c), r(route), want_grad(grad), b0(first), bc(count), cs(c->stream) {
@@ -674,6 +680,7 @@ struct ResidentChunk {
             aa.degree_counts = ctx->action_counts.p;
             ga.kv_f = ctx->kry_f.p; ga.kv_b = ctx->kry_b.p; ga.s_arr = ctx->s_arr.p; ga.g_rimg = ctx->g.r.p;
             ga.K = ctx->K; ga.m_max = r.m_max; ga.nsteps = nsteps; ga.dt = ctx->dt; ga.gstep = ctx->gstep.p;
+            sga.S = S;
         }
         return 0;
     }
@@ -750,7 +757,8 @@ struct ResidentChunk {
         if (!((dbg_skip & 1) && (phase & 1)) && !((dbg_skip & 2) && (phase & 2))) {
             if (r.action) {
                 aa.sw = sa;
-                if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
+                if (ctx->S > 1) qocx::launch_action_states_sweep(aa, bc, st);
+                else if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
                 else qocx::launch_action4_sweep(ctx->n, aa, bc, st);
             } else if (r.dense) qocx::launch_sweepd(sa, bc, st);
             else if (r.inverse_sweep) qocx::launch_sweepi(ctx->nb, sa, bc, st);
@@ -768,6 +776,9 @@ struct ResidentChunk {
         if (r.action) {
             ga.step0 = jb;
             if (dbg_skip & 4) {
+            } else if (ctx->S > 1) {
+                sga.g = ga;
+                qocx::launch_action_states_grad(sga, len, bc, cs);
             } else if (ctx->nb == 2) qocx::launch_action_grad(ga, len, bc, cs);
             else qocx::launch_action4_grad(ctx->n, ga, len, bc, cs);
         } else if (!(dbg_skip & 4)) qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
