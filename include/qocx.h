@@ -602,6 +602,13 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   generator cotangents summed before one contraction (qocx_action_states.hip). Any
  *                   other value is QOCX_ERR_ARG. Opt-in: at 0 every problem launches what it always
  *                   launched. n <= 16 and the wide route of "action" = 2 stay one-state.
+ *   "action_costs"  0 (default): the matrix-free route needs the one final TargetStateInfidelity. 1: one
+ *                   state, 17 <= n <= 32, where "action" admits the problem in every respect but the cost
+ *                   set: any set of device descriptors (COHERENT, INCOHERENT, FORBID; final or step; one
+ *                   or several) - the adjoint sweep carries the true cotangent, forward sweep first, then
+ *                   the adjoint sweep (qocx_action_costs.hip). Any other value is QOCX_ERR_ARG. Opt-in: at
+ *                   0 every problem launches what it always launched, and the single final target keeps
+ *                   its kernels at 1 too. Several states, n <= 16 and n > 32 stay on the Pade route.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;

@@ -29,7 +29,7 @@ _FD_STEP = 1e-6
 # against 11.3 at two states, 18.4 against 13.5 at three - tools/bench_action_states.py,
 # profiles/action_states.jsonl).
 ACTION_STATES_DEFAULT = 2
-MATRIX_FREE_VALUES = ("default", "wide", "states", "all")
+MATRIX_FREE_VALUES = ("default", "wide", "states", "all", "costs")
 
 
 def interpolation_keywords(backend, setter, interpolation_policy):
@@ -599,8 +599,12 @@ class SchroedingerEvaluator(_Evaluator):
         also takes them for 2 .. ACTION_STATES_DEFAULT states per seed at 17 <= n <= 32 under one
         coherent final TargetStateInfidelity (knob "action_states"; a wave per state, opt-in for the
         same reason); "all" asks for both. A problem of that many states asked for with "states" or
-        "all" is not put into latency mode, which the route yields to. A backend without knobs
-        ignores it; any other value is a ValueError.
+        "all" is not put into latency mode, which the route yields to. "costs" takes them for one
+        state at 17 <= n <= 32 under any set of costs the device evaluates - step costs
+        (TargetStateInfidelityTime, ForbidStates), several costs, an incoherent target - instead of
+        the one final TargetStateInfidelity (knob "action_costs" = 1; opt-in, not part of "all"); such
+        a problem is not put into latency mode either. A backend without knobs ignores it; any other
+        value is a ValueError.
         latency_mode: the evaluator will be asked for ONE control array at a time (the
         reference's evolve_* / grape_* entry points). Where the cost is a single final
         TargetStateInfidelity the engine then runs its two-sided pipeline (round 3: forward and
@@ -619,8 +623,8 @@ class SchroedingerEvaluator(_Evaluator):
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
         if not (isinstance(matrix_free, str) and matrix_free in MATRIX_FREE_VALUES):
-            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\" or \"all\", not {!r}."
-                             .format(matrix_free))
+            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\", \"all\" or \"costs\", "
+                             "not {!r}.".format(matrix_free))
         self.matrix_free = matrix_free
         initial_states = np.asarray(initial_states)
         self.state_count = initial_states.shape[0]
@@ -732,6 +736,8 @@ class SchroedingerEvaluator(_Evaluator):
             states = matrix_free in ("states", "all")
             if states and 2 <= self.state_count <= ACTION_STATES_DEFAULT:
                 latency_mode = False  # (the route asked for yields to it)
+            if matrix_free == "costs" and self._takes_action_costs(descriptors):
+                latency_mode = False
             self.backend.set_knob(
                 "sweep_impl", 3 if (latency_mode and 16 < self.hilbert_size <= 32) else 1)
             self.backend.set_knob("latency", 1 if latency_mode else 0)
@@ -739,6 +745,8 @@ class SchroedingerEvaluator(_Evaluator):
                 self.backend.set_knob("action", 2)
             if states:
                 self.backend.set_knob("action_states", ACTION_STATES_DEFAULT)
+            if matrix_free == "costs":
+                self.backend.set_knob("action_costs", 1)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:
@@ -755,6 +763,14 @@ class SchroedingerEvaluator(_Evaluator):
                                           interpolation_policy)))
         self._set_problem(h0, g)
         self.cost_eval_step = cost_eval_step
+
+    def _takes_action_costs(self, descriptors):
+        """matrix_free="costs": one state, 17 <= n <= 32, every cost of the states a device
+        descriptor, and not the single final target (which has kernels of its own)."""
+        single_final_target = (len(descriptors) == 1 and not descriptors[0]["step_cost"]
+                               and descriptors[0]["kind"] in (0, 1))  # COHERENT, INCOHERENT
+        return (self.state_count == 1 and 17 <= self.hilbert_size <= 32 and len(descriptors) >= 1
+                and not self.opaque_costs and not single_final_target)
 
     def _set_problem(self, h0, g):
         head, psi0, kw = self._problem_static

@@ -1389,7 +1389,7 @@ static const char* const kVariantKnobs[] = {
     "unit_adjoint", "latency", "fuse_lu", "lu_inverse", "lu_mfma", "lu_dpp", "pack8", "m4_linear", "magnus_4w",
     "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
     "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
-    "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states"};
+    "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs"};
 static const char* const kDiagKnobs[] = {"dbg_skip", "sweep3_dbg", "sweep3_stamps", "lindblad_stamps",
                                          "k1a_stamps", "k1a_dbg", "peak_mode"};
 
@@ -1410,6 +1410,8 @@ int qocx_debug_set_knob(qocx_ctx* ctx, const char* name, int64_t value) {
     if (kind > 0) {
         if (strcmp(name, "action_states") == 0 && value != 0 && (value < 2 || value > QOCX_ACTION_MAX_STATES))
             return fail(QOCX_ERR_ARG, "action_states must be 0 or 2 .. 4 (QOCX_ACTION_MAX_STATES)");
+        if (strcmp(name, "action_costs") == 0 && value != 0 && value != 1)
+            return fail(QOCX_ERR_ARG, "action_costs must be 0 or 1");
         ctx->knobs[name] = value;
         return 0;
     }

@@ -242,6 +242,12 @@ void launch_action_states_grad(const ActionStatesGradArgs& a, int nsteps, int ba
 void launch_action4_sweep(int n, const ActionArgs& a, int batch, hipStream_t st);
 void launch_action4_grad(int n, const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
 int action4_grad_lds_bytes(int n, int m_max, int K);
+// ... one state at 17 <= n <= 32 under any set of device cost descriptors (qocx_action_costs.hip, knob
+// "action_costs"): the same arguments and buffers; sw.unit_adjoint is 0, the forward launches carry the
+// partial cost in sw.cost_out, the adjoint sweep carries the true cotangent and reads psi_j from kv_f,
+// and gstep receives ONE real per (step, k) - [B][nsteps][K], KrylovArgs::gstep without the unit adjoint
+void launch_action_costs_sweep(const ActionArgs& a, int batch, hipStream_t st);
+void launch_action_costs_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
 
 // Magnus M4 / M6 generator kernels (qocx_magnus.hip)
 struct MagnusArgs {

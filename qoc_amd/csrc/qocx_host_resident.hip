@@ -282,6 +282,7 @@ struct ResidentRoute {
     bool pack8;          // n <= 8: two steps per 16 x 16 tile through K1a and K1b
     bool umode;          // the propagator itself in the Q image, one product per sweep sub-step
     bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip, qocx_action4.hip)
+    bool action_costs;   // ... under any device cost descriptors: the general adjoint, one-sided (qocx_action_costs.hip)
     bool action_table;   // ... at 33 <= n <= 64: launch_step_table for the sweeps alone (no K1a reads it)
     int m_max;           // ... and the Taylor terms per step its buffers hold
 };
@@ -364,11 +365,20 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
                           ctx->g_norm_dev.p != nullptr;
     const bool sized = nb == 2 ? (action_knob != 0 && r.step_table)
                                : (nb == 4 && action_knob == 2 && table_ok);  // (33 <= n <= 64: padded to 64)
-    r.action = allow_action && sized && states_ok && ctx->nt == 1 && ctx->hermitian &&
-               ctx->unit_ok && ctx->inj_count == 0 && !ctx->has_step_costs && !r.latency &&
-               !r.inverse_sweep && !ctx->keep_step_states && ctx->knob("pade_order", 0) == 0 &&
-               ctx->knob("unit_adjoint", 1) != 0 &&
-               host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
+    // Knob "action_costs": 0 (default) the cost set must be the one final TargetStateInfidelity of the
+    // unit adjoint; 1: a problem that meets every other condition at S = 1, 17 <= n <= 32 takes the route
+    // under ANY set of device descriptors - step costs, several costs, forbidden states - on the kernels
+    // of qocx_action_costs.hip, whose adjoint sweep carries the true cotangent: r.unit is false there
+    // (the scatter kernel applies no scalar) and the schedule is one-sided whatever "bidir" says. A
+    // unit_ok problem keeps the kernels above whatever this knob says.
+    const bool except_costs = allow_action && sized && states_ok && ctx->nt == 1 && ctx->hermitian &&
+                              ctx->inj_count == 0 && !r.latency && !r.inverse_sweep && !ctx->keep_step_states &&
+                              ctx->knob("pade_order", 0) == 0 &&
+                              host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
+    const bool unit_costs = ctx->unit_ok && !ctx->has_step_costs && ctx->knob("unit_adjoint", 1) != 0;
+    r.action_costs = except_costs && !ctx->unit_ok && ctx->knob("action_costs", 0) == 1 && S == 1 && nb == 2 &&
+                     ctx->cost_count > 0;
+    r.action = (except_costs && unit_costs) || r.action_costs;
     r.action_table = r.action && nb != 2;
     // (the device's bound of a step is the host's up to the rounding of the interpolation)
     r.m_max = r.action ? std::min(QOCX_ACTION_MAX_DEGREE, qocx::action_degree_for(host_bound * (1 + 1e-9))) : 0;
@@ -757,7 +767,8 @@ struct ResidentChunk {
         if (!((dbg_skip & 1) && (phase & 1)) && !((dbg_skip & 2) && (phase & 2))) {
             if (r.action) {
                 aa.sw = sa;
-                if (ctx->S > 1) qocx::launch_action_states_sweep(aa, bc, st);
+                if (r.action_costs) qocx::launch_action_costs_sweep(aa, bc, st);
+                else if (ctx->S > 1) qocx::launch_action_states_sweep(aa, bc, st);
                 else if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
                 else qocx::launch_action4_sweep(ctx->n, aa, bc, st);
             } else if (r.dense) qocx::launch_sweepd(sa, bc, st);
@@ -776,6 +787,8 @@ struct ResidentChunk {
         if (r.action) {
             ga.step0 = jb;
             if (dbg_skip & 4) {
+            } else if (r.action_costs) {
+                qocx::launch_action_costs_grad(ga, len, bc, cs);
             } else if (ctx->S > 1) {
                 sga.g = ga;
                 qocx::launch_action_states_grad(sga, len, bc, cs);
