@@ -609,6 +609,14 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   the adjoint sweep (qocx_action_costs.hip). Any other value is QOCX_ERR_ARG. Opt-in: at
  *                   0 every problem launches what it always launched, and the single final target keeps
  *                   its kernels at 1 too. Several states, n <= 16 and n > 32 stay on the Pade route.
+ *   "action_degree" 1 (default): the Taylor degree of a step of the matrix-free route (every kernel file of
+ *                   it) is the lesser of the Al-Mohy-Higham degree of the 1-norm bound |dt| (||H0||_1 +
+ *                   sum |u_k| ||G_k||_1) and the degree at which the Lagrange remainder beta^(m+1) / (m+1)!
+ *                   of a NORMAL generator is below 2^-53, beta = |dt| (rho(H0) + sum |u_k| rho(G_k)) from
+ *                   upper bounds of the spectral radii (qocx_debug_spectral_bound, qocx_debug_action_degree)
+ *                   - never more terms than the 1-norm alone asks for; the headline runs degree 8 instead
+ *                   of 11. 0: the 1-norm alone, bit for bit what the route computed before the knob
+ *                   existed. Any other value is QOCX_ERR_ARG. Pade orders and squarings stay on the 1-norm.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;
@@ -669,13 +677,26 @@ int qocx_pade_orders(qocx_ctx* ctx, int64_t* counts);
 /* Taylor degrees the last Schroedinger evaluation executed on the matrix-free route (one state,
  * Hermitian H, 17 <= n <= 32 - with knob "action" = 2 up to n = 64 -, one final TargetStateInfidelity;
  * qoc_amd/csrc/qocx_action.hip, qocx_action4.hip): counts[m], m = 1 .. 18, = propagator steps whose exp(a) psi was the degree-m
- * truncated Taylor series (Al-Mohy & Higham 2011; the least m with ||a||_1 <= theta_m), summed over
+ * truncated Taylor series (Al-Mohy & Higham 2011: the least m with ||a||_1 <= theta_m; with knob
+ * "action_degree" = 1, the default, no more than the normal generator's remainder needs), summed over
  * every seed of the evaluation. All 19 entries are zero when the evaluation took the Pade route. */
 int qocx_action_degrees(qocx_ctx* ctx, int64_t* counts);
 /* Evaluations of this context the matrix-free route handed back to the Pade route because a step's
  * degree, decided on the device, was beyond the buffers the host had sized from its norm bound
  * (stale after qocx_opt_step). The results are those of the Pade route. */
 int qocx_action_reruns(qocx_ctx* ctx, int64_t* count);
+/* The two host functions behind the degrees of the matrix-free route; no context, no GPU call.
+ * qocx_debug_spectral_bound: m is a HERMITIAN n x n matrix (complex row-major, 1 <= n <= 64); *bound is an
+ * upper bound of its spectral radius rho (= ||m||_2), rho <= *bound <= 1.01 rho, by eight normalised
+ * squarings (rho <= ||m^256||_F^(1/256) <= n^(1/512) rho); 0 for the zero matrix, NaN where an entry is
+ * not finite. The engine takes it of H0 and every G_k when a problem is set.
+ * qocx_debug_action_degree: the degree of a step whose generator a has ||a||_1 <= bound1 and
+ * ||a||_2 <= bound2. rule 0: the least m in 1 .. 18 with bound1 <= theta_m (Al-Mohy & Higham 2011), 19
+ * above theta_18 and for NaN. rule 1 (knob "action_degree", the default): the lesser of that and the least
+ * m with bound2^(m+1) / (m+1)! <= 2^-53 - the Lagrange remainder of e^(i lambda), which bounds the
+ * truncation error of T_m(a) psi for a NORMAL a (a = -i dt H, H Hermitian) - 19 above theta'_18 and for NaN. */
+int qocx_debug_spectral_bound(const double* m, int32_t n, double* bound);
+int qocx_debug_action_degree(double bound1, double bound2, int32_t rule, int32_t* degree);
 /* Matrices of the last Schroedinger evaluation (or qocx_debug_pade_factor call) whose LU factorisation
  * left the diagonal-pivot form with MFMA Schur updates (knob "lu_mfma"; qoc_amd/csrc/qocx_lu4.h,
  * qocx_lu4m.hip) for the general partial-pivoting elimination: LAPACK's pivot rule asked for a row

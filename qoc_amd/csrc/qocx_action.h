@@ -7,6 +7,8 @@
 // Taylor polynomial T_m(a) equals exp(a + da) with ||da|| <= 2^-53 ||a|| - the criterion of "Pade
 // order by norm" (qocx_wave.h) for another approximant. theta_m for m = 1 .. 18 as SciPy carries
 // them (scipy.sparse.linalg._expm_multiply._theta, the paper's Table 3.1 to three digits).
+// The generators of this route are normal, and a bound of their 2-norm admits a lower degree by the
+// remainder of the series itself (action_degree_normal); a step takes the lesser (action_degree_rule).
 #ifndef QOCX_ACTION_H
 #define QOCX_ACTION_H
 
@@ -52,6 +54,54 @@ __host__ __device__ inline int action_degree_for(double bound) {
     for (int m = 1; m <= QOCX_ACTION_MAX_DEGREE; ++m)
         if (bound <= action_theta(m)) return m;
     return QOCX_ACTION_MAX_DEGREE + 1;
+}
+
+// A NORMAL a (every generator of this route: a = -i dt H, H Hermitian) with ||a||_2 <= beta: the
+// eigenvalues i lambda lie on the imaginary axis, |lambda| <= beta, and T_m(a) psi - exp(a) psi is, in
+// the eigenbasis, the Lagrange remainder of e^(i lambda): at most beta^(m+1) / (m+1)! ||psi||. Asking
+// that to be <= 2^-53 - below one rounding of the state - gives
+//     theta'_m = ((m+1)! 2^-53)^(1/(m+1)),
+// here each rounded DOWN to a double (theta'_m^(m+1) <= (m+1)! 2^-53 holds in exact arithmetic).
+__host__ __device__ inline double action_theta_normal(int m) {
+    double t = 0.0;
+    switch (m) {
+        case 1: t = 1.4901161193847656e-08; break;
+        case 2: t = 8.733476581980375e-06; break;
+        case 3: t = 0.00022719845192922352; break;
+        case 4: t = 0.0016784882105346471; break;
+        case 5: t = 0.006563323151782549; break;
+        case 6: t = 0.01777016817886154; break;
+        case 7: t = 0.038138740273514826; break;
+        case 8: t = 0.06998730192918919; break;
+        case 9: t = 0.11495221029281477; break;
+        case 10: t = 0.17401909444156718; break;
+        case 11: t = 0.24763513660365769; break;
+        case 12: t = 0.3358381601514265; break;
+        case 13: t = 0.43837339055193697; break;
+        case 14: t = 0.5547883372015275; break;
+        case 15: t = 0.6845053769594961; break;
+        case 16: t = 0.8268751230769177; break;
+        case 17: t = 0.9812145020859808; break;
+        case 18: t = 1.1468331956329982; break;
+    }
+    return t;
+}
+
+// the least m with beta <= theta'_m; QOCX_ACTION_MAX_DEGREE + 1 above theta'_18 (also NaN)
+__host__ __device__ inline int action_degree_normal(double beta) {
+    for (int m = 1; m <= QOCX_ACTION_MAX_DEGREE; ++m)
+        if (beta <= action_theta_normal(m)) return m;
+    return QOCX_ACTION_MAX_DEGREE + 1;
+}
+
+// The degree of a step. bound1 >= ||a||_1 and bound2 >= ||a||_2 of its generator; rule 1 (knob
+// "action_degree", default): the lesser of the two criteria - never above what the 1-norm alone asks
+// for; rule 0: the 1-norm alone.
+__host__ __device__ inline int action_degree_rule(double bound1, double bound2, int rule) {
+    const int m1 = action_degree_for(bound1);
+    if (rule == 0) return m1;
+    const int m2 = action_degree_normal(bound2);
+    return m2 < m1 ? m2 : m1;
 }
 
 __host__ __device__ inline int step_degree(int entry) {

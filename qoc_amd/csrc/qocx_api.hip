@@ -7,6 +7,8 @@
 #include <dlfcn.h>
 #include <unistd.h>
 
+#include <cfloat>
+
 #include "qocx_host.h"
 #include "qocx_action.h"
 
@@ -35,9 +37,11 @@ int pade_scale_count(double norm1) {
     return s;
 }
 
-int commit_step_bound(qocx_ctx* ctx, double bound, bool keep_larger, const char* needs) {
+int commit_step_bound(qocx_ctx* ctx, double bound, bool keep_larger, const char* needs, double bound2) {
     const int sb = pade_scale_count(bound);
     if (!keep_larger) ctx->sbound = sb, ctx->norm_bound = bound;  // (an upload: even where refused below)
+    ctx->norm2_bound = keep_larger ? std::max(ctx->norm2_bound, bound2) : bound2;
+    ctx->norm2_bound_mid = 1e300;
     if (sb > 10)
         return fail(QOCX_ERR_CAPACITY, std::string("||dt H||_1 ") + needs +
                                            " more than 2^10 squaring sub-steps per step; reduce dt");
@@ -58,6 +62,50 @@ double one_norm(const double* m, int n) {  // complex row-major
         best = std::max(best, s);
     }
     return best;
+}
+
+// An upper bound of the spectral radius of a Hermitian matrix (complex row-major, n <= 64), which is its
+// 2-norm: rho(A) = rho(A^(2^k))^(1/2^k) <= ||A^(2^k)||_F^(1/2^k), and ||.||_F <= sqrt(n) rho for a normal
+// matrix, so after k = 8 squarings the overshoot is at most n^(1/512) (0.82 % at n = 64). Every square is
+// normalised by its Frobenius norm (no overflow or underflow whatever the scale of A) and the logarithms of
+// the norms are carried: with B_0 = A / f_0, B_(j+1) = B_j^2 / f_(j+1), f_j = ||.||_F before the division,
+//     ||A^(2^k)||_F^(1/2^k) = exp(sum_j log(f_j) / 2^j).
+// The rounding of 8 products of n <= 64 terms moves the result by parts in 1e13; the final (1 + 1e-9) keeps
+// it an upper bound. Zero matrix: 0. Not finite (or n out of range): NaN - the caller keeps the 1-norm.
+double spectral_bound(const double* m, int n) {
+    if (n < 1 || n > 64) return std::nan("");
+    const size_t nn = (size_t)n * n;
+    std::vector<double> a(m, m + 2 * nn), b(2 * nn);
+    double log_sum = 0, weight = 1;
+    for (int j = 0;; ++j) {
+        double big = 0;
+        for (size_t i = 0; i < 2 * nn; ++i)
+            if (!(fabs(a[i]) <= big)) big = fabs(a[i]);  // (also catches NaN)
+        if (big == 0 && j == 0) return 0;
+        // (inf / NaN, or a square that vanished: A was nilpotent to rounding, which no Hermitian A is)
+        if (!(big > 0 && big <= DBL_MAX)) return std::nan("");
+        double f = 0;  // ||a||_F, scaled by its largest entry
+        for (size_t i = 0; i < 2 * nn; ++i) f += (a[i] / big) * (a[i] / big);
+        f = sqrt(f);
+        log_sum += weight * (log(big) + log(f));
+        for (size_t i = 0; i < 2 * nn; ++i) a[i] = a[i] / big / f;
+        if (j == 8) break;
+        weight *= 0.5;
+        for (int r = 0; r < n; ++r)
+            for (int c = 0; c < n; ++c) {
+                double re = 0, im = 0;
+                for (int q = 0; q < n; ++q) {
+                    const double xr = a[2 * ((size_t)r * n + q)], xi = a[2 * ((size_t)r * n + q) + 1];
+                    const double yr = a[2 * ((size_t)q * n + c)], yi = a[2 * ((size_t)q * n + c) + 1];
+                    re += xr * yr - xi * yi;
+                    im += xr * yi + xi * yr;
+                }
+                b[2 * ((size_t)r * n + c)] = re;
+                b[2 * ((size_t)r * n + c) + 1] = im;
+            }
+        a.swap(b);
+    }
+    return exp(log_sum) * (1.0 + 1e-9);
 }
 
 }  // namespace qocx::host
@@ -310,9 +358,23 @@ int upload_operators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
         for (int k = 0; k < K; ++k)
             ctx->g_norm_max[k] = std::max(ctx->g_norm_max[k], one_norm(p->g + ((size_t)t * K + k) * nn2, n));
     }
+    // The spectral-norm bounds behind the Taylor degrees of the matrix-free route (qocx_action.h). They
+    // sharpen the 1-norms only where that route can run - Hermitian operators, constant in time, n <= 64 -
+    // and never exceed them (||A||_2 <= ||A||_1 for a Hermitian A; the bound may overshoot by 1 %).
+    ctx->h0_norm2_max = ctx->h0_norm_max;
+    ctx->g_norm2_max = ctx->g_norm_max;
+    if (ctx->hermitian && nt == 1 && n <= 64) {
+        auto sharpen = [&](const double* m, double norm1) {
+            const double s = spectral_bound(m, n);
+            return s <= norm1 ? s : norm1;  // (NaN: the 1-norm)
+        };
+        ctx->h0_norm2_max = sharpen(p->h0, ctx->h0_norm_max);
+        for (int k = 0; k < K; ++k) ctx->g_norm2_max[k] = sharpen(p->g + (size_t)k * nn2, ctx->g_norm_max[k]);
+    }
     return ctx->h0.build(p->h0, (size_t)nt, n, ctx->nb, ctx->stream) ||
                    ctx->g.build(p->g, (size_t)nt * K, n, ctx->nb, ctx->stream) ||
-                   (K > 0 && ctx->g_norm_dev.upload(ctx->g_norm_max, ctx->stream))  // step table
+                   (K > 0 && (ctx->g_norm_dev.upload(ctx->g_norm_max, ctx->stream) ||  // step table
+                              ctx->g_norm2_dev.upload(ctx->g_norm2_max, ctx->stream)))
                ? QOCX_ERR_HIP : 0;
 }
 
@@ -1076,6 +1138,7 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     // (with an ensemble the caller's array holds the seeds' K_r channels)
     const size_t per = (size_t)ctx->nc * (ens ? ctx->seeds.Kr : ctx->K);
     double bound = ctx->h0_norm_max;
+    double bound2 = 1e300, bound2_mid = 1e300;  // of ||step generator||_2, where formed below
     if (ctx->K > 0) {
         if (!controls) return fail(QOCX_ERR_ARG, "controls is NULL");
         // One pass over the caller's array: the per-control maxima for the squaring bound, and a
@@ -1096,7 +1159,10 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         // sum_k |u_k(t)| ||G_k||_1 is largest at a control knot (u is linear between knots, the sum
         // convex): the largest knot sum bounds every step, every Magnus node, and the device's
         // per-step bound (launch_step_table) - tighter than sum_k max_t |u_k(t)| ||G_k||_1
+        // (s2*: the same sums with the spectral-norm bounds, for the Taylor buffers of the matrix-free route;
+        // an ensemble or sweep forms none and sizes them from the 1-norm)
         double smax = 0.0, smid = 0.0, sprev = 0.0;
+        double s2max = 0.0, s2mid = 0.0, s2prev = 0.0;
         double* stage = ctx->pin_controls;
         if (ctx->seeds.dur.mirror_stale)  // (a duration search whose tables qocx_opt_clip has rewritten since)
             if (int rc = sweep_mirror_tables(ctx)) return rc;
@@ -1104,26 +1170,36 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
         for (size_t row = 0; !ens && row < (size_t)batch * ctx->nc; ++row) {
             const double* src = controls + row * K;
             double* dst = stage + row * K;
-            double srow = 0.0;
+            double srow = 0.0, s2row = 0.0;
             for (int k = 0; k < K; ++k) {
                 const double v = src[k];
                 dst[k] = v;
                 srow += fabs(v) * ctx->g_norm_max[k];
+                s2row += fabs(v) * ctx->g_norm2_max[k];
             }
             if (!(srow <= smax)) smax = srow;  // also catches NaN
+            if (!(s2row <= s2max)) s2max = s2row;
             // midpoint of two knots of the same seed: |u_mid| <= (|u_j| + |u_j+1|) / 2
             if (row % (size_t)ctx->nc != 0) {
-                const double m = 0.5 * (sprev + srow);
+                const double m = 0.5 * (sprev + srow), m2 = 0.5 * (s2prev + s2row);
                 if (!(m <= smid)) smid = m;
+                if (!(m2 <= s2mid)) s2mid = m2;
             }
             sprev = srow;
+            s2prev = s2row;
         }
         // (piecewise constant: a step reads ONE slice, never the mean of two rows - the knot sums
         // above are then exact for every step and the midpoint bound does not apply)
-        if (ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->eff.quad_count() == 0 && !ctx->pwc)
+        const bool mid_applies = ctx->nodes == 1 && ctx->nc == ctx->nsteps + 1 && ctx->eff.quad_count() == 0 && !ctx->pwc;
+        if (mid_applies)
             ctx->norm_bound_mid = (bound + smid) * fabs(ctx->dt) * (1.0 + 1e-12);
         else
             ctx->norm_bound_mid = 1e300;
+        // (only the plain M2 problem takes the matrix-free route: nothing else needs the spectral bounds)
+        if (!ens && ctx->nodes == 1 && ctx->eff.quad_count() == 0) {
+            bound2 = (ctx->h0_norm2_max + s2max) * fabs(ctx->dt);
+            if (mid_applies) bound2_mid = (ctx->h0_norm2_max + s2mid) * fabs(ctx->dt) * (1.0 + 1e-12);
+        }
         bound += smax;
         // Quadratic terms: r_k(t) r_l(t) is not convex between knots (r_k 0 -> a, r_l a -> 0 peaks at
         // a^2 / 4 mid-interval), so the knot sums above do not bound it. |r_k(t)| <= max over the knots of
@@ -1142,7 +1218,9 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
     }
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite controls or Hamiltonian");
-    if (int rc = commit_step_bound(ctx, bound, false, "bound needs")) return rc;
+    if (!(bound2 < 1e300)) bound2 = bound2_mid = 1e300;
+    if (int rc = commit_step_bound(ctx, bound, false, "bound needs", bound2)) return rc;
+    ctx->norm2_bound_mid = bound2_mid;
     ctx->B = ens ? batch * ctx->seeds.M : batch;
     ctx->ens_B = ens ? batch : 0;
     ctx->have_results = false;
@@ -1389,7 +1467,8 @@ static const char* const kVariantKnobs[] = {
     "unit_adjoint", "latency", "fuse_lu", "lu_inverse", "lu_mfma", "lu_dpp", "pack8", "m4_linear", "magnus_4w",
     "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
     "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
-    "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs"};
+    "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs",
+    "action_degree"};
 static const char* const kDiagKnobs[] = {"dbg_skip", "sweep3_dbg", "sweep3_stamps", "lindblad_stamps",
                                          "k1a_stamps", "k1a_dbg", "peak_mode"};
 
@@ -1412,6 +1491,8 @@ int qocx_debug_set_knob(qocx_ctx* ctx, const char* name, int64_t value) {
             return fail(QOCX_ERR_ARG, "action_states must be 0 or 2 .. 4 (QOCX_ACTION_MAX_STATES)");
         if (strcmp(name, "action_costs") == 0 && value != 0 && value != 1)
             return fail(QOCX_ERR_ARG, "action_costs must be 0 or 1");
+        if (strcmp(name, "action_degree") == 0 && value != 0 && value != 1)
+            return fail(QOCX_ERR_ARG, "action_degree must be 0 or 1");
         ctx->knobs[name] = value;
         return 0;
     }

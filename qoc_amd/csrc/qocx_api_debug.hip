@@ -1,6 +1,7 @@
 // qocx_api_debug.hip - the debug and self-test entry points of the C ABI (include/qocx.h) and the
 // counters the tests and tools read back.
 #include "qocx_host.h"
+#include "qocx_action.h"
 
 namespace {
 
@@ -251,6 +252,20 @@ int qocx_action_degrees(qocx_ctx* ctx, int64_t* counts) {
     int v[19];
     HIP_TRY(hipMemcpy(v, ctx->action_counts.p, sizeof(v), hipMemcpyDeviceToHost));
     for (int i = 0; i < 19; ++i) counts[i] = v[i];
+    return 0;
+}
+
+int qocx_debug_spectral_bound(const double* m, int32_t n, double* bound) {
+    if (!m || !bound) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (n < 1 || n > 64) return fail(QOCX_ERR_ARG, "n must be in 1..64");
+    *bound = spectral_bound(m, n);
+    return 0;
+}
+
+int qocx_debug_action_degree(double bound1, double bound2, int32_t rule, int32_t* degree) {
+    if (!degree) return fail(QOCX_ERR_ARG, "NULL argument");
+    if (rule != 0 && rule != 1) return fail(QOCX_ERR_ARG, "rule must be 0 or 1");
+    *degree = qocx::action_degree_rule(bound1, bound2, rule);
     return 0;
 }
 

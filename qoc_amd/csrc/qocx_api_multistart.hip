@@ -503,7 +503,16 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     bound += quad_bound(ctx, channel_norms.data());
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
-    if (int rc = commit_step_bound(ctx, bound, true, "bound needs")) return rc;
+    // (the plain M2 problem: the same bound with the spectral norms, for the Taylor buffers of the
+    // matrix-free route - qocx_upload_controls)
+    double bound2 = 1e300;
+    if (!ens && ctx->nodes == 1 && ctx->eff.quad_count() == 0 && (int)ctx->g_norm2_max.size() >= Ks) {
+        bound2 = ctx->h0_norm2_max;
+        for (int k = 0; k < Ks; ++k) bound2 += channel_norms[k] * ctx->g_norm2_max[k];
+        bound2 *= fabs(ctx->dt);
+        if (!(bound2 < 1e300)) bound2 = 1e300;
+    }
+    if (int rc = commit_step_bound(ctx, bound, true, "bound needs", bound2)) return rc;
     // (the Lindblad path checks the second of these grid limits in qocx_lindblad_upload_controls and has
     // no check of the first: to be revisited)
     if ((v.total() + 255) / 256 > 0x7fffffffu || v.per_seed() > 65535u * 256u)

@@ -89,7 +89,11 @@ struct StepTableArgs {
     int sq_max = 30;           // the squaring count the host sized the sub-step slots for
     int order_max = 13;        // 5: the three-wave K1a of qocx_pade3.hip runs the evaluation (host bound below theta_5)
     int action = 0;            // the entries also carry the Taylor degree of the step (qocx_action.h)
-    double* ustep;             // out: [B][nsteps][K]
+    // ... by action_degree_rule from the bound above and |dt| (h0_norm2 + sum_k |u_k| g_norm2[k]) >= ||a||_2
+    double h0_norm2 = 0;       // max over time of an upper bound of ||H0(t)||_2 (Hermitian H: its spectral radius)
+    const double* g_norm2 = nullptr;  // [K] the same of G_k(t) (device memory; read where action and degree_rule are set)
+    int degree_rule = 0;       // knob "action_degree": 1 the lesser of the two criteria, 0 the 1-norm alone
+    double* ustep;            // out: [B][nsteps][K]
     int* s_arr;                // out: [B][nsteps]
     int* status;               // bit 1: non-finite controls
 };

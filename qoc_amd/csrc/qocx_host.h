@@ -219,6 +219,10 @@ struct qocx_ctx {
     int has_step_costs = 0, cost_count = 0;
     double h0_norm_max = 0;
     std::vector<double> g_norm_max;
+    // upper bounds of the SPECTRAL norms of the same operators (spectral_bound; the 1-norms above where it
+    // does not apply): they decide the Taylor degrees of the matrix-free route and nothing else
+    double h0_norm2_max = 0;
+    std::vector<double> g_norm2_max;
     OperatorImages h0, g;  // [nt], [nt][K]
     DevBuf<double2> psi0, cost_vectors;
     DevBuf<qocx::StepInterp> interp;
@@ -234,6 +238,9 @@ struct qocx_ctx {
     // where u is the mean of two knots - what the step table's per-step bound can reach at most; 1e300 when
     // it does not apply. Decides only whether the two-wave K1a is launched beside the three-wave one.
     double norm_bound_mid = 1e300;
+    // the same two bounds of ||step generator||_2, from h0_norm2_max / g_norm2_max: they size the Taylor
+    // buffers of the matrix-free route (ResidentRoute::m_max); 1e300 where no such bound was formed
+    double norm2_bound = 1e300, norm2_bound_mid = 1e300;
     size_t slot_cap = 0;
     int chunk_user = 0;
     int pipe_user = 0;
@@ -293,6 +300,7 @@ struct qocx_ctx {
     std::vector<double> ens_qscale_max;                 // max_m |c_mq|
     DevBuf<double> ens_qscales;                         // [M][count]
     DevBuf<double> ustep, g_norm_dev;  // step table (launch_step_table): u_k(t_mid) per step; ||G_k||_1
+    DevBuf<double> g_norm2_dev;        // ... and the bounds of ||G_k||_2
     // explicit-generator mode (qocx_upload_generators): opaque Hamiltonians sampled by the host
     bool explicit_mode = false;
     int explicit_hermitian = 0;
@@ -442,8 +450,12 @@ void time_collect(qocx_ctx* ctx);
 // ---- qocx_api.hip: norm bounds of the step generators; the seed-level view ----
 int pade_scale_count(double norm1);
 // sbound, norm_bound and slot_cap from a bound of ||step generator||_1; `needs`: the caller's wording
-int commit_step_bound(qocx_ctx* ctx, double bound, bool keep_larger, const char* needs);
+// bound2: the same of ||step generator||_2 into norm2_bound (1e300: none formed; norm2_bound_mid is reset
+// with norm_bound_mid - qocx_upload_controls sets both after the call)
+int commit_step_bound(qocx_ctx* ctx, double bound, bool keep_larger, const char* needs, double bound2 = 1e300);
 double one_norm(const double* m, int n);  // complex row-major
+// Hermitian m, n <= 64: a value in [rho(m), 1.01 rho(m)] - never below the spectral radius (= ||m||_2)
+double spectral_bound(const double* m, int n);
 double pade_eps_max(double theta);
 double magnus_norm_bound(int nodes, double bound);
 double quad_bound(const qocx_ctx* ctx, const double* umax);

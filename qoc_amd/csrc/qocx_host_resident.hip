@@ -381,7 +381,15 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     r.action = (except_costs && unit_costs) || r.action_costs;
     r.action_table = r.action && nb != 2;
     // (the device's bound of a step is the host's up to the rounding of the interpolation)
-    r.m_max = r.action ? std::min(QOCX_ACTION_MAX_DEGREE, qocx::action_degree_for(host_bound * (1 + 1e-9))) : 0;
+    // Knob "action_degree": 1 (default) the degree of a step is the lesser of the Al-Mohy-Higham degree of
+    // its 1-norm bound and the degree the remainder of a NORMAL generator needs at its spectral-norm bound
+    // (qocx_action.h: action_degree_rule); 0: the 1-norm alone. The route predicate above stays on the
+    // 1-norm; only the buffers follow the rule - the host's two bounds of the same control maxima.
+    const double host_bound2 = std::min(ctx->norm2_bound, ctx->norm2_bound_mid);
+    r.m_max = r.action ? std::min(QOCX_ACTION_MAX_DEGREE,
+                                  qocx::action_degree_rule(host_bound * (1 + 1e-9), host_bound2 * (1 + 1e-9),
+                                                           ctx->knob("action_degree", 1) != 0 ? 1 : 0))
+                       : 0;
     return r;
 }
 
@@ -567,6 +575,8 @@ struct ResidentChunk {
             ta.nsteps = nsteps; ta.batch = bc; ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max;
             ta.g_norm = ctx->g_norm_dev.p; ta.pade_policy = fa.pade_policy;
             ta.action = r.action ? 1 : 0;
+            ta.h0_norm2 = ctx->h0_norm2_max; ta.g_norm2 = ctx->g_norm2_dev.p;
+            ta.degree_rule = ctx->knob("action_degree", 1) != 0 && ta.g_norm2 != nullptr ? 1 : 0;
             ta.sq_max = std::min(30, ctx->sbound);
             // only the three-wave K1a (orders 3 and 5) will be launched: no step above order 5
             qocx::FactorArgs probe = fa;

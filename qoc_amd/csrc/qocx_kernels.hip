@@ -1540,20 +1540,25 @@ __global__ __launch_bounds__(64, NB < 4 ? 2 : 1) void krylov_grad_skew_kernel(Kr
 // bound dt (||H0||_1 + sum |u_k| ||G_k||_1) >= ||a||_1 of the step's generator, and from it the
 // Pade order (Higham's thresholds) and the squaring count - decisions K1a used to take from the
 // norm of the matrix it had just built, at the price of two reductions and a workgroup barrier in
-// front of its first product.
+// front of its first product. For the matrix-free route the Taylor degree, from that bound and the same
+// sum over spectral-norm bounds (qocx_action.h); the Pade order and the squarings never read the latter.
 __global__ __launch_bounds__(256) void step_table_kernel(StepTableArgs args) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)args.batch * args.nsteps) return;
     const int b = (int)(idx / args.nsteps), step = (int)(idx % args.nsteps);
     const StepInterp si = args.interp[step];
     const double* ctl_b = args.controls + (size_t)b * args.nc * args.K;
-    double bound = args.h0_norm;
+    // (matrix-free route under the rule of the normal generator: the same sum with the spectral-norm bounds)
+    const bool normal = args.action && args.degree_rule != 0;
+    double bound = args.h0_norm, bound2 = args.h0_norm2;
     for (int k = 0; k < args.K; ++k) {
         const double uk = control_at(ctl_b, si, args.K, k);
         args.ustep[idx * args.K + k] = uk;
         bound = fma(fabs(uk), args.g_norm[k], bound);
+        if (normal) bound2 = fma(fabs(uk), args.g_norm2[k], bound2);
     }
     bound *= fabs(args.dt);
+    bound2 *= fabs(args.dt);
     int sq = 0, order = 13;
     bool dominant = false;
     if (!(bound < 1e300)) {  // inf / nan
@@ -1574,8 +1579,10 @@ __global__ __launch_bounds__(256) void step_table_kernel(StepTableArgs args) {
         }
         dominant = pade_denominator_dominant(order, ldexp(bound, -sq));
     }
-    // (matrix-free route, qocx_action.hip: the Taylor degree from the same bound; NaN: beyond every degree)
-    const int degree = args.action ? (action_degree_for(bound) << QOCX_STEP_DEGREE_SHIFT) : 0;
+    // (matrix-free route, qocx_action.hip: the Taylor degree from the same bound and, under rule 1, the
+    // spectral one - never above what this bound alone asks for; NaN: beyond every degree)
+    const int degree =
+        args.action ? (action_degree_rule(bound, bound2, normal ? 1 : 0) << QOCX_STEP_DEGREE_SHIFT) : 0;
     args.s_arr[idx] = step_entry(sq, order) | (dominant ? QOCX_STEP_DOMINANT : 0) | degree;
 }
 void launch_step_table(const StepTableArgs& a, hipStream_t st) {

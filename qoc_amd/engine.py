@@ -196,6 +196,8 @@ SIGNATURES = {
     "qocx_lu_fallbacks": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "qocx_action_degrees": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "qocx_action_reruns": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
+    "qocx_debug_spectral_bound": (ctypes.c_int, [_c_double_p, _I32, _c_double_p]),
+    "qocx_debug_action_degree": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, _I32, _c_int_p]),
     "qocx_debug_mfma_peak": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_opt_begin": (ctypes.c_int, [_VP]),
     "qocx_opt_clip": (ctypes.c_int, [_VP, _c_double_p]),
