@@ -22,17 +22,56 @@ namespace qocx {
 
 namespace action {
 
-// KR: the G_k images held in registers beside H0 (those of further controls are read per step)
-template <int NB, int KR>
-__global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
+// What an EARLIER launch wrote and every lane reads at one address - the step words, the step controls -
+// goes through the scalar unit: such a load is counted by lgkmcnt and does not wait, as a vector load's
+// vmcnt does, for the stores of the step before it.
+#define QOCX_SCALAR_MEM __attribute__((address_space(4)))
+typedef const QOCX_SCALAR_MEM int* ScalarInts;
+typedef const QOCX_SCALAR_MEM double* ScalarDoubles;
+
+// 1 / p from a table the code addresses relative to its own position (INV_P, which the host can see, is
+// reached through a pointer that a sweep fetched anew in every step)
+static __device__ __forceinline__ double inv_p(int p) {
+    constexpr InvTable table;
+    return table.v[p];
+}
+
+// The 16 columns of a lane group's block in ONE block of 64 multiply-adds: dpp_cmac4<0>, <4>, <8>, <12> of
+// qocx_action_core.h one after the other - the same instructions on the same accumulator pairs in the same
+// order - behind a single s_nop, since x is written once before the first of them.
+__device__ __forceinline__ void dpp_cmac16(double& r0, double& i0, double& r1, double& i1, double xr, double xi,
+                                           const double (&ar)[16], const double (&ai)[16]) {
+#define QOCX_ACTION_CMAC(R, I, C)                                                                          \
+    "v_fmac_f64_dpp %[" R "], %[xr], %[ar" #C "] row_newbcast:" #C " row_mask:0xf bank_mask:0xf\n\t"         \
+    "v_fmac_f64_dpp %[" I "], %[xi], %[ar" #C "] row_newbcast:" #C " row_mask:0xf bank_mask:0xf\n\t"         \
+    "v_fmac_f64_dpp %[" R "], -%[xi], %[ai" #C "] row_newbcast:" #C " row_mask:0xf bank_mask:0xf\n\t"        \
+    "v_fmac_f64_dpp %[" I "], %[xr], %[ai" #C "] row_newbcast:" #C " row_mask:0xf bank_mask:0xf\n\t"
+#define QOCX_ACTION_CMAC2(C, D) QOCX_ACTION_CMAC("r0", "i0", C) QOCX_ACTION_CMAC("r1", "i1", D)
+#define QOCX_ACTION_COL(C) [ar##C] "v"(ar[C]), [ai##C] "v"(ai[C])
+    asm("s_nop 1\n\t" QOCX_ACTION_CMAC2(0, 1) QOCX_ACTION_CMAC2(2, 3) QOCX_ACTION_CMAC2(4, 5) QOCX_ACTION_CMAC2(6, 7)
+            QOCX_ACTION_CMAC2(8, 9) QOCX_ACTION_CMAC2(10, 11) QOCX_ACTION_CMAC2(12, 13) QOCX_ACTION_CMAC2(14, 15)
+        : [r0] "+v"(r0), [i0] "+v"(i0), [r1] "+v"(r1), [i1] "+v"(i1)
+        : [xr] "v"(xr), [xi] "v"(xi), QOCX_ACTION_COL(0), QOCX_ACTION_COL(1), QOCX_ACTION_COL(2), QOCX_ACTION_COL(3),
+          QOCX_ACTION_COL(4), QOCX_ACTION_COL(5), QOCX_ACTION_COL(6), QOCX_ACTION_COL(7), QOCX_ACTION_COL(8),
+          QOCX_ACTION_COL(9), QOCX_ACTION_COL(10), QOCX_ACTION_COL(11), QOCX_ACTION_COL(12), QOCX_ACTION_COL(13),
+          QOCX_ACTION_COL(14), QOCX_ACTION_COL(15));
+#undef QOCX_ACTION_COL
+#undef QOCX_ACTION_CMAC2
+#undef QOCX_ACTION_CMAC
+}
+
+// The sweeps of one seed on one wave. KR: the G_k images held in registers beside H0 (those of further
+// controls are read per step). EXACT: K == KR, known to the compiler - a = fma(u1, g1, fma(u0, g0, h0))
+// with no copy of h0 and no branch.
+template <int NB, int KR, bool EXACT>
+static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args, double2* turn) {
     typedef Geo<NB> G;
     constexpr int NP = G::NP, CPL = G::CPL, H = G::H;
-    __shared__ __attribute__((aligned(16))) double2 turn[NP];  // the vector where the cost code reads / writes it
     const SweepArgs& sw = args.sw;
     const int b = blockIdx.x;
     const int lane = lane_id(), i = lane % NP, h = lane / NP;
     const bool g0 = (h == 0);
-    const int nsteps = sw.nsteps, K = args.K, m_max = args.m_max;
+    const int nsteps = sw.nsteps, K = EXACT ? KR : args.K, m_max = args.m_max;
     const int jb = sw.j_begin, je = sw.j_end;
     const double dt = args.dt;
     __builtin_amdgcn_s_setprio(3);  // the serial chain of the evaluation goes first on its SIMD
@@ -58,33 +97,59 @@ __global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
             gi[k][cc] = -dt * e.x;
         }
 
-    const int* words = sw.s_arr + (size_t)b * nsteps;
-    const double* u_b = args.ustep + (size_t)b * nsteps * K;
+    const ScalarInts words = (ScalarInts)(sw.s_arr + (size_t)b * nsteps);
+    const ScalarDoubles u_b = (ScalarDoubles)(args.ustep + (size_t)b * nsteps * K);
+    // What a step reads first: its word and its controls in registers. The sweep asks for those of the
+    // step after the one it is about to run, so that no step begins by waiting on memory.
+    struct StepHead {
+        int word;
+        double u[KR];
+    };
+    auto fetch = [&](int step) __attribute__((always_inline)) {
+        StepHead s;
+        s.word = words[step];
+#pragma unroll
+        for (int k = 0; k < KR; ++k) s.u[k] = k < K ? u_b[(size_t)step * K + k] : 0.0;
+        return s;
+    };
     double are[CPL], aim[CPL];
-    auto build = [&](int step) __attribute__((always_inline)) {
-        const double* u = u_b + (size_t)step * K;
-#pragma unroll
-        for (int cc = 0; cc < CPL; ++cc) {
-            are[cc] = h0r[cc];
-            aim[cc] = h0i[cc];
-        }
-#pragma unroll
-        for (int k = 0; k < KR; ++k)
-            if (k < K) {
-                const double uk = u[k];
-#pragma unroll
-                for (int cc = 0; cc < CPL; ++cc) {
-                    are[cc] = fma(uk, gr[k][cc], are[cc]);
-                    aim[cc] = fma(uk, gi[k][cc], aim[cc]);
-                }
-            }
-        for (int k = KR; k < K; ++k) {
-            const double uk = u[k] * dt;
+    auto build = [&](int step, const StepHead& s) __attribute__((always_inline)) {
+        if constexpr (EXACT) {
 #pragma unroll
             for (int cc = 0; cc < CPL; ++cc) {
-                const double2 e = args.g_rimg[(size_t)k * G::MAT + image_at(cc)];
-                are[cc] = fma(uk, e.y, are[cc]);
-                aim[cc] = fma(-uk, e.x, aim[cc]);
+                double r = h0r[cc], im = h0i[cc];
+#pragma unroll
+                for (int k = 0; k < KR; ++k) {
+                    r = fma(s.u[k], gr[k][cc], r);
+                    im = fma(s.u[k], gi[k][cc], im);
+                }
+                are[cc] = r;
+                aim[cc] = im;
+            }
+        } else {
+#pragma unroll
+            for (int cc = 0; cc < CPL; ++cc) {
+                are[cc] = h0r[cc];
+                aim[cc] = h0i[cc];
+            }
+#pragma unroll
+            for (int k = 0; k < KR; ++k)
+                if (k < K) {
+                    const double uk = s.u[k];
+#pragma unroll
+                    for (int cc = 0; cc < CPL; ++cc) {
+                        are[cc] = fma(uk, gr[k][cc], are[cc]);
+                        aim[cc] = fma(uk, gi[k][cc], aim[cc]);
+                    }
+                }
+            for (int k = KR; k < K; ++k) {
+                const double uk = u_b[(size_t)step * K + k] * dt;
+#pragma unroll
+                for (int cc = 0; cc < CPL; ++cc) {
+                    const double2 e = args.g_rimg[(size_t)k * G::MAT + image_at(cc)];
+                    are[cc] = fma(uk, e.y, are[cc]);
+                    aim[cc] = fma(-uk, e.x, aim[cc]);
+                }
             }
         }
     };
@@ -93,13 +158,7 @@ __global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
     auto matvec = [&](double xr, double xi, double& yr, double& yi) __attribute__((always_inline)) {
         const double sxr = spread_halves(xr, h), sxi = spread_halves(xi, h);
         double s0r = 0, s0i = 0, s1r = 0, s1i = 0;
-        for_each_const(
-            [&](auto Q) __attribute__((always_inline)) {
-                constexpr int k = 4 * decltype(Q)::value;
-                dpp_cmac4<k>(s0r, s0i, s1r, s1i, sxr, sxi, are[k], aim[k], are[k + 1], aim[k + 1],
-                             are[k + 2], aim[k + 2], are[k + 3], aim[k + 3]);
-            },
-            std::make_integer_sequence<int, 4>{});
+        dpp_cmac16(s0r, s0i, s1r, s1i, sxr, sxi, are, aim);
         yr = sum_groups<NB>(s0r + s1r);
         yi = sum_groups<NB>(s0i + s1i);
     };
@@ -107,18 +166,20 @@ __global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
     // terms 0 .. m - 1 go to `keep`. False: the degree is outside the buffers.
     double vr = 0, vi = 0;
     int count = 0;  // lane l: steps at degree l
-    auto step_apply = [&](int step, double sign, double2* keep_base) __attribute__((always_inline)) {
-        const int m = step_degree(words[step]);
+    auto step_apply = [&](int step, const StepHead& s, double sign, double2* keep_base)
+                          __attribute__((always_inline)) {
+        // (one value for the wave, and said so: the branch below is the scalar unit's)
+        const int m = step_degree(__builtin_amdgcn_readfirstlane(s.word));
         if (m < 1 || m > m_max) return false;
-        build(step);
+        build(step, s);
         double2* keep = keep_base ? keep_base + ((size_t)b * nsteps + step) * m_max * NP : nullptr;
         count += (lane == m) ? 1 : 0;
         double sr = vr, si = vi;
         for (int p = 1; p <= m; ++p) {
+            const double f = sign * inv_p(p);  // (asked for before the products, used after them)
             if (keep != nullptr && g0) keep[(size_t)(p - 1) * NP + i] = make_double2(vr, vi);
             double yr, yi;
             matvec(vr, vi, yr, yi);
-            const double f = sign * INV_P.v[p];
             vr = f * yr;
             vi = f * yi;
             sr += vr;
@@ -137,11 +198,16 @@ __global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
         const double2 p0 = jb == 0 ? sw.psi0[i] : args.carry_f[(size_t)b * NP + i];
         vr = p0.x;
         vi = p0.y;
-        for (int step = jb; step < je; ++step)
-            if (!step_apply(step, 1.0, args.kv_f)) {
+        StepHead head = fetch(jb);
+        for (int step = jb; step < je; ++step) {
+            // (the look-ahead of the launch's last step stays inside [jb, je): it reads that step again)
+            const StepHead next = fetch(step + 1 < je ? step + 1 : step);
+            if (!step_apply(step, head, 1.0, args.kv_f)) {
                 refuse();
                 return;
             }
+            head = next;
+        }
         if (count > 0 && lane <= MMAX) atomicAdd(args.degree_counts + lane, count);
         if (je == nsteps) {
             turn[i] = make_double2(vr, vi);  // (every lane group holds the same value: all store)
@@ -169,19 +235,41 @@ __global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
         vr = t.x;
         vi = t.y;
     }
-    for (int step = je - 1; step >= jb; --step)
-        if (!step_apply(step, -1.0, args.kv_b)) {
+    StepHead head = fetch(je - 1);
+    for (int step = je - 1; step >= jb; --step) {
+        const StepHead next = fetch(step - 1 >= jb ? step - 1 : step);
+        if (!step_apply(step, head, -1.0, args.kv_b)) {
             refuse();
             return;
         }
+        head = next;
+    }
     if (jb > 0 && g0) sw.lam_buf[(size_t)b * NP + i] = make_double2(vr, vi);
 }
 
-// One wave per (step, seed). LDS: v_0 .. v_(m-1) [m_max][NP], then two slots for the current rho.
+template <int NB, int KR>
+__global__ __launch_bounds__(64) void action_sweep_kernel(ActionArgs args) {
+    __shared__ __attribute__((aligned(16))) double2 turn[Geo<NB>::NP];  // the vector where the cost code reads / writes it
+    action_sweep_body<NB, KR, false>(args, turn);
+}
+
+// K == 2, the headline's: the same sweeps with the control count a constant
 template <int NB>
-__global__ __launch_bounds__(64, 3) void action_grad_kernel(ActionGradArgs args) {
+__global__ __launch_bounds__(64) void action_sweep_exact_kernel(ActionArgs args) {
+    __shared__ __attribute__((aligned(16))) double2 turn[Geo<NB>::NP];
+    action_sweep_body<NB, 2, true>(args, turn);
+}
+
+// One wave per (step, seed). LDS: v_0 .. v_(m-1) [m_max][NP], then two slots for the current rho.
+// Loads go out in batches of GB and are used after the batch, never one round trip per use. Built for five
+// waves to a SIMD (96 registers: two waves fit beside a sweep wave) - measured against batches of 8 on four
+// waves and of 16 on three, which had fewer round trips and were slower on the headline.
+template <int NB>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void action_grad_kernel(
+    ActionGradArgs args) {
     typedef Geo<NB> G;
-    constexpr int NP = G::NP, CPL = G::CPL, H = G::H;
+    constexpr int NP = G::NP, CPL = G::CPL, H = G::H, GB = 4;
+    static_assert(H == 2, "the two lane groups share the terms of rho");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double2* vl = reinterpret_cast<double2*>(smem);
     double2* rho = vl + (size_t)args.m_max * NP;
@@ -193,7 +281,20 @@ __global__ __launch_bounds__(64, 3) void action_grad_kernel(ActionGradArgs args)
     if (m < 1 || m > args.m_max) return;  // (the sweeps have raised the status bit)
     const double2* vf = args.kv_f + idx * args.m_max * NP;
     const double2* wb = args.kv_b + idx * args.m_max * NP;
-    for (int l = h; l < m; l += H) vl[l * NP + i] = vf[(size_t)l * NP + i];
+    double2 tv = wb[i];
+    // (four terms per lane group asked for at once: the sweeps wrote them, they come from L2 or further)
+    // (a read past the last term reads the last term again and is not stored)
+    for (int l0 = h; l0 < m + h; l0 += 4 * H) {
+        double2 t[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[q] = vf[(size_t)min(l0 + q * H, m - 1) * NP + i];
+        // (the four are used here, whatever the branches below: no load moves down into its store)
+        asm volatile("" : "+v"(t[0].x), "+v"(t[0].y), "+v"(t[1].x), "+v"(t[1].y), "+v"(t[2].x), "+v"(t[2].y),
+                          "+v"(t[3].x), "+v"(t[3].y));
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (l0 + q * H < m) vl[(l0 + q * H) * NP + i] = t[q];
+    }
     double abr[CPL], abi[CPL];
 #pragma unroll
     for (int cc = 0; cc < CPL; ++cc) {
@@ -201,15 +302,19 @@ __global__ __launch_bounds__(64, 3) void action_grad_kernel(ActionGradArgs args)
         abi[cc] = 0;
     }
     wave_sync();
-    double2 tv = wb[i];
     for (int ii = 0; ii < m; ++ii) {
-        // rho_ii: the lane groups share the terms, l = h, h + H, ...
+        // rho_ii: the lane groups share the terms, l = h, h + H, ... The coefficients of a pair of terms
+        // come through the scalar unit (one address for the wave) and a lane group picks its own.
         double rr = 0, ri = 0;
-        for (int l = h; l < m - ii; l += H) {
-            const double c = COEF.c[ii * MMAX + l];
-            const double2 v = vl[l * NP + i];
-            rr = fma(c, v.x, rr);
-            ri = fma(c, v.y, ri);
+        for (int l0 = 0; l0 < m - ii; l0 += H) {
+            const double c0 = COEF.c[ii * MMAX + l0], c1 = COEF.c[ii * MMAX + l0 + 1];
+            const double c = h == 0 ? c0 : c1;
+            const int l = l0 + h;
+            if (l < m - ii) {
+                const double2 v = vl[l * NP + i];
+                rr = fma(c, v.x, rr);
+                ri = fma(c, v.y, ri);
+            }
         }
         rr = sum_groups<NB>(rr);
         ri = sum_groups<NB>(ri);
@@ -219,11 +324,16 @@ __global__ __launch_bounds__(64, 3) void action_grad_kernel(ActionGradArgs args)
         const double2 w = tv;
         if (ii + 1 < m) tv = wb[(size_t)(ii + 1) * NP + i];
 #pragma unroll
-        for (int cc = 0; cc < CPL; ++cc) {
-            const double2 r = slot[cc * H + h];
-            // w * conj(rho)
-            abr[cc] = fma(w.y, r.y, fma(w.x, r.x, abr[cc]));
-            abi[cc] = fma(-w.x, r.y, fma(w.y, r.x, abi[cc]));
+        for (int c0 = 0; c0 < CPL; c0 += GB) {
+            double2 r[GB];  // (the reads of a batch in flight, then its products)
+#pragma unroll
+            for (int cc = 0; cc < GB; ++cc) r[cc] = slot[(c0 + cc) * H + h];
+#pragma unroll
+            for (int cc = 0; cc < GB; ++cc) {
+                // w * conj(rho)
+                abr[c0 + cc] = fma(w.y, r[cc].y, fma(w.x, r[cc].x, abr[c0 + cc]));
+                abi[c0 + cc] = fma(-w.x, r[cc].y, fma(w.y, r[cc].x, abi[c0 + cc]));
+            }
         }
     }
     // gamma_k = sum conj(abar) E_k, E_k = -i dt G_k (krylov_grad_body, unit adjoint)
@@ -231,10 +341,16 @@ __global__ __launch_bounds__(64, 3) void action_grad_kernel(ActionGradArgs args)
     for (int k = 0; k < K; ++k) {
         double acc = 0, acc_im = 0;
 #pragma unroll
-        for (int cc = 0; cc < CPL; ++cc) {
-            const double2 e = args.g_rimg[(size_t)k * G::MAT + cc * 64 + lane];
-            acc = fma(abi[cc], -dts * e.x, fma(abr[cc], dts * e.y, acc));
-            acc_im = fma(abi[cc], -dts * e.y, fma(abr[cc], -dts * e.x, acc_im));
+        for (int c0 = 0; c0 < CPL; c0 += GB) {
+            double2 e[GB];  // the fragments of G_k of a batch asked for before the first is used
+#pragma unroll
+            for (int cc = 0; cc < GB; ++cc) e[cc] = args.g_rimg[(size_t)k * G::MAT + (c0 + cc) * 64 + lane];
+            asm volatile("" ::: "memory");  // (no load of the next batch moves up between these)
+#pragma unroll
+            for (int cc = 0; cc < GB; ++cc) {
+                acc = fma(abi[c0 + cc], -dts * e[cc].x, fma(abr[c0 + cc], dts * e[cc].y, acc));
+                acc_im = fma(abi[c0 + cc], -dts * e[cc].y, fma(abr[c0 + cc], -dts * e[cc].x, acc_im));
+            }
         }
         acc = wave_sum(acc);
         acc_im = wave_sum(acc_im);
@@ -251,7 +367,10 @@ int action_grad_lds_bytes(int m_max) { return (m_max + 2) * Geo<2>::NP * (int)si
 
 void launch_action_sweep(const ActionArgs& a, int batch, hipStream_t st) {
     if (batch <= 0 || a.sw.j_end <= a.sw.j_begin) return;
-    hipLaunchKernelGGL((action::action_sweep_kernel<2, 2>), dim3(batch), dim3(64), 0, st, a);
+    if (a.K == 2)
+        hipLaunchKernelGGL((action::action_sweep_exact_kernel<2>), dim3(batch), dim3(64), 0, st, a);
+    else
+        hipLaunchKernelGGL((action::action_sweep_kernel<2, 2>), dim3(batch), dim3(64), 0, st, a);
 }
 
 void launch_action_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st) {
