@@ -617,6 +617,10 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   - never more terms than the 1-norm alone asks for; the headline runs degree 8 instead
  *                   of 11. 0: the 1-norm alone, bit for bit what the route computed before the knob
  *                   existed. Any other value is QOCX_ERR_ARG. Pade orders and squarings stay on the 1-norm.
+ *   "action_plan"   1 (default): in the two-sided pipeline each sweep of the matrix-free route runs to the
+ *                   crossing of the two as ONE launch (nothing is factored on this route, so its segment
+ *                   boundaries there buy nothing) and in pieces from there on; 0: one launch per piece, as
+ *                   before the knob existed. The same bits. Any other value is QOCX_ERR_ARG.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;

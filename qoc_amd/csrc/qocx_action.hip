@@ -63,6 +63,11 @@ __device__ __forceinline__ void dpp_cmac16(double& r0, double& i0, double& r1, d
 // The sweeps of one seed on one wave. KR: the G_k images held in registers beside H0 (those of further
 // controls are read per step). EXACT: K == KR, known to the compiler - a = fma(u1, g1, fma(u0, g0, h0))
 // with no copy of h0 and no branch.
+// The vector lives in SPREAD FORM (qocx_action_core.h) from the launch's first load to its last store: lane
+// L holds the entry idx = 16 (L >> 5) + (L & 15), which is what the multiply-adds broadcast from, and the
+// exchange that sums the lane groups' partial products leaves its result in that form again. Only the
+// loads and stores of the vector know about it (the lanes with (L & 16) == 0 store, one per entry); the
+// generator's images stay where they were, lane (h, i): row i, columns 16 h ..
 template <int NB, int KR, bool EXACT>
 static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args, double2* turn) {
     typedef Geo<NB> G;
@@ -70,7 +75,8 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
     const SweepArgs& sw = args.sw;
     const int b = blockIdx.x;
     const int lane = lane_id(), i = lane % NP, h = lane / NP;
-    const bool g0 = (h == 0);
+    const int idx = spread_index(lane);       // the entry of the vector this lane holds
+    const bool holder = spread_holder(lane);  // ... and stores
     const int nsteps = sw.nsteps, K = EXACT ? KR : args.K, m_max = args.m_max;
     const int jb = sw.j_begin, je = sw.j_end;
     const double dt = args.dt;
@@ -153,17 +159,15 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
             }
         }
     };
-    // y = a x, x in registers (every lane group holds x[i]): the lane group's 16 columns, then the sum
-    // of the two lane groups of the row
+    // y = a x, x and y in spread form: the lane group's 16 columns, then the sum of the two lane groups'
+    // partial products of a row, delivered to the lanes that hold that row's entry
     auto matvec = [&](double xr, double xi, double& yr, double& yi) __attribute__((always_inline)) {
-        const double sxr = spread_halves(xr, h), sxi = spread_halves(xi, h);
         double s0r = 0, s0i = 0, s1r = 0, s1i = 0;
-        dpp_cmac16(s0r, s0i, s1r, s1i, sxr, sxi, are, aim);
-        yr = sum_groups<NB>(s0r + s1r);
-        yi = sum_groups<NB>(s0i + s1i);
+        dpp_cmac16(s0r, s0i, s1r, s1i, xr, xi, are, aim);
+        sum_spread2(s0r + s1r, s0i + s1i, yr, yi);
     };
-    // One step: the vector (vr, vi) - every lane group holds it - becomes sum_p (sign a)^p / p! v; the
-    // terms 0 .. m - 1 go to `keep`. False: the degree is outside the buffers.
+    // One step: the vector (vr, vi), in spread form, becomes sum_p (sign a)^p / p! v; the terms
+    // 0 .. m - 1 go to `keep`. False: the degree is outside the buffers.
     double vr = 0, vi = 0;
     int count = 0;  // lane l: steps at degree l
     auto step_apply = [&](int step, const StepHead& s, double sign, double2* keep_base)
@@ -177,7 +181,7 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
         double sr = vr, si = vi;
         for (int p = 1; p <= m; ++p) {
             const double f = sign * inv_p(p);  // (asked for before the products, used after them)
-            if (keep != nullptr && g0) keep[(size_t)(p - 1) * NP + i] = make_double2(vr, vi);
+            if (keep != nullptr && holder) keep[(size_t)(p - 1) * NP + idx] = make_double2(vr, vi);
             double yr, yi;
             matvec(vr, vi, yr, yi);
             vr = f * yr;
@@ -195,7 +199,7 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
 
     // ---- forward sweep ----------------------------------------------------------------------
     if (sw.phase & 1) {
-        const double2 p0 = jb == 0 ? sw.psi0[i] : args.carry_f[(size_t)b * NP + i];
+        const double2 p0 = jb == 0 ? sw.psi0[idx] : args.carry_f[(size_t)b * NP + idx];
         vr = p0.x;
         vi = p0.y;
         StepHead head = fetch(jb);
@@ -210,14 +214,14 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
         }
         if (count > 0 && lane <= MMAX) atomicAdd(args.degree_counts + lane, count);
         if (je == nsteps) {
-            turn[i] = make_double2(vr, vi);  // (every lane group holds the same value: all store)
+            turn[idx] = make_double2(vr, vi);  // (both holders of an entry hold the same value: all store)
             wave_sync();
             const double cost = eval_costs<NB>(sw, false, true, turn, nullptr, h, i);
             if (sw.unit_adjoint && sw.want_grad) unit_adjoint_scales<NB>(sw, turn, b, h, i);
-            if (g0) sw.final_out[(size_t)b * NP + i] = make_double2(vr, vi);
+            if (holder) sw.final_out[(size_t)b * NP + idx] = make_double2(vr, vi);
             if (lane == 0) sw.cost_out[b] = cost;
-        } else if (g0) {
-            args.carry_f[(size_t)b * NP + i] = make_double2(vr, vi);
+        } else if (holder) {
+            args.carry_f[(size_t)b * NP + idx] = make_double2(vr, vi);
         }
     }
     if (!(sw.phase & 2)) return;
@@ -227,11 +231,11 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
     if (je == nsteps) {
         unit_adjoint_seed<NB>(sw, turn, 0, 1, h, i);
         wave_sync();
-        const double2 t = turn[i];
+        const double2 t = turn[idx];
         vr = t.x;
         vi = t.y;
     } else {
-        const double2 t = sw.lam_buf[(size_t)b * NP + i];
+        const double2 t = sw.lam_buf[(size_t)b * NP + idx];
         vr = t.x;
         vi = t.y;
     }
@@ -244,7 +248,7 @@ static __device__ __forceinline__ void action_sweep_body(const ActionArgs& args,
         }
         head = next;
     }
-    if (jb > 0 && g0) sw.lam_buf[(size_t)b * NP + i] = make_double2(vr, vi);
+    if (jb > 0 && holder) sw.lam_buf[(size_t)b * NP + idx] = make_double2(vr, vi);
 }
 
 template <int NB, int KR>

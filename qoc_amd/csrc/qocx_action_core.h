@@ -1,7 +1,8 @@
 // qocx_action_core.h - what the matrix-free kernels of 17 <= n <= 32 share (qocx_action.hip: one state
 // per seed; qocx_action_states.hip: two to four): the tables of 1 / p and of the reverse rule's
 // coefficients, the four-column multiply-add with the broadcast inside, the spread of a vector over the
-// rows of 16 lanes.
+// rows of 16 lanes - and the spread form in which the one-state sweeps keep their vector from term to term,
+// with the exchange that sums the lane groups' partial products into it.
 #ifndef QOCX_ACTION_CORE_H
 #define QOCX_ACTION_CORE_H
 
@@ -67,6 +68,35 @@ __device__ __forceinline__ double spread_halves(double v, int h) {
     auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
     auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
     return h == 0 ? make_f64((int)a[0], (int)b[0]) : make_f64((int)a[1], (int)b[1]);
+}
+
+// SPREAD FORM of a vector of 32 entries on one wave (the sweeps of qocx_action.hip keep theirs in it): lane
+// L holds the entry 16 (L >> 5) + (L & 15) - the rows 0 and 1 of 16 lanes x[0 .. 15], the rows 2 and 3
+// x[16 .. 31], which is what spread_halves makes and what the multiply-adds above broadcast from. Every
+// entry has two holders; the one with (L & 16) == 0 stores it.
+__device__ __forceinline__ int spread_index(int lane) { return 16 * (lane >> 5) + (lane & 15); }
+__device__ __forceinline__ bool spread_holder(int lane) { return (lane & 16) == 0; }
+
+// The sum over the two lane groups of the partial products p of a matrix-vector product (lane (h, i): row
+// i, the columns of lane group h), delivered in spread form. The rows of 16 lanes hold [p0, p1, p2, p3]:
+//   permlane16_swap of p with its copy   X = [p0, p0, p2, p2], Y = [p1, p1, p3, p3]
+//   permlane32_swap of X and Y           X = [p0, p0, p1, p1], Y = [p2, p2, p3, p3]
+// and X + Y is p(0, i) + p(1, i) at both holders of entry i: the two addends of sum_groups<2>, so the same
+// bits, without the trip back to "lane (h, i) holds x[i]" that the next product would undo at once. A pair
+// of values (re, im) at a time, so that one chain's instructions fill the wait states of the other's swaps.
+__device__ __forceinline__ void sum_spread2(double pr, double pi, double& yr, double& yi) {
+    const unsigned rl = (unsigned)__double2loint(pr), rh = (unsigned)__double2hiint(pr);
+    const unsigned il = (unsigned)__double2loint(pi), ih = (unsigned)__double2hiint(pi);
+    auto a = __builtin_amdgcn_permlane16_swap(rl, rl, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(rh, rh, false, false);
+    auto c = __builtin_amdgcn_permlane16_swap(il, il, false, false);
+    auto d = __builtin_amdgcn_permlane16_swap(ih, ih, false, false);
+    auto e = __builtin_amdgcn_permlane32_swap(a[0], a[1], false, false);
+    auto f = __builtin_amdgcn_permlane32_swap(b[0], b[1], false, false);
+    auto g = __builtin_amdgcn_permlane32_swap(c[0], c[1], false, false);
+    auto k = __builtin_amdgcn_permlane32_swap(d[0], d[1], false, false);
+    yr = make_f64((int)e[0], (int)f[0]) + make_f64((int)e[1], (int)f[1]);
+    yi = make_f64((int)g[0], (int)k[0]) + make_f64((int)g[1], (int)k[1]);
 }
 
 }  // namespace action

@@ -1468,7 +1468,7 @@ static const char* const kVariantKnobs[] = {
     "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
     "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
     "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs",
-    "action_degree"};
+    "action_degree", "action_plan"};
 static const char* const kDiagKnobs[] = {"dbg_skip", "sweep3_dbg", "sweep3_stamps", "lindblad_stamps",
                                          "k1a_stamps", "k1a_dbg", "peak_mode"};
 
@@ -1493,6 +1493,8 @@ int qocx_debug_set_knob(qocx_ctx* ctx, const char* name, int64_t value) {
             return fail(QOCX_ERR_ARG, "action_costs must be 0 or 1");
         if (strcmp(name, "action_degree") == 0 && value != 0 && value != 1)
             return fail(QOCX_ERR_ARG, "action_degree must be 0 or 1");
+        if (strcmp(name, "action_plan") == 0 && value != 0 && value != 1)
+            return fail(QOCX_ERR_ARG, "action_plan must be 0 or 1");
         ctx->knobs[name] = value;
         return 0;
     }

@@ -850,6 +850,8 @@ int run_one_sided(ResidentChunk& c) {
 // The compute stream factors from both ends towards the middle; each sweep takes a segment as soon
 // as it is factored AND the sweep has finished the one before it (stream order); K3 follows from
 // the middle outwards.
+// On the matrix-free route there is nothing to factor: each sweep runs to the crossing of the two as ONE
+// launch and in pieces from there on (knob "action_plan", below).
 int run_two_sided(ResidentChunk& c) {
     qocx_ctx* ctx = c.ctx;
     const int nseg = c.nseg;
@@ -876,6 +878,18 @@ int run_two_sided(ResidentChunk& c) {
     }
     first[nseg] = (int)piece.size();
     const int P = (int)piece.size();
+    const int mid = first[nseg / 2];  // the piece at which the sweeps cross
+    // The matrix-free route factors nothing (factor_segment only records its event), and no gradient launch
+    // can begin before the sweeps have crossed: the launch boundaries of a sweep's way TO the crossing buy
+    // nothing and each costs a launch gap and a start-up on the serial chain. So that way is ONE launch
+    // (knob "action_plan" = 1, the default), with the events of all its pieces recorded behind it; from the
+    // crossing outwards the pieces stay, for the gradient to follow closely. A step's arithmetic does not
+    // depend on where a launch begins: the same bits. Headline: the sweeps reach the crossing at 1.19 /
+    // 1.30 ms instead of 1.64 / 1.67 (profiles/action_spread_timeline.txt).
+    // (Measured and not kept, DESIGN.md 6: the pieces mid + d and mid - 1 - d as the two step ranges of ONE
+    // gradient launch - the forward sweep is the faster of the two, so such a launch waits 0.1 ms for a
+    // partner that the single piece does not need: 0.06-0.1 ms slower per evaluation.)
+    const bool fuse_inward = c.r.action && ctx->knob("action_plan", 1) != 0;
     std::vector<char> factored(nseg, 0);
     int next_f = 0, next_b = nseg - 1;
     // (the adjoint sweep is the slower of the two - it gathers its images transposed -: with one control
@@ -889,6 +903,14 @@ int run_two_sided(ResidentChunk& c) {
         factored[i] = 1;
         while (next_f < nseg && factored[next_f]) {
             HIP_TRY(hipStreamWaitEvent(sf, ctx->ev_factored[next_f], 0));
+            // (every ev_factored of this route follows the step table on the compute stream, which is all a
+            // sweep waits for: the first of them stands for the segments behind it)
+            if (fuse_inward && next_f == 0) {  // the segments below the crossing in one launch
+                if (piece[mid - 1].hi > piece[0].lo) c.sweep(piece[0].lo, piece[mid - 1].hi, 1, sf);
+                for (int p = 0; p < mid; ++p) HIP_TRY(hipEventRecord(ctx->ev_fwd[p], sf));
+                next_f = nseg / 2;
+                continue;
+            }
             for (int p = first[next_f]; p < first[next_f + 1]; ++p) {
                 if (piece[p].hi > piece[p].lo) c.sweep(piece[p].lo, piece[p].hi, 1, sf);
                 HIP_TRY(hipEventRecord(ctx->ev_fwd[p], sf));
@@ -897,6 +919,12 @@ int run_two_sided(ResidentChunk& c) {
         }
         while (next_b >= 0 && factored[next_b]) {
             HIP_TRY(hipStreamWaitEvent(sb, ctx->ev_factored[next_b], 0));
+            if (fuse_inward && next_b == nseg - 1) {  // the segments from the crossing up in one launch
+                if (piece[P - 1].hi > piece[mid].lo) c.sweep(piece[mid].lo, piece[P - 1].hi, 2, sb);
+                for (int p = P - 1; p >= mid; --p) HIP_TRY(hipEventRecord(ctx->ev_swept[p], sb));
+                next_b = nseg / 2 - 1;
+                continue;
+            }
             for (int p = first[next_b + 1] - 1; p >= first[next_b]; --p) {
                 if (piece[p].hi > piece[p].lo) c.sweep(piece[p].lo, piece[p].hi, 2, sb);
                 HIP_TRY(hipEventRecord(ctx->ev_swept[p], sb));
@@ -906,7 +934,6 @@ int run_two_sided(ResidentChunk& c) {
     }
     // K3 from the middle outwards: a piece is complete once the forward sweep (going up) and the
     // adjoint sweep (going down) have both crossed it
-    const int mid = first[nseg / 2];
     for (int d = 0; d < P; ++d)
         for (int p : {mid + d, mid - 1 - d}) {
             if (p < 0 || p >= P || piece[p].hi <= piece[p].lo) continue;
