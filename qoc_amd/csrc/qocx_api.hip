@@ -371,6 +371,19 @@ int upload_operators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
         ctx->h0_norm2_max = sharpen(p->h0, ctx->h0_norm_max);
         for (int k = 0; k < K; ++k) ctx->g_norm2_max[k] = sharpen(p->g + (size_t)k * nn2, ctx->g_norm_max[k]);
     }
+    // E_k = -i dt G_k for the gradient kernel of the matrix-free route at 17 <= n <= 32 (qocx_action.hip):
+    // (dt y, -dt x) of every element of the r image, the products the kernel formed per step before. Here,
+    // because this is the one place that writes ctx->dt or the G_k images: the image cannot go stale.
+    if (ctx->nb == 2 && nt == 1 && K > 0) {
+        const int np = ctx->np;
+        const size_t mat = (size_t)np * np;
+        std::vector<double2> img(K * mat);
+        for (int k = 0; k < K; ++k) r_image(p->g + (size_t)k * nn2, n, np, false, img.data() + k * mat);
+        for (double2& e : img) e = make_double2(ctx->dt * e.y, -ctx->dt * e.x);
+        if (ctx->g_eimg.upload(img, ctx->stream)) return QOCX_ERR_HIP;
+    } else {
+        ctx->g_eimg.release();
+    }
     return ctx->h0.build(p->h0, (size_t)nt, n, ctx->nb, ctx->stream) ||
                    ctx->g.build(p->g, (size_t)nt * K, n, ctx->nb, ctx->stream) ||
                    (K > 0 && (ctx->g_norm_dev.upload(ctx->g_norm_max, ctx->stream) ||  // step table

@@ -226,6 +226,9 @@ struct ActionGradArgs {
     int step0;                 // grid.x covers steps [step0, step0 + gridDim.x), grid.y the seeds
     double dt;
     double* gstep;             // [B][nsteps][K][2]: gamma_k as KrylovArgs::gstep under the unit adjoint
+    // [K] E_k = -i dt G_k in the order of g_rimg, (re, im) = (dt G.y, -dt G.x): what action_grad_kernel
+    // contracts with (qocx_action.hip). The problem setter builds it, where dt and the G_k are set.
+    const double2* e_img = nullptr;
 };
 void launch_action_sweep(const ActionArgs& a, int batch, hipStream_t st);
 void launch_action_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);

@@ -224,6 +224,9 @@ struct qocx_ctx {
     double h0_norm2_max = 0;
     std::vector<double> g_norm2_max;
     OperatorImages h0, g;  // [nt], [nt][K]
+    // [K] E_k = -i dt G_k in the order of g.r (ActionGradArgs::e_img), where the matrix-free route of
+    // 17 <= n <= 32 can run (nt == 1); upload_operators writes it with g and dt, and nothing else writes those
+    DevBuf<double2> g_eimg;
     DevBuf<double2> psi0, cost_vectors;
     DevBuf<qocx::StepInterp> interp;
     DevBuf<qocx::DevCost> costs;

@@ -700,6 +700,9 @@ struct ResidentChunk {
             aa.degree_counts = ctx->action_counts.p;
             ga.kv_f = ctx->kry_f.p; ga.kv_b = ctx->kry_b.p; ga.s_arr = ctx->s_arr.p; ga.g_rimg = ctx->g.r.p;
             ga.K = ctx->K; ga.m_max = r.m_max; ga.nsteps = nsteps; ga.dt = ctx->dt; ga.gstep = ctx->gstep.p;
+            ga.e_img = ctx->g_eimg.p;
+            if (want_grad && ctx->nb == 2 && S == 1 && !r.action_costs && ga.e_img == nullptr)
+                return fail(QOCX_ERR_STATE, "the matrix-free gradient has no image of -i dt G_k (upload_operators)");
             sga.S = S;
         }
         return 0;
