@@ -621,6 +621,13 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   crossing of the two as ONE launch (nothing is factored on this route, so its segment
  *                   boundaries there buy nothing) and in pieces from there on; 0: one launch per piece, as
  *                   before the knob existed. The same bits. Any other value is QOCX_ERR_ARG.
+ *   "action_small"  0 (default): n <= 16 stays on the Pade route. 1: one state, Hermitian H, n <= 16, every
+ *                   other condition of "action" (one final TargetStateInfidelity, "pade_order" 0, not latency
+ *                   mode, bound <= theta_18): matrix-free sweeps there too (qocx_action16.hip: one wave per
+ *                   seed, its four rows of 16 lanes the four real products of a complex one), decided before
+ *                   and independent of "sweep_inverse_small", "pack8" and "sweep_umode". Any other value is
+ *                   QOCX_ERR_ARG. Opt-in: at 0 every problem launches what it always launched; no effect
+ *                   above n = 16; "action_states" and "action_costs" stay at 17 <= n <= 32.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;

@@ -30,6 +30,8 @@ _FD_STEP = 1e-6
 # profiles/action_states.jsonl).
 ACTION_STATES_DEFAULT = 2
 MATRIX_FREE_VALUES = ("default", "wide", "states", "all", "costs")
+# ... and the value that opts n <= 16 in (knob "action_small"), beside the tuple existing callers enumerate
+MATRIX_FREE_SMALL = "small"
 
 
 def interpolation_keywords(backend, setter, interpolation_policy):
@@ -603,8 +605,12 @@ class SchroedingerEvaluator(_Evaluator):
         state at 17 <= n <= 32 under any set of costs the device evaluates - step costs
         (TargetStateInfidelityTime, ForbidStates), several costs, an incoherent target - instead of
         the one final TargetStateInfidelity (knob "action_costs" = 1; opt-in, not part of "all"); such
-        a problem is not put into latency mode either. A backend without knobs ignores it; any other
-        value is a ValueError.
+        a problem is not put into latency mode either. "small" takes them for one-state Hermitian
+        problems at n <= 16 under the one final TargetStateInfidelity (knob "action_small" = 1; a
+        wave per seed whose four rows of 16 lanes do the four real products of a complex one;
+        opt-in because the Pade route there is what existing callers measure and assert on, and
+        not part of "all"); latency mode keeps its route, the new one yields to it as "wide" does.
+        A backend without knobs ignores it; any other value is a ValueError.
         latency_mode: the evaluator will be asked for ONE control array at a time (the
         reference's evolve_* / grape_* entry points). Where the cost is a single final
         TargetStateInfidelity the engine then runs its two-sided pipeline (round 3: forward and
@@ -622,9 +628,9 @@ class SchroedingerEvaluator(_Evaluator):
         self.interpolation_policy = interpolation_policy
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
-        if not (isinstance(matrix_free, str) and matrix_free in MATRIX_FREE_VALUES):
-            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\", \"all\" or \"costs\", "
-                             "not {!r}.".format(matrix_free))
+        if not (isinstance(matrix_free, str) and matrix_free in MATRIX_FREE_VALUES + (MATRIX_FREE_SMALL,)):
+            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\", \"all\", \"costs\" or "
+                             "\"small\", not {!r}.".format(matrix_free))
         self.matrix_free = matrix_free
         initial_states = np.asarray(initial_states)
         self.state_count = initial_states.shape[0]
@@ -747,6 +753,8 @@ class SchroedingerEvaluator(_Evaluator):
                 self.backend.set_knob("action_states", ACTION_STATES_DEFAULT)
             if matrix_free == "costs":
                 self.backend.set_knob("action_costs", 1)
+            if matrix_free == MATRIX_FREE_SMALL:
+                self.backend.set_knob("action_small", 1)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:

@@ -371,10 +371,10 @@ int upload_operators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
         ctx->h0_norm2_max = sharpen(p->h0, ctx->h0_norm_max);
         for (int k = 0; k < K; ++k) ctx->g_norm2_max[k] = sharpen(p->g + (size_t)k * nn2, ctx->g_norm_max[k]);
     }
-    // E_k = -i dt G_k for the gradient kernel of the matrix-free route at 17 <= n <= 32 (qocx_action.hip):
+    // E_k = -i dt G_k for the gradient kernels of the matrix-free route at n <= 32 (qocx_action.hip, qocx_action16.hip):
     // (dt y, -dt x) of every element of the r image, the products the kernel formed per step before. Here,
     // because this is the one place that writes ctx->dt or the G_k images: the image cannot go stale.
-    if (ctx->nb == 2 && nt == 1 && K > 0) {
+    if (ctx->nb <= 2 && nt == 1 && K > 0) {
         const int np = ctx->np;
         const size_t mat = (size_t)np * np;
         std::vector<double2> img(K * mat);
@@ -1481,7 +1481,7 @@ static const char* const kVariantKnobs[] = {
     "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
     "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
     "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs",
-    "action_degree", "action_plan"};
+    "action_degree", "action_plan", "action_small"};
 static const char* const kDiagKnobs[] = {"dbg_skip", "sweep3_dbg", "sweep3_stamps", "lindblad_stamps",
                                          "k1a_stamps", "k1a_dbg", "peak_mode"};
 
@@ -1508,6 +1508,8 @@ int qocx_debug_set_knob(qocx_ctx* ctx, const char* name, int64_t value) {
             return fail(QOCX_ERR_ARG, "action_degree must be 0 or 1");
         if (strcmp(name, "action_plan") == 0 && value != 0 && value != 1)
             return fail(QOCX_ERR_ARG, "action_plan must be 0 or 1");
+        if (strcmp(name, "action_small") == 0 && value != 0 && value != 1)
+            return fail(QOCX_ERR_ARG, "action_small must be 0 or 1");
         ctx->knobs[name] = value;
         return 0;
     }

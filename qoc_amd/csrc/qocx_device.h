@@ -249,6 +249,11 @@ void launch_action_states_grad(const ActionStatesGradArgs& a, int nsteps, int ba
 void launch_action4_sweep(int n, const ActionArgs& a, int batch, hipStream_t st);
 void launch_action4_grad(int n, const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
 int action4_grad_lds_bytes(int n, int m_max, int K);
+// ... at n <= 16 (qocx_action16.hip, knob "action_small" = 1; NP = 16 in the buffer shapes): one wave per
+// seed whose four rows of 16 lanes do the four real products of a complex one; the same arguments,
+// buffers and contract
+void launch_action16_sweep(const ActionArgs& a, int batch, hipStream_t st);
+void launch_action16_grad(const ActionGradArgs& a, int nsteps, int batch, hipStream_t st);
 // ... one state at 17 <= n <= 32 under any set of device cost descriptors (qocx_action_costs.hip, knob
 // "action_costs"): the same arguments and buffers; sw.unit_adjoint is 0, the forward launches carry the
 // partial cost in sw.cost_out, the adjoint sweep carries the true cotangent and reads psi_j from kv_f,

@@ -281,9 +281,9 @@ struct ResidentRoute {
     bool all_dominant;   // every Pade denominator diagonally dominant
     bool pack8;          // n <= 8: two steps per 16 x 16 tile through K1a and K1b
     bool umode;          // the propagator itself in the Q image, one product per sweep sub-step
-    bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip, qocx_action4.hip)
+    bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip, qocx_action4.hip, qocx_action16.hip)
     bool action_costs;   // ... under any device cost descriptors: the general adjoint, one-sided (qocx_action_costs.hip)
-    bool action_table;   // ... at 33 <= n <= 64: launch_step_table for the sweeps alone (no K1a reads it)
+    bool action_table;   // ... at 33 <= n <= 64 and at n <= 16: launch_step_table for the sweeps alone (no K1a reads it)
     int m_max;           // ... and the Taylor terms per step its buffers hold
 };
 
@@ -363,7 +363,11 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     const int64_t action_knob = ctx->knob("action", 1);
     const bool table_ok = !explicit_gen && r.nodes == 1 && !r.eff && !r.dense && ctx->K > 0 &&
                           ctx->g_norm_dev.p != nullptr;
+    // Knob "action_small": 0 (default) never at n <= 16; 1: there too (qocx_action16.hip: one wave per seed, its
+    // four rows of 16 lanes the four real products of a complex one), with the step table launched for the
+    // sweeps alone as above 32. Opt-in: the Pade route at n <= 16 is what existing callers measure and assert on.
     const bool sized = nb == 2 ? (action_knob != 0 && r.step_table)
+                     : nb == 1 ? (ctx->knob("action_small", 0) == 1 && table_ok)
                                : (nb == 4 && action_knob == 2 && table_ok);  // (33 <= n <= 64: padded to 64)
     // Knob "action_costs": 0 (default) the cost set must be the one final TargetStateInfidelity of the
     // unit adjoint; 1: a problem that meets every other condition at S = 1, 17 <= n <= 32 takes the route
@@ -371,8 +375,11 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // of qocx_action_costs.hip, whose adjoint sweep carries the true cotangent: r.unit is false there
     // (the scatter kernel applies no scalar) and the schedule is one-sided whatever "bidir" says. A
     // unit_ok problem keeps the kernels above whatever this knob says.
+    // (Nothing here reads inverse_sweep, pack8 or umode: above n = 16 the inverse-image sweep exists in latency
+    // mode only, which the route yields to by name, and at n <= 16, where it is the DEFAULT, the route is
+    // decided without it - and switches all three off below, so that no buffer or launch follows them.)
     const bool except_costs = allow_action && sized && states_ok && ctx->nt == 1 && ctx->hermitian &&
-                              ctx->inj_count == 0 && !r.latency && !r.inverse_sweep && !ctx->keep_step_states &&
+                              ctx->inj_count == 0 && !r.latency && !ctx->keep_step_states &&
                               ctx->knob("pade_order", 0) == 0 &&
                               host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
     const bool unit_costs = ctx->unit_ok && !ctx->has_step_costs && ctx->knob("unit_adjoint", 1) != 0;
@@ -380,6 +387,7 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
                      ctx->cost_count > 0;
     r.action = (except_costs && unit_costs) || r.action_costs;
     r.action_table = r.action && nb != 2;
+    if (r.action) r.inverse_sweep = r.pack8 = r.umode = false;
     // (the device's bound of a step is the host's up to the rounding of the interpolation)
     // Knob "action_degree": 1 (default) the degree of a step is the lesser of the Al-Mohy-Higham degree of
     // its 1-norm bound and the degree the remainder of a NORMAL generator needs at its spectral-norm bound
@@ -701,7 +709,7 @@ struct ResidentChunk {
             ga.kv_f = ctx->kry_f.p; ga.kv_b = ctx->kry_b.p; ga.s_arr = ctx->s_arr.p; ga.g_rimg = ctx->g.r.p;
             ga.K = ctx->K; ga.m_max = r.m_max; ga.nsteps = nsteps; ga.dt = ctx->dt; ga.gstep = ctx->gstep.p;
             ga.e_img = ctx->g_eimg.p;
-            if (want_grad && ctx->nb == 2 && S == 1 && !r.action_costs && ga.e_img == nullptr)
+            if (want_grad && ctx->nb <= 2 && S == 1 && !r.action_costs && ga.e_img == nullptr)
                 return fail(QOCX_ERR_STATE, "the matrix-free gradient has no image of -i dt G_k (upload_operators)");
             sga.S = S;
         }
@@ -783,6 +791,7 @@ struct ResidentChunk {
                 if (r.action_costs) qocx::launch_action_costs_sweep(aa, bc, st);
                 else if (ctx->S > 1) qocx::launch_action_states_sweep(aa, bc, st);
                 else if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
+                else if (ctx->nb == 1) qocx::launch_action16_sweep(aa, bc, st);
                 else qocx::launch_action4_sweep(ctx->n, aa, bc, st);
             } else if (r.dense) qocx::launch_sweepd(sa, bc, st);
             else if (r.inverse_sweep) qocx::launch_sweepi(ctx->nb, sa, bc, st);
@@ -806,6 +815,7 @@ struct ResidentChunk {
                 sga.g = ga;
                 qocx::launch_action_states_grad(sga, len, bc, cs);
             } else if (ctx->nb == 2) qocx::launch_action_grad(ga, len, bc, cs);
+            else if (ctx->nb == 1) qocx::launch_action16_grad(ga, len, bc, cs);
             else qocx::launch_action4_grad(ctx->n, ga, len, bc, cs);
         } else if (!(dbg_skip & 4)) qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
         if (r.nodes > 1) {
