@@ -157,7 +157,7 @@ def step_controls(controls, N, T, interpolation="linear", mutant=None):
 
 
 def evaluate_features(h0, g, psi0, costs, N, T, controls, interpolation="linear", cost_eval_step=1,
-                      mutant=None, ghost=None, scalar=None):
+                      mutant=None, ghost=None, scalar=None, first=2):
     """The route's mathematics at any control count K, any knot count Nc, either interpolation, psi0
     (S, n) and any oracle costs (oracle/qoc_numpy.py: cost and states_bar on states (S, n, 1)): the
     general adjoint of tests/action_costs_model.py - the sweep carries the true cotangent, the step
@@ -166,7 +166,9 @@ def evaluate_features(h0, g, psi0, costs, N, T, controls, interpolation="linear"
 
     scalar: the final cotangent is scalar * target instead of the cost's own (the unit adjoint with a
     scalar from elsewhere; one final coherent TargetStateInfidelity only). mutant: one of MUTANTS - a
-    plausibly wrong kernel; ghost: the matrix a kernel that keeps two images would read at K = 1.
+    plausibly wrong kernel; ghost: the matrix a kernel that keeps two images would read at K = 1; first: the
+    control at which the "k >= 2" mutants begin - the boundary between two ways a kernel holds its images
+    (2: the register images of qocx_action.hip; 1 and 4: registers / LDS / streamed in qocx_action16.hip).
     Returns dict(cost, grads [Nc, K], final (S, n), degrees, scalar - that of the unit adjoint or None)."""
     controls = np.asarray(controls, dtype=np.float64)
     nc, K = controls.shape
@@ -196,8 +198,8 @@ def evaluate_features(h0, g, psi0, costs, N, T, controls, interpolation="linear"
         u = ustep[j]
         bound = abs(dt) * (h0n + sum(abs(u[k]) * gn[k] for k in range(K)))
         degrees.append(degree_for(bound))
-        h = h0 + sum(u[k] * g[k] for k in range(min(K, 2)))
-        for k in range(2, K):
+        h = h0 + sum(u[k] * g[k] for k in range(min(K, first)))
+        for k in range(first, K):
             if mutant == "generator without k >= 2":
                 continue
             uk = ustep[(j + 1) % nsteps][k] if mutant == "wrong step for k >= 2" else u[k]
@@ -232,7 +234,7 @@ def evaluate_features(h0, g, psi0, costs, N, T, controls, interpolation="linear"
             abar = abar + generator_cotangent(vs[j][s], w, degrees[j])
         lam = np.array(new)
         for k in range(K):
-            if mutant == "gradient without k >= 2" and k >= 2:
+            if mutant == "gradient without k >= 2" and k >= first:
                 continue
             gk = np.real(np.sum(np.conj(abar) * (-1j * dt * g[k])))
             for knot, weight in weights[j]:

@@ -12,6 +12,10 @@ kernel, and is reachable by a correct one:
     at the wrong step, a second image at K = 1, a slice index off by one, the two knot weights
     transposed, the seed-0 scalar on every item of an ensemble - misses one of the project's gates by a
     factor of 100 on some case.
+
+The cases of the n <= 16 kernel (qocx_action16.hip, tag "small") are held to the same three proofs, the
+control mutants also at its own boundaries - k >= 1 (registers / LDS) and k >= 4 (LDS / streamed) -, and its
+one final incoherent target of scale 0.7 to a scale mutant.
 """
 
 import numpy as np
@@ -23,6 +27,12 @@ from tests.helpers import rel_err
 
 CASES = [c + (af.LINEAR, af.N) for c in af.CONTROL_COUNTS] + af.INTERPOLATIONS
 TABLES = dict(ensemble=af.ensemble, sweep=af.sweep, durations=af.durations)
+TABLES.update({"small-ensemble": lambda: af.ensemble("small"), "small-sweep": lambda: af.sweep("small"),
+               "small-durations": lambda: af.durations("small"), "small-ensemble-streamed": af.ensemble_streamed})
+STARTS = [(v, "one") for v in af.OPTIMISER_STARTS] + [(v, "small") for v in af.OPTIMISER_STARTS]
+# the boundaries of qocx_action16.hip, for the mutants that drop or misplace the controls k >= first:
+# 1 (registers / LDS) where K > 1, 4 (LDS / streamed) where K > 4
+SMALL_FIRSTS = (1, 4)
 
 
 def case_id(case):
@@ -74,11 +84,12 @@ def test_a_seed_table_stays_on_the_route_and_spans_three_degrees(name):
     assert len(degrees) >= 3, degrees
 
 
-@pytest.mark.parametrize("variant", af.OPTIMISER_STARTS)
-def test_an_optimiser_start_stays_on_the_route_and_its_clip_binds(variant):
+@pytest.mark.parametrize("variant, kernel", STARTS, ids=[v if k == "one" else k + "-" + v for v, k in STARTS])
+def test_an_optimiser_start_stays_on_the_route_and_its_clip_binds(variant, kernel):
     """The bound of the upload and the bound opt_clip commits from its norms (a complex control: both
     channels up to the modulus) are <= 0.9 theta_18, and the loud seed starts outside the norms."""
-    p = af.optimiser_start(variant)
+    p = af.optimiser_start(variant, kernel)
+    assert p["kernel"] == kernel and p["n"] == af.TABLE_SIZE[kernel]
     channels = np.repeat(p["max_norms"], 2) if variant == "complex" else p["max_norms"]
     assert p["controls"].shape == (3, p["Nc"], len(channels)) and len(channels) == len(p["g"])
     assert af.host_bound(p) <= 0.9 * am.THETA[18]
@@ -158,6 +169,24 @@ def test_no_mutant_passes():
                     assert miss >= 100, (mutant, case, miss)
         print("{}: {} evaluations, worst miss {:.1e} gates".format(mutant, count, worst))
         assert count and worst >= 100, (mutant, worst)
+    # the same three control mutants at the boundaries of the small kernel
+    for first in SMALL_FIRSTS:
+        for mutant in am.MUTANTS[:3]:
+            worst, least, count = 0.0, np.inf, 0
+            for case in CASES:
+                if case[0] != "small" or case[2] <= first:
+                    continue
+                p = af.build(*case)
+                for b, ref in enumerate(af.references(p)):
+                    miss = misses(model(p, p["controls"][b], mutant=mutant, first=first), ref)
+                    worst = max(worst, miss)
+                    count += 1
+                    if b == 1:
+                        least = min(least, miss)
+                        assert miss >= 100, (mutant, first, case, miss)
+            print("{} at first = {}: {} evaluations, worst miss {:.1e} gates, least on an ordinary seed {:.1e}"
+                  .format(mutant, first, count, worst, least))
+            assert count and worst >= 100, (mutant, first, worst)
 
 
 def test_transposed_knot_weights_pass_at_one_knot_per_grid_point():
@@ -185,3 +214,45 @@ def test_the_scalar_of_seed_0_on_every_item_of_an_ensemble_cannot_pass():
         assert rel_err(right, want) < 1e-11
         worst = max(worst, rel_err(wrong, want) / 1e-8)
     assert worst >= 100, worst
+
+
+# ---- 4. one final incoherent target of scale 0.7 on the small kernel ---------------------------------
+
+@pytest.mark.parametrize("kernel, n", af.INCOHERENT_TARGETS)
+def test_the_incoherent_target_stays_on_the_route_and_the_model_agrees(kernel, n):
+    p = af.incoherent(kernel, n)
+    costs = af.oracle_costs(p)
+    assert len(costs) == 1 and costs[0].neglect_relative_pahse and costs[0].cost_multiplier == 0.7
+    assert not costs[0].requires_step_evaluation
+    assert af.descriptors(p) == [dict(kind=1, step_cost=0, scale=0.7, vectors=p["target"])]
+    assert af.host_bound(p) <= 0.9 * am.THETA[18]
+    degrees = set()
+    for b, ref in enumerate(af.references(p)):
+        out = model(p, p["controls"][b])
+        degrees |= set(out["degrees"])
+        assert_model((kernel, n, b), out, ref)
+    assert len(degrees) >= 3, degrees
+
+
+@pytest.mark.parametrize("kernel, n", af.INCOHERENT_TARGETS)
+def test_no_wrong_scalar_of_the_incoherent_target_passes(kernel, n):
+    """Two ways to get the scalar of the unit adjoint wrong under an incoherent target at S = 1.
+    The coherent scalar, -2 scale sum_s <t_s|psi_s> / S^2, in place of the incoherent one, -2 scale
+    <t_s|psi_s> / S: at ONE state the two costs are the same function of the state - the same value and
+    the same cotangent -, so this mutant cannot differ and no test at S = 1 can see it; asserted here
+    as an equality. The scale mutant - 1 in place of 0.7, in the cost and in the scalar - must miss a gate
+    by a factor of 100 on every seed."""
+    p = af.incoherent(kernel, n)
+    target = p["target"][:, :, None]
+    coherent = [am.onp.TargetStateInfidelity(target, cost_multiplier=af.INCOHERENT_SCALE)]
+    unscaled = [am.onp.TargetStateInfidelity(target, neglect_relative_pahse=True)]
+
+    def run(costs, u):
+        return am.evaluate_features(p["h0"], p["g"], p["psi0"], costs, af.N, p["T"], u, p["interpolation"], 1)
+
+    for b, ref in enumerate(af.references(p)):
+        same = misses(run(coherent, p["controls"][b]), ref)
+        wrong = misses(run(unscaled, p["controls"][b]), ref)
+        print("n={} seed {}: coherent scalar {:.1e} gates, scale 1 {:.1e} gates".format(n, b, same, wrong))
+        assert same < 1
+        assert wrong >= 100, (n, b, wrong)

@@ -8,9 +8,12 @@ Pade route switches to pack8), 9 (just past it), 13 (ragged) and 16 (full). Agai
 route at the project's gates (1e-10 cost and final states, 1e-8 of the largest entry for the gradient); the
 default knob leaves every launch as it was, and no other knob of the route reaches n <= 16; no effect
 above 16; bit-identity across chunks, time segments and schedules; exact zeros in the padding; the control
-counts on either side of the kernel's boundaries; every condition under which the route must yield; one
+counts on either side of the kernel's boundaries; every condition under which the route must yield (Pade
+order 13, two states, a step cost, a non-Hermitian drift, latency mode, a bound above theta_18, tables with
+nt > 1, quadratic terms, kept step states, knob "unit_adjoint" = 0, Magnus M4, a final ForbidStates); one
 composed problem (a duration sweep) and the keyword.
-tests/test_action_small_model.py checks the mathematics on the CPU.
+tests/test_action_small_model.py checks the mathematics on the CPU; tests/test_gpu_action_features.py holds the
+route to the oracle away from Nc = N, a plain batch and a coherent target of scale 1.
 """
 
 import json
@@ -294,6 +297,129 @@ def test_yields_to_a_host_bound_above_theta_18(small):
     check_yield(small, p, loud, refs)
     small.evaluate(p["controls"], True)
     on_the_route(small)
+
+
+def run_again_on_the_route(small, p):
+    """The plain condition is back: the route runs."""
+    small.evaluate(p["controls"], True)
+    on_the_route(small)
+
+
+def oracle_of(p, costs=None, hamiltonian=None, cls=onp.SchroedingerProblem, **kw):
+    """The oracle's problem of problem(n) under other costs, another Hamiltonian or another Magnus policy."""
+    h0, g = p["h0"], p["g"]
+
+    def linear(u, t):
+        return h0 + sum(u[j] * g[j] for j in range(K))
+
+    return cls(p["T"], linear if hamiltonian is None else hamiltonian, p["psi0"][:, :, None], N,
+               control_eval_count=N, costs=costs or [onp.TargetStateInfidelity(p["target"][:, :, None])],
+               control_count=K, **kw)
+
+
+def test_yields_to_time_dependent_tables(small):
+    """nt = N - 1: H0(t) and G_k(t) of tests/time_dependent_drive.py, every sample different from its
+    neighbour. The kernel reads ONE h0 and ONE set of G_k images: were the predicate to let such a problem
+    through, the tables would be frozen at their first sample and the oracle's gates missed by orders of
+    magnitude. The loudest seed stays below theta_18, so the host's bound is not what makes the route yield."""
+    from tests import time_dependent_drive as tdd
+    q = tdd.drive_problem(n=8, N=N, Nc=5, K=K, S=1, policy="M2", costs="final")
+    assert q["h0"].shape[0] == q["g"].shape[0] == STEPS and q["nodes"] == 1
+    controls = tdd.controls(q, 3, quiet=0.12, loud=0.9)
+    assert q["dt"] * (1.3 * onp.one_norm(q["drive"].h0) + np.max(np.abs(controls) @ tdd.g_norms(q))) < 1.09
+    tdd.set_engine_problem(small, q)
+    refs = [onp.evaluate_with_grad(q["oracle"], u) for u in controls]
+    check_yield(small, q, controls, refs)
+    p = problem(8)
+    set_problem(small, p)
+    run_again_on_the_route(small, p)
+
+
+def test_yields_to_quadratic_terms(small):
+    """qocx_set_quadratic_terms, one term u_0^2 Q: the quadratic effective controls know no step table."""
+    from tests.state_costs import _SlopesAtControls  # (d H / d u_k at the controls under evaluation)
+    from tests.test_gpu_action_wide import hermitian
+    p = problem(8)
+    h0, g = p["h0"], p["g"]
+    quad = 0.1 * hermitian(np.random.default_rng(808), 8)
+    set_problem(small, p)
+    small.set_quadratic_terms(np.array([[0, 0]], dtype=np.int32), quad[None])
+    refs = []
+    for u in p["controls"]:
+        prob = oracle_of(p, hamiltonian=lambda c, t: h0 + c[0] * g[0] + c[1] * g[1] + c[0] * c[0] * quad,
+                         cls=_SlopesAtControls)
+        prob.slopes = lambda c: [g[0] + 2 * c[0] * quad, g[1]]
+        prob.at_controls = u
+        refs.append(onp.evaluate_with_grad(prob, u))
+    assert abs(refs[1][0] - p["refs"][1][0]) > 1e-6  # (the term is felt)
+    check_yield(small, p, refs=refs)
+    small.set_quadratic_terms(np.zeros((0, 2), dtype=np.int32), None)
+    run_again_on_the_route(small, p)
+
+
+def test_yields_to_kept_step_states(small):
+    """qocx_set_keep_step_states: the route keeps Taylor terms, not states. The states of every system step
+    come from the Pade route, at the gate of the final states."""
+    p = problem(8)
+    set_problem(small, p)
+    small.set_keep_step_states(True)
+    try:
+        check_yield(small, p)
+        small.evaluate(p["controls"], True)
+        assert not executed(small)
+        steps = small.download_step_states()
+    finally:
+        small.set_keep_step_states(False)
+    assert steps.shape == (3, N, 1, 8)
+    worst = 0.0
+    for b in range(3):
+        states = []
+        onp.evaluate(p["oracle"], p["controls"][b], intermediate=states)
+        assert len(states) == N
+        worst = max(worst, max(np.abs(steps[b, j] - states[j][:, :, 0]).max() for j in range(N)))
+    print("step states against the oracle {:.2e}".format(worst))
+    assert worst < 1e-10
+    run_again_on_the_route(small, p)
+
+
+def test_yields_to_the_knob_unit_adjoint_0(small):
+    p = problem(8)
+    set_problem(small, p)
+    small.set_knob("unit_adjoint", 0)
+    try:
+        check_yield(small, p)
+    finally:
+        small.set_knob("unit_adjoint", 1)
+    run_again_on_the_route(small, p)
+
+
+def test_yields_to_magnus_m4(small):
+    """M4 on a constant system (nt = 1): two quadrature nodes per step as the M4-linear effective controls."""
+    p = problem(8)
+    set_problem(small, p, magnus_policy="M4")
+    oracle = oracle_of(p, magnus_policy="M4")
+    refs = [onp.evaluate_with_grad(oracle, u) for u in p["controls"]]
+    assert max(rel_err(r[1], s[1]) for r, s in zip(refs, p["refs"])) > 1e-6  # (the policy is felt)
+    check_yield(small, p, refs=refs)
+    set_problem(small, p)
+    run_again_on_the_route(small, p)
+
+
+def test_yields_to_a_final_forbid_states(small):
+    """One final ForbidStates descriptor at S = 1 is not the unit adjoint's one separable target."""
+    from tests import state_costs as sc
+    p = problem(8)
+    rng = np.random.default_rng(88)
+    forbidden = rng.standard_normal((2, 8)) + 1j * rng.standard_normal((2, 8))
+    forbidden /= np.linalg.norm(forbidden, axis=1, keepdims=True)
+    cost = sc.DescriptorCost(sc.FORBID, 0, 0.9, forbidden, [2])
+    q = dict(p, descs=[cost.descriptor()])
+    set_problem(small, q)
+    oracle = oracle_of(p, costs=[cost])
+    refs = [onp.evaluate_with_grad(oracle, u) for u in p["controls"]]
+    check_yield(small, q, refs=refs)
+    set_problem(small, p)
+    run_again_on_the_route(small, p)
 
 
 @pytest.mark.parametrize("n", (8, 16))
