@@ -628,6 +628,22 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *                   and independent of "sweep_inverse_small", "pack8" and "sweep_umode". Any other value is
  *                   QOCX_ERR_ARG. Opt-in: at 0 every problem launches what it always launched; no effect
  *                   above n = 16; "action_states" and "action_costs" stay at 17 <= n <= 32.
+ *   "action_eff"    0 (default): a problem on EFFECTIVE controls - MAGNUS_M4 on a time-independent system, or
+ *                   quadratic terms (qocx_set_quadratic_terms) under M2 - stays on the Pade route. 1: one
+ *                   state, every operator Hermitian (the Q_q included), every other condition of "action" (one
+ *                   final TargetStateInfidelity, "pade_order" 0, not latency mode, bound <= theta_18): the
+ *                   matrix-free sweeps run on its Ke effective controls over the augmented operators
+ *                   (qocx_action_eff.hip: one kernel writes them and the Taylor degree of every step, from the
+ *                   norms of the augmented operators), on the kernels its size selects - 17 <= n <= 32 where
+ *                   "action" is not 0, n <= 16 only with "action_small" = 1, 33 <= n <= 64 only with "action" =
+ *                   2 -, and the chain kernel folds the Ke step cotangents back. Any other value is
+ *                   QOCX_ERR_ARG. Opt-in: at 0 every problem launches what it always launched. Several states,
+ *                   step costs or several costs ("action_states", "action_costs" do not combine with it), M6, M4
+ *                   on a time-dependent system and explicit generators keep their routes.
+ *   "action_eff_exact" 1 (default): with "action_eff", 17 <= n <= 32 and Ke = 5 (M4 with two controls) the
+ *                   sweep holds all five operator images in registers; 0: the build that streams every image
+ *                   past the second from memory at every step, as every other Ke > 2 does. The same numbers to
+ *                   rounding; kept for the measurement (tools/bench_action_effective.py). 0 or 1.
  *   "unit_adjoint"  one final TargetStateInfidelity: the adjoint sweep back-propagates the targets.
  *   "bidir"         with it: forward and adjoint sweep side by side, factorisation from both ends.
  *   "fuse_lu"       17 <= n <= 32: the LU factorisation runs inside the Pade kernel;

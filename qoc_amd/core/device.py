@@ -32,6 +32,9 @@ ACTION_STATES_DEFAULT = 2
 MATRIX_FREE_VALUES = ("default", "wide", "states", "all", "costs")
 # ... and the value that opts n <= 16 in (knob "action_small"), beside the tuple existing callers enumerate
 MATRIX_FREE_SMALL = "small"
+# ... and the value that opts problems on effective controls in (knob "action_eff"): M4 on a time-independent
+# system, a QuadraticHamiltonian under M2
+MATRIX_FREE_EFFECTIVE = "effective"
 
 
 def interpolation_keywords(backend, setter, interpolation_policy):
@@ -610,6 +613,11 @@ class SchroedingerEvaluator(_Evaluator):
         wave per seed whose four rows of 16 lanes do the four real products of a complex one;
         opt-in because the Pade route there is what existing callers measure and assert on, and
         not part of "all"); latency mode keeps its route, the new one yields to it as "wide" does.
+        "effective" takes them for one-state problems under the one final TargetStateInfidelity
+        whose step generator is linear in EFFECTIVE controls: MagnusPolicy.M4 on a time-independent
+        Hermitian system, and a QuadraticHamiltonian under M2 (knob "action_eff" = 1, at 17 <= n <=
+        32; opt-in because the Pade route is what existing callers measure and assert on for these
+        problems, and not part of "all"); latency mode keeps its route here too.
         A backend without knobs ignores it; any other value is a ValueError.
         latency_mode: the evaluator will be asked for ONE control array at a time (the
         reference's evolve_* / grape_* entry points). Where the cost is a single final
@@ -628,9 +636,10 @@ class SchroedingerEvaluator(_Evaluator):
         self.interpolation_policy = interpolation_policy
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
-        if not (isinstance(matrix_free, str) and matrix_free in MATRIX_FREE_VALUES + (MATRIX_FREE_SMALL,)):
-            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\", \"all\", \"costs\" or "
-                             "\"small\", not {!r}.".format(matrix_free))
+        if not (isinstance(matrix_free, str)
+                and matrix_free in MATRIX_FREE_VALUES + (MATRIX_FREE_SMALL, MATRIX_FREE_EFFECTIVE)):
+            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\", \"all\", \"costs\", "
+                             "\"small\" or \"effective\", not {!r}.".format(matrix_free))
         self.matrix_free = matrix_free
         initial_states = np.asarray(initial_states)
         self.state_count = initial_states.shape[0]
@@ -755,6 +764,8 @@ class SchroedingerEvaluator(_Evaluator):
                 self.backend.set_knob("action_costs", 1)
             if matrix_free == MATRIX_FREE_SMALL:
                 self.backend.set_knob("action_small", 1)
+            if matrix_free == MATRIX_FREE_EFFECTIVE:
+                self.backend.set_knob("action_eff", 1)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:

@@ -49,7 +49,8 @@ def evolve_schroedinger_discrete(evolution_time, hamiltonian, initial_states, sy
     (qoc_amd.standard) the error is the weighted sum over its members, final_states gains a
     member axis (M x state_count x n x 1) and the result's member_errors holds each member's
     unweighted device cost.
-    matrix_free: SchroedingerEvaluator's keyword ("default", "wide", "states", "all", "costs" or "small").
+    matrix_free: SchroedingerEvaluator's keyword ("default", "wide", "states", "all", "costs", "small" or
+    "effective").
     """
     reject_lindblad_sweep(hamiltonian)
     reject_sweep(hamiltonian, "evolve_schroedinger_discrete", _SWEEP_HINT)
@@ -105,7 +106,8 @@ def grape_schroedinger_discrete(control_count, control_eval_count, costs, evolut
     With a HamiltonianEnsemble the error is the weighted sum over its members, best_final_states
     has a member axis, and member_errors holds each member's unweighted device cost at
     best_controls (one forward evaluation after the loop).
-    matrix_free: SchroedingerEvaluator's keyword ("default", "wide", "states", "all", "costs" or "small").
+    matrix_free: SchroedingerEvaluator's keyword ("default", "wide", "states", "all", "costs", "small" or
+    "effective").
     """
     reject_lindblad_sweep(hamiltonian)
     reject_sweep(hamiltonian, "grape_schroedinger_discrete", _SWEEP_HINT)
@@ -256,7 +258,9 @@ def grape_schroedinger_discrete_batch(control_count, control_eval_count, costs, 
     TargetStateInfidelity into them (any batch size); "all" asks for both; "costs" opts one-state
     Hermitian problems at 17 <= n <= 32 into them under any costs the device evaluates (step costs,
     several costs, forbidden states; any batch size); "small" opts one-state Hermitian problems at
-    n <= 16 into them (more than 128 evaluated items, as "wide").
+    n <= 16 into them (more than 128 evaluated items, as "wide"); "effective" opts one-state
+    problems under MagnusPolicy.M4 on a time-independent Hermitian system, or with a
+    QuadraticHamiltonian under M2, into them at 17 <= n <= 32 (more than 128 evaluated items).
     Returns GrapeSchroedingerBatchResult.
     """
     reject_lindblad_sweep(hamiltonian)

@@ -391,6 +391,36 @@ int upload_operators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
                ? QOCX_ERR_HIP : 0;
 }
 
+// The tables of the matrix-free route on effective controls for the operators [first, first + count) of the
+// augmented set (EffectiveControls::op_norm1, ::op_norm2, ::eimg); the caller has sized the host vectors and,
+// where it is formed (n <= 32, nt == 1), the image for all Ke operators. The device copies of the norms are
+// uploaded by the call that delivers the LAST operators.
+int effective_operator_tables(qocx_ctx* ctx, const double* m, int first, int count) {
+    EffectiveControls& eff = ctx->eff;
+    const int n = ctx->n, np = ctx->np;
+    const size_t nn2 = (size_t)n * n * 2, mat = (size_t)np * np;
+    const bool sharpen = ctx->hermitian && ctx->nt == 1 && n <= 64;
+    std::vector<double2> img(eff.eimg.p != nullptr ? count * mat : 0);
+    for (int e = 0; e < count; ++e) {
+        const double* op = m + (size_t)e * nn2;
+        const double norm1 = one_norm(op, n);
+        const double s = sharpen ? spectral_bound(op, n) : norm1;
+        eff.op_norm1[first + e] = norm1;
+        eff.op_norm2[first + e] = s <= norm1 ? s : norm1;  // (NaN: the 1-norm)
+        if (!img.empty()) r_image(op, n, np, false, img.data() + e * mat);
+    }
+    if (!img.empty()) {
+        for (double2& x : img) x = make_double2(ctx->dt * x.y, -ctx->dt * x.x);
+        HIP_TRY(hipMemcpyAsync(eff.eimg.p + (size_t)first * mat, img.data(), img.size() * sizeof(double2),
+                               hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // img is this scope's
+    }
+    if (first + count == (int)eff.op_norm1.size() &&
+        (eff.op_norm1_dev.upload(eff.op_norm1, ctx->stream) || eff.op_norm2_dev.upload(eff.op_norm2, ctx->stream)))
+        return QOCX_ERR_HIP;
+    return 0;
+}
+
 // M4, time-independent H0 / G_k: the commutators leave the time loop (M4LinArgs). Constant
 // matrices G_k, A_k = -i [G_k, H0], B_kl = -i [G_k, G_l] (k < l); Hermitian when H0 and the
 // G_k are (made so bit for bit, the Hermitian kernel forms rely on it).
@@ -435,6 +465,15 @@ int upload_m4_commutators(qocx_ctx* ctx, const qocx_schroedinger_problem* p) {
     if (ctx->eff.images.build(ge.data(), (size_t)Ke, n, ctx->nb, ctx->stream) ||
         ctx->eff.interp_id.upload(identity_interp(ctx->nsteps), ctx->stream))
         return QOCX_ERR_HIP;
+    // norms and the E_e image of all Ke operators, for the matrix-free route (knob "action_eff")
+    ctx->eff.op_norm1.assign(Ke, 0.0);
+    ctx->eff.op_norm2.assign(Ke, 0.0);
+    if (ctx->nb <= 2) {
+        if (ctx->eff.eimg.ensure((size_t)Ke * ctx->np * ctx->np)) return QOCX_ERR_HIP;
+    } else {
+        ctx->eff.eimg.release();
+    }
+    if (int rc = effective_operator_tables(ctx, ge.data(), 0, Ke)) return rc;
     ctx->eff.kind = EffectiveControls::M4_LINEAR;
     ctx->eff.Ke = Ke;
     return 0;
@@ -741,6 +780,23 @@ int qocx_set_quadratic_terms(qocx_ctx* ctx, int32_t count, const int32_t* pairs,
         ctx->eff.pairs_dev.upload(pr, ctx->stream))
         return QOCX_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // q is released at the end of this scope
+    // The matrix-free route (knob "action_eff"; it takes the problem at nt == 1 only): the norms of the G_k as
+    // upload_operators left them, those of the Q_q from spectral_bound where ALL operators are Hermitian, and
+    // the E image of the G_k followed by that of the Q_q.
+    ctx->hermitian = herm ? 1 : 0;  // (effective_operator_tables reads it)
+    ctx->eff.op_norm1.assign(Ke, 0.0);
+    ctx->eff.op_norm2.assign(Ke, 0.0);
+    for (int k = 0; k < K; ++k) {
+        ctx->eff.op_norm1[k] = ctx->g_norm_max[k];
+        ctx->eff.op_norm2[k] = ctx->g_norm2_max[k];
+    }
+    if (ctx->nb <= 2 && nt == 1 && ctx->g_eimg.p != nullptr) {
+        if (ctx->eff.eimg.ensure((size_t)Ke * mat)) return QOCX_ERR_HIP;
+        HIP_TRY(hipMemcpyAsync(ctx->eff.eimg.p, ctx->g_eimg.p, gbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        ctx->eff.eimg.release();
+    }
+    if (int rc = effective_operator_tables(ctx, matrices, K, count)) return rc;
     ctx->eff.pairs = pr;
     ctx->eff.norm = norms;
     ctx->eff.kind = EffectiveControls::QUADRATIC;
@@ -1208,7 +1264,8 @@ int qocx_upload_controls(qocx_ctx* ctx, int32_t batch, const double* controls) {
             ctx->norm_bound_mid = (bound + smid) * fabs(ctx->dt) * (1.0 + 1e-12);
         else
             ctx->norm_bound_mid = 1e300;
-        // (only the plain M2 problem takes the matrix-free route: nothing else needs the spectral bounds)
+        // (the plain M2 problem alone: a problem on effective controls - knob "action_eff" - sizes its Taylor
+        // buffers from the 1-norm bound, norm2_bound stays at 1e300)
         if (!ens && ctx->nodes == 1 && ctx->eff.quad_count() == 0) {
             bound2 = (ctx->h0_norm2_max + s2max) * fabs(ctx->dt);
             if (mid_applies) bound2_mid = (ctx->h0_norm2_max + s2mid) * fabs(ctx->dt) * (1.0 + 1e-12);
@@ -1481,7 +1538,7 @@ static const char* const kVariantKnobs[] = {
     "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
     "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
     "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs",
-    "action_degree", "action_plan", "action_small"};
+    "action_degree", "action_plan", "action_small", "action_eff", "action_eff_exact"};
 static const char* const kDiagKnobs[] = {"dbg_skip", "sweep3_dbg", "sweep3_stamps", "lindblad_stamps",
                                          "k1a_stamps", "k1a_dbg", "peak_mode"};
 
@@ -1510,6 +1567,10 @@ int qocx_debug_set_knob(qocx_ctx* ctx, const char* name, int64_t value) {
             return fail(QOCX_ERR_ARG, "action_plan must be 0 or 1");
         if (strcmp(name, "action_small") == 0 && value != 0 && value != 1)
             return fail(QOCX_ERR_ARG, "action_small must be 0 or 1");
+        if (strcmp(name, "action_eff") == 0 && value != 0 && value != 1)
+            return fail(QOCX_ERR_ARG, "action_eff must be 0 or 1");
+        if (strcmp(name, "action_eff_exact") == 0 && value != 0 && value != 1)
+            return fail(QOCX_ERR_ARG, "action_eff_exact must be 0 or 1");
         ctx->knobs[name] = value;
         return 0;
     }

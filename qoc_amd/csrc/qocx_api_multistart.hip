@@ -504,7 +504,8 @@ int qocx_opt_clip(qocx_ctx* ctx, const double* max_norms) {
     bound = magnus_norm_bound(ctx->nodes, bound * fabs(ctx->dt));
     if (!(bound < 1e300)) return fail(QOCX_ERR_ARG, "non-finite bound");
     // (the plain M2 problem: the same bound with the spectral norms, for the Taylor buffers of the
-    // matrix-free route - qocx_upload_controls)
+    // matrix-free route - qocx_upload_controls; M4 and quadratic terms, knob "action_eff": none, the
+    // buffers follow the 1-norm bound above)
     double bound2 = 1e300;
     if (!ens && ctx->nodes == 1 && ctx->eff.quad_count() == 0 && (int)ctx->g_norm2_max.size() >= Ks) {
         bound2 = ctx->h0_norm2_max;

@@ -8,8 +8,7 @@
 //     over {G_k} u {Q_q}. With an ensemble whose members scale the terms (QuadArgs::term_scales) item i
 //     carries c_(i % M, q) r_kq r_lq in effective control K + q, and its cotangent takes the same factor
 //     on the way back. SCALED is a template parameter: without scales the kernels are what they were.
-#include "qocx_device.h"
-#include "qocx_wave.h"
+#include "qocx_effctl.h"
 
 namespace qocx {
 
@@ -27,21 +26,7 @@ __device__ inline double effctl_cotangent(const EffCtlArgs& args, size_t w, size
 __global__ __launch_bounds__(256) void m4lin_controls_kernel(M4LinArgs args) {
     const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= args.total) return;
-    const int step = (int)(w % args.nsteps), K = args.K;
-    const size_t b = w / args.nsteps;
-    const double* ctl_b = args.controls + b * args.nc * K;
-    const StepInterp s1 = args.interp[(size_t)step * 2], s2 = args.interp[(size_t)step * 2 + 1];
-    double u1[QOCX_M4LIN_MAX_K], u2[QOCX_M4LIN_MAX_K];
-    double* v = args.veff + w * args.Ke;
-    for (int k = 0; k < K; ++k) {
-        u1[k] = control_at(ctl_b, s1, K, k);
-        u2[k] = control_at(ctl_b, s2, K, k);
-        v[k] = 0.5 * (u1[k] + u2[k]);
-        v[K + k] = args.f0dt * (u2[k] - u1[k]);
-    }
-    int e = 2 * K;
-    for (int k = 0; k < K; ++k)
-        for (int l = k + 1; l < K; ++l) v[e++] = args.f0dt * (u2[k] * u1[l] - u2[l] * u1[k]);
+    QOCX_M4LIN_EFFECTIVE(args, w)
 }
 
 // Writes gchain [B][nsteps * 2][K]: the cotangents of the controls at the two nodes of every step.
@@ -81,21 +66,7 @@ template <bool SCALED>
 __global__ __launch_bounds__(256) void quad_controls_kernel(QuadArgs args) {
     const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= args.total) return;
-    const int step = (int)(w % args.nsteps), K = args.K;
-    const size_t b = w / args.nsteps;
-    const double* ctl_b = args.controls + b * args.nc * K;
-    const StepInterp si = args.interp[step];
-    double* v = args.veff + w * args.Ke;
-    for (int k = 0; k < K; ++k) v[k] = control_at(ctl_b, si, K, k);
-    // (control_at again rather than a local array indexed by the pair: no scratch, same bits)
-    const double* cm = nullptr;  // the item's member's term scales
-    (void)cm;
-    if constexpr (SCALED) cm = args.term_scales + ((args.item0 + b) % (size_t)args.M) * (size_t)args.count;
-    for (int q = 0; q < args.count; ++q) {
-        const double rr = control_at(ctl_b, si, K, args.pairs[2 * q]) * control_at(ctl_b, si, K, args.pairs[2 * q + 1]);
-        if constexpr (SCALED) v[K + q] = cm[q] * rr;
-        else v[K + q] = rr;
-    }
+    QOCX_QUAD_EFFECTIVE(args, w, SCALED)
 }
 
 // One thread per (seed, step): dC/dr_k = gbar_k + sum_q c_q r_other gbar_(K+q), c_q = 2 for a

@@ -158,6 +158,14 @@ struct EffectiveControls {
     std::vector<int> pairs;              // quadratic terms: [count][2]
     std::vector<double> norm;            // ||Q_q||_1
     DevBuf<int> pairs_dev;
+    // The matrix-free route on effective controls (qocx_action_eff.hip, knob "action_eff"): ||G^_e||_1 of each
+    // of the Ke augmented operators and the bound of its spectral norm (spectral_bound where the problem is
+    // Hermitian and constant in time, never above the 1-norm), on the host and on the device; and at n <= 32
+    // the image of E_e = -i dt G^_e the gradient kernels contract with, in the layout of qocx_ctx::g_eimg
+    // (released where it cannot be formed: a time-dependent system, n > 32).
+    std::vector<double> op_norm1, op_norm2;
+    DevBuf<double> op_norm1_dev, op_norm2_dev;
+    DevBuf<double2> eimg;
     int quad_count() const { return kind == QUADRATIC ? (int)pairs.size() / 2 : 0; }
 };
 

@@ -3,6 +3,7 @@
 // resident pipeline of the wavefront kernels - route, buffers, chunks, schedules.
 #include "qocx_host.h"
 #include "qocx_action.h"
+#include "qocx_effctl.h"
 
 // Evaluation for Hilbert sizes above 64 (qocx_general.hip): classic order, one stream - factor every step,
 // forward sweep, adjoint sweep, K3, scatter - per memory chunk of seeds.
@@ -52,8 +53,10 @@ struct EffCtlChunk {
 
     // fills the args, launches the controls kernel (`timed`: as a launch of K1a); lam_scale: the
     // chunk's scalars under the unit adjoint, which the chain kernel then applies
+    // table: the matrix-free route (knob "action_eff") - the step table of qocx_action_eff.hip in place of the
+    // controls kernel: the same veff, and the step words with the Taylor degrees
     void begin(qocx_ctx* c, EffKind k, const double* controls, const double2* lam_scale, int b0, int bc,
-               hipStream_t stream, bool timed) {
+               hipStream_t stream, bool timed, bool table = false) {
         ctx = c; kind = k; st = stream;
         if (!kind) return;
         qocx::EffCtlArgs& a = kind == EffectiveControls::M4_LINEAR ? (qocx::EffCtlArgs&)m4 : qa;
@@ -61,16 +64,23 @@ struct EffCtlChunk {
         a.K = ctx->K; a.Ke = ctx->eff.Ke; a.nc = ctx->nc; a.nsteps = ctx->nsteps; a.S = ctx->S;
         a.veff = ctx->eff.veff.p; a.gstep = ctx->gstep.p; a.lam_scale = lam_scale; a.gchain = ctx->eff.gchain.p;
         a.total = (size_t)bc * ctx->nsteps;
+        qocx::EffTableArgs ta;
+        ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max; ta.h0_norm2 = ctx->h0_norm2_max;
+        ta.norm1 = ctx->eff.op_norm1_dev.p; ta.norm2 = ctx->eff.op_norm2_dev.p;
+        ta.degree_rule = ctx->knob("action_degree", 1) != 0 ? 1 : 0;
+        ta.s_arr = ctx->s_arr.p; ta.status = ctx->status.p;
         if (timed) time_begin(ctx, 0, st);
         if (kind == EffectiveControls::M4_LINEAR) {
             m4.f0dt = (std::sqrt(3.0) / 12) * ctx->dt;
-            qocx::launch_m4lin_controls(m4, st);
+            if (table) qocx::launch_m4lin_table(m4, ta, st);
+            else qocx::launch_m4lin_controls(m4, st);
         } else {
             qa.pairs = ctx->eff.pairs_dev.p; qa.count = ctx->eff.quad_count();
             if (ctx->seeds.M > 0 && ctx->ens_qscales_set) {
                 qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->seeds.M; qa.item0 = (size_t)b0;
             }
-            qocx::launch_quad_controls(qa, st);
+            if (table) qocx::launch_quad_table(qa, ta, st);
+            else qocx::launch_quad_controls(qa, st);
         }
         if (timed) time_end(ctx, st);
     }
@@ -284,6 +294,7 @@ struct ResidentRoute {
     bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip, qocx_action4.hip, qocx_action16.hip)
     bool action_costs;   // ... under any device cost descriptors: the general adjoint, one-sided (qocx_action_costs.hip)
     bool action_table;   // ... at 33 <= n <= 64 and at n <= 16: launch_step_table for the sweeps alone (no K1a reads it)
+    bool action_eff;     // ... on effective controls: the table, veff and the operator set of qocx_action_eff.hip
     int m_max;           // ... and the Taylor terms per step its buffers hold
 };
 
@@ -300,7 +311,8 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // Both effective-control routes: one control row per step read through interp_id (nodes 1), the
     // unit adjoint with the scalar applied by the chain kernel, no step table (it interpolates the K
     // real controls at the knots and bounds with ||G_k||_1 alone, blind to the augmented operators),
-    // no pack8 (kept to the plain structured problem).
+    // no pack8 (kept to the plain structured problem). (Knob "action_eff", below: the matrix-free route on
+    // the same effective controls, with a table of its own.)
     r.eff = ctx->effctl_kind(true);
     r.Kk = EffCtlChunk::channels(ctx, r.eff);
     r.nodes = r.eff == EffectiveControls::M4_LINEAR ? 1 : ctx->nodes;
@@ -366,7 +378,21 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // Knob "action_small": 0 (default) never at n <= 16; 1: there too (qocx_action16.hip: one wave per seed, its
     // four rows of 16 lanes the four real products of a complex one), with the step table launched for the
     // sweeps alone as above 32. Opt-in: the Pade route at n <= 16 is what existing callers measure and assert on.
-    const bool sized = nb == 2 ? (action_knob != 0 && r.step_table)
+    // Knob "action_eff": 0 (default) a problem on effective controls - M4 on a time-independent system, H
+    // quadratic in the controls - never takes the route; 1: it does where it meets every other condition at
+    // S = 1 under the unit adjoint (no "action_states", no "action_costs" there), on the kernels its size
+    // selects under the knobs "action" and "action_small" as for a plain problem: its generator is linear in
+    // the Ke effective controls over Hermitian operators (ctx->hermitian covers the Q_q; the commutators of
+    // M4 are made Hermitian bit for bit), the step table of qocx_action_eff.hip writes veff and the degrees
+    // from the norms of the augmented operators, and the chain kernel folds the Ke cotangents back as on the
+    // Pade route. Opt-in: the Pade route is what existing callers measure and assert on for these problems.
+    const bool eff_ok = r.eff && ctx->knob("action_eff", 0) == 1 && !explicit_gen && r.nodes == 1 && !r.dense &&
+                        ctx->K > 0 && S == 1 && ctx->eff.op_norm1_dev.p != nullptr &&
+                        ctx->eff.op_norm2_dev.p != nullptr && (nb > 2 || ctx->eff.eimg.p != nullptr);
+    const bool sized = eff_ok ? (nb == 2 ? action_knob != 0
+                                 : nb == 1 ? ctx->knob("action_small", 0) == 1
+                                           : (nb == 4 && action_knob == 2))
+                     : nb == 2 ? (action_knob != 0 && r.step_table)
                      : nb == 1 ? (ctx->knob("action_small", 0) == 1 && table_ok)
                                : (nb == 4 && action_knob == 2 && table_ok);  // (33 <= n <= 64: padded to 64)
     // Knob "action_costs": 0 (default) the cost set must be the one final TargetStateInfidelity of the
@@ -383,10 +409,11 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
                               ctx->knob("pade_order", 0) == 0 &&
                               host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
     const bool unit_costs = ctx->unit_ok && !ctx->has_step_costs && ctx->knob("unit_adjoint", 1) != 0;
-    r.action_costs = except_costs && !ctx->unit_ok && ctx->knob("action_costs", 0) == 1 && S == 1 && nb == 2 &&
+    r.action_costs = except_costs && !r.eff && !ctx->unit_ok && ctx->knob("action_costs", 0) == 1 && S == 1 && nb == 2 &&
                      ctx->cost_count > 0;
     r.action = (except_costs && unit_costs) || r.action_costs;
-    r.action_table = r.action && nb != 2;
+    r.action_eff = r.action && r.eff;
+    r.action_table = r.action && !r.eff && nb != 2;
     if (r.action) r.inverse_sweep = r.pack8 = r.umode = false;
     // (the device's bound of a step is the host's up to the rounding of the interpolation)
     // Knob "action_degree": 1 (default) the degree of a step is the lesser of the Al-Mohy-Higham degree of
@@ -409,8 +436,11 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
     if (r.action) {
         // no Q / LU images, 1 / U_kk, permutations or sub-step slots: the Taylor terms of both sweeps
         // (gradient wanted) of every state, the step table and the step cotangents
+        // (on effective controls: Kk = Ke channels per step in veff and gstep, and the chain kernel's output)
+        const size_t Kc = r.action_eff ? (size_t)r.Kk : (size_t)K;
         const size_t terms = want_grad ? (size_t)S * r.m_max * np : 0;
-        const size_t seed_bytes = (size_t)nsteps * (2 * terms * 16 + 4 + (size_t)K * 8 + (size_t)K * 16) + (size_t)S * np * 64;
+        const size_t seed_bytes = (size_t)nsteps * (2 * terms * 16 + 4 + Kc * 8 + Kc * 16 + (r.action_eff ? (size_t)K * 16 : 0)) +
+                                  (size_t)S * np * 64;
         chunk = ctx->chunk_user;
         if (chunk <= 0) {
             size_t free_b = 0, total_b = 0;
@@ -423,7 +453,8 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
         const size_t cm = (size_t)chunk * nsteps;
         if (ctx->s_arr.ensure(cm) || ctx->kry_f.ensure(std::max<size_t>(1, cm * terms)) ||
             ctx->kry_b.ensure(std::max<size_t>(1, cm * terms)) || ctx->action_carry.ensure((size_t)chunk * S * np) ||
-            ctx->gstep.ensure(cm * std::max(K, 1) * 2) || ctx->cost_out.ensure(B) ||
+            ctx->gstep.ensure(cm * std::max<size_t>(Kc, 1) * 2) || ctx->cost_out.ensure(B) ||
+            (r.action_eff && EffCtlChunk::reserve(ctx, r.eff, cm, want_grad)) ||
             ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) || ctx->final_out.ensure((size_t)B * S * np) ||
             ctx->lam_buf.ensure((size_t)chunk * S * np) || ctx->lu_fallbacks.ensure(1))
             return QOCX_ERR_HIP;
@@ -552,7 +583,7 @@ struct ResidentChunk {
         fa.h0_cimg = ctx->h0.c.p;
         fa.g_cimg = ctx->g.c.p;
         fa.K = K; fa.nc = ctx->nc; fa.nsteps = nsteps; fa.nt = ctx->nt; fa.dt = ctx->dt;
-        eff.begin(ctx, r.eff, fa.controls, lam_scale(), b0, bc, cs, true);
+        eff.begin(ctx, r.eff, fa.controls, lam_scale(), b0, bc, cs, true, r.action_eff);
         eff.redirect(fa, fa.g_cimg, ctx->eff.images.c);
         fa.hermitian = explicit_gen ? ctx->explicit_hermitian : ctx->hermitian;
         fa.n = ctx->n;
@@ -709,6 +740,10 @@ struct ResidentChunk {
             ga.kv_f = ctx->kry_f.p; ga.kv_b = ctx->kry_b.p; ga.s_arr = ctx->s_arr.p; ga.g_rimg = ctx->g.r.p;
             ga.K = ctx->K; ga.m_max = r.m_max; ga.nsteps = nsteps; ga.dt = ctx->dt; ga.gstep = ctx->gstep.p;
             ga.e_img = ctx->g_eimg.p;
+            if (r.action_eff) {  // one row of Ke effective controls per step over the augmented operators
+                aa.ustep = ctx->eff.veff.p; aa.g_rimg = ga.g_rimg = ctx->eff.images.r.p;
+                aa.K = ga.K = ctx->eff.Ke; ga.e_img = ctx->eff.eimg.p;
+            }
             if (want_grad && ctx->nb <= 2 && S == 1 && !r.action_costs && ga.e_img == nullptr)
                 return fail(QOCX_ERR_STATE, "the matrix-free gradient has no image of -i dt G_k (upload_operators)");
             sga.S = S;
@@ -790,6 +825,9 @@ struct ResidentChunk {
                 aa.sw = sa;
                 if (r.action_costs) qocx::launch_action_costs_sweep(aa, bc, st);
                 else if (ctx->S > 1) qocx::launch_action_states_sweep(aa, bc, st);
+                else if (ctx->nb == 2 && r.action_eff && qocx::action_eff_exact_supports(aa.K) &&
+                         ctx->knob("action_eff_exact", 1) != 0)
+                    qocx::launch_action_eff_sweep(aa, bc, st);
                 else if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
                 else if (ctx->nb == 1) qocx::launch_action16_sweep(aa, bc, st);
                 else qocx::launch_action4_sweep(ctx->n, aa, bc, st);
