@@ -724,6 +724,40 @@ int qocx_action_reruns(qocx_ctx* ctx, int64_t* count);
  * truncation error of T_m(a) psi for a NORMAL a (a = -i dt H, H Hermitian) - 19 above theta'_18 and for NaN. */
 int qocx_debug_spectral_bound(const double* m, int32_t n, double* bound);
 int qocx_debug_action_degree(double bound1, double bound2, int32_t rule, int32_t* degree);
+/* What decides whether an evaluation takes the matrix-free route, and on which kernels
+ * (qoc_amd/csrc/qocx_action_route.h: action_plan - the engine fills these from its context once per
+ * evaluation): the problem, what the problem setter left on the device, the host's norm bounds and the
+ * knobs above, by their names. Flags are 0 / 1. */
+typedef struct qocx_action_facts {
+    int32_t n, S, K;           /* Hilbert size, states per seed, real controls */
+    int32_t nt;                /* time samples of the operators (1: a time-independent system) */
+    int32_t nodes;             /* nodes of the generator kernels (1: M2, and M4 on effective controls) */
+    int32_t eff_kind;          /* effective controls: 0 none, 1 M4-linear, 2 quadratic ... */
+    int32_t Ke;                /* ... and how many per step */
+    int32_t hermitian;         /* every operator is exactly Hermitian */
+    int32_t unit_ok;           /* the cost set is one final TargetStateInfidelity with one scalar for all states */
+    int32_t has_step_costs, cost_count;
+    int32_t inj_count;         /* externally supplied state cotangents (qocx_set_state_cotangents) */
+    int32_t keep_step_states;  /* qocx_set_keep_step_states */
+    int32_t explicit_gen;      /* generators sampled by the host (qocx_upload_generators) */
+    int32_t dense;             /* the dense-state sweep serves the problem ("sweep_dense") */
+    int32_t one_wave_k1a;      /* diagnostic library only: the one-wave K1a, which knows no step table */
+    int32_t latency;           /* knob "latency" */
+    int32_t have_norms;        /* ||G_k||_1 of the operators are on the device */
+    int32_t have_eff_norms;    /* both norms of the augmented operators of effective controls are */
+    int32_t have_e_img;        /* the images E = -i dt G of the operators the gradient contracts with are */
+    double bound1, bound1_mid; /* the host's bounds of ||a||_1 of a step: over the knots, at the step midpoints */
+    double bound2, bound2_mid; /* ... and of ||a||_2 */
+    int32_t action, action_states, action_costs, action_small, action_eff, action_eff_exact;
+    int32_t action_degree, action_plan, pade_order, unit_adjoint;  /* the knobs' values */
+    int32_t allow;             /* 0: the evaluation is the rerun after a step's degree was beyond the buffers */
+} qocx_action_facts;
+/* qocx_debug_action_route: the route decision itself; no context, no GPU call. *kernel: 0 the Pade route,
+ * 1 qocx_action.hip, 2 the Ke = 5 sweep of qocx_action_eff.hip (gradient: qocx_action.hip), 3
+ * qocx_action_states.hip, 4 qocx_action_costs.hip, 5 qocx_action16.hip, 6 qocx_action4.hip. *table: 0
+ * launch_step_table, 1 the table of qocx_action_eff.hip. *m_max: the Taylor terms per step the buffers
+ * hold (0 on the Pade route). */
+int qocx_debug_action_route(const qocx_action_facts* facts, int32_t* kernel, int32_t* table, int32_t* m_max);
 /* Matrices of the last Schroedinger evaluation (or qocx_debug_pade_factor call) whose LU factorisation
  * left the diagonal-pivot form with MFMA Schur updates (knob "lu_mfma"; qoc_amd/csrc/qocx_lu4.h,
  * qocx_lu4m.hip) for the general partial-pivoting elimination: LAPACK's pivot rule asked for a row

@@ -35,6 +35,16 @@ MATRIX_FREE_SMALL = "small"
 # ... and the value that opts problems on effective controls in (knob "action_eff"): M4 on a time-independent
 # system, a QuadraticHamiltonian under M2
 MATRIX_FREE_EFFECTIVE = "effective"
+# Every accepted value and the engine knobs it sets, in the order they are set
+MATRIX_FREE_KNOBS = {
+    "default": (),
+    "wide": (("action", 2),),
+    "states": (("action_states", ACTION_STATES_DEFAULT),),
+    "all": (("action", 2), ("action_states", ACTION_STATES_DEFAULT)),
+    "costs": (("action_costs", 1),),
+    MATRIX_FREE_SMALL: (("action_small", 1),),
+    MATRIX_FREE_EFFECTIVE: (("action_eff", 1),),
+}
 
 
 def interpolation_keywords(backend, setter, interpolation_policy):
@@ -636,10 +646,10 @@ class SchroedingerEvaluator(_Evaluator):
         self.interpolation_policy = interpolation_policy
         if not isinstance(magnus_policy, MagnusPolicy):
             raise ValueError("Unrecognized magnus policy {}.".format(magnus_policy))
-        if not (isinstance(matrix_free, str)
-                and matrix_free in MATRIX_FREE_VALUES + (MATRIX_FREE_SMALL, MATRIX_FREE_EFFECTIVE)):
-            raise ValueError("matrix_free must be \"default\", \"wide\", \"states\", \"all\", \"costs\", "
-                             "\"small\" or \"effective\", not {!r}.".format(matrix_free))
+        if not (isinstance(matrix_free, str) and matrix_free in MATRIX_FREE_KNOBS):
+            names = ['"{}"'.format(value) for value in MATRIX_FREE_KNOBS]
+            raise ValueError("matrix_free must be {} or {}, not {!r}.".format(
+                ", ".join(names[:-1]), names[-1], matrix_free))
         self.matrix_free = matrix_free
         initial_states = np.asarray(initial_states)
         self.state_count = initial_states.shape[0]
@@ -748,24 +758,16 @@ class SchroedingerEvaluator(_Evaluator):
             g = self._append_perturbations(g)
         self.backend = backend if backend is not None else make_backend()
         if hasattr(self.backend, "set_knob"):
-            states = matrix_free in ("states", "all")
-            if states and 2 <= self.state_count <= ACTION_STATES_DEFAULT:
+            knobs = dict(MATRIX_FREE_KNOBS[matrix_free])
+            if "action_states" in knobs and 2 <= self.state_count <= knobs["action_states"]:
                 latency_mode = False  # (the route asked for yields to it)
-            if matrix_free == "costs" and self._takes_action_costs(descriptors):
+            if "action_costs" in knobs and self._takes_action_costs(descriptors):
                 latency_mode = False
             self.backend.set_knob(
                 "sweep_impl", 3 if (latency_mode and 16 < self.hilbert_size <= 32) else 1)
             self.backend.set_knob("latency", 1 if latency_mode else 0)
-            if matrix_free in ("wide", "all"):
-                self.backend.set_knob("action", 2)
-            if states:
-                self.backend.set_knob("action_states", ACTION_STATES_DEFAULT)
-            if matrix_free == "costs":
-                self.backend.set_knob("action_costs", 1)
-            if matrix_free == MATRIX_FREE_SMALL:
-                self.backend.set_knob("action_small", 1)
-            if matrix_free == MATRIX_FREE_EFFECTIVE:
-                self.backend.set_knob("action_eff", 1)
+            for name, value in knobs.items():
+                self.backend.set_knob(name, value)
         self.kr = control_count * (2 if complex_controls else 1)
         device_k = 0 if self.opaque_hamiltonian is not None else self.kr
         if self.ensemble is not None:

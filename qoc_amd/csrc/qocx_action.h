@@ -1,6 +1,6 @@
 // qocx_action.h - the degree of the truncated Taylor series that applies exp(a) to a vector
 // (qocx_action.hip), shared by the step table (qocx_kernels.hip) and the host's route decision
-// (qocx_host_resident.hip).
+// (qocx_action_route.h: action_plan).
 //
 // A. H. Al-Mohy, N. J. Higham, "Computing the action of the matrix exponential, with an application
 // to exponential integrators", SIAM J. Sci. Comput. 33 (2011): for ||a||_1 <= theta_m the degree-m

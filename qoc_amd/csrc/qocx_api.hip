@@ -1559,18 +1559,9 @@ int qocx_debug_set_knob(qocx_ctx* ctx, const char* name, int64_t value) {
     if (kind > 0) {
         if (strcmp(name, "action_states") == 0 && value != 0 && (value < 2 || value > QOCX_ACTION_MAX_STATES))
             return fail(QOCX_ERR_ARG, "action_states must be 0 or 2 .. 4 (QOCX_ACTION_MAX_STATES)");
-        if (strcmp(name, "action_costs") == 0 && value != 0 && value != 1)
-            return fail(QOCX_ERR_ARG, "action_costs must be 0 or 1");
-        if (strcmp(name, "action_degree") == 0 && value != 0 && value != 1)
-            return fail(QOCX_ERR_ARG, "action_degree must be 0 or 1");
-        if (strcmp(name, "action_plan") == 0 && value != 0 && value != 1)
-            return fail(QOCX_ERR_ARG, "action_plan must be 0 or 1");
-        if (strcmp(name, "action_small") == 0 && value != 0 && value != 1)
-            return fail(QOCX_ERR_ARG, "action_small must be 0 or 1");
-        if (strcmp(name, "action_eff") == 0 && value != 0 && value != 1)
-            return fail(QOCX_ERR_ARG, "action_eff must be 0 or 1");
-        if (strcmp(name, "action_eff_exact") == 0 && value != 0 && value != 1)
-            return fail(QOCX_ERR_ARG, "action_eff_exact must be 0 or 1");
+        for (const char* k : {"action_costs", "action_degree", "action_plan", "action_small", "action_eff", "action_eff_exact"})
+            if (strcmp(name, k) == 0 && value != 0 && value != 1)
+                return fail(QOCX_ERR_ARG, std::string(k) + " must be 0 or 1");
         ctx->knobs[name] = value;
         return 0;
     }

@@ -1,7 +1,7 @@
 // qocx_api_debug.hip - the debug and self-test entry points of the C ABI (include/qocx.h) and the
 // counters the tests and tools read back.
 #include "qocx_host.h"
-#include "qocx_action.h"
+#include "qocx_action_route.h"
 
 namespace {
 
@@ -266,6 +266,13 @@ int qocx_debug_action_degree(double bound1, double bound2, int32_t rule, int32_t
     if (!degree) return fail(QOCX_ERR_ARG, "NULL argument");
     if (rule != 0 && rule != 1) return fail(QOCX_ERR_ARG, "rule must be 0 or 1");
     *degree = qocx::action_degree_rule(bound1, bound2, rule);
+    return 0;
+}
+
+int qocx_debug_action_route(const qocx_action_facts* facts, int32_t* kernel, int32_t* table, int32_t* m_max) {
+    if (!facts || !kernel || !table || !m_max) return fail(QOCX_ERR_ARG, "NULL argument");
+    const qocx::ActionPlan plan = qocx::action_plan(*facts);
+    *kernel = plan.kernel; *table = plan.table; *m_max = plan.m_max;
     return 0;
 }
 

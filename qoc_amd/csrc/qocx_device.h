@@ -205,6 +205,8 @@ struct KrylovArgs {
 // Matrix-free route of one-state Hermitian problems at 17 <= n <= 32 (qocx_action.hip; 33 <= n <= 64:
 // qocx_action4.hip, NP = 64 in the buffer shapes below): the sweeps
 // apply exp(a_j) to their vector by the truncated Taylor series and leave its terms behind
+// (which problems take it, and on which of the kernel families below: qocx_action_route.h, action_plan;
+// who fills these blocks and launches them: qocx_host_action.h)
 struct ActionArgs {
     SweepArgs sw;              // phase, j_begin / j_end, psi0, costs, cost_out, final_out, lam_scale, lam_buf, s_arr, status
     const double* ustep;       // [B][nsteps][K] the step table's u_k(t_mid)

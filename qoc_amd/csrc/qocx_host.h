@@ -430,7 +430,7 @@ struct qocx_ctx {
         size_t seed_items() const { return seeds.M > 0 ? (size_t)seeds.M : 1; }
     } lb;
     // ---- qocx_debug_set_knob: kernel-variant switches for A/B measurements and tests ----
-    std::map<std::string, int64_t> knobs;
+    std::map<std::string, int64_t, std::less<>> knobs;  // (std::less<>: a lookup by const char* builds no string)
     DevBuf<unsigned long long> stamps;  // sweep3 diagnostic build
     int64_t knob(const char* name, int64_t dflt) const {
         auto it = knobs.find(name);

@@ -2,7 +2,6 @@
 // (eval_items, behind qocx_eval_resident): the general path for Hilbert sizes above 64 and the
 // resident pipeline of the wavefront kernels - route, buffers, chunks, schedules.
 #include "qocx_host.h"
-#include "qocx_action.h"
 #include "qocx_effctl.h"
 
 // Evaluation for Hilbert sizes above 64 (qocx_general.hip): classic order, one stream - factor every step,
@@ -51,12 +50,9 @@ struct EffCtlChunk {
         return ctx->eff.veff.ensure(cm * ctx->eff.Ke) || ctx->eff.gchain.ensure(want_grad ? cm * per_step : 1);
     }
 
-    // fills the args, launches the controls kernel (`timed`: as a launch of K1a); lam_scale: the
-    // chunk's scalars under the unit adjoint, which the chain kernel then applies
-    // table: the matrix-free route (knob "action_eff") - the step table of qocx_action_eff.hip in place of the
-    // controls kernel: the same veff, and the step words with the Taylor degrees
-    void begin(qocx_ctx* c, EffKind k, const double* controls, const double2* lam_scale, int b0, int bc,
-               hipStream_t stream, bool timed, bool table = false) {
+    // fills the args; lam_scale: the chunk's scalars under the unit adjoint, which the chain kernel then applies
+    void set(qocx_ctx* c, EffKind k, const double* controls, const double2* lam_scale, int b0, int bc,
+             hipStream_t stream) {
         ctx = c; kind = k; st = stream;
         if (!kind) return;
         qocx::EffCtlArgs& a = kind == EffectiveControls::M4_LINEAR ? (qocx::EffCtlArgs&)m4 : qa;
@@ -64,25 +60,42 @@ struct EffCtlChunk {
         a.K = ctx->K; a.Ke = ctx->eff.Ke; a.nc = ctx->nc; a.nsteps = ctx->nsteps; a.S = ctx->S;
         a.veff = ctx->eff.veff.p; a.gstep = ctx->gstep.p; a.lam_scale = lam_scale; a.gchain = ctx->eff.gchain.p;
         a.total = (size_t)bc * ctx->nsteps;
-        qocx::EffTableArgs ta;
-        ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max; ta.h0_norm2 = ctx->h0_norm2_max;
-        ta.norm1 = ctx->eff.op_norm1_dev.p; ta.norm2 = ctx->eff.op_norm2_dev.p;
-        ta.degree_rule = ctx->knob("action_degree", 1) != 0 ? 1 : 0;
-        ta.s_arr = ctx->s_arr.p; ta.status = ctx->status.p;
-        if (timed) time_begin(ctx, 0, st);
         if (kind == EffectiveControls::M4_LINEAR) {
             m4.f0dt = (std::sqrt(3.0) / 12) * ctx->dt;
-            if (table) qocx::launch_m4lin_table(m4, ta, st);
-            else qocx::launch_m4lin_controls(m4, st);
         } else {
             qa.pairs = ctx->eff.pairs_dev.p; qa.count = ctx->eff.quad_count();
             if (ctx->seeds.M > 0 && ctx->ens_qscales_set) {
                 qa.term_scales = ctx->ens_qscales.p; qa.M = ctx->seeds.M; qa.item0 = (size_t)b0;
             }
-            if (table) qocx::launch_quad_table(qa, ta, st);
-            else qocx::launch_quad_controls(qa, st);
         }
+    }
+
+    // ... and launches the controls kernel (`timed`: as a launch of K1a)
+    void begin(qocx_ctx* c, EffKind k, const double* controls, const double2* lam_scale, int b0, int bc,
+               hipStream_t stream, bool timed) {
+        set(c, k, controls, lam_scale, b0, bc, stream);
+        if (!kind) return;
+        if (timed) time_begin(ctx, 0, st);
+        if (kind == EffectiveControls::M4_LINEAR) qocx::launch_m4lin_controls(m4, st);
+        else qocx::launch_quad_controls(qa, st);
         if (timed) time_end(ctx, st);
+    }
+
+    // ... or, on the matrix-free route, the step table of qocx_action_eff.hip in place of the controls kernel:
+    // the same veff, and the step words with the Taylor degrees (degree_rule: qocx_action.h)
+    void table(qocx_ctx* c, EffKind k, const double* controls, const double2* lam_scale, int b0, int bc,
+               hipStream_t stream, int degree_rule) {
+        set(c, k, controls, lam_scale, b0, bc, stream);
+        if (!kind) return;
+        qocx::EffTableArgs ta;
+        ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max; ta.h0_norm2 = ctx->h0_norm2_max;
+        ta.norm1 = ctx->eff.op_norm1_dev.p; ta.norm2 = ctx->eff.op_norm2_dev.p;
+        ta.degree_rule = degree_rule;
+        ta.s_arr = ctx->s_arr.p; ta.status = ctx->status.p;
+        time_begin(ctx, 0, st);
+        if (kind == EffectiveControls::M4_LINEAR) qocx::launch_m4lin_table(m4, ta, st);
+        else qocx::launch_quad_table(qa, ta, st);
+        time_end(ctx, st);
     }
 
     // K1a: a row of Ke effective controls per step through the identity table; `g`: its operator images
@@ -270,6 +283,8 @@ static int eval_general(qocx_ctx* ctx, int want_grad) {
 }
 
 // ---- the resident Schroedinger evaluation (n <= 64): route, buffers, chunks, schedules ----------
+#include "qocx_host_action.h"  // the matrix-free route: its buffers, argument blocks and launches (needs EffCtlChunk)
+
 namespace {
 
 // Which kernels serve the evaluation: a property of the PROBLEM, the context's knobs and the host's
@@ -287,15 +302,11 @@ struct ResidentRoute {
     bool magnus4w;       // Magnus kernels as four-wave workgroups (qocx_magnus4w.hip)
     bool one_wave_k1a;   // (experiments: the one-wave K1a)
     bool fused_lu;       // K1b fused into the two-wave K1a
-    bool step_table;     // launch_step_table in front of K1a
+    bool step_table;     // launch_step_table in front of K1a (or, where it is action.table, for the sweeps alone)
     bool all_dominant;   // every Pade denominator diagonally dominant
     bool pack8;          // n <= 8: two steps per 16 x 16 tile through K1a and K1b
     bool umode;          // the propagator itself in the Q image, one product per sweep sub-step
-    bool action;         // matrix-free Taylor sweeps, nothing factored (qocx_action.hip, qocx_action4.hip, qocx_action16.hip)
-    bool action_costs;   // ... under any device cost descriptors: the general adjoint, one-sided (qocx_action_costs.hip)
-    bool action_table;   // ... at 33 <= n <= 64 and at n <= 16: launch_step_table for the sweeps alone (no K1a reads it)
-    bool action_eff;     // ... on effective controls: the table, veff and the operator set of qocx_action_eff.hip
-    int m_max;           // ... and the Taylor terms per step its buffers hold
+    qocx::ActionPlan action;  // matrix-free Taylor sweeps, nothing factored: whether, and on which kernels (qocx_action_route.h)
 };
 
 ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_action) {
@@ -311,8 +322,8 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // Both effective-control routes: one control row per step read through interp_id (nodes 1), the
     // unit adjoint with the scalar applied by the chain kernel, no step table (it interpolates the K
     // real controls at the knots and bounds with ||G_k||_1 alone, blind to the augmented operators),
-    // no pack8 (kept to the plain structured problem). (Knob "action_eff", below: the matrix-free route on
-    // the same effective controls, with a table of its own.)
+    // no pack8 (kept to the plain structured problem). (The matrix-free route, below, runs on
+    // the same effective controls where its plan says so, with a table of its own.)
     r.eff = ctx->effctl_kind(true);
     r.Kk = EffCtlChunk::channels(ctx, r.eff);
     r.nodes = r.eff == EffectiveControls::M4_LINEAR ? 1 : ctx->nodes;
@@ -355,76 +366,36 @@ ResidentRoute resident_route(const qocx_ctx* ctx, int want_grad, bool allow_acti
     // itself in the Q image; the sweeps apply ONE matrix per sub-step, the adjoint sweep hands lambda'
     // to K3, which forms x = P^-H lambda' from the P^-1 image (knob "sweep_umode").
     r.umode = r.latency && r.inverse_sweep && !r.dense && nb <= 2 && ctx->knob("sweep_umode", 1) != 0;
-    // One state, Hermitian H, 17 <= n <= 32, structured M2, one final TargetStateInfidelity: the evaluation
-    // needs exp(a_j) psi and exp(a_j)^H lambda, never the matrix - the sweeps apply the truncated Taylor
-    // series (degree per step from the step table) and leave its terms to the gradient kernel; no K1a, no
-    // LU, no stored factors. Independent of want_grad (a forward-only evaluation returns the same costs
-    // bit for bit), of the batch size, chunking and segmentation. "pade_order" = 13 keeps executing
-    // [13/13]. The degree is decided on the device; the host's bound sizes the buffers (m_max) and a
-    // step beyond them sends the evaluation back to the Pade route (eval_items).
-    // Knob "action": 0 never, 1 (default) at 17 <= n <= 32, 2 also at 33 <= n <= 64 (qocx_action4.hip:
-    // workgroups of three waves up to n = 48, of four above). There the step table - which at nb = 2 also
-    // serves K1a - is launched for the sweeps alone; the Pade route above n = 32 knows no step table and
-    // stays as it is.
-    // Knob "action_states": 0 (default) one state only; 2 .. QOCX_ACTION_MAX_STATES: the most states per
-    // seed that take the route at 17 <= n <= 32 (qocx_action_states.hip: a wave per state). unit_ok admits
-    // several states for a coherent target only - one scalar for all of them.
-    const int action_states = (int)ctx->knob("action_states", 0);
-    const bool states_ok = S == 1 || (nb == 2 && S >= 2 && S <= std::min(action_states, QOCX_ACTION_MAX_STATES));
-    const double host_bound = std::min(ctx->norm_bound, ctx->norm_bound_mid);
-    const int64_t action_knob = ctx->knob("action", 1);
-    const bool table_ok = !explicit_gen && r.nodes == 1 && !r.eff && !r.dense && ctx->K > 0 &&
-                          ctx->g_norm_dev.p != nullptr;
-    // Knob "action_small": 0 (default) never at n <= 16; 1: there too (qocx_action16.hip: one wave per seed, its
-    // four rows of 16 lanes the four real products of a complex one), with the step table launched for the
-    // sweeps alone as above 32. Opt-in: the Pade route at n <= 16 is what existing callers measure and assert on.
-    // Knob "action_eff": 0 (default) a problem on effective controls - M4 on a time-independent system, H
-    // quadratic in the controls - never takes the route; 1: it does where it meets every other condition at
-    // S = 1 under the unit adjoint (no "action_states", no "action_costs" there), on the kernels its size
-    // selects under the knobs "action" and "action_small" as for a plain problem: its generator is linear in
-    // the Ke effective controls over Hermitian operators (ctx->hermitian covers the Q_q; the commutators of
-    // M4 are made Hermitian bit for bit), the step table of qocx_action_eff.hip writes veff and the degrees
-    // from the norms of the augmented operators, and the chain kernel folds the Ke cotangents back as on the
-    // Pade route. Opt-in: the Pade route is what existing callers measure and assert on for these problems.
-    const bool eff_ok = r.eff && ctx->knob("action_eff", 0) == 1 && !explicit_gen && r.nodes == 1 && !r.dense &&
-                        ctx->K > 0 && S == 1 && ctx->eff.op_norm1_dev.p != nullptr &&
-                        ctx->eff.op_norm2_dev.p != nullptr && (nb > 2 || ctx->eff.eimg.p != nullptr);
-    const bool sized = eff_ok ? (nb == 2 ? action_knob != 0
-                                 : nb == 1 ? ctx->knob("action_small", 0) == 1
-                                           : (nb == 4 && action_knob == 2))
-                     : nb == 2 ? (action_knob != 0 && r.step_table)
-                     : nb == 1 ? (ctx->knob("action_small", 0) == 1 && table_ok)
-                               : (nb == 4 && action_knob == 2 && table_ok);  // (33 <= n <= 64: padded to 64)
-    // Knob "action_costs": 0 (default) the cost set must be the one final TargetStateInfidelity of the
-    // unit adjoint; 1: a problem that meets every other condition at S = 1, 17 <= n <= 32 takes the route
-    // under ANY set of device descriptors - step costs, several costs, forbidden states - on the kernels
-    // of qocx_action_costs.hip, whose adjoint sweep carries the true cotangent: r.unit is false there
-    // (the scatter kernel applies no scalar) and the schedule is one-sided whatever "bidir" says. A
-    // unit_ok problem keeps the kernels above whatever this knob says.
-    // (Nothing here reads inverse_sweep, pack8 or umode: above n = 16 the inverse-image sweep exists in latency
-    // mode only, which the route yields to by name, and at n <= 16, where it is the DEFAULT, the route is
-    // decided without it - and switches all three off below, so that no buffer or launch follows them.)
-    const bool except_costs = allow_action && sized && states_ok && ctx->nt == 1 && ctx->hermitian &&
-                              ctx->inj_count == 0 && !r.latency && !ctx->keep_step_states &&
-                              ctx->knob("pade_order", 0) == 0 &&
-                              host_bound <= qocx::action_theta(QOCX_ACTION_MAX_DEGREE);
-    const bool unit_costs = ctx->unit_ok && !ctx->has_step_costs && ctx->knob("unit_adjoint", 1) != 0;
-    r.action_costs = except_costs && !r.eff && !ctx->unit_ok && ctx->knob("action_costs", 0) == 1 && S == 1 && nb == 2 &&
-                     ctx->cost_count > 0;
-    r.action = (except_costs && unit_costs) || r.action_costs;
-    r.action_eff = r.action && r.eff;
-    r.action_table = r.action && !r.eff && nb != 2;
-    if (r.action) r.inverse_sweep = r.pack8 = r.umode = false;
-    // (the device's bound of a step is the host's up to the rounding of the interpolation)
-    // Knob "action_degree": 1 (default) the degree of a step is the lesser of the Al-Mohy-Higham degree of
-    // its 1-norm bound and the degree the remainder of a NORMAL generator needs at its spectral-norm bound
-    // (qocx_action.h: action_degree_rule); 0: the 1-norm alone. The route predicate above stays on the
-    // 1-norm; only the buffers follow the rule - the host's two bounds of the same control maxima.
-    const double host_bound2 = std::min(ctx->norm2_bound, ctx->norm2_bound_mid);
-    r.m_max = r.action ? std::min(QOCX_ACTION_MAX_DEGREE,
-                                  qocx::action_degree_rule(host_bound * (1 + 1e-9), host_bound2 * (1 + 1e-9),
-                                                           ctx->knob("action_degree", 1) != 0 ? 1 : 0))
-                       : 0;
+    // The matrix-free route: the facts its decision reads (plain values, no allocation), the decision itself
+    // and the knobs' commentary in qocx_action_route.h. It is taken without the inverse-image sweep, pack8
+    // or umode, so that no buffer or launch follows them; its plain step table is launch_step_table, which
+    // above n = 32 and at n <= 16 no K1a reads.
+    qocx::ActionFacts f{};
+    f.n = ctx->n; f.S = S; f.K = ctx->K; f.nt = ctx->nt; f.nodes = r.nodes;
+    f.eff_kind = (int)r.eff; f.Ke = ctx->eff.Ke;
+    f.hermitian = ctx->hermitian; f.unit_ok = ctx->unit_ok; f.has_step_costs = ctx->has_step_costs;
+    f.cost_count = ctx->cost_count; f.inj_count = ctx->inj_count; f.keep_step_states = ctx->keep_step_states;
+    f.explicit_gen = explicit_gen; f.dense = r.dense; f.one_wave_k1a = r.one_wave_k1a; f.latency = r.latency;
+    f.have_norms = ctx->g_norm_dev.p != nullptr;
+    f.have_eff_norms = ctx->eff.op_norm1_dev.p != nullptr && ctx->eff.op_norm2_dev.p != nullptr;
+    f.have_e_img = (r.eff ? ctx->eff.eimg.p : ctx->g_eimg.p) != nullptr;
+    f.bound1 = ctx->norm_bound; f.bound1_mid = ctx->norm_bound_mid;
+    f.bound2 = ctx->norm2_bound; f.bound2_mid = ctx->norm2_bound_mid;
+    // (a knob is an int64 and "action" takes any: saturated, no comparison of the decision changes)
+    const auto knob = [ctx](const char* name, int dflt) {
+        return (int)std::min<int64_t>(std::max<int64_t>(ctx->knob(name, dflt), INT32_MIN), INT32_MAX);
+    };
+    f.action = knob("action", 1); f.action_states = knob("action_states", 0);
+    f.action_costs = knob("action_costs", 0); f.action_small = knob("action_small", 0);
+    f.action_eff = knob("action_eff", 0); f.action_eff_exact = knob("action_eff_exact", 1);
+    f.action_degree = knob("action_degree", 1); f.action_plan = knob("action_plan", 1);
+    f.pade_order = knob("pade_order", 0); f.unit_adjoint = knob("unit_adjoint", 1);
+    f.allow = allow_action;
+    r.action = qocx::action_plan(f);
+    if (r.action.on()) {
+        r.inverse_sweep = r.pack8 = r.umode = false;
+        r.step_table = r.action.table == qocx::ActionPlan::PLAIN;
+    }
     return r;
 }
 
@@ -433,33 +404,7 @@ int reserve_resident(qocx_ctx* ctx, const ResidentRoute& r, int want_grad, int& 
     const int B = ctx->B, np = ctx->np, mat = np * np, S = ctx->S, K = ctx->K, nsteps = ctx->nsteps;
     if (r.unit && ctx->lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
     if (ctx->action_counts.ensure(QOCX_ACTION_MAX_DEGREE + 1)) return QOCX_ERR_HIP;
-    if (r.action) {
-        // no Q / LU images, 1 / U_kk, permutations or sub-step slots: the Taylor terms of both sweeps
-        // (gradient wanted) of every state, the step table and the step cotangents
-        // (on effective controls: Kk = Ke channels per step in veff and gstep, and the chain kernel's output)
-        const size_t Kc = r.action_eff ? (size_t)r.Kk : (size_t)K;
-        const size_t terms = want_grad ? (size_t)S * r.m_max * np : 0;
-        const size_t seed_bytes = (size_t)nsteps * (2 * terms * 16 + 4 + Kc * 8 + Kc * 16 + (r.action_eff ? (size_t)K * 16 : 0)) +
-                                  (size_t)S * np * 64;
-        chunk = ctx->chunk_user;
-        if (chunk <= 0) {
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            const size_t have = (ctx->kry_f.count + ctx->kry_b.count) * 16;
-            const size_t budget = (size_t)((double)(free_b + have) * 0.6);
-            chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, budget / seed_bytes));
-        }
-        chunk = std::min(chunk, B);
-        const size_t cm = (size_t)chunk * nsteps;
-        if (ctx->s_arr.ensure(cm) || ctx->kry_f.ensure(std::max<size_t>(1, cm * terms)) ||
-            ctx->kry_b.ensure(std::max<size_t>(1, cm * terms)) || ctx->action_carry.ensure((size_t)chunk * S * np) ||
-            ctx->gstep.ensure(cm * std::max<size_t>(Kc, 1) * 2) || ctx->cost_out.ensure(B) ||
-            (r.action_eff && EffCtlChunk::reserve(ctx, r.eff, cm, want_grad)) ||
-            ctx->grads.ensure((size_t)B * ctx->nc * std::max(K, 1)) || ctx->final_out.ensure((size_t)B * S * np) ||
-            ctx->lam_buf.ensure((size_t)chunk * S * np) || ctx->lu_fallbacks.ensure(1))
-            return QOCX_ERR_HIP;
-        return 0;
-    }
+    if (r.action.on()) return reserve_action(ctx, r.action, r.eff, want_grad, chunk);
     const size_t per_seed = (size_t)nsteps * ((size_t)mat * 32 + (size_t)np * 20 + 4) +
                             ctx->slot_cap * S * np * 32 + (size_t)(nsteps + 1) * 4 +
                             (size_t)nsteps * ctx->nodes * std::max(r.Kk, 1) * 24 +
@@ -543,9 +488,7 @@ struct ResidentChunk {
     qocx::MagnusArgs ma;
     qocx::SweepArgs sa;
     qocx::KrylovArgs ka;
-    qocx::ActionArgs aa;       // the matrix-free route (r.action)
-    qocx::ActionGradArgs ga;
-    qocx::ActionStatesGradArgs sga;  // ... with several states per seed (qocx_action_states.hip)
+    ActionChunk act;  // the matrix-free route (r.action)
 
     ResidentChunk(qocx_ctx* c, const ResidentRoute& route, int grad, int first, int count)
         : ctx(c), r(route), want_grad(grad), b0(first), bc(count), cs(c->stream) {
@@ -569,23 +512,72 @@ struct ResidentChunk {
     // the chunk's scalars of the unit adjoint
     double2* lam_scale() const { return r.unit ? ctx->lam_scale.p + (size_t)b0 * ctx->S : nullptr; }
 
+    // the argument blocks; launches the step table and the effective-controls kernel. On the matrix-free
+    // route nothing is factored: no LuArgs, and of FactorArgs what the step table reads
     int init() {
+        if (int rc = init_table()) return rc;
+        if (int rc = init_sweep_args()) return rc;
+        if (r.action.on())
+            return act.init(ctx, r.action, eff, r.eff, fa.controls, lam_scale(), want_grad, b0, bc, cs);
         if (int rc = init_factor()) return rc;
-        return init_sweep();
+        return init_krylov();
     }
 
-    // FactorArgs, LuArgs; launches the effective-controls kernel and the step table
-    int init_factor() {
+    // the chunk's controls and, where the route has one (r.step_table), the step table - with the part of
+    // FactorArgs that the table and its question to K1a (pq3_supports) read
+    int init_table() {
         const int K = ctx->K, nsteps = ctx->nsteps;
-        const bool explicit_gen = ctx->explicit_mode;
         fa.controls = ctx->controls.p ? ctx->controls.p + (size_t)b0 * ctx->nc * K : nullptr;
         fa.interp = ctx->interp.p;
+        fa.K = K; fa.nc = ctx->nc; fa.nsteps = nsteps; fa.nt = ctx->nt; fa.dt = ctx->dt;
+        fa.hermitian = ctx->explicit_mode ? ctx->explicit_hermitian : ctx->hermitian;
+        fa.lu_dpp = (int)ctx->knob("lu_dpp", 1);
+        fa.pade_policy = (int)ctx->knob("pade_order", 0);  // 0: by norm (qocx_wave.h), 13: always 13
+        fa.prefer_low = ctx->norm_bound < 2.539398330063230e-01 ? 2 : ctx->norm_bound < 2.097847961257068 ? 1 : 0;  // theta_5, theta_9
+        fa.s_arr = ctx->s_arr.p; fa.status = ctx->status.p;
+        fa.fuse_lu = r.fused_lu ? 1 : 0;
+        if (b0 == 0) HIP_TRY(hipMemsetAsync(ctx->lu_fallbacks.p, 0, sizeof(int), cs));
+        if (!r.step_table) return 0;
+        if (ctx->ustep.ensure((size_t)bc * nsteps * K)) return QOCX_ERR_HIP;
+        qocx::StepTableArgs ta;
+        ta.controls = fa.controls; ta.interp = fa.interp; ta.K = K; ta.nc = ctx->nc;
+        ta.nsteps = nsteps; ta.batch = bc; ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max;
+        ta.g_norm = ctx->g_norm_dev.p; ta.pade_policy = fa.pade_policy;
+        ta.action = r.action.on() ? 1 : 0;
+        ta.h0_norm2 = ctx->h0_norm2_max; ta.g_norm2 = ctx->g_norm2_dev.p;
+        ta.degree_rule = r.action.degree_rule && ta.g_norm2 != nullptr ? 1 : 0;
+        ta.sq_max = std::min(30, ctx->sbound);
+        fa.direct = 1;  // (K1a and K3 read the table: fa.controls, below)
+        fa.three_wave = (int)ctx->knob("k1a_three", 1);
+        // (1: the second halves of the factorisations four to a wave in a kernel of their own behind K1a,
+        // 2: on the factor side stream, beside the next segment's K1a. Measured, profiles/r05_k1a_four.txt:
+        // K1a 0.650 -> 0.587 ms, the second kernel 0.061 ms - it moves 4 KB per step in and out, 262 MB
+        // per segment -, the evaluation 8.05 -> 8.05 (1) / 7.93 ms (2). Off: 1.3 % for a kernel and a
+        // stream more and 2 GB more traffic per evaluation.)
+        fa.four_steps = (int)ctx->knob("k1a_four", 0);
+        fa.gen_share = (int)ctx->knob("k1a_share", 2);
+        if (fa.four_steps == 2 && ctx->lu_stream == nullptr) fa.four_steps = 1;
+        // (the bound at the step midpoints, where it applies, speaks for the two-wave K1a only: the
+        // four-wave kernels and the slot capacity keep the bound over the knots)
+        // only the three-wave K1a (orders 3 and 5) will be launched: no step above order 5
+        if (fa.three_wave && qocx::pq3_supports(fa) &&
+            std::min(ctx->norm_bound, ctx->norm_bound_mid) < 2.539398330063230e-01) {
+            fa.prefer_low = 2;
+            ta.order_max = 5;
+        }
+        ta.ustep = ctx->ustep.p; ta.s_arr = fa.s_arr; ta.status = fa.status;
+        qocx::launch_step_table(ta, cs);
+        fa.controls = ctx->ustep.p; fa.nc = nsteps;
+        return 0;
+    }
+
+    // the rest of FactorArgs, LuArgs; launches the effective-controls kernel
+    int init_factor() {
+        const int nsteps = ctx->nsteps;
         fa.h0_cimg = ctx->h0.c.p;
         fa.g_cimg = ctx->g.c.p;
-        fa.K = K; fa.nc = ctx->nc; fa.nsteps = nsteps; fa.nt = ctx->nt; fa.dt = ctx->dt;
-        eff.begin(ctx, r.eff, fa.controls, lam_scale(), b0, bc, cs, true, r.action_eff);
+        eff.begin(ctx, r.eff, fa.controls, lam_scale(), b0, bc, cs, true);
         eff.redirect(fa, fa.g_cimg, ctx->eff.images.c);
-        fa.hermitian = explicit_gen ? ctx->explicit_hermitian : ctx->hermitian;
         fa.n = ctx->n;
         fa.skip_q = (dbg_skip & 8) ? 1 : 0;
         fa.dbg = (int)ctx->knob("k1a_dbg", 0);  // (diagnostic build: qocx_device.h)
@@ -597,49 +589,10 @@ struct ResidentChunk {
             fa.stamps = ctx->stamps.p;
         }
         fa.lu_mfma = (int)ctx->knob("lu_mfma", 1);
-        fa.lu_dpp = (int)ctx->knob("lu_dpp", 1);
         fa.herm_tiles = (int)ctx->knob("k1a_herm4", 1);
-        if (b0 == 0) HIP_TRY(hipMemsetAsync(ctx->lu_fallbacks.p, 0, sizeof(int), cs));
         fa.lu_fallbacks = ctx->lu_fallbacks.p;
-        fa.pade_policy = (int)ctx->knob("pade_order", 0);  // 0: by norm (qocx_wave.h), 13: always 13
-        fa.prefer_low = ctx->norm_bound < 2.539398330063230e-01 ? 2 : ctx->norm_bound < 2.097847961257068 ? 1 : 0;  // theta_5, theta_9
         fa.q_img = ctx->q_img.p; fa.lu_img = ctx->lu_img.p;
-        fa.s_arr = ctx->s_arr.p; fa.status = ctx->status.p;
-        fa.fuse_lu = r.fused_lu ? 1 : 0;
         fa.dinv = ctx->dinv.p; fa.perm = ctx->perm.p; fa.iperm = ctx->iperm.p;
-        if (r.step_table || r.action_table) {
-            if (ctx->ustep.ensure((size_t)bc * nsteps * K)) return QOCX_ERR_HIP;
-            qocx::StepTableArgs ta;
-            ta.controls = fa.controls; ta.interp = fa.interp; ta.K = K; ta.nc = ctx->nc;
-            ta.nsteps = nsteps; ta.batch = bc; ta.dt = ctx->dt; ta.h0_norm = ctx->h0_norm_max;
-            ta.g_norm = ctx->g_norm_dev.p; ta.pade_policy = fa.pade_policy;
-            ta.action = r.action ? 1 : 0;
-            ta.h0_norm2 = ctx->h0_norm2_max; ta.g_norm2 = ctx->g_norm2_dev.p;
-            ta.degree_rule = ctx->knob("action_degree", 1) != 0 && ta.g_norm2 != nullptr ? 1 : 0;
-            ta.sq_max = std::min(30, ctx->sbound);
-            // only the three-wave K1a (orders 3 and 5) will be launched: no step above order 5
-            qocx::FactorArgs probe = fa;
-            probe.direct = 1;
-            fa.three_wave = (int)ctx->knob("k1a_three", 1);
-            // (1: the second halves of the factorisations four to a wave in a kernel of their own behind K1a,
-            // 2: on the factor side stream, beside the next segment's K1a. Measured, profiles/r05_k1a_four.txt:
-            // K1a 0.650 -> 0.587 ms, the second kernel 0.061 ms - it moves 4 KB per step in and out, 262 MB
-            // per segment -, the evaluation 8.05 -> 8.05 (1) / 7.93 ms (2). Off: 1.3 % for a kernel and a
-            // stream more and 2 GB more traffic per evaluation.)
-            fa.four_steps = (int)ctx->knob("k1a_four", 0);
-            fa.gen_share = (int)ctx->knob("k1a_share", 2);
-            if (fa.four_steps == 2 && ctx->lu_stream == nullptr) fa.four_steps = 1;
-            // (the bound at the step midpoints, where it applies, speaks for the two-wave K1a only: the
-            // four-wave kernels and the slot capacity keep the bound over the knots)
-            if (fa.three_wave && qocx::pq3_supports(probe) &&
-                std::min(ctx->norm_bound, ctx->norm_bound_mid) < 2.539398330063230e-01) {
-                fa.prefer_low = 2;
-                ta.order_max = 5;
-            }
-            ta.ustep = ctx->ustep.p; ta.s_arr = fa.s_arr; ta.status = fa.status;
-            qocx::launch_step_table(ta, cs);
-            fa.controls = ctx->ustep.p; fa.nc = nsteps; fa.direct = 1;
-        }
         const int k1a_dbg = (int)ctx->knob("k1a_dbg", 0);
         la.lu_img = fa.lu_img; la.dinv = ctx->dinv.p; la.perm = ctx->perm.p;
         la.iperm = ctx->iperm.p; la.status = ctx->status.p; la.nsteps = nsteps; la.n = ctx->n;
@@ -660,18 +613,11 @@ struct ResidentChunk {
         return 0;
     }
 
-    // MagnusArgs, SweepArgs, KrylovArgs
-    int init_sweep() {
+    // SweepArgs: the chunk's states, costs and carries (the matrix-free sweeps take them too, ActionArgs::sw)
+    int init_sweep_args() {
         const int S = ctx->S, np = ctx->np, nsteps = ctx->nsteps;
-        const size_t mat = (size_t)np * np;
-        const bool explicit_gen = ctx->explicit_mode;
-        ma.controls = fa.controls; ma.interp = ctx->interp.p;
-        ma.h0_cimg = ctx->h0.c.p; ma.g_cimg = ctx->g.c.p;
-        ma.K = ctx->K; ma.nc = ctx->nc; ma.nsteps = nsteps; ma.nt = ctx->nt; ma.nodes = r.nodes;
-        ma.dt = ctx->dt; ma.scratch = ctx->magnus_scratch.p; ma.n = ctx->n;
-        ma.skew = ctx->hermitian;
-        sa.q_img = fa.q_img; sa.lu_img = fa.lu_img; sa.dinv = la.dinv;
-        sa.perm = la.perm; sa.iperm = la.iperm; sa.s_arr = fa.s_arr;
+        sa.q_img = ctx->q_img.p; sa.lu_img = ctx->lu_img.p; sa.dinv = ctx->dinv.p;
+        sa.perm = ctx->perm.p; sa.iperm = ctx->iperm.p; sa.s_arr = ctx->s_arr.p;
         sa.psi0 = ctx->psi0.p;
         sa.umode = r.umode ? 1 : 0;
         sa.qt_img = r.umode ? ctx->qt_img.p : nullptr;
@@ -706,6 +652,19 @@ struct ResidentChunk {
         sa.inj_index = ctx->inj_count > 0 ? ctx->inj_index.p : nullptr;
         sa.inj_bars = ctx->inj_count > 0
                           ? ctx->inj_bars.p + (size_t)b0 * ctx->inj_count * S * np : nullptr;
+        return 0;
+    }
+
+    // MagnusArgs, KrylovArgs
+    int init_krylov() {
+        const int S = ctx->S, np = ctx->np, nsteps = ctx->nsteps;
+        const size_t mat = (size_t)np * np;
+        const bool explicit_gen = ctx->explicit_mode;
+        ma.controls = fa.controls; ma.interp = ctx->interp.p;
+        ma.h0_cimg = ctx->h0.c.p; ma.g_cimg = ctx->g.c.p;
+        ma.K = ctx->K; ma.nc = ctx->nc; ma.nsteps = nsteps; ma.nt = ctx->nt; ma.nodes = r.nodes;
+        ma.dt = ctx->dt; ma.scratch = ctx->magnus_scratch.p; ma.n = ctx->n;
+        ma.skew = ctx->hermitian;
         ka.controls = fa.controls;
         ka.interp = fa.interp;
         ka.h0_rimg = ctx->h0.r.p; ka.h0_timg = ctx->h0.t.p;
@@ -730,24 +689,6 @@ struct ResidentChunk {
             ka.mbar_rm = want_grad ? ctx->genbar_rm.p + (size_t)b0 * nsteps * mat : nullptr;
         }
         ka.skew = explicit_gen ? ctx->explicit_hermitian : ctx->hermitian;
-        if (r.action) {
-            aa.ustep = ctx->ustep.p; aa.h0_rimg = ctx->h0.r.p; aa.g_rimg = ctx->g.r.p;
-            aa.K = ctx->K; aa.m_max = r.m_max; aa.dt = ctx->dt;
-            aa.kv_f = want_grad ? ctx->kry_f.p : nullptr;
-            aa.kv_b = want_grad ? ctx->kry_b.p : nullptr;
-            aa.carry_f = ctx->action_carry.p;
-            aa.degree_counts = ctx->action_counts.p;
-            ga.kv_f = ctx->kry_f.p; ga.kv_b = ctx->kry_b.p; ga.s_arr = ctx->s_arr.p; ga.g_rimg = ctx->g.r.p;
-            ga.K = ctx->K; ga.m_max = r.m_max; ga.nsteps = nsteps; ga.dt = ctx->dt; ga.gstep = ctx->gstep.p;
-            ga.e_img = ctx->g_eimg.p;
-            if (r.action_eff) {  // one row of Ke effective controls per step over the augmented operators
-                aa.ustep = ctx->eff.veff.p; aa.g_rimg = ga.g_rimg = ctx->eff.images.r.p;
-                aa.K = ga.K = ctx->eff.Ke; ga.e_img = ctx->eff.eimg.p;
-            }
-            if (want_grad && ctx->nb <= 2 && S == 1 && !r.action_costs && ga.e_img == nullptr)
-                return fail(QOCX_ERR_STATE, "the matrix-free gradient has no image of -i dt G_k (upload_operators)");
-            sga.S = S;
-        }
         return 0;
     }
 
@@ -758,7 +699,7 @@ struct ResidentChunk {
         // that K1b might find P in the last-level cache: 13.1 / 13.8 / 15.5 ms against 12.7 -
         // the launch tails cost more than any cache hit returns.)
         const int nb = ctx->nb, np = ctx->np, plo = lo[i], len = lo[i + 1] - lo[i];
-        if (r.action) {  // nothing to factor: the sweeps wait for the step table only
+        if (r.action.on()) {  // nothing to factor: the sweeps wait for the step table only
             if (nseg > 1) HIP_TRY(hipEventRecord(ctx->ev_factored[i], cs));
             return 0;
         }
@@ -821,17 +762,8 @@ struct ResidentChunk {
         sa.j_begin = jb; sa.j_end = je; sa.phase = phase;
         time_begin(ctx, 1, st);
         if (!((dbg_skip & 1) && (phase & 1)) && !((dbg_skip & 2) && (phase & 2))) {
-            if (r.action) {
-                aa.sw = sa;
-                if (r.action_costs) qocx::launch_action_costs_sweep(aa, bc, st);
-                else if (ctx->S > 1) qocx::launch_action_states_sweep(aa, bc, st);
-                else if (ctx->nb == 2 && r.action_eff && qocx::action_eff_exact_supports(aa.K) &&
-                         ctx->knob("action_eff_exact", 1) != 0)
-                    qocx::launch_action_eff_sweep(aa, bc, st);
-                else if (ctx->nb == 2) qocx::launch_action_sweep(aa, bc, st);
-                else if (ctx->nb == 1) qocx::launch_action16_sweep(aa, bc, st);
-                else qocx::launch_action4_sweep(ctx->n, aa, bc, st);
-            } else if (r.dense) qocx::launch_sweepd(sa, bc, st);
+            if (r.action.on()) act.sweep(sa, st);
+            else if (r.dense) qocx::launch_sweepd(sa, bc, st);
             else if (r.inverse_sweep) qocx::launch_sweepi(ctx->nb, sa, bc, st);
             else if (r.sweep3) qocx::launch_sweep3(ctx->nb, sa, bc, st);
             else qocx::launch_sweep(ctx->nb, sa, bc, st);
@@ -844,18 +776,9 @@ struct ResidentChunk {
         const int len = je - jb;
         ka.step0 = jb;
         time_begin(ctx, 2, cs);
-        if (r.action) {
-            ga.step0 = jb;
-            if (dbg_skip & 4) {
-            } else if (r.action_costs) {
-                qocx::launch_action_costs_grad(ga, len, bc, cs);
-            } else if (ctx->S > 1) {
-                sga.g = ga;
-                qocx::launch_action_states_grad(sga, len, bc, cs);
-            } else if (ctx->nb == 2) qocx::launch_action_grad(ga, len, bc, cs);
-            else if (ctx->nb == 1) qocx::launch_action16_grad(ga, len, bc, cs);
-            else qocx::launch_action4_grad(ctx->n, ga, len, bc, cs);
-        } else if (!(dbg_skip & 4)) qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
+        if (dbg_skip & 4) {
+        } else if (r.action.on()) act.grad(jb, len, cs);
+        else qocx::launch_krylov(ctx->nb, ka, len, bc, cs);
         if (r.nodes > 1) {
             ma.step0 = jb; ma.seg_len = len; ma.total = (size_t)bc * len;
             ma.m_rm = nullptr; ma.mbar_rm = ka.mbar_rm; ma.gstep = ka.gstep;
@@ -902,7 +825,7 @@ int run_one_sided(ResidentChunk& c) {
 // as it is factored AND the sweep has finished the one before it (stream order); K3 follows from
 // the middle outwards.
 // On the matrix-free route there is nothing to factor: each sweep runs to the crossing of the two as ONE
-// launch and in pieces from there on (knob "action_plan", below).
+// launch and in pieces from there on (ActionPlan::fuse, below).
 int run_two_sided(ResidentChunk& c) {
     qocx_ctx* ctx = c.ctx;
     const int nseg = c.nseg;
@@ -933,14 +856,14 @@ int run_two_sided(ResidentChunk& c) {
     // The matrix-free route factors nothing (factor_segment only records its event), and no gradient launch
     // can begin before the sweeps have crossed: the launch boundaries of a sweep's way TO the crossing buy
     // nothing and each costs a launch gap and a start-up on the serial chain. So that way is ONE launch
-    // (knob "action_plan" = 1, the default), with the events of all its pieces recorded behind it; from the
+    // (ActionPlan::fuse, the default), with the events of all its pieces recorded behind it; from the
     // crossing outwards the pieces stay, for the gradient to follow closely. A step's arithmetic does not
     // depend on where a launch begins: the same bits. Headline: the sweeps reach the crossing at 1.19 /
     // 1.30 ms instead of 1.64 / 1.67 (profiles/action_spread_timeline.txt).
     // (Measured and not kept, DESIGN.md 6: the pieces mid + d and mid - 1 - d as the two step ranges of ONE
     // gradient launch - the forward sweep is the faster of the two, so such a launch waits 0.1 ms for a
     // partner that the single piece does not need: 0.06-0.1 ms slower per evaluation.)
-    const bool fuse_inward = c.r.action && ctx->knob("action_plan", 1) != 0;
+    const bool fuse_inward = c.r.action.on() && c.r.action.fuse;
     std::vector<char> factored(nseg, 0);
     int next_f = 0, next_b = nseg - 1;
     // (the adjoint sweep is the slower of the two - it gathers its images transposed -: with one control
@@ -1039,7 +962,7 @@ int eval_resident(qocx_ctx* ctx, int32_t want_grad, bool allow_action) {
         ctx->last_chunk = c.bc;
         if (int rc = c.init()) return rc;
         if (int rc = c.two_sided ? run_two_sided(c) : run_one_sided(c)) return rc;
-        if (want_grad) scatter_gradients(ctx, c.eff, c.ka.gstep, c.lam_scale(), b0, c.bc, c.cs);
+        if (want_grad) scatter_gradients(ctx, c.eff, ctx->gstep.p, c.lam_scale(), b0, c.bc, c.cs);
     }
     return finish_items(ctx, want_grad);
 }

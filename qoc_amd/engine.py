@@ -115,6 +115,19 @@ class _LindbladProblem(ctypes.Structure):
                 ("op_stages", _c_double_p)]
 
 
+class ActionFacts(ctypes.Structure):
+    """qocx_action_facts of include/qocx.h: what qocx_debug_action_route decides on."""
+    _fields_ = ([(name, ctypes.c_int32) for name in (
+        "n", "S", "K", "nt", "nodes", "eff_kind", "Ke", "hermitian", "unit_ok", "has_step_costs",
+        "cost_count", "inj_count", "keep_step_states", "explicit_gen", "dense", "one_wave_k1a",
+        "latency", "have_norms", "have_eff_norms", "have_e_img")]
+                + [(name, ctypes.c_double) for name in ("bound1", "bound1_mid", "bound2", "bound2_mid")]
+                + [(name, ctypes.c_int32) for name in (
+                    "action", "action_states", "action_costs", "action_small", "action_eff",
+                    "action_eff_exact", "action_degree", "action_plan", "pade_order", "unit_adjoint",
+                    "allow")])
+
+
 # name -> (restype, argtypes); every symbol declared in include/qocx.h
 _VP = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -198,6 +211,7 @@ SIGNATURES = {
     "qocx_action_reruns": (ctypes.c_int, [_VP, ctypes.POINTER(_I64)]),
     "qocx_debug_spectral_bound": (ctypes.c_int, [_c_double_p, _I32, _c_double_p]),
     "qocx_debug_action_degree": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, _I32, _c_int_p]),
+    "qocx_debug_action_route": (ctypes.c_int, [ctypes.POINTER(ActionFacts), _c_int_p, _c_int_p, _c_int_p]),
     "qocx_debug_mfma_peak": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_opt_begin": (ctypes.c_int, [_VP]),
     "qocx_opt_clip": (ctypes.c_int, [_VP, _c_double_p]),
