@@ -118,7 +118,9 @@ typedef struct qocx_schroedinger_problem {
  */
 typedef struct qocx_lindblad_problem {
     int32_t struct_size;          /* sizeof(qocx_lindblad_problem) of the CALLER's header         */
-    int32_t hilbert_size;         /* n, 1..32 (n > 16: four tiles per matrix, HBM scratch)         */
+    int32_t hilbert_size;         /* n, 1..32 (n > 16: four tiles per matrix, HBM scratch); with the
+                                     knob "lindblad_wide" at 1: 1..64 (33..64: static problems only,
+                                     no stage tables; 65 and more are refused by name)             */
     int32_t density_count;        /* S >= 1                                                        */
     int32_t control_count;        /* K real controls, 0..8                                         */
     int32_t control_eval_count;   /* Nc                                                            */
@@ -675,6 +677,14 @@ int qocx_debug_selftest(qocx_ctx* ctx, int32_t* failures, char* report, int32_t 
  *   "lindblad_hermitian": that kernel's shorter stages for Hermitian problems (Y A_R = (A_L Y)^H; 0: the general stages).
  *   "lindblad_pad_operator": Lindblad with ONE operator at n <= 16 on the four-wave launches of two (the second zero);
  *                   read when the problem is set (0: the three-wave form).
+ *   "lindblad_wide": 1: qocx_set_lindblad_problem takes 33 <= hilbert_size <= 64 (the sixteen-wave kernel of
+ *                   qocx_lindblad16t.hip: one workgroup per seed, the classic launch, 0..8 operators); read when the
+ *                   problem is set. Default 0: hilbert_size > 32 is refused as ever. Above 32 stage tables
+ *                   (fixed_subdivision > 0, h0_stages, g_stages, op_stages), per-member and per-seed rates
+ *                   (qocx_lindblad_set_ensemble_rates, rate_scales of qocx_lindblad_set_sweep), per-seed durations
+ *                   (qocx_lindblad_sweep_set_durations) and rate sensitivities are refused by name: each has kernels
+ *                   of its own at n <= 32, and nothing runs two-sided. Ensembles and sweeps without rates, density
+ *                   cotangents, step densities and the qocx_lindblad_opt_* family work as at n <= 32.
  * Diagnostic knobs - libqocx_diag.so only (make diag, -DQOCX_DIAG; the product library answers
  * QOCX_ERR_ARG): "dbg_skip", "sweep3_dbg", "k1a_dbg" switch parts of an evaluation off for timing
  * (results are garbage); "sweep3_stamps", "lindblad_stamps", "k1a_stamps" run kernel builds that

@@ -906,6 +906,7 @@ class LindbladEvaluator(_Evaluator):
     """
 
     MAX_HILBERT_SIZE = 32
+    WIDE_HILBERT_SIZE = 64    # with wide=True (knob "lindblad_wide"): static problems, classic launch
     opt_prefix = "lindblad_"
     subtotal_costs = False
     _frozen_slices = None     # (callable, controls) of piecewise-constant frozen controls
@@ -926,8 +927,17 @@ class LindbladEvaluator(_Evaluator):
                  lindblad_data=None, control_count=0, control_eval_count=0,
                  complex_controls=False, costs=(), cost_eval_step=1,
                  interpolation_policy=InterpolationPolicy.LINEAR, need_gradients=True,
-                 backend=None, control_bounds=None, frozen_controls=None):
+                 backend=None, control_bounds=None, frozen_controls=None, wide=False):
         """
+        wide: False refuses hilbert_size > 32, as ever. True takes 33 <= hilbert_size <= 64 on the
+        sixteen-wave kernel (knob "lindblad_wide" = 1 on a backend with set_knob; an evaluator
+        with wide=False sets it to 0, so a shared backend never leaks the opt-in). That kernel
+        evaluates time-independent systems in the classic launch only: above 32 a time-dependent
+        hamiltonian or lindblad_data (stage tables; so also a hamiltonian that is not linear in the
+        controls), rate_scales of an ensemble or a sweep, LindbladSweep.durations and a
+        duration_search are refused by name, and sweep_sensitivities() has no rate_scales and no
+        evolution_time_gradients (nothing runs two-sided).
+
         frozen_controls :: (Nc x K) or None. Forward-only evaluation of ONE control array under a
         hamiltonian(controls, time) that is not linear in the controls (the reference calls any
         callable per RHS evaluation, lindbladdiscrete.py:479-483): the controls are folded into a
@@ -994,10 +1004,15 @@ class LindbladEvaluator(_Evaluator):
         initial_densities = np.asarray(initial_densities)
         self.density_count = initial_densities.shape[0]
         self.hilbert_size = initial_densities.shape[1]
-        if self.hilbert_size > self.MAX_HILBERT_SIZE:
+        self.wide = bool(wide)
+        size_limit = self.WIDE_HILBERT_SIZE if self.wide else self.MAX_HILBERT_SIZE
+        if self.hilbert_size > size_limit:
             raise NotImplementedError(
                 "the MI355X Lindblad engine handles hilbert_size <= {} (got {}); there is no "
-                "CPU fallback.".format(self.MAX_HILBERT_SIZE, self.hilbert_size))
+                "CPU fallback.".format(size_limit, self.hilbert_size))
+        above_32 = self.hilbert_size > self.MAX_HILBERT_SIZE
+        if above_32:
+            self._reject_above_32(ensemble, sweep, frozen_controls)
         self.control_count = control_count
         self.control_eval_count = control_eval_count
         self.complex_controls = complex_controls
@@ -1006,6 +1021,12 @@ class LindbladEvaluator(_Evaluator):
         self.cost_eval_step = cost_eval_step
         self.costs = list(costs)
         self.backend = backend if backend is not None else make_backend()
+        if self.wide and not hasattr(self.backend, "set_knob"):
+            raise NotImplementedError(
+                "wide=True needs a backend with set_knob (the knob lindblad_wide), got "
+                "{!r}".format(self.backend))
+        if hasattr(self.backend, "set_knob"):
+            self.backend.set_knob("lindblad_wide", 1 if self.wide else 0)
         self.kr = control_count * (2 if complex_controls else 1)
         self.device_k = self.kr   # the problem's channels: with an ensemble K_r + J
         if ensemble is not None:
@@ -1069,10 +1090,18 @@ class LindbladEvaluator(_Evaluator):
                     "route evaluates one control array at a time), got {!r}".format(hamiltonian))
             if frozen_controls is not None or control_count == 0:
                 raise
+            if above_32:
+                raise NotImplementedError(self._above_32_message(
+                    "a hamiltonian that is not linear in the controls (its tangent goes to the "
+                    "engine as stage tables)"))
             self.linearized_hamiltonian = hamiltonian
             h0, g, dissipators, operators, _, data_dependent = probe(None)
             self.time_dependent = True
             hamiltonian = None
+        if above_32 and (self.time_dependent or data_dependent):
+            raise NotImplementedError(self._above_32_message(
+                "a time-dependent hamiltonian or lindblad_data (the engine holds them in stage "
+                "tables, fixed_subdivision > 0)"))
         if self.ensemble is not None and self.ensemble.rate_scales is not None:
             self._check_rate_scales(self.ensemble.rate_scales, dissipators, data_dependent,
                                     "(M, L)", "member")
@@ -1112,6 +1141,33 @@ class LindbladEvaluator(_Evaluator):
             bounds = np.repeat(np.asarray(control_bounds, dtype=np.float64),
                                2 if complex_controls else 1)
             self._set_time_dependent_problem(bounds)
+
+    @staticmethod
+    def _above_32_message(what):
+        return ("{} is not available at hilbert_size > 32: the wide=True kernel (33 <= "
+                "hilbert_size <= 64) evaluates time-independent systems in the classic launch "
+                "only".format(what))
+
+    def _reject_above_32(self, ensemble, sweep, frozen_controls):
+        """What has kernels of its own at hilbert_size <= 32 only, by name, before the backend
+        sees a problem."""
+        if frozen_controls is not None:
+            raise NotImplementedError(self._above_32_message(
+                "a hamiltonian that is not linear in the controls (frozen controls go to the "
+                "engine as stage tables)"))
+        if ensemble is not None and ensemble.rate_scales is not None:
+            raise NotImplementedError(self._above_32_message(
+                "rate_scales of a HamiltonianEnsemble (per-member rates)"))
+        if sweep is not None:
+            if sweep.searches_duration:
+                raise NotImplementedError(self._above_32_message(
+                    "duration_search of a LindbladSweep (it needs the two-sided evaluation)"))
+            if sweep.time_scaled:
+                raise NotImplementedError(self._above_32_message(
+                    "durations of a LindbladSweep (every seed's rates scale with its duration)"))
+            if sweep.rate_scales is not None:
+                raise NotImplementedError(self._above_32_message(
+                    "rate_scales of a LindbladSweep (per-seed rates)"))
 
     def _set_problem(self, **tables):
         """The problem (with its stage tables, if any) to the backend, then the ensemble or the
@@ -1326,7 +1382,11 @@ class LindbladEvaluator(_Evaluator):
     # -- Lindblad sweeps ------------------------------------------------------------------------
     def want_rate_sensitivities(self, on):
         """Ask the evaluations from here on for the sweep's rate sensitivities (one more kernel
-        launch per piece of an evaluation with gradients); sweep_sensitivities() returns them."""
+        launch per piece of an evaluation with gradients); sweep_sensitivities() returns them.
+        Above hilbert_size 32 nothing runs two-sided, so nothing is asked for (the engine refuses
+        the request by name) and sweep_sensitivities() keeps its rule: rate_scales is None."""
+        if self.hilbert_size > self.MAX_HILBERT_SIZE:
+            return
         if hasattr(self.backend, "lindblad_sweep_want_rate_sensitivities"):
             self.backend.lindblad_sweep_want_rate_sensitivities(bool(on))
 

@@ -65,7 +65,7 @@ def _ensemble_member_errors(evaluator, result):
 def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_count,
                              controls=None, cost_eval_step=1, costs=list(), hamiltonian=None,
                              interpolation_policy=InterpolationPolicy.LINEAR, lindblad_data=None,
-                             save_file_path=None, save_intermediate_densities=False):
+                             save_file_path=None, save_intermediate_densities=False, wide=False):
     """
     Evolve density matrices under the Lindblad master equation and compute the optimization
     error. Arguments as in the reference (lindbladdiscrete.py:31-91):
@@ -80,6 +80,8 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
     perturbations, and no save file. An ensemble with rate_scales (M x L) gives member m the
     dissipation rates rate_scales[m] * dissipators of lindblad_data (an uncertain T1 / T2); that
     needs a hamiltonian and a lindblad_data without explicit time dependence.
+    wide=True takes 33 <= n <= 64 (time-independent systems without rates or durations of their
+    own; LindbladEvaluator); the default refuses n > 32.
     """
     _check_ensemble(hamiltonian, costs, save_file_path, "evolve_lindblad_discrete")
     if controls is not None:
@@ -94,7 +96,7 @@ def evolve_lindblad_discrete(evolution_time, initial_densities, system_eval_coun
     pstate.save_initial(controls)
     common = dict(hamiltonian=hamiltonian, lindblad_data=lindblad_data, costs=costs,
                   cost_eval_step=cost_eval_step, interpolation_policy=interpolation_policy,
-                  need_gradients=False)
+                  need_gradients=False, wide=wide)
     try:
         evaluator = LindbladEvaluator(
             evolution_time, initial_densities, system_eval_count, control_count=control_count,
@@ -126,7 +128,7 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
                             iteration_count=1000, lindblad_data=None, log_iteration_step=10,
                             max_control_norms=None, min_error=0, optimizer=Adam(),
                             save_file_path=None, save_intermediate_densities=False,
-                            save_iteration_step=0, control_basis=None):
+                            save_iteration_step=0, control_basis=None, wide=False):
     """
     Optimize time-discrete controls for the evolution of a set of densities under the Lindblad
     equation (GRAPE). Arguments as in the reference (lindbladdiscrete.py:106-212).
@@ -139,6 +141,7 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
     weighted sum over its members, best_final_densities has a member axis, and member_errors
     holds each member's unweighted device cost at best_controls (one forward evaluation after the
     loop).
+    wide=True takes 33 <= n <= 64 (as in evolve_lindblad_discrete); the default refuses n > 32.
     """
     _check_ensemble(hamiltonian, costs, save_file_path, "grape_lindblad_discrete")
     reject_basis_save(control_basis, save_file_path)
@@ -165,7 +168,7 @@ def grape_lindblad_discrete(control_count, control_eval_count, costs, evolution_
         lindblad_data=lindblad_data, control_count=control_count,
         control_eval_count=control_eval_count, complex_controls=complex_controls, costs=costs,
         cost_eval_step=cost_eval_step, interpolation_policy=interpolation_policy,
-        need_gradients=True, control_bounds=max_control_norms)
+        need_gradients=True, control_bounds=max_control_norms, wide=wide)
     pstate.log_and_save_initial()
     reporter = Dummy()
     reporter.iteration = 0
@@ -233,7 +236,7 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
                                   interpolation_policy=InterpolationPolicy.LINEAR,
                                   iteration_count=1000, lindblad_data=None, log_iteration_step=10,
                                   max_control_norms=None, min_error=0, optimizer=Adam(),
-                                  comm=None, control_basis=None):
+                                  comm=None, control_basis=None, wide=False):
     """
     Multi-start Lindblad GRAPE: B = len(initial_controls) independent optimisations of the same
     problem, one batched device evaluation per iteration. Seed b follows EXACTLY the iteration of
@@ -283,6 +286,9 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
     The search needs the two-sided evaluation: exactly one cost of the densities, a final
     TargetDensityInfidelity (costs of the controls alone may join it), and 1 to 4 Lindblad
     operators; anything else is refused by name.
+    wide=True takes 33 <= n <= 64 on either route: time-independent systems, ensembles and sweeps
+    without rates, durations or a duration search; sweep_sensitivities then holds the channel tables
+    only (rate_scales and evolution_time_gradients are None: nothing runs two-sided above 32).
     Returns GrapeLindbladBatchResult.
     """
     _check_ensemble(hamiltonian, costs)
@@ -299,7 +305,7 @@ def grape_lindblad_discrete_batch(control_count, control_eval_count, costs, evol
         lindblad_data=lindblad_data, control_count=control_count,
         control_eval_count=control_eval_count, complex_controls=complex_controls, costs=costs,
         cost_eval_step=cost_eval_step, interpolation_policy=interpolation_policy,
-        need_gradients=True, control_bounds=pstate.max_control_norms)
+        need_gradients=True, control_bounds=pstate.max_control_norms, wide=wide)
     stepper = batch.batched_stepper(optimizer, params)
     if evaluator.sweep is not None and evaluator.sweep.searches_duration:
         pstate.duration_search = evaluator  # (both loops carry tau_b beside the controls)

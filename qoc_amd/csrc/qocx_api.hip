@@ -1537,7 +1537,7 @@ static const char* const kVariantKnobs[] = {
     "unit_adjoint", "latency", "fuse_lu", "lu_inverse", "lu_mfma", "lu_dpp", "pack8", "m4_linear", "magnus_4w",
     "pade_order", "k1a_three", "k1a_four", "k1a_share", "k1a_herm4", "general_split", "general_skew",
     "lindblad_two_sided", "lindblad_side_limit", "lindblad_q2", "lindblad_chain", "lindblad_real_ops", "lindblad_4t",
-    "lindblad_hermitian", "lindblad_pad_operator", "action", "action_states", "action_costs",
+    "lindblad_hermitian", "lindblad_pad_operator", "lindblad_wide", "action", "action_states", "action_costs",
     "action_degree", "action_plan", "action_small", "action_eff", "action_eff_exact"};
 static const char* const kDiagKnobs[] = {"dbg_skip", "sweep3_dbg", "sweep3_stamps", "lindblad_stamps",
                                          "k1a_stamps", "k1a_dbg", "peak_mode"};

@@ -69,7 +69,8 @@ double two_norm(const double* m, int n) {
 
 // C-layout dump of an n x n matrix padded to 16 nb: reg r of tile (ti, tj) of lane l <-> element
 // (row 16 ti + 4 r + (l >> 4), col 16 tj + (l & 15)), index ((ti nb + tj) 4 + r) 64 + l
-int dump_tiles(int n) { return n <= 16 ? 1 : 2; }
+// (33 <= n <= 64: the 64 x 64 images of qocx_lindblad16t.hip)
+int dump_tiles(int n) { return n <= 16 ? 1 : (n <= 32 ? 2 : 4); }
 
 // f(dump index, row-major element index) for every element of the matrix; f(dump index, -1) for the padding
 template <typename F>
@@ -254,12 +255,24 @@ ControlFree control_free_part(const cmat& h0, double h0_norm, const std::vector<
     return cf;
 }
 
+// What the kernel of 33 <= n <= 64 does not serve, by name: every such feature has kernels of its own at n <= 32
+std::string wide_only(const char* what) {
+    return std::string(what) + " are not available at hilbert_size > 32: the kernel of 33 <= n <= 64 evaluates static "
+           "problems in the classic launch only (knob lindblad_wide)";
+}
+
 // qocx_set_lindblad_problem by stage. First every refusal that reads the description alone: it runs before
 // any state of the context is touched, so an argument fault leaves the previous problem in place
-int check_lindblad_problem(const qocx_lindblad_problem* p) {
+// (`wide`: the knob lindblad_wide - 33 <= n <= 64 on the kernel of qocx_lindblad16t.hip, static problems only)
+int check_lindblad_problem(const qocx_lindblad_problem* p, bool wide) {
     const int n = p->hilbert_size, S = p->density_count, K = p->control_count;
     const int N = p->system_eval_count, nc = p->control_eval_count, L = p->operator_count;
-    if (n < 1 || n > 32) return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..32 for the Lindblad engine");
+    if (wide && n > 64)
+        return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..64 for the Lindblad engine (knob lindblad_wide = 1)");
+    if (n < 1 || (n > 32 && !wide)) return fail(QOCX_ERR_ARG, "hilbert_size must be in 1..32 for the Lindblad engine");
+    if (n > 32 && (p->fixed_subdivision > 0 || p->h0_stages != nullptr || p->op_stages != nullptr ||
+                   p->g_stages != nullptr || p->diss_stages != nullptr))
+        return fail(QOCX_ERR_ARG, wide_only("stage tables (fixed_subdivision > 0, h0_stages, g_stages, op_stages)"));
     if (S < 1 || S > 64) return fail(QOCX_ERR_ARG, "density_count must be in 1..64");
     if (K < 0 || K > QOCX_LINDBLAD_MAX_K) return fail(QOCX_ERR_ARG, "control_count must be in 0..8");
     // (1..4 operators: the several-wave / tile-per-wave stage loops; 5..8: the one-wave kernels, whose stage
@@ -348,11 +361,14 @@ int upload_static_part(qocx_ctx* ctx, const qocx_lindblad_problem* p, cmat& deca
         gpd.push_back(cm_adjoint(gp.back(), n));
         gpt.push_back(cm_transpose(gp.back(), n));
     }
+    // (n > 32: the operators are left and right operands read from memory, so L_i^H is dumped behind them)
+    std::vector<cmat> ops_both = ops;
+    for (size_t i = 0; n > 32 && i < ops.size(); ++i) ops_both.push_back(cm_adjoint(ops[i], n));
     if (upload_dumps(lb.a0l, {cf.a0l}, n, ctx->stream) || upload_dumps(lb.a0r, {cf.a0r}, n, ctx->stream) ||
         upload_dumps(lb.a0ld, {cm_adjoint(cf.a0l, n)}, n, ctx->stream) ||
         upload_dumps(lb.a0rd, {cm_adjoint(cf.a0r, n)}, n, ctx->stream) ||
         upload_dumps(lb.gp, gp, n, ctx->stream) || upload_dumps(lb.gpd, gpd, n, ctx->stream) ||
-        upload_dumps(lb.gpt, gpt, n, ctx->stream) || upload_dumps(lb.ops, ops, n, ctx->stream) ||
+        upload_dumps(lb.gpt, gpt, n, ctx->stream) || upload_dumps(lb.ops, n > 32 ? ops_both : ops, n, ctx->stream) ||
         lb.gammas.upload(gammas, ctx->stream))
         return QOCX_ERR_HIP;
     return 0;
@@ -476,7 +492,7 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
         return fail(QOCX_ERR_ARG, "qocx_lindblad_problem.struct_size does not match this "
                                   "library's header (stale binding?)");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (int rc = check_lindblad_problem(p)) return rc;
+    if (int rc = check_lindblad_problem(p, ctx->knob("lindblad_wide", 0) != 0)) return rc;
     auto& lb = ctx->lb;
     lb.has_problem = false;
     lb.control_costs.clear();
@@ -570,6 +586,7 @@ int qocx_lindblad_set_ensemble_rates(qocx_ctx* ctx, int32_t members, int32_t ope
     auto& lb = ctx->lb;
     if (!lb.has_problem || lb.seeds.M == 0 || lb.seeds.swp_B > 0)
         return fail(QOCX_ERR_STATE, "no Lindblad ensemble set (qocx_lindblad_set_ensemble first)");
+    if (lb.n > 32 && rate_scales) return fail(QOCX_ERR_STATE, wide_only("per-member rates (rate_scales)"));
     if (lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "per-member rates need a static problem: this one was set with stage tables "
                                     "(fixed_subdivision > 0), which hold one control-free generator per stage");
@@ -605,6 +622,7 @@ int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const d
     if (seeds < 1 || seeds > 1024) return fail(QOCX_ERR_ARG, "sweep seeds must be 1 .. 1024");
     const int L = lb.nops, n = lb.n;
     const bool rates = rate_scales != nullptr && L > 0;
+    if (rates && n > 32) return fail(QOCX_ERR_STATE, wide_only("per-seed rates (rate_scales)"));
     if (rates && lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "per-seed rates need a static problem: this one was set with stage tables "
                                     "(fixed_subdivision > 0), which hold one control-free generator per stage");
@@ -636,6 +654,8 @@ int qocx_lindblad_set_sweep(qocx_ctx* ctx, int32_t seeds, int32_t fixed, const d
 int qocx_lindblad_sweep_want_rate_sensitivities(qocx_ctx* ctx, int32_t on) {
     if (!ctx) return fail(QOCX_ERR_ARG, "ctx is NULL");
     if (ctx->lb.seeds.swp_B == 0) return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep)");
+    if (ctx->lb.n > 32 && on)
+        return fail(QOCX_ERR_STATE, wide_only("rate sensitivities (they come out of the two-sided evaluation)"));
     ctx->lb.swp_want_rates = on != 0;
     return 0;
 }
@@ -906,7 +926,9 @@ int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of,
     // (n > 16: the tile-per-wave kernel of qocx_lindblad4t.hip in its phases, constant tables only)
     const bool two_sided_small = n <= 16 && lb.nops >= 1 && lb.multi_wave && !lb.global_scratch &&
                                  lb.dbg_wave_mode != 1;
-    const bool two_sided_tiles = plan.two_sided_tiles = n > 16 && ctx->knob("lindblad_4t", 1) != 0 && lb.nops <= 4;
+    // (n > 32: never - the kernel of qocx_lindblad16t.hip knows the classic launch only)
+    const bool two_sided_tiles = plan.two_sided_tiles = n > 16 && n <= 32 && ctx->knob("lindblad_4t", 1) != 0 &&
+                                                        lb.nops <= 4;
     const bool two_sided_ok = plan.two_sided_ok = want_grad && lb.unit_ok && lb.inj_count == 0 &&
                               (two_sided_small || two_sided_tiles) && lb.fixed_ksub == 0 &&
                               (int)ctx->sweep_streams.size() >= 1 && ctx->knob("lindblad_two_sided", 1) != 0;
@@ -1105,6 +1127,8 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
     for (const LindbladPiece& pc : plan.pieces) {
         const auto& gr = lb.grids[pc.ksub];
         const qocx::LindbladArgs la = lindblad_piece_args(ctx, ev, pc);
+        if (n > 32 && !qocx::lindblad16t_supports(la))  // (every such problem was refused by name when it was set)
+            return fail(QOCX_ERR_STATE, "no Lindblad kernel for this problem at hilbert_size > 32");
         if (ev.two_sided && pc.keep_stages && (pc.multi_wave || plan.two_sided_tiles)) {
             if (int rc = launch_two_sided(ctx, ev, la, pc)) return rc;
         } else {
@@ -1383,6 +1407,7 @@ int qocx_lindblad_sweep_set_durations(qocx_ctx* ctx, const double* tau, const do
     auto& lb = ctx->lb;
     if (!lb.has_problem || lb.seeds.swp_B == 0)
         return fail(QOCX_ERR_STATE, "no sweep set (qocx_lindblad_set_sweep before qocx_lindblad_sweep_set_durations)");
+    if (lb.n > 32) return fail(QOCX_ERR_STATE, wide_only("per-seed durations (a duration sweep needs per-seed rates)"));
     if (lb.fixed_ksub > 0)
         return fail(QOCX_ERR_STATE, "a duration search needs a static problem: this one was set with stage tables "
                                     "(fixed_subdivision > 0), which hold one control-free generator per stage");

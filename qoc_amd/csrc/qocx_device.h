@@ -384,7 +384,7 @@ struct LindbladArgs {
     const double2* op_tab;     // time-dependent lindblad_data: [nsub * 12][nops] dumps of L_i at the
                                // stage times (+ gamma_tab [nsub * 12][nops]), or nullptr
     const double* gamma_tab;
-    const double2* op_cimg;    // [nops] L_i
+    const double2* op_cimg;    // [nops] L_i (n > 32: then [nops] L_i^H)
     const double* gammas;      // [nops]
     const double2* rho0_cimg;  // [S]
     int n, S, K, nc, nops, nsub, nsteps, cost_eval_step, want_grad, has_step_costs;
@@ -395,7 +395,7 @@ struct LindbladArgs {
     double2* checkpoints;      // [B][nsub][S] C-dumps: densities at the start of each sub-interval
     int multi_wave;            // 1: nops + 2 wavefronts per seed (n <= 16, everything in LDS)
     int cache_gen;             // multi_wave: constant generator dumps copied to LDS
-    double2* scratch;          // [B][2 S + 12] (n > 16: [B][2 S + 36]) dumps when densities / cotangents / stage
+    double2* scratch;          // [B][2 S + 12] (n > 16: [B][2 S + 36], n > 32: [B][2 S + 31]) dumps when densities / cotangents / stage
                                // derivatives do not live in LDS (always for n > 16), else nullptr
     double2* ystages;          // [B][nsub][S][12] C-dumps of the stage values, or nullptr: the
                                // adjoint then recomputes them from the checkpoints
@@ -704,6 +704,11 @@ void launch_lindblad4t_rates(const LindbladArgs& a, const LindbladMembers& mem, 
 void launch_lindblad_ratesens(const LindbladArgs& a, const RateSensArgs& r, int batch, hipStream_t st);
 int lindblad_lds_size(int n, int S, int nops, int mode, int K);
 size_t lindblad_scratch_elems(int n, int S);
+// 33 <= n <= 64 (qocx_lindblad16t.hip; the host accepts such problems under the knob lindblad_wide)
+bool lindblad16t_supports(const LindbladArgs& a);
+void launch_lindblad16t(const LindbladArgs& a, int batch, hipStream_t st);
+int lindblad16t_lds_bytes();
+size_t lindblad16t_scratch_elems(int S);
 
 void launch_pq(int nb, const FactorArgs& a, int nsteps, int batch, hipStream_t st);
 void launch_pq_explicit(int nb, const double2* a_in, int n, const FactorArgs& a, int count,

@@ -131,7 +131,8 @@ void launch_lindblad_combine(const LindbladArgs& a, int batch, hipStream_t st) {
 }
 
 void launch_lindblad(const LindbladArgs& a, int batch, hipStream_t st) {
-    if (lindblad4t_supports(a)) launch_lindblad4t(a, batch, st);
+    if (a.n > 32) launch_lindblad16t(a, batch, st);  // (lindblad_launch_groups has asked lindblad16t_supports)
+    else if (lindblad4t_supports(a)) launch_lindblad4t(a, batch, st);
     else lindblad_dispatch(a, Launch{a, batch, st});
 }
 
@@ -139,6 +140,7 @@ void launch_lindblad(const LindbladArgs& a, int batch, hipStream_t st) {
 // densities / cotangents in HBM scratch (always for n > 16); 2: nops + 2 waves per seed; 3: as 2
 // with the constant generator dumps of K controls cached in LDS
 int lindblad_lds_size(int n, int S, int nops, int mode, int K) {
+    if (n > 32) return lindblad16t_lds_bytes();  // two matrices, whatever the problem
     if (n > 16) return LB<2, true, false>::lds_bytes(S, nops);
     if (mode == 1) return LB<1, true, false>::lds_bytes(S, nops);
     if (mode == 2) return LB<1, false, true>::lds_bytes(S, nops);
@@ -150,6 +152,7 @@ int lindblad_lds_size(int n, int S, int nops, int mode, int K) {
 // (n > 16: a second set of stage dumps - the two passes of the two-sided evaluation run side by side -
 // and a third for stage values recomputed from a checkpoint)
 size_t lindblad_scratch_elems(int n, int S) {
+    if (n > 32) return lindblad16t_scratch_elems(S);
     return n > 16 ? (size_t)(2 * S + 3 * STAGES) * 1024 : (size_t)(2 * S + STAGES) * 256;
 }
 
