@@ -768,6 +768,47 @@ typedef struct qocx_action_facts {
  * launch_step_table, 1 the table of qocx_action_eff.hip. *m_max: the Taylor terms per step the buffers
  * hold (0 on the Pade route). */
 int qocx_debug_action_route(const qocx_action_facts* facts, int32_t* kernel, int32_t* table, int32_t* m_max);
+/* What decides the kernels of a Lindblad evaluation and whether it runs two-sided
+ * (qoc_amd/csrc/qocx_lindblad_route.h: lindblad_form when a problem is set, lindblad_route once per
+ * evaluation - the engine fills these from its context): the problem, the evaluation, and the knobs above by
+ * their names. Flags are 0 / 1. */
+typedef struct qocx_lindblad_facts {
+    int32_t n, S, K, nops;         /* Hilbert size, densities per seed, real controls, Lindblad operators */
+    int32_t stage_tables;          /* the problem was set with stage tables (fixed_subdivision > 0) ... */
+    int32_t g_tables, op_tables;   /* ... among them time-dependent G_k (g_stages), operators (op_stages) */
+    int32_t hermitian;             /* H0, G_k, sum gamma L^H L, initial densities and cost matrices are Hermitian */
+    int32_t ops_real;              /* every Lindblad operator has a zero imaginary part */
+    int32_t unit_ok;               /* the cost set is one final target-density infidelity */
+    int32_t inj_count;             /* host-supplied density cotangents (qocx_set_density_cotangents) */
+    int32_t want_grad;
+    int32_t rates;                 /* per-member or per-seed rates (rate_scales) */
+    int32_t sweep;                 /* a sweep is set (qocx_lindblad_set_sweep) ... */
+    int32_t want_rate_sens;        /* ... which asked for rate sensitivities, or searches its durations */
+    int32_t side_streams;          /* streams beside the context's own */
+    int32_t cu_count;
+    int32_t dbg_wave_mode;         /* qocx_debug_lindblad_knobs */
+    int32_t lindblad_4t, lindblad_two_sided, lindblad_hermitian, lindblad_q2, lindblad_chain;
+    int32_t lindblad_real_ops, lindblad_pad_operator, lindblad_side_limit, lindblad_stamps;  /* the knobs' values */
+    int32_t single_wave;           /* diagnostic library only: the environment switch QOCX_LINDBLAD_SINGLE_WAVE */
+} qocx_lindblad_facts;
+/* qocx_debug_lindblad_route: the form and the route of these facts; no context, no GPU call. kernels[3]: the
+ * kernel of the classic launch, of the forward and of the adjoint launch of a two-sided piece - 0 none, 1 one
+ * wave in LDS, 2 one wave with scratch, 3 one wave at 17 <= n <= 32, 4 nops + 2 waves, 5 four waves, 6 four
+ * waves q2, 7 four waves chain, 8 tile-per-wave, 9 its Hermitian build, 10 the sixteen-wave kernel of
+ * 33 <= n <= 64. *multi_wave: pieces run several waves per seed; *two_sided: a piece that keeps its stage
+ * values runs as forward launch, adjoint launch and combine; *rate_sens: such an evaluation delivers rate
+ * sensitivities. form[4]: scratch, pad_op, multi_wave, cache_gen as the problem setter stores them. */
+int qocx_debug_lindblad_route(const qocx_lindblad_facts* facts, int32_t* kernels, int32_t* multi_wave,
+                              int32_t* two_sided, int32_t* rate_sens, int32_t* form);
+/* qocx_debug_lindblad_pieces: the piece schedule of one group of `seeds` seeds with `per_seed` stage elements
+ * each (lindblad_group_pieces of the same header) under a stage budget in elements, the values of
+ * qocx_debug_lindblad_knobs and the CU count; no context, no GPU call. counts / keep_stages / multi_wave
+ * receive up to `capacity` pieces in launch order, *pieces how many there are, *sized_for the seeds the stage
+ * buffers are sized for (0: no piece keeps its stage values). */
+int qocx_debug_lindblad_pieces(int32_t want_grad, int32_t multi_wave, int64_t stage_budget,
+                               int64_t stage_budget_seeds, int32_t min_piece, int32_t wave_mode, int32_t cu_count,
+                               int32_t seeds, int64_t per_seed, int32_t capacity, int32_t* counts,
+                               int32_t* keep_stages, int32_t* piece_multi_wave, int32_t* pieces, int64_t* sized_for);
 /* Matrices of the last Schroedinger evaluation (or qocx_debug_pade_factor call) whose LU factorisation
  * left the diagonal-pivot form with MFMA Schur updates (knob "lu_mfma"; qoc_amd/csrc/qocx_lu4.h,
  * qocx_lu4m.hip) for the general partial-pivoting elimination: LAPACK's pivot rule asked for a row

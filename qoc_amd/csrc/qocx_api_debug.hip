@@ -276,6 +276,40 @@ int qocx_debug_action_route(const qocx_action_facts* facts, int32_t* kernel, int
     return 0;
 }
 
+int qocx_debug_lindblad_route(const qocx_lindblad_facts* facts, int32_t* kernels, int32_t* multi_wave,
+                              int32_t* two_sided, int32_t* rate_sens, int32_t* form) {
+    if (!facts || !kernels || !multi_wave || !two_sided || !rate_sens || !form)
+        return fail(QOCX_ERR_ARG, "NULL argument");
+    const qocx::LindbladFacts& f = *facts;
+    const qocx::LindbladForm m = qocx::lindblad_form(
+        f, [&](int mode, int nops) { return qocx::lindblad_lds_size(f.n, f.S, nops, mode, f.K); });
+    const qocx::LindbladRoute r = qocx::lindblad_route(m, f);
+    for (int ph = 0; ph < 3; ++ph) kernels[ph] = (int32_t)r.kernel[ph];
+    *multi_wave = r.multi_wave; *two_sided = r.two_sided; *rate_sens = r.rate_sens;
+    form[0] = m.scratch; form[1] = m.pad_op; form[2] = m.multi_wave; form[3] = m.cache_gen;
+    return 0;
+}
+
+int qocx_debug_lindblad_pieces(int32_t want_grad, int32_t multi_wave, int64_t stage_budget,
+                               int64_t stage_budget_seeds, int32_t min_piece, int32_t wave_mode, int32_t cu_count,
+                               int32_t seeds, int64_t per_seed, int32_t capacity, int32_t* counts,
+                               int32_t* keep_stages, int32_t* piece_multi_wave, int32_t* pieces, int64_t* sized_for) {
+    if (!counts || !keep_stages || !piece_multi_wave || !pieces || !sized_for)
+        return fail(QOCX_ERR_ARG, "NULL argument");
+    if (stage_budget < 0 || stage_budget_seeds < 0 || min_piece < 1 || wave_mode < 0 || wave_mode > 2 ||
+        cu_count < 1 || seeds < 1 || per_seed < 1 || capacity < 0)
+        return fail(QOCX_ERR_ARG, "bad argument");
+    const qocx::PieceRule rule{want_grad != 0, multi_wave != 0, (size_t)stage_budget, stage_budget_seeds, min_piece,
+                               wave_mode, cu_count};
+    std::vector<qocx::LindbladPiece> out;
+    *sized_for = (int64_t)qocx::lindblad_group_pieces(rule, 1, 0, seeds, (size_t)per_seed, out);
+    *pieces = (int32_t)out.size();
+    for (size_t i = 0; i < out.size() && i < (size_t)capacity; ++i) {
+        counts[i] = out[i].count; keep_stages[i] = out[i].keep_stages; piece_multi_wave[i] = out[i].multi_wave;
+    }
+    return 0;
+}
+
 int qocx_action_reruns(qocx_ctx* ctx, int64_t* count) {
     if (!ctx || !count) return fail(QOCX_ERR_ARG, "NULL argument");
     *count = ctx->action_reruns;

@@ -283,7 +283,7 @@ int check_lindblad_problem(const qocx_lindblad_problem* p, bool wide) {
     if (p->cost_eval_step < 1) return fail(QOCX_ERR_ARG, "cost_eval_step must be >= 1");
     if (!p->initial_densities || (K > 0 && !p->g) || (L > 0 && (!p->operators || !p->dissipators)))
         return fail(QOCX_ERR_ARG, "missing problem arrays");
-    const int scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;  // (choose_launch_form)
+    const int scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;  // (lindblad_form)
     if (qocx::lindblad_lds_size(n, S, L, scratch, K) > 160 * 1024)
         return fail(QOCX_ERR_ARG, "too many operators for the kernel's LDS");
     if ((p->op_stages != nullptr) != (p->diss_stages != nullptr))
@@ -305,24 +305,44 @@ int check_lindblad_problem(const qocx_lindblad_problem* p, bool wide) {
     return 0;
 }
 
+// What the route reads, from the context (the only place the Lindblad knobs are read): the problem as it is
+// set, the evaluation, the knobs
+// (a knob is an int64: saturated, no comparison of the decision changes)
+qocx::LindbladFacts lindblad_facts(const qocx_ctx* ctx, int want_grad) {
+    const auto& lb = ctx->lb;
+    const auto knob = [ctx](const char* name, int64_t dflt) {
+        return (int)std::min<int64_t>(std::max<int64_t>(ctx->knob(name, dflt), INT32_MIN), INT32_MAX);
+    };
+    qocx::LindbladFacts f{};
+    f.n = lb.n; f.S = lb.S; f.K = lb.K; f.nops = lb.nops;
+    f.stage_tables = lb.fixed_ksub > 0;
+    f.g_tables = f.stage_tables && lb.gp_tab.p != nullptr; f.op_tables = f.stage_tables && lb.op_tab.p != nullptr;
+    f.hermitian = lb.hermitian; f.ops_real = lb.ops_real; f.unit_ok = lb.unit_ok; f.inj_count = lb.inj_count;
+    f.want_grad = want_grad != 0;
+    f.rates = lb.ens_rates;
+    // (a duration search asks for the rate sensitivities in every evaluation with gradients: dE/dtau needs its
+    // rate part)
+    f.sweep = lb.seeds.swp_B > 0; f.want_rate_sens = lb.swp_want_rates || lb.seeds.dur.set;
+    f.side_streams = (int)ctx->sweep_streams.size(); f.cu_count = ctx->cu_count; f.dbg_wave_mode = lb.dbg_wave_mode;
+    f.lindblad_4t = knob("lindblad_4t", 1); f.lindblad_two_sided = knob("lindblad_two_sided", 1);
+    f.lindblad_hermitian = knob("lindblad_hermitian", 1); f.lindblad_q2 = knob("lindblad_q2", 1);
+    f.lindblad_chain = knob("lindblad_chain", 1); f.lindblad_real_ops = knob("lindblad_real_ops", 1);
+    f.lindblad_pad_operator = knob("lindblad_pad_operator", 1);
+    f.lindblad_side_limit = knob("lindblad_side_limit", ctx->cu_count / 2);
+    f.lindblad_stamps = knob("lindblad_stamps", 0);
+    f.single_wave = qocx::diag_getenv("QOCX_LINDBLAD_SINGLE_WAVE") != nullptr;
+    return f;
+}
+
 // The launch form of the problem: where its densities live, and how many waves work on a seed
+// (lb holds the sizes of `p` already, its tables not yet: those facts come from the description)
 void choose_launch_form(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     auto& lb = ctx->lb;
-    const int n = p->hilbert_size, S = p->density_count, K = p->control_count, L = p->operator_count;
-    // densities, cotangents and stage derivatives live in LDS when they fit (n <= 16), else in per-seed HBM scratch
-    lb.global_scratch = (n > 16 || qocx::lindblad_lds_size(n, S, L, 0, K) > 160 * 1024) ? 1 : 0;
-    // several waves per seed (generator terms | one per operator | control cotangents) whenever
-    // that layout fits LDS: the recursion in time is serial, this shortens every stage
-    // (ONE operator - the T1 problem - runs the several-wave launches as two, the second one zero: the
-    // four-wave stage loops of section 14 exist for L = 2 only and are 1.5 times faster than the three-wave
-    // form of L = 1 although they multiply by that zero: 17.2 -> 11.5 ms on configs[3]'s sizes)
-    lb.pad_op = (L == 1 && n <= 16 && p->op_stages == nullptr && ctx->knob("lindblad_pad_operator", 1) != 0) ? 1 : 0;
-    const int Lmw = lb.pad_op ? 2 : L;
-    lb.multi_wave = (!lb.global_scratch && L > 0 && L <= 4 &&
-                     qocx::lindblad_lds_size(n, S, Lmw, 2, K) <= 160 * 1024 &&
-                     !qocx::diag_getenv("QOCX_LINDBLAD_SINGLE_WAVE")) ? 1 : 0;
-    lb.cache_gen = (lb.multi_wave && p->fixed_subdivision <= 0 &&
-                    qocx::lindblad_lds_size(n, S, Lmw, 3, K) <= 160 * 1024) ? 1 : 0;
+    qocx::LindbladFacts f = lindblad_facts(ctx, 0);
+    f.stage_tables = p->fixed_subdivision > 0;
+    f.g_tables = p->g_stages != nullptr; f.op_tables = p->op_stages != nullptr;
+    lb.form = qocx::lindblad_form(
+        f, [&](int mode, int nops) { return qocx::lindblad_lds_size(lb.n, lb.S, nops, mode, lb.K); });
 }
 
 // The control-free part (host copies, norm bounds) and the images of G_k; `decay`: sum gamma_i L_i^H L_i
@@ -337,7 +357,7 @@ int upload_static_part(qocx_ctx* ctx, const qocx_lindblad_problem* p, cmat& deca
         gammas[i] = p->dissipators[i];
         op_norms[i] = two_norm(ops[i].data(), n);
     }
-    if (lb.pad_op) {
+    if (lb.form.pad_op) {
         ops.push_back(cm_zero(n));
         gammas.push_back(0.0);
     }
@@ -496,9 +516,9 @@ int qocx_set_lindblad_problem(qocx_ctx* ctx, const qocx_lindblad_problem* p) {
     auto& lb = ctx->lb;
     lb.has_problem = false;
     lb.control_costs.clear();
-    choose_launch_form(ctx, p);
     lb.n = p->hilbert_size; lb.S = p->density_count; lb.K = p->control_count; lb.nc = p->control_eval_count;
     lb.N = p->system_eval_count; lb.nsteps = lb.N - 1; lb.ces = p->cost_eval_step; lb.nops = p->operator_count;
+    choose_launch_form(ctx, p);
     lb.T = p->evolution_time; lb.dt = p->evolution_time / lb.nsteps;
     lb.pwc = ctx->interp_policy == QOCX_INTERP_PIECEWISE_CONSTANT;
     lb.fixed_ksub = 0;
@@ -853,53 +873,19 @@ int lindblad_subdivisions(qocx_ctx* ctx, int B, const double* umax, std::vector<
     return 0;
 }
 
-// One piece of an evaluation - one launch, or the three of a two-sided piece: `count` seeds of the group
-// with sub-division count `ksub`, from position `first` of the launch order (lb.order).
-struct LindbladPiece {
-    int ksub = 0, first = 0, count = 0;
-    // the forward pass keeps its stage values for the adjoint (else: recomputed); several waves per seed
-    bool keep_stages = false, multi_wave = false;
-};
-
-// What decides the schedule: the stage budget (double2 elements), the record's debug knobs, the launch form
-struct PieceRule {
-    bool want_grad = false, multi_wave = false;
-    size_t stage_budget = 0;
-    int64_t dbg_stage_seeds = 0;
-    int dbg_min_piece = 256, dbg_wave_mode = 0, cu_count = 1;
-};
-
-// THE schedule (plain C++ over integers), for one group of `Bg` seeds from position `first`, `per_seed` stage
-// elements each; its pieces are appended in launch order. The stage values of the forward pass are kept for
-// the adjoint (12 x the checkpoints of the seeds in flight); a group that does not fit goes in pieces that do,
-// and only if a piece would fall below dbg_min_piece seeds does the adjoint recompute them instead (one piece,
-// as without gradients). Several waves per seed whenever the kernel is built for the problem; batches beyond
-// the CU count then go in rounds of one seed per CU. (Round 1 switched to one wave per seed, two seeds per CU,
-// beyond 256 seeds; on configs[3] at 300 / 512 / 768 / 1024 seeds: 73.7 / 80.7 / 126.6 / 123.7 ms against 74.4 /
-// 76.6 / 82.7 / 104.8 ms in rounds.) Returns the seeds the stage buffers are sized for: the kept piece BEFORE
-// the round cap (0: none kept), which over-provisions a capped group: the footprint of old.
-size_t lindblad_group_pieces(const PieceRule& r, int ksub, int first, int Bg, size_t per_seed,
-                             std::vector<LindbladPiece>& out) {
-    int piece = Bg;
-    bool keep = false;
-    if (r.want_grad) {
-        const size_t fit = r.dbg_stage_seeds > 0 ? (size_t)r.dbg_stage_seeds
-                                                 : std::max<size_t>(1, r.stage_budget / per_seed);
-        if (fit >= (size_t)Bg) { keep = true; }
-        else if (fit >= (size_t)r.dbg_min_piece) { keep = true; piece = (int)fit; }
-    }
-    const size_t sized_for = keep ? (size_t)piece : 0;
-    const bool multi = r.multi_wave && r.dbg_wave_mode != 1;
-    if (multi && r.dbg_wave_mode != 2) piece = std::min(piece, r.cu_count);
-    for (int p0 = 0; p0 < Bg; p0 += piece) out.push_back({ksub, first + p0, std::min(piece, Bg - p0), keep, multi});
-    return sized_for;
-}
-
 // What an evaluation of these sub-division counts launches: seeds with equal counts go together (`lb.order`
 // lists the seeds group by group) in the pieces of the schedule above; the grid tables and buffers for them.
 struct LindbladPlan {
-    std::vector<LindbladPiece> pieces;  // launch order
-    bool two_sided_ok = false, two_sided_tiles = false;
+    std::vector<qocx::LindbladPiece> pieces;  // launch order
+    qocx::LindbladRoute route;                // the kernels of every launch, two-sided or not (qocx_lindblad_route.h)
+    // a piece runs two-sided where the route does and the piece keeps its stage values
+    bool two_sided(const qocx::LindbladPiece& pc) const { return route.two_sided && pc.keep_stages; }
+    // rate sensitivities come out of the two-sided launches: one piece that recomputes its stages leaves the
+    // evaluation without them
+    bool rate_sens() const {
+        return route.rate_sens &&
+               std::all_of(pieces.begin(), pieces.end(), [](const qocx::LindbladPiece& pc) { return pc.keep_stages; });
+    }
 };
 
 int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of, LindbladPlan& plan) {
@@ -921,39 +907,31 @@ int lindblad_plan(qocx_ctx* ctx, int want_grad, const std::vector<int>& ksub_of,
         lb.last_subintervals += (int64_t)seed_subs;
         for (int b : kv.second) lb.order.push_back(b);
     }
-    // Two-sided evaluation (LindbladArgs::phase): where it applies the adjoint's stage cotangents
-    // need a buffer like the forward's stage values, and gsub holds complex numbers
-    // (n > 16: the tile-per-wave kernel of qocx_lindblad4t.hip in its phases, constant tables only)
-    const bool two_sided_small = n <= 16 && lb.nops >= 1 && lb.multi_wave && !lb.global_scratch &&
-                                 lb.dbg_wave_mode != 1;
-    // (n > 32: never - the kernel of qocx_lindblad16t.hip knows the classic launch only)
-    const bool two_sided_tiles = plan.two_sided_tiles = n > 16 && n <= 32 && ctx->knob("lindblad_4t", 1) != 0 &&
-                                                        lb.nops <= 4;
-    const bool two_sided_ok = plan.two_sided_ok = want_grad && lb.unit_ok && lb.inj_count == 0 &&
-                              (two_sided_small || two_sided_tiles) && lb.fixed_ksub == 0 &&
-                              (int)ctx->sweep_streams.size() >= 1 && ctx->knob("lindblad_two_sided", 1) != 0;
-    if (two_sided_ok && lb.lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
-    PieceRule rule{want_grad != 0, lb.multi_wave != 0, 0, lb.dbg_stage_seeds, lb.dbg_min_piece, lb.dbg_wave_mode,
-                   ctx->cu_count};
+    const qocx::LindbladRoute& route = plan.route = qocx::lindblad_route(lb.form, lindblad_facts(ctx, want_grad));
+    // Two-sided evaluation (LindbladArgs::phase): the adjoint's stage cotangents need a buffer like the
+    // forward's stage values, and gsub holds complex numbers
+    if (route.two_sided && lb.lam_scale.ensure((size_t)B * S)) return QOCX_ERR_HIP;
+    qocx::PieceRule rule{want_grad != 0, lb.form.multi_wave != 0, 0, lb.dbg_stage_seeds, lb.dbg_min_piece,
+                         lb.dbg_wave_mode, ctx->cu_count};
     if (want_grad) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         rule.stage_budget =
             (size_t)(0.45 * (double)(free_b + (lb.ystages.count + lb.kbstages.count) * sizeof(double2))) / sizeof(double2);
-        if (two_sided_ok) rule.stage_budget /= 2;  // kbar_i beside Y_i
+        if (route.two_sided) rule.stage_budget /= 2;  // kbar_i beside Y_i
     }
     size_t stage_elems = 0;  // of the largest kept piece, before its round cap (lindblad_group_pieces)
     int first = 0;
     for (auto& kv : groups) {
         const int Bg = (int)kv.second.size();
         const size_t per_seed = (size_t)lb.grids[kv.first].nsub * S * md * 12;
-        stage_elems = std::max(stage_elems, per_seed * lindblad_group_pieces(rule, kv.first, first, Bg, per_seed,
+        stage_elems = std::max(stage_elems, per_seed * qocx::lindblad_group_pieces(rule, kv.first, first, Bg, per_seed,
                                                                             plan.pieces));
         first += Bg;
     }
-    if (stage_elems > 0 && (lb.ystages.ensure(stage_elems) || (two_sided_ok && lb.kbstages.ensure(stage_elems))))
+    if (stage_elems > 0 && (lb.ystages.ensure(stage_elems) || (route.two_sided && lb.kbstages.ensure(stage_elems))))
         return QOCX_ERR_HIP;
-    if (lb.global_scratch && lb.scratch.ensure((size_t)B * qocx::lindblad_scratch_elems(n, S))) return QOCX_ERR_HIP;
+    if (lb.form.scratch && lb.scratch.ensure((size_t)B * qocx::lindblad_scratch_elems(n, S))) return QOCX_ERR_HIP;
     const size_t csz = (size_t)nc * K;
     if (lb.controls.ensure((size_t)B * std::max<size_t>(csz, 1)) || lb.cost_out.ensure(B) ||
         lb.grads.ensure((size_t)B * std::max<size_t>(csz, 1)) || lb.gsub.ensure(gsub_total) ||
@@ -982,17 +960,15 @@ int upload_density_cotangents(qocx_ctx* ctx) {
     return (lb.inj_index.upload(index, ctx->stream) || lb.inj_bars.upload(dumps, ctx->stream)) ? QOCX_ERR_HIP : 0;
 }
 
-// The launches of one evaluation: what is the same for every piece, read once (the knobs are map lookups by
-// name), and the running offsets of the pieces into the evaluation's buffers
+// The launches of one evaluation: the running offsets of the pieces into the evaluation's buffers
 struct LindbladLaunch {
-    int want_grad = 0, tile4 = 0, hermitian = 0, q2 = 0, chain = 0, ops_real = 0, side_limit = 0;
-    bool two_sided = false, stamps = false;
     qocx::LindbladMembers mem;  // per-member rates (lb.ens_rates): the strides; item_member is the piece's
     size_t ckpt_off = 0, gsub_off = 0, rate_off = 0;
 };
 
 // The arguments of the classic launch of piece `pc`; the two-sided launches add theirs (launch_two_sided)
-qocx::LindbladArgs lindblad_piece_args(qocx_ctx* ctx, const LindbladLaunch& ev, const LindbladPiece& pc) {
+qocx::LindbladArgs lindblad_piece_args(qocx_ctx* ctx, const qocx::LindbladRoute& route, int want_grad,
+                                       const LindbladLaunch& ev, const qocx::LindbladPiece& pc) {
     auto& lb = ctx->lb;
     const int S = lb.S, nsteps = lb.nsteps;
     const size_t md = dump_elems(lb.n), csz = (size_t)lb.nc * lb.K, pos0 = pc.first;
@@ -1012,48 +988,55 @@ qocx::LindbladArgs lindblad_piece_args(qocx_ctx* ctx, const LindbladLaunch& ev, 
     la.op_tab = (lb.fixed_ksub > 0 && lb.op_tab.p) ? lb.op_tab.p : nullptr;
     la.gamma_tab = la.op_tab ? lb.gamma_tab.p : nullptr;
     la.n = lb.n; la.S = S; la.K = lb.K; la.nc = lb.nc; la.nsub = gr.nsub; la.nsteps = nsteps;
-    la.nops = (pc.multi_wave && lb.pad_op) ? 2 : lb.nops;
-    la.cost_eval_step = lb.ces; la.want_grad = ev.want_grad; la.has_step_costs = lb.has_step_costs; la.cost_count = lb.cost_count;
+    la.nops = (pc.multi_wave && lb.form.pad_op) ? 2 : lb.nops;
+    la.cost_eval_step = lb.ces; la.want_grad = want_grad; la.has_step_costs = lb.has_step_costs; la.cost_count = lb.cost_count;
     la.costs = lb.costs.p; la.cost_matrices = lb.cost_matrices.p; la.cost_counts = lb.cost_counts.p;
     la.checkpoints = lb.checkpoints.p + ev.ckpt_off; la.gsub = lb.gsub.p + ev.gsub_off;
     la.ystages = pc.keep_stages ? lb.ystages.p : nullptr;     // reused piece after piece
-    la.scratch = lb.global_scratch ? lb.scratch.p : nullptr;  // likewise
+    la.scratch = lb.form.scratch ? lb.scratch.p : nullptr;    // likewise
     // several waves per seed shorten a seed's serial chain by ~1.4x but hold one seed
     // per CU instead of two: worth it while the batch leaves CUs idle
     la.multi_wave = pc.multi_wave ? 1 : 0;
-    la.cache_gen = (la.multi_wave && lb.cache_gen) ? 1 : 0;
+    la.cache_gen = (la.multi_wave && lb.form.cache_gen) ? 1 : 0;
     la.cost_out = lb.cost_out.p + pos0; la.final_out = lb.final_out.p + pos0 * S * md;
     la.step_densities = ctx->keep_step_states ? lb.step_densities.p + pos0 * (nsteps + 1) * S * md : nullptr;
-    la.tile4 = ev.tile4; la.hermitian = ev.hermitian;
+    la.tile4 = route.tile4; la.hermitian = route.hermitian;
     // ([B] sets of the forward pass / classic launch, then [B] of the unit adjoint)
-    la.stamps = ev.stamps ? ctx->stamps.p + pos0 * 48 : nullptr;
+    la.stamps = route.stamps ? ctx->stamps.p + pos0 * 48 : nullptr;
     la.inj_count = lb.inj_count;
     la.inj_index = lb.inj_count > 0 ? lb.inj_index.p : nullptr;
     la.inj_bars = lb.inj_count > 0 ? lb.inj_bars.p + pos0 * lb.inj_count * S * md : nullptr;
     return la;
 }
 
+// One launch of piece `pc`, on the kernel the route names for the phase of `args`
 // (per-member rates: kernels of their own, qocx_lindblad_rates.hip / qocx_lindblad4t_rates.hip, whose workgroup i
 // reads the tables of member item_member[i]: behind the order, in launch order)
-void launch_lindblad_piece(qocx_ctx* ctx, const LindbladLaunch& ev, const qocx::LindbladArgs& args,
-                           const LindbladPiece& pc, hipStream_t st) {
+int launch_lindblad_piece(qocx_ctx* ctx, const qocx::LindbladRoute& route, const LindbladLaunch& ev,
+                          const qocx::LindbladArgs& args, const qocx::LindbladPiece& pc, hipStream_t st) {
     auto& lb = ctx->lb;
+    const qocx::LindbladKernel kernel = route.kernel[args.phase];
+    int none = 0;
     time_begin(ctx, 5, st);
     if (lb.ens_rates) {
         qocx::LindbladMembers mem = ev.mem;
         mem.item_member = lb.order_dev.p + lb.order.size() + pc.first;
-        qocx::launch_lindblad_rates(args, mem, pc.count, st);
-    } else qocx::launch_lindblad(args, pc.count, st);
+        none = qocx::launch_lindblad_rates(kernel, route.stamped, args, mem, pc.count, st);
+    } else none = qocx::launch_lindblad(kernel, route.stamped, args, pc.count, st);
     time_end(ctx, st);
+    // (every such problem was refused by name when it was set)
+    return none ? fail(QOCX_ERR_STATE, "no Lindblad kernel for this problem at hilbert_size > 32") : 0;
 }
 
 // Two-sided: forward pass and unit adjoint as two launches, then the combine kernel on the whole chip.
 // While both launches find CUs of their own they run on two streams (2 Bp CUs busy instead of Bp); a
 // bigger piece runs them one after the other - the same three kernels, so a seed's result does not depend
 // on the batch it is part of. Then, for a sweep that asked, the rate sensitivities of the piece.
-int launch_two_sided(qocx_ctx* ctx, const LindbladLaunch& ev, qocx::LindbladArgs la, const LindbladPiece& pc) {
+int launch_two_sided(qocx_ctx* ctx, const LindbladPlan& plan, const LindbladLaunch& ev, qocx::LindbladArgs la,
+                     const qocx::LindbladPiece& pc) {
     auto& lb = ctx->lb;
-    hipStream_t side = pc.count <= ev.side_limit ? ctx->sweep_streams[0] : ctx->stream;
+    const qocx::LindbladRoute& route = plan.route;
+    hipStream_t side = pc.count <= route.side_limit ? ctx->sweep_streams[0] : ctx->stream;
     la.kbstages = lb.kbstages.p;
     la.lam_scale = lb.lam_scale.p + (size_t)pc.first * lb.S;
     // everything enqueued so far (uploads, earlier pieces that reuse the stage buffers)
@@ -1063,10 +1046,10 @@ int launch_two_sided(qocx_ctx* ctx, const LindbladLaunch& ev, qocx::LindbladArgs
     }
     qocx::LindbladArgs fwd = la, adj = la;
     fwd.phase = 1; adj.phase = 2;
-    fwd.q2 = adj.q2 = ev.q2; fwd.chain = adj.chain = ev.chain; fwd.ops_real = adj.ops_real = ev.ops_real;
+    fwd.q2 = adj.q2 = route.q2; fwd.chain = adj.chain = route.chain; fwd.ops_real = adj.ops_real = route.ops_real;
     if (la.stamps != nullptr) adj.stamps = la.stamps + lb.order.size() * 48;
-    launch_lindblad_piece(ctx, ev, fwd, pc, ctx->stream);
-    launch_lindblad_piece(ctx, ev, adj, pc, side);
+    if (int rc = launch_lindblad_piece(ctx, route, ev, fwd, pc, ctx->stream)) return rc;
+    if (int rc = launch_lindblad_piece(ctx, route, ev, adj, pc, side)) return rc;
     if (side != ctx->stream) {
         HIP_TRY(hipEventRecord(ctx->ev_swept[0], side));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_swept[0], 0));
@@ -1094,47 +1077,23 @@ int lindblad_launch_groups(qocx_ctx* ctx, int want_grad, const LindbladPlan& pla
     const size_t md = dump_elems(n), csz = (size_t)nc * K;
     if (int rc = lb.inj_count > 0 ? upload_density_cotangents(ctx) : 0) return rc;
     // Rate sensitivities of a sweep (qocx_lindblad_sweep_want_rate_sensitivities): a launch of
-    // qocx_lindblad_ratesens.hip behind every piece's combine launch; a piece that does not run two-sided
-    // (or a problem with more than four operators) leaves the evaluation without them.
-    // (a duration search asks for them in every evaluation with gradients: dE/dtau needs its rate part)
-    const bool want_rates = lb.seeds.swp_B > 0 && (lb.swp_want_rates || lb.seeds.dur.set) && want_grad;
-    lb.swp_rates_ok = want_rates && lb.nops >= 1 && lb.nops <= 4;
+    // qocx_lindblad_ratesens.hip behind every piece's combine launch
+    lb.swp_rates_ok = plan.rate_sens();
     if (lb.swp_rates_ok && (lb.swp_rate_partials.ensure((size_t)lb.last_subintervals * lb.nops) ||
                             lb.swp_rate_sens.ensure((size_t)B * lb.nops)))
         return QOCX_ERR_HIP;
     LindbladLaunch ev;
-    ev.want_grad = want_grad;
-    ev.tile4 = ctx->knob("lindblad_4t", 1) != 0 ? 1 : 0;
-    ev.hermitian = (lb.hermitian && lb.inj_count == 0 && ctx->knob("lindblad_hermitian", 1) != 0) ? 1 : 0;
-    ev.q2 = ctx->knob("lindblad_q2", 1) != 0 ? 1 : 0; ev.chain = ctx->knob("lindblad_chain", 1) != 0 ? 1 : 0;
-    ev.ops_real = (lb.ops_real && ctx->knob("lindblad_real_ops", 1) != 0) ? 1 : 0;
-    ev.side_limit = (int)ctx->knob("lindblad_side_limit", ctx->cu_count / 2);
-    ev.stamps = ctx->knob("lindblad_stamps", 0) != 0;
     ev.mem.a0_stride = 4 * md; ev.mem.gamma_stride = lb.gammas_h.size();
-    if (ev.stamps) {  // the whole buffer once: a piece's launches stamp only their own seeds' sets
+    if (plan.route.stamps) {  // the whole buffer once: a piece's launches stamp only their own seeds' sets
         if (ctx->stamps.ensure((size_t)B * 96)) return QOCX_ERR_HIP;
         HIP_TRY(hipMemsetAsync(ctx->stamps.p, 0, (size_t)B * 96 * sizeof(unsigned long long), ctx->stream));
     }
-    ev.two_sided = plan.two_sided_ok;
-    if (ev.two_sided && n > 16 && !plan.pieces.empty()) {
-        // above one tile only the tile-per-wave kernel knows the phases: ask IT whether it takes these
-        // launches (the one-wave form would run the whole evaluation twice). Its answer reads nothing that
-        // differs between the pieces that ask - those that keep their stage values, in the one buffer.
-        qocx::LindbladArgs probe = lindblad_piece_args(ctx, ev, plan.pieces[0]);
-        probe.phase = 1; probe.ystages = lb.ystages.p;
-        ev.two_sided = qocx::lindblad4t_supports(probe);
-    }
-    for (const LindbladPiece& pc : plan.pieces) {
+    for (const qocx::LindbladPiece& pc : plan.pieces) {
         const auto& gr = lb.grids[pc.ksub];
-        const qocx::LindbladArgs la = lindblad_piece_args(ctx, ev, pc);
-        if (n > 32 && !qocx::lindblad16t_supports(la))  // (every such problem was refused by name when it was set)
-            return fail(QOCX_ERR_STATE, "no Lindblad kernel for this problem at hilbert_size > 32");
-        if (ev.two_sided && pc.keep_stages && (pc.multi_wave || plan.two_sided_tiles)) {
-            if (int rc = launch_two_sided(ctx, ev, la, pc)) return rc;
-        } else {
-            lb.swp_rates_ok = false;
-            launch_lindblad_piece(ctx, ev, la, pc, ctx->stream);
-        }
+        const qocx::LindbladArgs la = lindblad_piece_args(ctx, plan.route, want_grad, ev, pc);
+        if (int rc = plan.two_sided(pc) ? launch_two_sided(ctx, plan, ev, la, pc)
+                                        : launch_lindblad_piece(ctx, plan.route, ev, la, pc, ctx->stream))
+            return rc;
         if (want_grad) {
             qocx::ScatterArgs sc;
             sc.gstep = la.gsub; sc.row_ptr = gr.row_ptr.p; sc.col_step = gr.col.p;

@@ -694,18 +694,22 @@ void launch_scatter_seeds(const double* cost, double* cost_out, const double* gr
                           size_t grad_per_seed, const double2* final_states, double2* final_out,
                           size_t final_per_seed, const int* order, int batch, hipStream_t st);
 
-void launch_lindblad(const LindbladArgs& a, int batch, hipStream_t st);
+// The kernel of a launch is the host's to name (qocx_lindblad_route.h: lindblad_route); the launchers decide
+// nothing. `stamped`: the four-wave kernels in their stamped builds (diagnostic library only). Nonzero: the
+// launcher has no such kernel, and nothing was launched.
+enum class LindbladKernel : int;
+int launch_lindblad(LindbladKernel kernel, bool stamped, const LindbladArgs& a, int batch, hipStream_t st);
 void launch_lindblad_combine(const LindbladArgs& a, int batch, hipStream_t st);
-bool lindblad4t_supports(const LindbladArgs& a);
-void launch_lindblad4t(const LindbladArgs& a, int batch, hipStream_t st);
+void launch_lindblad4t(bool hermitian, const LindbladArgs& a, int batch, hipStream_t st);
 void launch_lindblad4t_combine(const LindbladArgs& a, int batch, hipStream_t st);
-void launch_lindblad_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st);
-void launch_lindblad4t_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st);
+int launch_lindblad_rates(LindbladKernel kernel, bool stamped, const LindbladArgs& a, const LindbladMembers& mem,
+                          int batch, hipStream_t st);
+void launch_lindblad4t_rates(bool hermitian, const LindbladArgs& a, const LindbladMembers& mem, int batch,
+                             hipStream_t st);
 void launch_lindblad_ratesens(const LindbladArgs& a, const RateSensArgs& r, int batch, hipStream_t st);
 int lindblad_lds_size(int n, int S, int nops, int mode, int K);
 size_t lindblad_scratch_elems(int n, int S);
 // 33 <= n <= 64 (qocx_lindblad16t.hip; the host accepts such problems under the knob lindblad_wide)
-bool lindblad16t_supports(const LindbladArgs& a);
 void launch_lindblad16t(const LindbladArgs& a, int batch, hipStream_t st);
 int lindblad16t_lds_bytes();
 size_t lindblad16t_scratch_elems(int S);

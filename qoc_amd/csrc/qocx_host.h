@@ -19,6 +19,7 @@
 #include "../../include/qocx.h"
 #include "qocx_device.h"
 #include "qocx_diag.h"
+#include "qocx_lindblad_route.h"
 
 namespace qocx::host {
 
@@ -367,8 +368,7 @@ struct qocx_ctx {
         bool hermitian = false;               // H0, G_k, sum gamma L^H L, initial densities and cost matrices
                                               // are Hermitian: so is every density and every cotangent
         bool ops_real = false;                // every Lindblad operator has a zero imaginary part
-        int global_scratch = 0, multi_wave = 0, cache_gen = 0;
-        int pad_op = 0;  // L = 1: a zero second operator behind the real one, for the four-wave launches
+        qocx::LindbladForm form;         // where the densities live, how many waves work on a seed (set time)
         int fixed_ksub = 0;              // > 0: time-dependent Hamiltonian sampled for this grid
         // qocx_debug_lindblad_knobs (tests force the kernel variants large batches / little HBM use)
         int64_t last_subintervals = 0;   // sum over the seeds of the last evaluation

@@ -130,10 +130,14 @@ void launch_lindblad_combine(const LindbladArgs& a, int batch, hipStream_t st) {
     hipLaunchKernelGGL(lindblad_combine_kernel, dim3(a.nsub, batch), dim3(64), 0, st, a);
 }
 
-void launch_lindblad(const LindbladArgs& a, int batch, hipStream_t st) {
-    if (a.n > 32) launch_lindblad16t(a, batch, st);  // (lindblad_launch_groups has asked lindblad16t_supports)
-    else if (lindblad4t_supports(a)) launch_lindblad4t(a, batch, st);
-    else lindblad_dispatch(a, Launch{a, batch, st});
+int launch_lindblad(LindbladKernel kernel, bool stamped, const LindbladArgs& a, int batch, hipStream_t st) {
+    switch (kernel) {
+    case LindbladKernel::NONE: return 1;
+    case LindbladKernel::TILE16: launch_lindblad16t(a, batch, st); return 0;
+    case LindbladKernel::TILE4:
+    case LindbladKernel::TILE4_HERM: launch_lindblad4t(kernel == LindbladKernel::TILE4_HERM, a, batch, st); return 0;
+    default: return lindblad_dispatch(kernel, stamped, a, Launch{a, batch, st}) ? 0 : 1;
+    }
 }
 
 // LDS bytes of one seed. mode 0: one wave, everything in LDS; 1: one wave, stage derivatives /

@@ -220,12 +220,6 @@ __global__ __launch_bounds__(1024) void lindblad16t_kernel(LindbladArgs a) {
 
 }  // namespace lindblad16t
 
-bool lindblad16t_supports(const LindbladArgs& a) {
-    return a.n > 32 && a.n <= 64 && a.phase == 0 && a.a0_tab == nullptr && a.gp_tab == nullptr &&
-           a.op_tab == nullptr && a.nops <= lindblad16t::MAX_OPS && a.scratch != nullptr &&
-           a.K <= QOCX_LINDBLAD_MAX_K;
-}
-
 int lindblad16t_lds_bytes() { return lindblad16t::LDS_BYTES; }
 
 size_t lindblad16t_scratch_elems(int S) { return (size_t)(2 * S + lindblad16t::SCRATCH_EXTRA) * lindblad16t::MAT; }

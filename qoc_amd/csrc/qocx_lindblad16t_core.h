@@ -27,7 +27,7 @@ typedef Dim<G> D;
 
 constexpr int STAGES = QOCX_RK_STAGES;
 constexpr int MAT = D::IMAT;  // complex elements of a C-dump
-constexpr int MAX_OPS = 8;    // the operators are read from memory: the engine's limit
+constexpr int MAX_OPS = LINDBLAD_TILE16_MAX_OPS;  // the operators are read from memory: the engine's limit
 
 // LDS matrices (pitch 65): the argument of the right-hand side, and one temporary - t_i = gamma_i L_i Y of
 // the operator at hand, then the stage value of the control-cotangent products. Behind them the partial

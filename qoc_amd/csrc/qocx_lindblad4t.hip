@@ -97,12 +97,6 @@ __global__ __launch_bounds__(256) void lindblad4t_combine_kernel(LindbladArgs a)
 
 }  // namespace lindblad4t
 
-bool lindblad4t_supports(const LindbladArgs& a) {
-    return a.tile4 && a.n > 16 && a.n <= 32 && (a.phase == 0 || a.ystages != nullptr) &&
-           (!a.hermitian || (a.a0_tab == nullptr && a.inj_index == nullptr)) && a.nops <= lindblad4t::MAX_OPS &&
-           a.scratch != nullptr && a.K <= QOCX_LINDBLAD_MAX_K;
-}
-
 void launch_lindblad4t_combine(const LindbladArgs& a, int batch, hipStream_t st) {
     if (a.hermitian)
         hipLaunchKernelGGL(lindblad4t::lindblad4t_combine_kernel<true>, dim3(a.nsub, batch), dim3(256), 0, st, a);
@@ -110,7 +104,7 @@ void launch_lindblad4t_combine(const LindbladArgs& a, int batch, hipStream_t st)
         hipLaunchKernelGGL(lindblad4t::lindblad4t_combine_kernel<false>, dim3(a.nsub, batch), dim3(256), 0, st, a);
 }
 
-void launch_lindblad4t(const LindbladArgs& a, int batch, hipStream_t st) {
+void launch_lindblad4t(bool hermitian, const LindbladArgs& a, int batch, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lindblad4t::lindblad4t_kernel<false>),
@@ -119,7 +113,7 @@ void launch_lindblad4t(const LindbladArgs& a, int batch, hipStream_t st) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lindblad4t::LDS_BYTES);
         attr_set = true;
     }
-    if (a.hermitian)
+    if (hermitian)
         hipLaunchKernelGGL(lindblad4t::lindblad4t_kernel<true>, dim3(batch), dim3(256), lindblad4t::LDS_BYTES, st, a);
     else
         hipLaunchKernelGGL(lindblad4t::lindblad4t_kernel<false>, dim3(batch), dim3(256), lindblad4t::LDS_BYTES, st, a);

@@ -6,6 +6,7 @@
 #define QOCX_LINDBLAD4T_CORE_H
 
 #include "qocx_device.h"
+#include "qocx_lindblad_route.h"
 #include "qocx_tilewave.h"
 #include "dop853_tableau.h"
 
@@ -22,7 +23,7 @@ typedef Dim<G> D;
 
 constexpr int STAGES = QOCX_RK_STAGES;
 constexpr int MAT = D::IMAT;  // complex elements of a C-dump
-constexpr int MAX_OPS = 4;
+constexpr int MAX_OPS = LINDBLAD_TILE4_MAX_OPS;  // (the route sends no launch with more)
 
 // LDS matrices (pitch 33): the argument of the right-hand side, the two generators at the stage's
 // time (then t_0, t_1), the operators, the stage value of the control-cotangent products; behind them

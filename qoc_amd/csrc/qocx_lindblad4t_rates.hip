@@ -19,7 +19,8 @@ __global__ __launch_bounds__(256) void lindblad4t_rates_kernel(LindbladArgs a, L
 
 }  // namespace lindblad4t
 
-void launch_lindblad4t_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st) {
+void launch_lindblad4t_rates(bool hermitian, const LindbladArgs& a, const LindbladMembers& mem, int batch,
+                             hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lindblad4t::lindblad4t_rates_kernel<false>),
@@ -28,7 +29,7 @@ void launch_lindblad4t_rates(const LindbladArgs& a, const LindbladMembers& mem, 
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lindblad4t::LDS_BYTES);
         attr_set = true;
     }
-    if (a.hermitian)
+    if (hermitian)
         hipLaunchKernelGGL(lindblad4t::lindblad4t_rates_kernel<true>, dim3(batch), dim3(256), lindblad4t::LDS_BYTES, st,
                            a, mem);
     else

@@ -26,6 +26,7 @@
 
 #include <cstddef>
 #include "dop853_tableau.h"
+#include "qocx_lindblad_route.h"
 #include "qocx_wave.h"
 
 namespace qocx {
@@ -1992,27 +1993,35 @@ void launch_t(const LindbladArgs& a, const Go& go) {
     go.template operator()<LNB, GS, MW, MW4, STAMP, Q2, CH>(bytes, 64 * (CH ? I::chain_waves(a.nops) : I::waves(a.nops)));
 }
 
+static_assert(LINDBLAD_MAX_CONTROLS == QOCX_LINDBLAD_MAX_K, "the route admits what the kernels' arrays hold");
+
+// The one-tile engine's kernels by name (qocx_lindblad_route.h decides); false: `kernel` is none of them.
+// `stamped`: the stamped builds of the four-wave kernels (qocx_diag.h), which only the diagnostic library has.
 template <class Go>
-void lindblad_dispatch(const LindbladArgs& a, const Go& go) {
-    // the two-sided evaluation's stage loop: four waves, constant H0 / G_k, stage values kept
-    const bool q2 = a.q2 && a.phase != 0 && a.a0_tab == nullptr && a.gp_tab == nullptr && a.ystages != nullptr &&
-                    a.op_tab == nullptr && a.K <= 4;
-    if (a.n > 16) launch_t<2, true, false>(a, go);
-    else if (a.scratch != nullptr) launch_t<1, true, false>(a, go);
+bool lindblad_dispatch(LindbladKernel kernel, bool stamped, const LindbladArgs& a, const Go& go) {
 #ifdef QOCX_DIAG
-    else if (a.multi_wave && a.nops == 2 && a.stamps != nullptr && q2 && a.chain)
-        launch_t<1, false, true, true, true, true, true>(a, go);
-    else if (a.multi_wave && a.nops == 2 && a.stamps != nullptr && q2)
-        launch_t<1, false, true, true, true, true>(a, go);  // stamped builds (qocx_diag.h)
-    else if (a.multi_wave && a.nops == 2 && a.stamps != nullptr)
-        launch_t<1, false, true, true, true>(a, go);
+    constexpr bool STAMP = true;
+#else
+    constexpr bool STAMP = false;  // (both arms below are then the one unstamped instantiation)
 #endif
-    else if (a.multi_wave && a.nops >= 2 && a.nops <= 4 && q2 && a.chain)
-        launch_t<1, false, true, true, false, true, true>(a, go);
-    else if (a.multi_wave && a.nops == 2 && q2) launch_t<1, false, true, true, false, true>(a, go);
-    else if (a.multi_wave && a.nops == 2) launch_t<1, false, true, true>(a, go);
-    else if (a.multi_wave) launch_t<1, false, true>(a, go);
-    else launch_t<1, false, false>(a, go);
+    switch (kernel) {  // (in the order the translation units have always emitted the kernels)
+    case LindbladKernel::ONE_WAVE_32: launch_t<2, true, false>(a, go); return true;
+    case LindbladKernel::ONE_WAVE_SCRATCH: launch_t<1, true, false>(a, go); return true;
+    case LindbladKernel::FOUR_WAVES_CHAIN:
+        stamped ? launch_t<1, false, true, true, STAMP, true, true>(a, go)
+                : launch_t<1, false, true, true, false, true, true>(a, go);
+        return true;
+    case LindbladKernel::FOUR_WAVES_Q2:
+        stamped ? launch_t<1, false, true, true, STAMP, true>(a, go)
+                : launch_t<1, false, true, true, false, true>(a, go);
+        return true;
+    case LindbladKernel::FOUR_WAVES:
+        stamped ? launch_t<1, false, true, true, STAMP>(a, go) : launch_t<1, false, true, true>(a, go);
+        return true;
+    case LindbladKernel::WAVES_NOPS2: launch_t<1, false, true>(a, go); return true;
+    case LindbladKernel::ONE_WAVE_LDS: launch_t<1, false, false>(a, go); return true;
+    default: return false;
+    }
 }
 
 }  // namespace

@@ -37,9 +37,18 @@ struct LaunchRates {  // (lindblad_dispatch)
 
 }  // namespace
 
-void launch_lindblad_rates(const LindbladArgs& a, const LindbladMembers& mem, int batch, hipStream_t st) {
-    if (lindblad4t_supports(a)) launch_lindblad4t_rates(a, mem, batch, st);
-    else lindblad_dispatch(a, LaunchRates{a, mem, batch, st});
+// (33 <= n <= 64 has no kernel with a member table: the setters refuse rates there, and so does this)
+int launch_lindblad_rates(LindbladKernel kernel, bool stamped, const LindbladArgs& a, const LindbladMembers& mem,
+                          int batch, hipStream_t st) {
+    switch (kernel) {
+    case LindbladKernel::NONE:
+    case LindbladKernel::TILE16: return 1;
+    case LindbladKernel::TILE4:
+    case LindbladKernel::TILE4_HERM:
+        launch_lindblad4t_rates(kernel == LindbladKernel::TILE4_HERM, a, mem, batch, st);
+        return 0;
+    default: return lindblad_dispatch(kernel, stamped, a, LaunchRates{a, mem, batch, st}) ? 0 : 1;
+    }
 }
 
 }  // namespace qocx

@@ -128,6 +128,16 @@ class ActionFacts(ctypes.Structure):
                     "allow")])
 
 
+class LindbladFacts(ctypes.Structure):
+    """qocx_lindblad_facts of include/qocx.h: what qocx_debug_lindblad_route decides on."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        "n", "S", "K", "nops", "stage_tables", "g_tables", "op_tables", "hermitian", "ops_real", "unit_ok",
+        "inj_count", "want_grad", "rates", "sweep", "want_rate_sens", "side_streams", "cu_count",
+        "dbg_wave_mode", "lindblad_4t", "lindblad_two_sided", "lindblad_hermitian", "lindblad_q2",
+        "lindblad_chain", "lindblad_real_ops", "lindblad_pad_operator", "lindblad_side_limit",
+        "lindblad_stamps", "single_wave")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/qocx.h
 _VP = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -212,6 +222,11 @@ SIGNATURES = {
     "qocx_debug_spectral_bound": (ctypes.c_int, [_c_double_p, _I32, _c_double_p]),
     "qocx_debug_action_degree": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, _I32, _c_int_p]),
     "qocx_debug_action_route": (ctypes.c_int, [ctypes.POINTER(ActionFacts), _c_int_p, _c_int_p, _c_int_p]),
+    "qocx_debug_lindblad_route": (ctypes.c_int, [ctypes.POINTER(LindbladFacts), _c_int_p, _c_int_p, _c_int_p,
+                                                 _c_int_p, _c_int_p]),
+    "qocx_debug_lindblad_pieces": (ctypes.c_int, [_I32, _I32, _I64, _I64, _I32, _I32, _I32, _I32, _I64, _I32,
+                                                  _c_int_p, _c_int_p, _c_int_p, _c_int_p,
+                                                  ctypes.POINTER(_I64)]),
     "qocx_debug_mfma_peak": (ctypes.c_int, [_VP, _I32, _I32, _c_double_p]),
     "qocx_opt_begin": (ctypes.c_int, [_VP]),
     "qocx_opt_clip": (ctypes.c_int, [_VP, _c_double_p]),
